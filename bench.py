@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/sec of the MI355X rasteriser on the fixed e1m1 camera path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4,5}] [--width W --height H] [--batch 1000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3,4,5}] [--width W --height H] [--batch 1000] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
 
 Workload (config.workload): by default BASELINE config 3 — the 1 000-frame scripted camera path through the e1m1-like
@@ -395,6 +395,10 @@ def run(args, backend_factory=DoomGpuBackend):
     value = aggregate_fps(args.steps * frames_per_step, world, elapsed)
     fallbacks = ctx.fallbacks() if hasattr(ctx, "fallbacks") else None
 
+    # ---- what the last timed step computed, for output-for-output comparison of two builds (rank 0) -------------------
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, be, submitted[0], batches_per_step, np)
+
     # ---- CPU baseline + parity of the frames the timed steps left in HBM (rank 0, N = 1 only) -----------------------
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -521,6 +525,45 @@ def run(args, backend_factory=DoomGpuBackend):
     if dist is not None:
         dist.barrier()
     return line
+
+
+DUMP_SEED = 1993
+DUMP_FRAMES, DUMP_FRAME_BYTES = 4, 48 << 20       # whole frames of the sample: at most 4, at most 48 MiB as float32
+DUMP_PIXELS = 1024                                # pixel positions sampled in every frame of the step (12 MB at 1000 frames)
+
+
+def dump_outputs(out_dir, ctx, be, submitted, batches_per_step, np):
+    """--dump-outputs DIR: the RGB24 frames the last timed step left in HBM (what a caller of the path receives), as float32 .npy:
+      frames.npy       (k, H, W, 3)  k whole frames picked with a fixed seed (k <= 4, <= 48 MiB)
+      frame_index.npy  (k,)          their positions on the 1000-frame camera path (float64)
+      pixels.npy       (n, P, 3)     P = 1024 fixed, seeded pixel positions of each of the step's n frames, in path order
+    A frame's content depends on its path position alone, so the files do not depend on which slot the step used."""
+    W, H, B = be.args.width, be.args.height, be.args.batch
+    held = {}                                     # path position -> (slot, frame in slot), for the batches still in their slots
+    for g in range(submitted - min(batches_per_step, be.n_slots), submitted):
+        s = g % be.n_slots
+        for j in range(B):
+            held.setdefault((be.batch_first[s] + j) % PATH_FRAMES, (s, j))
+    order = sorted(held)
+    rng = np.random.default_rng(DUMP_SEED)
+    pos = np.sort(rng.choice(H * W, min(DUMP_PIXELS, H * W), replace=False))
+    k = min(DUMP_FRAMES, DUMP_FRAME_BYTES // (H * W * 3 * 4), len(order))
+    picked = sorted(rng.choice(len(order), k, replace=False).tolist())
+    pixels = np.empty((len(order), len(pos), 3), dtype=np.float32)
+    frames = np.empty((k, H, W, 3), dtype=np.float32)
+    for s in sorted({s for s, _ in held.values()}):
+        ctx.wait(s)
+    for r, i in enumerate(order):
+        s, j = held[i]
+        f = ctx.readback(s, j, 1)[0]
+        pixels[r] = f.reshape(H * W, 3)[pos]
+        if r in picked:
+            frames[picked.index(r)] = f
+    out = {"frames": frames, "frame_index": np.array([order[r] for r in picked], dtype=np.float64), "pixels": pixels}
+    assert sum(a.nbytes for a in out.values()) <= 64 * 10**6
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(args, be, ctx, n_slots, np):
@@ -791,11 +834,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-latency", action="store_true", help="skip the one-view-per-call latency leg (`latency` in the JSON line)")
     ap.add_argument("--no-side-legs", action="store_true", help="skip the short legs of configs 2 and 5 and of config 3 with two host threads (`side_legs` in the JSON line)")
     ap.add_argument("--latency", action="store_true", help="(default) measure the one-view-per-call latency leg at 1024x768 and the bench size")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                                                                          "(float32 frames and a seeded pixel sample; see dump_outputs)")
     a = ap.parse_args(argv)
     _, cw, ch, cb, _, _ = CONFIGS[a.config]
     a.width = a.width or cw
     a.height = a.height or ch
     a.batch = a.batch or cb
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.batch <= 0 or PATH_FRAMES % a.batch:
         ap.error(f"--batch must divide the {PATH_FRAMES}-frame path (a step is one pass over the whole path)")
     return a

@@ -68,11 +68,21 @@ class _StubBackend:
         return self.ctx
 
 
+def _hide_gpus(torch, monkeypatch=None):
+    """The stub runs are CPU tests: bench.run must see no GPU wherever they run (with one visible GPU, pick_device gives every rank
+    ordinal 0, and bench.run would open the device)."""
+    set_ = monkeypatch.setattr if monkeypatch else setattr
+    set_(torch.cuda, "device_count", lambda: 0)
+    set_(torch.cuda, "is_available", lambda: False)
+
+
 def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
                       LOCAL_WORLD_SIZE=str(world))
+    import torch
     import torch.distributed as dist
     import bench
+    _hide_gpus(torch)
     dist.init_process_group(backend="gloo", rank=rank, world_size=world)
     dist.barrier()
     slow = bench.dist_max(0.5 + rank, dist)            # rank 1 is the slow one
@@ -327,3 +337,96 @@ def test_synth_map_runs_are_labelled_as_not_a_baseline_configuration(monkeypatch
     assert holder["be"].ctx.submits == (line["gpu_clock_warmup"]["steps"] + 1 + 2) * 1          # one 1 000-frame batch per step: clock warm-up + W + K
     plain = bench.run(bench.parse_args(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-resident", "--no-host-frames", "--no-latency"]), factory)
     assert plain["config"]["workload"].startswith("BASELINE config 3")
+
+
+def _stub_frame(i, W, H):
+    """The RGB24 frame a stub slot holds at camera-path position i: a function of i alone, like the renderer's frames."""
+    return ((np.arange(H * W * 3) * 7 + i * 13) % 251).astype(np.uint8).reshape(H, W, 3)
+
+
+class _FrameCtx(_StubCtx):
+    """_StubCtx whose slots hold frames: slot s holds path positions batch_first[s] ... batch_first[s] + batch - 1."""
+
+    def __init__(self, n_slots, batch, batch_first, W, H):
+        super().__init__(0, n_slots, batch)
+        self.batch_first, self.W, self.H = batch_first, W, H
+
+    def readback(self, slot, first, count):
+        assert 0 <= first and first + count <= self.batch
+        return np.stack([_stub_frame((self.batch_first[slot] + first + j) % 1000, self.W, self.H) for j in range(count)])
+
+
+class _FrameBackend(_StubBackend):
+    def load(self, map_id, path_seed, camera="path"):
+        super().load(map_id, path_seed, camera)
+        self.ctx = _FrameCtx(self.n_slots, self.args.batch, self.batch_first, self.args.width, self.args.height)
+        return self.ctx
+
+
+def test_dump_outputs_hold_what_the_last_timed_step_computed(tmp_path, monkeypatch):
+    """--dump-outputs DIR: float32 .npy files of the frames the last of exactly K timed steps left in the slots (a seeded sample of whole
+    frames with their path positions, a seeded pixel sample of every frame of the step), under 64 MiB, the same from run to run."""
+    import torch
+    import bench
+    _hide_gpus(torch, monkeypatch)
+    monkeypatch.setenv("RANK", "0")
+    monkeypatch.setenv("WORLD_SIZE", "1")
+    W, H, K = 40, 30, 3
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        args = bench.parse_args(["--steps", str(K), "--warmup", "1", "--clock-warmup-ms", "0", "--no-cpu-baseline", "--width", str(W),
+                                 "--height", str(H), "--batch", "250", "--dump-outputs", str(out)])
+        holder = {}
+
+        def factory(a, device):
+            holder["be"] = _FrameBackend(a, device)
+            return holder["be"]
+        line = bench.run(args, factory)
+        assert line["steps"] == K and line["ms_per_step"] > 0
+        assert holder["be"].ctx.submits == (1 + K) * 4                  # W + K steps of four 250-frame batches
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["frame_index.npy", "frames.npy", "pixels.npy"]
+        assert sum((out / f).stat().st_size for f in files) <= 64 * 10**6
+        d = {f[:-4]: np.load(out / f) for f in files}
+        assert d["frames"].dtype == d["pixels"].dtype == np.float32 and d["frame_index"].dtype == np.float64
+        assert d["frames"].shape == (4, H, W, 3) and d["pixels"].shape == (1000, 1024, 3)
+        for k, i in enumerate(d["frame_index"]):
+            assert np.array_equal(d["frames"][k], _stub_frame(int(i), W, H))
+        pos = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(H * W, 1024, replace=False))
+        for i in range(1000):                                            # every frame of the step, in path order
+            assert np.array_equal(d["pixels"][i], _stub_frame(i, W, H).reshape(-1, 3)[pos])
+        assert len(set(d["frame_index"].tolist())) == 4
+        dumps.append(d)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name])
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_real_path_are_the_oracles_frames(tmp_path, dg, synth, campath_mod, oracle):
+    """bench.py --dump-outputs on the GPU (config 2 in four 250-frame batches over four slots, in a process of its own): the dumped whole
+    frames and the pixel sample of all 1 000 frames of the last timed step are the oracle's frames at those path positions."""
+    import subprocess
+    import bench
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "2", "--batch", "250", "--steps", "3", "--warmup", "1",
+                        "--no-cpu-baseline", "--no-resident", "--no-host-frames", "--no-latency", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert '"ms_per_step"' in r.stdout
+    frames, index, pixels = (np.load(out / f"{n}.npy") for n in ("frames", "frame_index", "pixels"))
+    W, H = 320, 200
+    assert frames.shape == (4, H, W, 3) and pixels.shape == (1000, 1024, 3)
+    wad = synth.build_synth_iwad(1993)
+    scene, osc = dg.Scene(wad, "e1m1"), oracle.Scene(wad, "e1m1")
+    path = campath_mod.make_camera_path(bench.seeded_route(synth.synth_route(1993), 1993), lambda x, y, d: scene.floor_height_at(x, y, d), bench.PATH_FRAMES)
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(H * W, 1024, replace=False))
+    for i in range(bench.PATH_FRAMES):
+        ref = np.frombuffer(osc.render(W, H, path[i]), dtype=np.uint8).reshape(H, W, 3)
+        assert np.array_equal(pixels[i], ref.reshape(-1, 3)[pos]), f"frame {i}"
+        if i in index:
+            assert np.array_equal(frames[list(index).index(i)], ref), f"frame {i}"
+    scene.close()
+    osc.close()
