@@ -349,25 +349,30 @@ DG_HD void fs_ph_keep(const FsParams &P, FsShared &S, int f, int lane) {
     });
 }
 // phases 2f / 2g: the survivors get their place in the frame's part list (and their sky event slot).  Lane l walks its slice of the candidate
-// row again (candidate indices from lane_k0); lane_cnt packs (survivors | survivors that want a sky slot << 16).
+// row again (candidate indices from lane_k0); lane_cnt packs (survivors | survivors that want a sky slot << FS_SKY_SHIFT), each of the two
+// counts of a lane saturated at one past its frame capacity.  A frame's list holds up to n_segs x FS_CALLS candidates (90 000 on a map of
+// doom2's scale): unsaturated, a survivor total of 2^16 or more would carry into the sky field and pass as a small frame.  Saturated, the
+// sums over the lanes fit their fields, are exact while the frame fits both capacities and exceed one of them when it does not.
+constexpr uint32_t FS_SKY_SHIFT = 17;
+static_assert(FS_LANES * (FS_PART_CAP + 1) < (1u << FS_SKY_SHIFT) && FS_LANES * (FS_SKY_CAP + 1) < (1u << (32 - FS_SKY_SHIFT)), "fs_ph_kept_count fields");
 DG_HD void fs_ph_kept_count(const FsParams &P, FsShared &S, int f, int lane) {
     // (flags of candidate k: cl[k] >> 24)
-    uint32_t c = 0;
+    uint32_t c = 0, sky = 0;
     if (!S.fail) {
         const uint32_t *cl = fs_cl(P, S, f), *keepw = fs_keepw(P, S, f);
         const uint32_t k1 = lane + 1 < FS_LANES ? S.lane_k0[lane + 1] : S.n_cl;
         for (uint32_t k = S.lane_k0[lane]; k < k1; k++)
-            if ((keepw[k >> 5] >> (k & 31u)) & 1u) c += 1u + (fs_part_wants_sky_slot(cl[k] >> 24) ? 0x10000u : 0u);
+            if ((keepw[k >> 5] >> (k & 31u)) & 1u) { c++; sky += fs_part_wants_sky_slot(cl[k] >> 24) ? 1u : 0u; }
     }
-    S.lane_cnt[lane] = c;
+    S.lane_cnt[lane] = (c < FS_PART_CAP + 1 ? c : FS_PART_CAP + 1) | (sky < FS_SKY_CAP + 1 ? sky : FS_SKY_CAP + 1) << FS_SKY_SHIFT;
 }
 DG_HD void fs_ph_kept_place(const FsParams &P, FsShared &S, int f, int lane) {
     const uint32_t n = P.n_segs * FS_CALLS;
     const uint32_t off = fs_lane_offset(S, lane);
-    uint32_t o = off & 0xffffu, sky = off >> 16;
+    uint32_t o = off & ((1u << FS_SKY_SHIFT) - 1u), sky = off >> FS_SKY_SHIFT;
     if (lane == FS_LANES - 1) {
         const uint32_t end = off + S.lane_cnt[lane];
-        S.n_parts = end & 0xffffu; S.n_sky = end >> 16;
+        S.n_parts = end & ((1u << FS_SKY_SHIFT) - 1u); S.n_sky = end >> FS_SKY_SHIFT;
         if (S.n_parts > FS_PART_CAP || S.n_sky > FS_SKY_CAP) { S.fail = 1; S.n_parts = 0; S.n_sky = 0; }
     }
     if (S.fail || S.lane_cnt[lane] == 0u) return;                        // (no survivor in this lane's slice: nothing to look up)

@@ -667,3 +667,39 @@ extern "C" int emul_fs_frame(void *scene, int W, int H, const dg_view *view_in, 
     for (uint32_t i = 0; i < sbin_off[nb]; i++) if (sbin_sprites[i] != arena.sbin_sprites[i]) return bad("sprite bin entry " + std::to_string(i));
     return 0;
 }
+
+// dg_fs_frame's survivor counts alone (phases 2f / 2g: fs_ph_kept_count, fs_ph_block_sums, fs_ph_kept_place) for a made-up frame: the
+// slice of lane l holds survivors[l] kept candidates, the first sky[l] of which want a sky slot (a full-height part over a sky floor); the
+// list lives in the global candidate rows, as on a map of doom2's scale.  The occupancy row stays empty, so the place walk writes nothing.
+// out = [fail, n_parts, n_sky]; -1 when sky[l] > survivors[l].
+extern "C" int emul_fs_kept_counts(const uint32_t *survivors, const uint32_t *sky, uint32_t *out) {
+    uint32_t total = 0;
+    for (int l = 0; l < FS_LANES; l++) {
+        if (sky[l] > survivors[l]) return -1;
+        total += survivors[l];
+    }
+    FsParams P{};
+    P.n_segs = total / FS_CALLS + 1;
+    P.cl_row_cap = (P.n_segs * FS_CALLS + 31u) / 32u * 32u;
+    std::vector<uint32_t> cl(P.cl_row_cap, 0), keep(P.cl_row_cap / 32, 0), occ(fs_occ_words(P.n_segs), 0);
+    std::vector<uint2> lite(1, uint2{0xdeadbeefu, 0xdeadbeefu});
+    P.cl_rows = cl.data(); P.keep_rows = keep.data(); P.occ = occ.data(); P.lite = lite.data();
+    static thread_local FsShared S;
+    fs_ph_init(S);
+    S.cl_big = 1;
+    S.n_cl = total;
+    for (uint32_t l = 0, k = 0; l < (uint32_t)FS_LANES; l++) {
+        S.lane_k0[l] = k;
+        for (uint32_t j = 0; j < survivors[l]; j++, k++) {
+            cl[k] = (j < sky[l] ? (uint32_t)FEP_FLOOR_SKY : 0u) << 24;
+            keep[k >> 5] |= 1u << (k & 31u);
+        }
+    }
+#define LANES(body) for (int lane = 0; lane < FS_LANES; lane++) { body; }
+    LANES(fs_ph_kept_count(P, S, 0, lane))
+    LANES(fs_ph_block_sums(S, lane))
+    LANES(fs_ph_kept_place(P, S, 0, lane))
+#undef LANES
+    out[0] = S.fail; out[1] = S.n_parts; out[2] = S.n_sky;
+    return 0;
+}

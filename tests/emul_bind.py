@@ -31,11 +31,24 @@ def lib():
         L.emul_fs_frame.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(ctypes.c_uint64)]
         L.emul_fs_no_cl_rows.argtypes = [ctypes.c_int]
         L.emul_fs_no_cl_rows.restype = None
+        L.emul_fs_kept_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.emul_sprite_frame.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint8]
         L.emul_set_sector_light.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int16]
         L.emul_set_mobj_state.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_int]
         _lib = L
     return _lib
+
+
+def fs_kept_counts(survivors, sky):
+    """dg_fs_frame's survivor counting (fs_frame.h phases 2f / 2g) on the CPU for a made-up frame: lane l's slice of the candidate list
+    holds survivors[l] kept candidates, sky[l] of them wanting a sky slot (FS_LANES = 256 lanes).  -> (fail, n_parts, n_sky)."""
+    s = np.ascontiguousarray(survivors, dtype=np.uint32)
+    k = np.ascontiguousarray(sky, dtype=np.uint32)
+    assert s.shape == k.shape == (256,)
+    out = np.zeros(3, dtype=np.uint32)
+    if lib().emul_fs_kept_counts(s.ctypes.data, k.ctypes.data, out.ctypes.data):
+        raise ValueError("more sky survivors than survivors in a lane")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 class EmulScene:

@@ -10,6 +10,10 @@ What is pinned and by what:
   * frames_*.json        sha256 of ORACLE frames (oracle/doomref.c) at sampled path frames and sizes
   * checksums_*.json     dg_frame_checksums value (include/doomgpu.h) of EVERY oracle frame of the 1000-frame paths at
                          1280x800 (the bench size): the GPU tier compares all of them without moving a frame over PCIe
+  * checksums_map*.u64   the same, as raw little-endian u64, for every frame bench.py renders: one file per distinct (map, camera
+                         path, frame size) that bench.rank_plan gives the 8 ranks of configs 1-5 (tests/rank_plans.py)
+  * rank_plans.json      what each of those files pins: map, camera, path seed, size, and the sha256 of the path, built as bench
+                         builds it (here with the oracle's floor_height_at)
 
 The reference itself ships no fixtures and cannot be run here, so these vectors pin the in-repo CPU
 restatement against regressions ("parity unpinned" w.r.t. the Rust binary).
@@ -26,6 +30,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import doomref  # noqa: E402
+
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import rank_plans  # noqa: E402
 
 sw = importlib.import_module("doom-rust-renderer_amd.synth_wad")
 cp = importlib.import_module("doom-rust-renderer_amd.camera_path")
@@ -58,6 +65,30 @@ def full_path_checksums(wad, path, W, H):
     return out
 
 
+def write_rank_plan_fixtures():
+    """One checksum vector per plan of tests/rank_plans.py that no older fixture pins already, and the index that describes them."""
+    scenes, index = {}, {}
+    for plan in sorted(rank_plans.plans(), key=str):
+        if plan in rank_plans.LEGACY:
+            continue
+        map_seed, heavy, camera, path_seed, size = plan
+        if (map_seed, heavy) not in scenes:
+            wad = sw.build_synth_iwad(map_seed, heavy=heavy)
+            scenes[(map_seed, heavy)] = (wad, doomref.Scene(wad, "e1m1"))
+        wad, sc = scenes[(map_seed, heavy)]
+        path = rank_plans.bench_path(plan, sc, cp, sw)
+        W, H = map(int, size.split("x"))
+        sums = full_path_checksums(wad, path[:1] if camera == "start" else path, W, H)
+        name = rank_plans.fixture_name(plan)
+        np.array([int(h, 16) for h in sums], dtype="<u8").tofile(os.path.join(OUT, name))
+        index[name] = {"map_seed": map_seed, "heavy": heavy, "camera": camera, "path_seed": path_seed, "size": size,
+                       "path_sha256": rank_plans.path_sha256(path)}
+        print("wrote", name, flush=True)
+    json.dump(index, open(os.path.join(OUT, rank_plans.INDEX), "w"), indent=1, sort_keys=True)
+    for _, sc in scenes.values():
+        sc.close()
+
+
 def main():
     wads = {}
     for seed, heavy, vanilla in ((1993, False, False), (1994, True, False), (1995, False, True)):
@@ -81,6 +112,7 @@ def main():
         json.dump({"size": "1280x800", "checksums": full_path_checksums(wad, path, 1280, 800)},
                   open(os.path.join(OUT, f"checksums_seed{seed}_1280x800.json"), "w"))
     json.dump(wads, open(os.path.join(OUT, "synth_wad.json"), "w"), indent=1, sort_keys=True)
+    write_rank_plan_fixtures()
 
 
 if __name__ == "__main__":

@@ -236,3 +236,41 @@ def test_the_second_opinion_on_this_rounds_maps(synth, campath_mod, which):
         want = np.frombuffer(osc.render(W, H, r), dtype=np.uint8).reshape(H, W, 3)
         bad = np.argwhere(np.any(got != want, axis=2))
         assert len(bad) == 0, f"{which}: {len(bad)} pixels differ, first at (x={bad[0][1]}, y={bad[0][0]})"
+
+
+def _lanes(total):
+    """`total` spread over the 256 lanes as evenly as it goes."""
+    return np.array([total // 256 + (1 if l < total % 256 else 0) for l in range(256)], dtype=np.uint32)
+
+
+@pytest.mark.parametrize("case", ["256 lanes x 257 survivors", "65 546 survivors, 3 sky", "256 survivors, 64 sky", "257 survivors",
+                                  "65 sky", "one lane with 256 survivors", "one lane with 65 536 + 10 survivors"])
+def test_the_survivor_count_of_a_frame_is_exact_or_the_frame_is_given_up(case):
+    """dg_fs_frame counts the candidates that survive the hidden-part culling per lane and sums the counts over the 256 lanes, survivors
+    and survivors that want a sky slot in one word (fs_ph_kept_count / fs_ph_kept_place).  A frame's candidate list holds up to
+    n_segs x FS_CALLS entries (90 000 on a map of doom2's scale): a survivor total that does not fit its field must not carry into the
+    sky count and pass as a small frame.  The frame either fits both capacities and is counted exactly, or it is handed to the host."""
+    import emul_bind
+    zero = np.zeros(256, dtype=np.uint32)
+    if case == "256 lanes x 257 survivors":                   # 65 792 = 0x10100 survivors: 256 parts and 1 sky slot if the count carried
+        surv, sky, fits = np.full(256, 257, dtype=np.uint32), zero, False
+    elif case == "65 546 survivors, 3 sky":
+        surv, sky, fits = _lanes(65536 + 10), zero.copy(), False
+        sky[[0, 100, 255]] = 1
+    elif case == "256 survivors, 64 sky":                     # both capacities exactly
+        surv, sky, fits = _lanes(FS_PART_CAP), _lanes(FS_SKY_CAP), True
+    elif case == "257 survivors":
+        surv, sky, fits = _lanes(FS_PART_CAP + 1), zero, False
+    elif case == "65 sky":
+        surv, sky, fits = _lanes(200), _lanes(FS_SKY_CAP + 1), False
+    elif case == "one lane with 256 survivors":               # the whole part list in one lane's slice, the sky slots in another's
+        surv, sky, fits = zero.copy(), zero.copy(), True
+        surv[17], surv[200], sky[200] = FS_PART_CAP - 40, 40, 40
+    else:
+        surv, sky, fits = zero.copy(), zero.copy(), False
+        surv[255], sky[255] = 65536 + 10, 1
+    fail, n_parts, n_sky = emul_bind.fs_kept_counts(surv, sky)
+    if fits:
+        assert (fail, n_parts, n_sky) == (0, int(surv.sum()), int(sky.sum())), case
+    else:
+        assert fail == 1, f"{case}: accepted with {n_parts} parts and {n_sky} sky slots"
