@@ -35,7 +35,7 @@ def random_case(seed, W, H):
         if rng.integers(0, 6) == 0:
             end_x = start_x
         cols = []
-        for x in sorted(rng.choice(np.arange(-2, W + 3), size=int(rng.integers(1, W)), replace=False).tolist()):
+        for x in sorted(rng.choice(np.arange(-2, W + 3), size=int(rng.integers(1, max(W, 2))), replace=False).tolist()):
             ct = int(rng.integers(0, H)); cb = int(rng.integers(0, H))
             if rng.integers(0, 8) != 0 and ct > cb:
                 ct, cb = cb, ct                                                                  # (one in eight stays empty: ct > cb)
