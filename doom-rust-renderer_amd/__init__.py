@@ -22,6 +22,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "doomgpu.h")
 
 DG_OK, DG_ERR_INVALID, DG_ERR_NO_DEVICE, DG_ERR_HIP, DG_ERR_WAD, DG_ERR_RENDER, DG_ERR_CAPACITY = 0, -1, -2, -3, -4, -5, -6
 DG_FE_AUTO, DG_FE_HOST, DG_FE_DEVICE, DG_FE_DEVICE_SEGS = 0, 1, 2, 3
+DG_FE_MAP = 4   # dg_timing.front_end of a 2-D map submission
 
 
 class DoomGpuError(RuntimeError):
@@ -58,6 +59,10 @@ class DgTiming(ctypes.Structure):
                 ("n_spans", ctypes.c_uint64), ("n_frames", ctypes.c_uint64), ("covered_pixels", ctypes.c_uint64),
                 ("n_walls", ctypes.c_uint64), ("n_planes", ctypes.c_uint64), ("list_bytes", ctypes.c_uint64),
                 ("front_end", ctypes.c_int32)]
+
+
+class DgMapLine(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in "x0 y0 x1 y1".split()] + [("rgb", ctypes.c_uint32)]
 
 
 class DgBitmapColumn(ctypes.Structure):
@@ -139,6 +144,9 @@ _SIGNATURES = {
     "dg_scene_bitmap_size": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "dg_draw_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P]),
     "dg_build_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgFrameLists)]),
+    "dg_map_lines": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgMapLine), ctypes.c_int]),
+    "dg_submit_map_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int]),
+    "dg_render_map_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, _P]),
     "dg_last_error": (ctypes.c_char_p, []),
     "dg_version": (ctypes.c_char_p, []),
     "dg_slot_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgTiming)]),
@@ -228,6 +236,17 @@ class Scene:
         _check(lib().dg_build_lists(self._h, W, H, ctypes.byref(view), ctypes.byref(fl)))
         return fl
 
+    def map_lines(self, W: int, H: int, view=None) -> np.ndarray:
+        """dg_map_lines: the lines of one 2-D map frame in draw order, (n, 5) int64 rows [x0, y0, x1, y1, rgb] (rgb = r | g<<8 | b<<16);
+        view None: the linedefs only."""
+        vp = ctypes.byref(view) if view is not None else None
+        n = _check(lib().dg_map_lines(self._h, W, H, vp, None, 0))
+        arr = (DgMapLine * max(1, n))()
+        _check(lib().dg_map_lines(self._h, W, H, vp, arr, n))
+        rows = np.frombuffer(arr, dtype=np.int32, count=5 * n).reshape(n, 5).astype(np.int64)
+        rows[:, 4] &= 0xFFFFFFFF
+        return rows
+
     def close(self):
         if self._h:
             lib().dg_scene_free(self._h)
@@ -270,6 +289,17 @@ class Context:
             _check(lib().dg_submit_views(self._h, slot, views, len(views) if n is None else n))
         else:
             _check(lib().dg_submit_views_state(self._h, slot, views, states, len(views) if n is None else n))
+
+    def submit_map(self, slot: int, views, n=None):
+        """dg_submit_map_views: 2-D map frames (the reference's viewing_map) into the slot, asynchronously."""
+        _check(lib().dg_submit_map_views(self._h, slot, views, len(views) if n is None else n))
+
+    def render_map(self, views) -> np.ndarray:
+        """dg_render_map_views: synchronous 2-D map frames through slot 0; returns (n, H, W, 3) uint8."""
+        n = len(views)
+        out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
+        _check(lib().dg_render_map_views(self._h, views, n, out.ctypes.data_as(_P)))
+        return out
 
     def render_state(self, views, states) -> np.ndarray:
         """render() with one game-state snapshot per view (make_view_states)."""

@@ -8,7 +8,9 @@
 //             framebuffer slab  F x 3*W*H bytes RGB24 (the reference's Pixels.pixels, one per frame)
 //             DG_FE_DEVICE: record slab [DevFrame x F | FeFrame x F | FePart.. | FeSprite.. | behind bits.. | sky slot -> part.. | column bins..] (one H2D copy),
 //             col_off F*(W+1) written by dg_fe_finalize, 2F status words (overflow flags, span totals)
-//   per ctx : DG_FE_DEVICE column scratch [F][slot][W]: compact spans 16 B (48 slots), wall-record columns 8 B (48 slots),
+//             2-D map view: the arrow lines of the batch (MapSeg x 3F) at the start of the list slab
+//   per ctx : 2-D map view layer 3*W*H bytes RGB24 (allocated by the first map submission, rebuilt after every dg_upload_scene)
+//             DG_FE_DEVICE column scratch [F][slot][W]: compact spans 16 B (48 slots), wall-record columns 8 B (48 slots),
 //             counts, sky event bits — shared by the slots because their kernels run back to back
 #include <hip/hip_runtime_api.h>
 #include <sched.h>
@@ -33,6 +35,7 @@
 #include "fs_kernels.hpp"
 #include "frontend.hpp"
 #include "kernels.hpp"
+#include "map_kernels.hpp"
 #include "scene.hpp"
 
 using namespace dg;
@@ -141,6 +144,8 @@ struct Slot {
     bool fs_mode = false;         // the last submission's per-seg half ran on the GPU too
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
     bool fe_mode = false;         // the last submission went through the device column walk
+    bool map_mode = false;        // the last submission was 2-D map frames (dg_submit_map_views): arrow lines at the start of d_lists
+    bool map_built = false;       // ... and its enqueue built the ctx's map layer (ev_start .. ev_setup time that)
     bool fe_check = false;        // ... and its overflow flags have not been looked at yet
     std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
     // ... and a private copy of their game-state snapshots (the caller's arrays need not outlive the call)
@@ -245,6 +250,9 @@ struct dg_ctx {
     uint32_t *d_fe_cnt = nullptr;
     FeU4 *d_fe_cspans = nullptr;
     FeColRec *d_fe_recs = nullptr;
+    // 2-D map view: every drawn linedef of the uploaded scene, RGB24, built by the first map submission after dg_upload_scene
+    uint8_t *d_map_layer = nullptr;
+    bool map_layer_ok = false;
 };
 
 namespace {
@@ -310,6 +318,7 @@ void free_ctx(dg_ctx *c) {
     if (c->d_fe_recs) (void)hipFree(c->d_fe_recs);
     if (c->d_fs_scene) (void)hipFree(c->d_fs_scene);
     if (c->d_fs_scratch) (void)hipFree(c->d_fs_scratch);
+    if (c->d_map_layer) (void)hipFree(c->d_map_layer);
     delete c;
 }
 
@@ -380,7 +389,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
     P.n_frames = n;
     s.max_spans = max_spans; s.n_spans = spans; s.covered = covered; s.n_frames = n; s.n_walls = walls; s.n_planes = planes;
     s.list_bytes = total;
-    s.fe_mode = false; s.fs_mode = false; s.fe_check = false;
+    s.fe_mode = false; s.fs_mode = false; s.fe_check = false; s.map_mode = false;
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(s.d_lists, s.h_lists, total, hipMemcpyHostToDevice, s.stream));
     return DG_OK;
@@ -508,7 +517,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     P.n_frames = n;
     s.max_spans = 0; s.n_spans = 0; s.covered = 0; s.n_frames = n; s.n_walls = parts; s.n_planes = sprites;
     s.list_bytes = total;
-    s.fe_mode = true; s.fs_mode = false; s.fe_check = false;
+    s.fe_mode = true; s.fs_mode = false; s.fe_check = false; s.map_mode = false;
     s.views.assign(views, views + n);
     s.keep_states(states, n);
     s.snapshot_scene(sc);
@@ -726,7 +735,7 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     P.n_frames = n;
     s.max_spans = 0; s.n_spans = 0; s.covered = 0; s.n_frames = n; s.n_walls = 0; s.n_planes = 0;
     s.list_bytes = upload;
-    s.fe_mode = true; s.fs_mode = true; s.fe_check = false;
+    s.fe_mode = true; s.fs_mode = true; s.fe_check = false; s.map_mode = false;
     s.keep_states(states, n);
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -744,6 +753,43 @@ int build_batch(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *
         if (rc != kPartsUnsupported) return rc;
     }
     return build_batch_host(c, s, views, given, n, states);
+}
+
+// The 2-D map view's linedef layer of the uploaded scene, on the kernel stream (timed by the slot's ev_start / ev_setup).  The line records
+// and the W*H owner words are transient: freed once the layer is built.
+int build_map_layer(dg_ctx *c, Slot &s) {
+    const int W = c->cfg.width, H = c->cfg.height;
+    std::vector<dg_map_line> lines;
+    std::string err;
+    int rc = map_frame_lines(*c->scene, W, H, nullptr, lines, err);
+    if (rc) return set_err(rc, err);
+    const size_t n = lines.size();
+    std::vector<MapSeg> segs(std::max<size_t>(n, 1));
+    std::vector<uint32_t> base(n + 1);
+    uint64_t total = 0;
+    for (size_t k = 0; k < n; k++) {
+        const dg_map_line &l = lines[k];
+        segs[k] = map_seg_make(l.x0, l.y0, l.x1, l.y1, l.rgb, W, H);
+        base[k] = (uint32_t)total;
+        total += (uint64_t)segs[k].count;
+    }
+    if (total >= (1ull << 31)) return set_err(DG_ERR_CAPACITY, "map layer: too many line steps");
+    base[n] = (uint32_t)total;
+    if (!c->d_map_layer) HIP_TRY(hipMalloc((void **)&c->d_map_layer, (size_t)3 * (size_t)W * (size_t)H));
+    const size_t off_segs = align_up((size_t)W * (size_t)H * 4, 256), off_base = align_up(off_segs + segs.size() * sizeof(MapSeg), 256);
+    uint8_t *tmp = nullptr;
+    HIP_TRY(hipMalloc((void **)&tmp, off_base + base.size() * 4));
+    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } tmp_guard{tmp};
+    uint32_t *owner = reinterpret_cast<uint32_t *>(tmp);
+    MapSeg *d_segs = reinterpret_cast<MapSeg *>(tmp + off_segs);
+    uint32_t *d_base = reinterpret_cast<uint32_t *>(tmp + off_base);
+    HIP_TRY(hipMemcpy(d_segs, segs.data(), segs.size() * sizeof(MapSeg), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_base, base.data(), base.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(owner, 0, (size_t)W * (size_t)H * 4, c->kstream));
+    HIP_TRY(launch_map_layer(d_segs, d_base, (uint32_t)n, (uint32_t)total, owner, c->d_map_layer, W, H, c->kstream, s.ev_start, s.ev_setup));
+    HIP_TRY(hipStreamSynchronize(c->kstream));           // (before the transient buffers go)
+    c->map_layer_ok = true;
+    return DG_OK;
 }
 
 constexpr size_t kOverlapMaxPixels = 500000;          // frames up to this size overlap their raster launch with the next batch's front end (dg_create)
@@ -767,6 +813,21 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     s.fe_check = false;
     HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
     HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
+    if (s.map_mode) {                                     // 2-D map frames: the layer (once per scene upload), then copy + arrow per frame
+        s.map_built = false;
+        if (!c->map_layer_ok) {
+            const int rc = build_map_layer(c, s);
+            if (rc) return rc;
+            s.map_built = true;
+        }
+        HIP_TRY(launch_map_frames(c->d_map_layer, reinterpret_cast<const MapSeg *>(s.d_lists), s.n_frames, s.d_fb, c->cfg.width, c->cfg.height,
+                                  ks, s.ev_rstart, s.ev_raster));
+        guard.armed = false;
+        s.harvested = true;                               // (never DG_FE_AUTO's measurement)
+        s.raster_recorded = true;
+        s.busy = true; s.timed = true;
+        return DG_OK;
+    }
     if (fe_mode) {
         std::memset(s.h_status, 0, (size_t)2 * (size_t)c->cfg.max_batch * 4);
         // the overflow flags, the launch-order counters and the event bits behind them start from zero: dg_fe_scan leaves them so (its
@@ -951,7 +1012,7 @@ int check_slot(dg_ctx *c, int slot) {
 extern "C" {
 
 const char *dg_last_error(void) { return t_err.c_str(); }
-const char *dg_version(void) { return "doomgpu 0.4 (gfx950; ABI 4)"; }
+const char *dg_version(void) { return "doomgpu 0.5 (gfx950; ABI 4)"; }
 
 int dg_scene_load_wad(const uint8_t *wad, size_t len, const char *map_name, dg_scene **out) {
     if (!wad || !map_name || !out) return set_err(DG_ERR_INVALID, "null argument");
@@ -1158,7 +1219,8 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     if (c->d_texel_opq) { (void)hipFree(c->d_texel_opq); c->d_texel_opq = nullptr; }
     c->d_flats = nullptr;               // inside d_texel_idx's allocation
     // the slots' prepared records point into the device scene that was just freed: nothing may be replayed from them
-    for (Slot &s : c->slots) { s.n_frames = 0; s.timed = false; s.fe_check = false; s.busy = false; s.snap_scene = nullptr; }   // (a new scene may reuse the old one's address and revision)
+    for (Slot &s : c->slots) { s.n_frames = 0; s.timed = false; s.fe_check = false; s.busy = false; s.snap_scene = nullptr; }
+    c->map_layer_ok = false;            // the map view's linedef layer belongs to the old scene   // (a new scene may reuse the old one's address and revision)
     uint32_t pal[256];
     for (int i = 0; i < 256; i++) pal[i] = (uint32_t)sc.palette[3 * i] | ((uint32_t)sc.palette[3 * i + 1] << 8) | ((uint32_t)sc.palette[3 * i + 2] << 16);
     const size_t nt = std::max<size_t>(sc.texel_idx.size(), 16), nf = std::max<size_t>(sc.flat_pool.size(), 16);
@@ -1386,6 +1448,59 @@ int dg_draw_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, int n, uint
     return dg_wait(c, slot);
 }
 
+int dg_map_lines(const dg_scene *s, int width, int height, const dg_view *view, dg_map_line *out, int cap) {
+    if (!s) return set_err(DG_ERR_INVALID, "null scene");
+    dg_view v{};
+    if (view) { v = *view; fill_view_trig(v); }
+    static thread_local std::vector<dg_map_line> lines;
+    std::string err;
+    const int rc = map_frame_lines(*s->sc, width, height, view ? &v : nullptr, lines, err);
+    if (rc) return set_err(rc, err);
+    if (out && cap >= 0 && (size_t)cap >= lines.size() && !lines.empty()) std::memcpy(out, lines.data(), lines.size() * sizeof(dg_map_line));
+    return (int)lines.size();
+}
+
+int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!views) return set_err(DG_ERR_INVALID, "null views");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    const int W = c->cfg.width, H = c->cfg.height;
+    if (W < 40 || H < 40) return set_err(DG_ERR_INVALID, "map frames need width and height >= 40");
+    if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
+    const size_t bytes = (size_t)n * 3 * sizeof(MapSeg);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    Slot &s = c->slots[(size_t)slot];
+    if (s.busy || s.copy_pending) { rc = finish_slot(c, s); if (rc) return rc; }
+    if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
+    s.fe_check = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    // the arrow's three lines per view, clipped to the frame (the host owns the libm trig: dg_view has no field for the head angles)
+    MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists);
+    std::string err;
+    for (int i = 0; i < n; i++) {
+        dg_view v = views[i];
+        fill_view_trig(v);
+        dg_map_line l[3];
+        rc = map_arrow_lines(*c->scene, W, H, v, l, err);
+        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
+        for (int k = 0; k < 3; k++) h[3 * i + k] = map_seg_make(l[k].x0, l[k].y0, l[k].x1, l[k].y1, l[k].rgb, W, H);
+    }
+    s.map_mode = true; s.fe_mode = false; s.fs_mode = false;
+    s.n_frames = n; s.max_spans = 0; s.n_spans = 0; s.covered = 0; s.n_walls = 0; s.n_planes = 0;
+    s.list_bytes = bytes;
+    s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    HIP_TRY(hipMemcpyAsync(s.d_lists, s.h_lists, bytes, hipMemcpyHostToDevice, s.stream));
+    return enqueue_kernels(c, s);
+}
+
+int dg_render_map_views(dg_ctx *c, const dg_view *views, int n, uint8_t *out) {
+    int rc = dg_submit_map_views(c, 0, views, n);
+    if (rc) return rc;
+    if (out) return dg_readback(c, 0, 0, n, out);
+    return dg_wait(c, 0);
+}
+
 int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
@@ -1400,6 +1515,18 @@ int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
         if (rc) return rc;
     }
     std::memset(out, 0, sizeof *out);
+    if (s.map_mode) {
+        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
+        if (s.map_built) {
+            HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
+            HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));
+        } else {
+            out->total_ms = out->raster_ms;
+        }
+        out->n_frames = (uint64_t)s.n_frames; out->host_ms = s.host_ms; out->list_bytes = s.list_bytes;
+        out->front_end = DG_FE_MAP;
+        return DG_OK;
+    }
     HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
     HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
     HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));

@@ -6,6 +6,7 @@
 //   Player { position, floor_height, angle }                                                            doom::Player
 //   Map + MapObjects + Textures + Sprites + sky_texture + Flats + Palette (borrowed by Renderer::new)   doom::World
 //   Renderer::new(&mut pixels, .., &player, timestamp).render()                                         doom::Renderer
+//   Game::render with viewing_map (draw_map_linedefs + draw_map_player, src/game.rs:229-309,491-499)   doom::Renderer::render_map
 //
 // Same names, argument meaning and ownership: the caller owns Pixels and World, the Renderer borrows them for one
 // frame.  Where the reference panics these wrappers throw doom::Error carrying the dg_status code.
@@ -119,6 +120,9 @@ public:
         view_ = dg_view{player.position.x, player.position.y, a, player.floor_height, std::cos(a), std::sin(a), std::cos(-a), std::sin(-a), timestamp, 1};
     }
     void render() { check(dg_render_views(dev_.handle(), &view_, 1, pixels_.pixels.data())); }
+    // The viewing_map branch of Game::render (src/game.rs:491-499): canvas.clear() to black, draw_map_linedefs, draw_map_player, into
+    // the same Pixels.  Reads the player's position and angle only.
+    void render_map() { check(dg_render_map_views(dev_.handle(), &view_, 1, pixels_.pixels.data())); }
 private:
     Pixels &pixels_;
     Device &dev_;

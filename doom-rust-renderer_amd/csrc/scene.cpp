@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <unordered_map>
@@ -683,6 +684,12 @@ Scene *load_scene_from_wad(const uint8_t *bytes, size_t len, const char *map_nam
                 sc->mobjs.push_back(m);
             }
         }
+        for (const LinedefRec &d : sc->linedefs)
+            for (int32_t v : {d.v1, d.v2}) {
+                const float x = sc->vx[(size_t)v], y = sc->vy[(size_t)v];
+                sc->map_left = std::min(sc->map_left, x); sc->map_right = std::max(sc->map_right, x);
+                sc->map_top = std::min(sc->map_top, y); sc->map_bottom = std::max(sc->map_bottom, y);
+            }
         sc->rebuild_fs_tables();
         return sc;
     } catch (const std::exception &ex) {
@@ -690,6 +697,78 @@ Scene *load_scene_from_wad(const uint8_t *bytes, size_t len, const char *map_nam
         delete sc;
         return nullptr;
     }
+}
+
+}  // namespace dg
+
+namespace dg {
+
+// transform_vertex_to_point_for_map (src/game.rs:229-243), every operation in f32 in the reference's order (no FMA: -ffp-contract=off)
+namespace {
+struct MapXform {
+    float left, top, xs, ys, sw, sh;
+    void point(float vx, float vy, int32_t &X, int32_t &Y) const {
+        const float b = 20.0f;
+        X = f32_as_i32(b + ((vx - left) * sw) / xs);
+        Y = f32_as_i32(((b + sh) - 1.0f) - ((vy - top) * sh) / ys);
+    }
+};
+MapXform map_xform(const Scene &sc, int W, int H) {
+    return MapXform{sc.map_left, sc.map_top, sc.map_right - sc.map_left, sc.map_bottom - sc.map_top, (float)(W - 40), (float)(H - 40)};
+}
+constexpr uint32_t kMapRed = 0x0000ffu, kMapYellow = 0x00ffffu;   // Color::RGB(255, 0, 0) / (255, 255, 0) as r | g << 8 | b << 16
+}  // namespace
+
+int map_arrow_lines(const Scene &sc, int W, int H, const dg_view &view, dg_map_line out[3], std::string &err) {
+    if (W < 40 || H < 40 || W > 16384 || H > 16384) { err = "map frames need width and height in [40, 16384]"; return DG_ERR_INVALID; }
+    const MapXform t = map_xform(sc, W, H);
+    // draw_map_player, game.rs:287-309: Vertex::rotate (vertexes.rs:20-25) evaluated literally, 0.0 products included
+    const float PI = 3.14159265358979323846f;                                  // std::f32::consts::PI
+    const float a = view.angle, len = (float)W / 16.0f, alen = (float)W / 32.0f;
+    const float zero = 0.0f;
+    const float c = view.cos_a, s = view.sin_a;
+    const float px = view.x, py = view.y;
+    const float ex = px + (len * c - zero * s), ey = py + (zero * c + len * s);
+    const float ar = (a - PI) - PI / 4.0f, al = (a - PI) + PI / 4.0f;
+    const float cr = cosf(ar), sr = sinf(ar), cl = cosf(al), sl = sinf(al);
+    const float rx = ex + (alen * cr - zero * sr), ry = ey + (zero * cr + alen * sr);
+    const float lx = ex + (alen * cl - zero * sl), ly = ey + (zero * cl + alen * sl);
+    int32_t P[4][2];
+    t.point(px, py, P[0][0], P[0][1]);
+    t.point(ex, ey, P[1][0], P[1][1]);
+    t.point(rx, ry, P[2][0], P[2][1]);
+    t.point(lx, ly, P[3][0], P[3][1]);
+    for (auto &p : P)
+        for (int32_t v : p)
+            if (v < -(1 << 24) || v > (1 << 24)) {
+                err = "the player arrow lands beyond +-2^24 pixels of the map frame (out of contract: SDL's int -> float -> int round trip is not exact there)";
+                return DG_ERR_INVALID;
+            }
+    out[0] = dg_map_line{P[0][0], P[0][1], P[1][0], P[1][1], kMapYellow};
+    out[1] = dg_map_line{P[2][0], P[2][1], P[1][0], P[1][1], kMapYellow};
+    out[2] = dg_map_line{P[3][0], P[3][1], P[1][0], P[1][1], kMapYellow};
+    return DG_OK;
+}
+
+int map_frame_lines(const Scene &sc, int W, int H, const dg_view *view, std::vector<dg_map_line> &out, std::string &err) {
+    out.clear();
+    if (W < 40 || H < 40 || W > 16384 || H > 16384) { err = "map frames need width and height in [40, 16384]"; return DG_ERR_INVALID; }
+    dg_map_line arrow[3];
+    if (view) {
+        const int rc = map_arrow_lines(sc, W, H, *view, arrow, err);
+        if (rc) return rc;
+    }
+    const MapXform t = map_xform(sc, W, H);
+    for (const LinedefRec &d : sc.linedefs) {                                  // draw_map_linedefs, game.rs:245-262
+        if (d.flags & 128) continue;                                           // DONTDRAW
+        dg_map_line l;
+        t.point(sc.vx[(size_t)d.v1], sc.vy[(size_t)d.v1], l.x0, l.y0);
+        t.point(sc.vx[(size_t)d.v2], sc.vy[(size_t)d.v2], l.x1, l.y1);
+        l.rgb = (d.flags & 4) ? kMapYellow : kMapRed;                          // TWOSIDED
+        out.push_back(l);
+    }
+    if (view) out.insert(out.end(), arrow, arrow + 3);
+    return DG_OK;
 }
 
 }  // namespace dg

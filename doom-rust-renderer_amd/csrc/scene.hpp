@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/doomgpu.h"
 #include "fs_frame.h"
 
 namespace dg {
@@ -70,6 +71,8 @@ struct Scene {
     std::vector<NodeRec> nodes;
     std::vector<MapObjectRec> mobjs;
     float start_x = 0, start_y = 0, start_angle = 0;
+    // Map::bounding_box (src/map/mod.rs:59-64, src/geometry.rs:11-28): both vertices of every linedef, in LINEDEFS order
+    float map_left = 3.40282347e38f, map_top = 3.40282347e38f, map_right = -3.40282347e38f, map_bottom = -3.40282347e38f;
     bool has_start = false;
     bool may_panic = false;                         // some sidedef texture / sector flat lookup would panic in the reference when reached
     // graphics
@@ -109,6 +112,13 @@ struct Scene {
     int sector_from_vertex(float x, float y) const;                              // renderer/bsp.rs:9-44
     int find_or_add_sprite_frame(const std::string &sprite, uint8_t frame, std::string &err);
 };
+
+// The lines of one 2-D map frame (Game::render with viewing_map, src/game.rs:229-308) in draw order: every linedef without DONTDRAW, then
+// (view != nullptr) the player arrow's three lines P->E, R->E, L->E.  DG_ERR_INVALID for a frame under 40 x 40 or over 16384 x 16384,
+// or an arrow endpoint beyond +-2^24 after the transform.  view's trig must be filled (fill_view_trig).
+int map_frame_lines(const Scene &sc, int W, int H, const dg_view *view, std::vector<dg_map_line> &out, std::string &err);
+// The arrow's three lines alone (what changes from one map frame to the next), with the same checks.
+int map_arrow_lines(const Scene &sc, int W, int H, const dg_view &view, dg_map_line out[3], std::string &err);
 
 // Returns nullptr and fills err on any condition where the reference's loaders panic.
 Scene *load_scene_from_wad(const uint8_t *wad, size_t len, const char *map_name, std::string &err);

@@ -122,6 +122,8 @@ typedef struct dg_config {
  *                      instruction stream, and which fallback counters — a given batch gets is NOT reproducible from run to run.
  *                      Ask for DG_FE_DEVICE or DG_FE_DEVICE_SEGS where that matters. */
 enum { DG_FE_AUTO = 0, DG_FE_HOST = 1, DG_FE_DEVICE = 2, DG_FE_DEVICE_SEGS = 3 };
+/* dg_timing.front_end of a 2-D map submission (dg_submit_map_views); never a dg_config.front_end. */
+enum { DG_FE_MAP = 4 };
 
 int dg_create(const dg_config *cfg, dg_ctx **out);
 void dg_destroy(dg_ctx *ctx);
@@ -229,6 +231,27 @@ int dg_draw_lists(dg_ctx *ctx, int slot, const dg_frame_lists *frames, int n, ui
  * host logic without a GPU).  The returned pointers live in an internal per-thread arena and stay valid
  * until the next dg_build_lists call on the same thread. */
 int dg_build_lists(const dg_scene *s, int width, int height, const dg_view *view, dg_frame_lists *out);
+
+/* ---- 2-D map view (reference: Game::render with viewing_map, src/game.rs:491-499, 229-309) --------------------------------- */
+/* What the window holds after render() in map mode, RGB24 like every frame: black; every linedef without DONTDRAW (flags & 128) in
+ * LINEDEFS order, yellow (255, 255, 0) when TWOSIDED (flags & 4) else red (255, 0, 0); then the player arrow in yellow: P->E, R->E, L->E.
+ * Points go through transform_vertex_to_point_for_map (f32, the reference's operand order, `as i32`) and lines are rasterised as SDL2's
+ * RenderDrawLineBresenham with draw_last (DESIGN.md section 8a states the rule).  The view's x, y, angle and trig are read (trig_valid = 0:
+ * cosf / sinf of angle); floor_height and timestamp are not.  The two arrow-head angles always take the host's cosf / sinf.
+ * Frames under 40 x 40 are DG_ERR_INVALID (the reference's u32 subtraction underflows), and so is a view whose arrow lands beyond +-2^24
+ * pixels after the transform (out of contract). */
+typedef struct dg_map_line { int32_t x0, y0, x1, y1; uint32_t rgb; /* r | g<<8 | b<<16 */ } dg_map_line;
+/* The lines of one map frame in draw order: drawn linedefs, then the 3 arrow lines (view == NULL: linedefs only).
+ * Returns the count; out == NULL or cap too small: count only.  Host only, like dg_build_lists. */
+int dg_map_lines(const dg_scene *s, int width, int height, const dg_view *view, dg_map_line *out, int cap);
+/* Asynchronous, like dg_submit_views: n map frames into the slot's framebuffer slab, so dg_wait, dg_readback(_async),
+ * dg_frame_checksums, dg_slot_framebuffer and dg_slot_timing work on it unchanged (front_end = DG_FE_MAP, raster_ms = the per-frame
+ * kernels, setup_ms = the linedef layer when this submission built it, else 0).  The layer does not depend on the view: the first map
+ * submission after dg_upload_scene builds it (3*W*H bytes of device memory, kept by the ctx), later ones copy it and draw the arrow.
+ * dg_replay_slot re-runs the per-frame kernels.  No scene uploaded: DG_ERR_INVALID; n outside [1, max_batch]: DG_ERR_CAPACITY. */
+int dg_submit_map_views(dg_ctx *ctx, int slot, const dg_view *views, int n);
+/* Synchronous, slot 0: if rgb24_out != NULL copy n*3*W*H bytes to host memory. */
+int dg_render_map_views(dg_ctx *ctx, const dg_view *views, int n, uint8_t *rgb24_out);
 
 /* ---- misc ----------------------------------------------------------------------------------------------------- */
 const char *dg_last_error(void); /* thread-local message of the last failing call */

@@ -42,6 +42,11 @@ pub struct dg_frame_lists {
     pub order: *const dg_draw_cmd,        pub n_order: u32,
 }
 
+/// One line of a 2-D map frame (dg_map_lines): rgb = r | g << 8 | b << 16.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct dg_map_line { pub x0: i32, pub y0: i32, pub x1: i32, pub y1: i32, pub rgb: u32 }
+pub const DG_FE_MAP: i32 = 4;              // dg_timing.front_end of a map submission
+
 extern "C" {
     pub fn dg_scene_load_wad(wad: *const u8, len: usize, map_name: *const c_char, out: *mut *mut dg_scene) -> c_int;
     pub fn dg_scene_free(s: *mut dg_scene);
@@ -61,6 +66,9 @@ extern "C" {
     pub fn dg_render_views(ctx: *mut dg_ctx, views: *const dg_view, n: c_int, rgb24_out: *mut u8) -> c_int;
     pub fn dg_draw_lists(ctx: *mut dg_ctx, slot: c_int, frames: *const dg_frame_lists, n: c_int, rgb24_out: *mut u8) -> c_int;
     pub fn dg_frame_checksums(ctx: *mut dg_ctx, slot: c_int, first: c_int, count: c_int, out: *mut u64) -> c_int;
+    pub fn dg_map_lines(s: *const dg_scene, width: c_int, height: c_int, view: *const dg_view, out: *mut dg_map_line, cap: c_int) -> c_int;
+    pub fn dg_submit_map_views(ctx: *mut dg_ctx, slot: c_int, views: *const dg_view, n: c_int) -> c_int;
+    pub fn dg_render_map_views(ctx: *mut dg_ctx, views: *const dg_view, n: c_int, rgb24_out: *mut u8) -> c_int;
     pub fn dg_last_error() -> *const c_char;
 }
 
@@ -78,6 +86,12 @@ impl<'a> GpuRenderer<'a> {
     pub fn render(&mut self) {
         let rc = unsafe { dg_render_views(self.ctx, &self.view, 1, self.pixels.pixels.as_mut_ptr()) };
         if rc != 0 { panic!("doomgpu: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }  // the reference panics too
+    }
+    /// The `viewing_map` branch of Game::render (src/game.rs:491-499): black, draw_map_linedefs, draw_map_player — into the same
+    /// Pixels, so the caller copies `pixels.pixels` into the window texture as for a 3-D frame and needs no SDL canvas path.
+    pub fn render_map(&mut self) {
+        let rc = unsafe { dg_render_map_views(self.ctx, &self.view, 1, self.pixels.pixels.as_mut_ptr()) };
+        if rc != 0 { panic!("doomgpu: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
     }
 }
 
