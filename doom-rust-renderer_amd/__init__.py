@@ -23,6 +23,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "doomgpu.h")
 DG_OK, DG_ERR_INVALID, DG_ERR_NO_DEVICE, DG_ERR_HIP, DG_ERR_WAD, DG_ERR_RENDER, DG_ERR_CAPACITY = 0, -1, -2, -3, -4, -5, -6
 DG_FE_AUTO, DG_FE_HOST, DG_FE_DEVICE, DG_FE_DEVICE_SEGS = 0, 1, 2, 3
 DG_FE_MAP = 4   # dg_timing.front_end of a 2-D map submission
+DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 
 
 class DoomGpuError(RuntimeError):
@@ -140,6 +141,8 @@ _SIGNATURES = {
     "dg_replay_slot": (ctypes.c_int, [_P, ctypes.c_int]),
     "dg_scene_texture_id": (ctypes.c_int, [_P, ctypes.c_char_p]),
     "dg_scene_flat_id": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_float]),
+    "dg_scene_set_wall_effects": (ctypes.c_int, [_P, ctypes.c_uint32]),
+    "dg_scene_wall_texture_id": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_float]),
     "dg_scene_sprite_bitmap_id": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_uint8]),
     "dg_scene_bitmap_size": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "dg_draw_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P]),
@@ -230,6 +233,15 @@ class Scene:
 
     def set_mobj_state(self, mobj: int, sprite, frame: int = 0, full_bright: bool = False):
         _check(lib().dg_scene_set_mobj_state(self._h, mobj, sprite.encode() if sprite else None, frame, int(full_bright)))
+
+    def set_wall_effects(self, flags: int):
+        """dg_scene_set_wall_effects: DG_WALL_ANIMATE | DG_WALL_SCROLL, or 0 (may decode bitmaps: call before Context.upload_scene,
+        which is where the flags take effect for a Context; build_lists sees them at once)."""
+        _check(lib().dg_scene_set_wall_effects(self._h, flags))
+
+    def wall_texture_id(self, name: str, timestamp: float = 0.0) -> int:
+        """dg_scene_wall_texture_id: the texture's bitmap id after wall animation at `timestamp` (negative: unknown)."""
+        return lib().dg_scene_wall_texture_id(self._h, name.encode(), timestamp)
 
     def build_lists(self, W: int, H: int, view: DgView) -> DgFrameLists:
         fl = DgFrameLists()

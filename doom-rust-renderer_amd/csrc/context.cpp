@@ -237,6 +237,10 @@ struct dg_ctx {
     int since_fs_probe = 0;             // host-walker batches since the seg walk was last timed (likewise)
     int gpu_samples[2] = {0, 0};        // finished batches seen per mode (host per-seg half / seg walk): the first of each runs on cold caches and clocks, not counted
     uint8_t *d_fs_scene = nullptr;
+    // wall effects: the scene's WallFx as of dg_upload_scene (every front end draws with this copy), and for the seg walk its device tables
+    WallFx fx;
+    uint8_t *d_wall_fx = nullptr;       // FsSegFx per seg | the live animation lists (only while fx.on() and the seg walk is uploaded)
+    FsFx fs_fx{};
     uint8_t *d_fs_scratch = nullptr;    // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
     size_t fs_zero_bytes = 0;
     FsParams fs_proto{};                // scene pointers and counts, filled at upload
@@ -318,6 +322,7 @@ void free_ctx(dg_ctx *c) {
     if (c->d_fe_recs) (void)hipFree(c->d_fe_recs);
     if (c->d_fs_scene) (void)hipFree(c->d_fs_scene);
     if (c->d_fs_scratch) (void)hipFree(c->d_fs_scratch);
+    if (c->d_wall_fx) (void)hipFree(c->d_wall_fx);
     if (c->d_map_layer) (void)hipFree(c->d_map_layer);
     delete c;
 }
@@ -342,7 +347,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
             dg_view v = views[i];
             fill_view_trig(v);
             dg_frame_lists fl;
-            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr);
+            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx);
             if (!rc[(size_t)i]) rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
         }
     });
@@ -411,7 +416,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         FeFrameOut &o = c->fe_out[(size_t)i];
         dg_view v = views[i];
         fill_view_trig(v);
-        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr);
+        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx);
         if (rc[(size_t)i]) return;
         o.parts.swap(A.parts); o.sprites.swap(A.sprites); o.behind.swap(A.behind); o.sky_parts.swap(A.sky_parts);
         o.bin_off.swap(A.bin_off); o.bin_parts.swap(A.bin_parts); o.sbin_off.swap(A.sbin_off); o.sbin_sprites.swap(A.sbin_sprites);
@@ -535,6 +540,16 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
 int upload_fs_scene(dg_ctx *c, const Scene &sc) {
     if (c->d_fs_scene) { (void)hipFree(c->d_fs_scene); c->d_fs_scene = nullptr; }
     if (c->d_fs_scratch) { (void)hipFree(c->d_fs_scratch); c->d_fs_scratch = nullptr; }
+    if (c->d_wall_fx) { (void)hipFree(c->d_wall_fx); c->d_wall_fx = nullptr; }
+    c->fs_fx = FsFx{};
+    if (c->fx.on()) {                                   // the wall effects' tables: only for a scene that has them on (dg_wfx_* read them)
+        const size_t seg_bytes = c->fx.seg.size() * sizeof(FsSegFx), at_lists = align_up(std::max<size_t>(seg_bytes, 16), 256);
+        const size_t list_bytes = c->fx.lists.size() * sizeof(FsAnim);
+        HIP_TRY(hipMalloc((void **)&c->d_wall_fx, at_lists + std::max<size_t>(list_bytes, 16)));
+        if (seg_bytes) HIP_TRY(hipMemcpy(c->d_wall_fx, c->fx.seg.data(), seg_bytes, hipMemcpyHostToDevice));
+        if (list_bytes) HIP_TRY(hipMemcpy(c->d_wall_fx + at_lists, c->fx.lists.data(), list_bytes, hipMemcpyHostToDevice));
+        c->fs_fx = FsFx{reinterpret_cast<const FsSegFx *>(c->d_wall_fx), reinterpret_cast<const FsAnim *>(c->d_wall_fx + at_lists)};
+    }
     struct Piece { const void *src; size_t bytes; size_t at; };
     std::vector<Piece> pieces;
     size_t total = 0;
@@ -599,9 +614,9 @@ void calibrate_host(dg_ctx *c, const dg_view *views, int n) {
     FrameArena &A = *c->arenas[0];
     std::string err;
     const int warm = std::min(4, n), timed = std::min(8, n);
-    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err); }
+    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx); }
     const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err); }
+    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx); }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->ema_host = ms / timed / std::max(1, c->n_threads) * 1.25;     // (the pool does not scale perfectly)
     c->host_samples = std::max(c->host_samples, 2);
@@ -837,7 +852,7 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
         if (s.fs_mode) {                                                                                // the seg walk writes what the column walk reads
             if (c->fs_rows_dirty) HIP_TRY(hipMemsetAsync(c->d_fs_scratch, 0, c->fs_zero_bytes, ks));    // (dg_fs_frame leaves its rows clean)
             c->fs_rows_dirty = true;
-            HIP_TRY(launch_fs(s.FSP, ks, s.ev_start));
+            HIP_TRY(c->fx.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, s.ev_start) : launch_fs(s.FSP, ks, s.ev_start));
             c->fs_rows_dirty = false;
         }
         HIP_TRY(launch_fe(s.FP, ks, s.fs_mode ? nullptr : s.ev_start, s.ev_setup));
@@ -872,7 +887,7 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     fill_view_trig(v);
     dg_frame_lists fl;
     Slot::RedoState redo_state;
-    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state));
+    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state), &c->fx);
     if (!rc) rc = bin_frame(sc, c->fk, fl, bf, err);
     if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
@@ -1012,7 +1027,7 @@ int check_slot(dg_ctx *c, int slot) {
 extern "C" {
 
 const char *dg_last_error(void) { return t_err.c_str(); }
-const char *dg_version(void) { return "doomgpu 0.5 (gfx950; ABI 4)"; }
+const char *dg_version(void) { return "doomgpu 0.6 (gfx950; ABI 4)"; }
 
 int dg_scene_load_wad(const uint8_t *wad, size_t len, const char *map_name, dg_scene **out) {
     if (!wad || !map_name || !out) return set_err(DG_ERR_INVALID, "null argument");
@@ -1057,6 +1072,13 @@ int dg_scene_set_mobj_state(dg_scene *s, int mobj, const char *sprite, uint8_t f
 }
 int dg_scene_texture_id(const dg_scene *s, const char *name) { return (s && name) ? s->sc->texture_id(name) : DG_ERR_INVALID; }
 int dg_scene_flat_id(const dg_scene *s, const char *name, float ts) { return (s && name) ? s->sc->flat_id(name, ts) : DG_ERR_INVALID; }
+int dg_scene_set_wall_effects(dg_scene *s, uint32_t flags) {
+    if (!s) return set_err(DG_ERR_INVALID, "null scene");
+    std::string err;
+    const int rc = s->sc->set_wall_effects(flags, err);
+    return rc ? set_err(rc, err) : DG_OK;
+}
+int dg_scene_wall_texture_id(const dg_scene *s, const char *name, float ts) { return (s && name) ? s->sc->wall_texture_id(name, ts) : DG_ERR_INVALID; }
 int dg_scene_sprite_bitmap_id(const dg_scene *s, const char *sprite, uint8_t frame, uint8_t rot) {
     return (s && sprite) ? s->sc->sprite_bitmap_id(sprite, frame, rot) : DG_ERR_INVALID;
 }
@@ -1073,7 +1095,7 @@ int dg_build_lists(const dg_scene *s, int width, int height, const dg_view *view
     dg_view v = *view;
     fill_view_trig(v);
     std::string err;
-    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err);
+    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err, nullptr, &s->sc->wall_fx);
     return rc ? set_err(rc, err) : DG_OK;
 }
 
@@ -1246,6 +1268,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     HIP_TRY(launch_row_table(c->dscene, c->dk, c->d_row_tab, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     c->scene = &sc;
+    c->fx = sc.wall_fx;                                 // dg_scene_set_wall_effects takes effect here
     c->fe_scene_ok = sky.w >= 256 && sky.h >= 128;    // a smaller sky bitmap is an index panic only when a sky visplane is drawn: host path
     c->uploaded_texels = sc.texel_idx.size();
     c->fs_scene_ok = false;
@@ -1257,6 +1280,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
             if (!said) { said = true; std::fprintf(stderr, "doomgpu: DG_FE_AUTO keeps the per-seg half on the host: no device memory for the seg walk's per-batch rows (%d views x %zu segs)\n", c->cfg.max_batch, sc.segs.size()); }
             if (c->d_fs_scene) { (void)hipFree(c->d_fs_scene); c->d_fs_scene = nullptr; }
             if (c->d_fs_scratch) { (void)hipFree(c->d_fs_scratch); c->d_fs_scratch = nullptr; }
+            if (c->d_wall_fx) { (void)hipFree(c->d_wall_fx); c->d_wall_fx = nullptr; }
             c->fs_scene_ok = false;
             (void)hipGetLastError();
         }

@@ -76,6 +76,10 @@ public:
     // Game::new, BEFORE Device::upload: decode a (sprite, frame) a later state may show (Sprites::new loads every sprite lump eagerly,
     // src/graphics/sprites.rs:26-97).  false: the WAD has no such sprite.
     bool preload_sprite_frame(const char *sprite, uint8_t frame) { return dg_scene_sprite_frame(h_, sprite, frame) >= 0; }
+    // Game::new, BEFORE Device::upload: draw the animated (DG_WALL_ANIMATE) and scrolling (DG_WALL_SCROLL) walls the reference leaves
+    // static.  May decode the animation frames' bitmaps.
+    void set_wall_effects(uint32_t flags) { check(dg_scene_set_wall_effects(h_, flags)); }
+    int wall_texture_id(const char *name, float timestamp) const { return dg_scene_wall_texture_id(h_, name, timestamp); }
     bool sector_floor_height(const Vertex &v, float &out) const { return dg_scene_floor_height_at(h_, v.x, v.y, &out) == 0; }  // bsp.rs:9-44
     dg_scene *handle() const { return h_; }
 private:

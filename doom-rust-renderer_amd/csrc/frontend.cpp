@@ -117,9 +117,10 @@ struct Walker {
     static constexpr uint32_t kCeilPool = 0x80000000u;
 
     const dg_view_state *state = nullptr;   // this view's game-state snapshot (light levels, mobj states) on top of the scene's
+    const WallFx *fx = nullptr;             // the wall effects to draw with (nullptr: none)
 
-    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st = nullptr)
-        : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e) {
+    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const WallFx *wfx)
+        : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e), fx(wfx && wfx->on() ? wfx : nullptr) {
         ppos = V2{v.x, v.y};
         player_height = v.floor_height + kEye;
         apply_state(st);
@@ -359,7 +360,8 @@ struct Walker {
 
     // Segs::process_seg, segs.rs:353-590: fs_seg (fs_core.h) classifies the seg and lists its process_sidedef calls
     void process_seg(size_t seg_index) {
-        const FsSeg &sg = sc.fs_segs[seg_index];
+        FsSeg sg = sc.fs_segs[seg_index];
+        if (fx) fs_seg_fx(sg, fx->seg[seg_index], fx->lists.data(), view.timestamp);
         FsSegOut so;
         const int16_t light = sg.front_sector >= 0 ? sector_light(sg.front_sector) : (int16_t)0;
         const int32_t st = fs_seg(k, sg, sc.fs_sectors.data(), sc.fs_anims.data(), ppos, view.cos_na, view.sin_na, player_height, view.timestamp, light, so);
@@ -600,7 +602,7 @@ struct Walker {
 
 }  // namespace
 
-int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state) {
+int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const WallFx *fx) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.renders.clear(); A.columns.clear(); A.visplanes.clear(); A.plane_tb.clear(); A.order.clear();
     A.recs->clear(); A.floor_tb.clear(); A.ceil_tb.clear();
@@ -610,7 +612,7 @@ int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameA
     A.top_clip.resize((size_t)W);
     A.bottom_clip.resize((size_t)W);
 
-    Walker wk(sc, W, H, view, A, err, state);
+    Walker wk(sc, W, H, view, A, err, state, fx);
     if (wk.status) return wk.status;
     wk.walk_bsp();
     if (wk.status) return wk.status;
@@ -658,11 +660,11 @@ void bin_by_columns(const std::vector<T> &recs, int W, Range range, std::vector<
 }
 }  // namespace
 
-int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state) {
+int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state, const WallFx *fx) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.parts.clear(); A.sprites.clear(); A.behind.clear(); A.sky_parts.clear(); A.behind_words = 0; A.n_sky_slots = 0;
     A.recs->clear();
-    Walker wk(sc, W, H, view, A, err, state);
+    Walker wk(sc, W, H, view, A, err, state, fx);
     if (wk.status) return wk.status;
     wk.parts_mode = true;
     wk.walk_bsp();

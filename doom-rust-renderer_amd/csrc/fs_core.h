@@ -150,6 +150,42 @@ DG_HD int32_t fs_resolve_flat(int32_t flat, int32_t anim, const FsAnim *anims, f
     return a.flat[cyc % (unsigned long long)a.n];
 }
 
+// ---- wall effects (dg_scene_set_wall_effects) ----------------------------------------------------------------------
+// Per seg, what the scene's effect flags change about its sidedef: the scroll count k (linedefs of special 48 whose front sidedef it is;
+// 0 without DG_WALL_SCROLL) and, per texture slot, the live animation list it belongs to (-1: static; always -1 without DG_WALL_ANIMATE).
+// The lists are FsAnim records over bitmap ids.
+struct FsSegFx { uint32_t scroll_k; int8_t anim_mid, anim_low, anim_up; uint8_t pad; };
+static_assert(sizeof(FsSegFx) == 8, "FsSegFx layout");
+// Clock::ticks: Rust's `(timestamp * 35.0f32) as u32` (saturating, NaN -> 0)
+DG_HD uint32_t fs_tics(float timestamp) {
+    const float t = timestamp * 35.0f;
+    return !(t > 0.0f) ? 0u : (t >= 4294967296.0f ? 0xffffffffu : (uint32_t)t);
+}
+// The seg as its sidedef reads at `timestamp`: each animated texture is its list's frame (the flat rule, fs_resolve_flat), and the x
+// offset is moved by k * tics mod 2^16 (vanilla's += FRACUNIT per tic and linedef, in whole texels).
+DG_HD void fs_seg_fx(FsSeg &sg, const FsSegFx &fx, const FsAnim *lists, float timestamp) {
+    sg.tex_mid = fs_resolve_flat(sg.tex_mid, fx.anim_mid, lists, timestamp);
+    sg.tex_low = fs_resolve_flat(sg.tex_low, fx.anim_low, lists, timestamp);
+    sg.tex_up = fs_resolve_flat(sg.tex_up, fx.anim_up, lists, timestamp);
+    if (fx.scroll_k) {
+        const uint32_t d = (fx.scroll_k * fs_tics(timestamp)) & 0xffffu;
+        sg.sd_xoff = (float)wrap_i16(f32_as_i16(sg.sd_xoff) + (int32_t)d);
+    }
+}
+// What fs_seg does to a seg's sidedef before it reads its textures and x offset: FsNoFx nothing (the seg itself — the default, and what
+// every caller without effects compiles to), FsFx the scene's wall effects (a copy of the seg through fs_seg_fx).
+struct FsNoFx {
+    DG_HD const FsSeg &seg(const FsSeg &sg, uint32_t, float) const { return sg; }
+};
+struct FsFx {
+    const FsSegFx *fx; const FsAnim *lists;      // per seg; the live animation lists
+    DG_HD FsSeg seg(const FsSeg &sg, uint32_t si, float timestamp) const {
+        FsSeg o = sg;
+        fs_seg_fx(o, fx[si], lists, timestamp);
+        return o;
+    }
+};
+
 enum : int32_t {                             // outcome of fs_seg / fs_part
     FS_OK = 0,
     FS_SKIP = 1,                             // nothing to record (not an error)
@@ -179,10 +215,11 @@ struct FsSegOut {                            // process_seg up to its process_si
 DG_HD FsCall fs_call(const FsSegOut &o, uint32_t i) { return i == 0u ? o.call[0] : i == 1u ? o.call[1] : i == 2u ? o.call[2] : o.call[3]; }
 
 // Segs::process_seg, segs.rs:353-590, for a viewer at ppos looking along (cos_na, sin_na) = (cos, sin)(-angle).  light: the front
-// sector's CURRENT light level.  Returns FS_OK with 1 .. 5 calls, FS_SKIP, or a failure.
-template <typename K>
+// sector's CURRENT light level.  Returns FS_OK with 1 .. 5 calls, FS_SKIP, or a failure.  fx / si: the wall effects and the seg's index
+// (applied past the clip and back-face tests, so that the segs turned away there never look at them).
+template <typename K, typename Fx = FsNoFx>
 DG_HD int32_t fs_seg(const K &k, const FsSeg &sg, const FsSector *sectors, const FsAnim *anims, V2 ppos, float cos_na, float sin_na, float player_height,
-                     float timestamp, int16_t light, FsSegOut &o) {
+                     float timestamp, int16_t light, FsSegOut &o, const Fx &fx = Fx(), uint32_t si = 0) {
     if (sg.front_sector < 0) return FS_SKIP;
     // (the clip comes first here: it needs the seg's two vertices only and turns away most segs of a map; the sector heights the
     // reference reads before it — segs.rs:364-402 — have no side effects and are read below, by the segs that are left)
@@ -204,6 +241,7 @@ DG_HD int32_t fs_seg(const K &k, const FsSeg &sg, const FsSector *sectors, const
 
     ScreenLine fl = project(k, o.cl.line, floor_height - player_height);
     if (fl.sx > fl.ex) return FS_SKIP;                            // back face
+    const auto &sw = fx.seg(sg, si, timestamp);                   // the sidedef's textures and x offset as drawn at this timestamp
 
     o.floor_flat = fs_resolve_flat(fs.floor_flat, fs.floor_anim, anims, timestamp);
     o.ceil_flat = fs_resolve_flat(fs.ceil_flat, fs.ceil_anim, anims, timestamp);
@@ -216,26 +254,26 @@ DG_HD int32_t fs_seg(const K &k, const FsSeg &sg, const FsSector *sectors, const
         draw_ceiling = false;
     }
     o.seg_offset = sg.seg_offset; o.floor_h = fs.floor_h; o.ceil_h = fs.ceil_h; o.light = light;
-    o.sd_xoff = sg.sd_xoff; o.sd_yoff = sg.sd_yoff;
+    o.sd_xoff = sw.sd_xoff; o.sd_yoff = sg.sd_yoff;
     const uint32_t dc = draw_ceiling ? FEP_DRAW_CEILING : 0u;
     if (!two_sided) {
         const int32_t oy = bottom_unpegged ? f32_as_i32(floor_height - ceiling_height) : 0;
-        o.call[0] = FsCall{floor_height - player_height, ceiling_height - player_height, oy, sg.tex_mid, dc};
+        o.call[0] = FsCall{floor_height - player_height, ceiling_height - player_height, oy, sw.tex_mid, dc};
         o.n_calls = 1; o.call_mask = 1u;
         return FS_OK;
     }
-    o.call[0] = FsCall{floor_height - player_height, ceiling_height - player_height, 0, sg.tex_mid, dc | FEP_ONLY_OCCL};
+    o.call[0] = FsCall{floor_height - player_height, ceiling_height - player_height, 0, sw.tex_mid, dc | FEP_ONLY_OCCL};
     const float mid_floor = has_pb ? pb_h : floor_height, mid_ceil = has_pt ? pt_h : ceiling_height;
-    o.call[1] = FsCall{mid_floor - player_height, mid_ceil - player_height, 0, sg.tex_mid, dc | FEP_TWO_SIDED_MID};
+    o.call[1] = FsCall{mid_floor - player_height, mid_ceil - player_height, 0, sw.tex_mid, dc | FEP_TWO_SIDED_MID};
     o.call_mask = 3u;
     if (has_pb) {
         const int32_t oy = bottom_unpegged ? f32_as_i32(ceiling_height - pb_h) : 0;
-        o.call[2] = FsCall{floor_height - player_height, pb_h - player_height, oy, sg.tex_low, dc | FEP_LOWER};
+        o.call[2] = FsCall{floor_height - player_height, pb_h - player_height, oy, sw.tex_low, dc | FEP_LOWER};
         o.call_mask |= 4u;
     }
     if (has_pt) {
         const int32_t oy = top_unpegged ? 0 : f32_as_i32(pt_h - ceiling_height);
-        o.call[3] = FsCall{pt_h - player_height, ceiling_height - player_height, oy, sg.tex_up, dc | FEP_UPPER};
+        o.call[3] = FsCall{pt_h - player_height, ceiling_height - player_height, oy, sw.tex_up, dc | FEP_UPPER};
         o.call_mask |= 8u;
     }
     o.n_calls = 4;

@@ -180,13 +180,14 @@ DG_HD FsSeg fs_load_seg(const FsSeg *p) {
 #endif
 }
 static_assert(sizeof(FsSeg) == 48, "fs_load_seg");
-DG_HD void fs_seg_lane(const FsParams &P, int f, uint32_t si) {
+// fx: the wall effects (fs_core.h FsFx, the variant kernels of fs_fx_kernels.hip) or none.  dg_fs_frame's fs_ph_emit must see the same.
+template <typename Fx = FsNoFx> DG_HD void fs_seg_lane(const FsParams &P, int f, uint32_t si, const Fx &fx = Fx()) {
     const dg_view &v = P.views[f];
     const uint32_t leaf = P.seg_leaf[si];
     const FsSeg sg = fs_load_seg(P.segs + si);
     FsSegOut so;
     // (the sector's light level is not read here: nothing below looks at it, fs_ph_emit fetches it for the parts that are kept)
-    const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, (int16_t)0, so);
+    const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, (int16_t)0, so, fx, si);
     if (st == FS_SKIP || leaf == 0xffffu) return;                             // (a seg of no reachable leaf is never visited; asked here, after the
                                                                               // clip, so that the seg's record is not fetched behind its leaf's)
     if (st != FS_OK) { fs_flag(P, f, FE_OVF_SEGS); return; }
@@ -394,7 +395,7 @@ DG_HD void fs_ph_kept_place(const FsParams &P, FsShared &S, int f, int lane) {
 }
 // phase 3: kept part o (lane-strided): process_seg + process_sidedef's head again for its (seg, call) — the finished FePart to its
 // place, its clipped line to shared memory (is_behind_vertex), its sky slot recorded
-DG_HD void fs_ph_emit(const FsParams &P, FsShared &S, int f, int lane) {
+template <typename Fx = FsNoFx> DG_HD void fs_ph_emit(const FsParams &P, FsShared &S, int f, int lane, const Fx &fx = Fx()) {
     if (S.fail) return;
     const dg_view &v = P.views[f];
     for (uint32_t o = (uint32_t)lane; o < S.n_parts; o += FS_LANES) {
@@ -402,7 +403,8 @@ DG_HD void fs_ph_emit(const FsParams &P, FsShared &S, int f, int lane) {
         const FsSeg &sg = P.segs[src >> 3];
         FsSegOut so;
         FePart p;
-        const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, P.sector_light[(size_t)f * P.light_stride + (size_t)sg.front_sector], so);
+        const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, P.sector_light[(size_t)f * P.light_stride + (size_t)sg.front_sector], so,
+                                  fx, src >> 3);
         if (st != FS_OK || fs_part(P.k, so, fs_call(so, src & 7u), P.bitmaps, P.flat_sky, v.floor_height, p) != FS_OK) { fs_or_u32(&S.fail, 1u); continue; }   // (cannot happen: dg_fs_segs passed it)
         p.sky_slot = S.kept_sky[o];
         P.parts[(size_t)f * FS_PART_CAP + o] = p;

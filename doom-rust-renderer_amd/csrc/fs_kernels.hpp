@@ -10,5 +10,7 @@ namespace dg {
 // dg_fs_frame leaves it so (the context zeroes it at upload and after a launch that failed half way).
 // start: attached to the first kernel's dispatch.
 hipError_t launch_fs(const FsParams &P, hipStream_t stream, hipEvent_t start = nullptr);
+// The same with the scene's wall effects (fs_fx_kernels.hip: dg_wfx_segs, dg_wfx_frame); X.fx has one entry per seg.
+hipError_t launch_fs_fx(const FsParams &P, const FsFx &X, hipStream_t stream, hipEvent_t start = nullptr);
 
 }  // namespace dg

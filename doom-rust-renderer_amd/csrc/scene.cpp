@@ -255,6 +255,19 @@ int anim_list_of(const std::string &name) {
     return -1;
 }
 
+// Animated wall lists (Doom's p_spec.c animdefs, wall entries, expanded to the frame names the stock IWADs hold between the first and the
+// last name; restated, not checked against an id WAD — DESIGN.md §8b).  A list animates only when every member is a known texture.
+const char *const kWallAnim[13][5] = {
+    {"BLODGR1", "BLODGR2", "BLODGR3", "BLODGR4", nullptr},   {"SLADRIP1", "SLADRIP2", "SLADRIP3", nullptr, nullptr},
+    {"BLODRIP1", "BLODRIP2", "BLODRIP3", "BLODRIP4", nullptr}, {"FIREWALA", "FIREWALB", "FIREWALL", nullptr, nullptr},
+    {"GSTFONT1", "GSTFONT2", "GSTFONT3", nullptr, nullptr},  {"FIRELAV3", "FIRELAVA", nullptr, nullptr, nullptr},
+    {"FIREMAG1", "FIREMAG2", "FIREMAG3", nullptr, nullptr},  {"FIREBLU1", "FIREBLU2", nullptr, nullptr, nullptr},
+    {"ROCKRED1", "ROCKRED2", "ROCKRED3", nullptr, nullptr},  {"BFALL1", "BFALL2", "BFALL3", "BFALL4", nullptr},
+    {"SFALL1", "SFALL2", "SFALL3", "SFALL4", nullptr},       {"WFALL1", "WFALL2", "WFALL3", "WFALL4", nullptr},
+    {"DBRAIN1", "DBRAIN2", "DBRAIN3", "DBRAIN4", nullptr},
+};
+constexpr int kWallScrollSpecial = 48;   // "scroll texture left" (p_spec.c P_UpdateSpecials)
+
 struct SpawnRow { int16_t id; const char *sprite; uint8_t frame, full_bright, is_null; };
 const SpawnRow kSpawn[] = {
 #include "../../data/mobj_spawn_table.inc"
@@ -397,6 +410,68 @@ int Scene::find_or_add_sprite_frame(const std::string &sprite, uint8_t frame, st
         err = ex.what();
         return -1;
     }
+}
+
+// dg_scene_set_wall_effects: the live lists (members decoded through Textures::get, new bitmaps appended), then the per-seg table.
+int Scene::set_wall_effects(uint32_t flags, std::string &err) {
+    if (flags & ~(uint32_t)(DG_WALL_ANIMATE | DG_WALL_SCROLL)) { err = "unknown wall effect bits"; return DG_ERR_INVALID; }
+    WallFx fx;
+    fx.flags = flags;
+    if (flags) {
+        std::vector<int32_t> list_of_bitmap;                                  // bitmap id -> live list (-1: none)
+        if (flags & DG_WALL_ANIMATE) {
+            try {
+                Builder b(*this);
+                for (size_t i = 0; i < bitmap_names.size(); i++) b.bitmap_by_key[bitmap_names[i]] = (int)i;
+                b.load_texture_defs();
+                for (const auto &l : kWallAnim) {
+                    FsAnim a{};
+                    bool live = true;
+                    for (a.n = 0; a.n < 4 && l[a.n]; a.n++) {
+                        a.flat[a.n] = b.texture_bitmap(l[a.n]);
+                        live &= a.flat[a.n] >= 0;
+                    }
+                    if (!live) continue;
+                    for (int k = 0; k < a.n; k++) {
+                        if ((size_t)a.flat[k] >= list_of_bitmap.size()) list_of_bitmap.resize((size_t)a.flat[k] + 1, -1);
+                        list_of_bitmap[(size_t)a.flat[k]] = (int32_t)fx.lists.size();
+                    }
+                    fx.lists.push_back(a);
+                }
+            } catch (const std::exception &ex) {
+                err = ex.what();
+                rebuild_fs_tables();                                          // (bitmaps decoded before the failure stay: ids never move)
+                return DG_ERR_WAD;
+            }
+        }
+        auto list_of = [&](int32_t tex) -> int8_t { return tex >= 0 && (size_t)tex < list_of_bitmap.size() ? (int8_t)list_of_bitmap[(size_t)tex] : (int8_t)-1; };
+        std::vector<uint32_t> k(sidedefs.size(), 0);
+        if (flags & DG_WALL_SCROLL)
+            for (const LinedefRec &d : linedefs)
+                if (d.special == kWallScrollSpecial && d.front >= 0) k[(size_t)d.front]++;
+        fx.seg.resize(segs.size());
+        for (size_t i = 0; i < segs.size(); i++) {
+            const LinedefRec &ld = linedefs[(size_t)segs[i].linedef];
+            const int sd = segs[i].direction ? ld.back : ld.front;            // the seg's own sidedef (fs_segs: segs.rs:358-362)
+            FsSegFx &f = fx.seg[i];
+            f = FsSegFx{0u, -1, -1, -1, 0};
+            if (sd < 0) continue;
+            const SidedefRec &r = sidedefs[(size_t)sd];
+            f.scroll_k = k[(size_t)sd];
+            f.anim_mid = list_of(r.middle); f.anim_low = list_of(r.lower); f.anim_up = list_of(r.upper);
+        }
+    }
+    wall_fx = std::move(fx);
+    rebuild_fs_tables();
+    return DG_OK;
+}
+int Scene::wall_texture_id(const std::string &name, float timestamp) const {
+    const int id = texture_id(name);
+    if (id < 0 || !(wall_fx.flags & DG_WALL_ANIMATE)) return id;
+    for (const FsAnim &a : wall_fx.lists)
+        for (int k = 0; k < a.n; k++)
+            if (a.flat[k] == id) return fs_resolve_flat(id, (int32_t)(&a - wall_fx.lists.data()), wall_fx.lists.data(), timestamp);
+    return id;
 }
 
 void Scene::rebuild_fs_tables() {
@@ -573,7 +648,7 @@ Scene *load_scene_from_wad(const uint8_t *bytes, size_t len, const char *map_nam
                 size_t o = l.off + i * 14;
                 LinedefRec &d = sc->linedefs[i];
                 int16_t v1 = w.i16(o), v2 = w.i16(o + 2), f = w.i16(o + 10), bk = w.i16(o + 12);
-                d.flags = w.i16(o + 4); d.pad = 0;
+                d.flags = w.i16(o + 4); d.special = w.i16(o + 6);
                 if (v1 < 0 || v2 < 0 || (size_t)v1 >= sc->vx.size() || (size_t)v2 >= sc->vx.size()) throw LoadError("linedef references a missing vertex");
                 if ((f != -1 && (f < 0 || (size_t)f >= sc->sidedefs.size())) || (bk != -1 && (bk < 0 || (size_t)bk >= sc->sidedefs.size())))
                     throw LoadError("linedef references a missing sidedef");

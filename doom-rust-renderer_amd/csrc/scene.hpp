@@ -37,7 +37,7 @@ struct SidedefRec {
     int32_t upper, lower, middle;   // bitmap id, TEX_NONE for "-", TEX_UNKNOWN if Textures::get would panic
     int32_t sector;
 };
-struct LinedefRec { int32_t v1, v2; int16_t flags; int16_t pad; int32_t front, back; };
+struct LinedefRec { int32_t v1, v2; int16_t flags; int16_t special; int32_t front, back; };   // special: special_type (linedefs.rs), read by the wall scroll
 struct SegRec { int32_t v1, v2, linedef; int16_t offset; uint8_t direction; uint8_t pad; };
 struct SubSectorRec { int32_t first, count; };
 struct NodeRec {
@@ -55,6 +55,15 @@ struct MapObjectRec {                                            // map_objects.
     int32_t sector;         // get_sector_from_vertex(position) — position is immutable in the reference
 };
 struct AnimList { int32_t n; int32_t flat[4]; };
+
+// The wall effects of a scene (dg_scene_set_wall_effects) as fs_core.h applies them: flags, and per seg its scroll count and
+// animation lists (fs_seg_fx), the lists over bitmap ids.  flags 0: both tables empty, nothing changes.  A dg_ctx keeps the copy it uploaded.
+struct WallFx {
+    uint32_t flags = 0;
+    std::vector<FsSegFx> seg;
+    std::vector<FsAnim> lists;
+    bool on() const { return flags != 0; }
+};
 
 enum : int32_t { TEX_NONE = -1, TEX_UNKNOWN = -2, FLAT_MISSING = -2 };
 
@@ -88,6 +97,7 @@ struct Scene {
     std::vector<std::string> sprite_frame_keys;     // "SPRT<frame>"
     int32_t sky_bitmap = TEX_UNKNOWN;
     uint64_t revision = 0;                          // bumped by the mutable-state setters
+    WallFx wall_fx;                                 // as last set by set_wall_effects (the host walker of dg_build_lists reads it)
     // The per-seg / per-sprite inputs of fs_core.h, flattened (rebuild_fs_tables: at load and whenever bitmaps or sprite frames are added):
     // what the host walker reads per seg and what dg_upload_scene copies to the GPU for DG_FE_DEVICE_SEGS.
     std::vector<FsSeg> fs_segs;                     // one per seg
@@ -111,6 +121,8 @@ struct Scene {
     int sprite_bitmap_id(const std::string &sprite, uint8_t frame, uint8_t rotation) const;
     int sector_from_vertex(float x, float y) const;                              // renderer/bsp.rs:9-44
     int find_or_add_sprite_frame(const std::string &sprite, uint8_t frame, std::string &err);
+    int set_wall_effects(uint32_t flags, std::string &err);                    // DG_OK, or DG_ERR_INVALID / DG_ERR_WAD with err
+    int wall_texture_id(const std::string &name, float timestamp) const;       // texture_id after animation (DG_WALL_ANIMATE)
 };
 
 // The lines of one 2-D map frame (Game::render with viewing_map, src/game.rs:229-308) in draw order: every linedef without DONTDRAW, then

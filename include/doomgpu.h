@@ -63,6 +63,21 @@ int dg_scene_set_mobj_state(dg_scene *s, int mobj, const char *sprite, uint8_t f
 /* A state change may decode sprite bitmaps the GPU copy does not hold yet: submissions then fail with DG_ERR_INVALID until
  * dg_upload_scene is called again (light levels never need a re-upload). */
 
+/* Wall effects (opt-in per scene; the reference draws these walls static — DESIGN.md section 8b).  Both are functions of the view's
+ * timestamp, nothing else:
+ *   DG_WALL_ANIMATE  a sidedef texture (upper, lower, middle, masked middles too) that belongs to a live animated-wall list (SLADRIP1-3,
+ *                    BFALL1-4, ...; live: every member is a known texture) draws list[c % n], c = the saturating u64 of timestamp * 3.0f
+ *                    (NaN or <= 0: 0) — the animated-flat rule; the phase does not depend on which member the map names.
+ *   DG_WALL_SCROLL   a sidedef that is the front of k linedefs of special 48 has its x offset moved by (u32)(k * tics) mod 65536,
+ *                    tics = (timestamp * 35.0f) as u32 (saturating, NaN: 0), wrapped to i16.
+ * Every front end gives the same pixels; the 2-D map view and dg_draw_lists ignore the flags. */
+#define DG_WALL_ANIMATE 1u
+#define DG_WALL_SCROLL  2u
+/* Takes effect at the next dg_upload_scene; dg_build_lists sees it at once.  May decode bitmaps.  Unknown bits: DG_ERR_INVALID. */
+int dg_scene_set_wall_effects(dg_scene *s, uint32_t flags);
+/* The dg_scene_texture_id of `name`, after animation at `timestamp` when DG_WALL_ANIMATE is set (the dg_scene_flat_id twin, for list-path callers). */
+int dg_scene_wall_texture_id(const dg_scene *s, const char *name, float timestamp);
+
 /* ---- viewpoint (reference: `Player`, src/game.rs:40-45, + Renderer::new's timestamp) ------------------------ */
 typedef struct dg_view {
     float x, y;          /* player.position */
@@ -70,7 +85,7 @@ typedef struct dg_view {
     float floor_height;  /* player.floor_height */
     float cos_a, sin_a;  /* f32::cos/sin(angle)   as the host libm returns them (src/map/vertexes.rs:20-25) */
     float cos_na, sin_na;/* f32::cos/sin(-angle) */
-    float timestamp;     /* clock.timestamp: selects the animated-flat frame (src/graphics/flats.rs:103-111) */
+    float timestamp;     /* clock.timestamp: selects the animated-flat frame (src/graphics/flats.rs:103-111) and the wall effects' frame */
     int32_t trig_valid;  /* 0: the library fills the four trig fields with cosf/sinf */
 } dg_view;
 

@@ -46,6 +46,8 @@ pub struct dg_frame_lists {
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct dg_map_line { pub x0: i32, pub y0: i32, pub x1: i32, pub y1: i32, pub rgb: u32 }
 pub const DG_FE_MAP: i32 = 4;              // dg_timing.front_end of a map submission
+pub const DG_WALL_ANIMATE: u32 = 1;         // dg_scene_set_wall_effects flags
+pub const DG_WALL_SCROLL: u32 = 2;
 
 extern "C" {
     pub fn dg_scene_load_wad(wad: *const u8, len: usize, map_name: *const c_char, out: *mut *mut dg_scene) -> c_int;
@@ -56,6 +58,8 @@ extern "C" {
     pub fn dg_scene_set_mobj_state(s: *mut dg_scene, mobj: c_int, sprite: *const c_char, frame: u8, full_bright: c_int) -> c_int;
     pub fn dg_scene_texture_id(s: *const dg_scene, name: *const c_char) -> c_int;
     pub fn dg_scene_flat_id(s: *const dg_scene, name: *const c_char, timestamp: f32) -> c_int;
+    pub fn dg_scene_set_wall_effects(s: *mut dg_scene, flags: u32) -> c_int;
+    pub fn dg_scene_wall_texture_id(s: *const dg_scene, name: *const c_char, timestamp: f32) -> c_int;
     pub fn dg_scene_sprite_bitmap_id(s: *const dg_scene, sprite: *const c_char, frame: u8, rotation: u8) -> c_int;
     pub fn dg_scene_sprite_frame(s: *mut dg_scene, sprite: *const c_char, frame: u8) -> c_int;
     pub fn dg_scene_sector_count(s: *const dg_scene) -> c_int;
@@ -105,6 +109,13 @@ impl<'a> GpuRenderer<'a> {
 /// `Game::new`, BEFORE dg_upload_scene: decode every (sprite, frame) a state can show — what `Sprites::new` does eagerly
 /// (src/graphics/sprites.rs:26-97) — so that no later `sync_state` meets a bitmap the GPU does not hold.  Sprites the WAD lacks
 /// (shareware IWADs) are skipped exactly like `Sprites::get_picture` would only fail when such a state is drawn.
+/// Game::new, before dg_upload_scene: draw animated (SLADRIP, BFALL, ...) and scrolling (linedef special 48) walls, which the
+/// reference renders static.  `flags`: DG_WALL_ANIMATE | DG_WALL_SCROLL, or 0.
+pub fn set_wall_effects(scene: *mut dg_scene, flags: u32) {
+    let rc = unsafe { dg_scene_set_wall_effects(scene, flags) };
+    if rc < 0 { panic!("dg_scene_set_wall_effects: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
+}
+
 pub fn preload_sprite_frames(scene: *mut dg_scene) {
     for st in crate::info::STATES.iter() {
         let name = CString::new(format!("{:?}", st.sprite)).unwrap();          // the lump prefix Sprites::new matches on (sprites.rs:30)
