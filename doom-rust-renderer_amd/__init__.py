@@ -24,6 +24,7 @@ DG_OK, DG_ERR_INVALID, DG_ERR_NO_DEVICE, DG_ERR_HIP, DG_ERR_WAD, DG_ERR_RENDER, 
 DG_FE_AUTO, DG_FE_HOST, DG_FE_DEVICE, DG_FE_DEVICE_SEGS = 0, 1, 2, 3
 DG_FE_MAP = 4   # dg_timing.front_end of a 2-D map submission
 DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
+DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
 
 
 class DoomGpuError(RuntimeError):
@@ -143,6 +144,8 @@ _SIGNATURES = {
     "dg_scene_flat_id": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_float]),
     "dg_scene_set_wall_effects": (ctypes.c_int, [_P, ctypes.c_uint32]),
     "dg_scene_wall_texture_id": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_float]),
+    "dg_scene_set_light_effects": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint64]),
+    "dg_scene_sector_lights_at": (ctypes.c_int, [_P, ctypes.c_float, ctypes.POINTER(ctypes.c_int16), ctypes.c_int]),
     "dg_scene_sprite_bitmap_id": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_uint8]),
     "dg_scene_bitmap_size": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "dg_draw_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P]),
@@ -242,6 +245,18 @@ class Scene:
     def wall_texture_id(self, name: str, timestamp: float = 0.0) -> int:
         """dg_scene_wall_texture_id: the texture's bitmap id after wall animation at `timestamp` (negative: unknown)."""
         return lib().dg_scene_wall_texture_id(self._h, name.encode(), timestamp)
+
+    def set_light_effects(self, flags: int, seed: int = 0):
+        """dg_scene_set_light_effects: DG_LIGHT_THINKERS or 0, and the seed of the random effects' stream (takes effect for a Context
+        at Context.upload_scene; build_lists and sector_lights_at see it at once)."""
+        _check(lib().dg_scene_set_light_effects(self._h, flags, seed & 0xFFFFFFFFFFFFFFFF))
+
+    def sector_lights_at(self, timestamp: float):
+        """dg_scene_sector_lights_at: every sector's level at `timestamp` as drawn with no view state (numpy int16 array)."""
+        n = lib().dg_scene_sector_count(self._h)
+        out = np.zeros(max(n, 0), dtype=np.int16)
+        _check(lib().dg_scene_sector_lights_at(self._h, timestamp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), n))
+        return out
 
     def build_lists(self, W: int, H: int, view: DgView) -> DgFrameLists:
         fl = DgFrameLists()

@@ -33,6 +33,7 @@
 #include "binner.hpp"
 #include "fe_kernels.hpp"
 #include "fs_kernels.hpp"
+#include "light_fx_kernels.hpp"
 #include "frontend.hpp"
 #include "kernels.hpp"
 #include "map_kernels.hpp"
@@ -141,6 +142,7 @@ struct Slot {
     uint32_t *d_flags = nullptr;                // [F] overflow flags the walk's kernels OR into; sits in front of d_events (one memset clears both)
     FeParams FP{};
     FsParams FSP{};               // DG_FE_DEVICE_SEGS: the device seg walk in front of the column walk
+    LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
     bool fs_mode = false;         // the last submission's per-seg half ran on the GPU too
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
     bool fe_mode = false;         // the last submission went through the device column walk
@@ -169,10 +171,15 @@ struct Slot {
     // The game state frame i of the last submission was rendered with, for the host walker: nullptr = the scene as it is (unchanged since the
     // submission, no per-view snapshot); else the submit-time scene state with the view's own entries on top (later entries win).
     struct RedoState { std::vector<dg_sector_light> lights; std::vector<dg_mobj_state> mobjs; dg_view_state st{}; };
-    const dg_view_state *state_for_redo(const Scene &sc, int i, RedoState &tmp) const {
+    // lfx: the light effects the frame was drawn with — their sectors keep the effect's level, so the snapshot does not list them.
+    const dg_view_state *state_for_redo(const Scene &sc, int i, RedoState &tmp, const LightFx &lfx) const {
         const dg_view_state *own = states.empty() ? nullptr : &states[(size_t)i];
         if (snap_scene != &sc || snap_rev == sc.revision) return own;
-        tmp.lights = snap_lights; tmp.mobjs = snap_mobjs;
+        tmp.lights.clear();
+        const bool fx_on = lfx.on() && lfx.rec_of.size() == snap_lights.size();
+        for (const dg_sector_light &l : snap_lights)
+            if (!fx_on || lfx.rec_of[(size_t)l.sector] < 0) tmp.lights.push_back(l);
+        tmp.mobjs = snap_mobjs;
         if (own) { tmp.lights.insert(tmp.lights.end(), own->lights, own->lights + own->n_lights); tmp.mobjs.insert(tmp.mobjs.end(), own->mobjs, own->mobjs + own->n_mobjs); }
         tmp.st = dg_view_state{tmp.lights.data(), (uint32_t)tmp.lights.size(), tmp.mobjs.data(), (uint32_t)tmp.mobjs.size()};
         return &tmp.st;
@@ -241,6 +248,10 @@ struct dg_ctx {
     WallFx fx;
     uint8_t *d_wall_fx = nullptr;       // FsSegFx per seg | the live animation lists (only while fx.on() and the seg walk is uploaded)
     FsFx fs_fx{};
+    // light effects: the scene's LightFx as of dg_upload_scene (likewise), and for the seg walk its records, tables and per-sector map
+    LightFx lfx;
+    uint8_t *d_light_fx = nullptr;      // LfxRec per effect sector | rec_of per sector | tables (only while lfx.on() and the seg walk is uploaded)
+    LfxRows lfx_proto{};                // its pointers and the seed, filled at upload
     uint8_t *d_fs_scratch = nullptr;    // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
     size_t fs_zero_bytes = 0;
     FsParams fs_proto{};                // scene pointers and counts, filled at upload
@@ -323,6 +334,7 @@ void free_ctx(dg_ctx *c) {
     if (c->d_fs_scene) (void)hipFree(c->d_fs_scene);
     if (c->d_fs_scratch) (void)hipFree(c->d_fs_scratch);
     if (c->d_wall_fx) (void)hipFree(c->d_wall_fx);
+    if (c->d_light_fx) (void)hipFree(c->d_light_fx);
     if (c->d_map_layer) (void)hipFree(c->d_map_layer);
     delete c;
 }
@@ -347,7 +359,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
             dg_view v = views[i];
             fill_view_trig(v);
             dg_frame_lists fl;
-            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx);
+            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, &c->lfx);
             if (!rc[(size_t)i]) rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
         }
     });
@@ -416,7 +428,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         FeFrameOut &o = c->fe_out[(size_t)i];
         dg_view v = views[i];
         fill_view_trig(v);
-        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx);
+        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, &c->lfx);
         if (rc[(size_t)i]) return;
         o.parts.swap(A.parts); o.sprites.swap(A.sprites); o.behind.swap(A.behind); o.sky_parts.swap(A.sky_parts);
         o.bin_off.swap(A.bin_off); o.bin_parts.swap(A.bin_parts); o.sbin_off.swap(A.sbin_off); o.sbin_sprites.swap(A.sbin_sprites);
@@ -550,6 +562,21 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
         if (list_bytes) HIP_TRY(hipMemcpy(c->d_wall_fx + at_lists, c->fx.lists.data(), list_bytes, hipMemcpyHostToDevice));
         c->fs_fx = FsFx{reinterpret_cast<const FsSegFx *>(c->d_wall_fx), reinterpret_cast<const FsAnim *>(c->d_wall_fx + at_lists)};
     }
+    if (c->d_light_fx) { (void)hipFree(c->d_light_fx); c->d_light_fx = nullptr; }
+    c->lfx_proto = LfxRows{};
+    if (c->lfx.on()) {                                  // the light effects' records and tables: only for a scene that has them on (dg_light_rows reads them)
+        const size_t rec_bytes = c->lfx.recs.size() * sizeof(LfxRec), map_bytes = c->lfx.rec_of.size() * 4, tab_bytes = c->lfx.tab.size() * 4;
+        const size_t at_map = align_up(rec_bytes, 256), at_tab = align_up(at_map + map_bytes, 256);
+        HIP_TRY(hipMalloc((void **)&c->d_light_fx, at_tab + std::max<size_t>(tab_bytes, 16)));
+        HIP_TRY(hipMemcpy(c->d_light_fx, c->lfx.recs.data(), rec_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_light_fx + at_map, c->lfx.rec_of.data(), map_bytes, hipMemcpyHostToDevice));
+        if (tab_bytes) HIP_TRY(hipMemcpy(c->d_light_fx + at_tab, c->lfx.tab.data(), tab_bytes, hipMemcpyHostToDevice));
+        c->lfx_proto.recs = reinterpret_cast<const LfxRec *>(c->d_light_fx);
+        c->lfx_proto.rec_of = reinterpret_cast<const int32_t *>(c->d_light_fx + at_map);
+        c->lfx_proto.tab = reinterpret_cast<const uint32_t *>(c->d_light_fx + at_tab);
+        c->lfx_proto.seed = c->lfx.seed;
+        c->lfx_proto.n_sectors = (uint32_t)c->lfx.rec_of.size();
+    }
     struct Piece { const void *src; size_t bytes; size_t at; };
     std::vector<Piece> pieces;
     size_t total = 0;
@@ -614,9 +641,9 @@ void calibrate_host(dg_ctx *c, const dg_view *views, int n) {
     FrameArena &A = *c->arenas[0];
     std::string err;
     const int warm = std::min(4, n), timed = std::min(8, n);
-    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx); }
+    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx, &c->lfx); }
     const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx); }
+    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx, &c->lfx); }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->ema_host = ms / timed / std::max(1, c->n_threads) * 1.25;     // (the pool does not scale perfectly)
     c->host_samples = std::max(c->host_samples, 2);
@@ -658,9 +685,15 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     // entries on top — instead of one copy for the batch; the kernels index them with a per-frame stride
     const size_t state_frames = states ? (size_t)n : 1;
     const size_t off_mstate = align_up(off_lights + state_frames * sc.sectors.size() * 2, 256);
-    const size_t upload = align_up(off_mstate + state_frames * sc.mobjs.size() * 4, 256);
+    // light effects (dg_light_rows): with view states, per frame a mask of the sectors its state overrides (the rows above are then
+    // completed in place); without, the kernel writes the per-view rows from the one base row into the device-written part
+    const bool lfx = c->lfx.on() && c->lfx_proto.recs && c->lfx.rec_of.size() == sc.sectors.size();
+    const size_t mask_words = (sc.sectors.size() + 31) / 32;
+    const size_t off_lmask = align_up(off_mstate + state_frames * sc.mobjs.size() * 4, 256);
+    const size_t upload = align_up(off_lmask + (lfx && states ? (size_t)n * mask_words * 4 : 0), 256);
     // device-written part
-    const size_t off_ff = upload;
+    const size_t off_lrows = upload;
+    const size_t off_ff = align_up(off_lrows + (lfx && !states ? (size_t)n * sc.sectors.size() * 2 : 0), 256);
     const size_t off_parts = align_up(off_ff + (size_t)n * sizeof(FeFrame), 256);
     const size_t off_sprites = align_up(off_parts + (size_t)n * FS_PART_CAP * sizeof(FePart), 256);
     const size_t off_behind = align_up(off_sprites + (size_t)n * c->fs_proto.sprite_stride * sizeof(FeSprite), 256);
@@ -682,6 +715,7 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     });
     int16_t *lights = reinterpret_cast<int16_t *>(s.h_fe + off_lights);
     int32_t *mstate = reinterpret_cast<int32_t *>(s.h_fe + off_mstate);
+    uint32_t *lmask = reinterpret_cast<uint32_t *>(s.h_fe + off_lmask);
     std::atomic<int> bad_state{-1};
     c->pool->parallel_for((int)state_frames, [&](int i, int) {
         int16_t *l = lights + (size_t)i * sc.sectors.size();
@@ -689,10 +723,13 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         for (size_t k = 0; k < sc.sectors.size(); k++) l[k] = sc.sectors[k].light;
         for (size_t k = 0; k < sc.mobjs.size(); k++) m[k] = sc.mobjs[k].sprite_frame < 0 ? -1 : sc.mobjs[k].sprite_frame * 2 + (sc.mobjs[k].full_bright ? 1 : 0);
         if (!states) return;
+        uint32_t *lm = lfx ? lmask + (size_t)i * mask_words : nullptr;
+        if (lm) std::memset(lm, 0, mask_words * 4);
         const dg_view_state &st = states[i];                        // the same rules as the host walker's (frontend.cpp: Walker::apply_state): later entries win
         for (uint32_t k = 0; k < st.n_lights; k++) {
             if (st.lights[k].sector < 0 || (size_t)st.lights[k].sector >= sc.sectors.size()) { bad_state = i; continue; }
             l[(size_t)st.lights[k].sector] = (int16_t)st.lights[k].light_level;
+            if (lm) lm[(size_t)st.lights[k].sector / 32] |= 1u << ((uint32_t)st.lights[k].sector % 32);
         }
         for (uint32_t k = 0; k < st.n_mobjs; k++) {
             const dg_mobj_state &ms = st.mobjs[k];
@@ -708,6 +745,19 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     Q.sector_light = reinterpret_cast<const int16_t *>(s.d_fe + off_lights);
     Q.mobj_state = reinterpret_cast<const int32_t *>(s.d_fe + off_mstate);
     Q.light_stride = states ? (uint32_t)sc.sectors.size() : 0u;
+    s.LR = LfxRows{};
+    if (lfx) {                                              // dg_light_rows completes the rows the seg walk reads
+        s.LR = c->lfx_proto;
+        s.LR.views = reinterpret_cast<const dg_view *>(s.d_fe + off_views);
+        s.LR.base = Q.sector_light;
+        s.LR.base_stride = Q.light_stride;
+        s.LR.mask = states ? reinterpret_cast<const uint32_t *>(s.d_fe + off_lmask) : nullptr;
+        s.LR.mask_words = (uint32_t)mask_words;
+        s.LR.out = states ? reinterpret_cast<int16_t *>(s.d_fe + off_lights) : reinterpret_cast<int16_t *>(s.d_fe + off_lrows);
+        s.LR.n_frames = n;
+        Q.sector_light = s.LR.out;
+        Q.light_stride = (uint32_t)sc.sectors.size();
+    }
     Q.mstate_stride = states ? (uint32_t)sc.mobjs.size() : 0u;
     Q.views = reinterpret_cast<const dg_view *>(s.d_fe + off_views);
     Q.n_frames = n;
@@ -852,7 +902,9 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
         if (s.fs_mode) {                                                                                // the seg walk writes what the column walk reads
             if (c->fs_rows_dirty) HIP_TRY(hipMemsetAsync(c->d_fs_scratch, 0, c->fs_zero_bytes, ks));    // (dg_fs_frame leaves its rows clean)
             c->fs_rows_dirty = true;
-            HIP_TRY(c->fx.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, s.ev_start) : launch_fs(s.FSP, ks, s.ev_start));
+            hipEvent_t fs_start = s.ev_start;
+            if (s.LR.n_frames > 0) { HIP_TRY(launch_light_rows(s.LR, ks, s.ev_start)); fs_start = nullptr; }   // the rows dg_fs_* read
+            HIP_TRY(c->fx.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
             c->fs_rows_dirty = false;
         }
         HIP_TRY(launch_fe(s.FP, ks, s.fs_mode ? nullptr : s.ev_start, s.ev_setup));
@@ -887,7 +939,7 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     fill_view_trig(v);
     dg_frame_lists fl;
     Slot::RedoState redo_state;
-    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state), &c->fx);
+    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->lfx), &c->fx, &c->lfx);
     if (!rc) rc = bin_frame(sc, c->fk, fl, bf, err);
     if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
@@ -956,7 +1008,7 @@ int settle_slot(dg_ctx *c, Slot &s) {
             std::vector<dg_view_state> sts;
             bool any_state = false;
             for (size_t i = 0; i < views.size(); i++) {
-                const dg_view_state *st = s.state_for_redo(*c->scene, (int)i, redo_states[i]);
+                const dg_view_state *st = s.state_for_redo(*c->scene, (int)i, redo_states[i], c->lfx);
                 any_state |= st != nullptr;
                 sts.push_back(st ? *st : dg_view_state{nullptr, 0, nullptr, 0});
             }
@@ -1079,6 +1131,22 @@ int dg_scene_set_wall_effects(dg_scene *s, uint32_t flags) {
     return rc ? set_err(rc, err) : DG_OK;
 }
 int dg_scene_wall_texture_id(const dg_scene *s, const char *name, float ts) { return (s && name) ? s->sc->wall_texture_id(name, ts) : DG_ERR_INVALID; }
+int dg_scene_set_light_effects(dg_scene *s, uint32_t flags, uint64_t seed) {
+    if (!s) return set_err(DG_ERR_INVALID, "null scene");
+    std::string err;
+    const int rc = s->sc->set_light_effects(flags, seed, err);
+    return rc ? set_err(rc, err) : DG_OK;
+}
+int dg_scene_sector_lights_at(const dg_scene *s, float ts, int16_t *out, int n) {
+    if (!s || !out) return set_err(DG_ERR_INVALID, "null argument");
+    const Scene &sc = *s->sc;
+    if (n < 0 || (size_t)n != sc.sectors.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_sector_count");
+    for (size_t i = 0; i < sc.sectors.size(); i++) out[i] = sc.sectors[i].light;
+    const LightFx &fx = sc.light_fx;
+    if (fx.on())
+        for (size_t r = 0; r < fx.recs.size(); r++) out[fx.recs[r].sector] = fx.level(r, ts);
+    return DG_OK;
+}
 int dg_scene_sprite_bitmap_id(const dg_scene *s, const char *sprite, uint8_t frame, uint8_t rot) {
     return (s && sprite) ? s->sc->sprite_bitmap_id(sprite, frame, rot) : DG_ERR_INVALID;
 }
@@ -1095,7 +1163,7 @@ int dg_build_lists(const dg_scene *s, int width, int height, const dg_view *view
     dg_view v = *view;
     fill_view_trig(v);
     std::string err;
-    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err, nullptr, &s->sc->wall_fx);
+    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err, nullptr, &s->sc->wall_fx, &s->sc->light_fx);
     return rc ? set_err(rc, err) : DG_OK;
 }
 
@@ -1269,6 +1337,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     HIP_TRY(hipDeviceSynchronize());
     c->scene = &sc;
     c->fx = sc.wall_fx;                                 // dg_scene_set_wall_effects takes effect here
+    c->lfx = sc.light_fx;                               // dg_scene_set_light_effects too
     c->fe_scene_ok = sky.w >= 256 && sky.h >= 128;    // a smaller sky bitmap is an index panic only when a sky visplane is drawn: host path
     c->uploaded_texels = sc.texel_idx.size();
     c->fs_scene_ok = false;
@@ -1281,6 +1350,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
             if (c->d_fs_scene) { (void)hipFree(c->d_fs_scene); c->d_fs_scene = nullptr; }
             if (c->d_fs_scratch) { (void)hipFree(c->d_fs_scratch); c->d_fs_scratch = nullptr; }
             if (c->d_wall_fx) { (void)hipFree(c->d_wall_fx); c->d_wall_fx = nullptr; }
+            if (c->d_light_fx) { (void)hipFree(c->d_light_fx); c->d_light_fx = nullptr; }
             c->fs_scene_ok = false;
             (void)hipGetLastError();
         }

@@ -80,6 +80,14 @@ public:
     // static.  May decode the animation frames' bitmaps.
     void set_wall_effects(uint32_t flags) { check(dg_scene_set_wall_effects(h_, flags)); }
     int wall_texture_id(const char *name, float timestamp) const { return dg_scene_wall_texture_id(h_, name, timestamp); }
+    // Game::new, BEFORE Device::upload: draw the sector light effects (DG_LIGHT_THINKERS: lights.rs' thinkers as functions of the view's
+    // timestamp, random ones from `seed`).  A game that runs the thinkers itself leaves this off.
+    void set_light_effects(uint32_t flags, uint64_t seed) { check(dg_scene_set_light_effects(h_, flags, seed)); }
+    // Every sector's level at `timestamp` as drawn with no view state (for list-path callers); out.size() sectors.
+    void sector_lights_at(float timestamp, std::vector<int16_t> &out) const {
+        out.resize((size_t)dg_scene_sector_count(h_));
+        check(dg_scene_sector_lights_at(h_, timestamp, out.data(), (int)out.size()));
+    }
     bool sector_floor_height(const Vertex &v, float &out) const { return dg_scene_floor_height_at(h_, v.x, v.y, &out) == 0; }  // bsp.rs:9-44
     dg_scene *handle() const { return h_; }
 private:

@@ -465,6 +465,71 @@ int Scene::set_wall_effects(uint32_t flags, std::string &err) {
     rebuild_fs_tables();
     return DG_OK;
 }
+// dg_scene_set_light_effects: init_sector_thinkers (thinkers.rs:14-76) on the map as loaded — the WAD's levels, whatever
+// set_sector_light has done since — with its ThreadRng draws replaced by lfx_draw; the flash and fire tables follow light_fx.h.
+int Scene::set_light_effects(uint32_t flags, uint64_t seed, std::string &err) {
+    if (flags & ~(uint32_t)DG_LIGHT_THINKERS) { err = "unknown light effect bits"; return DG_ERR_INVALID; }
+    LightFx fx;
+    fx.flags = flags; fx.seed = seed;
+    if (flags) {
+        auto min_surrounding = [&](size_t sector, int16_t mx) {          // find_min_surrounding_light, lights.rs:16-42
+            int16_t lv = mx;
+            for (const LinedefRec &d : linedefs) {
+                if (d.front < 0 || d.back < 0) continue;
+                const size_t fs = (size_t)sidedefs[(size_t)d.front].sector, bs = (size_t)sidedefs[(size_t)d.back].sector;
+                if (fs == sector) lv = std::min(lv, wad_light[bs]);
+                if (bs == sector) lv = std::min(lv, wad_light[fs]);
+            }
+            return lv;
+        };
+        fx.rec_of.assign(sectors.size(), -1);
+        for (size_t i = 0; i < sectors.size(); i++) {
+            const int16_t t = sectors[i].special;
+            if (t != 1 && t != 2 && t != 3 && t != 4 && t != 8 && t != 12 && t != 13 && t != 17) continue;
+            const int16_t mx = wad_light[i], surr = min_surrounding(i, mx);
+            LfxRec r{(uint32_t)i, (uint8_t)t, 0, 0, surr, mx, 0};
+            if (t == LFX_FIRE) r.min = lfx_wrap((uint32_t)(int32_t)surr + 16u);
+            if (t == 2 || t == 3 || t == 4 || t == 12 || t == 13) {
+                r.min = surr == mx ? (int16_t)0 : surr;
+                r.dark = (t == 3 || t == 12) ? 35 : 15;           // SLOW_DARK / FAST_DARK
+                r.c0 = (t == 12 || t == 13) ? 1 : (uint16_t)(1u + lfx_draw(seed, 2u, (uint32_t)i, 0u, 8u));
+            }
+            if (t == LFX_FLASH) {
+                r.tab = (uint32_t)fx.tab.size();
+                fx.tab.resize(fx.tab.size() + LFX_FLASH_WORDS);
+                uint32_t *S = fx.tab.data() + r.tab, sum = 0;
+                S[0] = 0;
+                for (uint32_t k = 0; k < LFX_PERIOD_DRAWS; k++) {
+                    sum += 1u + lfx_draw(seed, 1u, (uint32_t)i, k, (k & 1u) ? 7u : 64u);
+                    if ((k + 1) % LFX_CHECKPOINT == 0) S[(k + 1) / LFX_CHECKPOINT] = sum;
+                }
+            }
+            if (t == LFX_FIRE) {
+                r.tab = (uint32_t)fx.tab.size();
+                fx.tab.resize(fx.tab.size() + LFX_FIRE_WORDS, 0u);
+                uint8_t *b = reinterpret_cast<uint8_t *>(fx.tab.data() + r.tab), *trans = b, *pmap = b + 20, *cp = b + 25;
+                for (uint32_t x = 0; x < 5; x++)
+                    for (uint32_t d = 0; d < 4; d++) {
+                        const int16_t L = lfx_fire_level(r, x);
+                        trans[x * 4 + d] = lfx_wrap((uint32_t)(int32_t)L - 16u * d) < r.min ? 4 : (uint8_t)d;
+                    }
+                for (uint32_t x0 = 0; x0 < 5; x0++) {
+                    uint32_t x = x0;
+                    for (uint32_t j = 1; j <= LFX_PERIOD_DRAWS; j++) {
+                        if ((j - 1) % LFX_CHECKPOINT == 0) cp[x0 * 64 + (j - 1) / LFX_CHECKPOINT] = (uint8_t)x;
+                        x = trans[x * 4 + lfx_draw(seed, 3u, (uint32_t)i, j % LFX_PERIOD_DRAWS, 4u)];
+                    }
+                    pmap[x0] = (uint8_t)x;
+                }
+            }
+            fx.rec_of[i] = (int32_t)fx.recs.size();
+            fx.recs.push_back(r);
+        }
+    }
+    light_fx = std::move(fx);
+    return DG_OK;
+}
+
 int Scene::wall_texture_id(const std::string &name, float timestamp) const {
     const int id = texture_id(name);
     if (id < 0 || !(wall_fx.flags & DG_WALL_ANIMATE)) return id;
@@ -597,11 +662,13 @@ Scene *load_scene_from_wad(const uint8_t *bytes, size_t len, const char *map_nam
             const Lump &l = w.map_lump(map_name, SECTORS);
             size_t n = l.size / 26;
             sc->sectors.resize(n);
+            sc->wad_light.resize(n);
             for (size_t i = 0; i < n; i++) {
                 size_t o = l.off + i * 26;
                 SectorRec &s = sc->sectors[i];
                 std::memset(&s, 0, sizeof s);
-                s.floor_h = w.i16(o); s.ceil_h = w.i16(o + 2); s.light = w.i16(o + 20);
+                s.floor_h = w.i16(o); s.ceil_h = w.i16(o + 2); s.light = w.i16(o + 20); s.special = w.i16(o + 22);
+                sc->wad_light[i] = s.light;
                 std::string fn = w.name8(o + 4), cn = w.name8(o + 12);
                 s.floor_sky = fn.find("SKY") != std::string::npos;
                 s.ceil_sky = s.ceil_tex_sky = cn.find("SKY") != std::string::npos;

@@ -12,6 +12,7 @@
 
 #include "../../include/doomgpu.h"
 #include "fs_frame.h"
+#include "light_fx.h"
 
 namespace dg {
 
@@ -25,7 +26,7 @@ struct BitmapInfo {          // reference Bitmap (src/graphics/bitmap.rs:11-15):
 
 struct SectorRec {
     int16_t floor_h, ceil_h, light;
-    int16_t pad;
+    int16_t special;                // special_type (SECTORS +22), read by the light effects
     int32_t floor_flat, ceil_flat;  // flat id when not animated (>= 0), FLAT_MISSING if the lump does not exist
     int32_t floor_anim, ceil_anim;  // index into Scene::anim (or -1)
     uint8_t floor_sky, ceil_sky;    // name contains "SKY"
@@ -65,6 +66,18 @@ struct WallFx {
     bool on() const { return flags != 0; }
 };
 
+// The light effects of a scene (dg_scene_set_light_effects) as light_fx.h evaluates them: flags, seed, one record per
+// effect sector, the flash / fire tables, and per sector its record (-1: none).  flags 0: all empty.  A dg_ctx keeps the copy it uploaded.
+struct LightFx {
+    uint32_t flags = 0;
+    uint64_t seed = 0;
+    std::vector<LfxRec> recs;
+    std::vector<uint32_t> tab;
+    std::vector<int32_t> rec_of;
+    bool on() const { return flags != 0 && !recs.empty(); }
+    int16_t level(size_t rec, float timestamp) const { return lfx_level(recs[rec], tab.data(), seed, fs_tics(timestamp)); }
+};
+
 enum : int32_t { TEX_NONE = -1, TEX_UNKNOWN = -2, FLAT_MISSING = -2 };
 
 struct Scene {
@@ -98,6 +111,8 @@ struct Scene {
     int32_t sky_bitmap = TEX_UNKNOWN;
     uint64_t revision = 0;                          // bumped by the mutable-state setters
     WallFx wall_fx;                                 // as last set by set_wall_effects (the host walker of dg_build_lists reads it)
+    std::vector<int16_t> wad_light;                 // per sector its level as the WAD holds it (the light effects' max and surrounding min)
+    LightFx light_fx;                               // as last set by set_light_effects (dg_build_lists, dg_scene_sector_lights_at read it)
     // The per-seg / per-sprite inputs of fs_core.h, flattened (rebuild_fs_tables: at load and whenever bitmaps or sprite frames are added):
     // what the host walker reads per seg and what dg_upload_scene copies to the GPU for DG_FE_DEVICE_SEGS.
     std::vector<FsSeg> fs_segs;                     // one per seg
@@ -123,6 +138,7 @@ struct Scene {
     int find_or_add_sprite_frame(const std::string &sprite, uint8_t frame, std::string &err);
     int set_wall_effects(uint32_t flags, std::string &err);                    // DG_OK, or DG_ERR_INVALID / DG_ERR_WAD with err
     int wall_texture_id(const std::string &name, float timestamp) const;       // texture_id after animation (DG_WALL_ANIMATE)
+    int set_light_effects(uint32_t flags, uint64_t seed, std::string &err);    // DG_OK, or DG_ERR_INVALID with err
 };
 
 // The lines of one 2-D map frame (Game::render with viewing_map, src/game.rs:229-308) in draw order: every linedef without DONTDRAW, then

@@ -78,6 +78,21 @@ int dg_scene_set_wall_effects(dg_scene *s, uint32_t flags);
 /* The dg_scene_texture_id of `name`, after animation at `timestamp` when DG_WALL_ANIMATE is set (the dg_scene_flat_id twin, for list-path callers). */
 int dg_scene_wall_texture_id(const dg_scene *s, const char *name, float timestamp);
 
+/* Sector light effects (opt-in per scene; the reference runs them as sector thinkers, src/lights.rs — DESIGN.md section 8c).
+ *   DG_LIGHT_THINKERS  every sector of special 1, 2, 3, 4, 8, 12, 13 or 17 draws the level its thinker leaves after
+ *                      tics = (timestamp * 35.0f) as u32 (saturating, NaN: 0) calls of mutate(), min / max taken from the WAD's levels.
+ *                      Glow (8) and the synced strobes (12, 13) equal the reference; the random draws of 1, 2, 3, 4 and 17 come from
+ *                      a pinned stream of `seed` (same rules, same distributions, reproducible).
+ * Per view and sector: a dg_view_state entry wins, else the effect's level, else the scene's level (dg_scene_set_sector_light).
+ * Every front end gives the same pixels; the 2-D map view and dg_draw_lists ignore the flags. */
+#define DG_LIGHT_THINKERS 1u
+/* Takes effect at the next dg_upload_scene; dg_build_lists and dg_scene_sector_lights_at see it at once.
+ * Unknown bits or a NULL scene: DG_ERR_INVALID.  flags 0 turns the effects off again. */
+int dg_scene_set_light_effects(dg_scene *s, uint32_t flags, uint64_t seed);
+/* The level of every sector at `timestamp` as this library draws it with no view state: the effect's level for a sector that
+ * has one, else the scene's level (dg_scene_set_sector_light).  n must equal dg_scene_sector_count. */
+int dg_scene_sector_lights_at(const dg_scene *s, float timestamp, int16_t *out, int n);
+
 /* ---- viewpoint (reference: `Player`, src/game.rs:40-45, + Renderer::new's timestamp) ------------------------ */
 typedef struct dg_view {
     float x, y;          /* player.position */

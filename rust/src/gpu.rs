@@ -48,6 +48,7 @@ pub struct dg_map_line { pub x0: i32, pub y0: i32, pub x1: i32, pub y1: i32, pub
 pub const DG_FE_MAP: i32 = 4;              // dg_timing.front_end of a map submission
 pub const DG_WALL_ANIMATE: u32 = 1;         // dg_scene_set_wall_effects flags
 pub const DG_WALL_SCROLL: u32 = 2;
+pub const DG_LIGHT_THINKERS: u32 = 1;       // dg_scene_set_light_effects flag
 
 extern "C" {
     pub fn dg_scene_load_wad(wad: *const u8, len: usize, map_name: *const c_char, out: *mut *mut dg_scene) -> c_int;
@@ -60,6 +61,8 @@ extern "C" {
     pub fn dg_scene_flat_id(s: *const dg_scene, name: *const c_char, timestamp: f32) -> c_int;
     pub fn dg_scene_set_wall_effects(s: *mut dg_scene, flags: u32) -> c_int;
     pub fn dg_scene_wall_texture_id(s: *const dg_scene, name: *const c_char, timestamp: f32) -> c_int;
+    pub fn dg_scene_set_light_effects(s: *mut dg_scene, flags: u32, seed: u64) -> c_int;
+    pub fn dg_scene_sector_lights_at(s: *const dg_scene, timestamp: f32, out: *mut i16, n: c_int) -> c_int;
     pub fn dg_scene_sprite_bitmap_id(s: *const dg_scene, sprite: *const c_char, frame: u8, rotation: u8) -> c_int;
     pub fn dg_scene_sprite_frame(s: *mut dg_scene, sprite: *const c_char, frame: u8) -> c_int;
     pub fn dg_scene_sector_count(s: *const dg_scene) -> c_int;
@@ -114,6 +117,13 @@ impl<'a> GpuRenderer<'a> {
 pub fn set_wall_effects(scene: *mut dg_scene, flags: u32) {
     let rc = unsafe { dg_scene_set_wall_effects(scene, flags) };
     if rc < 0 { panic!("dg_scene_set_wall_effects: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
+}
+
+/// Game::new, before dg_upload_scene: draw the sector light effects (flicker, strobes, glow, fire: lights.rs) as functions of the
+/// timestamp, for callers that run no thinkers.  A game that runs `init_thinkers` itself keeps `sync_state` and leaves this off.
+pub fn set_light_effects(scene: *mut dg_scene, flags: u32, seed: u64) {
+    let rc = unsafe { dg_scene_set_light_effects(scene, flags, seed) };
+    if rc < 0 { panic!("dg_scene_set_light_effects: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
 }
 
 pub fn preload_sprite_frames(scene: *mut dg_scene) {
