@@ -25,6 +25,8 @@ DG_FE_AUTO, DG_FE_HOST, DG_FE_DEVICE, DG_FE_DEVICE_SEGS = 0, 1, 2, 3
 DG_FE_MAP = 4   # dg_timing.front_end of a 2-D map submission
 DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
+DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
+DG_MOBJ_KILL, DG_MOBJ_EXPLODE, DG_MOBJ_RESPAWN = 1, 2, 3   # dg_scene_mobj_event
 
 
 class DoomGpuError(RuntimeError):
@@ -44,6 +46,15 @@ class DgSectorLight(ctypes.Structure):
 
 class DgMobjState(ctypes.Structure):
     _fields_ = [("mobj", ctypes.c_int32), ("sprite_frame", ctypes.c_int32), ("full_bright", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class DgStateRec(ctypes.Structure):
+    _fields_ = [("sprite", ctypes.c_char * 4), ("frame", ctypes.c_uint8), ("full_bright", ctypes.c_uint8), ("tics", ctypes.c_int16),
+                ("next_state", ctypes.c_int32)]
+
+
+class DgMobjInfoRec(ctypes.Structure):
+    _fields_ = [("doomednum", ctypes.c_int32), ("spawn_state", ctypes.c_int32), ("death_state", ctypes.c_int32), ("xdeath_state", ctypes.c_int32)]
 
 
 class DgViewState(ctypes.Structure):
@@ -146,6 +157,9 @@ _SIGNATURES = {
     "dg_scene_wall_texture_id": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_float]),
     "dg_scene_set_light_effects": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint64]),
     "dg_scene_sector_lights_at": (ctypes.c_int, [_P, ctypes.c_float, ctypes.POINTER(ctypes.c_int16), ctypes.c_int]),
+    "dg_scene_set_mobj_thinkers": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(DgStateRec), ctypes.c_int, ctypes.POINTER(DgMobjInfoRec), ctypes.c_int]),
+    "dg_scene_mobj_event": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_float]),
+    "dg_scene_mobj_states_at": (ctypes.c_int, [_P, ctypes.c_float, ctypes.POINTER(DgMobjState), ctypes.c_int]),
     "dg_scene_sprite_bitmap_id": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_uint8]),
     "dg_scene_bitmap_size": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "dg_draw_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P]),
@@ -257,6 +271,26 @@ class Scene:
         out = np.zeros(max(n, 0), dtype=np.int16)
         _check(lib().dg_scene_sector_lights_at(self._h, timestamp, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), n))
         return out
+
+    def set_mobj_thinkers(self, flags: int, states=(), infos=()):
+        """dg_scene_set_mobj_thinkers: DG_MOBJ_THINKERS or 0; states = [(sprite, frame, full_bright, tics, next_state), ...] with row 0
+        S_NULL, infos = [(doomednum, spawn_state, death_state, xdeath_state), ...] (takes effect for a Context at Context.upload_scene;
+        build_lists and mobj_states_at see it at once).  Drops the event list."""
+        sa = (DgStateRec * max(1, len(states)))(*[DgStateRec((sp or "").encode(), int(fr), int(bool(fb)), int(tics), int(nxt))
+                                                  for sp, fr, fb, tics, nxt in states])
+        ia = (DgMobjInfoRec * max(1, len(infos)))(*[DgMobjInfoRec(*[int(v) for v in row]) for row in infos])
+        _check(lib().dg_scene_set_mobj_thinkers(self._h, flags, sa, len(states), ia, len(infos)))
+
+    def mobj_event(self, what: int, timestamp: float = 0.0):
+        """dg_scene_mobj_event: DG_MOBJ_KILL / _EXPLODE / _RESPAWN for every map object at `timestamp`; 0 clears the list."""
+        _check(lib().dg_scene_mobj_event(self._h, what, timestamp))
+
+    def mobj_states_at(self, timestamp: float):
+        """dg_scene_mobj_states_at: every map object's (sprite_frame or -1, full_bright) at `timestamp` as drawn with no view state."""
+        n = lib().dg_scene_mobj_count(self._h)
+        out = (DgMobjState * max(1, n))()
+        _check(lib().dg_scene_mobj_states_at(self._h, timestamp, out, n))
+        return [(out[i].sprite_frame, out[i].full_bright) for i in range(n)]
 
     def build_lists(self, W: int, H: int, view: DgView) -> DgFrameLists:
         fl = DgFrameLists()

@@ -34,6 +34,7 @@
 #include "fe_kernels.hpp"
 #include "fs_kernels.hpp"
 #include "light_fx_kernels.hpp"
+#include "mobj_fx_kernels.hpp"
 #include "frontend.hpp"
 #include "kernels.hpp"
 #include "map_kernels.hpp"
@@ -143,6 +144,7 @@ struct Slot {
     FeParams FP{};
     FsParams FSP{};               // DG_FE_DEVICE_SEGS: the device seg walk in front of the column walk
     LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
+    MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
     bool fs_mode = false;         // the last submission's per-seg half ran on the GPU too
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
     bool fe_mode = false;         // the last submission went through the device column walk
@@ -172,14 +174,18 @@ struct Slot {
     // submission, no per-view snapshot); else the submit-time scene state with the view's own entries on top (later entries win).
     struct RedoState { std::vector<dg_sector_light> lights; std::vector<dg_mobj_state> mobjs; dg_view_state st{}; };
     // lfx: the light effects the frame was drawn with — their sectors keep the effect's level, so the snapshot does not list them.
-    const dg_view_state *state_for_redo(const Scene &sc, int i, RedoState &tmp, const LightFx &lfx) const {
+    // mfx: likewise the map-object thinkers and the objects they drive.
+    const dg_view_state *state_for_redo(const Scene &sc, int i, RedoState &tmp, const LightFx &lfx, const MobjFx &mfx) const {
         const dg_view_state *own = states.empty() ? nullptr : &states[(size_t)i];
         if (snap_scene != &sc || snap_rev == sc.revision) return own;
         tmp.lights.clear();
         const bool fx_on = lfx.on() && lfx.rec_of.size() == snap_lights.size();
         for (const dg_sector_light &l : snap_lights)
             if (!fx_on || lfx.rec_of[(size_t)l.sector] < 0) tmp.lights.push_back(l);
-        tmp.mobjs = snap_mobjs;
+        tmp.mobjs.clear();
+        const bool mfx_on = mfx.on() && mfx.type_of.size() == snap_mobjs.size();
+        for (const dg_mobj_state &m : snap_mobjs)
+            if (!mfx_on || mfx.type_of[(size_t)m.mobj] < 0) tmp.mobjs.push_back(m);
         if (own) { tmp.lights.insert(tmp.lights.end(), own->lights, own->lights + own->n_lights); tmp.mobjs.insert(tmp.mobjs.end(), own->mobjs, own->mobjs + own->n_mobjs); }
         tmp.st = dg_view_state{tmp.lights.data(), (uint32_t)tmp.lights.size(), tmp.mobjs.data(), (uint32_t)tmp.mobjs.size()};
         return &tmp.st;
@@ -252,6 +258,10 @@ struct dg_ctx {
     LightFx lfx;
     uint8_t *d_light_fx = nullptr;      // LfxRec per effect sector | rec_of per sector | tables (only while lfx.on() and the seg walk is uploaded)
     LfxRows lfx_proto{};                // its pointers and the seed, filled at upload
+    // map-object thinkers: the scene's MobjFx as of dg_upload_scene (likewise), and for the seg walk its tables
+    MobjFx mfx;
+    uint8_t *d_mobj_fx = nullptr;       // steps | chains | types | type_of per map object | events (only while mfx.on() and the seg walk is uploaded)
+    MfxRows mfx_proto{};                // its pointers and counts, filled at upload
     uint8_t *d_fs_scratch = nullptr;    // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
     size_t fs_zero_bytes = 0;
     FsParams fs_proto{};                // scene pointers and counts, filled at upload
@@ -335,6 +345,7 @@ void free_ctx(dg_ctx *c) {
     if (c->d_fs_scratch) (void)hipFree(c->d_fs_scratch);
     if (c->d_wall_fx) (void)hipFree(c->d_wall_fx);
     if (c->d_light_fx) (void)hipFree(c->d_light_fx);
+    if (c->d_mobj_fx) (void)hipFree(c->d_mobj_fx);
     if (c->d_map_layer) (void)hipFree(c->d_map_layer);
     delete c;
 }
@@ -359,7 +370,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
             dg_view v = views[i];
             fill_view_trig(v);
             dg_frame_lists fl;
-            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, &c->lfx);
+            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, &c->lfx, &c->mfx);
             if (!rc[(size_t)i]) rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
         }
     });
@@ -428,7 +439,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         FeFrameOut &o = c->fe_out[(size_t)i];
         dg_view v = views[i];
         fill_view_trig(v);
-        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, &c->lfx);
+        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, &c->lfx, &c->mfx);
         if (rc[(size_t)i]) return;
         o.parts.swap(A.parts); o.sprites.swap(A.sprites); o.behind.swap(A.behind); o.sky_parts.swap(A.sky_parts);
         o.bin_off.swap(A.bin_off); o.bin_parts.swap(A.bin_parts); o.sbin_off.swap(A.sbin_off); o.sbin_sprites.swap(A.sbin_sprites);
@@ -577,6 +588,27 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
         c->lfx_proto.seed = c->lfx.seed;
         c->lfx_proto.n_sectors = (uint32_t)c->lfx.rec_of.size();
     }
+    if (c->d_mobj_fx) { (void)hipFree(c->d_mobj_fx); c->d_mobj_fx = nullptr; }
+    c->mfx_proto = MfxRows{};
+    if (c->mfx.on()) {                                  // the map-object thinkers' tables: only for a scene that has them on (dg_mobj_rows reads them)
+        const size_t step_bytes = c->mfx.steps.size() * sizeof(MfxStep), chain_bytes = c->mfx.chains.size() * sizeof(MfxChain);
+        const size_t type_bytes = c->mfx.types.size() * sizeof(MfxType), map_bytes = c->mfx.type_of.size() * 4, ev_bytes = c->mfx.events.size() * sizeof(MfxEvent);
+        const size_t at_chains = align_up(step_bytes, 256), at_types = align_up(at_chains + chain_bytes, 256);
+        const size_t at_map = align_up(at_types + type_bytes, 256), at_ev = align_up(at_map + map_bytes, 256);
+        HIP_TRY(hipMalloc((void **)&c->d_mobj_fx, at_ev + std::max<size_t>(ev_bytes, 16)));
+        HIP_TRY(hipMemcpy(c->d_mobj_fx, c->mfx.steps.data(), step_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_mobj_fx + at_chains, c->mfx.chains.data(), chain_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_mobj_fx + at_types, c->mfx.types.data(), type_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_mobj_fx + at_map, c->mfx.type_of.data(), map_bytes, hipMemcpyHostToDevice));
+        if (ev_bytes) HIP_TRY(hipMemcpy(c->d_mobj_fx + at_ev, c->mfx.events.data(), ev_bytes, hipMemcpyHostToDevice));
+        c->mfx_proto.steps = reinterpret_cast<const MfxStep *>(c->d_mobj_fx);
+        c->mfx_proto.chains = reinterpret_cast<const MfxChain *>(c->d_mobj_fx + at_chains);
+        c->mfx_proto.types = reinterpret_cast<const MfxType *>(c->d_mobj_fx + at_types);
+        c->mfx_proto.type_of = reinterpret_cast<const int32_t *>(c->d_mobj_fx + at_map);
+        c->mfx_proto.events = reinterpret_cast<const MfxEvent *>(c->d_mobj_fx + at_ev);
+        c->mfx_proto.n_events = (uint32_t)c->mfx.events.size();
+        c->mfx_proto.n_mobjs = (uint32_t)c->mfx.type_of.size();
+    }
     struct Piece { const void *src; size_t bytes; size_t at; };
     std::vector<Piece> pieces;
     size_t total = 0;
@@ -641,9 +673,9 @@ void calibrate_host(dg_ctx *c, const dg_view *views, int n) {
     FrameArena &A = *c->arenas[0];
     std::string err;
     const int warm = std::min(4, n), timed = std::min(8, n);
-    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx, &c->lfx); }
+    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx, &c->lfx, &c->mfx); }
     const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx, &c->lfx); }
+    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx, &c->lfx, &c->mfx); }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->ema_host = ms / timed / std::max(1, c->n_threads) * 1.25;     // (the pool does not scale perfectly)
     c->host_samples = std::max(c->host_samples, 2);
@@ -690,10 +722,16 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     const bool lfx = c->lfx.on() && c->lfx_proto.recs && c->lfx.rec_of.size() == sc.sectors.size();
     const size_t mask_words = (sc.sectors.size() + 31) / 32;
     const size_t off_lmask = align_up(off_mstate + state_frames * sc.mobjs.size() * 4, 256);
-    const size_t upload = align_up(off_lmask + (lfx && states ? (size_t)n * mask_words * 4 : 0), 256);
+    // map-object thinkers (dg_mobj_rows): the same two layouts for the map-object rows
+    const bool mfx = c->mfx.on() && c->mfx_proto.steps && c->mfx.type_of.size() == sc.mobjs.size();
+    if (mfx && (uint64_t)n * sc.mobjs.size() >= (1ull << 31)) return kPartsUnsupported;
+    const size_t mmask_words = (sc.mobjs.size() + 31) / 32;
+    const size_t off_mmask = align_up(off_lmask + (lfx && states ? (size_t)n * mask_words * 4 : 0), 256);
+    const size_t upload = align_up(off_mmask + (mfx && states ? (size_t)n * mmask_words * 4 : 0), 256);
     // device-written part
     const size_t off_lrows = upload;
-    const size_t off_ff = align_up(off_lrows + (lfx && !states ? (size_t)n * sc.sectors.size() * 2 : 0), 256);
+    const size_t off_mrows = align_up(off_lrows + (lfx && !states ? (size_t)n * sc.sectors.size() * 2 : 0), 256);
+    const size_t off_ff = align_up(off_mrows + (mfx && !states ? (size_t)n * sc.mobjs.size() * 4 : 0), 256);
     const size_t off_parts = align_up(off_ff + (size_t)n * sizeof(FeFrame), 256);
     const size_t off_sprites = align_up(off_parts + (size_t)n * FS_PART_CAP * sizeof(FePart), 256);
     const size_t off_behind = align_up(off_sprites + (size_t)n * c->fs_proto.sprite_stride * sizeof(FeSprite), 256);
@@ -716,6 +754,7 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     int16_t *lights = reinterpret_cast<int16_t *>(s.h_fe + off_lights);
     int32_t *mstate = reinterpret_cast<int32_t *>(s.h_fe + off_mstate);
     uint32_t *lmask = reinterpret_cast<uint32_t *>(s.h_fe + off_lmask);
+    uint32_t *mmask = reinterpret_cast<uint32_t *>(s.h_fe + off_mmask);
     std::atomic<int> bad_state{-1};
     c->pool->parallel_for((int)state_frames, [&](int i, int) {
         int16_t *l = lights + (size_t)i * sc.sectors.size();
@@ -725,6 +764,8 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         if (!states) return;
         uint32_t *lm = lfx ? lmask + (size_t)i * mask_words : nullptr;
         if (lm) std::memset(lm, 0, mask_words * 4);
+        uint32_t *mm = mfx ? mmask + (size_t)i * mmask_words : nullptr;
+        if (mm) std::memset(mm, 0, mmask_words * 4);
         const dg_view_state &st = states[i];                        // the same rules as the host walker's (frontend.cpp: Walker::apply_state): later entries win
         for (uint32_t k = 0; k < st.n_lights; k++) {
             if (st.lights[k].sector < 0 || (size_t)st.lights[k].sector >= sc.sectors.size()) { bad_state = i; continue; }
@@ -735,6 +776,7 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
             const dg_mobj_state &ms = st.mobjs[k];
             if (ms.mobj < 0 || (size_t)ms.mobj >= sc.mobjs.size() || ms.sprite_frame >= (int32_t)sc.sprite_frames.size()) { bad_state = i; continue; }
             m[(size_t)ms.mobj] = (ms.sprite_frame < 0 ? -1 : ms.sprite_frame) * 2 + (ms.full_bright ? 1 : 0);
+            if (mm) mm[(size_t)ms.mobj / 32] |= 1u << ((uint32_t)ms.mobj % 32);
         }
     });
     if (bad_state >= 0) return set_err(DG_ERR_INVALID, "frame " + std::to_string(bad_state.load()) + ": view state: sector, map object or sprite frame index out of range");
@@ -759,6 +801,19 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         Q.light_stride = (uint32_t)sc.sectors.size();
     }
     Q.mstate_stride = states ? (uint32_t)sc.mobjs.size() : 0u;
+    s.MR = MfxRows{};
+    if (mfx) {                                              // dg_mobj_rows completes the rows the seg walk reads
+        s.MR = c->mfx_proto;
+        s.MR.views = reinterpret_cast<const dg_view *>(s.d_fe + off_views);
+        s.MR.base = Q.mobj_state;
+        s.MR.base_stride = Q.mstate_stride;
+        s.MR.mask = states ? reinterpret_cast<const uint32_t *>(s.d_fe + off_mmask) : nullptr;
+        s.MR.mask_words = (uint32_t)mmask_words;
+        s.MR.out = states ? reinterpret_cast<int32_t *>(s.d_fe + off_mstate) : reinterpret_cast<int32_t *>(s.d_fe + off_mrows);
+        s.MR.n_frames = n;
+        Q.mobj_state = s.MR.out;
+        Q.mstate_stride = (uint32_t)sc.mobjs.size();
+    }
     Q.views = reinterpret_cast<const dg_view *>(s.d_fe + off_views);
     Q.n_frames = n;
     Q.flags = s.d_flags;
@@ -903,7 +958,8 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
             if (c->fs_rows_dirty) HIP_TRY(hipMemsetAsync(c->d_fs_scratch, 0, c->fs_zero_bytes, ks));    // (dg_fs_frame leaves its rows clean)
             c->fs_rows_dirty = true;
             hipEvent_t fs_start = s.ev_start;
-            if (s.LR.n_frames > 0) { HIP_TRY(launch_light_rows(s.LR, ks, s.ev_start)); fs_start = nullptr; }   // the rows dg_fs_* read
+            if (s.LR.n_frames > 0) { HIP_TRY(launch_light_rows(s.LR, ks, fs_start)); fs_start = nullptr; }     // the rows dg_fs_* read
+            if (s.MR.n_frames > 0) { HIP_TRY(launch_mobj_rows(s.MR, ks, fs_start)); fs_start = nullptr; }
             HIP_TRY(c->fx.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
             c->fs_rows_dirty = false;
         }
@@ -939,7 +995,7 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     fill_view_trig(v);
     dg_frame_lists fl;
     Slot::RedoState redo_state;
-    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->lfx), &c->fx, &c->lfx);
+    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->lfx, c->mfx), &c->fx, &c->lfx, &c->mfx);
     if (!rc) rc = bin_frame(sc, c->fk, fl, bf, err);
     if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
@@ -1008,7 +1064,7 @@ int settle_slot(dg_ctx *c, Slot &s) {
             std::vector<dg_view_state> sts;
             bool any_state = false;
             for (size_t i = 0; i < views.size(); i++) {
-                const dg_view_state *st = s.state_for_redo(*c->scene, (int)i, redo_states[i], c->lfx);
+                const dg_view_state *st = s.state_for_redo(*c->scene, (int)i, redo_states[i], c->lfx, c->mfx);
                 any_state |= st != nullptr;
                 sts.push_back(st ? *st : dg_view_state{nullptr, 0, nullptr, 0});
             }
@@ -1147,6 +1203,33 @@ int dg_scene_sector_lights_at(const dg_scene *s, float ts, int16_t *out, int n) 
         for (size_t r = 0; r < fx.recs.size(); r++) out[fx.recs[r].sector] = fx.level(r, ts);
     return DG_OK;
 }
+int dg_scene_set_mobj_thinkers(dg_scene *s, uint32_t flags, const dg_state_rec *states, int n_states, const dg_mobj_info_rec *infos, int n_infos) {
+    if (!s) return set_err(DG_ERR_INVALID, "null scene");
+    std::string err;
+    const int rc = s->sc->set_mobj_thinkers(flags, states, n_states, infos, n_infos, err);
+    return rc ? set_err(rc, err) : DG_OK;
+}
+int dg_scene_mobj_event(dg_scene *s, int what, float ts) {
+    if (!s) return set_err(DG_ERR_INVALID, "null scene");
+    std::string err;
+    const int rc = s->sc->mobj_event(what, ts, err);
+    return rc ? set_err(rc, err) : DG_OK;
+}
+int dg_scene_mobj_states_at(const dg_scene *s, float ts, dg_mobj_state *out, int n) {
+    if (!s || !out) return set_err(DG_ERR_INVALID, "null argument");
+    const Scene &sc = *s->sc;
+    if (n < 0 || (size_t)n != sc.mobjs.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_mobj_count");
+    for (size_t i = 0; i < sc.mobjs.size(); i++)
+        out[i] = dg_mobj_state{(int32_t)i, sc.mobjs[i].sprite_frame < 0 ? -1 : sc.mobjs[i].sprite_frame, sc.mobjs[i].sprite_frame < 0 ? 0 : (sc.mobjs[i].full_bright ? 1 : 0), 0};
+    const MobjFx &fx = sc.mobj_fx;
+    if (fx.on() && fx.type_of.size() == sc.mobjs.size())
+        for (uint32_t i : fx.driven) {
+            const int32_t v = fx.value(i, ts);
+            out[i].sprite_frame = v < 0 ? -1 : v >> 1;
+            out[i].full_bright = v < 0 ? 0 : v & 1;
+        }
+    return DG_OK;
+}
 int dg_scene_sprite_bitmap_id(const dg_scene *s, const char *sprite, uint8_t frame, uint8_t rot) {
     return (s && sprite) ? s->sc->sprite_bitmap_id(sprite, frame, rot) : DG_ERR_INVALID;
 }
@@ -1163,7 +1246,7 @@ int dg_build_lists(const dg_scene *s, int width, int height, const dg_view *view
     dg_view v = *view;
     fill_view_trig(v);
     std::string err;
-    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err, nullptr, &s->sc->wall_fx, &s->sc->light_fx);
+    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err, nullptr, &s->sc->wall_fx, &s->sc->light_fx, &s->sc->mobj_fx);
     return rc ? set_err(rc, err) : DG_OK;
 }
 
@@ -1338,6 +1421,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     c->scene = &sc;
     c->fx = sc.wall_fx;                                 // dg_scene_set_wall_effects takes effect here
     c->lfx = sc.light_fx;                               // dg_scene_set_light_effects too
+    c->mfx = sc.mobj_fx;                                // and dg_scene_set_mobj_thinkers with its events
     c->fe_scene_ok = sky.w >= 256 && sky.h >= 128;    // a smaller sky bitmap is an index panic only when a sky visplane is drawn: host path
     c->uploaded_texels = sc.texel_idx.size();
     c->fs_scene_ok = false;
@@ -1351,6 +1435,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
             if (c->d_fs_scratch) { (void)hipFree(c->d_fs_scratch); c->d_fs_scratch = nullptr; }
             if (c->d_wall_fx) { (void)hipFree(c->d_wall_fx); c->d_wall_fx = nullptr; }
             if (c->d_light_fx) { (void)hipFree(c->d_light_fx); c->d_light_fx = nullptr; }
+            if (c->d_mobj_fx) { (void)hipFree(c->d_mobj_fx); c->d_mobj_fx = nullptr; }
             c->fs_scene_ok = false;
             (void)hipGetLastError();
         }

@@ -88,6 +88,19 @@ public:
         out.resize((size_t)dg_scene_sector_count(h_));
         check(dg_scene_sector_lights_at(h_, timestamp, out.data(), (int)out.size()));
     }
+    // Game::new, BEFORE Device::upload: run the map-object state machine (DG_MOBJ_THINKERS: map_objects.rs' MapObjectThinker as a
+    // function of the view's timestamp) over the caller's tables — info::STATES / MAP_OBJECT_INFOS, row 0 = S_NULL.
+    // A game that runs the thinkers itself leaves this off.
+    void set_mobj_thinkers(uint32_t flags, const std::vector<dg_state_rec> &states, const std::vector<dg_mobj_info_rec> &infos) {
+        check(dg_scene_set_mobj_thinkers(h_, flags, states.data(), (int)states.size(), infos.data(), (int)infos.size()));
+    }
+    // kill_everything / explode_everything / respawn_everything (DG_MOBJ_KILL, _EXPLODE, _RESPAWN) at `timestamp`; 0 clears the list.
+    void mobj_event(int what, float timestamp) { check(dg_scene_mobj_event(h_, what, timestamp)); }
+    // Every map object's state at `timestamp` as drawn with no view state (for list-path callers); out.size() map objects.
+    void mobj_states_at(float timestamp, std::vector<dg_mobj_state> &out) const {
+        out.resize((size_t)dg_scene_mobj_count(h_));
+        check(dg_scene_mobj_states_at(h_, timestamp, out.data(), (int)out.size()));
+    }
     bool sector_floor_height(const Vertex &v, float &out) const { return dg_scene_floor_height_at(h_, v.x, v.y, &out) == 0; }  // bsp.rs:9-44
     dg_scene *handle() const { return h_; }
 private:

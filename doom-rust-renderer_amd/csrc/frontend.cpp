@@ -119,11 +119,13 @@ struct Walker {
     const dg_view_state *state = nullptr;   // this view's game-state snapshot (light levels, mobj states) on top of the scene's
     const WallFx *fx = nullptr;             // the wall effects to draw with (nullptr: none)
     const LightFx *lfx = nullptr;           // the light effects to draw with (nullptr: none)
+    const MobjFx *mfx = nullptr;            // the map-object thinkers to draw with (nullptr: none)
 
     Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const WallFx *wfx,
-           const LightFx *lf)
+           const LightFx *lf, const MobjFx *mf)
         : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e), fx(wfx && wfx->on() ? wfx : nullptr),
-          lfx(lf && lf->on() && lf->rec_of.size() == s.sectors.size() ? lf : nullptr) {
+          lfx(lf && lf->on() && lf->rec_of.size() == s.sectors.size() ? lf : nullptr),
+          mfx(mf && mf->on() && mf->type_of.size() == s.mobjs.size() ? mf : nullptr) {
         ppos = V2{v.x, v.y};
         player_height = v.floor_height + kEye;
         apply_state(st);
@@ -131,10 +133,16 @@ struct Walker {
             if (A.fx_light.size() != sc.sectors.size()) A.fx_light.assign(sc.sectors.size(), kNoOverride);
             for (size_t r = 0; r < lfx->recs.size(); r++) A.fx_light[lfx->recs[r].sector] = lfx->level(r, v.timestamp);
         }
+        if (mfx) {                                                   // every driven object once per frame
+            if (A.fx_mobj.size() != sc.mobjs.size()) A.fx_mobj.assign(sc.mobjs.size(), kNoOverride);
+            for (uint32_t i : mfx->driven) A.fx_mobj[i] = mfx->value(i, v.timestamp);
+        }
     }
     ~Walker() {                                                      // the arena's overlay tables go back to "no override"
         if (lfx)
             for (const LfxRec &r : lfx->recs) A.fx_light[r.sector] = kNoOverride;
+        if (mfx)
+            for (uint32_t i : mfx->driven) A.fx_mobj[i] = kNoOverride;
         if (!state) return;
         for (uint32_t i = 0; i < state->n_lights; i++)
             if ((size_t)state->lights[i].sector < A.light_ov.size()) A.light_ov[(size_t)state->lights[i].sector] = kNoOverride;
@@ -145,7 +153,7 @@ struct Walker {
 
     // sector.light_level / map object state as the reference's thinkers would have left them before this frame
     // (src/lights.rs:47-259, src/map_objects.rs:63-121): the view's snapshot entry if there is one, else the light effect's level
-    // (DESIGN.md §8c), else the scene's value.
+    //  or the map-object thinker's state (§8d), else the scene's value.
     void apply_state(const dg_view_state *st) {
         if (!st || (st->n_lights == 0 && st->n_mobjs == 0)) return;
         if (A.light_ov.size() != sc.sectors.size()) A.light_ov.assign(sc.sectors.size(), kNoOverride);
@@ -174,6 +182,9 @@ struct Walker {
         sprite_frame = m.sprite_frame; full_bright = m.full_bright;
         if (state && A.mobj_ov[i] != kNoOverride) {
             const int32_t v = A.mobj_ov[i];
+            sprite_frame = v < 0 ? -1 : v >> 1; full_bright = v < 0 ? 0 : v & 1;
+        } else if (mfx && A.fx_mobj[i] != kNoOverride) {
+            const int32_t v = A.fx_mobj[i];
             sprite_frame = v < 0 ? -1 : v >> 1; full_bright = v < 0 ? 0 : v & 1;
         }
     }
@@ -614,7 +625,7 @@ struct Walker {
 }  // namespace
 
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const WallFx *fx,
-                      const LightFx *lfx) {
+                      const LightFx *lfx, const MobjFx *mfx) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.renders.clear(); A.columns.clear(); A.visplanes.clear(); A.plane_tb.clear(); A.order.clear();
     A.recs->clear(); A.floor_tb.clear(); A.ceil_tb.clear();
@@ -624,7 +635,7 @@ int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameA
     A.top_clip.resize((size_t)W);
     A.bottom_clip.resize((size_t)W);
 
-    Walker wk(sc, W, H, view, A, err, state, fx, lfx);
+    Walker wk(sc, W, H, view, A, err, state, fx, lfx, mfx);
     if (wk.status) return wk.status;
     wk.walk_bsp();
     if (wk.status) return wk.status;
@@ -673,11 +684,11 @@ void bin_by_columns(const std::vector<T> &recs, int W, Range range, std::vector<
 }  // namespace
 
 int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state, const WallFx *fx,
-                      const LightFx *lfx) {
+                      const LightFx *lfx, const MobjFx *mfx) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.parts.clear(); A.sprites.clear(); A.behind.clear(); A.sky_parts.clear(); A.behind_words = 0; A.n_sky_slots = 0;
     A.recs->clear();
-    Walker wk(sc, W, H, view, A, err, state, fx, lfx);
+    Walker wk(sc, W, H, view, A, err, state, fx, lfx, mfx);
     if (wk.status) return wk.status;
     wk.parts_mode = true;
     wk.walk_bsp();

@@ -47,6 +47,7 @@ struct FrameArena {
     std::vector<int16_t> floor_ocl, ceil_ocl, top_clip, bottom_clip;
     std::vector<int32_t> light_ov, mobj_ov;     // per sector / per map object: this view's snapshot value or "no override" (Walker)
     std::vector<int32_t> fx_light;              // per sector: the light effect's level at this view's tics or "no effect" (Walker)
+    std::vector<int32_t> fx_mobj;               // per map object: the thinker's state at this view's tics or "not driven" (Walker)
     FrameArena();
     ~FrameArena();
     FrameArena(const FrameArena &) = delete;
@@ -58,8 +59,10 @@ struct FrameArena {
 // `state` (optional): the view's game-state snapshot (include/doomgpu.h dg_view_state).
 // `fx` (optional): the wall effects to draw with (Scene::wall_fx, or the copy a dg_ctx uploaded).
 // `lfx` (optional): the light effects to draw with (Scene::light_fx, or the copy a dg_ctx uploaded).
+// `mfx` (optional): the map-object thinkers to draw with (Scene::mobj_fx, or the copy a dg_ctx uploaded).
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, dg_frame_lists &out, std::string &err,
-                      const dg_view_state *state = nullptr, const WallFx *fx = nullptr, const LightFx *lfx = nullptr);
+                      const dg_view_state *state = nullptr, const WallFx *fx = nullptr, const LightFx *lfx = nullptr,
+                      const MobjFx *mfx = nullptr);
 
 void fill_view_trig(dg_view &v);
 
@@ -69,7 +72,8 @@ void fill_view_trig(dg_view &v);
 // host list path can judge: the caller redoes the frame with build_frame_lists).
 constexpr int kPartsUnsupported = 1000;
 int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, std::string &err, const dg_view_state *state = nullptr,
-                      const WallFx *fx = nullptr, const LightFx *lfx = nullptr);
+                      const WallFx *fx = nullptr, const LightFx *lfx = nullptr,
+                      const MobjFx *mfx = nullptr);
 
 // Per-record constants of render_vertical_bitmap_line (bitmap_render.rs:233-251), shared by the binner and the parts builder.
 DevWallRec make_wall_rec(const BitmapInfo &bi, float lsx, float lsy, float lex, float ley, float start_offset, int32_t start_x, int32_t end_x,

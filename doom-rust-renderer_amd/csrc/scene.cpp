@@ -530,6 +530,133 @@ int Scene::set_light_effects(uint32_t flags, uint64_t seed, std::string &err) {
     return DG_OK;
 }
 
+// Whether add_sprite_frame would resolve (sprite, frame) as far as the lump names tell (Sprites::new's rules), decoding nothing.
+static bool sprite_frame_resolves(const Builder &b, const std::string &sprite, uint8_t frame) {
+    const std::string key = sprite + (char)('A' + frame);
+    for (const std::string &k : b.sc.sprite_frame_keys)
+        if (k == key) return true;
+    if (sprite.size() != 4) return false;
+    bool have[256] = {false};
+    for (int idx = b.first_sprite; idx < b.last_sprite; idx++) {
+        const std::string &nm = b.wad.dir[(size_t)idx].name;
+        if (nm.compare(0, 4, sprite) != 0) continue;
+        if (nm.size() < 6 || nm.size() == 7) return false;
+        if ((uint8_t)(nm[4] - 65) == frame) have[(uint8_t)(nm[5] - 48)] = true;
+        if (nm.size() > 6 && (uint8_t)(nm[6] - 65) == frame) have[(uint8_t)(nm[7] - 48)] = true;
+    }
+    int nkeys = 0;
+    for (bool h : have) nkeys += h;
+    if (nkeys == 1) return have[0];
+    if (nkeys != 8) return false;
+    for (int r = 1; r < 9; r++)
+        if (!have[r]) return false;
+    return true;
+}
+
+// dg_scene_set_mobj_thinkers: init_map_obj_thinkers (thinkers.rs:82-86) over the caller's tables.  Per start state in use — the spawn
+// states of the things' types, and their death / xdeath states for the events — the chain mutate() walks (map_objects.rs:92-121),
+// flattened for mobj_fx.h when it is live; the frames of live chains are decoded here (appended: ids never move).
+int Scene::set_mobj_thinkers(uint32_t flags, const dg_state_rec *states, int n_states, const dg_mobj_info_rec *infos, int n_infos, std::string &err) {
+    if (flags & ~(uint32_t)DG_MOBJ_THINKERS) { err = "unknown map-object thinker bits"; return DG_ERR_INVALID; }
+    MobjFx fx;
+    fx.flags = flags;
+    if (!flags) { mobj_fx = std::move(fx); return DG_OK; }
+    if (!states || n_states < 1 || n_states > MFX_MAX_STATES) { err = "state table: NULL or n_states outside [1, 65536]"; return DG_ERR_INVALID; }
+    if (n_infos < 0 || (n_infos > 0 && !infos)) { err = "info table: NULL or n_infos negative"; return DG_ERR_INVALID; }
+    for (int i = 0; i < n_states; i++) {
+        if (states[i].tics < -1) { err = "state " + std::to_string(i) + ": tics below -1"; return DG_ERR_INVALID; }
+        if (states[i].next_state < 0 || states[i].next_state >= n_states) { err = "state " + std::to_string(i) + ": next_state out of range"; return DG_ERR_INVALID; }
+    }
+    for (int i = 0; i < n_infos; i++)
+        for (int32_t st : {infos[i].spawn_state, infos[i].death_state, infos[i].xdeath_state})
+            if (st < 0 || st >= n_states) { err = "info row " + std::to_string(i) + ": state out of range"; return DG_ERR_INVALID; }
+
+    const size_t frames_before = sprite_frames.size();
+    try {
+        Builder b(*this);
+        for (size_t i = 0; i < bitmap_names.size(); i++) b.bitmap_by_key[bitmap_names[i]] = (int)i;
+        b.first_sprite = b.wad.find("S_START"); b.last_sprite = b.wad.find("S_END");
+        std::vector<int8_t> resolves((size_t)n_states, -1);                  // per state: -1 not asked yet, 0 / 1
+        std::vector<int32_t> chain_of((size_t)n_states, -2), pos((size_t)n_states, -1);   // per start state: -2 not built yet, -1 not live, else its chain
+        std::vector<int32_t> walk;
+        auto sprite_of = [&](int32_t st) { return std::string(states[st].sprite, strnlen(states[st].sprite, 4)); };
+        auto chain_from = [&](int32_t start) -> int32_t {
+            if (chain_of[(size_t)start] != -2) return chain_of[(size_t)start];
+            walk.clear();
+            int32_t st = start, cycle_at = -1;                               // cycle_at: where in the walk the cycle starts
+            for (;;) {
+                pos[(size_t)st] = (int32_t)walk.size();
+                walk.push_back(st);
+                if (states[st].tics == -1) { cycle_at = (int32_t)walk.size() - 1; break; }     // for ever: a cycle of this one state
+                st = states[st].next_state;
+                if (pos[(size_t)st] >= 0) { cycle_at = pos[(size_t)st]; break; }
+            }
+            bool live = true;
+            for (int32_t w : walk) {
+                pos[(size_t)w] = -1;
+                if (w == 0) continue;
+                if (resolves[(size_t)w] < 0) resolves[(size_t)w] = sprite_frame_resolves(b, sprite_of(w), states[w].frame) ? 1 : 0;
+                live &= resolves[(size_t)w] == 1;
+            }
+            int32_t id = -1;
+            if (live) {
+                MfxChain c{(uint32_t)fx.steps.size(), (uint32_t)cycle_at, (uint32_t)walk.size() - (uint32_t)cycle_at, 0u, 0u, 0u};
+                uint32_t sum = 0;
+                for (size_t k = 0; k < walk.size(); k++) {
+                    const dg_state_rec &r = states[walk[k]];
+                    if (k == (size_t)cycle_at) { c.prefix_total = sum; sum = 0; }
+                    sum += r.tics < 1 ? 1u : (uint32_t)r.tics;
+                    const int32_t val = walk[k] == 0 ? -1 : add_sprite_frame(b, sprite_of(walk[k]), r.frame) * 2 + (r.full_bright ? 1 : 0);
+                    fx.steps.push_back(MfxStep{sum, val});
+                }
+                c.period = sum;
+                id = (int32_t)fx.chains.size();
+                fx.chains.push_back(c);
+            }
+            return chain_of[(size_t)start] = id;
+        };
+        std::vector<int32_t> type_of_row((size_t)n_infos, -2);               // per info row: -2 not built yet, -1 not driven, else its MfxType
+        fx.type_of.assign(mobjs.size(), -1);
+        for (size_t i = 0; i < mobjs.size(); i++) {
+            int row = -1;
+            for (int k = 0; k < n_infos; k++)
+                if (infos[k].doomednum == (int32_t)mobj_type[i]) row = k;    // a later row wins (HashMap::insert)
+            if (row < 0) continue;
+            if (type_of_row[(size_t)row] == -2) {
+                type_of_row[(size_t)row] = -1;
+                const int32_t spawn = chain_from(infos[row].spawn_state);
+                if (spawn >= 0) {
+                    MfxType t{{spawn, -1, -1, spawn}};
+                    if (infos[row].death_state != 0) t.chain[DG_MOBJ_KILL] = chain_from(infos[row].death_state);
+                    t.chain[DG_MOBJ_EXPLODE] = infos[row].xdeath_state != 0 ? chain_from(infos[row].xdeath_state) : t.chain[DG_MOBJ_KILL];
+                    type_of_row[(size_t)row] = (int32_t)fx.types.size();
+                    fx.types.push_back(t);
+                }
+            }
+            fx.type_of[i] = type_of_row[(size_t)row];
+            if (fx.type_of[i] >= 0) fx.driven.push_back((uint32_t)i);
+        }
+    } catch (const std::exception &ex) {
+        err = ex.what();
+        if (sprite_frames.size() != frames_before) { revision++; rebuild_fs_tables(); }     // (frames decoded before the failure stay: ids never move)
+        return DG_ERR_WAD;
+    }
+    if (sprite_frames.size() != frames_before) { revision++; rebuild_fs_tables(); }
+    mobj_fx = std::move(fx);
+    return DG_OK;
+}
+
+int Scene::mobj_event(int what, float timestamp, std::string &err) {
+    if (what == 0) { mobj_fx.events.clear(); return DG_OK; }
+    if (!mobj_fx.flags) { err = "no map-object thinkers set"; return DG_ERR_INVALID; }
+    if (what != DG_MOBJ_KILL && what != DG_MOBJ_EXPLODE && what != DG_MOBJ_RESPAWN) { err = "unknown map-object event"; return DG_ERR_INVALID; }
+    const uint32_t tics = fs_tics(timestamp);
+    if (!mobj_fx.events.empty() && tics < mobj_fx.events.back().tics) { err = "map-object events must not go back in time"; return DG_ERR_INVALID; }
+    if (mobj_fx.events.size() >= MFX_MAX_EVENTS) { err = "more than 16 map-object events"; return DG_ERR_INVALID; }
+    mobj_fx.events.push_back(MfxEvent{tics, (uint32_t)what});
+    return DG_OK;
+}
+
 int Scene::wall_texture_id(const std::string &name, float timestamp) const {
     const int id = texture_id(name);
     if (id < 0 || !(wall_fx.flags & DG_WALL_ANIMATE)) return id;
@@ -824,6 +951,7 @@ Scene *load_scene_from_wad(const uint8_t *bytes, size_t len, const char *map_nam
                 m.sprite_frame = row->is_null ? -1 : add_sprite_frame(b, row->sprite, row->frame);
                 m.sector = sc->sector_from_vertex(x, y);
                 sc->mobjs.push_back(m);
+                sc->mobj_type.push_back(type);
             }
         }
         for (const LinedefRec &d : sc->linedefs)

@@ -13,6 +13,7 @@
 #include "../../include/doomgpu.h"
 #include "fs_frame.h"
 #include "light_fx.h"
+#include "mobj_fx.h"
 
 namespace dg {
 
@@ -78,6 +79,23 @@ struct LightFx {
     int16_t level(size_t rec, float timestamp) const { return lfx_level(recs[rec], tab.data(), seed, fs_tics(timestamp)); }
 };
 
+// The map-object thinkers of a scene (dg_scene_set_mobj_thinkers) as mobj_fx.h evaluates them: the live chains' steps,
+// one record per driven thing type, per map object its type (-1: not driven), the driven objects, and the events.  flags 0: all empty.
+// A dg_ctx keeps the copy it uploaded.
+struct MobjFx {
+    uint32_t flags = 0;
+    std::vector<MfxStep> steps;
+    std::vector<MfxChain> chains;
+    std::vector<MfxType> types;
+    std::vector<int32_t> type_of;
+    std::vector<uint32_t> driven;
+    std::vector<MfxEvent> events;
+    bool on() const { return flags != 0 && !driven.empty(); }
+    int32_t value(size_t mobj, float timestamp) const {
+        return mfx_value(types[(size_t)type_of[mobj]], events.data(), (uint32_t)events.size(), chains.data(), steps.data(), fs_tics(timestamp));
+    }
+};
+
 enum : int32_t { TEX_NONE = -1, TEX_UNKNOWN = -2, FLAT_MISSING = -2 };
 
 struct Scene {
@@ -92,6 +110,7 @@ struct Scene {
     std::vector<SubSectorRec> subsectors;
     std::vector<NodeRec> nodes;
     std::vector<MapObjectRec> mobjs;
+    std::vector<int16_t> mobj_type;                 // per map object its thing type (doomednum), read by the map-object thinkers
     float start_x = 0, start_y = 0, start_angle = 0;
     // Map::bounding_box (src/map/mod.rs:59-64, src/geometry.rs:11-28): both vertices of every linedef, in LINEDEFS order
     float map_left = 3.40282347e38f, map_top = 3.40282347e38f, map_right = -3.40282347e38f, map_bottom = -3.40282347e38f;
@@ -113,6 +132,7 @@ struct Scene {
     WallFx wall_fx;                                 // as last set by set_wall_effects (the host walker of dg_build_lists reads it)
     std::vector<int16_t> wad_light;                 // per sector its level as the WAD holds it (the light effects' max and surrounding min)
     LightFx light_fx;                               // as last set by set_light_effects (dg_build_lists, dg_scene_sector_lights_at read it)
+    MobjFx mobj_fx;                                 // as last set by set_mobj_thinkers / mobj_event (dg_build_lists, dg_scene_mobj_states_at read it)
     // The per-seg / per-sprite inputs of fs_core.h, flattened (rebuild_fs_tables: at load and whenever bitmaps or sprite frames are added):
     // what the host walker reads per seg and what dg_upload_scene copies to the GPU for DG_FE_DEVICE_SEGS.
     std::vector<FsSeg> fs_segs;                     // one per seg
@@ -139,6 +159,9 @@ struct Scene {
     int set_wall_effects(uint32_t flags, std::string &err);                    // DG_OK, or DG_ERR_INVALID / DG_ERR_WAD with err
     int wall_texture_id(const std::string &name, float timestamp) const;       // texture_id after animation (DG_WALL_ANIMATE)
     int set_light_effects(uint32_t flags, uint64_t seed, std::string &err);    // DG_OK, or DG_ERR_INVALID with err
+    int set_mobj_thinkers(uint32_t flags, const dg_state_rec *states, int n_states, const dg_mobj_info_rec *infos, int n_infos,
+                          std::string &err);                                   // DG_OK, or DG_ERR_INVALID / DG_ERR_WAD with err
+    int mobj_event(int what, float timestamp, std::string &err);               // DG_OK, or DG_ERR_INVALID with err
 };
 
 // The lines of one 2-D map frame (Game::render with viewing_map, src/game.rs:229-308) in draw order: every linedef without DONTDRAW, then

@@ -118,6 +118,42 @@ typedef struct dg_view_state {
  * negative on error.  Like dg_scene_set_mobj_state it may decode new bitmaps: call it before dg_upload_scene. */
 int dg_scene_sprite_frame(dg_scene *s, const char *sprite, uint8_t frame);
 
+/* Map-object state machine (opt-in per scene; the reference runs it as MapObjectThinker, src/map_objects.rs:62-121 — DESIGN.md
+ * section 8d).  The state table is the CALLER's (the reference's info::STATES / MAP_OBJECT_INFOS, or a mod's): the library ships none.
+ *   dg_state_rec      one state: sprite (4 characters, not terminated), frame (0 = 'A'), full_bright, tics (-1: for ever, 0: one
+ *                     tic, n: n tics), next_state.  Row 0 is S_NULL: an object in it is not drawn.  `action` is not used (nor by the reference).
+ *   dg_mobj_info_rec  one thing type: doomednum and its spawn, death and xdeath states.  A later row of the same doomednum wins.
+ *   DG_MOBJ_THINKERS  every map object whose type has a row and whose spawn chain is live is drawn in the state its thinker shows after
+ *                     tics = (timestamp * 35.0f) as u32 (saturating, NaN and <= 0: 0) calls of mutate(), the scene's events in between.
+ * A chain is every state reachable from a start state through next_state; it is live when each of its states other than row 0
+ * resolves as dg_scene_sprite_frame would.  An object without a row or a live spawn chain is drawn as without the setting.
+ * Per view and object: a dg_view_state entry wins, else the thinker's state, else the scene's (dg_scene_set_mobj_state).
+ * Every front end gives the same pixels; the 2-D map view and dg_draw_lists ignore the setting (list-path callers: dg_scene_mobj_states_at). */
+typedef struct dg_state_rec { char sprite[4]; uint8_t frame; uint8_t full_bright; int16_t tics; int32_t next_state; } dg_state_rec;
+typedef struct dg_mobj_info_rec { int32_t doomednum, spawn_state, death_state, xdeath_state; } dg_mobj_info_rec;
+#define DG_MOBJ_THINKERS 1u
+/* Copies both tables, decodes the sprite frames of the live chains (new ids are appended, none moves) and drops the event list.
+ * Takes effect at the next dg_upload_scene; dg_build_lists and dg_scene_mobj_states_at see it at once.  flags 0 turns the setting off
+ * and drops the tables (the table arguments are not read).  DG_ERR_INVALID: a NULL scene or table, unknown bits, n_states outside
+ * [1, 65536], n_infos < 0, tics < -1 (the reference's i16 count would wrap below -1: out of contract), a next_state or an info state
+ * outside [0, n_states).  DG_ERR_WAD: a sprite lump of a live chain does not decode. */
+int dg_scene_set_mobj_thinkers(dg_scene *s, uint32_t flags, const dg_state_rec *states, int n_states,
+                               const dg_mobj_info_rec *infos, int n_infos);
+/* The reference's everything-keys at tics E = (timestamp * 35.0f) as u32, after the E-th mutate and before the next:
+ *   DG_MOBJ_KILL     to the type's death_state unless that is 0
+ *   DG_MOBJ_EXPLODE  to its xdeath_state unless that is 0, else as DG_MOBJ_KILL
+ *   DG_MOBJ_RESPAWN  to its spawn_state
+ * An event whose target chain is not live does not move that object.  The events are part of the setting: a list of at most 16 per
+ * scene, in non-decreasing tics (of equal tics the later call acts last), which a ctx takes at dg_upload_scene.  what = 0 clears the list.
+ * DG_ERR_INVALID: a NULL scene, the setting off, another `what`, tics below the last event's, a 17th event. */
+#define DG_MOBJ_KILL 1
+#define DG_MOBJ_EXPLODE 2
+#define DG_MOBJ_RESPAWN 3
+int dg_scene_mobj_event(dg_scene *s, int what, float timestamp);
+/* Every map object's state at `timestamp` as this library draws it with no view state (out[i].mobj = i): the thinker's state for an
+ * object it drives, else the scene's.  n must equal dg_scene_mobj_count. */
+int dg_scene_mobj_states_at(const dg_scene *s, float timestamp, dg_mobj_state *out, int n);
+
 /* ---- context ------------------------------------------------------------------------------------------------ */
 typedef struct dg_config {
     int32_t device;        /* HIP device ordinal */

@@ -49,6 +49,16 @@ pub const DG_FE_MAP: i32 = 4;              // dg_timing.front_end of a map submi
 pub const DG_WALL_ANIMATE: u32 = 1;         // dg_scene_set_wall_effects flags
 pub const DG_WALL_SCROLL: u32 = 2;
 pub const DG_LIGHT_THINKERS: u32 = 1;       // dg_scene_set_light_effects flag
+pub const DG_MOBJ_THINKERS: u32 = 1;        // dg_scene_set_mobj_thinkers flag
+pub const DG_MOBJ_KILL: c_int = 1;          // dg_scene_mobj_event
+pub const DG_MOBJ_EXPLODE: c_int = 2;
+pub const DG_MOBJ_RESPAWN: c_int = 3;
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct dg_state_rec { pub sprite: [u8; 4], pub frame: u8, pub full_bright: u8, pub tics: i16, pub next_state: i32 }
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct dg_mobj_info_rec { pub doomednum: i32, pub spawn_state: i32, pub death_state: i32, pub xdeath_state: i32 }
 
 extern "C" {
     pub fn dg_scene_load_wad(wad: *const u8, len: usize, map_name: *const c_char, out: *mut *mut dg_scene) -> c_int;
@@ -63,6 +73,10 @@ extern "C" {
     pub fn dg_scene_wall_texture_id(s: *const dg_scene, name: *const c_char, timestamp: f32) -> c_int;
     pub fn dg_scene_set_light_effects(s: *mut dg_scene, flags: u32, seed: u64) -> c_int;
     pub fn dg_scene_sector_lights_at(s: *const dg_scene, timestamp: f32, out: *mut i16, n: c_int) -> c_int;
+    pub fn dg_scene_set_mobj_thinkers(s: *mut dg_scene, flags: u32, states: *const dg_state_rec, n_states: c_int,
+                                      infos: *const dg_mobj_info_rec, n_infos: c_int) -> c_int;
+    pub fn dg_scene_mobj_event(s: *mut dg_scene, what: c_int, timestamp: f32) -> c_int;
+    pub fn dg_scene_mobj_states_at(s: *const dg_scene, timestamp: f32, out: *mut dg_mobj_state, n: c_int) -> c_int;
     pub fn dg_scene_sprite_bitmap_id(s: *const dg_scene, sprite: *const c_char, frame: u8, rotation: u8) -> c_int;
     pub fn dg_scene_sprite_frame(s: *mut dg_scene, sprite: *const c_char, frame: u8) -> c_int;
     pub fn dg_scene_sector_count(s: *const dg_scene) -> c_int;
@@ -124,6 +138,29 @@ pub fn set_wall_effects(scene: *mut dg_scene, flags: u32) {
 pub fn set_light_effects(scene: *mut dg_scene, flags: u32, seed: u64) {
     let rc = unsafe { dg_scene_set_light_effects(scene, flags, seed) };
     if rc < 0 { panic!("dg_scene_set_light_effects: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
+}
+
+/// Game::new, before dg_upload_scene: let the library run the map-object state machine (map_objects.rs:62-121) as a function of the
+/// timestamp, for callers that run no thinkers.  The tables are info::STATES / MAP_OBJECT_INFOS as they stand: StateId values are the
+/// rows' indices (S_NULL = 0).  A game that runs `init_thinkers` itself keeps `sync_state` and leaves this off.
+pub fn set_mobj_thinkers(scene: *mut dg_scene, flags: u32) {
+    let states: Vec<dg_state_rec> = crate::info::STATES.iter().map(|st| {
+        let name = format!("{:?}", st.sprite);
+        let mut sprite = [0u8; 4];
+        for (d, b) in sprite.iter_mut().zip(name.bytes()) { *d = b; }
+        dg_state_rec { sprite, frame: st.frame, full_bright: st.full_bright as u8, tics: st.tics, next_state: st.next_state as i32 }
+    }).collect();
+    let infos: Vec<dg_mobj_info_rec> = crate::info::MAP_OBJECT_INFOS.iter().map(|i| dg_mobj_info_rec {
+        doomednum: i.id as i32, spawn_state: i.spawn_state as i32, death_state: i.death_state as i32, xdeath_state: i.xdeath_state as i32,
+    }).collect();
+    let rc = unsafe { dg_scene_set_mobj_thinkers(scene, flags, states.as_ptr(), states.len() as c_int, infos.as_ptr(), infos.len() as c_int) };
+    if rc < 0 { panic!("dg_scene_set_mobj_thinkers: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
+}
+
+/// The K / X / R keys (kill_everything, explode_everything, respawn_everything) at `timestamp`; takes effect at the next dg_upload_scene.
+pub fn mobj_event(scene: *mut dg_scene, what: c_int, timestamp: f32) {
+    let rc = unsafe { dg_scene_mobj_event(scene, what, timestamp) };
+    if rc < 0 { panic!("dg_scene_mobj_event: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
 }
 
 pub fn preload_sprite_frames(scene: *mut dg_scene) {
