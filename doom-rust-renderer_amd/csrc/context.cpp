@@ -12,6 +12,7 @@
 //   per ctx : 2-D map view layer 3*W*H bytes RGB24 (allocated by the first map submission, rebuilt after every dg_upload_scene)
 //             DG_FE_DEVICE column scratch [F][slot][W]: compact spans 16 B (48 slots), wall-record columns 8 B (48 slots),
 //             counts, sky event bits — shared by the slots because their kernels run back to back
+// The exact order and offsets of every slab's pieces: slab_layout.h.
 #include <hip/hip_runtime_api.h>
 #include <sched.h>
 
@@ -39,6 +40,7 @@
 #include "kernels.hpp"
 #include "map_kernels.hpp"
 #include "scene.hpp"
+#include "slab_layout.h"
 
 using namespace dg;
 
@@ -110,6 +112,27 @@ private:
     bool stop_ = false;
 };
 
+// Move-only owners of device memory (hipMalloc) and pinned host memory (hipHostMalloc).  Whoever destroys one has made the owning
+// ctx's device current and synchronised the streams that may still use the memory (free_ctx, dg_upload_scene).
+struct DevMem {
+    static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    void operator()(void *p) const { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    void operator()(void *p) const { (void)hipHostFree(p); }
+};
+template <class T> using DevPtr = std::unique_ptr<T, DevMem>;
+template <class T> using PinnedPtr = std::unique_ptr<T, PinnedMem>;
+// (Re)allocate: what p held is freed first, and p stays empty when the allocation fails.
+template <class T, class Mem> hipError_t hip_alloc(std::unique_ptr<T, Mem> &p, size_t bytes) {
+    p.reset();
+    void *q = nullptr;
+    const hipError_t e = Mem::alloc(&q, bytes);
+    if (e == hipSuccess) p.reset(static_cast<T *>(q));
+    return e;
+}
+
 struct Slot {
     hipStream_t stream = nullptr;
     // timing events, attached to the dispatches themselves (kernels.hpp): first / last front-end kernel, raster launch; ev_raster is also
@@ -120,10 +143,10 @@ struct Slot {
     uint8_t *copy_out = nullptr;         // pending asynchronous readback (re-issued if the batch has to be redone)
     int copy_first = 0, copy_count = 0;
     bool copy_pending = false;
-    uint8_t *h_lists = nullptr;   // pinned staging
-    uint8_t *d_lists = nullptr;
-    DevRSpan *d_rspans = nullptr;
-    uint8_t *d_fb = nullptr;
+    PinnedPtr<uint8_t> h_lists;   // pinned staging
+    DevPtr<uint8_t> d_lists;
+    DevPtr<DevRSpan> d_rspans;
+    DevPtr<uint8_t> d_fb;
     size_t lists_cap = 0;
     // last submission
     RasterParams P{};
@@ -133,24 +156,32 @@ struct Slot {
     float host_ms = 0.0f;         // list generation + binning + packing of the last submission
     bool busy = false, timed = false;
     // device column walk (DG_FE_DEVICE)
-    uint8_t *h_fe = nullptr, *d_fe = nullptr;   // record slab: pinned staging / HBM
-    uint32_t *d_fe_coloff = nullptr;
-    uint32_t *h_status = nullptr;               // pinned host memory the walk's kernels write: [F] overflow flags, [F] spans per frame
-    uint64_t *d_events = nullptr;               // sky event bits (fe_event_words), zeroed before every walk
-    size_t flags_bytes = 0, walk_state_bytes = 0;   // the flag words + order counters; the whole allocation with the event bits
+    PinnedPtr<uint8_t> h_fe;                    // record slab: pinned staging
+    DevPtr<uint8_t> d_fe;                       // ... and HBM
+    DevPtr<uint32_t> d_fe_coloff;
+    PinnedPtr<uint32_t> h_status;               // pinned host memory the walk's kernels write: [F] overflow flags, [F] spans per frame
+    uint64_t *d_events = nullptr;               // sky event bits (fe_event_words), zeroed before every walk: inside d_flags' allocation
+    size_t walk_state_bytes = 0;                // that whole allocation (dg_create)
     bool walk_state_clean = false;              // d_flags .. is all zero (dg_fe_scan cleans up after the walk; enqueue_kernels clears a slot that is not)
-    uint32_t *d_order = nullptr;                // dg_fe_columns' launch-order lists as dg_fs_frame builds them (FsParams::order_list)
-    uint32_t *d_flags = nullptr;                // [F] overflow flags the walk's kernels OR into; sits in front of d_events (one memset clears both)
+    DevPtr<uint32_t> d_order;                   // dg_fe_columns' launch-order lists as dg_fs_frame builds them (FsParams::order_list)
+    DevPtr<uint32_t> d_flags;                   // [F] overflow flags the walk's kernels OR into; sits in front of d_events (one memset clears both)
     FeParams FP{};
     FsParams FSP{};               // DG_FE_DEVICE_SEGS: the device seg walk in front of the column walk
     LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
     MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
-    bool fs_mode = false;         // the last submission's per-seg half ran on the GPU too
+    // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
+    // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too) or DG_FE_MAP (2-D map frames: arrow lines at the start of d_lists)
+    int32_t front_end = DG_FE_HOST;
+    // A new submission of n frames through front end fe, `bytes` of lists or records uploaded for it (span statistics: the host list path's alone)
+    void describe(int32_t fe, int n, uint64_t bytes, uint64_t walls, uint64_t planes) {
+        front_end = fe; fe_check = false; n_frames = n; list_bytes = bytes; n_walls = walls; n_planes = planes;
+        max_spans = 0; n_spans = 0; covered = 0;
+    }
+    bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
+    bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
-    bool fe_mode = false;         // the last submission went through the device column walk
-    bool map_mode = false;        // the last submission was 2-D map frames (dg_submit_map_views): arrow lines at the start of d_lists
-    bool map_built = false;       // ... and its enqueue built the ctx's map layer (ev_start .. ev_setup time that)
-    bool fe_check = false;        // ... and its overflow flags have not been looked at yet
+    bool map_built = false;       // a map submission whose enqueue built the ctx's map layer (ev_start .. ev_setup time that)
+    bool fe_check = false;        // a column-walk submission whose overflow flags have not been looked at yet
     std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
     // ... and a private copy of their game-state snapshots (the caller's arrays need not outlive the call)
     std::vector<dg_view_state> states;
@@ -220,10 +251,11 @@ struct dg_ctx {
     const Scene *scene = nullptr;
     size_t uploaded_texels = 0;         // texel pool size at dg_upload_scene time (grows when new sprite bitmaps are decoded)
     // device scene
-    uint32_t *d_palette = nullptr;      // 256 x u32 RGBX, followed by 256 x (r, g, b, 0) f32
-    uint8_t *d_texel_idx = nullptr, *d_texel_opq = nullptr, *d_flats = nullptr;
-    unsigned long long *d_checksums = nullptr;   // dg_frame_checksums scratch, max_batch entries
-    uint4 *d_row_tab = nullptr;         // per-row constants of the flat / sky mappers (dg_row_table), rebuilt per scene upload
+    DevPtr<uint32_t> d_palette;         // 256 x u32 RGBX, followed by 256 x (r, g, b, 0) f32
+    DevPtr<uint8_t> d_texel_idx, d_texel_opq;
+    uint8_t *d_flats = nullptr;         // inside d_texel_idx's allocation
+    DevPtr<unsigned long long> d_checksums;      // dg_frame_checksums scratch, max_batch entries
+    DevPtr<uint4> d_row_tab;            // per-row constants of the flat / sky mappers (dg_row_table), rebuilt per scene upload
     DevScene dscene{};
     std::vector<Slot> slots;
     hipStream_t kstream = nullptr;      // every kernel of every slot, in submission order (enqueue_kernels)
@@ -249,40 +281,38 @@ struct dg_ctx {
     int since_probe = 0;                // seg-walk batches since the host walker was last timed (it is timed again every 32 batches)
     int since_fs_probe = 0;             // host-walker batches since the seg walk was last timed (likewise)
     int gpu_samples[2] = {0, 0};        // finished batches seen per mode (host per-seg half / seg walk): the first of each runs on cold caches and clocks, not counted
-    uint8_t *d_fs_scene = nullptr;
+    DevPtr<uint8_t> d_fs_scene;
     // wall effects: the scene's WallFx as of dg_upload_scene (every front end draws with this copy), and for the seg walk its device tables
     WallFx fx;
-    uint8_t *d_wall_fx = nullptr;       // FsSegFx per seg | the live animation lists (only while fx.on() and the seg walk is uploaded)
+    DevPtr<uint8_t> d_wall_fx;          // FsSegFx per seg | the live animation lists (only while fx.on() and the seg walk is uploaded)
     FsFx fs_fx{};
     // light effects: the scene's LightFx as of dg_upload_scene (likewise), and for the seg walk its records, tables and per-sector map
     LightFx lfx;
-    uint8_t *d_light_fx = nullptr;      // LfxRec per effect sector | rec_of per sector | tables (only while lfx.on() and the seg walk is uploaded)
+    DevPtr<uint8_t> d_light_fx;         // LfxRec per effect sector | rec_of per sector | tables (only while lfx.on() and the seg walk is uploaded)
     LfxRows lfx_proto{};                // its pointers and the seed, filled at upload
     // map-object thinkers: the scene's MobjFx as of dg_upload_scene (likewise), and for the seg walk its tables
     MobjFx mfx;
-    uint8_t *d_mobj_fx = nullptr;       // steps | chains | types | type_of per map object | events (only while mfx.on() and the seg walk is uploaded)
+    DevPtr<uint8_t> d_mobj_fx;          // steps | chains | types | type_of per map object | events (only while mfx.on() and the seg walk is uploaded)
     MfxRows mfx_proto{};                // its pointers and counts, filled at upload
-    uint8_t *d_fs_scratch = nullptr;    // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
+    DevPtr<uint8_t> d_fs_scratch;       // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
     size_t fs_zero_bytes = 0;
     FsParams fs_proto{};                // scene pointers and counts, filled at upload
     uint64_t fallbacks_fe = 0;          // batches in which frames were redone because a device-side capacity was exceeded (dg_ctx_fallbacks)
     uint64_t redone_frames = 0;         // frames redone through the host list path, one at a time (dg_ctx_redone_frames)
-    DevRSpan *d_redo_rspans = nullptr;  // resolved spans of ONE frame being redone (allocated on first use)
+    DevPtr<DevRSpan> d_redo_rspans;     // resolved spans of ONE frame being redone (allocated on first use)
     size_t redo_span_cap = 0;
     std::vector<FeFrameOut> fe_out;     // one per frame of a batch
     uint32_t fe_col_slots = FE_DEFAULT_COL_SLOTS;
     size_t fe_part_cap = 0, fe_sprite_cap = 0, fe_behind_cap = 0, fe_bin_cap = 0, fe_sbin_cap = 0, fe_slab_cap = 0;
-    uint32_t *d_fe_cnt = nullptr;
-    FeU4 *d_fe_cspans = nullptr;
-    FeColRec *d_fe_recs = nullptr;
+    DevPtr<uint32_t> d_fe_cnt;
+    DevPtr<FeU4> d_fe_cspans;
+    DevPtr<FeColRec> d_fe_recs;
     // 2-D map view: every drawn linedef of the uploaded scene, RGB24, built by the first map submission after dg_upload_scene
-    uint8_t *d_map_layer = nullptr;
+    DevPtr<uint8_t> d_map_layer;
     bool map_layer_ok = false;
 };
 
 namespace {
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // CPUs' worth of run time the container allows this process (cgroup v2 cpu.max, v1 cfs quota), rounded up; 0 = no limit / unknown.
 int cgroup_cpu_quota() {
@@ -305,6 +335,7 @@ hipError_t slot_sync(Slot &s) {
     return hipStreamSynchronize(s.stream);
 }
 
+// The members' owners free the memory: with the ctx's device current, and only after every stream that may still use it has drained.
 void free_ctx(dg_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
@@ -312,51 +343,78 @@ void free_ctx(dg_ctx *c) {
     if (c->rstream) (void)hipStreamSynchronize(c->rstream);
     for (Slot &s : c->slots) {
         if (s.stream) (void)hipStreamSynchronize(s.stream);
-        if (s.h_lists) (void)hipHostFree(s.h_lists);
-        if (s.d_lists) (void)hipFree(s.d_lists);
-        if (s.d_rspans) (void)hipFree(s.d_rspans);
-        if (s.d_fb) (void)hipFree(s.d_fb);
-        if (s.h_fe) (void)hipHostFree(s.h_fe);
-        if (s.d_fe) (void)hipFree(s.d_fe);
-        if (s.d_fe_coloff) (void)hipFree(s.d_fe_coloff);
-        if (s.d_order) (void)hipFree(s.d_order);
-        if (s.d_flags) (void)hipFree(s.d_flags);    // (d_events lies inside this allocation)
-        if (s.h_status) (void)hipHostFree(s.h_status);
-        if (s.ev_start) (void)hipEventDestroy(s.ev_start);
-        if (s.ev_setup) (void)hipEventDestroy(s.ev_setup);
-        if (s.ev_raster) (void)hipEventDestroy(s.ev_raster);
-        if (s.ev_rstart) (void)hipEventDestroy(s.ev_rstart);
-        if (s.ev_h2d) (void)hipEventDestroy(s.ev_h2d);
-        if (s.copy_stream) { (void)hipStreamSynchronize(s.copy_stream); (void)hipStreamDestroy(s.copy_stream); }
+        if (s.copy_stream) (void)hipStreamSynchronize(s.copy_stream);
+        for (hipEvent_t ev : {s.ev_start, s.ev_setup, s.ev_raster, s.ev_rstart, s.ev_h2d})
+            if (ev) (void)hipEventDestroy(ev);
+        if (s.copy_stream) (void)hipStreamDestroy(s.copy_stream);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
     if (c->kstream) (void)hipStreamDestroy(c->kstream);
     if (c->rstream) (void)hipStreamDestroy(c->rstream);
-    if (c->d_palette) (void)hipFree(c->d_palette);
-    if (c->d_texel_idx) (void)hipFree(c->d_texel_idx);
-    if (c->d_texel_opq) (void)hipFree(c->d_texel_opq);
-    if (c->d_row_tab) (void)hipFree(c->d_row_tab);
-    if (c->d_redo_rspans) (void)hipFree(c->d_redo_rspans);
-    if (c->d_checksums) (void)hipFree(c->d_checksums);
-    if (c->d_fe_cnt) (void)hipFree(c->d_fe_cnt);
-    if (c->d_fe_cspans) (void)hipFree(c->d_fe_cspans);
-    if (c->d_fe_recs) (void)hipFree(c->d_fe_recs);
-    if (c->d_fs_scene) (void)hipFree(c->d_fs_scene);
-    if (c->d_fs_scratch) (void)hipFree(c->d_fs_scratch);
-    if (c->d_wall_fx) (void)hipFree(c->d_wall_fx);
-    if (c->d_light_fx) (void)hipFree(c->d_light_fx);
-    if (c->d_mobj_fx) (void)hipFree(c->d_mobj_fx);
-    if (c->d_map_layer) (void)hipFree(c->d_map_layer);
     delete c;
+}
+
+// What every batch builder checks first: a scene is resident, the batch fits, the resident texels are still the scene's.
+int check_batch(const dg_ctx *c, int n) {
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
+    if (c->scene->texel_idx.size() != c->uploaded_texels) return set_err(DG_ERR_INVALID, "the scene decoded new bitmaps since dg_upload_scene: upload it again");
+    return DG_OK;
+}
+
+// One binned frame into list slab `h` laid out as L: frame i of the batch, its records at the bases its header names.
+void pack_binned(uint8_t *h, const ListLayout &L, const BinnedFrame &bf, size_t i, size_t W) {
+    std::memcpy(h + L.frames + i * sizeof(DevFrame), &bf.hdr, sizeof(DevFrame));
+    std::memcpy(h + L.col_off + i * (W + 1) * 4, bf.col_off.data(), (W + 1) * 4);
+    if (!bf.walls.empty()) std::memcpy(h + L.walls + (size_t)bf.hdr.wall_base * sizeof(DevWallRec), bf.walls.data(), bf.walls.size() * sizeof(DevWallRec));
+    if (!bf.planes.empty()) std::memcpy(h + L.planes + (size_t)bf.hdr.plane_base * sizeof(DevPlaneRec), bf.planes.data(), bf.planes.size() * sizeof(DevPlaneRec));
+    if (!bf.spans.empty()) std::memcpy(h + L.spans + (size_t)bf.hdr.span_base * sizeof(DevSpan), bf.spans.data(), bf.spans.size() * sizeof(DevSpan));
+}
+
+// ... and the rasteriser's list pointers into the device copy `d` of such a slab.
+void point_at_lists(RasterParams &P, const uint8_t *d, const ListLayout &L) {
+    P.frames = reinterpret_cast<const DevFrame *>(d + L.frames);
+    P.col_off = reinterpret_cast<const uint32_t *>(d + L.col_off);
+    P.walls = reinterpret_cast<const DevWallRec *>(d + L.walls);
+    P.planes = reinterpret_cast<const DevPlaneRec *>(d + L.planes);
+    P.spans = reinterpret_cast<const DevSpan *>(d + L.spans);
+}
+
+// The part of slot.P that is the same whoever wrote the lists.
+void fill_raster_params(dg_ctx *c, Slot &s, int n) {
+    RasterParams &P = s.P;
+    P.scene = c->dscene;
+    P.k = c->dk;
+    P.rspans = s.d_rspans.get();
+    P.fb = s.d_fb.get();
+    P.row_tab = c->d_row_tab.get();
+    P.n_frames = n;
+}
+
+uint32_t fe_span_stride(const dg_ctx *c) { return (uint32_t)(c->span_cap_per_batch / (size_t)c->cfg.max_batch); }
+
+// The part of slot.FP / slot.P that does not depend on who wrote the records (the host walker or the device seg walk), given F.frames.
+void fill_walk_params(dg_ctx *c, Slot &s, int n) {
+    FeParams &F = s.FP;
+    F.scene = c->dscene;
+    F.k = c->dk;
+    F.cspans = c->d_fe_cspans.get(); F.recs = c->d_fe_recs.get(); F.cnt = c->d_fe_cnt.get();
+    F.events = s.d_events;
+    F.flags = s.d_flags.get();
+    F.host_flags = s.h_status.get(); F.totals = s.h_status.get() + c->cfg.max_batch;  // pinned host memory, written by dg_fe_scan with plain stores
+    F.col_off = s.d_fe_coloff.get(); F.rspans = s.d_rspans.get();
+    F.n_frames = n; F.span_stride = fe_span_stride(c); F.w64 = (uint32_t)((c->cfg.width + 63) / 64); F.col_slots = c->fe_col_slots;
+    fill_raster_params(c, s, n);
+    s.P.frames = F.frames;
+    s.P.col_off = s.d_fe_coloff.get();
+    s.P.walls = nullptr; s.P.planes = nullptr; s.P.spans = nullptr;
 }
 
 // Build + bin the lists of n views in parallel, pack them into the slot's pinned slab, fill slot.P.
 int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
-    if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
+    if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
-    if (sc.texel_idx.size() != c->uploaded_texels) return set_err(DG_ERR_INVALID, "the scene decoded new bitmaps since dg_upload_scene: upload it again");
     const int W = c->cfg.width, H = c->cfg.height;
     std::vector<int> rc((size_t)n, 0);
     std::vector<std::string> errs((size_t)n);
@@ -388,38 +446,15 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
     }
     if (spans > c->span_cap_per_batch || walls > c->wall_cap_per_batch || planes > c->plane_cap_per_batch)
         return set_err(DG_ERR_CAPACITY, "frame lists exceed the slot's list slab");
-    const size_t off_frames = 0;
-    const size_t off_col = align_up(off_frames + (size_t)n * sizeof(DevFrame), 256);
-    const size_t off_walls = align_up(off_col + (size_t)n * (size_t)(W + 1) * 4, 256);
-    const size_t off_planes = align_up(off_walls + walls * sizeof(DevWallRec), 256);
-    const size_t off_spans = align_up(off_planes + planes * sizeof(DevPlaneRec), 256);
-    const size_t total = off_spans + spans * sizeof(DevSpan);
-    if (total > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
-    c->pool->parallel_for(n, [&](int i, int) {
-        const BinnedFrame &bf = c->binned[(size_t)i];
-        std::memcpy(s.h_lists + off_frames + (size_t)i * sizeof(DevFrame), &bf.hdr, sizeof(DevFrame));
-        std::memcpy(s.h_lists + off_col + (size_t)i * (size_t)(W + 1) * 4, bf.col_off.data(), (size_t)(W + 1) * 4);
-        if (!bf.walls.empty()) std::memcpy(s.h_lists + off_walls + (size_t)bf.hdr.wall_base * sizeof(DevWallRec), bf.walls.data(), bf.walls.size() * sizeof(DevWallRec));
-        if (!bf.planes.empty()) std::memcpy(s.h_lists + off_planes + (size_t)bf.hdr.plane_base * sizeof(DevPlaneRec), bf.planes.data(), bf.planes.size() * sizeof(DevPlaneRec));
-        if (!bf.spans.empty()) std::memcpy(s.h_lists + off_spans + (size_t)bf.hdr.span_base * sizeof(DevSpan), bf.spans.data(), bf.spans.size() * sizeof(DevSpan));
-    });
-    RasterParams &P = s.P;
-    P.scene = c->dscene;
-    P.k = c->dk;
-    P.frames = reinterpret_cast<const DevFrame *>(s.d_lists + off_frames);
-    P.col_off = reinterpret_cast<const uint32_t *>(s.d_lists + off_col);
-    P.walls = reinterpret_cast<const DevWallRec *>(s.d_lists + off_walls);
-    P.planes = reinterpret_cast<const DevPlaneRec *>(s.d_lists + off_planes);
-    P.spans = reinterpret_cast<const DevSpan *>(s.d_lists + off_spans);
-    P.rspans = s.d_rspans;
-    P.fb = s.d_fb;
-    P.row_tab = c->d_row_tab;
-    P.n_frames = n;
-    s.max_spans = max_spans; s.n_spans = spans; s.covered = covered; s.n_frames = n; s.n_walls = walls; s.n_planes = planes;
-    s.list_bytes = total;
-    s.fe_mode = false; s.fs_mode = false; s.fe_check = false; s.map_mode = false;
+    const ListLayout L = list_layout((size_t)n, (size_t)W, walls, planes, spans);
+    if (L.total > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
+    c->pool->parallel_for(n, [&](int i, int) { pack_binned(s.h_lists.get(), L, c->binned[(size_t)i], (size_t)i, (size_t)W); });
+    fill_raster_params(c, s, n);
+    point_at_lists(s.P, s.d_lists.get(), L);
+    s.describe(DG_FE_HOST, n, L.total, walls, planes);
+    s.max_spans = max_spans; s.n_spans = spans; s.covered = covered;
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(s.d_lists, s.h_lists, total, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), L.total, hipMemcpyHostToDevice, s.stream));
     return DG_OK;
 }
 
@@ -427,10 +462,8 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
 // fill slot.FP / slot.P.  Returns kPartsUnsupported when the batch has to go through build_batch_host instead.
 int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
-    if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
+    if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
-    if (sc.texel_idx.size() != c->uploaded_texels) return set_err(DG_ERR_INVALID, "the scene decoded new bitmaps since dg_upload_scene: upload it again");
     const int W = c->cfg.width, H = c->cfg.height;
     std::vector<int> rc((size_t)n, 0);
     std::vector<std::string> errs((size_t)n);
@@ -464,22 +497,11 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     }
     if (parts > c->fe_part_cap || sprites > c->fe_sprite_cap || behind > c->fe_behind_cap || bins > c->fe_bin_cap || sbins > c->fe_sbin_cap)
         return kPartsUnsupported;
-    const size_t nb1 = (size_t)(W + FE_BIN_W - 1) / FE_BIN_W + 1;
-    const uint32_t span_stride = (uint32_t)(c->span_cap_per_batch / (size_t)c->cfg.max_batch);
-    const size_t off_frames = 0;
-    const size_t off_ff = align_up(off_frames + (size_t)n * sizeof(DevFrame), 256);
-    const size_t off_parts = align_up(off_ff + (size_t)n * sizeof(FeFrame), 256);
-    const size_t off_sprites = align_up(off_parts + parts * sizeof(FePart), 256);
-    const size_t off_behind = align_up(off_sprites + sprites * sizeof(FeSprite), 256);
-    const size_t off_sky = align_up(off_behind + behind * 4, 256);
-    const size_t off_boff = align_up(off_sky + skies * 4, 256);
-    const size_t off_sboff = align_up(off_boff + (size_t)n * nb1 * 4, 256);
-    const size_t off_bins = align_up(off_sboff + (size_t)n * nb1 * 4, 256);
-    const size_t off_sbins = align_up(off_bins + bins * 2, 256);
-    const size_t groups = (size_t)(W + 255) / 256;                  // dg_fe_columns: one workgroup per (frame, 256 columns)
-    const size_t off_order = align_up(off_sbins + sbins * 2, 256);
-    const size_t total = off_order + (size_t)n * groups * 4;
-    if (total > c->fe_slab_cap) return kPartsUnsupported;
+    const size_t nb1 = fe_bin_offsets((size_t)W), groups = fe_col_groups((size_t)W);
+    const uint32_t span_stride = fe_span_stride(c);
+    const FeLayout L = fe_layout((size_t)n, (size_t)W, parts, sprites, behind, skies, bins, sbins);
+    if (L.total > c->fe_slab_cap) return kPartsUnsupported;
+    uint8_t *const h = s.h_fe.get();
     {   // launch order of dg_fe_columns: heaviest workgroup first (weight = its longest bin: parts + 2 x sprites), counting sort
         std::vector<uint32_t> weight((size_t)n * groups), start(258, 0);
         for (int i = 0; i < n; i++) {
@@ -494,58 +516,40 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
             }
         }
         for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
-        uint32_t *order = reinterpret_cast<uint32_t *>(s.h_fe + off_order);
+        uint32_t *order = reinterpret_cast<uint32_t *>(h + L.order);
         for (size_t it = 0; it < weight.size(); it++) order[start[weight[it]]++] = (uint32_t)it;
     }
     c->pool->parallel_for(n, [&](int i, int) {
         FeFrameOut &o = c->fe_out[(size_t)i];
         const FeFrame &ff = ffs[(size_t)i];
         o.hdr.span_base = (uint32_t)i * span_stride;
-        std::memcpy(s.h_fe + off_frames + (size_t)i * sizeof(DevFrame), &o.hdr, sizeof(DevFrame));
-        std::memcpy(s.h_fe + off_ff + (size_t)i * sizeof(FeFrame), &ff, sizeof(FeFrame));
-        if (!o.parts.empty()) std::memcpy(s.h_fe + off_parts + (size_t)ff.part_base * sizeof(FePart), o.parts.data(), o.parts.size() * sizeof(FePart));
-        if (!o.sprites.empty()) std::memcpy(s.h_fe + off_sprites + (size_t)ff.sprite_base * sizeof(FeSprite), o.sprites.data(), o.sprites.size() * sizeof(FeSprite));
-        if (!o.behind.empty()) std::memcpy(s.h_fe + off_behind + (size_t)ff.behind_base * 4, o.behind.data(), o.behind.size() * 4);
-        if (!o.sky_parts.empty()) std::memcpy(s.h_fe + off_sky + (size_t)ff.sky_base * 4, o.sky_parts.data(), o.sky_parts.size() * 4);
-        std::memcpy(s.h_fe + off_boff + (size_t)i * nb1 * 4, o.bin_off.data(), nb1 * 4);
-        std::memcpy(s.h_fe + off_sboff + (size_t)i * nb1 * 4, o.sbin_off.data(), nb1 * 4);
-        if (!o.bin_parts.empty()) std::memcpy(s.h_fe + off_bins + (size_t)ff.bin_base * 2, o.bin_parts.data(), o.bin_parts.size() * 2);
-        if (!o.sbin_sprites.empty()) std::memcpy(s.h_fe + off_sbins + (size_t)ff.sbin_base * 2, o.sbin_sprites.data(), o.sbin_sprites.size() * 2);
+        std::memcpy(h + L.frames + (size_t)i * sizeof(DevFrame), &o.hdr, sizeof(DevFrame));
+        std::memcpy(h + L.fframes + (size_t)i * sizeof(FeFrame), &ff, sizeof(FeFrame));
+        if (!o.parts.empty()) std::memcpy(h + L.parts + (size_t)ff.part_base * sizeof(FePart), o.parts.data(), o.parts.size() * sizeof(FePart));
+        if (!o.sprites.empty()) std::memcpy(h + L.sprites + (size_t)ff.sprite_base * sizeof(FeSprite), o.sprites.data(), o.sprites.size() * sizeof(FeSprite));
+        if (!o.behind.empty()) std::memcpy(h + L.behind + (size_t)ff.behind_base * 4, o.behind.data(), o.behind.size() * 4);
+        if (!o.sky_parts.empty()) std::memcpy(h + L.sky + (size_t)ff.sky_base * 4, o.sky_parts.data(), o.sky_parts.size() * 4);
+        std::memcpy(h + L.bin_off + (size_t)i * nb1 * 4, o.bin_off.data(), nb1 * 4);
+        std::memcpy(h + L.sbin_off + (size_t)i * nb1 * 4, o.sbin_off.data(), nb1 * 4);
+        if (!o.bin_parts.empty()) std::memcpy(h + L.bins + (size_t)ff.bin_base * 2, o.bin_parts.data(), o.bin_parts.size() * 2);
+        if (!o.sbin_sprites.empty()) std::memcpy(h + L.sbins + (size_t)ff.sbin_base * 2, o.sbin_sprites.data(), o.sbin_sprites.size() * 2);
     });
+    const uint8_t *const d = s.d_fe.get();
     FeParams &F = s.FP;
-    F.scene = c->dscene;
-    F.k = c->dk;
-    F.frames = reinterpret_cast<const DevFrame *>(s.d_fe + off_frames);
-    F.fframes = reinterpret_cast<const FeFrame *>(s.d_fe + off_ff);
-    F.parts = reinterpret_cast<const FePart *>(s.d_fe + off_parts);
-    F.sprites = reinterpret_cast<const FeSprite *>(s.d_fe + off_sprites);
-    F.behind = reinterpret_cast<const uint32_t *>(s.d_fe + off_behind);
-    F.sky_parts = reinterpret_cast<const uint32_t *>(s.d_fe + off_sky);
+    F.frames = reinterpret_cast<const DevFrame *>(d + L.frames);
+    F.fframes = reinterpret_cast<const FeFrame *>(d + L.fframes);
+    F.parts = reinterpret_cast<const FePart *>(d + L.parts);
+    F.sprites = reinterpret_cast<const FeSprite *>(d + L.sprites);
+    F.behind = reinterpret_cast<const uint32_t *>(d + L.behind);
+    F.sky_parts = reinterpret_cast<const uint32_t *>(d + L.sky);
     F.max_sky_slots = max_sky; F.gap_waves = 0;
-    F.bin_off = reinterpret_cast<const uint32_t *>(s.d_fe + off_boff);
-    F.sbin_off = reinterpret_cast<const uint32_t *>(s.d_fe + off_sboff);
-    F.bin_parts = reinterpret_cast<const uint16_t *>(s.d_fe + off_bins);
-    F.sbin_sprites = reinterpret_cast<const uint16_t *>(s.d_fe + off_sbins);
-    F.order = reinterpret_cast<const uint32_t *>(s.d_fe + off_order); F.order_cnt = nullptr;
-    F.cspans = c->d_fe_cspans; F.recs = c->d_fe_recs; F.cnt = c->d_fe_cnt;
-    F.events = s.d_events;
-    F.flags = s.d_flags;
-    F.host_flags = s.h_status; F.totals = s.h_status + c->cfg.max_batch;  // pinned host memory, written by dg_fe_scan with plain stores
-    F.col_off = s.d_fe_coloff; F.rspans = s.d_rspans;
-    F.n_frames = n; F.span_stride = span_stride; F.w64 = (uint32_t)((W + 63) / 64); F.col_slots = c->fe_col_slots;
-    RasterParams &P = s.P;
-    P.scene = c->dscene;
-    P.k = c->dk;
-    P.frames = F.frames;
-    P.col_off = s.d_fe_coloff;
-    P.walls = nullptr; P.planes = nullptr; P.spans = nullptr;
-    P.rspans = s.d_rspans;
-    P.fb = s.d_fb;
-    P.row_tab = c->d_row_tab;
-    P.n_frames = n;
-    s.max_spans = 0; s.n_spans = 0; s.covered = 0; s.n_frames = n; s.n_walls = parts; s.n_planes = sprites;
-    s.list_bytes = total;
-    s.fe_mode = true; s.fs_mode = false; s.fe_check = false; s.map_mode = false;
+    F.bin_off = reinterpret_cast<const uint32_t *>(d + L.bin_off);
+    F.sbin_off = reinterpret_cast<const uint32_t *>(d + L.sbin_off);
+    F.bin_parts = reinterpret_cast<const uint16_t *>(d + L.bins);
+    F.sbin_sprites = reinterpret_cast<const uint16_t *>(d + L.sbins);
+    F.order = reinterpret_cast<const uint32_t *>(d + L.order); F.order_cnt = nullptr;
+    fill_walk_params(c, s, n);
+    s.describe(DG_FE_DEVICE, n, L.total, parts, sprites);
     s.views.assign(views, views + n);
     s.keep_states(states, n);
     s.snapshot_scene(sc);
@@ -554,108 +558,91 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         const double v = (double)s.host_ms / n;
         c->ema_host = c->host_samples == 2 ? v : 0.75 * c->ema_host + 0.25 * v;
     }
-    HIP_TRY(hipMemcpyAsync(s.d_fe, s.h_fe, total, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.d_fe.get(), s.h_fe.get(), L.total, hipMemcpyHostToDevice, s.stream));
     return DG_OK;
 }
 
-// DG_FE_DEVICE_SEGS: the scene's per-seg / per-sprite tables and BSP tables (Scene::rebuild_fs_tables) in one device allocation, and the
-// per-batch scratch of the seg walk, whose size follows the scene (segs, leaves).
+// Host tables packed into one device allocation: each starts on a 256-byte boundary and takes at least 16 bytes (an empty table
+// still has an address of its own).  add() the tables, upload() them (one hipMalloc, one copy), then at<T>() what add() returned.
+struct TablePack {
+    std::vector<uint8_t> staged;
+    SlabCursor cur;
+    const uint8_t *base = nullptr;
+    template <class T> size_t add(const std::vector<T> &v) {
+        const size_t at = cur.take(std::max<size_t>(v.size() * sizeof(T), 16));
+        staged.resize(cur.next);
+        if (!v.empty()) std::memcpy(staged.data() + at, v.data(), v.size() * sizeof(T));
+        return at;
+    }
+    hipError_t upload(DevPtr<uint8_t> &mem) {
+        const hipError_t e = hip_alloc(mem, staged.size());
+        base = mem.get();
+        return e != hipSuccess ? e : hipMemcpy(mem.get(), staged.data(), staged.size(), hipMemcpyHostToDevice);
+    }
+    template <class T> const T *at(size_t off) const { return reinterpret_cast<const T *>(base + off); }
+};
+
+// DG_FE_DEVICE_SEGS: the scene's per-seg / per-sprite tables and BSP tables (Scene::rebuild_fs_tables) in one device allocation, the
+// tables of the effects that are on in one each, and the per-batch scratch of the seg walk, whose size follows the scene (segs, leaves).
 int upload_fs_scene(dg_ctx *c, const Scene &sc) {
-    if (c->d_fs_scene) { (void)hipFree(c->d_fs_scene); c->d_fs_scene = nullptr; }
-    if (c->d_fs_scratch) { (void)hipFree(c->d_fs_scratch); c->d_fs_scratch = nullptr; }
-    if (c->d_wall_fx) { (void)hipFree(c->d_wall_fx); c->d_wall_fx = nullptr; }
+    c->d_fs_scene.reset(); c->d_fs_scratch.reset(); c->d_wall_fx.reset(); c->d_light_fx.reset(); c->d_mobj_fx.reset();
     c->fs_fx = FsFx{};
     if (c->fx.on()) {                                   // the wall effects' tables: only for a scene that has them on (dg_wfx_* read them)
-        const size_t seg_bytes = c->fx.seg.size() * sizeof(FsSegFx), at_lists = align_up(std::max<size_t>(seg_bytes, 16), 256);
-        const size_t list_bytes = c->fx.lists.size() * sizeof(FsAnim);
-        HIP_TRY(hipMalloc((void **)&c->d_wall_fx, at_lists + std::max<size_t>(list_bytes, 16)));
-        if (seg_bytes) HIP_TRY(hipMemcpy(c->d_wall_fx, c->fx.seg.data(), seg_bytes, hipMemcpyHostToDevice));
-        if (list_bytes) HIP_TRY(hipMemcpy(c->d_wall_fx + at_lists, c->fx.lists.data(), list_bytes, hipMemcpyHostToDevice));
-        c->fs_fx = FsFx{reinterpret_cast<const FsSegFx *>(c->d_wall_fx), reinterpret_cast<const FsAnim *>(c->d_wall_fx + at_lists)};
+        TablePack t;
+        const size_t seg = t.add(c->fx.seg), lists = t.add(c->fx.lists);
+        HIP_TRY(t.upload(c->d_wall_fx));
+        c->fs_fx = FsFx{t.at<FsSegFx>(seg), t.at<FsAnim>(lists)};
     }
-    if (c->d_light_fx) { (void)hipFree(c->d_light_fx); c->d_light_fx = nullptr; }
     c->lfx_proto = LfxRows{};
     if (c->lfx.on()) {                                  // the light effects' records and tables: only for a scene that has them on (dg_light_rows reads them)
-        const size_t rec_bytes = c->lfx.recs.size() * sizeof(LfxRec), map_bytes = c->lfx.rec_of.size() * 4, tab_bytes = c->lfx.tab.size() * 4;
-        const size_t at_map = align_up(rec_bytes, 256), at_tab = align_up(at_map + map_bytes, 256);
-        HIP_TRY(hipMalloc((void **)&c->d_light_fx, at_tab + std::max<size_t>(tab_bytes, 16)));
-        HIP_TRY(hipMemcpy(c->d_light_fx, c->lfx.recs.data(), rec_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_light_fx + at_map, c->lfx.rec_of.data(), map_bytes, hipMemcpyHostToDevice));
-        if (tab_bytes) HIP_TRY(hipMemcpy(c->d_light_fx + at_tab, c->lfx.tab.data(), tab_bytes, hipMemcpyHostToDevice));
-        c->lfx_proto.recs = reinterpret_cast<const LfxRec *>(c->d_light_fx);
-        c->lfx_proto.rec_of = reinterpret_cast<const int32_t *>(c->d_light_fx + at_map);
-        c->lfx_proto.tab = reinterpret_cast<const uint32_t *>(c->d_light_fx + at_tab);
+        TablePack t;
+        const size_t recs = t.add(c->lfx.recs), rec_of = t.add(c->lfx.rec_of), tab = t.add(c->lfx.tab);
+        HIP_TRY(t.upload(c->d_light_fx));
+        c->lfx_proto.recs = t.at<LfxRec>(recs);
+        c->lfx_proto.rec_of = t.at<int32_t>(rec_of);
+        c->lfx_proto.tab = t.at<uint32_t>(tab);
         c->lfx_proto.seed = c->lfx.seed;
         c->lfx_proto.n_sectors = (uint32_t)c->lfx.rec_of.size();
     }
-    if (c->d_mobj_fx) { (void)hipFree(c->d_mobj_fx); c->d_mobj_fx = nullptr; }
     c->mfx_proto = MfxRows{};
     if (c->mfx.on()) {                                  // the map-object thinkers' tables: only for a scene that has them on (dg_mobj_rows reads them)
-        const size_t step_bytes = c->mfx.steps.size() * sizeof(MfxStep), chain_bytes = c->mfx.chains.size() * sizeof(MfxChain);
-        const size_t type_bytes = c->mfx.types.size() * sizeof(MfxType), map_bytes = c->mfx.type_of.size() * 4, ev_bytes = c->mfx.events.size() * sizeof(MfxEvent);
-        const size_t at_chains = align_up(step_bytes, 256), at_types = align_up(at_chains + chain_bytes, 256);
-        const size_t at_map = align_up(at_types + type_bytes, 256), at_ev = align_up(at_map + map_bytes, 256);
-        HIP_TRY(hipMalloc((void **)&c->d_mobj_fx, at_ev + std::max<size_t>(ev_bytes, 16)));
-        HIP_TRY(hipMemcpy(c->d_mobj_fx, c->mfx.steps.data(), step_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_mobj_fx + at_chains, c->mfx.chains.data(), chain_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_mobj_fx + at_types, c->mfx.types.data(), type_bytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_mobj_fx + at_map, c->mfx.type_of.data(), map_bytes, hipMemcpyHostToDevice));
-        if (ev_bytes) HIP_TRY(hipMemcpy(c->d_mobj_fx + at_ev, c->mfx.events.data(), ev_bytes, hipMemcpyHostToDevice));
-        c->mfx_proto.steps = reinterpret_cast<const MfxStep *>(c->d_mobj_fx);
-        c->mfx_proto.chains = reinterpret_cast<const MfxChain *>(c->d_mobj_fx + at_chains);
-        c->mfx_proto.types = reinterpret_cast<const MfxType *>(c->d_mobj_fx + at_types);
-        c->mfx_proto.type_of = reinterpret_cast<const int32_t *>(c->d_mobj_fx + at_map);
-        c->mfx_proto.events = reinterpret_cast<const MfxEvent *>(c->d_mobj_fx + at_ev);
+        TablePack t;
+        const size_t steps = t.add(c->mfx.steps), chains = t.add(c->mfx.chains), types = t.add(c->mfx.types), type_of = t.add(c->mfx.type_of), events = t.add(c->mfx.events);
+        HIP_TRY(t.upload(c->d_mobj_fx));
+        c->mfx_proto.steps = t.at<MfxStep>(steps);
+        c->mfx_proto.chains = t.at<MfxChain>(chains);
+        c->mfx_proto.types = t.at<MfxType>(types);
+        c->mfx_proto.type_of = t.at<int32_t>(type_of);
+        c->mfx_proto.events = t.at<MfxEvent>(events);
         c->mfx_proto.n_events = (uint32_t)c->mfx.events.size();
         c->mfx_proto.n_mobjs = (uint32_t)c->mfx.type_of.size();
     }
-    struct Piece { const void *src; size_t bytes; size_t at; };
-    std::vector<Piece> pieces;
-    size_t total = 0;
-    auto add = [&](const void *src, size_t bytes) { pieces.push_back(Piece{src, bytes, total}); total = align_up(total + std::max<size_t>(bytes, 16), 256); return pieces.size() - 1; };
-    const size_t i_segs = add(sc.fs_segs.data(), sc.fs_segs.size() * sizeof(FsSeg));
-    const size_t i_leaf = add(sc.fs_seg_leaf.data(), sc.fs_seg_leaf.size() * 2);
-    const size_t i_first = add(sc.fs_leaf_first.data(), sc.fs_leaf_first.size() * 4);
-    const size_t i_sectors = add(sc.fs_sectors.data(), sc.fs_sectors.size() * sizeof(FsSector));
-    const size_t i_anims = add(sc.fs_anims.data(), sc.fs_anims.size() * sizeof(FsAnim));
-    const size_t i_bitmaps = add(sc.fs_bitmaps.data(), sc.fs_bitmaps.size() * sizeof(FsBitmap));
-    const size_t i_sky = add(sc.flat_sky.data(), sc.flat_sky.size());
-    const size_t i_mobjs = add(sc.fs_mobjs.data(), sc.fs_mobjs.size() * sizeof(FsMobj));
-    const size_t i_sframes = add(sc.sprite_frames.data(), sc.sprite_frames.size() * sizeof(SpriteFrameRec));
-    const size_t i_aoff = add(sc.fs_anc_off.data(), sc.fs_anc_off.size() * 4);
-    const size_t i_anc = add(sc.fs_anc.data(), sc.fs_anc.size() * sizeof(FsAnc));
-    HIP_TRY(hipMalloc((void **)&c->d_fs_scene, total));
-    for (const Piece &p : pieces)
-        if (p.bytes) HIP_TRY(hipMemcpy(c->d_fs_scene + p.at, p.src, p.bytes, hipMemcpyHostToDevice));
+    TablePack t;
+    const size_t segs = t.add(sc.fs_segs), leaf = t.add(sc.fs_seg_leaf), first = t.add(sc.fs_leaf_first), sectors = t.add(sc.fs_sectors);
+    const size_t anims = t.add(sc.fs_anims), bitmaps = t.add(sc.fs_bitmaps), sky = t.add(sc.flat_sky), mobjs = t.add(sc.fs_mobjs);
+    const size_t sframes = t.add(sc.sprite_frames), aoff = t.add(sc.fs_anc_off), anc = t.add(sc.fs_anc);
+    HIP_TRY(t.upload(c->d_fs_scene));
     FsParams &P = c->fs_proto;
     P = FsParams{};
     P.k = c->dk;
-    auto at = [&](size_t i) { return c->d_fs_scene + pieces[i].at; };
-    P.segs = reinterpret_cast<const FsSeg *>(at(i_segs)); P.seg_leaf = reinterpret_cast<const uint16_t *>(at(i_leaf)); P.leaf_first = reinterpret_cast<const uint32_t *>(at(i_first));
-    P.sectors = reinterpret_cast<const FsSector *>(at(i_sectors)); P.anims = reinterpret_cast<const FsAnim *>(at(i_anims));
-    P.bitmaps = reinterpret_cast<const FsBitmap *>(at(i_bitmaps)); P.flat_sky = at(i_sky);
-    P.mobjs = reinterpret_cast<const FsMobj *>(at(i_mobjs)); P.sframes = reinterpret_cast<const FsSpriteFrame *>(at(i_sframes));
-    P.anc_off = reinterpret_cast<const uint32_t *>(at(i_aoff)); P.anc = reinterpret_cast<const FsAnc *>(at(i_anc));
+    P.segs = t.at<FsSeg>(segs); P.seg_leaf = t.at<uint16_t>(leaf); P.leaf_first = t.at<uint32_t>(first);
+    P.sectors = t.at<FsSector>(sectors); P.anims = t.at<FsAnim>(anims);
+    P.bitmaps = t.at<FsBitmap>(bitmaps); P.flat_sky = t.at<uint8_t>(sky);
+    P.mobjs = t.at<FsMobj>(mobjs); P.sframes = t.at<FsSpriteFrame>(sframes);
+    P.anc_off = t.at<uint32_t>(aoff); P.anc = t.at<FsAnc>(anc);
     P.n_segs = (uint32_t)sc.segs.size(); P.n_leaves = (uint32_t)sc.subsectors.size(); P.n_mobjs = (uint32_t)sc.mobjs.size();
-    P.sprite_stride = std::min<uint32_t>(FS_SPRITE_CAP, std::max<uint32_t>(32u, (P.n_mobjs + 31u) / 32u * 32u));
-    P.sbin_stride = std::min<uint32_t>(FS_SBIN_CAP, P.sprite_stride * (uint32_t)((c->cfg.width + FE_BIN_W - 1) / FE_BIN_W));
-    // scratch: the occupancy rows (zero before every walk: dg_fs_frame leaves them so), then the candidate rows they index (never cleared)
-    const size_t F = (size_t)c->cfg.max_batch;
-    c->fs_zero_bytes = F * (size_t)fs_occ_words(P.n_segs) * 4;
-    const size_t off_lite = align_up(c->fs_zero_bytes, 256);
-    const size_t off_leaf = align_up(off_lite + F * (size_t)P.n_segs * FS_CALLS * sizeof(uint2), 256);
-    // ... and, per frame, room for a candidate list longer than dg_fs_frame's shared memory holds (FS_CL_CAP) with its keep bits: sized by the
-    // scene (every call of every seg), so that no frame of this map is handed back to the host for its number of candidates
-    const uint32_t cl_row_cap = (P.n_segs * FS_CALLS + 31u) / 32u * 32u;
-    const size_t off_cl = off_leaf;
-    const size_t off_keep = align_up(off_cl + (cl_row_cap > FS_CL_CAP ? F * (size_t)cl_row_cap * 4 : 0), 256);
-    HIP_TRY(hipMalloc((void **)&c->d_fs_scratch, off_keep + (cl_row_cap > FS_CL_CAP ? F * (size_t)(cl_row_cap / 32) * 4 : 0)));
+    P.sprite_stride = fs_sprite_stride(P.n_mobjs);
+    P.sbin_stride = fs_sbin_stride(P.sprite_stride, (size_t)c->cfg.width);
+    const FsScratchLayout L = fs_scratch_layout((size_t)c->cfg.max_batch, P.n_segs);
+    HIP_TRY(hip_alloc(c->d_fs_scratch, L.total));
+    c->fs_zero_bytes = L.zero_bytes;
     c->fs_rows_dirty = true;
-    P.occ = reinterpret_cast<uint32_t *>(c->d_fs_scratch);
-    P.lite = reinterpret_cast<uint2 *>(c->d_fs_scratch + off_lite);
-    P.cl_rows = reinterpret_cast<uint32_t *>(c->d_fs_scratch + off_cl);
-    P.keep_rows = reinterpret_cast<uint32_t *>(c->d_fs_scratch + off_keep);
-    P.cl_row_cap = cl_row_cap > FS_CL_CAP ? cl_row_cap : 0u;
+    uint8_t *const d = c->d_fs_scratch.get();
+    P.occ = reinterpret_cast<uint32_t *>(d + L.occ);
+    P.lite = reinterpret_cast<uint2 *>(d + L.lite);
+    P.cl_rows = reinterpret_cast<uint32_t *>(d + L.cl_rows);
+    P.keep_rows = reinterpret_cast<uint32_t *>(d + L.keep_rows);
+    P.cl_row_cap = L.cl_row_cap;
     c->fs_scene_ok = true;
     return DG_OK;
 }
@@ -703,58 +690,37 @@ bool choose_fs(dg_ctx *c, const dg_view *views, int n) {
 // with fixed per-frame strides (fs_frame.h), into the slot's record slab.
 int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
+    if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
-    if (sc.texel_idx.size() != c->uploaded_texels) return set_err(DG_ERR_INVALID, "the scene decoded new bitmaps since dg_upload_scene: upload it again");
     const int W = c->cfg.width;
-    const size_t nb1 = (size_t)(W + FE_BIN_W - 1) / FE_BIN_W + 1;
-    const uint32_t span_stride = (uint32_t)(c->span_cap_per_batch / (size_t)c->cfg.max_batch);
-    // uploaded part
-    const size_t off_frames = 0;
-    const size_t off_views = align_up(off_frames + (size_t)n * sizeof(DevFrame), 256);
-    const size_t off_lights = align_up(off_views + (size_t)n * sizeof(dg_view), 256);
+    const uint32_t span_stride = fe_span_stride(c);
     // per-view game state (dg_view_state): every frame gets its own copy of the two state arrays — the scene's values with the view's
     // entries on top — instead of one copy for the batch; the kernels index them with a per-frame stride
     const size_t state_frames = states ? (size_t)n : 1;
-    const size_t off_mstate = align_up(off_lights + state_frames * sc.sectors.size() * 2, 256);
     // light effects (dg_light_rows): with view states, per frame a mask of the sectors its state overrides (the rows above are then
     // completed in place); without, the kernel writes the per-view rows from the one base row into the device-written part
     const bool lfx = c->lfx.on() && c->lfx_proto.recs && c->lfx.rec_of.size() == sc.sectors.size();
     const size_t mask_words = (sc.sectors.size() + 31) / 32;
-    const size_t off_lmask = align_up(off_mstate + state_frames * sc.mobjs.size() * 4, 256);
     // map-object thinkers (dg_mobj_rows): the same two layouts for the map-object rows
     const bool mfx = c->mfx.on() && c->mfx_proto.steps && c->mfx.type_of.size() == sc.mobjs.size();
     if (mfx && (uint64_t)n * sc.mobjs.size() >= (1ull << 31)) return kPartsUnsupported;
     const size_t mmask_words = (sc.mobjs.size() + 31) / 32;
-    const size_t off_mmask = align_up(off_lmask + (lfx && states ? (size_t)n * mask_words * 4 : 0), 256);
-    const size_t upload = align_up(off_mmask + (mfx && states ? (size_t)n * mmask_words * 4 : 0), 256);
-    // device-written part
-    const size_t off_lrows = upload;
-    const size_t off_mrows = align_up(off_lrows + (lfx && !states ? (size_t)n * sc.sectors.size() * 2 : 0), 256);
-    const size_t off_ff = align_up(off_mrows + (mfx && !states ? (size_t)n * sc.mobjs.size() * 4 : 0), 256);
-    const size_t off_parts = align_up(off_ff + (size_t)n * sizeof(FeFrame), 256);
-    const size_t off_sprites = align_up(off_parts + (size_t)n * FS_PART_CAP * sizeof(FePart), 256);
-    const size_t off_behind = align_up(off_sprites + (size_t)n * c->fs_proto.sprite_stride * sizeof(FeSprite), 256);
-    const size_t off_sky = align_up(off_behind + (size_t)n * c->fs_proto.sprite_stride * FS_BEHIND_WORDS * 4, 256);
-    const size_t off_boff = align_up(off_sky + (size_t)n * FS_SKY_CAP * 4, 256);
-    const size_t off_sboff = align_up(off_boff + (size_t)n * nb1 * 4, 256);
-    const size_t off_bins = align_up(off_sboff + (size_t)n * nb1 * 4, 256);
-    const size_t off_sbins = align_up(off_bins + (size_t)n * FS_BIN_CAP * 2, 256);
-    const size_t total = off_sbins + (size_t)n * c->fs_proto.sbin_stride * 2;
-    if (total > c->fe_slab_cap) return kPartsUnsupported;
+    const FsLayout L = fs_layout((size_t)n, (size_t)W, sc.sectors.size(), sc.mobjs.size(), states != nullptr, lfx, mfx, c->fs_proto.sprite_stride, c->fs_proto.sbin_stride);
+    if (L.total > c->fe_slab_cap) return kPartsUnsupported;
+    uint8_t *const h = s.h_fe.get(), *const d = s.d_fe.get();
     s.views.assign(views, views + n);
     c->pool->parallel_for(n, [&](int i, int) {
         dg_view &v = s.views[(size_t)i];
         fill_view_trig(v);
         DevFrame hdr = make_frame_header(v);
         hdr.span_base = (uint32_t)i * span_stride;
-        std::memcpy(s.h_fe + off_frames + (size_t)i * sizeof(DevFrame), &hdr, sizeof hdr);
-        std::memcpy(s.h_fe + off_views + (size_t)i * sizeof(dg_view), &v, sizeof v);
+        std::memcpy(h + L.frames + (size_t)i * sizeof(DevFrame), &hdr, sizeof hdr);
+        std::memcpy(h + L.views + (size_t)i * sizeof(dg_view), &v, sizeof v);
     });
-    int16_t *lights = reinterpret_cast<int16_t *>(s.h_fe + off_lights);
-    int32_t *mstate = reinterpret_cast<int32_t *>(s.h_fe + off_mstate);
-    uint32_t *lmask = reinterpret_cast<uint32_t *>(s.h_fe + off_lmask);
-    uint32_t *mmask = reinterpret_cast<uint32_t *>(s.h_fe + off_mmask);
+    int16_t *lights = reinterpret_cast<int16_t *>(h + L.lights);
+    int32_t *mstate = reinterpret_cast<int32_t *>(h + L.mstate);
+    uint32_t *lmask = reinterpret_cast<uint32_t *>(h + L.lmask);
+    uint32_t *mmask = reinterpret_cast<uint32_t *>(h + L.mmask);
     std::atomic<int> bad_state{-1};
     c->pool->parallel_for((int)state_frames, [&](int i, int) {
         int16_t *l = lights + (size_t)i * sc.sectors.size();
@@ -783,19 +749,18 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
 
     FsParams &Q = s.FSP;
     Q = c->fs_proto;
-    Q.k = c->dk;
-    Q.sector_light = reinterpret_cast<const int16_t *>(s.d_fe + off_lights);
-    Q.mobj_state = reinterpret_cast<const int32_t *>(s.d_fe + off_mstate);
+    Q.sector_light = reinterpret_cast<const int16_t *>(d + L.lights);
+    Q.mobj_state = reinterpret_cast<const int32_t *>(d + L.mstate);
     Q.light_stride = states ? (uint32_t)sc.sectors.size() : 0u;
     s.LR = LfxRows{};
     if (lfx) {                                              // dg_light_rows completes the rows the seg walk reads
         s.LR = c->lfx_proto;
-        s.LR.views = reinterpret_cast<const dg_view *>(s.d_fe + off_views);
+        s.LR.views = reinterpret_cast<const dg_view *>(d + L.views);
         s.LR.base = Q.sector_light;
         s.LR.base_stride = Q.light_stride;
-        s.LR.mask = states ? reinterpret_cast<const uint32_t *>(s.d_fe + off_lmask) : nullptr;
+        s.LR.mask = states ? reinterpret_cast<const uint32_t *>(d + L.lmask) : nullptr;
         s.LR.mask_words = (uint32_t)mask_words;
-        s.LR.out = states ? reinterpret_cast<int16_t *>(s.d_fe + off_lights) : reinterpret_cast<int16_t *>(s.d_fe + off_lrows);
+        s.LR.out = states ? reinterpret_cast<int16_t *>(d + L.lights) : reinterpret_cast<int16_t *>(d + L.lrows);
         s.LR.n_frames = n;
         Q.sector_light = s.LR.out;
         Q.light_stride = (uint32_t)sc.sectors.size();
@@ -804,62 +769,43 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     s.MR = MfxRows{};
     if (mfx) {                                              // dg_mobj_rows completes the rows the seg walk reads
         s.MR = c->mfx_proto;
-        s.MR.views = reinterpret_cast<const dg_view *>(s.d_fe + off_views);
+        s.MR.views = reinterpret_cast<const dg_view *>(d + L.views);
         s.MR.base = Q.mobj_state;
         s.MR.base_stride = Q.mstate_stride;
-        s.MR.mask = states ? reinterpret_cast<const uint32_t *>(s.d_fe + off_mmask) : nullptr;
+        s.MR.mask = states ? reinterpret_cast<const uint32_t *>(d + L.mmask) : nullptr;
         s.MR.mask_words = (uint32_t)mmask_words;
-        s.MR.out = states ? reinterpret_cast<int32_t *>(s.d_fe + off_mstate) : reinterpret_cast<int32_t *>(s.d_fe + off_mrows);
+        s.MR.out = states ? reinterpret_cast<int32_t *>(d + L.mstate) : reinterpret_cast<int32_t *>(d + L.mrows);
         s.MR.n_frames = n;
         Q.mobj_state = s.MR.out;
         Q.mstate_stride = (uint32_t)sc.mobjs.size();
     }
-    Q.views = reinterpret_cast<const dg_view *>(s.d_fe + off_views);
+    Q.views = reinterpret_cast<const dg_view *>(d + L.views);
     Q.n_frames = n;
-    Q.flags = s.d_flags;
-    Q.fframes = reinterpret_cast<FeFrame *>(s.d_fe + off_ff);
-    Q.parts = reinterpret_cast<FePart *>(s.d_fe + off_parts);
-    Q.sprites = reinterpret_cast<FeSprite *>(s.d_fe + off_sprites);
-    Q.behind = reinterpret_cast<uint32_t *>(s.d_fe + off_behind);
-    Q.sky_parts = reinterpret_cast<uint32_t *>(s.d_fe + off_sky);
-    Q.bin_off = reinterpret_cast<uint32_t *>(s.d_fe + off_boff);
-    Q.sbin_off = reinterpret_cast<uint32_t *>(s.d_fe + off_sboff);
-    Q.bin_parts = reinterpret_cast<uint16_t *>(s.d_fe + off_bins);
-    Q.sbin_sprites = reinterpret_cast<uint16_t *>(s.d_fe + off_sbins);
+    Q.flags = s.d_flags.get();
+    Q.fframes = reinterpret_cast<FeFrame *>(d + L.fframes);
+    Q.parts = reinterpret_cast<FePart *>(d + L.parts);
+    Q.sprites = reinterpret_cast<FeSprite *>(d + L.sprites);
+    Q.behind = reinterpret_cast<uint32_t *>(d + L.behind);
+    Q.sky_parts = reinterpret_cast<uint32_t *>(d + L.sky);
+    Q.bin_off = reinterpret_cast<uint32_t *>(d + L.bin_off);
+    Q.sbin_off = reinterpret_cast<uint32_t *>(d + L.sbin_off);
+    Q.bin_parts = reinterpret_cast<uint16_t *>(d + L.bins);
+    Q.sbin_sprites = reinterpret_cast<uint16_t *>(d + L.sbins);
     FeParams &F = s.FP;
-    F.scene = c->dscene;
-    F.k = c->dk;
-    F.frames = reinterpret_cast<const DevFrame *>(s.d_fe + off_frames);
+    F.frames = reinterpret_cast<const DevFrame *>(d + L.frames);
     F.fframes = Q.fframes; F.parts = Q.parts; F.sprites = Q.sprites; F.behind = Q.behind; F.sky_parts = Q.sky_parts;
     F.max_sky_slots = FS_SKY_CAP; F.gap_waves = 12;
     F.bin_off = Q.bin_off; F.sbin_off = Q.sbin_off; F.bin_parts = Q.bin_parts; F.sbin_sprites = Q.sbin_sprites;
-    Q.order_cnt = s.d_flags + c->cfg.max_batch;            // zeroed with the flags (enqueue_kernels)
-    Q.order_list = s.d_order;
-    Q.n_items = (uint32_t)n * (uint32_t)((W + 255) / 256);
-    F.order = s.d_order; F.order_cnt = Q.order_cnt;
-    F.cspans = c->d_fe_cspans; F.recs = c->d_fe_recs; F.cnt = c->d_fe_cnt;
-    F.events = s.d_events;
-    F.flags = s.d_flags;
-    F.host_flags = s.h_status; F.totals = s.h_status + c->cfg.max_batch;
-    F.col_off = s.d_fe_coloff; F.rspans = s.d_rspans;
-    F.n_frames = n; F.span_stride = span_stride; F.w64 = (uint32_t)((W + 63) / 64); F.col_slots = c->fe_col_slots;
-    RasterParams &P = s.P;
-    P.scene = c->dscene;
-    P.k = c->dk;
-    P.frames = F.frames;
-    P.col_off = s.d_fe_coloff;
-    P.walls = nullptr; P.planes = nullptr; P.spans = nullptr;
-    P.rspans = s.d_rspans;
-    P.fb = s.d_fb;
-    P.row_tab = c->d_row_tab;
-    P.n_frames = n;
-    s.max_spans = 0; s.n_spans = 0; s.covered = 0; s.n_frames = n; s.n_walls = 0; s.n_planes = 0;
-    s.list_bytes = upload;
-    s.fe_mode = true; s.fs_mode = true; s.fe_check = false; s.map_mode = false;
+    Q.order_cnt = s.d_flags.get() + c->cfg.max_batch;      // zeroed with the flags (enqueue_kernels)
+    Q.order_list = s.d_order.get();
+    Q.n_items = (uint32_t)n * (uint32_t)fe_col_groups((size_t)W);
+    F.order = Q.order_list; F.order_cnt = Q.order_cnt;
+    fill_walk_params(c, s, n);
+    s.describe(DG_FE_DEVICE_SEGS, n, L.upload, 0, 0);
     s.keep_states(states, n);
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(s.d_fe, s.h_fe, upload, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(d, h, L.upload, hipMemcpyHostToDevice, s.stream));
     return DG_OK;
 }
 
@@ -895,18 +841,18 @@ int build_map_layer(dg_ctx *c, Slot &s) {
     }
     if (total >= (1ull << 31)) return set_err(DG_ERR_CAPACITY, "map layer: too many line steps");
     base[n] = (uint32_t)total;
-    if (!c->d_map_layer) HIP_TRY(hipMalloc((void **)&c->d_map_layer, (size_t)3 * (size_t)W * (size_t)H));
-    const size_t off_segs = align_up((size_t)W * (size_t)H * 4, 256), off_base = align_up(off_segs + segs.size() * sizeof(MapSeg), 256);
-    uint8_t *tmp = nullptr;
-    HIP_TRY(hipMalloc((void **)&tmp, off_base + base.size() * 4));
-    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } tmp_guard{tmp};
-    uint32_t *owner = reinterpret_cast<uint32_t *>(tmp);
-    MapSeg *d_segs = reinterpret_cast<MapSeg *>(tmp + off_segs);
-    uint32_t *d_base = reinterpret_cast<uint32_t *>(tmp + off_base);
+    if (!c->d_map_layer) HIP_TRY(hip_alloc(c->d_map_layer, (size_t)3 * (size_t)W * (size_t)H));
+    SlabCursor cur;
+    const size_t off_owner = cur.take((size_t)W * (size_t)H * 4), off_segs = cur.take(segs.size() * sizeof(MapSeg)), off_base = cur.take(base.size() * 4);
+    DevPtr<uint8_t> tmp;
+    HIP_TRY(hip_alloc(tmp, cur.end()));
+    uint32_t *owner = reinterpret_cast<uint32_t *>(tmp.get() + off_owner);
+    MapSeg *d_segs = reinterpret_cast<MapSeg *>(tmp.get() + off_segs);
+    uint32_t *d_base = reinterpret_cast<uint32_t *>(tmp.get() + off_base);
     HIP_TRY(hipMemcpy(d_segs, segs.data(), segs.size() * sizeof(MapSeg), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_base, base.data(), base.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(owner, 0, (size_t)W * (size_t)H * 4, c->kstream));
-    HIP_TRY(launch_map_layer(d_segs, d_base, (uint32_t)n, (uint32_t)total, owner, c->d_map_layer, W, H, c->kstream, s.ev_start, s.ev_setup));
+    HIP_TRY(launch_map_layer(d_segs, d_base, (uint32_t)n, (uint32_t)total, owner, c->d_map_layer.get(), W, H, c->kstream, s.ev_start, s.ev_setup));
     HIP_TRY(hipStreamSynchronize(c->kstream));           // (before the transient buffers go)
     c->map_layer_ok = true;
     return DG_OK;
@@ -929,18 +875,18 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
         Slot &s; bool armed = true;
         ~Invalidate() { if (armed) { s.n_frames = 0; s.timed = false; s.busy = false; s.fe_check = false; s.raster_recorded = false; } }
     } guard{s};
-    const bool fe_mode = s.fe_mode;
+    const bool fe_mode = s.column_walk();
     s.fe_check = false;
     HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
     HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
-    if (s.map_mode) {                                     // 2-D map frames: the layer (once per scene upload), then copy + arrow per frame
+    if (s.front_end == DG_FE_MAP) {                       // 2-D map frames: the layer (once per scene upload), then copy + arrow per frame
         s.map_built = false;
         if (!c->map_layer_ok) {
             const int rc = build_map_layer(c, s);
             if (rc) return rc;
             s.map_built = true;
         }
-        HIP_TRY(launch_map_frames(c->d_map_layer, reinterpret_cast<const MapSeg *>(s.d_lists), s.n_frames, s.d_fb, c->cfg.width, c->cfg.height,
+        HIP_TRY(launch_map_frames(c->d_map_layer.get(), reinterpret_cast<const MapSeg *>(s.d_lists.get()), s.n_frames, s.d_fb.get(), c->cfg.width, c->cfg.height,
                                   ks, s.ev_rstart, s.ev_raster));
         guard.armed = false;
         s.harvested = true;                               // (never DG_FE_AUTO's measurement)
@@ -949,13 +895,13 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
         return DG_OK;
     }
     if (fe_mode) {
-        std::memset(s.h_status, 0, (size_t)2 * (size_t)c->cfg.max_batch * 4);
+        std::memset(s.h_status.get(), 0, (size_t)2 * (size_t)c->cfg.max_batch * 4);
         // the overflow flags, the launch-order counters and the event bits behind them start from zero: dg_fe_scan leaves them so (its
         // last lines), and only a slot that is new or whose last enqueue failed half way is cleared here, whole
-        if (!s.walk_state_clean) HIP_TRY(hipMemsetAsync(s.d_flags, 0, s.walk_state_bytes, ks));
+        if (!s.walk_state_clean) HIP_TRY(hipMemsetAsync(s.d_flags.get(), 0, s.walk_state_bytes, ks));
         s.walk_state_clean = false;
-        if (s.fs_mode) {                                                                                // the seg walk writes what the column walk reads
-            if (c->fs_rows_dirty) HIP_TRY(hipMemsetAsync(c->d_fs_scratch, 0, c->fs_zero_bytes, ks));    // (dg_fs_frame leaves its rows clean)
+        if (s.seg_walk()) {                                                                             // the seg walk writes what the column walk reads
+            if (c->fs_rows_dirty) HIP_TRY(hipMemsetAsync(c->d_fs_scratch.get(), 0, c->fs_zero_bytes, ks));    // (dg_fs_frame leaves its rows clean)
             c->fs_rows_dirty = true;
             hipEvent_t fs_start = s.ev_start;
             if (s.LR.n_frames > 0) { HIP_TRY(launch_light_rows(s.LR, ks, fs_start)); fs_start = nullptr; }     // the rows dg_fs_* read
@@ -963,7 +909,7 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
             HIP_TRY(c->fx.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
             c->fs_rows_dirty = false;
         }
-        HIP_TRY(launch_fe(s.FP, ks, s.fs_mode ? nullptr : s.ev_start, s.ev_setup));
+        HIP_TRY(launch_fe(s.FP, ks, s.seg_walk() ? nullptr : s.ev_start, s.ev_setup));
     } else {
         HIP_TRY(launch_setup(s.P, s.max_spans, ks, s.ev_start, s.ev_setup));
     }
@@ -999,31 +945,19 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     if (!rc) rc = bin_frame(sc, c->fk, fl, bf, err);
     if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
-    const size_t off_col = align_up(sizeof(DevFrame), 256);
-    const size_t off_walls = align_up(off_col + (size_t)(W + 1) * 4, 256);
-    const size_t off_planes = align_up(off_walls + bf.walls.size() * sizeof(DevWallRec), 256);
-    const size_t off_spans = align_up(off_planes + bf.planes.size() * sizeof(DevPlaneRec), 256);
-    const size_t total = off_spans + bf.spans.size() * sizeof(DevSpan);
-    if (total > s.lists_cap) return DG_ERR_CAPACITY;
+    const ListLayout L = list_layout(1, (size_t)W, bf.walls.size(), bf.planes.size(), bf.spans.size());
+    if (L.total > s.lists_cap) return DG_ERR_CAPACITY;
     if (!c->d_redo_rspans) {
         c->redo_span_cap = (size_t)W * 64;                                   // 64 spans per column on average: far beyond any real frame
-        if (hipMalloc((void **)&c->d_redo_rspans, c->redo_span_cap * sizeof(DevRSpan)) != hipSuccess) { c->d_redo_rspans = nullptr; return DG_ERR_CAPACITY; }
+        if (hip_alloc(c->d_redo_rspans, c->redo_span_cap * sizeof(DevRSpan)) != hipSuccess) return DG_ERR_CAPACITY;
     }
     if (bf.spans.size() > c->redo_span_cap) return DG_ERR_CAPACITY;
-    std::memcpy(s.h_lists, &bf.hdr, sizeof(DevFrame));
-    std::memcpy(s.h_lists + off_col, bf.col_off.data(), (size_t)(W + 1) * 4);
-    if (!bf.walls.empty()) std::memcpy(s.h_lists + off_walls, bf.walls.data(), bf.walls.size() * sizeof(DevWallRec));
-    if (!bf.planes.empty()) std::memcpy(s.h_lists + off_planes, bf.planes.data(), bf.planes.size() * sizeof(DevPlaneRec));
-    if (!bf.spans.empty()) std::memcpy(s.h_lists + off_spans, bf.spans.data(), bf.spans.size() * sizeof(DevSpan));
-    HIP_TRY(hipMemcpyAsync(s.d_lists, s.h_lists, total, hipMemcpyHostToDevice, s.stream));
+    pack_binned(s.h_lists.get(), L, bf, 0, (size_t)W);
+    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), L.total, hipMemcpyHostToDevice, s.stream));
     RasterParams Q = s.P;
-    Q.frames = reinterpret_cast<const DevFrame *>(s.d_lists);
-    Q.col_off = reinterpret_cast<const uint32_t *>(s.d_lists + off_col);
-    Q.walls = reinterpret_cast<const DevWallRec *>(s.d_lists + off_walls);
-    Q.planes = reinterpret_cast<const DevPlaneRec *>(s.d_lists + off_planes);
-    Q.spans = reinterpret_cast<const DevSpan *>(s.d_lists + off_spans);
-    Q.rspans = c->d_redo_rspans;
-    Q.fb = s.d_fb + (size_t)i * (size_t)3 * (size_t)W * (size_t)H;
+    point_at_lists(Q, s.d_lists.get(), L);
+    Q.rspans = c->d_redo_rspans.get();
+    Q.fb = s.d_fb.get() + (size_t)i * (size_t)3 * (size_t)W * (size_t)H;
     Q.n_frames = 1;
     HIP_TRY(launch_setup(Q, (uint32_t)bf.spans.size(), s.stream));
     HIP_TRY(launch_raster(Q, s.stream));
@@ -1036,11 +970,12 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
 int settle_slot(dg_ctx *c, Slot &s) {
     if (s.fe_check) {
         s.fe_check = false;
+        const uint32_t *const status = s.h_status.get();      // [max_batch] overflow flags, [max_batch] spans per frame
         bool overflow = false;
         uint64_t spans = 0;
         for (int i = 0; i < s.n_frames; i++) {
-            overflow |= s.h_status[i] != 0;
-            spans += s.h_status[c->cfg.max_batch + i];
+            overflow |= status[i] != 0;
+            spans += status[c->cfg.max_batch + i];
         }
         s.n_spans = spans;
         bool whole_batch = overflow;
@@ -1050,7 +985,7 @@ int settle_slot(dg_ctx *c, Slot &s) {
             c->fallbacks_fe++;
             whole_batch = false;
             for (int i = 0; i < s.n_frames && !whole_batch; i++) {
-                if (s.h_status[i] == 0) continue;
+                if (status[i] == 0) continue;
                 const int rc = redo_frame_host(c, s, i);
                 if (rc == DG_ERR_CAPACITY) whole_batch = true;
                 else if (rc) return rc;
@@ -1081,13 +1016,13 @@ int settle_slot(dg_ctx *c, Slot &s) {
 int enqueue_copy(dg_ctx *c, Slot &s) {
     const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
     HIP_TRY(hipStreamWaitEvent(s.copy_stream, s.ev_raster, 0));
-    HIP_TRY(hipMemcpyAsync(s.copy_out, s.d_fb + (size_t)s.copy_first * fsz, (size_t)s.copy_count * fsz, hipMemcpyDeviceToHost, s.copy_stream));
+    HIP_TRY(hipMemcpyAsync(s.copy_out, s.d_fb.get() + (size_t)s.copy_first * fsz, (size_t)s.copy_count * fsz, hipMemcpyDeviceToHost, s.copy_stream));
     return DG_OK;
 }
 
 // DG_FE_AUTO's measurement of the GPU side: the span of a finished submission's kernels (never waits)
 void harvest_gpu_time(dg_ctx *c, Slot &s) {
-    if (s.harvested || !s.timed || !s.fe_mode || s.n_frames < 64 || c->fs_forced || !c->fs_enabled) return;
+    if (s.harvested || !s.timed || !s.column_walk() || s.n_frames < 64 || c->fs_forced || !c->fs_enabled) return;
     if (hipEventQuery(s.ev_raster) != hipSuccess) return;
     s.harvested = true;
     float ms = 0.0f;
@@ -1097,8 +1032,8 @@ void harvest_gpu_time(dg_ctx *c, Slot &s) {
         ms = std::max(fe_ms, r_ms);                        // (they overlap with the neighbouring batches': the longer one sets the pace)
         if (!(ms > 0.0f)) return;
     } else if (hipEventElapsedTime(&ms, s.ev_start, s.ev_raster) != hipSuccess || !(ms > 0.0f)) return;
-    if (c->gpu_samples[s.fs_mode ? 1 : 0]++ == 0) return;  // (the first batch of a mode: cold caches, code not yet resident, clocks down — a seg walk judged by it alone was never tried again)
-    double &ema = s.fs_mode ? c->ema_gpu_fs : c->ema_gpu_dev;
+    if (c->gpu_samples[s.seg_walk() ? 1 : 0]++ == 0) return;  // (the first batch of a mode: cold caches, code not yet resident, clocks down — a seg walk judged by it alone was never tried again)
+    double &ema = s.seg_walk() ? c->ema_gpu_fs : c->ema_gpu_dev;
     const double v = (double)ms / s.n_frames;
     ema = ema < 0.0 ? v : 0.75 * ema + 0.25 * v;
 }
@@ -1291,9 +1226,8 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
     c->span_cap_per_batch = F * W * 24;       // 24 spans per column on average; real scenes use 2-8
     c->wall_cap_per_batch = F * 4096;
     c->plane_cap_per_batch = F * 4096;
-    const size_t lists_cap = align_up(F * sizeof(DevFrame), 256) + align_up(F * (W + 1) * 4, 256) +
-                             align_up(c->wall_cap_per_batch * sizeof(DevWallRec), 256) +
-                             align_up(c->plane_cap_per_batch * sizeof(DevPlaneRec), 256) + c->span_cap_per_batch * sizeof(DevSpan) + 1024;
+    // (the slabs' capacities: the layouts at the caps, plus slack)
+    const size_t lists_cap = list_layout(F, W, c->wall_cap_per_batch, c->plane_cap_per_batch, c->span_cap_per_batch).total + 1024;
     c->fe_enabled = cfg->front_end != DG_FE_HOST;
     c->fs_enabled = cfg->front_end == DG_FE_DEVICE_SEGS || cfg->front_end == DG_FE_AUTO;
     c->fs_forced = cfg->front_end == DG_FE_DEVICE_SEGS;
@@ -1315,19 +1249,16 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
         c->fe_behind_cap = F * 256 * 32;   // one bit per (sprite, wall record)
         c->fe_bin_cap = F * 16384;         // column-bin entries (a record is listed in every 64-column strip it touches)
         c->fe_sbin_cap = F * 2048;
-        c->fe_slab_cap = align_up(F * sizeof(DevFrame), 256) + align_up(F * sizeof(FeFrame), 256) + align_up(c->fe_part_cap * sizeof(FePart), 256) +
-                         align_up(c->fe_sprite_cap * sizeof(FeSprite), 256) + align_up(c->fe_behind_cap * 4, 256) + align_up(F * FE_MAX_SKY_SLOTS * 4, 256) +
-                         2 * align_up(F * ((W + FE_BIN_W - 1) / FE_BIN_W + 1) * 4, 256) + align_up(c->fe_bin_cap * 2, 256) + align_up(c->fe_sbin_cap * 2, 256) +
-                         F * ((W + 255) / 256) * 4 + 1024;
+        c->fe_slab_cap = fe_layout(F, W, c->fe_part_cap, c->fe_sprite_cap, c->fe_behind_cap, F * FE_MAX_SKY_SLOTS, c->fe_bin_cap, c->fe_sbin_cap).total + 1024;
     }
     c->slots.resize((size_t)cfg->slots);
     hipError_t e;
 #define CTX_TRY(expr) if ((e = (expr)) != hipSuccess) { std::string m = std::string(#expr) + ": " + hipGetErrorString(e); free_ctx(c); return set_err(DG_ERR_HIP, m); }
-    CTX_TRY(hipMalloc((void **)&c->d_checksums, F * 8));
+    CTX_TRY(hip_alloc(c->d_checksums, F * 8));
     if (c->fe_enabled) {
-        CTX_TRY(hipMalloc((void **)&c->d_fe_cspans, F * c->fe_col_slots * W * sizeof(FeU4)));
-        CTX_TRY(hipMalloc((void **)&c->d_fe_recs, F * c->fe_col_slots * W * sizeof(FeColRec)));
-        CTX_TRY(hipMalloc((void **)&c->d_fe_cnt, F * W * 4));
+        CTX_TRY(hip_alloc(c->d_fe_cspans, F * c->fe_col_slots * W * sizeof(FeU4)));
+        CTX_TRY(hip_alloc(c->d_fe_recs, F * c->fe_col_slots * W * sizeof(FeColRec)));
+        CTX_TRY(hip_alloc(c->d_fe_cnt, F * W * 4));
     }
     {
         int lo = 0, hi = 0;
@@ -1343,26 +1274,25 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
     }
     for (Slot &s : c->slots) {
         CTX_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-        CTX_TRY(hipEventCreate(&s.ev_start));
-        CTX_TRY(hipEventCreate(&s.ev_setup));
-        CTX_TRY(hipEventCreate(&s.ev_raster));
-        CTX_TRY(hipEventCreate(&s.ev_rstart));
+        for (hipEvent_t *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart}) CTX_TRY(hipEventCreate(ev));
         CTX_TRY(hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming));
         CTX_TRY(hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking));
-        CTX_TRY(hipHostMalloc((void **)&s.h_lists, lists_cap, hipHostMallocDefault));
-        CTX_TRY(hipMalloc((void **)&s.d_lists, lists_cap));
-        CTX_TRY(hipMalloc((void **)&s.d_rspans, c->span_cap_per_batch * sizeof(DevRSpan)));
-        CTX_TRY(hipMalloc((void **)&s.d_fb, F * 3 * W * H));
+        CTX_TRY(hip_alloc(s.h_lists, lists_cap));
+        CTX_TRY(hip_alloc(s.d_lists, lists_cap));
+        CTX_TRY(hip_alloc(s.d_rspans, c->span_cap_per_batch * sizeof(DevRSpan)));
+        CTX_TRY(hip_alloc(s.d_fb, F * 3 * W * H));
         if (c->fe_enabled) {
-            CTX_TRY(hipHostMalloc((void **)&s.h_fe, c->fe_slab_cap, hipHostMallocDefault));
-            CTX_TRY(hipMalloc((void **)&s.d_fe, c->fe_slab_cap));
-            CTX_TRY(hipMalloc((void **)&s.d_fe_coloff, F * (W + 1) * 4));
-            s.flags_bytes = align_up(F * 4 + FS_ORDER_CLASSES * 4, 256);       // the flag words, then the seg walk's launch-order counters
-            CTX_TRY(hipMalloc((void **)&s.d_order, FS_ORDER_CLASSES * F * ((W + 255) / 256) * 4));
-            s.walk_state_bytes = s.flags_bytes + F * FE_MAX_SKY_SLOTS * 3 * ((W + 63) / 64) * 8;
-            CTX_TRY(hipMalloc((void **)&s.d_flags, s.walk_state_bytes));
-            s.d_events = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(s.d_flags) + s.flags_bytes);
-            CTX_TRY(hipHostMalloc((void **)&s.h_status, 2 * F * 4, hipHostMallocDefault));
+            CTX_TRY(hip_alloc(s.h_fe, c->fe_slab_cap));
+            CTX_TRY(hip_alloc(s.d_fe, c->fe_slab_cap));
+            CTX_TRY(hip_alloc(s.d_fe_coloff, F * (W + 1) * 4));
+            CTX_TRY(hip_alloc(s.d_order, FS_ORDER_CLASSES * F * fe_col_groups(W) * 4));
+            SlabCursor ws;
+            ws.take(F * 4 + FS_ORDER_CLASSES * 4);                              // the flag words, then the seg walk's launch-order counters
+            const size_t off_events = ws.take(F * FE_MAX_SKY_SLOTS * 3 * ((W + 63) / 64) * 8);
+            s.walk_state_bytes = ws.end();
+            CTX_TRY(hip_alloc(s.d_flags, s.walk_state_bytes));
+            s.d_events = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(s.d_flags.get()) + off_events);
+            CTX_TRY(hip_alloc(s.h_status, 2 * F * 4));
         }
         s.lists_cap = lists_cap;
     }
@@ -1387,9 +1317,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
         s.copy_pending = false;
     }
     const Scene &sc = *scene->sc;
-    if (c->d_palette) { (void)hipFree(c->d_palette); c->d_palette = nullptr; }
-    if (c->d_texel_idx) { (void)hipFree(c->d_texel_idx); c->d_texel_idx = nullptr; }
-    if (c->d_texel_opq) { (void)hipFree(c->d_texel_opq); c->d_texel_opq = nullptr; }
+    c->d_palette.reset(); c->d_texel_idx.reset(); c->d_texel_opq.reset();
     c->d_flats = nullptr;               // inside d_texel_idx's allocation
     // the slots' prepared records point into the device scene that was just freed: nothing may be replayed from them
     for (Slot &s : c->slots) { s.n_frames = 0; s.timed = false; s.fe_check = false; s.busy = false; s.snap_scene = nullptr; }
@@ -1399,24 +1327,24 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     const size_t nt = std::max<size_t>(sc.texel_idx.size(), 16), nf = std::max<size_t>(sc.flat_pool.size(), 16);
     float palf[256 * 4];
     for (int i = 0; i < 256; i++) { palf[4 * i] = (float)sc.palette[3 * i]; palf[4 * i + 1] = (float)sc.palette[3 * i + 1]; palf[4 * i + 2] = (float)sc.palette[3 * i + 2]; palf[4 * i + 3] = 0.0f; }
-    HIP_TRY(hipMalloc((void **)&c->d_palette, sizeof pal + sizeof palf));
+    HIP_TRY(hip_alloc(c->d_palette, sizeof pal + sizeof palf));
     // [column-major texel index plane | flats] share one allocation: the tile rasteriser gathers every kind's texel with one
     // 32-bit offset from texel_idx (flats at flats - texel_idx)
     const size_t flats_at = (nt + 255) & ~(size_t)255;
-    HIP_TRY(hipMalloc((void **)&c->d_texel_idx, flats_at + nf));
-    HIP_TRY(hipMalloc((void **)&c->d_texel_opq, nt));
-    c->d_flats = c->d_texel_idx + flats_at;
-    HIP_TRY(hipMemcpy(c->d_palette, pal, sizeof pal, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_palette + 256, palf, sizeof palf, hipMemcpyHostToDevice));
+    HIP_TRY(hip_alloc(c->d_texel_idx, flats_at + nf));
+    HIP_TRY(hip_alloc(c->d_texel_opq, nt));
+    c->d_flats = c->d_texel_idx.get() + flats_at;
+    HIP_TRY(hipMemcpy(c->d_palette.get(), pal, sizeof pal, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_palette.get() + 256, palf, sizeof palf, hipMemcpyHostToDevice));
     if (!sc.texel_idx.empty()) {
-        HIP_TRY(hipMemcpy(c->d_texel_idx, sc.texel_idx.data(), sc.texel_idx.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_texel_opq, sc.texel_opq.data(), sc.texel_opq.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_texel_idx.get(), sc.texel_idx.data(), sc.texel_idx.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_texel_opq.get(), sc.texel_opq.data(), sc.texel_opq.size(), hipMemcpyHostToDevice));
     }
     if (!sc.flat_pool.empty()) HIP_TRY(hipMemcpy(c->d_flats, sc.flat_pool.data(), sc.flat_pool.size(), hipMemcpyHostToDevice));
     const BitmapInfo &sky = sc.bitmaps[(size_t)sc.sky_bitmap];
-    c->dscene = DevScene{c->d_palette, reinterpret_cast<const float *>(c->d_palette + 256), c->d_texel_idx, c->d_texel_opq, c->d_flats, sky.texel_off, sky.w, sky.h, sky.has_holes};
-    if (!c->d_row_tab) HIP_TRY(hipMalloc((void **)&c->d_row_tab, (size_t)c->cfg.height * sizeof(uint4)));
-    HIP_TRY(launch_row_table(c->dscene, c->dk, c->d_row_tab, nullptr));
+    c->dscene = DevScene{c->d_palette.get(), reinterpret_cast<const float *>(c->d_palette.get() + 256), c->d_texel_idx.get(), c->d_texel_opq.get(), c->d_flats, sky.texel_off, sky.w, sky.h, sky.has_holes};
+    if (!c->d_row_tab) HIP_TRY(hip_alloc(c->d_row_tab, (size_t)c->cfg.height * sizeof(uint4)));
+    HIP_TRY(launch_row_table(c->dscene, c->dk, c->d_row_tab.get(), nullptr));
     HIP_TRY(hipDeviceSynchronize());
     c->scene = &sc;
     c->fx = sc.wall_fx;                                 // dg_scene_set_wall_effects takes effect here
@@ -1431,11 +1359,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
         if (rc) {
             static bool said = false;                      // once per process: the ctx works, but not the way it was asked to
             if (!said) { said = true; std::fprintf(stderr, "doomgpu: DG_FE_AUTO keeps the per-seg half on the host: no device memory for the seg walk's per-batch rows (%d views x %zu segs)\n", c->cfg.max_batch, sc.segs.size()); }
-            if (c->d_fs_scene) { (void)hipFree(c->d_fs_scene); c->d_fs_scene = nullptr; }
-            if (c->d_fs_scratch) { (void)hipFree(c->d_fs_scratch); c->d_fs_scratch = nullptr; }
-            if (c->d_wall_fx) { (void)hipFree(c->d_wall_fx); c->d_wall_fx = nullptr; }
-            if (c->d_light_fx) { (void)hipFree(c->d_light_fx); c->d_light_fx = nullptr; }
-            if (c->d_mobj_fx) { (void)hipFree(c->d_mobj_fx); c->d_mobj_fx = nullptr; }
+            c->d_fs_scene.reset(); c->d_fs_scratch.reset(); c->d_wall_fx.reset(); c->d_light_fx.reset(); c->d_mobj_fx.reset();
             c->fs_scene_ok = false;
             (void)hipGetLastError();
         }
@@ -1512,7 +1436,7 @@ int dg_slot_framebuffer(dg_ctx *c, int slot, void **p) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!p) return set_err(DG_ERR_INVALID, "null argument");
-    *p = c->slots[(size_t)slot].d_fb;
+    *p = c->slots[(size_t)slot].d_fb.get();
     return DG_OK;
 }
 
@@ -1528,7 +1452,7 @@ int dg_readback(dg_ctx *c, int slot, int first, int count, uint8_t *out) {
         rc = settle_slot(c, s);
         if (rc) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(out, s.d_fb + (size_t)first * fsz, (size_t)count * fsz, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(hipMemcpyAsync(out, s.d_fb.get() + (size_t)first * fsz, (size_t)count * fsz, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(slot_sync(s));
     s.busy = false;
     return DG_OK;
@@ -1547,9 +1471,9 @@ int dg_frame_checksums(dg_ctx *c, int slot, int first, int count, uint64_t *out)
         if (rc) return rc;
     }
     const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
-    unsigned long long *d_sum = c->d_checksums;      // max_batch entries, allocated at dg_create
+    unsigned long long *d_sum = c->d_checksums.get();      // max_batch entries, allocated at dg_create
     hipError_t e = hipMemsetAsync(d_sum, 0, (size_t)count * 8, s.stream);
-    if (e == hipSuccess) e = launch_checksums(s.d_fb + (size_t)first * fsz, fsz, count, d_sum, s.stream);
+    if (e == hipSuccess) e = launch_checksums(s.d_fb.get() + (size_t)first * fsz, fsz, count, d_sum, s.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_sum, (size_t)count * 8, hipMemcpyDeviceToHost, s.stream);
     if (e == hipSuccess) e = slot_sync(s);
     if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_frame_checksums: ") + hipGetErrorString(e));
@@ -1584,7 +1508,7 @@ int dg_prepare_views(dg_ctx *c, int slot, const dg_view *views, int n) {
     rc = build_batch(c, s, views, nullptr, n);
     c->preparing = false;
     if (rc) return rc;
-    if (s.fe_mode) {              // run the column walk once so that a batch that has to go through the host list path as a whole
+    if (s.column_walk()) {        // run the column walk once so that a batch that has to go through the host list path as a whole
         rc = enqueue_kernels(c, s);   // is re-prepared that way now, not on a replay
         if (rc) return rc;
     }
@@ -1655,7 +1579,7 @@ int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
     s.fe_check = false;
     const auto t0 = std::chrono::steady_clock::now();
     // the arrow's three lines per view, clipped to the frame (the host owns the libm trig: dg_view has no field for the head angles)
-    MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists);
+    MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
     std::string err;
     for (int i = 0; i < n; i++) {
         dg_view v = views[i];
@@ -1665,11 +1589,9 @@ int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
         if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
         for (int k = 0; k < 3; k++) h[3 * i + k] = map_seg_make(l[k].x0, l[k].y0, l[k].x1, l[k].y1, l[k].rgb, W, H);
     }
-    s.map_mode = true; s.fe_mode = false; s.fs_mode = false;
-    s.n_frames = n; s.max_spans = 0; s.n_spans = 0; s.covered = 0; s.n_walls = 0; s.n_planes = 0;
-    s.list_bytes = bytes;
+    s.describe(DG_FE_MAP, n, bytes, 0, 0);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(s.d_lists, s.h_lists, bytes, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream));
     return enqueue_kernels(c, s);
 }
 
@@ -1694,25 +1616,17 @@ int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
         if (rc) return rc;
     }
     std::memset(out, 0, sizeof *out);
-    if (s.map_mode) {
-        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
-        if (s.map_built) {
-            HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
-            HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));
-        } else {
-            out->total_ms = out->raster_ms;
-        }
-        out->n_frames = (uint64_t)s.n_frames; out->host_ms = s.host_ms; out->list_bytes = s.list_bytes;
-        out->front_end = DG_FE_MAP;
-        return DG_OK;
-    }
-    HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
+    out->front_end = s.front_end;
     HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
-    HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));
+    if (s.front_end != DG_FE_MAP || s.map_built) {        // (a map submission has a front-end half only when it built the map layer)
+        HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
+        HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));
+    } else {
+        out->total_ms = out->raster_ms;
+    }
     out->n_spans = s.n_spans; out->n_frames = (uint64_t)s.n_frames; out->covered_pixels = s.covered;
     out->host_ms = s.host_ms; out->list_bytes = s.list_bytes;
     out->n_walls = s.n_walls; out->n_planes = s.n_planes;
-    out->front_end = s.fs_mode ? DG_FE_DEVICE_SEGS : s.fe_mode ? DG_FE_DEVICE : DG_FE_HOST;
     return DG_OK;
 }
 

@@ -1,0 +1,130 @@
+// slab_layout.h — what lies where in every slab the runtime packs, declared once.  A slab is one allocation (pinned staging and / or
+// HBM) that holds several arrays, each starting on a 256-byte boundary.  context.cpp packs and points into slabs through these
+// layouts, dg_create sizes the slabs by the same layouts evaluated at the capacities, and the CPU harness (tests/emul) and
+// tests/slab_layout read them too: plain host C++, no HIP include.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "fs_frame.h"
+
+namespace dg {
+
+constexpr size_t SLAB_ALIGN = 256;
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Bump cursor over one slab: take() hands out the next piece's offset, end() is where the last piece ends (what has to be
+// allocated or copied), next where a further piece would start.
+struct SlabCursor {
+    size_t next = 0, last_end = 0;
+    size_t take(size_t bytes) {
+        const size_t at = next;
+        last_end = at + bytes;
+        next = align_up(last_end, SLAB_ALIGN);
+        return at;
+    }
+    size_t end() const { return last_end; }
+};
+
+inline size_t fe_bin_offsets(size_t W) { return (W + FE_BIN_W - 1) / FE_BIN_W + 1; }   // column-bin offsets per frame (one past the last bin)
+inline size_t fe_col_groups(size_t W) { return (W + 255) / 256; }                       // dg_fe_columns: one workgroup per (frame, 256 columns)
+
+// Host list slab (DG_FE_HOST, and the one frame redo_frame_host redoes with n_frames = 1): one H2D copy of [0, total).
+struct ListLayout { size_t frames, col_off, walls, planes, spans, total; };
+inline ListLayout list_layout(size_t n_frames, size_t W, size_t walls, size_t planes, size_t spans) {
+    SlabCursor c;
+    ListLayout L;
+    L.frames = c.take(n_frames * sizeof(DevFrame));
+    L.col_off = c.take(n_frames * (W + 1) * 4);
+    L.walls = c.take(walls * sizeof(DevWallRec));
+    L.planes = c.take(planes * sizeof(DevPlaneRec));
+    L.spans = c.take(spans * sizeof(DevSpan));
+    L.total = c.end();
+    return L;
+}
+
+// Record slab of the device column walk as the host walker packs it (DG_FE_DEVICE): one H2D copy of [0, total).
+struct FeLayout { size_t frames, fframes, parts, sprites, behind, sky, bin_off, sbin_off, bins, sbins, order, total; };
+inline FeLayout fe_layout(size_t n_frames, size_t W, size_t parts, size_t sprites, size_t behind, size_t skies, size_t bins, size_t sbins) {
+    SlabCursor c;
+    FeLayout L;
+    L.frames = c.take(n_frames * sizeof(DevFrame));
+    L.fframes = c.take(n_frames * sizeof(FeFrame));
+    L.parts = c.take(parts * sizeof(FePart));
+    L.sprites = c.take(sprites * sizeof(FeSprite));
+    L.behind = c.take(behind * 4);
+    L.sky = c.take(skies * 4);
+    L.bin_off = c.take(n_frames * fe_bin_offsets(W) * 4);
+    L.sbin_off = c.take(n_frames * fe_bin_offsets(W) * 4);
+    L.bins = c.take(bins * 2);
+    L.sbins = c.take(sbins * 2);
+    L.order = c.take(n_frames * fe_col_groups(W) * 4);                  // dg_fe_columns' launch order
+    L.total = c.end();
+    return L;
+}
+
+// The seg walk's strides, which follow the scene and the frame width.
+inline uint32_t fs_sprite_stride(uint32_t n_mobjs) { return std::min<uint32_t>(FS_SPRITE_CAP, std::max<uint32_t>(32u, (n_mobjs + 31u) / 32u * 32u)); }
+inline uint32_t fs_sbin_stride(uint32_t sprite_stride, size_t W) { return std::min<uint32_t>(FS_SBIN_CAP, sprite_stride * (uint32_t)((W + FE_BIN_W - 1) / FE_BIN_W)); }
+// Longest candidate list a frame of the scene can have (every call of every seg), in whole keep-bit words.
+inline uint32_t fs_cl_row_cap(uint32_t n_segs) { return (n_segs * FS_CALLS + 31u) / 32u * 32u; }
+
+// Record slab of the same walk as the device seg walk fills it (DG_FE_DEVICE_SEGS), with fixed per-frame strides: [0, upload) is
+// copied from the host, the rest is written by dg_light_rows / dg_mobj_rows / dg_fs_*.
+//   per_view_state: every frame has its own copy of the two state arrays (the kernels index them with a per-frame stride) and, with the
+//   effects on, a mask of the entries its state overrides (the rows are then completed in place); without it there is one copy for the
+//   batch, and the effects' kernels write per-view rows from it into the device-written part.
+struct FsLayout {
+    size_t frames, views, lights, mstate, lmask, mmask;                                                    // uploaded
+    size_t lrows, mrows, fframes, parts, sprites, behind, sky, bin_off, sbin_off, bins, sbins;             // device-written
+    size_t upload, total;
+};
+inline FsLayout fs_layout(size_t n_frames, size_t W, size_t n_sectors, size_t n_mobjs, bool per_view_state, bool lfx, bool mfx,
+                          uint32_t sprite_stride, uint32_t sbin_stride) {
+    const size_t n = n_frames, state_frames = per_view_state ? n : 1;
+    SlabCursor c;
+    FsLayout L;
+    L.frames = c.take(n * sizeof(DevFrame));
+    L.views = c.take(n * sizeof(dg_view));
+    L.lights = c.take(state_frames * n_sectors * 2);
+    L.mstate = c.take(state_frames * n_mobjs * 4);
+    L.lmask = c.take(lfx && per_view_state ? n * ((n_sectors + 31) / 32) * 4 : 0);
+    L.mmask = c.take(mfx && per_view_state ? n * ((n_mobjs + 31) / 32) * 4 : 0);
+    L.lrows = c.take(lfx && !per_view_state ? n * n_sectors * 2 : 0);
+    L.upload = L.lrows;
+    L.mrows = c.take(mfx && !per_view_state ? n * n_mobjs * 4 : 0);
+    L.fframes = c.take(n * sizeof(FeFrame));
+    L.parts = c.take(n * FS_PART_CAP * sizeof(FePart));
+    L.sprites = c.take(n * sprite_stride * sizeof(FeSprite));
+    L.behind = c.take(n * sprite_stride * FS_BEHIND_WORDS * 4);
+    L.sky = c.take(n * FS_SKY_CAP * 4);
+    L.bin_off = c.take(n * fe_bin_offsets(W) * 4);
+    L.sbin_off = c.take(n * fe_bin_offsets(W) * 4);
+    L.bins = c.take(n * FS_BIN_CAP * 2);
+    L.sbins = c.take(n * sbin_stride * 2);
+    L.total = c.end();
+    return L;
+}
+
+// Per-batch scratch of the seg walk, sized by the scene: the occupancy rows (zero before every walk: dg_fs_frame leaves them so), the
+// candidate rows they index (never cleared) and, only for a scene whose frames can have more candidates than dg_fs_frame's shared
+// memory holds (FS_CL_CAP), per frame a candidate list with its keep bits — so that no frame of the map is handed back to the host
+// for its number of candidates.  cl_row_cap is FsParams::cl_row_cap: 0 when there are no such rows (cl_rows == keep_rows then).
+struct FsScratchLayout { size_t occ, lite, cl_rows, keep_rows, total, zero_bytes; uint32_t cl_row_cap; };
+inline FsScratchLayout fs_scratch_layout(size_t max_batch, uint32_t n_segs) {
+    const uint32_t cap = fs_cl_row_cap(n_segs);
+    SlabCursor c;
+    FsScratchLayout L;
+    L.cl_row_cap = cap > FS_CL_CAP ? cap : 0u;
+    L.zero_bytes = max_batch * (size_t)fs_occ_words(n_segs) * 4;
+    L.occ = c.take(L.zero_bytes);
+    L.lite = c.take(max_batch * (size_t)n_segs * FS_CALLS * sizeof(uint2));
+    L.cl_rows = c.take(max_batch * (size_t)L.cl_row_cap * 4);
+    L.keep_rows = c.take(max_batch * (size_t)(L.cl_row_cap / 32) * 4);
+    L.total = c.end();
+    return L;
+}
+
+}  // namespace dg

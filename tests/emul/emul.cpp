@@ -15,6 +15,7 @@
 #include "../../doom-rust-renderer_amd/csrc/frontend.hpp"
 #include "../../doom-rust-renderer_amd/csrc/raster_core.h"
 #include "../../doom-rust-renderer_amd/csrc/scene.hpp"
+#include "../../doom-rust-renderer_amd/csrc/slab_layout.h"
 
 using namespace dg;
 
@@ -581,12 +582,12 @@ extern "C" int emul_fs_frame(void *scene, int W, int H, const dg_view *view_in, 
     P.mobjs = sc.fs_mobjs.data(); P.sframes = sc.sprite_frames_fs();
     P.anc_off = sc.fs_anc_off.data(); P.anc = sc.fs_anc.data();
     P.n_segs = (uint32_t)sc.segs.size(); P.n_leaves = (uint32_t)sc.subsectors.size(); P.n_mobjs = (uint32_t)sc.mobjs.size();
-    P.sprite_stride = std::min<uint32_t>(FS_SPRITE_CAP, std::max<uint32_t>(32u, (P.n_mobjs + 31u) / 32u * 32u));        // (context.cpp: upload_fs_scene)
-    P.sbin_stride = std::min<uint32_t>(FS_SBIN_CAP, P.sprite_stride * nb);
+    P.sprite_stride = fs_sprite_stride(P.n_mobjs);                                                        // (as upload_fs_scene sets them: slab_layout.h)
+    P.sbin_stride = fs_sbin_stride(P.sprite_stride, (size_t)W);
     P.sector_light = lights.data(); P.mobj_state = mstate.data();
     P.views = &view; P.n_frames = 1;
     std::vector<uint32_t> occ(fs_occ_words(P.n_segs), 0);
-    const uint32_t cl_row_cap = (P.n_segs * FS_CALLS + 31u) / 32u * 32u;                                  // (context.cpp: upload_fs_scene)
+    const uint32_t cl_row_cap = fs_cl_row_cap(P.n_segs);
     std::vector<uint32_t> cl_rows(cl_row_cap, 0xdeadbeefu), keep_rows(cl_row_cap / 32, 0xdeadbeefu);
     P.cl_rows = cl_rows.data(); P.keep_rows = keep_rows.data(); P.cl_row_cap = g_no_cl_rows ? 0u : cl_row_cap;
     P.lite = lite.data(); P.occ = occ.data(); P.flags = flags.data();
@@ -680,7 +681,7 @@ extern "C" int emul_fs_kept_counts(const uint32_t *survivors, const uint32_t *sk
     }
     FsParams P{};
     P.n_segs = total / FS_CALLS + 1;
-    P.cl_row_cap = (P.n_segs * FS_CALLS + 31u) / 32u * 32u;
+    P.cl_row_cap = fs_cl_row_cap(P.n_segs);
     std::vector<uint32_t> cl(P.cl_row_cap, 0), keep(P.cl_row_cap / 32, 0), occ(fs_occ_words(P.n_segs), 0);
     std::vector<uint2> lite(1, uint2{0xdeadbeefu, 0xdeadbeefu});
     P.cl_rows = cl.data(); P.keep_rows = keep.data(); P.occ = occ.data(); P.lite = lite.data();
