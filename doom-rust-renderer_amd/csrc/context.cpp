@@ -204,19 +204,18 @@ struct Slot {
     // The game state frame i of the last submission was rendered with, for the host walker: nullptr = the scene as it is (unchanged since the
     // submission, no per-view snapshot); else the submit-time scene state with the view's own entries on top (later entries win).
     struct RedoState { std::vector<dg_sector_light> lights; std::vector<dg_mobj_state> mobjs; dg_view_state st{}; };
-    // lfx: the light effects the frame was drawn with — their sectors keep the effect's level, so the snapshot does not list them.
-    // mfx: likewise the map-object thinkers and the objects they drive.
-    const dg_view_state *state_for_redo(const Scene &sc, int i, RedoState &tmp, const LightFx &lfx, const MobjFx &mfx) const {
+    // fx: the effects the frame was drawn with — the light effects' sectors keep the effect's level and the objects the thinkers drive
+    // their state, so the snapshot does not list them.
+    const dg_view_state *state_for_redo(const Scene &sc, int i, RedoState &tmp, const SceneFx &fx) const {
         const dg_view_state *own = states.empty() ? nullptr : &states[(size_t)i];
         if (snap_scene != &sc || snap_rev == sc.revision) return own;
         tmp.lights.clear();
-        const bool fx_on = lfx.on() && lfx.rec_of.size() == snap_lights.size();
+        const bool lfx = fx.light.fits(sc), mfx = fx.mobj.fits(sc);      // (the snapshot has the scene's sizes: snapshot_scene)
         for (const dg_sector_light &l : snap_lights)
-            if (!fx_on || lfx.rec_of[(size_t)l.sector] < 0) tmp.lights.push_back(l);
+            if (!lfx || fx.light.rec_of[(size_t)l.sector] < 0) tmp.lights.push_back(l);
         tmp.mobjs.clear();
-        const bool mfx_on = mfx.on() && mfx.type_of.size() == snap_mobjs.size();
         for (const dg_mobj_state &m : snap_mobjs)
-            if (!mfx_on || mfx.type_of[(size_t)m.mobj] < 0) tmp.mobjs.push_back(m);
+            if (!mfx || fx.mobj.type_of[(size_t)m.mobj] < 0) tmp.mobjs.push_back(m);
         if (own) { tmp.lights.insert(tmp.lights.end(), own->lights, own->lights + own->n_lights); tmp.mobjs.insert(tmp.mobjs.end(), own->mobjs, own->mobjs + own->n_mobjs); }
         tmp.st = dg_view_state{tmp.lights.data(), (uint32_t)tmp.lights.size(), tmp.mobjs.data(), (uint32_t)tmp.mobjs.size()};
         return &tmp.st;
@@ -282,17 +281,14 @@ struct dg_ctx {
     int since_fs_probe = 0;             // host-walker batches since the seg walk was last timed (likewise)
     int gpu_samples[2] = {0, 0};        // finished batches seen per mode (host per-seg half / seg walk): the first of each runs on cold caches and clocks, not counted
     DevPtr<uint8_t> d_fs_scene;
-    // wall effects: the scene's WallFx as of dg_upload_scene (every front end draws with this copy), and for the seg walk its device tables
-    WallFx fx;
-    DevPtr<uint8_t> d_wall_fx;          // FsSegFx per seg | the live animation lists (only while fx.on() and the seg walk is uploaded)
+    // the scene's effects as of dg_upload_scene (every front end draws with this copy), and for the seg walk the device tables of each
+    // effect that is on (only while the seg walk is uploaded)
+    SceneFx fx;
+    DevPtr<uint8_t> d_wall_fx;          // FsSegFx per seg | the live animation lists
     FsFx fs_fx{};
-    // light effects: the scene's LightFx as of dg_upload_scene (likewise), and for the seg walk its records, tables and per-sector map
-    LightFx lfx;
-    DevPtr<uint8_t> d_light_fx;         // LfxRec per effect sector | rec_of per sector | tables (only while lfx.on() and the seg walk is uploaded)
+    DevPtr<uint8_t> d_light_fx;         // LfxRec per effect sector | rec_of per sector | tables
     LfxRows lfx_proto{};                // its pointers and the seed, filled at upload
-    // map-object thinkers: the scene's MobjFx as of dg_upload_scene (likewise), and for the seg walk its tables
-    MobjFx mfx;
-    DevPtr<uint8_t> d_mobj_fx;          // steps | chains | types | type_of per map object | events (only while mfx.on() and the seg walk is uploaded)
+    DevPtr<uint8_t> d_mobj_fx;          // steps | chains | types | type_of per map object | events
     MfxRows mfx_proto{};                // its pointers and counts, filled at upload
     DevPtr<uint8_t> d_fs_scratch;       // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
     size_t fs_zero_bytes = 0;
@@ -428,7 +424,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
             dg_view v = views[i];
             fill_view_trig(v);
             dg_frame_lists fl;
-            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, &c->lfx, &c->mfx);
+            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx);
             if (!rc[(size_t)i]) rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
         }
     });
@@ -472,7 +468,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         FeFrameOut &o = c->fe_out[(size_t)i];
         dg_view v = views[i];
         fill_view_trig(v);
-        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, &c->lfx, &c->mfx);
+        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx);
         if (rc[(size_t)i]) return;
         o.parts.swap(A.parts); o.sprites.swap(A.sprites); o.behind.swap(A.behind); o.sky_parts.swap(A.sky_parts);
         o.bin_off.swap(A.bin_off); o.bin_parts.swap(A.bin_parts); o.sbin_off.swap(A.sbin_off); o.sbin_sprites.swap(A.sbin_sprites);
@@ -584,38 +580,42 @@ struct TablePack {
 
 // DG_FE_DEVICE_SEGS: the scene's per-seg / per-sprite tables and BSP tables (Scene::rebuild_fs_tables) in one device allocation, the
 // tables of the effects that are on in one each, and the per-batch scratch of the seg walk, whose size follows the scene (segs, leaves).
+void drop_fs_scene(dg_ctx *c) { c->d_fs_scene.reset(); c->d_fs_scratch.reset(); c->d_wall_fx.reset(); c->d_light_fx.reset(); c->d_mobj_fx.reset(); }
 int upload_fs_scene(dg_ctx *c, const Scene &sc) {
-    c->d_fs_scene.reset(); c->d_fs_scratch.reset(); c->d_wall_fx.reset(); c->d_light_fx.reset(); c->d_mobj_fx.reset();
+    drop_fs_scene(c);
     c->fs_fx = FsFx{};
-    if (c->fx.on()) {                                   // the wall effects' tables: only for a scene that has them on (dg_wfx_* read them)
+    const WallFx &wfx = c->fx.wall;
+    const LightFx &lfx = c->fx.light;
+    const MobjFx &mfx = c->fx.mobj;
+    if (wfx.on()) {                                     // the wall effects' tables: only for a scene that has them on (dg_wfx_* read them)
         TablePack t;
-        const size_t seg = t.add(c->fx.seg), lists = t.add(c->fx.lists);
+        const size_t seg = t.add(wfx.seg), lists = t.add(wfx.lists);
         HIP_TRY(t.upload(c->d_wall_fx));
         c->fs_fx = FsFx{t.at<FsSegFx>(seg), t.at<FsAnim>(lists)};
     }
     c->lfx_proto = LfxRows{};
-    if (c->lfx.on()) {                                  // the light effects' records and tables: only for a scene that has them on (dg_light_rows reads them)
+    if (lfx.on()) {                                     // the light effects' records and tables: only for a scene that has them on (dg_light_rows reads them)
         TablePack t;
-        const size_t recs = t.add(c->lfx.recs), rec_of = t.add(c->lfx.rec_of), tab = t.add(c->lfx.tab);
+        const size_t recs = t.add(lfx.recs), rec_of = t.add(lfx.rec_of), tab = t.add(lfx.tab);
         HIP_TRY(t.upload(c->d_light_fx));
         c->lfx_proto.recs = t.at<LfxRec>(recs);
         c->lfx_proto.rec_of = t.at<int32_t>(rec_of);
         c->lfx_proto.tab = t.at<uint32_t>(tab);
-        c->lfx_proto.seed = c->lfx.seed;
-        c->lfx_proto.n_sectors = (uint32_t)c->lfx.rec_of.size();
+        c->lfx_proto.seed = lfx.seed;
+        c->lfx_proto.n_sectors = (uint32_t)lfx.rec_of.size();
     }
     c->mfx_proto = MfxRows{};
-    if (c->mfx.on()) {                                  // the map-object thinkers' tables: only for a scene that has them on (dg_mobj_rows reads them)
+    if (mfx.on()) {                                     // the map-object thinkers' tables: only for a scene that has them on (dg_mobj_rows reads them)
         TablePack t;
-        const size_t steps = t.add(c->mfx.steps), chains = t.add(c->mfx.chains), types = t.add(c->mfx.types), type_of = t.add(c->mfx.type_of), events = t.add(c->mfx.events);
+        const size_t steps = t.add(mfx.steps), chains = t.add(mfx.chains), types = t.add(mfx.types), type_of = t.add(mfx.type_of), events = t.add(mfx.events);
         HIP_TRY(t.upload(c->d_mobj_fx));
         c->mfx_proto.steps = t.at<MfxStep>(steps);
         c->mfx_proto.chains = t.at<MfxChain>(chains);
         c->mfx_proto.types = t.at<MfxType>(types);
         c->mfx_proto.type_of = t.at<int32_t>(type_of);
         c->mfx_proto.events = t.at<MfxEvent>(events);
-        c->mfx_proto.n_events = (uint32_t)c->mfx.events.size();
-        c->mfx_proto.n_mobjs = (uint32_t)c->mfx.type_of.size();
+        c->mfx_proto.n_events = (uint32_t)mfx.events.size();
+        c->mfx_proto.n_mobjs = (uint32_t)mfx.type_of.size();
     }
     TablePack t;
     const size_t segs = t.add(sc.fs_segs), leaf = t.add(sc.fs_seg_leaf), first = t.add(sc.fs_leaf_first), sectors = t.add(sc.fs_sectors);
@@ -660,9 +660,9 @@ void calibrate_host(dg_ctx *c, const dg_view *views, int n) {
     FrameArena &A = *c->arenas[0];
     std::string err;
     const int warm = std::min(4, n), timed = std::min(8, n);
-    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx, &c->lfx, &c->mfx); }
+    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx); }
     const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx, &c->lfx, &c->mfx); }
+    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx); }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->ema_host = ms / timed / std::max(1, c->n_threads) * 1.25;     // (the pool does not scale perfectly)
     c->host_samples = std::max(c->host_samples, 2);
@@ -685,6 +685,23 @@ bool choose_fs(dg_ctx *c, const dg_view *views, int n) {
     return fs;
 }
 
+// dg_light_rows / dg_mobj_rows complete the rows the seg walk reads (Rows: LfxRows / MfxRows, whose fields carry the same names).  R
+// becomes the ctx's proto wired to one batch: `row` / `stride` as its base, `mask` the views' override masks (nullptr: no view states),
+// `out` the rows it writes, n elements per frame.  The seg walk's `row` / `stride` move on to those.
+template <class Rows, class T>
+void wire_rows(Rows &R, const Rows &proto, const dg_view *views, int n_frames, const uint32_t *mask, T *out, size_t n, const T *&row, uint32_t &stride) {
+    R = proto;
+    R.views = views;
+    R.n_frames = n_frames;
+    R.base = row;
+    R.base_stride = stride;
+    R.mask = mask;
+    R.mask_words = (uint32_t)((n + 31) / 32);
+    R.out = out;
+    row = out;
+    stride = (uint32_t)n;
+}
+
 // DG_FE_DEVICE_SEGS: nothing of the front end runs on the host.  Per frame it ships the view (trig filled) and the DevFrame header,
 // per batch the scene's current light levels and map-object states; dg_fs_* then write the same record arrays build_batch_fe packs,
 // with fixed per-frame strides (fs_frame.h), into the slot's record slab.
@@ -699,10 +716,10 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     const size_t state_frames = states ? (size_t)n : 1;
     // light effects (dg_light_rows): with view states, per frame a mask of the sectors its state overrides (the rows above are then
     // completed in place); without, the kernel writes the per-view rows from the one base row into the device-written part
-    const bool lfx = c->lfx.on() && c->lfx_proto.recs && c->lfx.rec_of.size() == sc.sectors.size();
+    const bool lfx = c->lfx_proto.recs && c->fx.light.fits(sc);
     const size_t mask_words = (sc.sectors.size() + 31) / 32;
     // map-object thinkers (dg_mobj_rows): the same two layouts for the map-object rows
-    const bool mfx = c->mfx.on() && c->mfx_proto.steps && c->mfx.type_of.size() == sc.mobjs.size();
+    const bool mfx = c->mfx_proto.steps && c->fx.mobj.fits(sc);
     if (mfx && (uint64_t)n * sc.mobjs.size() >= (1ull << 31)) return kPartsUnsupported;
     const size_t mmask_words = (sc.mobjs.size() + 31) / 32;
     const FsLayout L = fs_layout((size_t)n, (size_t)W, sc.sectors.size(), sc.mobjs.size(), states != nullptr, lfx, mfx, c->fs_proto.sprite_stride, c->fs_proto.sbin_stride);
@@ -726,24 +743,17 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         int16_t *l = lights + (size_t)i * sc.sectors.size();
         int32_t *m = mstate + (size_t)i * sc.mobjs.size();
         for (size_t k = 0; k < sc.sectors.size(); k++) l[k] = sc.sectors[k].light;
-        for (size_t k = 0; k < sc.mobjs.size(); k++) m[k] = sc.mobjs[k].sprite_frame < 0 ? -1 : sc.mobjs[k].sprite_frame * 2 + (sc.mobjs[k].full_bright ? 1 : 0);
+        for (size_t k = 0; k < sc.mobjs.size(); k++) m[k] = mfx_encode(sc.mobjs[k].sprite_frame, sc.mobjs[k].full_bright);
         if (!states) return;
         uint32_t *lm = lfx ? lmask + (size_t)i * mask_words : nullptr;
         if (lm) std::memset(lm, 0, mask_words * 4);
         uint32_t *mm = mfx ? mmask + (size_t)i * mmask_words : nullptr;
         if (mm) std::memset(mm, 0, mmask_words * 4);
-        const dg_view_state &st = states[i];                        // the same rules as the host walker's (frontend.cpp: Walker::apply_state): later entries win
-        for (uint32_t k = 0; k < st.n_lights; k++) {
-            if (st.lights[k].sector < 0 || (size_t)st.lights[k].sector >= sc.sectors.size()) { bad_state = i; continue; }
-            l[(size_t)st.lights[k].sector] = (int16_t)st.lights[k].light_level;
-            if (lm) lm[(size_t)st.lights[k].sector / 32] |= 1u << ((uint32_t)st.lights[k].sector % 32);
-        }
-        for (uint32_t k = 0; k < st.n_mobjs; k++) {
-            const dg_mobj_state &ms = st.mobjs[k];
-            if (ms.mobj < 0 || (size_t)ms.mobj >= sc.mobjs.size() || ms.sprite_frame >= (int32_t)sc.sprite_frames.size()) { bad_state = i; continue; }
-            m[(size_t)ms.mobj] = (ms.sprite_frame < 0 ? -1 : ms.sprite_frame) * 2 + (ms.full_bright ? 1 : 0);
-            if (mm) mm[(size_t)ms.mobj / 32] |= 1u << ((uint32_t)ms.mobj % 32);
-        }
+        const unsigned bad = apply_view_state(
+            sc, states[i],
+            [&](size_t k, int32_t level) { l[k] = (int16_t)level; if (lm) lm[k / 32] |= 1u << (k % 32); },
+            [&](size_t k, int32_t val) { m[k] = val; if (mm) mm[k / 32] |= 1u << (k % 32); });
+        if (bad) bad_state = i;
     });
     if (bad_state >= 0) return set_err(DG_ERR_INVALID, "frame " + std::to_string(bad_state.load()) + ": view state: sector, map object or sprite frame index out of range");
 
@@ -752,35 +762,15 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     Q.sector_light = reinterpret_cast<const int16_t *>(d + L.lights);
     Q.mobj_state = reinterpret_cast<const int32_t *>(d + L.mstate);
     Q.light_stride = states ? (uint32_t)sc.sectors.size() : 0u;
-    s.LR = LfxRows{};
-    if (lfx) {                                              // dg_light_rows completes the rows the seg walk reads
-        s.LR = c->lfx_proto;
-        s.LR.views = reinterpret_cast<const dg_view *>(d + L.views);
-        s.LR.base = Q.sector_light;
-        s.LR.base_stride = Q.light_stride;
-        s.LR.mask = states ? reinterpret_cast<const uint32_t *>(d + L.lmask) : nullptr;
-        s.LR.mask_words = (uint32_t)mask_words;
-        s.LR.out = states ? reinterpret_cast<int16_t *>(d + L.lights) : reinterpret_cast<int16_t *>(d + L.lrows);
-        s.LR.n_frames = n;
-        Q.sector_light = s.LR.out;
-        Q.light_stride = (uint32_t)sc.sectors.size();
-    }
     Q.mstate_stride = states ? (uint32_t)sc.mobjs.size() : 0u;
-    s.MR = MfxRows{};
-    if (mfx) {                                              // dg_mobj_rows completes the rows the seg walk reads
-        s.MR = c->mfx_proto;
-        s.MR.views = reinterpret_cast<const dg_view *>(d + L.views);
-        s.MR.base = Q.mobj_state;
-        s.MR.base_stride = Q.mstate_stride;
-        s.MR.mask = states ? reinterpret_cast<const uint32_t *>(d + L.mmask) : nullptr;
-        s.MR.mask_words = (uint32_t)mmask_words;
-        s.MR.out = states ? reinterpret_cast<int32_t *>(d + L.mstate) : reinterpret_cast<int32_t *>(d + L.mrows);
-        s.MR.n_frames = n;
-        Q.mobj_state = s.MR.out;
-        Q.mstate_stride = (uint32_t)sc.mobjs.size();
-    }
     Q.views = reinterpret_cast<const dg_view *>(d + L.views);
     Q.n_frames = n;
+    s.LR = LfxRows{};
+    if (lfx) wire_rows(s.LR, c->lfx_proto, Q.views, n, states ? reinterpret_cast<const uint32_t *>(d + L.lmask) : nullptr,
+                       reinterpret_cast<int16_t *>(d + (states ? L.lights : L.lrows)), sc.sectors.size(), Q.sector_light, Q.light_stride);
+    s.MR = MfxRows{};
+    if (mfx) wire_rows(s.MR, c->mfx_proto, Q.views, n, states ? reinterpret_cast<const uint32_t *>(d + L.mmask) : nullptr,
+                       reinterpret_cast<int32_t *>(d + (states ? L.mstate : L.mrows)), sc.mobjs.size(), Q.mobj_state, Q.mstate_stride);
     Q.flags = s.d_flags.get();
     Q.fframes = reinterpret_cast<FeFrame *>(d + L.fframes);
     Q.parts = reinterpret_cast<FePart *>(d + L.parts);
@@ -906,7 +896,7 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
             hipEvent_t fs_start = s.ev_start;
             if (s.LR.n_frames > 0) { HIP_TRY(launch_light_rows(s.LR, ks, fs_start)); fs_start = nullptr; }     // the rows dg_fs_* read
             if (s.MR.n_frames > 0) { HIP_TRY(launch_mobj_rows(s.MR, ks, fs_start)); fs_start = nullptr; }
-            HIP_TRY(c->fx.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
+            HIP_TRY(c->fx.wall.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
             c->fs_rows_dirty = false;
         }
         HIP_TRY(launch_fe(s.FP, ks, s.seg_walk() ? nullptr : s.ev_start, s.ev_setup));
@@ -941,7 +931,7 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     fill_view_trig(v);
     dg_frame_lists fl;
     Slot::RedoState redo_state;
-    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->lfx, c->mfx), &c->fx, &c->lfx, &c->mfx);
+    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->fx), &c->fx);
     if (!rc) rc = bin_frame(sc, c->fk, fl, bf, err);
     if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
@@ -999,7 +989,7 @@ int settle_slot(dg_ctx *c, Slot &s) {
             std::vector<dg_view_state> sts;
             bool any_state = false;
             for (size_t i = 0; i < views.size(); i++) {
-                const dg_view_state *st = s.state_for_redo(*c->scene, (int)i, redo_states[i], c->lfx, c->mfx);
+                const dg_view_state *st = s.state_for_redo(*c->scene, (int)i, redo_states[i], c->fx);
                 any_state |= st != nullptr;
                 sts.push_back(st ? *st : dg_view_state{nullptr, 0, nullptr, 0});
             }
@@ -1133,7 +1123,7 @@ int dg_scene_sector_lights_at(const dg_scene *s, float ts, int16_t *out, int n) 
     const Scene &sc = *s->sc;
     if (n < 0 || (size_t)n != sc.sectors.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_sector_count");
     for (size_t i = 0; i < sc.sectors.size(); i++) out[i] = sc.sectors[i].light;
-    const LightFx &fx = sc.light_fx;
+    const LightFx &fx = sc.fx.light;
     if (fx.on())
         for (size_t r = 0; r < fx.recs.size(); r++) out[fx.recs[r].sector] = fx.level(r, ts);
     return DG_OK;
@@ -1156,13 +1146,9 @@ int dg_scene_mobj_states_at(const dg_scene *s, float ts, dg_mobj_state *out, int
     if (n < 0 || (size_t)n != sc.mobjs.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_mobj_count");
     for (size_t i = 0; i < sc.mobjs.size(); i++)
         out[i] = dg_mobj_state{(int32_t)i, sc.mobjs[i].sprite_frame < 0 ? -1 : sc.mobjs[i].sprite_frame, sc.mobjs[i].sprite_frame < 0 ? 0 : (sc.mobjs[i].full_bright ? 1 : 0), 0};
-    const MobjFx &fx = sc.mobj_fx;
-    if (fx.on() && fx.type_of.size() == sc.mobjs.size())
-        for (uint32_t i : fx.driven) {
-            const int32_t v = fx.value(i, ts);
-            out[i].sprite_frame = v < 0 ? -1 : v >> 1;
-            out[i].full_bright = v < 0 ? 0 : v & 1;
-        }
+    const MobjFx &fx = sc.fx.mobj;
+    if (fx.fits(sc))
+        for (uint32_t i : fx.driven) mfx_decode(fx.value(i, ts), out[i].sprite_frame, out[i].full_bright);
     return DG_OK;
 }
 int dg_scene_sprite_bitmap_id(const dg_scene *s, const char *sprite, uint8_t frame, uint8_t rot) {
@@ -1181,7 +1167,7 @@ int dg_build_lists(const dg_scene *s, int width, int height, const dg_view *view
     dg_view v = *view;
     fill_view_trig(v);
     std::string err;
-    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err, nullptr, &s->sc->wall_fx, &s->sc->light_fx, &s->sc->mobj_fx);
+    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err, nullptr, &s->sc->fx);
     return rc ? set_err(rc, err) : DG_OK;
 }
 
@@ -1347,9 +1333,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     HIP_TRY(launch_row_table(c->dscene, c->dk, c->d_row_tab.get(), nullptr));
     HIP_TRY(hipDeviceSynchronize());
     c->scene = &sc;
-    c->fx = sc.wall_fx;                                 // dg_scene_set_wall_effects takes effect here
-    c->lfx = sc.light_fx;                               // dg_scene_set_light_effects too
-    c->mfx = sc.mobj_fx;                                // and dg_scene_set_mobj_thinkers with its events
+    c->fx = sc.fx;                                      // the effects' setters (and dg_scene_mobj_event) take effect here
     c->fe_scene_ok = sky.w >= 256 && sky.h >= 128;    // a smaller sky bitmap is an index panic only when a sky visplane is drawn: host path
     c->uploaded_texels = sc.texel_idx.size();
     c->fs_scene_ok = false;
@@ -1359,7 +1343,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
         if (rc) {
             static bool said = false;                      // once per process: the ctx works, but not the way it was asked to
             if (!said) { said = true; std::fprintf(stderr, "doomgpu: DG_FE_AUTO keeps the per-seg half on the host: no device memory for the seg walk's per-batch rows (%d views x %zu segs)\n", c->cfg.max_batch, sc.segs.size()); }
-            c->d_fs_scene.reset(); c->d_fs_scratch.reset(); c->d_wall_fx.reset(); c->d_light_fx.reset(); c->d_mobj_fx.reset();
+            drop_fs_scene(c);
             c->fs_scene_ok = false;
             (void)hipGetLastError();
         }

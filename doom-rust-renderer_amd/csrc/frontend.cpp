@@ -120,73 +120,42 @@ struct Walker {
     const WallFx *fx = nullptr;             // the wall effects to draw with (nullptr: none)
     const LightFx *lfx = nullptr;           // the light effects to draw with (nullptr: none)
     const MobjFx *mfx = nullptr;            // the map-object thinkers to draw with (nullptr: none)
-
-    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const WallFx *wfx,
-           const LightFx *lf, const MobjFx *mf)
-        : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e), fx(wfx && wfx->on() ? wfx : nullptr),
-          lfx(lf && lf->on() && lf->rec_of.size() == s.sectors.size() ? lf : nullptr),
-          mfx(mf && mf->on() && mf->type_of.size() == s.mobjs.size() ? mf : nullptr) {
-        ppos = V2{v.x, v.y};
-        player_height = v.floor_height + kEye;
-        apply_state(st);
-        if (lfx) {                                                   // every effect sector once per frame, not once per seg
-            if (A.fx_light.size() != sc.sectors.size()) A.fx_light.assign(sc.sectors.size(), kNoOverride);
-            for (size_t r = 0; r < lfx->recs.size(); r++) A.fx_light[lfx->recs[r].sector] = lfx->level(r, v.timestamp);
-        }
-        if (mfx) {                                                   // every driven object once per frame
-            if (A.fx_mobj.size() != sc.mobjs.size()) A.fx_mobj.assign(sc.mobjs.size(), kNoOverride);
-            for (uint32_t i : mfx->driven) A.fx_mobj[i] = mfx->value(i, v.timestamp);
-        }
-    }
-    ~Walker() {                                                      // the arena's overlay tables go back to "no override"
-        if (lfx)
-            for (const LfxRec &r : lfx->recs) A.fx_light[r.sector] = kNoOverride;
-        if (mfx)
-            for (uint32_t i : mfx->driven) A.fx_mobj[i] = kNoOverride;
-        if (!state) return;
-        for (uint32_t i = 0; i < state->n_lights; i++)
-            if ((size_t)state->lights[i].sector < A.light_ov.size()) A.light_ov[(size_t)state->lights[i].sector] = kNoOverride;
-        for (uint32_t i = 0; i < state->n_mobjs; i++)
-            if ((size_t)state->mobjs[i].mobj < A.mobj_ov.size()) A.mobj_ov[(size_t)state->mobjs[i].mobj] = kNoOverride;
-    }
     static constexpr int32_t kNoOverride = INT32_MIN;
 
     // sector.light_level / map object state as the reference's thinkers would have left them before this frame
     // (src/lights.rs:47-259, src/map_objects.rs:63-121): the view's snapshot entry if there is one, else the light effect's level
-    //  or the map-object thinker's state (§8d), else the scene's value.
-    void apply_state(const dg_view_state *st) {
-        if (!st || (st->n_lights == 0 && st->n_mobjs == 0)) return;
-        if (A.light_ov.size() != sc.sectors.size()) A.light_ov.assign(sc.sectors.size(), kNoOverride);
-        if (A.mobj_ov.size() != sc.mobjs.size()) A.mobj_ov.assign(sc.mobjs.size(), kNoOverride);
-        for (uint32_t i = 0; i < st->n_lights; i++) {
-            const dg_sector_light &l = st->lights[i];
-            if (l.sector < 0 || (size_t)l.sector >= sc.sectors.size()) { status = DG_ERR_INVALID; err = "view state: sector index out of range"; continue; }
-            A.light_ov[(size_t)l.sector] = (int32_t)l.light_level;
-        }
-        for (uint32_t i = 0; i < st->n_mobjs; i++) {
-            const dg_mobj_state &m = st->mobjs[i];
-            if (m.mobj < 0 || (size_t)m.mobj >= sc.mobjs.size() || m.sprite_frame >= (int32_t)sc.sprite_frames.size()) {
-                status = DG_ERR_INVALID; err = "view state: map object or sprite frame index out of range"; continue;
-            }
-            A.mobj_ov[(size_t)m.mobj] = (m.sprite_frame < 0 ? -1 : m.sprite_frame) * 2 + (m.full_bright ? 1 : 0);   // -2 / -1: S_NULL
-        }
-        state = st;
+    //  or the map-object thinker's state (§8d), else the scene's value.  The arena's two rows hold what overrides the
+    // scene: the effects' values, every effect sector and driven object once per frame, then the view's entries on top.
+    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const SceneFx *f)
+        : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e), state(st), fx(f && f->wall.on() ? &f->wall : nullptr),
+          lfx(f && f->light.fits(s) ? &f->light : nullptr), mfx(f && f->mobj.fits(s) ? &f->mobj : nullptr) {
+        ppos = V2{v.x, v.y};
+        player_height = v.floor_height + kEye;
+        if (A.light_row.size() != sc.sectors.size()) A.light_row.assign(sc.sectors.size(), kNoOverride);
+        if (A.mobj_row.size() != sc.mobjs.size()) A.mobj_row.assign(sc.mobjs.size(), kNoOverride);
+        if (lfx)
+            for (size_t r = 0; r < lfx->recs.size(); r++) A.light_row[lfx->recs[r].sector] = lfx->level(r, v.timestamp);
+        if (mfx)
+            for (uint32_t i : mfx->driven) A.mobj_row[i] = mfx->value(i, v.timestamp);
+        if (!state) return;
+        const unsigned bad = apply_view_state(sc, *state, [&](size_t i, int32_t level) { A.light_row[i] = level; }, [&](size_t i, int32_t val) { A.mobj_row[i] = val; });
+        if (bad) { status = DG_ERR_INVALID; err = bad & 2u ? "view state: map object or sprite frame index out of range" : "view state: sector index out of range"; }
+    }
+    ~Walker() {                                                      // the entries written go back to "no override"
+        if (lfx)
+            for (const LfxRec &r : lfx->recs) A.light_row[r.sector] = kNoOverride;
+        if (mfx)
+            for (uint32_t i : mfx->driven) A.mobj_row[i] = kNoOverride;
+        if (state) apply_view_state(sc, *state, [&](size_t i, int32_t) { A.light_row[i] = kNoOverride; }, [&](size_t i, int32_t) { A.mobj_row[i] = kNoOverride; });
     }
     int16_t sector_light(int sector) const {
-        if (state && A.light_ov[(size_t)sector] != kNoOverride) return (int16_t)A.light_ov[(size_t)sector];
-        if (lfx && A.fx_light[(size_t)sector] != kNoOverride) return (int16_t)A.fx_light[(size_t)sector];
-        return sc.sectors[(size_t)sector].light;
+        const int32_t v = A.light_row[(size_t)sector];
+        return v != kNoOverride ? (int16_t)v : sc.sectors[(size_t)sector].light;
     }
     void mobj_state(size_t i, int32_t &sprite_frame, int32_t &full_bright) const {
         const MapObjectRec &m = sc.mobjs[i];
-        sprite_frame = m.sprite_frame; full_bright = m.full_bright;
-        if (state && A.mobj_ov[i] != kNoOverride) {
-            const int32_t v = A.mobj_ov[i];
-            sprite_frame = v < 0 ? -1 : v >> 1; full_bright = v < 0 ? 0 : v & 1;
-        } else if (mfx && A.fx_mobj[i] != kNoOverride) {
-            const int32_t v = A.fx_mobj[i];
-            sprite_frame = v < 0 ? -1 : v >> 1; full_bright = v < 0 ? 0 : v & 1;
-        }
+        if (A.mobj_row[i] != kNoOverride) mfx_decode(A.mobj_row[i], sprite_frame, full_bright);
+        else { sprite_frame = m.sprite_frame; full_bright = m.full_bright; }
     }
 
     int fail(const std::string &m) {
@@ -624,8 +593,7 @@ struct Walker {
 
 }  // namespace
 
-int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const WallFx *fx,
-                      const LightFx *lfx, const MobjFx *mfx) {
+int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const SceneFx *fx) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.renders.clear(); A.columns.clear(); A.visplanes.clear(); A.plane_tb.clear(); A.order.clear();
     A.recs->clear(); A.floor_tb.clear(); A.ceil_tb.clear();
@@ -635,7 +603,7 @@ int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameA
     A.top_clip.resize((size_t)W);
     A.bottom_clip.resize((size_t)W);
 
-    Walker wk(sc, W, H, view, A, err, state, fx, lfx, mfx);
+    Walker wk(sc, W, H, view, A, err, state, fx);
     if (wk.status) return wk.status;
     wk.walk_bsp();
     if (wk.status) return wk.status;
@@ -683,12 +651,11 @@ void bin_by_columns(const std::vector<T> &recs, int W, Range range, std::vector<
 }
 }  // namespace
 
-int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state, const WallFx *fx,
-                      const LightFx *lfx, const MobjFx *mfx) {
+int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state, const SceneFx *fx) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.parts.clear(); A.sprites.clear(); A.behind.clear(); A.sky_parts.clear(); A.behind_words = 0; A.n_sky_slots = 0;
     A.recs->clear();
-    Walker wk(sc, W, H, view, A, err, state, fx, lfx, mfx);
+    Walker wk(sc, W, H, view, A, err, state, fx);
     if (wk.status) return wk.status;
     wk.parts_mode = true;
     wk.walk_bsp();

@@ -45,9 +45,9 @@ struct FrameArena {
     std::vector<int16_t> floor_tb, ceil_tb;
     std::vector<uint8_t> hor_ocl;
     std::vector<int16_t> floor_ocl, ceil_ocl, top_clip, bottom_clip;
-    std::vector<int32_t> light_ov, mobj_ov;     // per sector / per map object: this view's snapshot value or "no override" (Walker)
-    std::vector<int32_t> fx_light;              // per sector: the light effect's level at this view's tics or "no effect" (Walker)
-    std::vector<int32_t> fx_mobj;               // per map object: the thinker's state at this view's tics or "not driven" (Walker)
+    // per sector / per map object: the value this view draws with (its snapshot entry, else the effect's value at its tics) or "no
+    // override"; the Walker writes the entries of one frame and takes them back
+    std::vector<int32_t> light_row, mobj_row;
     FrameArena();
     ~FrameArena();
     FrameArena(const FrameArena &) = delete;
@@ -57,12 +57,28 @@ struct FrameArena {
 // Fills `arena` and `out` (pointers into arena).  Returns DG_OK or DG_ERR_RENDER with `err` set where the
 // reference would panic.  `view` must have its trig fields filled.
 // `state` (optional): the view's game-state snapshot (include/doomgpu.h dg_view_state).
-// `fx` (optional): the wall effects to draw with (Scene::wall_fx, or the copy a dg_ctx uploaded).
-// `lfx` (optional): the light effects to draw with (Scene::light_fx, or the copy a dg_ctx uploaded).
-// `mfx` (optional): the map-object thinkers to draw with (Scene::mobj_fx, or the copy a dg_ctx uploaded).
+// `fx` (optional): the effects to draw with (Scene::fx, or the copy a dg_ctx uploaded); nullptr: none.
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, dg_frame_lists &out, std::string &err,
-                      const dg_view_state *state = nullptr, const WallFx *fx = nullptr, const LightFx *lfx = nullptr,
-                      const MobjFx *mfx = nullptr);
+                      const dg_view_state *state = nullptr, const SceneFx *fx = nullptr);
+
+// Checks a view's snapshot against the scene's ranges and hands every valid entry, in order (later entries win), to light(sector, level)
+// or mobj(map object, mfx_encode'd state).  Returns 0, or bit 0: a sector index was out of range, bit 1: a map object or sprite frame
+// index was.  The host walker and build_batch_fs (context.cpp) both go through it.
+template <class LightFn, class MobjFn>
+unsigned apply_view_state(const Scene &sc, const dg_view_state &st, LightFn light, MobjFn mobj) {
+    unsigned bad = 0;
+    for (uint32_t i = 0; i < st.n_lights; i++) {
+        const dg_sector_light &l = st.lights[i];
+        if (l.sector < 0 || (size_t)l.sector >= sc.sectors.size()) bad |= 1u;
+        else light((size_t)l.sector, l.light_level);
+    }
+    for (uint32_t i = 0; i < st.n_mobjs; i++) {
+        const dg_mobj_state &m = st.mobjs[i];
+        if (m.mobj < 0 || (size_t)m.mobj >= sc.mobjs.size() || m.sprite_frame >= (int32_t)sc.sprite_frames.size()) bad |= 2u;
+        else mobj((size_t)m.mobj, mfx_encode(m.sprite_frame, m.full_bright));
+    }
+    return bad;
+}
 
 void fill_view_trig(dg_view &v);
 
@@ -72,8 +88,7 @@ void fill_view_trig(dg_view &v);
 // host list path can judge: the caller redoes the frame with build_frame_lists).
 constexpr int kPartsUnsupported = 1000;
 int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, std::string &err, const dg_view_state *state = nullptr,
-                      const WallFx *fx = nullptr, const LightFx *lfx = nullptr,
-                      const MobjFx *mfx = nullptr);
+                      const SceneFx *fx = nullptr);
 
 // Per-record constants of render_vertical_bitmap_line (bitmap_render.rs:233-251), shared by the binner and the parts builder.
 DevWallRec make_wall_rec(const BitmapInfo &bi, float lsx, float lsy, float lex, float ley, float start_offset, int32_t start_x, int32_t end_x,

@@ -25,6 +25,13 @@ struct MfxType { int32_t chain[4]; };
 struct MfxEvent { uint32_t tics, what; };
 static_assert(sizeof(MfxStep) == 8 && sizeof(MfxChain) == 24 && sizeof(MfxType) == 16 && sizeof(MfxEvent) == 8, "mobj_fx.h layouts");
 
+// A map-object state as one value (host side; the device reads it in fs_ph_mobj): sprite_frame * 2 + full_bright, -1 for S_NULL.
+inline int32_t mfx_encode(int32_t sprite_frame, int32_t full_bright) { return sprite_frame < 0 ? -1 : sprite_frame * 2 + (full_bright ? 1 : 0); }
+inline void mfx_decode(int32_t v, int32_t &sprite_frame, int32_t &full_bright) {
+    sprite_frame = v < 0 ? -1 : v >> 1;
+    full_bright = v < 0 ? 0 : v & 1;
+}
+
 // The value of chain c after m mutates.
 DG_HD int32_t mfx_chain_value(const MfxChain &c, const MfxStep *steps, uint32_t m) {
     const MfxStep *p = steps + c.off;

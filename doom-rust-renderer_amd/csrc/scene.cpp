@@ -100,6 +100,14 @@ struct Builder {
     int first_sprite = -1, last_sprite = -1;
 
     explicit Builder(Scene &s) : sc(s), wad(s.wad) {}
+    // A builder for a scene that is already loaded: the caches it needs, from what is in the scene
+    static Builder resume(Scene &s) {
+        Builder b(s);
+        for (size_t i = 0; i < s.bitmap_names.size(); i++) b.bitmap_by_key[s.bitmap_names[i]] = (int)i;
+        b.first_sprite = b.wad.find("S_START");
+        b.last_sprite = b.wad.find("S_END");
+        return b;
+    }
 
     int add_bitmap(const std::string &key, const Image &im, int16_t left, int16_t top) {
         BitmapInfo bi;
@@ -355,56 +363,77 @@ int Scene::sprite_bitmap_id(const std::string &sprite, uint8_t frame, uint8_t ro
     return TEX_UNKNOWN;
 }
 
+// Sprites::new restricted to one frame (src/graphics/sprites.rs:26-97), as far as the lump names tell: the lumps that hold (sprite,
+// frame) in lump order with the rotation key each fills, whether the frame rotates, and the verdict — error is what add_sprite_frame
+// throws, empty when the frame resolves.  Decodes nothing.
+struct SpriteScan {
+    struct Hit { int lump; uint8_t rot; bool mirror; };
+    std::vector<Hit> hits;
+    bool rotate = false;
+    std::string error;
+};
+static SpriteScan scan_sprite_frame(const Builder &b, const std::string &sprite, uint8_t frame) {
+    SpriteScan s;
+    bool have[256] = {false};
+    for (int idx = b.first_sprite; idx < b.last_sprite && s.error.empty(); idx++) {
+        const std::string &nm = b.wad.dir[(size_t)idx].name;
+        if (sprite.size() != 4 || nm.compare(0, 4, sprite) != 0) continue;
+        if (nm.size() < 6) s.error = "sprite lump " + nm + " too short";
+        else if (nm.size() == 7) s.error = "sprite lump " + nm + " malformed";
+        else
+            for (size_t at = 4; at < nm.size(); at += 2)
+                if ((uint8_t)(nm[at] - 65) == frame) {
+                    s.hits.push_back({idx, (uint8_t)(nm[at + 1] - 48), at > 4});
+                    have[s.hits.back().rot] = true;
+                }
+    }
+    if (!s.error.empty()) return s;
+    int nkeys = 0;
+    for (bool h : have) nkeys += h;
+    s.rotate = nkeys != 1;
+    if (nkeys == 0) s.error = "Unknown frame " + std::to_string(frame) + " for " + sprite + " (sprites.rs:104)";
+    else if (nkeys == 1 && !have[0]) s.error = "sprite " + sprite + ": single rotation is not 0";
+    else if (nkeys != 1 && nkeys != 8) s.error = "Got something other than 8 rotations for " + sprite;
+    else if (nkeys == 8 && std::find(have + 1, have + 9, false) != have + 9) s.error = "sprite " + sprite + " misses a rotation";
+    return s;
+}
+static int sprite_frame_index(const Scene &sc, const std::string &key) {
+    for (size_t i = 0; i < sc.sprite_frame_keys.size(); i++)
+        if (sc.sprite_frame_keys[i] == key) return (int)i;
+    return -1;
+}
+// Whether add_sprite_frame would resolve (sprite, frame) as far as the lump names tell, decoding nothing.
+static bool sprite_frame_resolves(const Builder &b, const std::string &sprite, uint8_t frame) {
+    return sprite_frame_index(b.sc, sprite + (char)('A' + frame)) >= 0 || scan_sprite_frame(b, sprite, frame).error.empty();
+}
 static int add_sprite_frame(Builder &b, const std::string &sprite, uint8_t frame) {
     Scene &sc = b.sc;
     std::string key = sprite + (char)('A' + frame);
-    for (size_t i = 0; i < sc.sprite_frame_keys.size(); i++)
-        if (sc.sprite_frame_keys[i] == key) return (int)i;
-    // Sprites::new restricted to one frame (src/graphics/sprites.rs:26-97)
+    const int known = sprite_frame_index(sc, key);
+    if (known >= 0) return known;
+    const SpriteScan scan = scan_sprite_frame(b, sprite, frame);
+    if (!scan.error.empty()) throw LoadError(scan.error);
     int rot_bitmap[256];
-    bool have[256] = {false};
-    for (int idx = b.first_sprite; idx < b.last_sprite; idx++) {
-        const std::string &nm = b.wad.dir[(size_t)idx].name;
-        if (sprite.size() != 4 || nm.compare(0, 4, sprite) != 0) continue;
-        if (nm.size() < 6) throw LoadError("sprite lump " + nm + " too short");
-        uint8_t fr = (uint8_t)(nm[4] - 65), ro = (uint8_t)(nm[5] - 48);
-        if (fr == frame) { rot_bitmap[ro] = b.picture_bitmap(nm, false); have[ro] = true; }
-        if (nm.size() > 6) {
-            if (nm.size() < 8) throw LoadError("sprite lump " + nm + " malformed");
-            uint8_t fr2 = (uint8_t)(nm[6] - 65), ro2 = (uint8_t)(nm[7] - 48);
-            if (fr2 == frame) { rot_bitmap[ro2] = b.picture_bitmap(nm, true); have[ro2] = true; }
-        }
-    }
-    int nkeys = 0;
-    for (bool h : have) nkeys += h;
-    if (nkeys == 0) throw LoadError("Unknown frame " + std::to_string(frame) + " for " + sprite + " (sprites.rs:104)");
+    for (const SpriteScan::Hit &h : scan.hits) rot_bitmap[h.rot] = b.picture_bitmap(b.wad.dir[(size_t)h.lump].name, h.mirror);
     SpriteFrameRec f{};
-    f.rotate = nkeys != 1;
-    if (f.rotate) {
-        if (nkeys != 8) throw LoadError("Got something other than 8 rotations for " + sprite);
-        for (int r = 1; r < 9; r++) {
-            if (!have[r]) throw LoadError("sprite " + sprite + " misses a rotation");
-            f.bitmap[r - 1] = rot_bitmap[r];
-        }
-    } else {
-        if (!have[0]) throw LoadError("sprite " + sprite + ": single rotation is not 0");
-        for (int r = 0; r < 8; r++) f.bitmap[r] = rot_bitmap[0];
-    }
+    f.rotate = scan.rotate;
+    for (int r = 0; r < 8; r++) f.bitmap[r] = rot_bitmap[f.rotate ? r + 1 : 0];
     sc.sprite_frames.push_back(f);
     sc.sprite_frame_keys.push_back(key);
     return (int)sc.sprite_frames.size() - 1;
 }
 
+void Scene::commit_new_frames(size_t frames_before) {
+    if (sprite_frames.size() == frames_before) return;
+    revision++;
+    rebuild_fs_tables();
+}
+
 int Scene::find_or_add_sprite_frame(const std::string &sprite, uint8_t frame, std::string &err) {
     try {
-        Builder b(*this);
-        // rebuild the caches the builder needs from what is already in the scene
-        for (size_t i = 0; i < bitmap_names.size(); i++) b.bitmap_by_key[bitmap_names[i]] = (int)i;
-        int a = b.wad.find("S_START"), e = b.wad.find("S_END");
-        b.first_sprite = a; b.last_sprite = e;
-        int id = add_sprite_frame(b, sprite, frame);
-        revision++;
-        rebuild_fs_tables();
+        Builder b = Builder::resume(*this);
+        const int id = add_sprite_frame(b, sprite, frame);
+        commit_new_frames(0);                                                 // whether or not the frame is new, as ever (an id: there is a frame)
         return id;
     } catch (const std::exception &ex) {
         err = ex.what();
@@ -421,8 +450,7 @@ int Scene::set_wall_effects(uint32_t flags, std::string &err) {
         std::vector<int32_t> list_of_bitmap;                                  // bitmap id -> live list (-1: none)
         if (flags & DG_WALL_ANIMATE) {
             try {
-                Builder b(*this);
-                for (size_t i = 0; i < bitmap_names.size(); i++) b.bitmap_by_key[bitmap_names[i]] = (int)i;
+                Builder b = Builder::resume(*this);
                 b.load_texture_defs();
                 for (const auto &l : kWallAnim) {
                     FsAnim a{};
@@ -461,7 +489,7 @@ int Scene::set_wall_effects(uint32_t flags, std::string &err) {
             f.anim_mid = list_of(r.middle); f.anim_low = list_of(r.lower); f.anim_up = list_of(r.upper);
         }
     }
-    wall_fx = std::move(fx);
+    this->fx.wall = std::move(fx);
     rebuild_fs_tables();
     return DG_OK;
 }
@@ -526,31 +554,8 @@ int Scene::set_light_effects(uint32_t flags, uint64_t seed, std::string &err) {
             fx.recs.push_back(r);
         }
     }
-    light_fx = std::move(fx);
+    this->fx.light = std::move(fx);
     return DG_OK;
-}
-
-// Whether add_sprite_frame would resolve (sprite, frame) as far as the lump names tell (Sprites::new's rules), decoding nothing.
-static bool sprite_frame_resolves(const Builder &b, const std::string &sprite, uint8_t frame) {
-    const std::string key = sprite + (char)('A' + frame);
-    for (const std::string &k : b.sc.sprite_frame_keys)
-        if (k == key) return true;
-    if (sprite.size() != 4) return false;
-    bool have[256] = {false};
-    for (int idx = b.first_sprite; idx < b.last_sprite; idx++) {
-        const std::string &nm = b.wad.dir[(size_t)idx].name;
-        if (nm.compare(0, 4, sprite) != 0) continue;
-        if (nm.size() < 6 || nm.size() == 7) return false;
-        if ((uint8_t)(nm[4] - 65) == frame) have[(uint8_t)(nm[5] - 48)] = true;
-        if (nm.size() > 6 && (uint8_t)(nm[6] - 65) == frame) have[(uint8_t)(nm[7] - 48)] = true;
-    }
-    int nkeys = 0;
-    for (bool h : have) nkeys += h;
-    if (nkeys == 1) return have[0];
-    if (nkeys != 8) return false;
-    for (int r = 1; r < 9; r++)
-        if (!have[r]) return false;
-    return true;
 }
 
 // dg_scene_set_mobj_thinkers: init_map_obj_thinkers (thinkers.rs:82-86) over the caller's tables.  Per start state in use — the spawn
@@ -560,7 +565,7 @@ int Scene::set_mobj_thinkers(uint32_t flags, const dg_state_rec *states, int n_s
     if (flags & ~(uint32_t)DG_MOBJ_THINKERS) { err = "unknown map-object thinker bits"; return DG_ERR_INVALID; }
     MobjFx fx;
     fx.flags = flags;
-    if (!flags) { mobj_fx = std::move(fx); return DG_OK; }
+    if (!flags) { this->fx.mobj = std::move(fx); return DG_OK; }
     if (!states || n_states < 1 || n_states > MFX_MAX_STATES) { err = "state table: NULL or n_states outside [1, 65536]"; return DG_ERR_INVALID; }
     if (n_infos < 0 || (n_infos > 0 && !infos)) { err = "info table: NULL or n_infos negative"; return DG_ERR_INVALID; }
     for (int i = 0; i < n_states; i++) {
@@ -573,9 +578,7 @@ int Scene::set_mobj_thinkers(uint32_t flags, const dg_state_rec *states, int n_s
 
     const size_t frames_before = sprite_frames.size();
     try {
-        Builder b(*this);
-        for (size_t i = 0; i < bitmap_names.size(); i++) b.bitmap_by_key[bitmap_names[i]] = (int)i;
-        b.first_sprite = b.wad.find("S_START"); b.last_sprite = b.wad.find("S_END");
+        Builder b = Builder::resume(*this);
         std::vector<int8_t> resolves((size_t)n_states, -1);                  // per state: -1 not asked yet, 0 / 1
         std::vector<int32_t> chain_of((size_t)n_states, -2), pos((size_t)n_states, -1);   // per start state: -2 not built yet, -1 not live, else its chain
         std::vector<int32_t> walk;
@@ -606,7 +609,7 @@ int Scene::set_mobj_thinkers(uint32_t flags, const dg_state_rec *states, int n_s
                     const dg_state_rec &r = states[walk[k]];
                     if (k == (size_t)cycle_at) { c.prefix_total = sum; sum = 0; }
                     sum += r.tics < 1 ? 1u : (uint32_t)r.tics;
-                    const int32_t val = walk[k] == 0 ? -1 : add_sprite_frame(b, sprite_of(walk[k]), r.frame) * 2 + (r.full_bright ? 1 : 0);
+                    const int32_t val = mfx_encode(walk[k] == 0 ? -1 : add_sprite_frame(b, sprite_of(walk[k]), r.frame), r.full_bright);
                     fx.steps.push_back(MfxStep{sum, val});
                 }
                 c.period = sum;
@@ -638,15 +641,16 @@ int Scene::set_mobj_thinkers(uint32_t flags, const dg_state_rec *states, int n_s
         }
     } catch (const std::exception &ex) {
         err = ex.what();
-        if (sprite_frames.size() != frames_before) { revision++; rebuild_fs_tables(); }     // (frames decoded before the failure stay: ids never move)
+        commit_new_frames(frames_before);                                    // (frames decoded before the failure stay: ids never move)
         return DG_ERR_WAD;
     }
-    if (sprite_frames.size() != frames_before) { revision++; rebuild_fs_tables(); }
-    mobj_fx = std::move(fx);
+    commit_new_frames(frames_before);
+    this->fx.mobj = std::move(fx);
     return DG_OK;
 }
 
 int Scene::mobj_event(int what, float timestamp, std::string &err) {
+    MobjFx &mobj_fx = fx.mobj;
     if (what == 0) { mobj_fx.events.clear(); return DG_OK; }
     if (!mobj_fx.flags) { err = "no map-object thinkers set"; return DG_ERR_INVALID; }
     if (what != DG_MOBJ_KILL && what != DG_MOBJ_EXPLODE && what != DG_MOBJ_RESPAWN) { err = "unknown map-object event"; return DG_ERR_INVALID; }
@@ -659,6 +663,7 @@ int Scene::mobj_event(int what, float timestamp, std::string &err) {
 
 int Scene::wall_texture_id(const std::string &name, float timestamp) const {
     const int id = texture_id(name);
+    const WallFx &wall_fx = fx.wall;
     if (id < 0 || !(wall_fx.flags & DG_WALL_ANIMATE)) return id;
     for (const FsAnim &a : wall_fx.lists)
         for (int k = 0; k < a.n; k++)

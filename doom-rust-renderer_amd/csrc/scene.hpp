@@ -57,6 +57,7 @@ struct MapObjectRec {                                            // map_objects.
     int32_t sector;         // get_sector_from_vertex(position) — position is immutable in the reference
 };
 struct AnimList { int32_t n; int32_t flat[4]; };
+struct Scene;
 
 // The wall effects of a scene (dg_scene_set_wall_effects) as fs_core.h applies them: flags, and per seg its scroll count and
 // animation lists (fs_seg_fx), the lists over bitmap ids.  flags 0: both tables empty, nothing changes.  A dg_ctx keeps the copy it uploaded.
@@ -76,6 +77,7 @@ struct LightFx {
     std::vector<uint32_t> tab;
     std::vector<int32_t> rec_of;
     bool on() const { return flags != 0 && !recs.empty(); }
+    bool fits(const Scene &sc) const;               // on(), and set on a scene with sc's sectors: rec_of indexes them
     int16_t level(size_t rec, float timestamp) const { return lfx_level(recs[rec], tab.data(), seed, fs_tics(timestamp)); }
 };
 
@@ -91,9 +93,18 @@ struct MobjFx {
     std::vector<uint32_t> driven;
     std::vector<MfxEvent> events;
     bool on() const { return flags != 0 && !driven.empty(); }
+    bool fits(const Scene &sc) const;               // on(), and set on a scene with sc's map objects: type_of indexes them
     int32_t value(size_t mobj, float timestamp) const {
         return mfx_value(types[(size_t)type_of[mobj]], events.data(), (uint32_t)events.size(), chains.data(), steps.data(), fs_tics(timestamp));
     }
+};
+
+// The three opt-in effects of a scene as one bundle: Scene::fx is what the setters last left, a dg_ctx draws with the copy it took at
+// dg_upload_scene, and the host walker takes a pointer to either (frontend.hpp).
+struct SceneFx {
+    WallFx wall;
+    LightFx light;
+    MobjFx mobj;
 };
 
 enum : int32_t { TEX_NONE = -1, TEX_UNKNOWN = -2, FLAT_MISSING = -2 };
@@ -129,10 +140,10 @@ struct Scene {
     std::vector<std::string> sprite_frame_keys;     // "SPRT<frame>"
     int32_t sky_bitmap = TEX_UNKNOWN;
     uint64_t revision = 0;                          // bumped by the mutable-state setters
-    WallFx wall_fx;                                 // as last set by set_wall_effects (the host walker of dg_build_lists reads it)
     std::vector<int16_t> wad_light;                 // per sector its level as the WAD holds it (the light effects' max and surrounding min)
-    LightFx light_fx;                               // as last set by set_light_effects (dg_build_lists, dg_scene_sector_lights_at read it)
-    MobjFx mobj_fx;                                 // as last set by set_mobj_thinkers / mobj_event (dg_build_lists, dg_scene_mobj_states_at read it)
+    // as last set by set_wall_effects, set_light_effects and set_mobj_thinkers / mobj_event (dg_build_lists, dg_scene_sector_lights_at and
+    // dg_scene_mobj_states_at read it)
+    SceneFx fx;
     // The per-seg / per-sprite inputs of fs_core.h, flattened (rebuild_fs_tables: at load and whenever bitmaps or sprite frames are added):
     // what the host walker reads per seg and what dg_upload_scene copies to the GPU for DG_FE_DEVICE_SEGS.
     std::vector<FsSeg> fs_segs;                     // one per seg
@@ -149,6 +160,7 @@ struct Scene {
     bool fs_ok = false;
     const FsSpriteFrame *sprite_frames_fs() const { return reinterpret_cast<const FsSpriteFrame *>(sprite_frames.data()); }
     void rebuild_fs_tables();
+    void commit_new_frames(size_t frames_before);   // sprite frames were added since: a new revision, and rebuild_fs_tables
 
     // lookups used by the C-ABI
     int texture_id(const std::string &name) const;                               // Textures::get
@@ -163,6 +175,9 @@ struct Scene {
                           std::string &err);                                   // DG_OK, or DG_ERR_INVALID / DG_ERR_WAD with err
     int mobj_event(int what, float timestamp, std::string &err);               // DG_OK, or DG_ERR_INVALID with err
 };
+
+inline bool LightFx::fits(const Scene &sc) const { return on() && rec_of.size() == sc.sectors.size(); }
+inline bool MobjFx::fits(const Scene &sc) const { return on() && type_of.size() == sc.mobjs.size(); }
 
 // The lines of one 2-D map frame (Game::render with viewing_map, src/game.rs:229-308) in draw order: every linedef without DONTDRAW, then
 // (view != nullptr) the player arrow's three lines P->E, R->E, L->E.  DG_ERR_INVALID for a frame under 40 x 40 or over 16384 x 16384,
