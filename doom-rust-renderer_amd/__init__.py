@@ -27,6 +27,7 @@ DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
 DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
 DG_MOBJ_KILL, DG_MOBJ_EXPLODE, DG_MOBJ_RESPAWN = 1, 2, 3   # dg_scene_mobj_event
+DG_KEY_LEFT, DG_KEY_RIGHT, DG_KEY_UP, DG_KEY_DOWN, DG_KEY_ALT, DG_KEY_SHIFT = 1, 2, 4, 8, 16, 32   # dg_walk_desc.keys
 
 
 class DoomGpuError(RuntimeError):
@@ -60,6 +61,11 @@ class DgMobjInfoRec(ctypes.Structure):
 class DgViewState(ctypes.Structure):
     _fields_ = [("lights", ctypes.POINTER(DgSectorLight)), ("n_lights", ctypes.c_uint32),
                 ("mobjs", ctypes.POINTER(DgMobjState)), ("n_mobjs", ctypes.c_uint32)]
+
+
+class DgWalkDesc(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_float), ("y", ctypes.c_float), ("angle", ctypes.c_float), ("from_player_start", ctypes.c_int32),
+                ("turbo", ctypes.c_int32), ("keys", ctypes.POINTER(ctypes.c_uint8)), ("n_tics", ctypes.c_uint32)]
 
 
 class DgConfig(ctypes.Structure):
@@ -167,6 +173,13 @@ _SIGNATURES = {
     "dg_map_lines": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgMapLine), ctypes.c_int]),
     "dg_submit_map_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int]),
     "dg_render_map_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, _P]),
+    "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
+    "dg_walk_free": (None, [_P]),
+    "dg_walk_tics": (ctypes.c_int, [_P]),
+    "dg_walk_probe_count": (ctypes.c_int, [_P]),
+    "dg_walk_floors": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float), ctypes.c_int]),
+    "dg_walk_views": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.POINTER(DgView)]),
+    "dg_ctx_locate_walks": (ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.c_int]),
     "dg_last_error": (ctypes.c_char_p, []),
     "dg_version": (ctypes.c_char_p, []),
     "dg_slot_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgTiming)]),
@@ -314,6 +327,45 @@ class Scene:
             self._h = None
 
 
+class Walk:
+    """dg_walk: a play-through moved as the reference moves its player (Game::process_down_keys, src/game.rs:314-389): a start pose
+    (x, y, angle; None: Player1Start), --turbo in percent and one DG_KEY_* mask per 35 Hz tic.  floors() / views() find the floor
+    heights on the host unless Context.locate_walks has found them on the GPU.  The scene must outlive the walk."""
+
+    def __init__(self, scene: Scene, keys, start=None, turbo: int = 100):
+        k = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1)
+        x, y, a = (0.0, 0.0, 0.0) if start is None else start
+        d = DgWalkDesc(x, y, a, int(start is None), int(turbo), k.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if k.size else None, k.size)
+        h = _P()
+        _check(lib().dg_walk_create(scene._h, ctypes.byref(d), ctypes.byref(h)))
+        self._h = h
+        self._scene = scene  # keep alive
+
+    def tics(self) -> int:
+        return _check(lib().dg_walk_tics(self._h))
+
+    def probe_count(self) -> int:
+        return _check(lib().dg_walk_probe_count(self._h))
+
+    def floors(self) -> np.ndarray:
+        """dg_walk_floors: floor_height after 0 .. tics() tics (float32 array)."""
+        out = np.zeros(self.tics() + 1, dtype=np.float32)
+        _check(lib().dg_walk_floors(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.size))
+        return out
+
+    def views(self, timestamps):
+        """dg_walk_views: a ctypes array of dg_view, one per timestamp, for every submit / render / map call."""
+        ts = np.ascontiguousarray(timestamps, dtype=np.float32).reshape(-1)
+        arr = (DgView * max(1, ts.size))()
+        _check(lib().dg_walk_views(self._h, ts.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ts.size, arr))
+        return arr if ts.size else (DgView * 0)()
+
+    def close(self):
+        if self._h:
+            lib().dg_walk_free(self._h)
+            self._h = None
+
+
 class Context:
     """dg_ctx on one GPU.  Mirrors the reference call shape: for every view, `Pixels::new()` +
     `Renderer::new(..).render()` -> `pixels.pixels` (src/game.rs:505-525), batched."""
@@ -412,6 +464,11 @@ class Context:
         out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
         _check(lib().dg_draw_lists(self._h, slot, frames, n, out.ctypes.data_as(_P)))
         return out
+
+    def locate_walks(self, walks):
+        """dg_ctx_locate_walks: the floor heights of all these walks in one pass on the GPU (synchronous; located walks are skipped)."""
+        arr = (_P * max(1, len(walks)))(*[w._h for w in walks])
+        _check(lib().dg_ctx_locate_walks(self._h, arr, len(walks)))
 
     def timing(self, slot: int) -> dict:
         t = DgTiming()

@@ -41,6 +41,8 @@
 #include "map_kernels.hpp"
 #include "scene.hpp"
 #include "slab_layout.h"
+#include "walk.hpp"
+#include "walk_kernels.hpp"
 
 using namespace dg;
 
@@ -306,6 +308,12 @@ struct dg_ctx {
     // 2-D map view: every drawn linedef of the uploaded scene, RGB24, built by the first map submission after dg_upload_scene
     DevPtr<uint8_t> d_map_layer;
     bool map_layer_ok = false;
+    // dg_ctx_locate_walks: the uploaded scene's node and leaf tables (walk_core.h), uploaded by the first call after dg_upload_scene, and
+    // a stream of its own, created by the first call of all — the slots' streams and the kernel stream are not touched
+    DevPtr<uint8_t> d_walk_tables;
+    const WalkNode *d_walk_nodes = nullptr;
+    const WalkLeaf *d_walk_leaves = nullptr;
+    hipStream_t wstream = nullptr;
 };
 
 namespace {
@@ -347,6 +355,7 @@ void free_ctx(dg_ctx *c) {
     }
     if (c->kstream) (void)hipStreamDestroy(c->kstream);
     if (c->rstream) (void)hipStreamDestroy(c->rstream);
+    if (c->wstream) { (void)hipStreamSynchronize(c->wstream); (void)hipStreamDestroy(c->wstream); }
     delete c;
 }
 
@@ -1307,6 +1316,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     c->d_flats = nullptr;               // inside d_texel_idx's allocation
     // the slots' prepared records point into the device scene that was just freed: nothing may be replayed from them
     for (Slot &s : c->slots) { s.n_frames = 0; s.timed = false; s.fe_check = false; s.busy = false; s.snap_scene = nullptr; }
+    c->d_walk_tables.reset();           // dg_ctx_locate_walks is synchronous: nothing of it is in flight
     c->map_layer_ok = false;            // the map view's linedef layer belongs to the old scene   // (a new scene may reuse the old one's address and revision)
     uint32_t pal[256];
     for (int i = 0; i < 256; i++) pal[i] = (uint32_t)sc.palette[3 * i] | ((uint32_t)sc.palette[3 * i + 1] << 8) | ((uint32_t)sc.palette[3 * i + 2] << 16);
@@ -1584,6 +1594,103 @@ int dg_render_map_views(dg_ctx *c, const dg_view *views, int n, uint8_t *out) {
     if (rc) return rc;
     if (out) return dg_readback(c, 0, 0, n, out);
     return dg_wait(c, 0);
+}
+
+int dg_walk_create(const dg_scene *s, const dg_walk_desc *d, dg_walk **out) {
+    if (!s || !d || !out) return set_err(DG_ERR_INVALID, "null argument");
+    std::string err;
+    const int rc = walk_create(*s->sc, *d, out, err);
+    return rc ? set_err(rc, err) : DG_OK;
+}
+void dg_walk_free(dg_walk *w) { delete w; }
+int dg_walk_tics(const dg_walk *w) { return w ? (int)w->tics() : set_err(DG_ERR_INVALID, "null argument"); }
+int dg_walk_probe_count(const dg_walk *w) { return w ? (int)w->px.size() : set_err(DG_ERR_INVALID, "null argument"); }
+int dg_walk_floors(dg_walk *w, float *out, int n) {
+    if (!w || !out) return set_err(DG_ERR_INVALID, "null argument");
+    if (n < 0 || (size_t)n != w->pose.size()) return set_err(DG_ERR_INVALID, "n must be tics + 1");
+    w->locate_host();
+    std::memcpy(out, w->floors.data(), (size_t)n * sizeof(float));
+    return DG_OK;
+}
+int dg_walk_views(dg_walk *w, const float *timestamps, int n, dg_view *out) {
+    if (!w || n < 0 || (n > 0 && (!timestamps || !out))) return set_err(DG_ERR_INVALID, "null argument");
+    w->locate_host();
+    for (int i = 0; i < n; i++) w->view_at(timestamps[i], out[i]);
+    return DG_OK;
+}
+
+int dg_ctx_locate_walks(dg_ctx *c, dg_walk *const *walks, int n_walks) {
+    if (!c || n_walks < 0 || (n_walks > 0 && !walks)) return set_err(DG_ERR_INVALID, "null argument");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded");
+    for (int i = 0; i < n_walks; i++) {
+        if (!walks[i]) return set_err(DG_ERR_INVALID, "null walk");
+        if (walks[i]->sc != c->scene) return set_err(DG_ERR_INVALID, "a walk was created on another scene than the one uploaded");
+    }
+    // the walks still to locate, each once, and what they add up to
+    std::vector<dg_walk *> todo;
+    uint64_t probes = 0, entries = 0;
+    for (int i = 0; i < n_walks; i++) {
+        dg_walk *w = walks[i];
+        if (w->located || w->queued) continue;
+        w->queued = true;
+        todo.push_back(w);
+        probes += w->px.size();
+        entries += w->pose.size();
+    }
+    for (dg_walk *w : todo) w->queued = false;
+    if (todo.empty()) return DG_OK;
+    if (probes > WALK_MAX_PROBES) return set_err(DG_ERR_CAPACITY, "more than 1 << 26 probes in one call");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    const Scene &sc = *c->scene;
+    if (!c->wstream) HIP_TRY(hipStreamCreateWithFlags(&c->wstream, hipStreamNonBlocking));
+    if (!c->d_walk_tables) {
+        TablePack t;
+        const size_t nodes = t.add(sc.walk_nodes), leaves = t.add(sc.walk_leaves);
+        const hipError_t e = t.upload(c->d_walk_tables);
+        if (e != hipSuccess) { c->d_walk_tables.reset(); return set_err(DG_ERR_HIP, std::string("walk tables: ") + hipGetErrorString(e)); }
+        c->d_walk_nodes = t.at<WalkNode>(nodes);
+        c->d_walk_leaves = t.at<WalkLeaf>(leaves);
+    }
+    // one slab: the probes of all walks, concatenated, go up in one copy; the floors come back in one
+    const WalkLayout L = walk_layout((size_t)probes, (size_t)entries);
+    std::vector<uint8_t> staged(L.upload);
+    float *hx = reinterpret_cast<float *>(staged.data() + L.x), *hy = reinterpret_cast<float *>(staged.data() + L.y);
+    uint8_t *hfirst = staged.data() + L.first;
+    uint32_t *heot = reinterpret_cast<uint32_t *>(staged.data() + L.end_of_tic);
+    size_t pi = 0, ei = 0;
+    for (const dg_walk *w : todo) {
+        const size_t np = w->px.size(), ne = w->pose.size();
+        std::memcpy(hx + pi, w->px.data(), np * 4);
+        std::memcpy(hy + pi, w->py.data(), np * 4);
+        hfirst[pi] = 1;
+        for (size_t t = 0; t < ne; t++) heot[ei + t] = (uint32_t)pi + w->end_of_tic[t];
+        pi += np; ei += ne;
+    }
+    DevPtr<uint8_t> d_slab;
+    HIP_TRY(hip_alloc(d_slab, L.total));
+    uint8_t *const d = d_slab.get();
+    WalkParams P{};
+    P.nodes = c->d_walk_nodes; P.leaves = c->d_walk_leaves;
+    P.x = reinterpret_cast<const float *>(d + L.x); P.y = reinterpret_cast<const float *>(d + L.y);
+    P.first = d + L.first; P.end_of_tic = reinterpret_cast<const uint32_t *>(d + L.end_of_tic);
+    P.value = reinterpret_cast<float *>(d + L.value); P.last = reinterpret_cast<uint32_t *>(d + L.last);
+    P.sums = reinterpret_cast<uint32_t *>(d + L.sums); P.floors = reinterpret_cast<float *>(d + L.floors);
+    P.root = (int32_t)sc.walk_nodes.size() - 1;
+    P.n_probes = (uint32_t)probes; P.n_blocks = (uint32_t)walk_scan_blocks((size_t)probes); P.n_entries = entries;
+    std::vector<float> floors((size_t)entries);
+    hipError_t e = hipMemcpyAsync(d, staged.data(), L.upload, hipMemcpyHostToDevice, c->wstream);
+    if (e == hipSuccess) e = launch_walk_locate(P, c->wstream);
+    if (e == hipSuccess) e = hipMemcpyAsync(floors.data(), d + L.floors, (size_t)entries * 4, hipMemcpyDeviceToHost, c->wstream);
+    const hipError_t es = hipStreamSynchronize(c->wstream);     // before d_slab and the staging go, whatever was queued has run
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_ctx_locate_walks: ") + hipGetErrorString(e));
+    ei = 0;
+    for (dg_walk *w : todo) {
+        w->floors.assign(floors.begin() + (ptrdiff_t)ei, floors.begin() + (ptrdiff_t)(ei + w->pose.size()));
+        w->located = true;
+        ei += w->pose.size();
+    }
+    return DG_OK;
 }
 
 int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {

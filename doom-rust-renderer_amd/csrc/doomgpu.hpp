@@ -133,6 +133,44 @@ private:
     dg_ctx *h_ = nullptr;
 };
 
+// A recorded play-through moved as Game::process_down_keys + update_current_player_height move the player (src/game.rs:314-389;
+// DESIGN.md section 8e): keys[t] is the DG_KEY_* mask held during tic t + 1.  locate() finds the floor heights of many walks in one
+// pass on the GPU; without it floors() / players() find them on the host.  The World must outlive the Walk.
+class Walk {
+public:
+    Walk(const World &world, const std::vector<uint8_t> &keys, int turbo = 100) {                       // from Player1Start
+        dg_walk_desc d{0, 0, 0, 1, turbo, keys.data(), (uint32_t)keys.size()};
+        check(dg_walk_create(world.handle(), &d, &h_));
+    }
+    Walk(const World &world, const Vertex &position, float angle, const std::vector<uint8_t> &keys, int turbo = 100) {   // OverridePlayer
+        dg_walk_desc d{position.x, position.y, angle, 0, turbo, keys.data(), (uint32_t)keys.size()};
+        check(dg_walk_create(world.handle(), &d, &h_));
+    }
+    ~Walk() { dg_walk_free(h_); }
+    Walk(const Walk &) = delete;
+    Walk &operator=(const Walk &) = delete;
+    int tics() const { return dg_walk_tics(h_); }
+    int probe_count() const { return dg_walk_probe_count(h_); }
+    std::vector<float> floors() {
+        std::vector<float> out((size_t)tics() + 1);
+        check(dg_walk_floors(h_, out.data(), (int)out.size()));
+        return out;
+    }
+    // The views at these timestamps, ready for dg_render_views / dg_submit_views / dg_render_map_views.
+    std::vector<dg_view> views(const std::vector<float> &timestamps) {
+        std::vector<dg_view> out(timestamps.size());
+        check(dg_walk_views(h_, timestamps.data(), (int)timestamps.size(), out.data()));
+        return out;
+    }
+    static void locate(Device &dev, const std::vector<Walk *> &walks) {
+        std::vector<dg_walk *> hs;
+        for (Walk *w : walks) hs.push_back(w->h_);
+        check(dg_ctx_locate_walks(dev.handle(), hs.data(), (int)hs.size()));
+    }
+private:
+    dg_walk *h_ = nullptr;
+};
+
 // src/renderer/mod.rs:27-58,118-136: construct per frame, call render(), read pixels.pixels.
 class Renderer {
 public:

@@ -332,6 +332,29 @@ int Scene::sector_from_vertex(float x, float y) const {
     }
 }
 
+// The flat tables of walk_core.h from the scene's records, by the rule of Scene::sector_from_vertex: the first seg of a leaf that has
+// a sidedef on its side decides.
+void Scene::build_walk_tables() {
+    walk_nodes.resize(nodes.size());
+    for (size_t i = 0; i < nodes.size(); i++) {
+        const NodeRec &n = nodes[i];
+        auto child = [](int16_t c) { return (c & (int16_t)0x8000) ? ~(int32_t)(c & 0x7fff) : (int32_t)(c & 0x7fff); };
+        walk_nodes[i] = WalkNode{n.x, n.y, n.dx, n.dy, {child(n.rchild), child(n.lchild)}};
+    }
+    walk_leaves.assign(subsectors.size(), WalkLeaf{0.0f, 1u});
+    for (size_t l = 0; l < subsectors.size(); l++) {
+        const SubSectorRec &ss = subsectors[l];
+        for (int k = 0; k < ss.count; k++) {
+            const SegRec &sg = segs[(size_t)(ss.first + k)];
+            const LinedefRec &ld = linedefs[(size_t)sg.linedef];
+            const int sd = sg.direction ? ld.back : ld.front;
+            if (sd < 0) continue;
+            walk_leaves[l] = WalkLeaf{(float)sectors[(size_t)sidedefs[(size_t)sd].sector].floor_h, 0u};
+            break;
+        }
+    }
+}
+
 int Scene::texture_id(const std::string &name) const {
     std::string key = "T:" + upper(name);
     for (size_t i = 0; i < bitmap_names.size(); i++)
@@ -966,6 +989,7 @@ Scene *load_scene_from_wad(const uint8_t *bytes, size_t len, const char *map_nam
                 sc->map_top = std::min(sc->map_top, y); sc->map_bottom = std::max(sc->map_bottom, y);
             }
         sc->rebuild_fs_tables();
+        sc->build_walk_tables();
         return sc;
     } catch (const std::exception &ex) {
         err = ex.what();

@@ -14,6 +14,7 @@
 #include "fs_frame.h"
 #include "light_fx.h"
 #include "mobj_fx.h"
+#include "walk_core.h"
 
 namespace dg {
 
@@ -158,6 +159,11 @@ struct Scene {
     std::vector<FsAnc> fs_anc;
     std::vector<uint32_t> fs_anc_off, fs_leaf_first;
     bool fs_ok = false;
+    // The BSP as walk_core.h descends it (dg_walk_*): per node its partition and children, per leaf its floor height or
+    // none, by the rule of sector_from_vertex.  Built once at load; dg_ctx_locate_walks uploads them.
+    std::vector<WalkNode> walk_nodes;
+    std::vector<WalkLeaf> walk_leaves;
+    void build_walk_tables();
     const FsSpriteFrame *sprite_frames_fs() const { return reinterpret_cast<const FsSpriteFrame *>(sprite_frames.data()); }
     void rebuild_fs_tables();
     void commit_new_frames(size_t frames_before);   // sprite frames were added since: a new revision, and rebuild_fs_tables

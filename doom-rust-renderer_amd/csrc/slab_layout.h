@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "fs_frame.h"
+#include "walk_core.h"
 
 namespace dg {
 
@@ -123,6 +124,27 @@ inline FsScratchLayout fs_scratch_layout(size_t max_batch, uint32_t n_segs) {
     L.lite = c.take(max_batch * (size_t)n_segs * FS_CALLS * sizeof(uint2));
     L.cl_rows = c.take(max_batch * (size_t)L.cl_row_cap * 4);
     L.keep_rows = c.take(max_batch * (size_t)(L.cl_row_cap / 32) * 4);
+    L.total = c.end();
+    return L;
+}
+
+// Transient buffers of one dg_ctx_locate_walks call (walk_kernels.hip): [0, upload) is one H2D copy of the probes of all its walks,
+// the rest is written by the kernels; [floors, floors + entries * 4) is the one D2H copy.  entries: one per (walk, tic), the walks' tic 0 included.
+// blocks: scan workgroups, walk_scan_blocks(probes).
+inline size_t walk_scan_blocks(size_t probes) { return (probes + WALK_SCAN_BLOCK - 1) / WALK_SCAN_BLOCK; }
+struct WalkLayout { size_t x, y, first, end_of_tic, upload, value, last, sums, floors, total; };
+inline WalkLayout walk_layout(size_t probes, size_t entries) {
+    SlabCursor c;
+    WalkLayout L;
+    L.x = c.take(probes * 4);
+    L.y = c.take(probes * 4);
+    L.first = c.take(probes);
+    L.end_of_tic = c.take(entries * 4);
+    L.upload = c.end();
+    L.value = c.take(probes * 4);
+    L.last = c.take(probes * 4);
+    L.sums = c.take(walk_scan_blocks(probes) * 4);
+    L.floors = c.take(entries * 4);
     L.total = c.end();
     return L;
 }

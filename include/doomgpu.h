@@ -319,6 +319,45 @@ int dg_submit_map_views(dg_ctx *ctx, int slot, const dg_view *views, int n);
 /* Synchronous, slot 0: if rgb24_out != NULL copy n*3*W*H bytes to host memory. */
 int dg_render_map_views(dg_ctx *ctx, const dg_view *views, int n, uint8_t *rgb24_out);
 
+/* ---- player movement from recorded keys (reference: Game::process_down_keys + update_current_player_height, src/game.rs:314-389) -- */
+/* A walk is a play-through as the reference would move it: a start pose, --turbo, and one key mask per 35 Hz tic.  The state after t tics
+ * (t = 0: Game::new) is process_down_keys applied t times, literally in f32 (DESIGN.md section 8e states the order and the operands); the
+ * turns and moves take the host's cosf / sinf, so the libm caveat of trig_valid = 0 applies.  Bits 6 and 7 of a mask are ignored.
+ * floor_height starts at 0.0 and follows get_sector_from_vertex after every move: a position in a sector replaces it (a mid-tic one too),
+ * a position in no sector leaves it.  Opt-in: nothing changes for callers who fill dg_view themselves. */
+#define DG_KEY_LEFT 1u
+#define DG_KEY_RIGHT 2u
+#define DG_KEY_UP 4u
+#define DG_KEY_DOWN 8u
+#define DG_KEY_ALT 16u      /* either Alt */
+#define DG_KEY_SHIFT 32u    /* either Shift */
+typedef struct dg_walk dg_walk;
+typedef struct dg_walk_desc {
+    float x, y, angle;          /* OverridePlayer; ignored when from_player_start != 0 (Player1Start) */
+    int32_t from_player_start;
+    int32_t turbo;              /* percent, the reference's i16 --turbo (default 100); outside i16: DG_ERR_INVALID */
+    const uint8_t *keys;        /* keys[t] = keys held during tick t + 1; copied */
+    uint32_t n_tics;            /* 0 .. 1 << 22 */
+} dg_walk_desc;
+/* The poses of all tics are worked out here (host, serial).  The scene must outlive the walk.  DG_ERR_INVALID: a NULL argument, keys == NULL
+ * with n_tics > 0, n_tics above 1 << 22, turbo outside i16, from_player_start on a map without a Player1Start.  A walk is not thread-safe. */
+int  dg_walk_create(const dg_scene *s, const dg_walk_desc *d, dg_walk **out);
+void dg_walk_free(dg_walk *w);
+int  dg_walk_tics(const dg_walk *w);
+/* Floor lookups the walk needs: the start position, then one per move that ran (at most four per tic). */
+int  dg_walk_probe_count(const dg_walk *w);
+/* out[t] = floor_height after t tics; n must be tics + 1.  Locates on the host (one BSP descent per probe) if the walk is not located yet. */
+int  dg_walk_floors(dg_walk *w, float *out, int n);
+/* out[i] = the view at timestamps[i]: the pose and floor after t = min((timestamp * 35.0f) as u32, tics) tics (NaN and <= 0: 0), the four
+ * trig fields as with trig_valid = 0, timestamp = timestamps[i], trig_valid = 1 — an ordinary dg_view array for every submit / render / map
+ * call.  Timestamps may come in any order.  Host only; locates on the host if the walk is not located yet. */
+int  dg_walk_views(dg_walk *w, const float *timestamps, int n, dg_view *out);
+/* The floors of all these walks in one pass on the GPU (one lane per probe, then a device-wide scan); synchronous, and the slots in flight
+ * are left alone.  Walks that are located already are skipped; afterwards dg_walk_floors / dg_walk_views on these walks do no BSP descent.
+ * DG_ERR_INVALID: a NULL argument, no scene uploaded, a walk created on another scene than the one uploaded.  DG_ERR_CAPACITY: more
+ * than 1 << 26 probes in one call.  The first call after dg_upload_scene uploads the scene's node and leaf tables. */
+int  dg_ctx_locate_walks(dg_ctx *ctx, dg_walk *const *walks, int n_walks);
+
 /* ---- misc ----------------------------------------------------------------------------------------------------- */
 const char *dg_last_error(void); /* thread-local message of the last failing call */
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its

@@ -199,3 +199,57 @@ extern "C" {
     pub fn dg_wait(ctx: *mut dg_ctx, slot: c_int) -> c_int;
     pub fn dg_readback_async(ctx: *mut dg_ctx, slot: c_int, first: c_int, count: c_int, rgb24_out: *mut u8) -> c_int;
 }
+
+// ---- player movement from recorded keys (include/doomgpu.h dg_walk_*) ----------------------------------------
+// A replayed play-through: what Game::process_down_keys and update_current_player_height (src/game.rs:314-389) do to the player, tic
+// by tic, from one key mask per tic.  dg_ctx_locate_walks finds the floor heights of many walks in one pass on the GPU.
+pub const DG_KEY_LEFT: u8 = 1;
+pub const DG_KEY_RIGHT: u8 = 2;
+pub const DG_KEY_UP: u8 = 4;
+pub const DG_KEY_DOWN: u8 = 8;
+pub const DG_KEY_ALT: u8 = 16;              // either Alt
+pub const DG_KEY_SHIFT: u8 = 32;            // either Shift
+#[repr(C)] pub struct dg_walk { _p: [u8; 0] }
+#[repr(C)]
+pub struct dg_walk_desc { pub x: f32, pub y: f32, pub angle: f32, pub from_player_start: i32, pub turbo: i32, pub keys: *const u8, pub n_tics: u32 }
+extern "C" {
+    pub fn dg_walk_create(s: *const dg_scene, d: *const dg_walk_desc, out: *mut *mut dg_walk) -> c_int;
+    pub fn dg_walk_free(w: *mut dg_walk);
+    pub fn dg_walk_tics(w: *const dg_walk) -> c_int;
+    pub fn dg_walk_probe_count(w: *const dg_walk) -> c_int;
+    pub fn dg_walk_floors(w: *mut dg_walk, out: *mut f32, n: c_int) -> c_int;
+    pub fn dg_walk_views(w: *mut dg_walk, timestamps: *const f32, n: c_int, out: *mut dg_view) -> c_int;
+    pub fn dg_ctx_locate_walks(ctx: *mut dg_ctx, walks: *const *mut dg_walk, n_walks: c_int) -> c_int;
+}
+
+/// The mask of `Game::pressed_keys` for one tic (src/game.rs:319-372).
+pub fn key_mask(pressed: &std::collections::HashSet<sdl2::keyboard::Keycode>) -> u8 {
+    use sdl2::keyboard::Keycode as K;
+    let has = |k: K| pressed.contains(&k);
+    (has(K::Left) as u8) * DG_KEY_LEFT | (has(K::Right) as u8) * DG_KEY_RIGHT | (has(K::Up) as u8) * DG_KEY_UP | (has(K::Down) as u8) * DG_KEY_DOWN
+        | ((has(K::LAlt) || has(K::RAlt)) as u8) * DG_KEY_ALT | ((has(K::LShift) || has(K::RShift)) as u8) * DG_KEY_SHIFT
+}
+
+/// A recorded play-through from Player1Start; `views` gives the dg_view of every timestamp asked for.
+pub struct Walk { h: *mut dg_walk }
+impl Walk {
+    pub fn from_player_start(scene: *const dg_scene, turbo: i16, keys: &[u8]) -> Walk {
+        let d = dg_walk_desc { x: 0.0, y: 0.0, angle: 0.0, from_player_start: 1, turbo: turbo as i32, keys: keys.as_ptr(), n_tics: keys.len() as u32 };
+        let mut h = std::ptr::null_mut();
+        let rc = unsafe { dg_walk_create(scene, &d, &mut h) };
+        if rc != 0 { panic!("dg_walk_create: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
+        Walk { h }
+    }
+    pub fn locate(ctx: *mut dg_ctx, walks: &[&Walk]) {
+        let hs: Vec<*mut dg_walk> = walks.iter().map(|w| w.h).collect();
+        let rc = unsafe { dg_ctx_locate_walks(ctx, hs.as_ptr(), hs.len() as c_int) };
+        if rc != 0 { panic!("dg_ctx_locate_walks: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
+    }
+    pub fn views(&mut self, timestamps: &[f32]) -> Vec<dg_view> {
+        let mut out = vec![dg_view::default(); timestamps.len()];
+        let rc = unsafe { dg_walk_views(self.h, timestamps.as_ptr(), timestamps.len() as c_int, out.as_mut_ptr()) };
+        if rc != 0 { panic!("dg_walk_views: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
+        out
+    }
+}
+impl Drop for Walk { fn drop(&mut self) { unsafe { dg_walk_free(self.h) } } }
