@@ -1,5 +1,7 @@
-// context.cpp — dg_ctx: one GPU's resident scene, per-slot list slabs / framebuffer slabs / streams, and the
-// host thread pool that builds the per-frame lists.  Implements the C-ABI declared in include/doomgpu.h.
+// context.cpp — dg_ctx: one GPU's resident scene, per-slot list slabs / framebuffer slabs / streams, the batch builders that run on
+// the host thread pool (pool.hpp), and a slot's way from one submission to the next (Slot::Phase, take_slot, make_final).  Implements
+// the entry points of the C-ABI (include/doomgpu.h) that take a dg_ctx; those that need no GPU are in api_scene.cpp, the memory owners
+// and TablePack in hip_mem.hpp.
 //
 // HBM layout (sized once at dg_create for 288 GB parts: nothing is reallocated on the submit path):
 //   scene   : palette 1 KB | texel index plane | texel opacity plane | flats (4 KB each)      immutable per map
@@ -18,27 +20,27 @@
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
 #include <chrono>
-#include <functional>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/doomgpu.h"
+#include "api_common.hpp"
 #include "binner.hpp"
 #include "fe_kernels.hpp"
 #include "fs_kernels.hpp"
 #include "light_fx_kernels.hpp"
 #include "mobj_fx_kernels.hpp"
 #include "frontend.hpp"
+#include "hip_mem.hpp"
 #include "kernels.hpp"
 #include "map_kernels.hpp"
+#include "pool.hpp"
 #include "scene.hpp"
 #include "slab_layout.h"
 #include "walk.hpp"
@@ -46,100 +48,21 @@
 
 using namespace dg;
 
-static thread_local std::string t_err;
-static int set_err(int code, const std::string &m) { t_err = m; return code; }
-
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) return set_err(DG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-struct dg_scene { Scene *sc; };
-
 namespace {
-
-// Minimal persistent pool: parallel_for over [0, n) with dynamic chunking.
-class Pool {
-public:
-    explicit Pool(int n) {
-        for (int i = 0; i < n; i++) workers_.emplace_back([this, i] { loop(i); });
-    }
-    ~Pool() {
-        { std::lock_guard<std::mutex> l(m_); stop_ = true; gen_++; }
-        cv_.notify_all();
-        for (auto &t : workers_) t.join();
-    }
-    int size() const { return (int)workers_.size(); }
-    // fn(index, worker_id); worker ids are 0..size() (the caller participates as id size()).
-    void parallel_for(int n, const std::function<void(int, int)> &fn) {
-        if (n <= 0) return;
-        { std::lock_guard<std::mutex> l(m_); fn_ = &fn; n_ = n; next_.store(0); pending_ = (int)workers_.size(); gen_++; }
-        cv_.notify_all();
-        run(fn, (int)workers_.size());
-        std::unique_lock<std::mutex> l(m_);
-        done_.wait(l, [this] { return pending_ == 0; });
-        fn_ = nullptr;
-    }
-private:
-    void run(const std::function<void(int, int)> &fn, int wid) {
-        for (;;) {
-            int i = next_.fetch_add(1);
-            if (i >= n_) break;
-            fn(i, wid);
-        }
-    }
-    void loop(int wid) {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::function<void(int, int)> *fn;
-            {
-                std::unique_lock<std::mutex> l(m_);
-                cv_.wait(l, [&] { return gen_ != seen; });
-                seen = gen_;
-                if (stop_) return;
-                fn = fn_;
-            }
-            if (fn) run(*fn, wid);
-            { std::lock_guard<std::mutex> l(m_); if (--pending_ == 0) done_.notify_all(); }
-        }
-    }
-    std::vector<std::thread> workers_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    const std::function<void(int, int)> *fn_ = nullptr;
-    std::atomic<int> next_{0};
-    int n_ = 0, pending_ = 0;
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
-
-// Move-only owners of device memory (hipMalloc) and pinned host memory (hipHostMalloc).  Whoever destroys one has made the owning
-// ctx's device current and synchronised the streams that may still use the memory (free_ctx, dg_upload_scene).
-struct DevMem {
-    static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
-    void operator()(void *p) const { (void)hipFree(p); }
-};
-struct PinnedMem {
-    static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
-    void operator()(void *p) const { (void)hipHostFree(p); }
-};
-template <class T> using DevPtr = std::unique_ptr<T, DevMem>;
-template <class T> using PinnedPtr = std::unique_ptr<T, PinnedMem>;
-// (Re)allocate: what p held is freed first, and p stays empty when the allocation fails.
-template <class T, class Mem> hipError_t hip_alloc(std::unique_ptr<T, Mem> &p, size_t bytes) {
-    p.reset();
-    void *q = nullptr;
-    const hipError_t e = Mem::alloc(&q, bytes);
-    if (e == hipSuccess) p.reset(static_cast<T *>(q));
-    return e;
-}
 
 struct Slot {
     hipStream_t stream = nullptr;
     // timing events, attached to the dispatches themselves (kernels.hpp): first / last front-end kernel, raster launch; ev_raster is also
     // what "the slot's kernels are done" is waited on
     hipEvent_t ev_start = nullptr, ev_setup = nullptr, ev_rstart = nullptr, ev_raster = nullptr, ev_h2d = nullptr;
+    // ev_raster has been recorded at least once: slot_sync waits only on an event that has.  Not part of the phase below, because it is
+    // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
     bool raster_recorded = false;
     hipStream_t copy_stream = nullptr;   // dg_readback_async: D2H of this slot's frames while another slot's kernels run
     uint8_t *copy_out = nullptr;         // pending asynchronous readback (re-issued if the batch has to be redone)
@@ -156,7 +79,17 @@ struct Slot {
     uint64_t n_spans = 0, covered = 0, list_bytes = 0, n_walls = 0, n_planes = 0;
     int n_frames = 0;
     float host_ms = 0.0f;         // list generation + binning + packing of the last submission
-    bool busy = false, timed = false;
+    // Where that submission stands.  Each step is written once: describe() (-> prepared), enqueue_kernels (-> queued, or
+    // -> empty when it fails), make_final (queued -> settled) and reset() (-> empty).
+    enum class Phase {
+        Empty,                    // no submission (n_frames == 0): a fresh slot, every slot after dg_upload_scene, one whose enqueue failed half way
+        Prepared,                 // lists or records are resident and have not run since they were built
+        Queued,                   // kernels are enqueued: nobody has waited for them or looked at the overflow flags
+        Settled                   // they have finished, frames that overflowed a capacity are redone: the framebuffer is final, the records still there to replay
+    } phase = Phase::Empty;
+    bool has_run() const { return phase >= Phase::Queued; }                        // the timing events are this submission's
+    bool unchecked() const { return phase == Phase::Queued && column_walk(); }     // its overflow flags still have to be looked at
+    void reset() { phase = Phase::Empty; n_frames = 0; snap_scene = nullptr; }     // (nothing may be replayed or redone from what the slot holds)
     // device column walk (DG_FE_DEVICE)
     PinnedPtr<uint8_t> h_fe;                    // record slab: pinned staging
     DevPtr<uint8_t> d_fe;                       // ... and HBM
@@ -176,14 +109,13 @@ struct Slot {
     int32_t front_end = DG_FE_HOST;
     // A new submission of n frames through front end fe, `bytes` of lists or records uploaded for it (span statistics: the host list path's alone)
     void describe(int32_t fe, int n, uint64_t bytes, uint64_t walls, uint64_t planes) {
-        front_end = fe; fe_check = false; n_frames = n; list_bytes = bytes; n_walls = walls; n_planes = planes;
+        front_end = fe; phase = Phase::Prepared; n_frames = n; list_bytes = bytes; n_walls = walls; n_planes = planes;
         max_spans = 0; n_spans = 0; covered = 0;
     }
     bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
     bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
     bool map_built = false;       // a map submission whose enqueue built the ctx's map layer (ev_start .. ev_setup time that)
-    bool fe_check = false;        // a column-walk submission whose overflow flags have not been looked at yet
     std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
     // ... and a private copy of their game-state snapshots (the caller's arrays need not outlive the call)
     std::vector<dg_view_state> states;
@@ -396,6 +328,15 @@ void fill_raster_params(dg_ctx *c, Slot &s, int n) {
     P.n_frames = n;
 }
 
+// One array of device slab `d` into a kernel parameter, and the walk's nine record arrays of a record slab laid out as L into P: FeLayout
+// and FsLayout name those pieces alike, and so do FeParams, which reads them, and FsParams, which writes them.
+template <class T> void point_at(T *&p, uint8_t *d, size_t off) { p = reinterpret_cast<T *>(d + off); }
+template <class Params, class Layout> void point_at_records(Params &P, uint8_t *d, const Layout &L) {
+    point_at(P.fframes, d, L.fframes); point_at(P.parts, d, L.parts); point_at(P.sprites, d, L.sprites);
+    point_at(P.behind, d, L.behind); point_at(P.sky_parts, d, L.sky);
+    point_at(P.bin_off, d, L.bin_off); point_at(P.sbin_off, d, L.sbin_off); point_at(P.bin_parts, d, L.bins); point_at(P.sbin_sprites, d, L.sbins);
+}
+
 uint32_t fe_span_stride(const dg_ctx *c) { return (uint32_t)(c->span_cap_per_batch / (size_t)c->cfg.max_batch); }
 
 // The part of slot.FP / slot.P that does not depend on who wrote the records (the host walker or the device seg walk), given F.frames.
@@ -539,20 +480,12 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         if (!o.bin_parts.empty()) std::memcpy(h + L.bins + (size_t)ff.bin_base * 2, o.bin_parts.data(), o.bin_parts.size() * 2);
         if (!o.sbin_sprites.empty()) std::memcpy(h + L.sbins + (size_t)ff.sbin_base * 2, o.sbin_sprites.data(), o.sbin_sprites.size() * 2);
     });
-    const uint8_t *const d = s.d_fe.get();
+    uint8_t *const d = s.d_fe.get();
     FeParams &F = s.FP;
-    F.frames = reinterpret_cast<const DevFrame *>(d + L.frames);
-    F.fframes = reinterpret_cast<const FeFrame *>(d + L.fframes);
-    F.parts = reinterpret_cast<const FePart *>(d + L.parts);
-    F.sprites = reinterpret_cast<const FeSprite *>(d + L.sprites);
-    F.behind = reinterpret_cast<const uint32_t *>(d + L.behind);
-    F.sky_parts = reinterpret_cast<const uint32_t *>(d + L.sky);
+    point_at(F.frames, d, L.frames);
+    point_at_records(F, d, L);
     F.max_sky_slots = max_sky; F.gap_waves = 0;
-    F.bin_off = reinterpret_cast<const uint32_t *>(d + L.bin_off);
-    F.sbin_off = reinterpret_cast<const uint32_t *>(d + L.sbin_off);
-    F.bin_parts = reinterpret_cast<const uint16_t *>(d + L.bins);
-    F.sbin_sprites = reinterpret_cast<const uint16_t *>(d + L.sbins);
-    F.order = reinterpret_cast<const uint32_t *>(d + L.order); F.order_cnt = nullptr;
+    point_at(F.order, d, L.order); F.order_cnt = nullptr;
     fill_walk_params(c, s, n);
     s.describe(DG_FE_DEVICE, n, L.total, parts, sprites);
     s.views.assign(views, views + n);
@@ -566,26 +499,6 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     HIP_TRY(hipMemcpyAsync(s.d_fe.get(), s.h_fe.get(), L.total, hipMemcpyHostToDevice, s.stream));
     return DG_OK;
 }
-
-// Host tables packed into one device allocation: each starts on a 256-byte boundary and takes at least 16 bytes (an empty table
-// still has an address of its own).  add() the tables, upload() them (one hipMalloc, one copy), then at<T>() what add() returned.
-struct TablePack {
-    std::vector<uint8_t> staged;
-    SlabCursor cur;
-    const uint8_t *base = nullptr;
-    template <class T> size_t add(const std::vector<T> &v) {
-        const size_t at = cur.take(std::max<size_t>(v.size() * sizeof(T), 16));
-        staged.resize(cur.next);
-        if (!v.empty()) std::memcpy(staged.data() + at, v.data(), v.size() * sizeof(T));
-        return at;
-    }
-    hipError_t upload(DevPtr<uint8_t> &mem) {
-        const hipError_t e = hip_alloc(mem, staged.size());
-        base = mem.get();
-        return e != hipSuccess ? e : hipMemcpy(mem.get(), staged.data(), staged.size(), hipMemcpyHostToDevice);
-    }
-    template <class T> const T *at(size_t off) const { return reinterpret_cast<const T *>(base + off); }
-};
 
 // DG_FE_DEVICE_SEGS: the scene's per-seg / per-sprite tables and BSP tables (Scene::rebuild_fs_tables) in one device allocation, the
 // tables of the effects that are on in one each, and the per-batch scratch of the seg walk, whose size follows the scene (segs, leaves).
@@ -681,7 +594,7 @@ bool choose_fs(dg_ctx *c, const dg_view *views, int n) {
     if (n < 64 || c->preparing) return false;
     if (c->ema_host < 0.0) calibrate_host(c, views, n);
     bool in_flight = false;
-    for (Slot &s : c->slots) { harvest_gpu_time(c, s); in_flight |= s.busy; }
+    for (Slot &s : c->slots) { harvest_gpu_time(c, s); in_flight |= s.phase == Slot::Phase::Queued; }
     if (!in_flight) return true;
     // No seg-walk batch timed yet: the GPU keeps the per-seg half until one has been (it costs the GPU ~0.1 ms per 1 000 frames; a batch on a
     // host that turns out to be the slower side costs the pipeline a millisecond).  From then on: whoever is the slower side of the pipeline.
@@ -781,20 +694,11 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     if (mfx) wire_rows(s.MR, c->mfx_proto, Q.views, n, states ? reinterpret_cast<const uint32_t *>(d + L.mmask) : nullptr,
                        reinterpret_cast<int32_t *>(d + (states ? L.mstate : L.mrows)), sc.mobjs.size(), Q.mobj_state, Q.mstate_stride);
     Q.flags = s.d_flags.get();
-    Q.fframes = reinterpret_cast<FeFrame *>(d + L.fframes);
-    Q.parts = reinterpret_cast<FePart *>(d + L.parts);
-    Q.sprites = reinterpret_cast<FeSprite *>(d + L.sprites);
-    Q.behind = reinterpret_cast<uint32_t *>(d + L.behind);
-    Q.sky_parts = reinterpret_cast<uint32_t *>(d + L.sky);
-    Q.bin_off = reinterpret_cast<uint32_t *>(d + L.bin_off);
-    Q.sbin_off = reinterpret_cast<uint32_t *>(d + L.sbin_off);
-    Q.bin_parts = reinterpret_cast<uint16_t *>(d + L.bins);
-    Q.sbin_sprites = reinterpret_cast<uint16_t *>(d + L.sbins);
+    point_at_records(Q, d, L);                             // the seg walk writes what the column walk reads
     FeParams &F = s.FP;
-    F.frames = reinterpret_cast<const DevFrame *>(d + L.frames);
-    F.fframes = Q.fframes; F.parts = Q.parts; F.sprites = Q.sprites; F.behind = Q.behind; F.sky_parts = Q.sky_parts;
+    point_at(F.frames, d, L.frames);
+    point_at_records(F, d, L);
     F.max_sky_slots = FS_SKY_CAP; F.gap_waves = 12;
-    F.bin_off = Q.bin_off; F.sbin_off = Q.sbin_off; F.bin_parts = Q.bin_parts; F.sbin_sprites = Q.sbin_sprites;
     Q.order_cnt = s.d_flags.get() + c->cfg.max_batch;      // zeroed with the flags (enqueue_kernels)
     Q.order_list = s.d_order.get();
     Q.n_items = (uint32_t)n * (uint32_t)fe_col_groups((size_t)W);
@@ -868,32 +772,24 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     // written by the kernels directly: nothing is queued behind the raster launch, so no stream ever holds a barrier that another
     // slot's upload could get stuck behind (streams share hardware queues).
     hipStream_t ks = c->kstream;
-    // A HIP call that fails half way leaves the slot describing no submission at all: later calls on it return DG_ERR_INVALID
-    // instead of waiting on a stale event or reading status words nobody wrote.
+    // A HIP call that fails half way leaves the slot empty: later calls on it return DG_ERR_INVALID instead of reading status words
+    // nobody wrote.
     struct Invalidate {
         Slot &s; bool armed = true;
-        ~Invalidate() { if (armed) { s.n_frames = 0; s.timed = false; s.busy = false; s.fe_check = false; s.raster_recorded = false; } }
+        ~Invalidate() { if (armed) s.reset(); }
     } guard{s};
     const bool fe_mode = s.column_walk();
-    s.fe_check = false;
     HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
     HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
-    if (s.front_end == DG_FE_MAP) {                       // 2-D map frames: the layer (once per scene upload), then copy + arrow per frame
+    const bool map = s.front_end == DG_FE_MAP;
+    if (map) {                                            // 2-D map frames: the layer (once per scene upload), then copy + arrow per frame
         s.map_built = false;
         if (!c->map_layer_ok) {
             const int rc = build_map_layer(c, s);
             if (rc) return rc;
             s.map_built = true;
         }
-        HIP_TRY(launch_map_frames(c->d_map_layer.get(), reinterpret_cast<const MapSeg *>(s.d_lists.get()), s.n_frames, s.d_fb.get(), c->cfg.width, c->cfg.height,
-                                  ks, s.ev_rstart, s.ev_raster));
-        guard.armed = false;
-        s.harvested = true;                               // (never DG_FE_AUTO's measurement)
-        s.raster_recorded = true;
-        s.busy = true; s.timed = true;
-        return DG_OK;
-    }
-    if (fe_mode) {
+    } else if (fe_mode) {
         std::memset(s.h_status.get(), 0, (size_t)2 * (size_t)c->cfg.max_batch * 4);
         // the overflow flags, the launch-order counters and the event bits behind them start from zero: dg_fe_scan leaves them so (its
         // last lines), and only a slot that is new or whose last enqueue failed half way is cleared here, whole
@@ -912,7 +808,10 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     } else {
         HIP_TRY(launch_setup(s.P, s.max_spans, ks, s.ev_start, s.ev_setup));
     }
-    if (c->raster_overlap && fe_mode) {                   // the front end of the next batch may start while this launch runs (the column scratch is the front end's alone)
+    if (map) {
+        HIP_TRY(launch_map_frames(c->d_map_layer.get(), reinterpret_cast<const MapSeg *>(s.d_lists.get()), s.n_frames, s.d_fb.get(), c->cfg.width, c->cfg.height,
+                                  ks, s.ev_rstart, s.ev_raster));
+    } else if (c->raster_overlap && fe_mode) {                   // the front end of the next batch may start while this launch runs (the column scratch is the front end's alone)
         HIP_TRY(hipStreamWaitEvent(c->rstream, s.ev_setup, 0));
         HIP_TRY(launch_raster(s.P, c->rstream, s.ev_rstart, s.ev_raster));
     } else {
@@ -920,10 +819,9 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     }
     if (fe_mode) s.walk_state_clean = true;               // everything was enqueued: dg_fe_scan will have cleaned up by the slot's next batch
     guard.armed = false;
-    s.harvested = false;
-    s.fe_check = fe_mode;
+    s.harvested = !fe_mode;                               // (only a column-walk batch is DG_FE_AUTO's measurement)
     s.raster_recorded = true;
-    s.busy = true; s.timed = true;
+    s.phase = Slot::Phase::Queued;
     return DG_OK;
 }
 
@@ -964,52 +862,48 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     return DG_OK;
 }
 
-// After the slot's stream has been synchronised: look at the overflow flags of a device-column-walk submission; a batch
-// that overflowed a per-column / per-frame capacity is redone through the host list path (which has the larger limits).
-int settle_slot(dg_ctx *c, Slot &s) {
-    if (s.fe_check) {
-        s.fe_check = false;
-        const uint32_t *const status = s.h_status.get();      // [max_batch] overflow flags, [max_batch] spans per frame
-        bool overflow = false;
-        uint64_t spans = 0;
-        for (int i = 0; i < s.n_frames; i++) {
-            overflow |= status[i] != 0;
-            spans += status[c->cfg.max_batch + i];
-        }
-        s.n_spans = spans;
-        bool whole_batch = overflow;
-        if (overflow) {
-            // Only the frames that overflowed are redone (through the host list path, one at a time); if one of them does not fit the
-            // single-frame scratch either, the whole batch is.
-            c->fallbacks_fe++;
-            whole_batch = false;
-            for (int i = 0; i < s.n_frames && !whole_batch; i++) {
-                if (status[i] == 0) continue;
-                const int rc = redo_frame_host(c, s, i);
-                if (rc == DG_ERR_CAPACITY) whole_batch = true;
-                else if (rc) return rc;
-                else c->redone_frames++;
-            }
-        }
-        if (whole_batch) {
-            // (the whole batch again, with every frame's submit-time state: build_batch_host reads the states while it runs and keeps nothing of them)
-            const std::vector<dg_view> views = s.views;
-            std::vector<Slot::RedoState> redo_states(views.size());
-            std::vector<dg_view_state> sts;
-            bool any_state = false;
-            for (size_t i = 0; i < views.size(); i++) {
-                const dg_view_state *st = s.state_for_redo(*c->scene, (int)i, redo_states[i], c->fx);
-                any_state |= st != nullptr;
-                sts.push_back(st ? *st : dg_view_state{nullptr, 0, nullptr, 0});
-            }
-            int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), any_state ? sts.data() : nullptr);
-            if (rc) return rc;
-            rc = enqueue_kernels(c, s);
-            if (rc) return rc;
-            HIP_TRY(slot_sync(s));
-        }
+enum class Copy { Leave, Complete };                   // what make_final does about the slot's pending dg_readback_async
+int make_final(dg_ctx *c, Slot &s, Copy copy);
+
+// The overflow flags of a column-walk submission whose kernels have finished (make_final): a batch that overflowed a per-column /
+// per-frame capacity is redone through the host list path (which has the larger limits).
+int redo_overflowed(dg_ctx *c, Slot &s) {
+    const uint32_t *const status = s.h_status.get();      // [max_batch] overflow flags, [max_batch] spans per frame
+    bool overflow = false;
+    uint64_t spans = 0;
+    for (int i = 0; i < s.n_frames; i++) {
+        overflow |= status[i] != 0;
+        spans += status[c->cfg.max_batch + i];
     }
-    return DG_OK;
+    s.n_spans = spans;
+    if (!overflow) return DG_OK;
+    // Only the frames that overflowed are redone (through the host list path, one at a time); if one of them does not fit the
+    // single-frame scratch either, the whole batch is.
+    c->fallbacks_fe++;
+    bool whole_batch = false;
+    for (int i = 0; i < s.n_frames && !whole_batch; i++) {
+        if (status[i] == 0) continue;
+        const int rc = redo_frame_host(c, s, i);
+        if (rc == DG_ERR_CAPACITY) whole_batch = true;
+        else if (rc) return rc;
+        else c->redone_frames++;
+    }
+    if (!whole_batch) return DG_OK;
+    // (the whole batch again, with every frame's submit-time state: build_batch_host reads the states while it runs and keeps nothing of them)
+    const std::vector<dg_view> views = s.views;
+    std::vector<Slot::RedoState> redo_states(views.size());
+    std::vector<dg_view_state> sts;
+    bool any_state = false;
+    for (size_t i = 0; i < views.size(); i++) {
+        const dg_view_state *st = s.state_for_redo(*c->scene, (int)i, redo_states[i], c->fx);
+        any_state |= st != nullptr;
+        sts.push_back(st ? *st : dg_view_state{nullptr, 0, nullptr, 0});
+    }
+    int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), any_state ? sts.data() : nullptr);
+    if (rc) return rc;
+    rc = enqueue_kernels(c, s);
+    if (rc) return rc;
+    return make_final(c, s, Copy::Leave);                  // (a host-list batch now: it is waited for, there are no flags to look at)
 }
 
 int enqueue_copy(dg_ctx *c, Slot &s) {
@@ -1021,7 +915,7 @@ int enqueue_copy(dg_ctx *c, Slot &s) {
 
 // DG_FE_AUTO's measurement of the GPU side: the span of a finished submission's kernels (never waits)
 void harvest_gpu_time(dg_ctx *c, Slot &s) {
-    if (s.harvested || !s.timed || !s.column_walk() || s.n_frames < 64 || c->fs_forced || !c->fs_enabled) return;
+    if (s.harvested || !s.has_run() || !s.column_walk() || s.n_frames < 64 || c->fs_forced || !c->fs_enabled) return;
     if (hipEventQuery(s.ev_raster) != hipSuccess) return;
     s.harvested = true;
     float ms = 0.0f;
@@ -1037,25 +931,53 @@ void harvest_gpu_time(dg_ctx *c, Slot &s) {
     ema = ema < 0.0 ? v : 0.75 * ema + 0.25 * v;
 }
 
-// Everything queued for the slot has finished: kernels, capacity checks (a batch that overflowed is redone here) and a
-// pending asynchronous readback (re-issued after a redo: its first copy took frames of the overflowed run).
-int finish_slot(dg_ctx *c, Slot &s) {
+// Making the last submission's results final, the one way from queued to settled: everything queued for the slot has finished, and the
+// overflow flags of a column-walk batch are looked at, once per enqueue (frames that overflowed are redone here).  On a slot that is
+// not queued this only waits, for a prepared slot's upload.  Copy::Complete is the wait path (dg_wait, take_slot): it owns the slot's
+// pending asynchronous readback as well — completed, and issued again after a redo, because its first copy took frames of the overflowed
+// run — and it is where DG_FE_AUTO reads the batch's GPU time.  Copy::Leave leaves both alone.
+int make_final(dg_ctx *c, Slot &s, Copy copy) {
     HIP_TRY(slot_sync(s));
-    harvest_gpu_time(c, s);
-    s.busy = false;
+    if (copy == Copy::Complete) harvest_gpu_time(c, s);
     const uint64_t redone = c->fallbacks_fe;
-    int rc = settle_slot(c, s);
-    if (rc) return rc;
-    if (s.copy_pending) {
+    const bool check = s.unchecked();
+    if (s.phase == Slot::Phase::Queued) s.phase = Slot::Phase::Settled;      // (before the redo: the flags are looked at once even when it fails)
+    if (check) {
+        const int rc = redo_overflowed(c, s);
+        if (rc) return rc;
+    }
+    if (copy == Copy::Complete && s.copy_pending) {
         HIP_TRY(hipStreamSynchronize(s.copy_stream));
         if (c->fallbacks_fe != redone) {
-            rc = enqueue_copy(c, s);
+            const int rc = enqueue_copy(c, s);
             if (rc) return rc;
             HIP_TRY(hipStreamSynchronize(s.copy_stream));
         }
         s.copy_pending = false;
     }
     return DG_OK;
+}
+
+// Taking the slot for a new submission: what is in flight is finished first, a pending asynchronous readback included (it reads the
+// framebuffer the new submission overwrites).  After that the slot is the builder's.
+int take_slot(dg_ctx *c, Slot &s) {
+    return s.phase == Slot::Phase::Queued || s.copy_pending ? make_final(c, s, Copy::Complete) : DG_OK;
+}
+
+// Slot `slot` for a new submission of n views (or of the caller's lists), and its kernels enqueued.
+int submit(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    Slot &s = c->slots[(size_t)slot];
+    int rc = take_slot(c, s);
+    if (rc) return rc;
+    rc = build_batch(c, s, views, given, n, states);
+    return rc ? rc : enqueue_kernels(c, s);
+}
+
+// The synchronous calls' tail, given what their submission returned: its n frames into `out`, or just its end.
+int read_or_wait(dg_ctx *c, int slot, int rc, int n, uint8_t *out) {
+    if (rc) return rc;
+    return out ? dg_readback(c, slot, 0, n, out) : dg_wait(c, slot);
 }
 
 int check_slot(dg_ctx *c, int slot) {
@@ -1067,118 +989,6 @@ int check_slot(dg_ctx *c, int slot) {
 }  // namespace
 
 extern "C" {
-
-const char *dg_last_error(void) { return t_err.c_str(); }
-const char *dg_version(void) { return "doomgpu 0.6 (gfx950; ABI 4)"; }
-
-int dg_scene_load_wad(const uint8_t *wad, size_t len, const char *map_name, dg_scene **out) {
-    if (!wad || !map_name || !out) return set_err(DG_ERR_INVALID, "null argument");
-    std::string err;
-    Scene *sc = load_scene_from_wad(wad, len, map_name, err);
-    if (!sc) return set_err(DG_ERR_WAD, err);
-    *out = new dg_scene{sc};
-    return DG_OK;
-}
-void dg_scene_free(dg_scene *s) { if (s) { delete s->sc; delete s; } }
-int dg_scene_player_start(const dg_scene *s, float *x, float *y, float *angle) {
-    if (!s || !x || !y || !angle) return set_err(DG_ERR_INVALID, "null argument");
-    if (!s->sc->has_start) return set_err(DG_ERR_WAD, "Could not find thing of type 1 (src/map/things.rs:46-55)");
-    *x = s->sc->start_x; *y = s->sc->start_y; *angle = s->sc->start_angle;
-    return DG_OK;
-}
-int dg_scene_floor_height_at(const dg_scene *s, float x, float y, float *h) {
-    if (!s || !h) return set_err(DG_ERR_INVALID, "null argument");
-    int sec = s->sc->sector_from_vertex(x, y);
-    if (sec < 0) return 1;
-    *h = (float)s->sc->sectors[(size_t)sec].floor_h;
-    return DG_OK;
-}
-int dg_scene_sector_count(const dg_scene *s) { return s ? (int)s->sc->sectors.size() : DG_ERR_INVALID; }
-int dg_scene_set_sector_light(dg_scene *s, int sector, int16_t light) {
-    if (!s || sector < 0 || (size_t)sector >= s->sc->sectors.size()) return set_err(DG_ERR_INVALID, "bad sector");
-    s->sc->sectors[(size_t)sector].light = light;
-    s->sc->revision++;
-    return DG_OK;
-}
-int dg_scene_mobj_count(const dg_scene *s) { return s ? (int)s->sc->mobjs.size() : DG_ERR_INVALID; }
-int dg_scene_set_mobj_state(dg_scene *s, int mobj, const char *sprite, uint8_t frame, int full_bright) {
-    if (!s || mobj < 0 || (size_t)mobj >= s->sc->mobjs.size()) return set_err(DG_ERR_INVALID, "bad map object");
-    MapObjectRec &m = s->sc->mobjs[(size_t)mobj];
-    s->sc->revision++;
-    if (!sprite) { m.sprite_frame = -1; return DG_OK; }
-    std::string err;
-    int sf = s->sc->find_or_add_sprite_frame(sprite, frame, err);
-    if (sf < 0) return set_err(DG_ERR_WAD, err);
-    m.sprite_frame = sf; m.full_bright = full_bright;
-    return DG_OK;
-}
-int dg_scene_texture_id(const dg_scene *s, const char *name) { return (s && name) ? s->sc->texture_id(name) : DG_ERR_INVALID; }
-int dg_scene_flat_id(const dg_scene *s, const char *name, float ts) { return (s && name) ? s->sc->flat_id(name, ts) : DG_ERR_INVALID; }
-int dg_scene_set_wall_effects(dg_scene *s, uint32_t flags) {
-    if (!s) return set_err(DG_ERR_INVALID, "null scene");
-    std::string err;
-    const int rc = s->sc->set_wall_effects(flags, err);
-    return rc ? set_err(rc, err) : DG_OK;
-}
-int dg_scene_wall_texture_id(const dg_scene *s, const char *name, float ts) { return (s && name) ? s->sc->wall_texture_id(name, ts) : DG_ERR_INVALID; }
-int dg_scene_set_light_effects(dg_scene *s, uint32_t flags, uint64_t seed) {
-    if (!s) return set_err(DG_ERR_INVALID, "null scene");
-    std::string err;
-    const int rc = s->sc->set_light_effects(flags, seed, err);
-    return rc ? set_err(rc, err) : DG_OK;
-}
-int dg_scene_sector_lights_at(const dg_scene *s, float ts, int16_t *out, int n) {
-    if (!s || !out) return set_err(DG_ERR_INVALID, "null argument");
-    const Scene &sc = *s->sc;
-    if (n < 0 || (size_t)n != sc.sectors.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_sector_count");
-    for (size_t i = 0; i < sc.sectors.size(); i++) out[i] = sc.sectors[i].light;
-    const LightFx &fx = sc.fx.light;
-    if (fx.on())
-        for (size_t r = 0; r < fx.recs.size(); r++) out[fx.recs[r].sector] = fx.level(r, ts);
-    return DG_OK;
-}
-int dg_scene_set_mobj_thinkers(dg_scene *s, uint32_t flags, const dg_state_rec *states, int n_states, const dg_mobj_info_rec *infos, int n_infos) {
-    if (!s) return set_err(DG_ERR_INVALID, "null scene");
-    std::string err;
-    const int rc = s->sc->set_mobj_thinkers(flags, states, n_states, infos, n_infos, err);
-    return rc ? set_err(rc, err) : DG_OK;
-}
-int dg_scene_mobj_event(dg_scene *s, int what, float ts) {
-    if (!s) return set_err(DG_ERR_INVALID, "null scene");
-    std::string err;
-    const int rc = s->sc->mobj_event(what, ts, err);
-    return rc ? set_err(rc, err) : DG_OK;
-}
-int dg_scene_mobj_states_at(const dg_scene *s, float ts, dg_mobj_state *out, int n) {
-    if (!s || !out) return set_err(DG_ERR_INVALID, "null argument");
-    const Scene &sc = *s->sc;
-    if (n < 0 || (size_t)n != sc.mobjs.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_mobj_count");
-    for (size_t i = 0; i < sc.mobjs.size(); i++)
-        out[i] = dg_mobj_state{(int32_t)i, sc.mobjs[i].sprite_frame < 0 ? -1 : sc.mobjs[i].sprite_frame, sc.mobjs[i].sprite_frame < 0 ? 0 : (sc.mobjs[i].full_bright ? 1 : 0), 0};
-    const MobjFx &fx = sc.fx.mobj;
-    if (fx.fits(sc))
-        for (uint32_t i : fx.driven) mfx_decode(fx.value(i, ts), out[i].sprite_frame, out[i].full_bright);
-    return DG_OK;
-}
-int dg_scene_sprite_bitmap_id(const dg_scene *s, const char *sprite, uint8_t frame, uint8_t rot) {
-    return (s && sprite) ? s->sc->sprite_bitmap_id(sprite, frame, rot) : DG_ERR_INVALID;
-}
-int dg_scene_bitmap_size(const dg_scene *s, int bitmap, int *w, int *h) {
-    if (!s || bitmap < 0 || (size_t)bitmap >= s->sc->bitmaps.size()) return set_err(DG_ERR_INVALID, "bad bitmap id");
-    if (w) *w = s->sc->bitmaps[(size_t)bitmap].w;
-    if (h) *h = s->sc->bitmaps[(size_t)bitmap].h;
-    return DG_OK;
-}
-
-int dg_build_lists(const dg_scene *s, int width, int height, const dg_view *view, dg_frame_lists *out) {
-    if (!s || !view || !out) return set_err(DG_ERR_INVALID, "null argument");
-    static thread_local FrameArena arena;
-    dg_view v = *view;
-    fill_view_trig(v);
-    std::string err;
-    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err, nullptr, &s->sc->fx);
-    return rc ? set_err(rc, err) : DG_OK;
-}
 
 int dg_create(const dg_config *cfg, dg_ctx **out) {
     if (!cfg || !out) return set_err(DG_ERR_INVALID, "null argument");
@@ -1306,7 +1116,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
         // A slot with work in flight is FINISHED against the scene it was rendered from (still resident): a device-walk batch that
         // overflowed a capacity is redone and its pending readback re-issued, exactly as dg_wait would have done.  (If that redo is
         // impossible — the old scene object itself was changed since its upload — the slot is just drained.)
-        if ((s.busy || s.copy_pending || s.fe_check) && c->scene && s.n_frames > 0 && finish_slot(c, s) == DG_OK) continue;
+        if (c->scene) (void)take_slot(c, s);
         HIP_TRY(slot_sync(s));
         HIP_TRY(hipStreamSynchronize(s.copy_stream));
         s.copy_pending = false;
@@ -1315,7 +1125,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     c->d_palette.reset(); c->d_texel_idx.reset(); c->d_texel_opq.reset();
     c->d_flats = nullptr;               // inside d_texel_idx's allocation
     // the slots' prepared records point into the device scene that was just freed: nothing may be replayed from them
-    for (Slot &s : c->slots) { s.n_frames = 0; s.timed = false; s.fe_check = false; s.busy = false; s.snap_scene = nullptr; }
+    for (Slot &s : c->slots) s.reset();
     c->d_walk_tables.reset();           // dg_ctx_locate_walks is synchronous: nothing of it is in flight
     c->map_layer_ok = false;            // the map view's linedef layer belongs to the old scene   // (a new scene may reuse the old one's address and revision)
     uint32_t pal[256];
@@ -1363,18 +1173,8 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
 
 int dg_submit_views(dg_ctx *c, int slot, const dg_view *views, int n) { return dg_submit_views_state(c, slot, views, nullptr, n); }
 
-int dg_scene_sprite_frame(dg_scene *s, const char *sprite, uint8_t frame) {
-    if (!s || !sprite) return set_err(DG_ERR_INVALID, "null argument");
-    std::string err;
-    const int sf = s->sc->find_or_add_sprite_frame(sprite, frame, err);
-    return sf < 0 ? set_err(DG_ERR_WAD, err) : sf;
-}
-
 int dg_render_views_state(dg_ctx *c, const dg_view *views, const dg_view_state *states, int n, uint8_t *out) {
-    int rc = dg_submit_views_state(c, 0, views, states, n);
-    if (rc) return rc;
-    if (out) return dg_readback(c, 0, 0, n, out);
-    return dg_wait(c, 0);
+    return read_or_wait(c, 0, dg_submit_views_state(c, 0, views, states, n), n, out);
 }
 
 int dg_submit_views_state(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, int n) {
@@ -1384,20 +1184,14 @@ int dg_submit_views_state(dg_ctx *c, int slot, const dg_view *views, const dg_vi
     if (states)
         for (int i = 0; i < n; i++)
             if ((states[i].n_lights && !states[i].lights) || (states[i].n_mobjs && !states[i].mobjs)) return set_err(DG_ERR_INVALID, "view state with a null array");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    Slot &s = c->slots[(size_t)slot];
-    if (s.busy || s.copy_pending) { rc = finish_slot(c, s); if (rc) return rc; }
-    s.fe_check = false;
-    rc = build_batch(c, s, views, nullptr, n, states);
-    if (rc) return rc;
-    return enqueue_kernels(c, s);
+    return submit(c, slot, views, nullptr, n, states);
 }
 
 int dg_wait(dg_ctx *c, int slot) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    return finish_slot(c, c->slots[(size_t)slot]);
+    return make_final(c, c->slots[(size_t)slot], Copy::Complete);
 }
 
 int dg_readback_async(dg_ctx *c, int slot, int first, int count, uint8_t *out) {
@@ -1441,14 +1235,10 @@ int dg_readback(dg_ctx *c, int slot, int first, int count, uint8_t *out) {
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
-    HIP_TRY(slot_sync(s));
-    if (s.fe_check) {
-        rc = settle_slot(c, s);
-        if (rc) return rc;
-    }
+    rc = make_final(c, s, Copy::Leave);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, s.d_fb.get() + (size_t)first * fsz, (size_t)count * fsz, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(slot_sync(s));
-    s.busy = false;
     return DG_OK;
 }
 
@@ -1459,11 +1249,8 @@ int dg_frame_checksums(dg_ctx *c, int slot, int first, int count, uint64_t *out)
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad frame range");
     if (count == 0) return DG_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(slot_sync(s));                       // (the kernels run on the ctx's kernel stream: the copy below is not ordered behind them by its stream)
-    if (s.fe_check) {
-        rc = settle_slot(c, s);
-        if (rc) return rc;
-    }
+    rc = make_final(c, s, Copy::Leave);          // (the kernels run on the ctx's kernel stream: the copy below is not ordered behind them by its stream)
+    if (rc) return rc;
     const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
     unsigned long long *d_sum = c->d_checksums.get();      // max_batch entries, allocated at dg_create
     hipError_t e = hipMemsetAsync(d_sum, 0, (size_t)count * 8, s.stream);
@@ -1471,7 +1258,6 @@ int dg_frame_checksums(dg_ctx *c, int slot, int first, int count, uint64_t *out)
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_sum, (size_t)count * 8, hipMemcpyDeviceToHost, s.stream);
     if (e == hipSuccess) e = slot_sync(s);
     if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_frame_checksums: ") + hipGetErrorString(e));
-    s.busy = false;
     return DG_OK;
 }
 
@@ -1483,10 +1269,7 @@ void *dg_alloc_host(size_t bytes) {
 void dg_free_host(void *p) { if (p) (void)hipHostFree(p); }
 
 int dg_render_views(dg_ctx *c, const dg_view *views, int n, uint8_t *out) {
-    int rc = dg_submit_views(c, 0, views, n);
-    if (rc) return rc;
-    if (out) return dg_readback(c, 0, 0, n, out);
-    return dg_wait(c, 0);
+    return read_or_wait(c, 0, dg_submit_views(c, 0, views, n), n, out);
 }
 
 int dg_prepare_views(dg_ctx *c, int slot, const dg_view *views, int n) {
@@ -1495,9 +1278,8 @@ int dg_prepare_views(dg_ctx *c, int slot, const dg_view *views, int n) {
     if (!views) return set_err(DG_ERR_INVALID, "null views");
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
-    if (s.busy || s.copy_pending) { rc = finish_slot(c, s); if (rc) return rc; }   // incl. a readback still copying out of the slot's framebuffer
-    HIP_TRY(slot_sync(s));
-    s.busy = false; s.fe_check = false;
+    rc = take_slot(c, s);
+    if (rc) return rc;
     c->preparing = true;
     rc = build_batch(c, s, views, nullptr, n);
     c->preparing = false;
@@ -1506,26 +1288,21 @@ int dg_prepare_views(dg_ctx *c, int slot, const dg_view *views, int n) {
         rc = enqueue_kernels(c, s);   // is re-prepared that way now, not on a replay
         if (rc) return rc;
     }
-    HIP_TRY(slot_sync(s));
-    s.busy = false;
-    return settle_slot(c, s);
+    return make_final(c, s, Copy::Leave);         // host lists: uploaded, and the slot stays prepared
 }
 
 int dg_replay_slot(dg_ctx *c, int slot) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if (s.n_frames <= 0) return set_err(DG_ERR_INVALID, "slot has no prepared lists");
+    if (s.phase == Slot::Phase::Empty) return set_err(DG_ERR_INVALID, "slot has no prepared lists");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    if (s.copy_pending) {   // a dg_readback_async is still reading the framebuffer these kernels are about to overwrite
-        rc = finish_slot(c, s);
-        if (rc) return rc;
-    }
-    if (s.fe_check) {   // a submission that was never waited for
-        HIP_TRY(slot_sync(s));
-        rc = settle_slot(c, s);
-        if (rc) return rc;
-    }
+    // A dg_readback_async may still be reading the framebuffer these kernels are about to overwrite, and a column-walk submission that
+    // was never waited for has its overflow flags looked at before the walk clears them.  A host-list submission still in flight is not
+    // waited for: its lists simply run again behind it.
+    if (s.copy_pending) rc = make_final(c, s, Copy::Complete);
+    else if (s.unchecked()) rc = make_final(c, s, Copy::Leave);
+    if (rc) return rc;
     return enqueue_kernels(c, s);  // (the overflow flags are looked at again: frames that overflowed are redone on every replay)
 }
 
@@ -1533,28 +1310,7 @@ int dg_draw_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, int n, uint
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!frames) return set_err(DG_ERR_INVALID, "null frames");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    Slot &s = c->slots[(size_t)slot];
-    if (s.busy || s.copy_pending) { rc = finish_slot(c, s); if (rc) return rc; }
-    s.fe_check = false;
-    rc = build_batch(c, s, nullptr, frames, n);
-    if (rc) return rc;
-    rc = enqueue_kernels(c, s);
-    if (rc) return rc;
-    if (out) return dg_readback(c, slot, 0, n, out);
-    return dg_wait(c, slot);
-}
-
-int dg_map_lines(const dg_scene *s, int width, int height, const dg_view *view, dg_map_line *out, int cap) {
-    if (!s) return set_err(DG_ERR_INVALID, "null scene");
-    dg_view v{};
-    if (view) { v = *view; fill_view_trig(v); }
-    static thread_local std::vector<dg_map_line> lines;
-    std::string err;
-    const int rc = map_frame_lines(*s->sc, width, height, view ? &v : nullptr, lines, err);
-    if (rc) return set_err(rc, err);
-    if (out && cap >= 0 && (size_t)cap >= lines.size() && !lines.empty()) std::memcpy(out, lines.data(), lines.size() * sizeof(dg_map_line));
-    return (int)lines.size();
+    return read_or_wait(c, slot, submit(c, slot, nullptr, frames, n, nullptr), n, out);
 }
 
 int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
@@ -1568,9 +1324,9 @@ int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
     const size_t bytes = (size_t)n * 3 * sizeof(MapSeg);
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
-    if (s.busy || s.copy_pending) { rc = finish_slot(c, s); if (rc) return rc; }
+    rc = take_slot(c, s);
+    if (rc) return rc;
     if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
-    s.fe_check = false;
     const auto t0 = std::chrono::steady_clock::now();
     // the arrow's three lines per view, clipped to the frame (the host owns the libm trig: dg_view has no field for the head angles)
     MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
@@ -1590,33 +1346,7 @@ int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
 }
 
 int dg_render_map_views(dg_ctx *c, const dg_view *views, int n, uint8_t *out) {
-    int rc = dg_submit_map_views(c, 0, views, n);
-    if (rc) return rc;
-    if (out) return dg_readback(c, 0, 0, n, out);
-    return dg_wait(c, 0);
-}
-
-int dg_walk_create(const dg_scene *s, const dg_walk_desc *d, dg_walk **out) {
-    if (!s || !d || !out) return set_err(DG_ERR_INVALID, "null argument");
-    std::string err;
-    const int rc = walk_create(*s->sc, *d, out, err);
-    return rc ? set_err(rc, err) : DG_OK;
-}
-void dg_walk_free(dg_walk *w) { delete w; }
-int dg_walk_tics(const dg_walk *w) { return w ? (int)w->tics() : set_err(DG_ERR_INVALID, "null argument"); }
-int dg_walk_probe_count(const dg_walk *w) { return w ? (int)w->px.size() : set_err(DG_ERR_INVALID, "null argument"); }
-int dg_walk_floors(dg_walk *w, float *out, int n) {
-    if (!w || !out) return set_err(DG_ERR_INVALID, "null argument");
-    if (n < 0 || (size_t)n != w->pose.size()) return set_err(DG_ERR_INVALID, "n must be tics + 1");
-    w->locate_host();
-    std::memcpy(out, w->floors.data(), (size_t)n * sizeof(float));
-    return DG_OK;
-}
-int dg_walk_views(dg_walk *w, const float *timestamps, int n, dg_view *out) {
-    if (!w || n < 0 || (n > 0 && (!timestamps || !out))) return set_err(DG_ERR_INVALID, "null argument");
-    w->locate_host();
-    for (int i = 0; i < n; i++) w->view_at(timestamps[i], out[i]);
-    return DG_OK;
+    return read_or_wait(c, 0, dg_submit_map_views(c, 0, views, n), n, out);
 }
 
 int dg_ctx_locate_walks(dg_ctx *c, dg_walk *const *walks, int n_walks) {
@@ -1698,14 +1428,10 @@ int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
     if (rc) return rc;
     if (!out) return set_err(DG_ERR_INVALID, "null argument");
     Slot &s = c->slots[(size_t)slot];
-    if (!s.timed) return set_err(DG_ERR_INVALID, "slot has not run yet");
+    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(hipEventSynchronize(s.ev_raster));
-    if (s.fe_check) {
-        HIP_TRY(slot_sync(s));
-        rc = settle_slot(c, s);
-        if (rc) return rc;
-    }
+    rc = make_final(c, s, Copy::Leave);
+    if (rc) return rc;
     std::memset(out, 0, sizeof *out);
     out->front_end = s.front_end;
     HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));

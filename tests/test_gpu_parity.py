@@ -454,6 +454,49 @@ def test_device_front_end_capacity_falls_back_to_host_lists(dg, scene1994, oracl
     ctx.close()
 
 
+def test_overflowed_batch_is_settled_by_whichever_call_meets_it_first(dg, scene1994, path1994, monkeypatch):
+    """The overflowing batch of the test above, met first by a call other than dg_wait: dg_frame_checksums, dg_slot_timing, and
+    dg_replay_slot without a wait.  Each of them has to look at the overflow flags itself, exactly once per enqueue: the frames are those
+    of the host list path, and both counters rise by what one overflowing enqueue adds."""
+    W, H = 320, 200
+    idx = list(range(0, 1000, 50))
+    n = len(idx)
+    views = dg.make_views(path1994[idx])
+    host = make_ctx(dg, scene1994, W, H, n, slots=1, front_end=dg.DG_FE_HOST)
+    want = host.render(views)
+    want_sums = host.frame_checksums(0, 0, n)
+    host.close()
+    monkeypatch.setenv("DOOMGPU_FE_COLUMN_SLOTS", "5")
+    ctx = make_ctx(dg, scene1994, W, H, n, slots=2, front_end=dg.DG_FE_DEVICE)
+    monkeypatch.delenv("DOOMGPU_FE_COLUMN_SLOTS")
+    assert np.array_equal(ctx.render(views), want)
+    fb = ctx.fallbacks()
+    per_enqueue = fb["redone_frames"]                    # what one overflowing enqueue of these views adds
+    assert fb["front_end"] == 1 and 1 <= per_enqueue <= n, fb
+
+    def counters_after(enqueues):
+        assert ctx.fallbacks() == {"front_end": enqueues, "redone_frames": enqueues * per_enqueue}, (enqueues, ctx.fallbacks())
+
+    # (a) checksums first
+    ctx.submit(1, views)
+    assert np.array_equal(ctx.frame_checksums(1, 0, n), want_sums)
+    assert np.array_equal(ctx.readback(1, 0, n), want)
+    counters_after(2)
+    # (b) timing first
+    ctx.submit(0, views)
+    t = ctx.timing(0)
+    assert np.array_equal(ctx.readback(0, 0, n), want)
+    assert t["front_end"] == dg.DG_FE_DEVICE and t["n_spans"] > 0, t
+    counters_after(3)
+    # (c) a replay without a wait: the submission is settled before its records run again, the replay at the wait
+    ctx.submit(1, views)
+    ctx.replay(1)
+    ctx.wait(1)
+    assert np.array_equal(ctx.readback(1, 0, n), want)
+    counters_after(5)
+    ctx.close()
+
+
 @pytest.mark.parametrize("front_end", [2, 3], ids=["device-column-walk", "device-seg-walk"])
 def test_redone_frames_see_the_scene_as_it_was_at_submit_time(dg, oracle, wad1994, path1994, monkeypatch, front_end):
     """A pipelined caller moves the scene on between dg_submit_views and dg_wait (gpu::sync_state: lights.rs:47-259, map_objects.rs:63-121).
