@@ -27,6 +27,7 @@ DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
 DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
 DG_MOBJ_KILL, DG_MOBJ_EXPLODE, DG_MOBJ_RESPAWN = 1, 2, 3   # dg_scene_mobj_event
+DG_REDUCE_RGB24, DG_REDUCE_GRAY8 = 0, 1  # dg_reduce_desc.format
 DG_KEY_LEFT, DG_KEY_RIGHT, DG_KEY_UP, DG_KEY_DOWN, DG_KEY_ALT, DG_KEY_SHIFT = 1, 2, 4, 8, 16, 32   # dg_walk_desc.keys
 
 
@@ -66,6 +67,10 @@ class DgViewState(ctypes.Structure):
 class DgWalkDesc(ctypes.Structure):
     _fields_ = [("x", ctypes.c_float), ("y", ctypes.c_float), ("angle", ctypes.c_float), ("from_player_start", ctypes.c_int32),
                 ("turbo", ctypes.c_int32), ("keys", ctypes.POINTER(ctypes.c_uint8)), ("n_tics", ctypes.c_uint32)]
+
+
+class DgReduceDesc(ctypes.Structure):
+    _fields_ = [("fx", ctypes.c_uint32), ("fy", ctypes.c_uint32), ("format", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class DgConfig(ctypes.Structure):
@@ -153,6 +158,13 @@ _SIGNATURES = {
     "dg_ctx_fallbacks": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     "dg_ctx_redone_frames": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     "dg_frame_checksums": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+    "dg_reduced_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgReduceDesc), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_size_t)]),
+    "dg_reduce_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgReduceDesc), _P]),
+    "dg_readback_reduced": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgReduceDesc), _P]),
+    "dg_readback_reduced_async": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgReduceDesc), _P]),
+    "dg_reduce_device": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgReduceDesc), _P]),
+    "dg_ctx_reduce_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "dg_alloc_host": (_P, [ctypes.c_size_t]),
     "dg_free_host": (None, [_P]),
     "dg_prepare_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int]),
@@ -205,6 +217,35 @@ def _check(rc: int):
     if rc < 0:
         raise DoomGpuError(rc, lib().dg_last_error().decode(errors="replace"))
     return rc
+
+
+def _reduce_desc(desc) -> DgReduceDesc:
+    """A DgReduceDesc as it is, or one from (fx, fy) / (fx, fy, format)."""
+    return desc if isinstance(desc, DgReduceDesc) else DgReduceDesc(int(desc[0]), int(desc[1]), int(desc[2]) if len(desc) > 2 else DG_REDUCE_RGB24, 0)
+
+
+def reduced_size(width: int, height: int, desc):
+    """dg_reduced_size: (oW, oH, bytes per reduced frame) of a width x height frame under desc (a DgReduceDesc, or (fx, fy[, format]))."""
+    w, h, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    _check(lib().dg_reduced_size(width, height, ctypes.byref(_reduce_desc(desc)), ctypes.byref(w), ctypes.byref(h), ctypes.byref(b)))
+    return w.value, h.value, b.value
+
+
+def _reduced_array(count: int, width: int, height: int, d: DgReduceDesc) -> np.ndarray:
+    ow, oh, _ = reduced_size(width, height, d)
+    return np.empty((count, oh, ow) if d.format == DG_REDUCE_GRAY8 else (count, oh, ow, 3), dtype=np.uint8)
+
+
+def reduce_host(frames, desc) -> np.ndarray:
+    """dg_reduce_host: the box downscale on the CPU of frames (n, H, W, 3) uint8; returns (n, oH, oW, 3) or, as gray, (n, oH, oW)."""
+    src = np.ascontiguousarray(frames, dtype=np.uint8)
+    if src.ndim != 4 or src.shape[3] != 3:
+        raise ValueError("frames must be (n, H, W, 3) uint8")
+    d = _reduce_desc(desc)
+    n, h, w, _ = src.shape
+    out = _reduced_array(n, w, h, d)
+    _check(lib().dg_reduce_host(src.ctypes.data_as(_P), w, h, n, ctypes.byref(d), out.ctypes.data_as(_P)))
+    return out
 
 
 def make_view_states(states):
@@ -444,6 +485,28 @@ class Context:
     def readback_async(self, slot: int, first: int, count: int, host_ptr: int):
         """Queue the D2H copy behind the slot's kernels (own copy stream); complete after wait(slot)."""
         _check(lib().dg_readback_async(self._h, slot, first, count, _P(host_ptr)))
+
+    def readback_reduced(self, slot: int, first: int, count: int, desc) -> np.ndarray:
+        """dg_readback_reduced: frames [first, first + count) of the slot, box-downscaled on the GPU; (count, oH, oW, 3) or (count, oH, oW)."""
+        d = _reduce_desc(desc)
+        out = _reduced_array(count, self.width, self.height, d)
+        _check(lib().dg_readback_reduced(self._h, slot, first, count, ctypes.byref(d), out.ctypes.data_as(_P)))
+        return out
+
+    def readback_reduced_async(self, slot: int, first: int, count: int, desc, host_ptr: int):
+        """dg_readback_reduced_async: the downscale and the D2H copy queued behind the slot's kernels; complete after wait(slot)."""
+        _check(lib().dg_readback_reduced_async(self._h, slot, first, count, ctypes.byref(_reduce_desc(desc)), _P(host_ptr)))
+
+    def reduce_device(self, src_ptr: int, width: int, height: int, n_frames: int, desc, dst_ptr: int):
+        """dg_reduce_device: n_frames RGB24 frames at device address src_ptr downscaled into device address dst_ptr (synchronous; a slot's
+        framebuffer_ptr or a tensor's data_ptr(), any alignment).  Touches no slot."""
+        _check(lib().dg_reduce_device(self._h, _P(src_ptr), width, height, n_frames, ctypes.byref(_reduce_desc(desc)), _P(dst_ptr)))
+
+    def reduce_kernel_ms(self) -> float:
+        """dg_ctx_reduce_kernel_ms: GPU time of the last reduce_device call's kernel."""
+        ms = ctypes.c_float()
+        _check(lib().dg_ctx_reduce_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def fallbacks(self) -> dict:
         a, f = ctypes.c_uint64(), ctypes.c_uint64()

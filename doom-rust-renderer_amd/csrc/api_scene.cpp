@@ -1,11 +1,13 @@
 // api_scene.cpp — the entry points of the C-ABI (include/doomgpu.h) that need no GPU: the error string and the version, the scene
-// (dg_scene_*), one frame's lists and map lines on the host, and the recorded walks.  Everything that takes a dg_ctx: context.cpp.
+// (dg_scene_*), one frame's lists and map lines on the host, the recorded walks, and the box downscale on the host (dg_reduced_size,
+// dg_reduce_host).  Everything that takes a dg_ctx: context.cpp.
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "api_common.hpp"
 #include "frontend.hpp"
+#include "reduce_core.h"
 #include "walk.hpp"
 
 using namespace dg;
@@ -165,6 +167,48 @@ int dg_walk_views(dg_walk *w, const float *timestamps, int n, dg_view *out) {
     if (!w || n < 0 || (n > 0 && (!timestamps || !out))) return set_err(DG_ERR_INVALID, "null argument");
     w->locate_host();
     for (int i = 0; i < n; i++) w->view_at(timestamps[i], out[i]);
+    return DG_OK;
+}
+
+int dg_reduced_size(int width, int height, const dg_reduce_desc *desc, int *out_w, int *out_h, size_t *bytes_per_frame) {
+    if (!desc) return set_err(DG_ERR_INVALID, "null argument");
+    if (width < 1 || height < 1) return set_err(DG_ERR_INVALID, "width and height must be positive");
+    if (!reduce_desc_ok(*desc)) return set_err(DG_ERR_INVALID, "reduce descriptor: fx and fy in 1..16, a known format, reserved 0");
+    if (out_w) *out_w = (int)reduce_out_dim((uint32_t)width, desc->fx);
+    if (out_h) *out_h = (int)reduce_out_dim((uint32_t)height, desc->fy);
+    if (bytes_per_frame) *bytes_per_frame = reduce_frame_bytes((uint32_t)width, (uint32_t)height, *desc);
+    return DG_OK;
+}
+
+int dg_reduce_host(const uint8_t *src_rgb24, int width, int height, int n_frames, const dg_reduce_desc *desc, uint8_t *dst) {
+    if (!src_rgb24 || !dst) return set_err(DG_ERR_INVALID, "null argument");
+    if (n_frames < 0) return set_err(DG_ERR_INVALID, "bad frame count");
+    const int rc = dg_reduced_size(width, height, desc, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    const uint32_t W = (uint32_t)width, H = (uint32_t)height, fx = desc->fx, fy = desc->fy;
+    const uint32_t oW = reduce_out_dim(W, fx), oH = reduce_out_dim(H, fy);
+    const bool gray = desc->format == DG_REDUCE_GRAY8;
+    const size_t row = (size_t)3 * W;
+    for (int f = 0; f < n_frames; f++) {
+        const uint8_t *const frame = src_rgb24 + (size_t)f * row * H;
+        for (uint32_t oy = 0; oy < oH; oy++) {
+            uint32_t y0;
+            const uint32_t ny = reduce_box(oy, fy, H, y0);
+            for (uint32_t ox = 0; ox < oW; ox++) {
+                uint32_t x0;
+                const uint32_t nx = reduce_box(ox, fx, W, x0), n = nx * ny, rcp = reduce_rcp(n);
+                uint32_t px[3];
+                for (uint32_t c = 0; c < 3; c++) {
+                    uint32_t s = 0;
+                    for (uint32_t y = y0; y < y0 + ny; y++)
+                        for (uint32_t x = x0; x < x0 + nx; x++) s += frame[(size_t)y * row + (size_t)3 * x + c];
+                    px[c] = reduce_round(s, n, rcp);
+                }
+                if (gray) *dst++ = (uint8_t)reduce_luma(px[0], px[1], px[2]);
+                else { *dst++ = (uint8_t)px[0]; *dst++ = (uint8_t)px[1]; *dst++ = (uint8_t)px[2]; }
+            }
+        }
+    }
     return DG_OK;
 }
 

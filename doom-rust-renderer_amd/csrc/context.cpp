@@ -41,6 +41,7 @@
 #include "kernels.hpp"
 #include "map_kernels.hpp"
 #include "pool.hpp"
+#include "reduce_kernels.hpp"
 #include "scene.hpp"
 #include "slab_layout.h"
 #include "walk.hpp"
@@ -64,10 +65,17 @@ struct Slot {
     // ev_raster has been recorded at least once: slot_sync waits only on an event that has.  Not part of the phase below, because it is
     // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
     bool raster_recorded = false;
-    hipStream_t copy_stream = nullptr;   // dg_readback_async: D2H of this slot's frames while another slot's kernels run
-    uint8_t *copy_out = nullptr;         // pending asynchronous readback (re-issued if the batch has to be redone)
-    int copy_first = 0, copy_count = 0;
+    hipStream_t copy_stream = nullptr;   // dg_readback_async / dg_readback_reduced_async: D2H of this slot's frames while another slot's kernels run
+    // What a readback moves: frames [first, first + count) to host memory `out`, as they are or reduced by `desc` on the way
+    struct Readback {
+        uint8_t *out = nullptr;
+        int first = 0, count = 0;
+        bool reduced = false;
+        dg_reduce_desc desc{};
+    } copy;                              // the pending asynchronous one (issued again if the batch has to be redone)
     bool copy_pending = false;
+    DevPtr<uint8_t> d_reduced;           // reduced readbacks: the kernel's output, allocated by the first one, grown when a later one needs more
+    size_t reduced_cap = 0;
     PinnedPtr<uint8_t> h_lists;   // pinned staging
     DevPtr<uint8_t> d_lists;
     DevPtr<DevRSpan> d_rspans;
@@ -246,6 +254,10 @@ struct dg_ctx {
     const WalkNode *d_walk_nodes = nullptr;
     const WalkLeaf *d_walk_leaves = nullptr;
     hipStream_t wstream = nullptr;
+    // dg_reduce_device: likewise a stream of its own and the events attached to its last call's kernel, created by the first call
+    hipStream_t xstream = nullptr;
+    hipEvent_t ev_reduce0 = nullptr, ev_reduce1 = nullptr;
+    bool reduce_timed = false;
 };
 
 namespace {
@@ -288,6 +300,9 @@ void free_ctx(dg_ctx *c) {
     if (c->kstream) (void)hipStreamDestroy(c->kstream);
     if (c->rstream) (void)hipStreamDestroy(c->rstream);
     if (c->wstream) { (void)hipStreamSynchronize(c->wstream); (void)hipStreamDestroy(c->wstream); }
+    if (c->xstream) { (void)hipStreamSynchronize(c->xstream); (void)hipStreamDestroy(c->xstream); }
+    for (hipEvent_t ev : {c->ev_reduce0, c->ev_reduce1})
+        if (ev) (void)hipEventDestroy(ev);
     delete c;
 }
 
@@ -906,11 +921,39 @@ int redo_overflowed(dg_ctx *c, Slot &s) {
     return make_final(c, s, Copy::Leave);                  // (a host-list batch now: it is waited for, there are no flags to look at)
 }
 
-int enqueue_copy(dg_ctx *c, Slot &s) {
-    const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
-    HIP_TRY(hipStreamWaitEvent(s.copy_stream, s.ev_raster, 0));
-    HIP_TRY(hipMemcpyAsync(s.copy_out, s.d_fb.get() + (size_t)s.copy_first * fsz, (size_t)s.copy_count * fsz, hipMemcpyDeviceToHost, s.copy_stream));
+// Room for `bytes` of reduced frames in the slot's scratch.  It only ever grows, and only when nothing of the slot can be using it:
+// after a sync of the slot's streams.
+int reserve_reduced(Slot &s, size_t bytes) {
+    if (bytes <= s.reduced_cap) return DG_OK;
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    HIP_TRY(hipStreamSynchronize(s.copy_stream));
+    s.reduced_cap = 0;
+    HIP_TRY(hip_alloc(s.d_reduced, bytes));
+    s.reduced_cap = bytes;
     return DG_OK;
+}
+
+// Readback r of the slot's frames on `stream`: the D2H copy of the frames themselves, or dg_reduce into the slot's scratch
+// (reserve_reduced) and the copy of that.  The caller has ordered `stream` behind the slot's kernels.
+int issue_readback(dg_ctx *c, Slot &s, const Slot::Readback &r, hipStream_t stream) {
+    const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
+    const uint8_t *const frames = s.d_fb.get() + (size_t)r.first * fsz;
+    if (!r.reduced) {
+        HIP_TRY(hipMemcpyAsync(r.out, frames, (size_t)r.count * fsz, hipMemcpyDeviceToHost, stream));
+        return DG_OK;
+    }
+    if (r.count == 0) return DG_OK;
+    const size_t bytes = (size_t)r.count * reduce_frame_bytes((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, r.desc);
+    if (bytes > s.reduced_cap) return set_err(DG_ERR_INVALID, "reduced readback: no scratch reserved");
+    HIP_TRY(launch_reduce(frames, c->cfg.width, c->cfg.height, r.count, r.desc, s.d_reduced.get(), stream));
+    HIP_TRY(hipMemcpyAsync(r.out, s.d_reduced.get(), bytes, hipMemcpyDeviceToHost, stream));
+    return DG_OK;
+}
+
+// The slot's pending readback onto its copy stream, behind the slot's kernels.
+int enqueue_copy(dg_ctx *c, Slot &s) {
+    HIP_TRY(hipStreamWaitEvent(s.copy_stream, s.ev_raster, 0));
+    return issue_readback(c, s, s.copy, s.copy_stream);
 }
 
 // DG_FE_AUTO's measurement of the GPU side: the span of a finished submission's kernels (never waits)
@@ -1194,17 +1237,87 @@ int dg_wait(dg_ctx *c, int slot) {
     return make_final(c, c->slots[(size_t)slot], Copy::Complete);
 }
 
-int dg_readback_async(dg_ctx *c, int slot, int first, int count, uint8_t *out) {
+// dg_readback_async and dg_readback_reduced_async (desc != nullptr, checked): the readback becomes the slot's pending one.
+static int readback_async(dg_ctx *c, int slot, int first, int count, const dg_reduce_desc *desc, uint8_t *out) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     if (s.copy_pending) return set_err(DG_ERR_INVALID, "the slot already has a readback in flight (dg_wait it first)");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    s.copy_out = out; s.copy_first = first; s.copy_count = count;
+    Slot::Readback r;
+    r.out = out; r.first = first; r.count = count;
+    if (desc) {
+        r.reduced = true; r.desc = *desc;
+        rc = reserve_reduced(s, (size_t)count * reduce_frame_bytes((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, *desc));
+        if (rc) return rc;
+    }
+    s.copy = r;
     rc = enqueue_copy(c, s);
     if (rc) return rc;
     s.copy_pending = true;
+    return DG_OK;
+}
+
+// What the reduced readbacks check before anything else.
+static int check_reduce_desc(const dg_reduce_desc *desc) {
+    if (!desc) return set_err(DG_ERR_INVALID, "null argument");
+    if (!reduce_desc_ok(*desc)) return set_err(DG_ERR_INVALID, "reduce descriptor: fx and fy in 1..16, a known format, reserved 0");
+    return DG_OK;
+}
+
+int dg_readback_async(dg_ctx *c, int slot, int first, int count, uint8_t *out) { return readback_async(c, slot, first, count, nullptr, out); }
+
+int dg_readback_reduced_async(dg_ctx *c, int slot, int first, int count, const dg_reduce_desc *desc, uint8_t *out) {
+    const int rc = check_reduce_desc(desc);
+    return rc ? rc : readback_async(c, slot, first, count, desc, out);
+}
+
+int dg_readback_reduced(dg_ctx *c, int slot, int first, int count, const dg_reduce_desc *desc, uint8_t *out) {
+    int rc = check_reduce_desc(desc);
+    if (!rc) rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
+    if (count == 0) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // (a pending asynchronous reduced readback owns the slot's scratch: it is completed first)
+    rc = make_final(c, s, s.copy_pending && s.copy.reduced ? Copy::Complete : Copy::Leave);
+    if (rc) return rc;
+    Slot::Readback r;
+    r.out = out; r.first = first; r.count = count; r.reduced = true; r.desc = *desc;
+    rc = reserve_reduced(s, (size_t)count * reduce_frame_bytes((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, *desc));
+    if (rc) return rc;
+    rc = issue_readback(c, s, r, s.stream);
+    if (rc) return rc;
+    HIP_TRY(slot_sync(s));
+    return DG_OK;
+}
+
+int dg_reduce_device(dg_ctx *c, const void *src, int width, int height, int n_frames, const dg_reduce_desc *desc, void *dst) {
+    if (!c || !src || !dst) return set_err(DG_ERR_INVALID, "null argument");
+    const int rc = check_reduce_desc(desc);
+    if (rc) return rc;
+    if (width < 1 || height < 1 || width > 16384 || height > 16384 || n_frames < 0) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384], n_frames >= 0");
+    if (n_frames == 0) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!c->xstream) HIP_TRY(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
+    if (!c->ev_reduce0) HIP_TRY(hipEventCreate(&c->ev_reduce0));
+    if (!c->ev_reduce1) HIP_TRY(hipEventCreate(&c->ev_reduce1));
+    c->reduce_timed = false;
+    hipError_t e = launch_reduce(static_cast<const uint8_t *>(src), width, height, n_frames, *desc, static_cast<uint8_t *>(dst), c->xstream, c->ev_reduce0, c->ev_reduce1);
+    const hipError_t es = hipStreamSynchronize(c->xstream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_reduce_device: ") + hipGetErrorString(e));
+    c->reduce_timed = true;
+    return DG_OK;
+}
+
+int dg_ctx_reduce_kernel_ms(dg_ctx *c, float *ms) {
+    if (!c || !ms) return set_err(DG_ERR_INVALID, "null argument");
+    if (!c->reduce_timed) return set_err(DG_ERR_INVALID, "no dg_reduce_device call has launched yet");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipEventElapsedTime(ms, c->ev_reduce0, c->ev_reduce1));
     return DG_OK;
 }
 

@@ -239,6 +239,45 @@ int dg_readback_async(dg_ctx *ctx, int slot, int first, int count, uint8_t *rgb2
  * thousands of large frames by 8 bytes each.  Waits for the slot like dg_readback. */
 int dg_frame_checksums(dg_ctx *ctx, int slot, int first, int count, uint64_t *out);
 
+/* ---- reduced-size frames ------------------------------------------------------------------------------------ */
+/* Frame sink for small pictures (thumbnails, a contact sheet, observation tensors): a box downscale on the GPU, so that 1/(fx*fy)
+ * of the bytes cross PCIe (a third of that as gray).  Exact, integer only:
+ *   oW = ceil(W / fx), oH = ceil(H / fy); output pixel (ox, oy) covers source columns [ox*fx, min(W, ox*fx + fx)) and rows likewise, so a
+ *   box at the right or bottom edge covers only the n pixels that exist;
+ *   per channel, s = the sum of the box's bytes and  out = floor((2*s + n) / (2*n))  (round to nearest, halves up);
+ *   DG_REDUCE_GRAY8 = (77*r + 150*g + 29*b + 128) >> 8  of those three rounded bytes.
+ * Output: frame-major, rows top down, tightly packed — 3*oW*oH bytes per frame (r, g, b as in the source) or oW*oH.  fx = fy = 1
+ * with DG_REDUCE_RGB24 is a copy. */
+enum { DG_REDUCE_RGB24 = 0, DG_REDUCE_GRAY8 = 1 };
+typedef struct dg_reduce_desc {
+    uint32_t fx, fy;             /* box size in source pixels, each 1..16 */
+    uint32_t format;             /* DG_REDUCE_RGB24 or DG_REDUCE_GRAY8 */
+    uint32_t reserved;           /* must be 0 */
+} dg_reduce_desc;
+/* Size of a width x height frame reduced by desc: *out_w, *out_h and the bytes of one reduced frame (each pointer may be NULL).
+ * Needs no ctx and no GPU.  DG_ERR_INVALID: a NULL desc, width or height < 1, a factor outside 1..16, an unknown format, reserved != 0. */
+int dg_reduced_size(int width, int height, const dg_reduce_desc *desc, int *out_w, int *out_h, size_t *bytes_per_frame);
+/* The same arithmetic on the CPU: n_frames RGB24 frames of width x height at src_rgb24 (host memory) into dst (n_frames reduced
+ * frames).  For callers without a GPU, and what the GPU paths below are tested against.  DG_ERR_INVALID as dg_reduced_size, and for a
+ * NULL src_rgb24 / dst or n_frames < 0. */
+int dg_reduce_host(const uint8_t *src_rgb24, int width, int height, int n_frames, const dg_reduce_desc *desc, uint8_t *dst);
+/* dg_readback with the downscale in front of the copy: frames [first, first+count) of the slot are reduced on the GPU into a scratch
+ * buffer of the slot (allocated by the slot's first reduced readback, grown when a later one needs more) and count reduced frames are
+ * copied to dst_host.  Waits for the slot like dg_readback.  DG_ERR_INVALID: a NULL argument, a bad descriptor, a bad frame range. */
+int dg_readback_reduced(dg_ctx *ctx, int slot, int first, int count, const dg_reduce_desc *desc, uint8_t *dst_host);
+/* The same without waiting, as dg_readback_async: the kernel and the copy are queued behind the slot's kernels on the slot's copy
+ * stream.  dst_host should be page-locked and is complete after dg_wait(slot); whatever completes a dg_readback_async first completes
+ * this one too.  One readback in flight per slot, plain or reduced: a second one is DG_ERR_INVALID. */
+int dg_readback_reduced_async(dg_ctx *ctx, int slot, int first, int count, const dg_reduce_desc *desc, uint8_t *dst_host);
+/* Device to device, synchronous, on a stream of the ctx that belongs to no slot: n_frames RGB24 frames of width x height at src_device
+ * into dst_device, both on the ctx's device — dg_slot_framebuffer of a finished slot, a tensor's data pointer — and at any alignment.
+ * Touches no slot: the route to tensors without a host round trip.  DG_ERR_INVALID: a NULL argument, a bad descriptor, width or
+ * height outside [1, 16384], n_frames < 0. */
+int dg_reduce_device(dg_ctx *ctx, const void *src_device, int width, int height, int n_frames, const dg_reduce_desc *desc, void *dst_device);
+/* GPU time of the last dg_reduce_device call's kernel in milliseconds, from events attached to the dispatch itself (the call's
+ * launch and wait are not in it).  DG_ERR_INVALID: a NULL argument, no dg_reduce_device call that launched yet. */
+int dg_ctx_reduce_kernel_ms(dg_ctx *ctx, float *ms);
+
 /* Pre-built list path used by benchmarks that want the raster kernels alone: build + upload lists for n views
  * into the slot (untimed), then dg_replay_slot re-runs only the device work (setup + raster kernels). */
 int dg_prepare_views(dg_ctx *ctx, int slot, const dg_view *views, int n);

@@ -45,6 +45,9 @@ pub struct dg_frame_lists {
 /// One line of a 2-D map frame (dg_map_lines): rgb = r | g << 8 | b << 16.
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct dg_map_line { pub x0: i32, pub y0: i32, pub x1: i32, pub y1: i32, pub rgb: u32 }
+/// Box downscale of a reduced readback (dg_readback_reduced): fx, fy in 1..16, format 0 = RGB24, 1 = GRAY8.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct dg_reduce_desc { pub fx: u32, pub fy: u32, pub format: u32, pub reserved: u32 }
 pub const DG_FE_MAP: i32 = 4;              // dg_timing.front_end of a map submission
 pub const DG_WALL_ANIMATE: u32 = 1;         // dg_scene_set_wall_effects flags
 pub const DG_WALL_SCROLL: u32 = 2;
@@ -87,6 +90,7 @@ extern "C" {
     pub fn dg_render_views(ctx: *mut dg_ctx, views: *const dg_view, n: c_int, rgb24_out: *mut u8) -> c_int;
     pub fn dg_draw_lists(ctx: *mut dg_ctx, slot: c_int, frames: *const dg_frame_lists, n: c_int, rgb24_out: *mut u8) -> c_int;
     pub fn dg_frame_checksums(ctx: *mut dg_ctx, slot: c_int, first: c_int, count: c_int, out: *mut u64) -> c_int;
+    pub fn dg_readback_reduced(ctx: *mut dg_ctx, slot: c_int, first: c_int, count: c_int, desc: *const dg_reduce_desc, dst_host: *mut u8) -> c_int;
     pub fn dg_map_lines(s: *const dg_scene, width: c_int, height: c_int, view: *const dg_view, out: *mut dg_map_line, cap: c_int) -> c_int;
     pub fn dg_submit_map_views(ctx: *mut dg_ctx, slot: c_int, views: *const dg_view, n: c_int) -> c_int;
     pub fn dg_render_map_views(ctx: *mut dg_ctx, views: *const dg_view, n: c_int, rgb24_out: *mut u8) -> c_int;
