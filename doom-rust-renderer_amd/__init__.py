@@ -23,6 +23,8 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "doomgpu.h")
 DG_OK, DG_ERR_INVALID, DG_ERR_NO_DEVICE, DG_ERR_HIP, DG_ERR_WAD, DG_ERR_RENDER, DG_ERR_CAPACITY = 0, -1, -2, -3, -4, -5, -6
 DG_FE_AUTO, DG_FE_HOST, DG_FE_DEVICE, DG_FE_DEVICE_SEGS = 0, 1, 2, 3
 DG_FE_MAP = 4   # dg_timing.front_end of a 2-D map submission
+DG_FE_DEPTH = 5  # dg_timing.front_end of a depth submission
+DG_KIND_NONE, DG_KIND_COLUMN, DG_KIND_FLAT, DG_KIND_SKY = 0, 1, 2, 3   # the kind plane of a depth frame
 DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
 DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
@@ -185,6 +187,11 @@ _SIGNATURES = {
     "dg_map_lines": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgMapLine), ctypes.c_int]),
     "dg_submit_map_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int]),
     "dg_render_map_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, _P]),
+    "dg_submit_depth_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int]),
+    "dg_render_depth_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int, _P, _P]),
+    "dg_depth_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P, _P]),
+    "dg_readback_depth": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "dg_depth_lists_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P, _P]),
     "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
     "dg_walk_free": (None, [_P]),
     "dg_walk_tics": (ctypes.c_int, [_P]),
@@ -246,6 +253,22 @@ def reduce_host(frames, desc) -> np.ndarray:
     out = _reduced_array(n, w, h, d)
     _check(lib().dg_reduce_host(src.ctypes.data_as(_P), w, h, n, ctypes.byref(d), out.ctypes.data_as(_P)))
     return out
+
+
+def _depth_planes(n: int, height: int, width: int, distance: bool = True, kind: bool = True):
+    """The two planes of n depth frames to fill, and the pointers to hand over (None for a plane that is not wanted)."""
+    d = np.empty((n, height, width), dtype=np.int16) if distance else None
+    k = np.empty((n, height, width), dtype=np.uint8) if kind else None
+    return d, k, (d.ctypes.data_as(_P) if distance else None), (k.ctypes.data_as(_P) if kind else None)
+
+
+def depth_lists_host(scene, width: int, height: int, frames, distance: bool = True, kind: bool = True):
+    """dg_depth_lists_host: the depth planes of caller-built lists on the CPU (no ctx, no GPU); returns (int16 [n,H,W], uint8 [n,H,W]),
+    None for a plane that was not asked for."""
+    n = len(frames)
+    d, k, dp, kp = _depth_planes(n, height, width, distance, kind)
+    _check(lib().dg_depth_lists_host(scene._h, width, height, frames, n, dp, kp))
+    return d, k
 
 
 def make_view_states(states):
@@ -461,6 +484,30 @@ class Context:
         out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
         _check(lib().dg_render_views_state(self._h, views, states, n, out.ctypes.data_as(_P)))
         return out
+
+    def submit_depth(self, slot: int, views, n=None, states=None):
+        """dg_submit_depth_views: depth + surface-kind frames into the slot, asynchronously (always through the host list path)."""
+        _check(lib().dg_submit_depth_views(self._h, slot, views, states, len(views) if n is None else n))
+
+    def render_depth(self, views, states=None, distance: bool = True, kind: bool = True):
+        """dg_render_depth_views: synchronous through slot 0; returns (int16 [n,H,W] distance, uint8 [n,H,W] kind)."""
+        n = len(views)
+        d, k, dp, kp = _depth_planes(n, self.height, self.width, distance, kind)
+        _check(lib().dg_render_depth_views(self._h, views, states, n, dp, kp))
+        return d, k
+
+    def depth_lists(self, slot: int, frames, distance: bool = True, kind: bool = True):
+        """dg_depth_lists: the depth planes of caller-built lists (synchronous); returns (distance, kind)."""
+        n = len(frames)
+        d, k, dp, kp = _depth_planes(n, self.height, self.width, distance, kind)
+        _check(lib().dg_depth_lists(self._h, slot, frames, n, dp, kp))
+        return d, k
+
+    def readback_depth(self, slot: int, first: int, count: int, distance: bool = True, kind: bool = True):
+        """dg_readback_depth: the planes of frames [first, first + count) of a depth slot; returns (distance, kind)."""
+        d, k, dp, kp = _depth_planes(count, self.height, self.width, distance, kind)
+        _check(lib().dg_readback_depth(self._h, slot, first, count, dp, kp))
+        return d, k
 
     def wait(self, slot: int):
         _check(lib().dg_wait(self._h, slot))

@@ -1,11 +1,13 @@
 // api_scene.cpp — the entry points of the C-ABI (include/doomgpu.h) that need no GPU: the error string and the version, the scene
-// (dg_scene_*), one frame's lists and map lines on the host, the recorded walks, and the box downscale on the host (dg_reduced_size,
-// dg_reduce_host).  Everything that takes a dg_ctx: context.cpp.
+// (dg_scene_*), one frame's lists and map lines on the host, the recorded walks, the box downscale on the host (dg_reduced_size,
+// dg_reduce_host) and the depth planes of caller-built lists on the host (dg_depth_lists_host).  Everything that takes a dg_ctx: context.cpp.
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "api_common.hpp"
+#include "binner.hpp"
+#include "depth_core.h"
 #include "frontend.hpp"
 #include "reduce_core.h"
 #include "walk.hpp"
@@ -208,6 +210,48 @@ int dg_reduce_host(const uint8_t *src_rgb24, int width, int height, int n_frames
                 else { *dst++ = (uint8_t)px[0]; *dst++ = (uint8_t)px[1]; *dst++ = (uint8_t)px[2]; }
             }
         }
+    }
+    return DG_OK;
+}
+
+// The binner (the same column-major, draw-ordered spans the GPU walks) and depth_core.h per pixel; here the spans of a column are laid
+// on in draw order, each row of a span that writes overwriting what is there — dg_depth_tiles reads the same order backwards.
+int dg_depth_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, int n, int16_t *distance, uint8_t *kind) {
+    if (!s || !frames) return set_err(DG_ERR_INVALID, "null argument");
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384]");
+    if (n < 0) return set_err(DG_ERR_INVALID, "bad frame count");
+    const Scene &sc = *s->sc;
+    const FrameConsts fk = make_consts(width, height);
+    const DevConsts dk{fk.ARC, fk.GCFX, fk.CFX, fk.CFY, width, height};
+    const BitmapInfo &sky = sc.bitmaps[(size_t)sc.sky_bitmap];
+    const DevScene ds{nullptr, nullptr, sc.texel_idx.data(), sc.texel_opq.data(), nullptr, sky.texel_off, sky.w, sky.h, sky.has_holes};
+    const size_t W = (size_t)width, px = W * (size_t)height;
+    BinnedFrame bf;
+    std::string err;
+    for (int f = 0; f < n; f++) {
+        dg_frame_lists fl = frames[f];
+        fill_view_trig(fl.view);
+        const int rc = bin_frame(sc, fk, fl, bf, err);
+        if (rc) return set_err(rc, "frame " + std::to_string(f) + ": " + err);
+        bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
+        int16_t *const dist = distance ? distance + (size_t)f * px : nullptr;
+        uint8_t *const kd = kind ? kind + (size_t)f * px : nullptr;
+        for (size_t i = 0; i < px; i++) {
+            if (dist) dist[i] = (int16_t)DEPTH_FAR;
+            if (kd) kd[i] = (uint8_t)KIND_NONE;
+        }
+        for (size_t x = 0; x < W; x++)
+            for (uint32_t j = bf.col_off[x]; j < bf.col_off[x + 1]; j++) {
+                const DevSpan &sp = bf.spans[j];
+                const DevRSpan r = depth_resolve_span(sp, bf.hdr, bf.walls.data(), bf.planes.data(), ds, dk);
+                for (int32_t y = sp.ctop; y <= sp.cbot; y++) {
+                    int32_t d;
+                    uint32_t k;
+                    if (!depth_span_writes(r, ds, dk, y, d, k)) continue;
+                    if (dist) dist[(size_t)y * W + x] = (int16_t)d;
+                    if (kd) kd[(size_t)y * W + x] = (uint8_t)k;
+                }
+            }
     }
     return DG_OK;
 }

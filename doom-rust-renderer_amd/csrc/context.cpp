@@ -11,6 +11,7 @@
 //             DG_FE_DEVICE: record slab [DevFrame x F | FeFrame x F | FePart.. | FeSprite.. | behind bits.. | sky slot -> part.. | column bins..] (one H2D copy),
 //             col_off F*(W+1) written by dg_fe_finalize, 2F status words (overflow flags, span totals)
 //             2-D map view: the arrow lines of the batch (MapSeg x 3F) at the start of the list slab
+//             depth frames (DG_FE_DEPTH): the host lists in the list slab; the framebuffer slab holds int16 distance[F][H][W], then uint8 kind[F][H][W]
 //   per ctx : 2-D map view layer 3*W*H bytes RGB24 (allocated by the first map submission, rebuilt after every dg_upload_scene)
 //             DG_FE_DEVICE column scratch [F][slot][W]: compact spans 16 B (48 slots), wall-record columns 8 B (48 slots),
 //             counts, sky event bits — shared by the slots because their kernels run back to back
@@ -32,6 +33,7 @@
 #include "../../include/doomgpu.h"
 #include "api_common.hpp"
 #include "binner.hpp"
+#include "depth_kernels.hpp"
 #include "fe_kernels.hpp"
 #include "fs_kernels.hpp"
 #include "light_fx_kernels.hpp"
@@ -113,7 +115,8 @@ struct Slot {
     LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
     MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
     // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
-    // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too) or DG_FE_MAP (2-D map frames: arrow lines at the start of d_lists)
+    // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP (2-D map frames: arrow lines at the start of d_lists) or
+    // DG_FE_DEPTH (host lists walked by dg_depth_tiles: the framebuffer slab holds the two planes, not RGB24)
     int32_t front_end = DG_FE_HOST;
     // A new submission of n frames through front end fe, `bytes` of lists or records uploaded for it (span statistics: the host list path's alone)
     void describe(int32_t fe, int n, uint64_t bytes, uint64_t walls, uint64_t planes) {
@@ -122,6 +125,7 @@ struct Slot {
     }
     bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
     bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
+    bool holds_depth() const { return front_end == DG_FE_DEPTH && phase != Phase::Empty; }     // the framebuffer slab is the two depth planes
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
     bool map_built = false;       // a map submission whose enqueue built the ctx's map layer (ev_start .. ev_setup time that)
     std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
@@ -371,8 +375,9 @@ void fill_walk_params(dg_ctx *c, Slot &s, int n) {
     s.P.walls = nullptr; s.P.planes = nullptr; s.P.spans = nullptr;
 }
 
-// Build + bin the lists of n views in parallel, pack them into the slot's pinned slab, fill slot.P.
-int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr) {
+// Build + bin the lists of n views in parallel, pack them into the slot's pinned slab, fill slot.P.  fe: what the submission is described
+// as — DG_FE_HOST, or DG_FE_DEPTH when dg_depth_tiles will walk the lists.
+int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, int32_t fe = DG_FE_HOST) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -412,7 +417,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
     c->pool->parallel_for(n, [&](int i, int) { pack_binned(s.h_lists.get(), L, c->binned[(size_t)i], (size_t)i, (size_t)W); });
     fill_raster_params(c, s, n);
     point_at_lists(s.P, s.d_lists.get(), L);
-    s.describe(DG_FE_HOST, n, L.total, walls, planes);
+    s.describe(fe, n, L.total, walls, planes);
     s.max_spans = max_spans; s.n_spans = spans; s.covered = covered;
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), L.total, hipMemcpyHostToDevice, s.stream));
@@ -1029,6 +1034,40 @@ int check_slot(dg_ctx *c, int slot) {
     return DG_OK;
 }
 
+// The calls that read the framebuffer slab as RGB24 frames, or run the colour kernels again, on a slot whose last submission was depth.
+int refuse_depth(const Slot &s, const char *what) {
+    if (!s.holds_depth()) return DG_OK;
+    return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds depth planes, not RGB24 frames (dg_readback_depth)");
+}
+
+// Slot `slot` for a depth submission of n views (or of the caller's lists): always the host list path, whatever front end the ctx has;
+// dg_depth_tiles on the slot's own stream, behind the upload.
+int submit_depth(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    Slot &s = c->slots[(size_t)slot];
+    int rc = take_slot(c, s);
+    if (rc) return rc;
+    rc = build_batch_host(c, s, views, given, n, states, DG_FE_DEPTH);
+    if (rc) return rc;
+    const size_t plane = (size_t)n * (size_t)c->cfg.width * (size_t)c->cfg.height;
+    const hipError_t e = launch_depth(s.P, reinterpret_cast<int16_t *>(s.d_fb.get()), s.d_fb.get() + 2 * plane, s.stream, s.ev_rstart, s.ev_raster);
+    if (e != hipSuccess) {                                // (as a failed enqueue_kernels: the slot is left empty)
+        s.reset();
+        return set_err(DG_ERR_HIP, std::string("launch_depth: ") + hipGetErrorString(e));
+    }
+    s.harvested = true;
+    s.raster_recorded = true;
+    s.phase = Slot::Phase::Queued;
+    return DG_OK;
+}
+
+int check_view_states(const dg_view_state *states, int n) {
+    if (states)
+        for (int i = 0; i < n; i++)
+            if ((states[i].n_lights && !states[i].lights) || (states[i].n_mobjs && !states[i].mobjs)) return set_err(DG_ERR_INVALID, "view state with a null array");
+    return DG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1224,9 +1263,8 @@ int dg_submit_views_state(dg_ctx *c, int slot, const dg_view *views, const dg_vi
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
-    if (states)
-        for (int i = 0; i < n; i++)
-            if ((states[i].n_lights && !states[i].lights) || (states[i].n_mobjs && !states[i].mobjs)) return set_err(DG_ERR_INVALID, "view state with a null array");
+    rc = check_view_states(states, n);
+    if (rc) return rc;
     return submit(c, slot, views, nullptr, n, states);
 }
 
@@ -1242,6 +1280,7 @@ static int readback_async(dg_ctx *c, int slot, int first, int count, const dg_re
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
+    if ((rc = refuse_depth(s, desc ? "dg_readback_reduced_async" : "dg_readback_async"))) return rc;
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     if (s.copy_pending) return set_err(DG_ERR_INVALID, "the slot already has a readback in flight (dg_wait it first)");
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -1278,6 +1317,7 @@ int dg_readback_reduced(dg_ctx *c, int slot, int first, int count, const dg_redu
     if (!rc) rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
+    if ((rc = refuse_depth(s, "dg_readback_reduced"))) return rc;
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     if (count == 0) return DG_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -1345,6 +1385,7 @@ int dg_readback(dg_ctx *c, int slot, int first, int count, uint8_t *out) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
+    if ((rc = refuse_depth(s, "dg_readback"))) return rc;
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
@@ -1359,6 +1400,7 @@ int dg_frame_checksums(dg_ctx *c, int slot, int first, int count, uint64_t *out)
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
+    if ((rc = refuse_depth(s, "dg_frame_checksums"))) return rc;
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad frame range");
     if (count == 0) return DG_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -1409,6 +1451,7 @@ int dg_replay_slot(dg_ctx *c, int slot) {
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
     if (s.phase == Slot::Phase::Empty) return set_err(DG_ERR_INVALID, "slot has no prepared lists");
+    if ((rc = refuse_depth(s, "dg_replay_slot"))) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
     // A dg_readback_async may still be reading the framebuffer these kernels are about to overwrite, and a column-walk submission that
     // was never waited for has its overflow flags looked at before the walk clears them.  A host-list submission still in flight is not
@@ -1424,6 +1467,51 @@ int dg_draw_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, int n, uint
     if (rc) return rc;
     if (!frames) return set_err(DG_ERR_INVALID, "null frames");
     return read_or_wait(c, slot, submit(c, slot, nullptr, frames, n, nullptr), n, out);
+}
+
+int dg_submit_depth_views(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, int n) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!views) return set_err(DG_ERR_INVALID, "null views");
+    rc = check_view_states(states, n);
+    if (rc) return rc;
+    return submit_depth(c, slot, views, nullptr, n, states);
+}
+
+int dg_readback_depth(dg_ctx *c, int slot, int first, int count, int16_t *distance, uint8_t *kind) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.holds_depth()) return set_err(DG_ERR_INVALID, "dg_readback_depth: the slot's last submission is not a depth submission");
+    if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
+    if (count == 0) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    rc = make_final(c, s, Copy::Leave);
+    if (rc) return rc;
+    const size_t px = (size_t)c->cfg.width * (size_t)c->cfg.height;
+    const int16_t *const d_dist = reinterpret_cast<const int16_t *>(s.d_fb.get());
+    const uint8_t *const d_kind = s.d_fb.get() + 2 * (size_t)s.n_frames * px;
+    if (distance) HIP_TRY(hipMemcpyAsync(distance, d_dist + (size_t)first * px, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream));
+    if (kind) HIP_TRY(hipMemcpyAsync(kind, d_kind + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(slot_sync(s));
+    return DG_OK;
+}
+
+// The synchronous depth calls' tail, given what their submission returned: the n frames' planes into the outputs, or just its end.
+static int read_depth_or_wait(dg_ctx *c, int slot, int rc, int n, int16_t *distance, uint8_t *kind) {
+    if (rc) return rc;
+    return distance || kind ? dg_readback_depth(c, slot, 0, n, distance, kind) : dg_wait(c, slot);
+}
+
+int dg_render_depth_views(dg_ctx *c, const dg_view *views, const dg_view_state *states, int n, int16_t *distance, uint8_t *kind) {
+    return read_depth_or_wait(c, 0, dg_submit_depth_views(c, 0, views, states, n), n, distance, kind);
+}
+
+int dg_depth_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, int n, int16_t *distance, uint8_t *kind) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!frames) return set_err(DG_ERR_INVALID, "null frames");
+    return read_depth_or_wait(c, slot, submit_depth(c, slot, nullptr, frames, n, nullptr), n, distance, kind);
 }
 
 int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
@@ -1548,7 +1636,7 @@ int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
     std::memset(out, 0, sizeof *out);
     out->front_end = s.front_end;
     HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
-    if (s.front_end != DG_FE_MAP || s.map_built) {        // (a map submission has a front-end half only when it built the map layer)
+    if (s.front_end != DG_FE_DEPTH && (s.front_end != DG_FE_MAP || s.map_built)) {   // (a map submission has a front-end half only when it built the map layer, a depth submission none)
         HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
         HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));
     } else {

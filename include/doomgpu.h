@@ -337,6 +337,45 @@ int dg_draw_lists(dg_ctx *ctx, int slot, const dg_frame_lists *frames, int n, ui
  * until the next dg_build_lists call on the same thread. */
 int dg_build_lists(const dg_scene *s, int width, int height, const dg_view *view, dg_frame_lists *out);
 
+/* ---- depth and surface-kind frames --------------------------------------------------------------------------------------- */
+/* The third picture of a view next to the screen and the 2-D map: per pixel, the `distance: i16` the reference hands to diminish_color
+ * for the draw call that wrote the pixel last (bitmap_render.rs:190-208), and which kind of draw call that was.  Both planes are exact —
+ * the reference's own arithmetic, no tolerance — and follow every rule of the colour frame: draw order (the later Pixels::set wins),
+ * transparent texels write nothing (bitmap_render.rs:265; a sky bitmap with holes likewise) so the pixel keeps its earlier owner, the
+ * row clamps, the `bottom - top <= 1` skip of draw_visplane (visplanes.rs:99, not for sky), columns at x >= W dropped.
+ *   uint8_t kind[H][W]        DG_KIND_NONE    never written (Pixels::new zero)
+ *                             DG_KIND_COLUMN  render_vertical_bitmap_line: inline wall, masked wall, sprite
+ *                             DG_KIND_FLAT    draw_visplane
+ *                             DG_KIND_SKY     draw_sky (also where the colour frame is black because the reference would index outside the sky bitmap)
+ *   int16_t distance[H][W]    DG_KIND_COLUMN: z of bitmap_render.rs:251;  DG_KIND_FLAT: `wx as i16`, wx = GAME_CAMERA_FOCUS_X * wz / vy
+ *                             (visplanes.rs:113,126; an IEEE quotient: the vy == 0 row gives 32767, -32768 or 0 by the `as` rules);
+ *                             DG_KIND_NONE and DG_KIND_SKY: 32767, so that a caller who ignores `kind` still sees "far".
+ * Negative and saturated distances are stored as they are; light levels and full_bright do not enter.
+ * Layout in the slot's framebuffer slab (dg_slot_framebuffer; 3*W*H bytes per frame is exactly what the two planes need): for a
+ * submission of n frames  int16 distance[n][H][W]  at the slab's base, then  uint8 kind[n][H][W]  at byte offset 2*n*W*H.
+ * A depth submission always takes the host list route (what dg_draw_lists consumes), whatever front end the ctx was created with: the
+ * device column walk's records carry no z.  Its rate is therefore bounded by host list generation (dg_timing.host_ms). */
+enum { DG_KIND_NONE = 0, DG_KIND_COLUMN = 1, DG_KIND_FLAT = 2, DG_KIND_SKY = 3 };
+/* dg_timing.front_end of a depth submission; never a dg_config.front_end. */
+enum { DG_FE_DEPTH = 5 };
+/* Asynchronous, like dg_submit_views_state (states may be NULL): wall effects, light effects, map-object thinkers and per-view snapshots
+ * apply exactly as to a colour frame.  On a depth slot dg_wait, dg_slot_timing (front_end = DG_FE_DEPTH, raster_ms = dg_depth_tiles,
+ * setup_ms = 0), dg_slot_framebuffer, dg_upload_scene and every new submission work as usual; dg_readback(_async),
+ * dg_readback_reduced(_async), dg_frame_checksums and dg_replay_slot return DG_ERR_INVALID (the planes are not RGB24) and leave the planes
+ * intact.  Capacity errors are the host list path's (DG_ERR_CAPACITY). */
+int dg_submit_depth_views(dg_ctx *ctx, int slot, const dg_view *views, const dg_view_state *states, int n);
+/* Synchronous, slot 0: n*W*H int16 into distance and n*W*H bytes into kind (host memory); either may be NULL. */
+int dg_render_depth_views(dg_ctx *ctx, const dg_view *views, const dg_view_state *states, int n, int16_t *distance, uint8_t *kind);
+/* Synchronous twin of dg_draw_lists for caller-built lists. */
+int dg_depth_lists(dg_ctx *ctx, int slot, const dg_frame_lists *frames, int n, int16_t *distance, uint8_t *kind);
+/* D2H copy of the planes of frames [first, first+count) of a depth slot; either output may be NULL; count = 0 does nothing.  Waits for
+ * the slot like dg_readback.  DG_ERR_INVALID: a bad range, a slot whose last submission is not a depth submission. */
+int dg_readback_depth(dg_ctx *ctx, int slot, int first, int count, int16_t *distance, uint8_t *kind);
+/* The same planes on the CPU for caller-built lists (dg_build_lists output, or hand-made): needs no ctx and no GPU, and is what the GPU
+ * path is tested against.  DG_ERR_INVALID: a NULL scene or frames, width or height outside [1, 16384], n < 0, malformed lists;
+ * DG_ERR_RENDER / DG_ERR_CAPACITY as dg_draw_lists.  Either output may be NULL. */
+int dg_depth_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, int n, int16_t *distance, uint8_t *kind);
+
 /* ---- 2-D map view (reference: Game::render with viewing_map, src/game.rs:491-499, 229-309) --------------------------------- */
 /* What the window holds after render() in map mode, RGB24 like every frame: black; every linedef without DONTDRAW (flags & 128) in
  * LINEDEFS order, yellow (255, 255, 0) when TWOSIDED (flags & 4) else red (255, 0, 0); then the player arrow in yellow: P->E, R->E, L->E.
@@ -401,7 +440,8 @@ int  dg_ctx_locate_walks(dg_ctx *ctx, dg_walk *const *walks, int n_walks);
 const char *dg_last_error(void); /* thread-local message of the last failing call */
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
- * (it marks the library in which dg_version started to carry the number).  A caller built against another ABI must not call on. */
+ * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
+ * the reduced readbacks, the depth frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
@@ -411,7 +451,7 @@ typedef struct dg_timing {
     float host_ms;            /* host list generation + binning + packing of that submission (wall clock) */
     uint64_t n_spans, n_frames, covered_pixels;
     uint64_t n_walls, n_planes, list_bytes; /* drawn records / visplanes, bytes of lists copied to HBM */
-    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS: what that submission actually used; with DG_FE_DEVICE setup_ms is
+    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH): what that submission actually used; with DG_FE_DEVICE setup_ms is
                                  the column walk (dg_fe_columns, dg_fe_gaps, dg_fe_scan, dg_fe_scatter), n_walls = wall records,
                                  n_planes = sprites, covered_pixels is not tracked (0) */
 } dg_timing;
