@@ -25,6 +25,10 @@ DG_FE_AUTO, DG_FE_HOST, DG_FE_DEVICE, DG_FE_DEVICE_SEGS = 0, 1, 2, 3
 DG_FE_MAP = 4   # dg_timing.front_end of a 2-D map submission
 DG_FE_DEPTH = 5  # dg_timing.front_end of a depth submission
 DG_KIND_NONE, DG_KIND_COLUMN, DG_KIND_FLAT, DG_KIND_SKY = 0, 1, 2, 3   # the kind plane of a depth frame
+DG_FE_LABELS = 6  # dg_timing.front_end of a label submission
+DG_LABEL_NONE, DG_LABEL_WALL, DG_LABEL_MOBJ, DG_LABEL_FLAT, DG_LABEL_SKY = 0, 1, 2, 3, 4   # the class plane of a label frame / the class of an owner tag
+# dg_label_box as a numpy record: boxes come back as an (n, map objects) array of these
+LABEL_BOX_DTYPE = np.dtype([("pixels", "<u4"), ("x0", "<i2"), ("y0", "<i2"), ("x1", "<i2"), ("y1", "<i2")])
 DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
 DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
@@ -192,6 +196,13 @@ _SIGNATURES = {
     "dg_depth_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P, _P]),
     "dg_readback_depth": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "dg_depth_lists_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P, _P]),
+    "dg_build_lists_owners": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgFrameLists), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32))]),
+    "dg_submit_label_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int]),
+    "dg_render_label_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int, _P, _P, _P]),
+    "dg_label_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.POINTER(_P), ctypes.c_int, _P, _P, _P]),
+    "dg_readback_labels": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "dg_slot_label_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "dg_label_lists_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.POINTER(_P), ctypes.c_int, _P, _P, _P]),
     "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
     "dg_walk_free": (None, [_P]),
     "dg_walk_tics": (ctypes.c_int, [_P]),
@@ -269,6 +280,37 @@ def depth_lists_host(scene, width: int, height: int, frames, distance: bool = Tr
     d, k, dp, kp = _depth_planes(n, height, width, distance, kind)
     _check(lib().dg_depth_lists_host(scene._h, width, height, frames, n, dp, kp))
     return d, k
+
+
+def owner_tag(cls: int, index: int) -> int:
+    """The owner tag of a draw record: DG_LABEL_WALL or DG_LABEL_MOBJ << 16 | the seg's / map object's index."""
+    return (cls << 16) | index
+
+
+def owner_pointers(owners):
+    """owners: per frame a uint32 array of owner tags (one per render record), or None -> (the `const uint32_t *const *` to hand over,
+    keep-alive list)."""
+    keep = [None if o is None else np.ascontiguousarray(o, dtype=np.uint32) for o in owners]
+    arr = (_P * max(1, len(keep)))(*[None if o is None else o.ctypes.data_as(_P) for o in keep])
+    return arr, keep
+
+
+def _label_outputs(n: int, height: int, width: int, n_mobjs: int, id: bool = True, cls: bool = True, boxes: bool = True):
+    """The planes and the box table of n label frames to fill, and the pointers to hand over (None for an output that is not wanted)."""
+    i = np.empty((n, height, width), dtype=np.uint16) if id else None
+    c = np.empty((n, height, width), dtype=np.uint8) if cls else None
+    b = np.empty((n, n_mobjs), dtype=LABEL_BOX_DTYPE) if boxes else None
+    return (i, c, b), [None if a is None else a.ctypes.data_as(_P) for a in (i, c, b)]
+
+
+def label_lists_host(scene, width: int, height: int, frames, owners, id: bool = True, cls: bool = True, boxes: bool = True):
+    """dg_label_lists_host: the label planes and boxes of caller-built lists on the CPU (no ctx, no GPU); owners: per frame the owner tags
+    of its render records.  Returns (uint16 [n,H,W] id, uint8 [n,H,W] cls, LABEL_BOX_DTYPE [n, map objects]), None for what was not asked for."""
+    n = len(frames)
+    out, ptrs = _label_outputs(n, height, width, scene.mobj_count(), id, cls, boxes)
+    op, keep = owner_pointers(owners)
+    _check(lib().dg_label_lists_host(scene._h, width, height, frames, op, n, *ptrs))
+    return out
 
 
 def make_view_states(states):
@@ -373,6 +415,13 @@ class Scene:
         fl = DgFrameLists()
         _check(lib().dg_build_lists(self._h, W, H, ctypes.byref(view), ctypes.byref(fl)))
         return fl
+
+    def build_lists_owners(self, W: int, H: int, view: DgView):
+        """dg_build_lists_owners: the lists of dg_build_lists and, as a uint32 array of its own, the owner tag of every render record."""
+        fl = DgFrameLists()
+        own = ctypes.POINTER(ctypes.c_uint32)()
+        _check(lib().dg_build_lists_owners(self._h, W, H, ctypes.byref(view), ctypes.byref(fl), ctypes.byref(own)))
+        return fl, np.array(own[:fl.n_renders], dtype=np.uint32)
 
     def map_lines(self, W: int, H: int, view=None) -> np.ndarray:
         """dg_map_lines: the lines of one 2-D map frame in draw order, (n, 5) int64 rows [x0, y0, x1, y1, rgb] (rgb = r | g<<8 | b<<16);
@@ -508,6 +557,38 @@ class Context:
         d, k, dp, kp = _depth_planes(count, self.height, self.width, distance, kind)
         _check(lib().dg_readback_depth(self._h, slot, first, count, dp, kp))
         return d, k
+
+    def submit_labels(self, slot: int, views, n=None, states=None):
+        """dg_submit_label_views: object-label frames into the slot, asynchronously (always through the host list path)."""
+        _check(lib().dg_submit_label_views(self._h, slot, views, states, len(views) if n is None else n))
+
+    def _label_outputs(self, n: int, id: bool, cls: bool, boxes: bool):
+        return _label_outputs(n, self.height, self.width, self._scene.mobj_count(), id, cls, boxes)
+
+    def render_labels(self, views, states=None, id: bool = True, cls: bool = True, boxes: bool = True):
+        """dg_render_label_views: synchronous through slot 0; returns (uint16 [n,H,W] id, uint8 [n,H,W] cls, boxes [n, map objects])."""
+        out, ptrs = self._label_outputs(len(views), id, cls, boxes)
+        _check(lib().dg_render_label_views(self._h, views, states, len(views), *ptrs))
+        return out
+
+    def label_lists(self, slot: int, frames, owners, id: bool = True, cls: bool = True, boxes: bool = True):
+        """dg_label_lists: the label planes and boxes of caller-built lists with their owner tags (synchronous)."""
+        out, ptrs = self._label_outputs(len(frames), id, cls, boxes)
+        op, keep = owner_pointers(owners)
+        _check(lib().dg_label_lists(self._h, slot, frames, op, len(frames), *ptrs))
+        return out
+
+    def readback_labels(self, slot: int, first: int, count: int, id: bool = True, cls: bool = True, boxes: bool = True):
+        """dg_readback_labels: the planes and box rows of frames [first, first + count) of a label slot."""
+        out, ptrs = self._label_outputs(count, id, cls, boxes)
+        _check(lib().dg_readback_labels(self._h, slot, first, count, *ptrs))
+        return out
+
+    def label_timing(self, slot: int) -> dict:
+        """dg_slot_label_timing: GPU time (ms) of dg_label_tiles and dg_label_boxes of the slot's last submission."""
+        t, b = ctypes.c_float(), ctypes.c_float()
+        _check(lib().dg_slot_label_timing(self._h, slot, ctypes.byref(t), ctypes.byref(b)))
+        return {"tiles_ms": t.value, "boxes_ms": b.value}
 
     def wait(self, slot: int):
         _check(lib().dg_wait(self._h, slot))

@@ -1,6 +1,8 @@
 // api_scene.cpp — the entry points of the C-ABI (include/doomgpu.h) that need no GPU: the error string and the version, the scene
 // (dg_scene_*), one frame's lists and map lines on the host, the recorded walks, the box downscale on the host (dg_reduced_size,
-// dg_reduce_host) and the depth planes of caller-built lists on the host (dg_depth_lists_host).  Everything that takes a dg_ctx: context.cpp.
+// dg_reduce_host), the depth planes and the label planes and boxes of caller-built lists on the host (dg_depth_lists_host,
+// dg_label_lists_host).  Everything that takes a dg_ctx: context.cpp.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -9,12 +11,19 @@
 #include "binner.hpp"
 #include "depth_core.h"
 #include "frontend.hpp"
+#include "label_core.h"
 #include "reduce_core.h"
 #include "walk.hpp"
 
 using namespace dg;
 
 thread_local std::string t_err;
+
+// dg_build_lists and dg_build_lists_owners share the arena: one walk fills the lists and the owner tags alike.
+static FrameArena &lists_arena() {
+    static thread_local FrameArena arena;
+    return arena;
+}
 
 extern "C" {
 
@@ -122,12 +131,22 @@ int dg_scene_bitmap_size(const dg_scene *s, int bitmap, int *w, int *h) {
 
 int dg_build_lists(const dg_scene *s, int width, int height, const dg_view *view, dg_frame_lists *out) {
     if (!s || !view || !out) return set_err(DG_ERR_INVALID, "null argument");
-    static thread_local FrameArena arena;
     dg_view v = *view;
     fill_view_trig(v);
     std::string err;
-    int rc = build_frame_lists(*s->sc, width, height, v, arena, *out, err, nullptr, &s->sc->fx);
+    int rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, nullptr, &s->sc->fx);
     return rc ? set_err(rc, err) : DG_OK;
+}
+
+int dg_build_lists_owners(const dg_scene *s, int width, int height, const dg_view *view, dg_frame_lists *out, const uint32_t **owners) {
+    if (!s || !view || !out || !owners) return set_err(DG_ERR_INVALID, "null argument");
+    std::string err;
+    int rc = check_label_scene(*s->sc, err);
+    if (rc) return set_err(rc, err);
+    rc = dg_build_lists(s, width, height, view, out);
+    if (rc) return rc;
+    *owners = lists_arena().owners.data();
+    return DG_OK;
 }
 
 int dg_scene_sprite_frame(dg_scene *s, const char *sprite, uint8_t frame) {
@@ -252,6 +271,71 @@ int dg_depth_lists_host(const dg_scene *s, int width, int height, const dg_frame
                     if (kd) kd[(size_t)y * W + x] = (uint8_t)k;
                 }
             }
+    }
+    return DG_OK;
+}
+
+// As dg_depth_lists_host: the binner's spans laid on per column in draw order, label_core.h per pixel; then the boxes of the planes.
+int dg_label_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, const uint32_t *const *owners, int n,
+                        uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
+    if (!s || !frames || !owners) return set_err(DG_ERR_INVALID, "null argument");
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384]");
+    if (n < 0) return set_err(DG_ERR_INVALID, "bad frame count");
+    const Scene &sc = *s->sc;
+    std::string err;
+    int rc = check_label_scene(sc, err);
+    if (rc) return set_err(rc, err);
+    const FrameConsts fk = make_consts(width, height);
+    const DevConsts dk{fk.ARC, fk.GCFX, fk.CFX, fk.CFY, width, height};
+    const BitmapInfo &sky = sc.bitmaps[(size_t)sc.sky_bitmap];
+    const DevScene ds{nullptr, nullptr, sc.texel_idx.data(), sc.texel_opq.data(), nullptr, sky.texel_off, sky.w, sky.h, sky.has_holes};
+    const size_t W = (size_t)width, H = (size_t)height, px = W * H, n_mobjs = sc.mobjs.size();
+    std::vector<BinnedFrame> binned((size_t)n);
+    std::vector<std::vector<uint32_t>> tags((size_t)n);
+    for (int f = 0; f < n; f++) {                                  // every frame is checked before anything is written
+        dg_frame_lists fl = frames[f];
+        fill_view_trig(fl.view);
+        rc = bin_frame(sc, fk, fl, binned[(size_t)f], err);
+        if (!rc) rc = wall_owners(sc, fl, owners[f], tags[(size_t)f], err);
+        if (rc) return set_err(rc, "frame " + std::to_string(f) + ": " + err);
+    }
+    std::vector<uint16_t> idp(px);
+    std::vector<uint8_t> clp(px);
+    std::vector<LabelRawBox> raw(n_mobjs);
+    for (int f = 0; f < n; f++) {
+        BinnedFrame &bf = binned[(size_t)f];
+        bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
+        std::fill(idp.begin(), idp.end(), (uint16_t)0);
+        std::fill(clp.begin(), clp.end(), (uint8_t)LABEL_NONE);
+        for (size_t x = 0; x < W; x++)
+            for (uint32_t j = bf.col_off[x]; j < bf.col_off[x + 1]; j++) {
+                const DevSpan &sp = bf.spans[j];
+                const DevRSpan r = label_resolve_span(sp, bf.hdr, bf.walls.data(), tags[(size_t)f].data(), ds, dk);
+                for (int32_t y = sp.ctop; y <= sp.cbot; y++) {
+                    uint32_t label;
+                    if (!label_span_writes(r, ds, dk, y, label)) continue;
+                    idp[(size_t)y * W + x] = (uint16_t)label_index(label);
+                    clp[(size_t)y * W + x] = (uint8_t)label_class(label);
+                }
+            }
+        if (id) std::memcpy(id + (size_t)f * px, idp.data(), px * sizeof(uint16_t));
+        if (cls) std::memcpy(cls + (size_t)f * px, clp.data(), px);
+        if (!boxes) continue;
+        std::memset(raw.data(), 0, n_mobjs * sizeof(LabelRawBox));
+        for (size_t y = 0; y < H; y++)
+            for (size_t x = 0; x < W; x++) {
+                if (clp[y * W + x] != (uint8_t)LABEL_MOBJ) continue;
+                uint32_t *const b = raw[idp[y * W + x]].w;
+                b[0]++;
+                b[1] = std::max(b[1], (uint32_t)x + 1); b[2] = std::max(b[2], (uint32_t)y + 1);
+                b[3] = std::max(b[3], (uint32_t)(W - x)); b[4] = std::max(b[4], (uint32_t)(H - y));
+            }
+        for (size_t m = 0; m < n_mobjs; m++) {
+            int32_t x0, y0, x1, y1;
+            dg_label_box &o = boxes[(size_t)f * n_mobjs + m];
+            label_box_finish(raw[m], width, height, o.pixels, x0, y0, x1, y1);
+            o.x0 = (int16_t)x0; o.y0 = (int16_t)y0; o.x1 = (int16_t)x1; o.y1 = (int16_t)y1;
+        }
     }
     return DG_OK;
 }

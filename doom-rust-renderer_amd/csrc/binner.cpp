@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "label_core.h"
 #include "rust_num.h"
 
 namespace dg {
@@ -120,6 +121,25 @@ int bin_frame(const Scene &sc, const FrameConsts &k, const dg_frame_lists &fl, B
     for (const DevSpan &s : out.events) out.spans[out.cursor[(size_t)s.x]++] = s;
     out.hdr.n_spans = (uint32_t)out.spans.size();
     return DG_OK;
+}
+
+int wall_owners(const Scene &sc, const dg_frame_lists &fl, const uint32_t *owners, std::vector<uint32_t> &out, std::string &err) {
+    out.clear();
+    if (!owners && fl.n_renders) { err = "no owner tags for the frame's render records"; return DG_ERR_INVALID; }
+    for (uint32_t i = 0; i < fl.n_renders; i++)
+        if (!label_tag_ok(owners[i], (uint32_t)sc.segs.size(), (uint32_t)sc.mobjs.size())) {
+            err = "owner tag " + std::to_string(i) + " names no wall seg or map object of the scene";
+            return DG_ERR_INVALID;
+        }
+    for (uint32_t oi = 0; oi < fl.n_order; oi++)
+        if (fl.order[oi].kind == 0) out.push_back(owners[fl.order[oi].index]);
+    return DG_OK;
+}
+
+int check_label_scene(const Scene &sc, std::string &err) {
+    if (sc.segs.size() <= 65536 && sc.mobjs.size() <= 65536) return DG_OK;
+    err = "more than 65536 segs or map objects: an owner tag cannot hold the index";
+    return DG_ERR_CAPACITY;
 }
 
 }  // namespace dg

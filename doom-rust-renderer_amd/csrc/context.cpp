@@ -12,6 +12,9 @@
 //             col_off F*(W+1) written by dg_fe_finalize, 2F status words (overflow flags, span totals)
 //             2-D map view: the arrow lines of the batch (MapSeg x 3F) at the start of the list slab
 //             depth frames (DG_FE_DEPTH): the host lists in the list slab; the framebuffer slab holds int16 distance[F][H][W], then uint8 kind[F][H][W]
+//             label frames (DG_FE_LABELS): likewise, the framebuffer slab holds uint16 id[F][H][W], then uint8 cls[F][H][W]; the owner tags
+//             parallel to the list slab's wall records and the box table [max_batch][map objects] are buffers of the slot's own,
+//             allocated by its first label submission (the box table again after dg_upload_scene)
 //   per ctx : 2-D map view layer 3*W*H bytes RGB24 (allocated by the first map submission, rebuilt after every dg_upload_scene)
 //             DG_FE_DEVICE column scratch [F][slot][W]: compact spans 16 B (48 slots), wall-record columns 8 B (48 slots),
 //             counts, sky event bits — shared by the slots because their kernels run back to back
@@ -41,6 +44,7 @@
 #include "frontend.hpp"
 #include "hip_mem.hpp"
 #include "kernels.hpp"
+#include "label_kernels.hpp"
 #include "map_kernels.hpp"
 #include "pool.hpp"
 #include "reduce_kernels.hpp"
@@ -83,6 +87,12 @@ struct Slot {
     DevPtr<DevRSpan> d_rspans;
     DevPtr<uint8_t> d_fb;
     size_t lists_cap = 0;
+    // label frames: owner tags parallel to the wall records of d_lists (staging + HBM, wall_cap_per_batch entries) and the box table
+    // max_batch x box_mobjs — none of it exists before the slot's first label submission; dg_upload_scene drops the box table
+    PinnedPtr<uint32_t> h_owners;
+    DevPtr<uint32_t> d_owners;
+    DevPtr<LabelRawBox> d_boxes;
+    size_t box_mobjs = 0;
     // last submission
     RasterParams P{};
     uint32_t max_spans = 0;
@@ -116,7 +126,8 @@ struct Slot {
     MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
     // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
     // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP (2-D map frames: arrow lines at the start of d_lists) or
-    // DG_FE_DEPTH (host lists walked by dg_depth_tiles: the framebuffer slab holds the two planes, not RGB24)
+    // DG_FE_DEPTH (host lists walked by dg_depth_tiles: the framebuffer slab holds the two planes, not RGB24) or DG_FE_LABELS (host lists
+    // walked by dg_label_tiles: the slab holds the id and class planes)
     int32_t front_end = DG_FE_HOST;
     // A new submission of n frames through front end fe, `bytes` of lists or records uploaded for it (span statistics: the host list path's alone)
     void describe(int32_t fe, int n, uint64_t bytes, uint64_t walls, uint64_t planes) {
@@ -126,6 +137,7 @@ struct Slot {
     bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
     bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
     bool holds_depth() const { return front_end == DG_FE_DEPTH && phase != Phase::Empty; }     // the framebuffer slab is the two depth planes
+    bool holds_labels() const { return front_end == DG_FE_LABELS && phase != Phase::Empty; }   // ... the two label planes
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
     bool map_built = false;       // a map submission whose enqueue built the ctx's map layer (ev_start .. ev_setup time that)
     std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
@@ -209,6 +221,7 @@ struct dg_ctx {
     std::unique_ptr<Pool> pool;
     std::vector<std::unique_ptr<FrameArena>> arenas;   // one per worker (+ caller)
     std::vector<BinnedFrame> binned;                   // one per frame of a batch
+    std::vector<std::vector<uint32_t>> label_tags;     // label submissions: the owner tag of every wall record of binned[i]
     size_t span_cap_per_batch = 0, wall_cap_per_batch = 0, plane_cap_per_batch = 0;
     int n_threads = 1;
     // device column walk
@@ -376,26 +389,32 @@ void fill_walk_params(dg_ctx *c, Slot &s, int n) {
 }
 
 // Build + bin the lists of n views in parallel, pack them into the slot's pinned slab, fill slot.P.  fe: what the submission is described
-// as — DG_FE_HOST, or DG_FE_DEPTH when dg_depth_tiles will walk the lists.
-int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, int32_t fe = DG_FE_HOST) {
+// as — DG_FE_HOST, DG_FE_DEPTH when dg_depth_tiles will walk the lists, or DG_FE_LABELS when dg_label_tiles will: then the owner tags of
+// the wall records go into the slot's owner array as well (the caller has allocated it), from given_owners[i] for the caller's lists.
+int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, int32_t fe = DG_FE_HOST,
+                     const uint32_t *const *given_owners = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
     const int W = c->cfg.width, H = c->cfg.height;
     std::vector<int> rc((size_t)n, 0);
     std::vector<std::string> errs((size_t)n);
+    const bool labels = fe == DG_FE_LABELS;
+    if (labels && c->label_tags.size() < (size_t)n) c->label_tags.resize((size_t)n);
     c->pool->parallel_for(n, [&](int i, int wid) {
         BinnedFrame &bf = c->binned[(size_t)i];
         if (given) {
             dg_frame_lists fl = given[i];
             fill_view_trig(fl.view);
             rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
+            if (labels && !rc[(size_t)i]) rc[(size_t)i] = wall_owners(sc, fl, given_owners[i], c->label_tags[(size_t)i], errs[(size_t)i]);
         } else {
             dg_view v = views[i];
             fill_view_trig(v);
             dg_frame_lists fl;
             rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx);
             if (!rc[(size_t)i]) rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
+            if (labels && !rc[(size_t)i]) rc[(size_t)i] = wall_owners(sc, fl, c->arenas[(size_t)wid]->owners.data(), c->label_tags[(size_t)i], errs[(size_t)i]);
         }
     });
     for (int i = 0; i < n; i++)
@@ -414,13 +433,18 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
         return set_err(DG_ERR_CAPACITY, "frame lists exceed the slot's list slab");
     const ListLayout L = list_layout((size_t)n, (size_t)W, walls, planes, spans);
     if (L.total > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
-    c->pool->parallel_for(n, [&](int i, int) { pack_binned(s.h_lists.get(), L, c->binned[(size_t)i], (size_t)i, (size_t)W); });
+    c->pool->parallel_for(n, [&](int i, int) {
+        pack_binned(s.h_lists.get(), L, c->binned[(size_t)i], (size_t)i, (size_t)W);
+        const std::vector<uint32_t> *tags = labels ? &c->label_tags[(size_t)i] : nullptr;      // (as many as the frame has wall records)
+        if (tags && !tags->empty()) std::memcpy(s.h_owners.get() + c->binned[(size_t)i].hdr.wall_base, tags->data(), tags->size() * sizeof(uint32_t));
+    });
     fill_raster_params(c, s, n);
     point_at_lists(s.P, s.d_lists.get(), L);
     s.describe(fe, n, L.total, walls, planes);
     s.max_spans = max_spans; s.n_spans = spans; s.covered = covered;
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), L.total, hipMemcpyHostToDevice, s.stream));
+    if (labels && walls) HIP_TRY(hipMemcpyAsync(s.d_owners.get(), s.h_owners.get(), walls * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream));
     return DG_OK;
 }
 
@@ -1035,7 +1059,9 @@ int check_slot(dg_ctx *c, int slot) {
 }
 
 // The calls that read the framebuffer slab as RGB24 frames, or run the colour kernels again, on a slot whose last submission was depth.
+// ... or a label submission.
 int refuse_depth(const Slot &s, const char *what) {
+    if (s.holds_labels()) return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds label planes, not RGB24 frames (dg_readback_labels)");
     if (!s.holds_depth()) return DG_OK;
     return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds depth planes, not RGB24 frames (dg_readback_depth)");
 }
@@ -1054,6 +1080,41 @@ int submit_depth(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists
     if (e != hipSuccess) {                                // (as a failed enqueue_kernels: the slot is left empty)
         s.reset();
         return set_err(DG_ERR_HIP, std::string("launch_depth: ") + hipGetErrorString(e));
+    }
+    s.harvested = true;
+    s.raster_recorded = true;
+    s.phase = Slot::Phase::Queued;
+    return DG_OK;
+}
+
+// Slot `slot` for a label submission of n views (or of the caller's lists with their owner tags): the host list path like depth;
+// dg_label_tiles and dg_label_boxes on the slot's own stream, behind the uploads.  ev_setup, which a label submission has no front-end
+// half to time with, marks the end of dg_label_tiles.
+int submit_labels(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, const uint32_t *const *owners, int n, const dg_view_state *states) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    Slot &s = c->slots[(size_t)slot];
+    int rc = take_slot(c, s);
+    if (rc) return rc;
+    if (const int bad = check_batch(c, n)) return bad;
+    std::string err;
+    if ((rc = check_label_scene(*c->scene, err))) return set_err(rc, err);
+    const size_t n_mobjs = c->scene->mobjs.size();
+    if (!s.d_owners) {
+        HIP_TRY(hip_alloc(s.h_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
+        HIP_TRY(hip_alloc(s.d_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
+    }
+    if (!s.d_boxes || s.box_mobjs != n_mobjs) {
+        HIP_TRY(hip_alloc(s.d_boxes, std::max<size_t>((size_t)c->cfg.max_batch * n_mobjs, 1) * sizeof(LabelRawBox)));
+        s.box_mobjs = n_mobjs;
+    }
+    rc = build_batch_host(c, s, views, given, n, states, DG_FE_LABELS, owners);
+    if (rc) return rc;
+    const size_t plane = (size_t)n * (size_t)c->cfg.width * (size_t)c->cfg.height;
+    const hipError_t e = launch_labels(s.P, s.d_owners.get(), reinterpret_cast<uint16_t *>(s.d_fb.get()), s.d_fb.get() + 2 * plane, s.d_boxes.get(), (uint32_t)n_mobjs,
+                                       s.stream, s.ev_rstart, s.ev_setup, s.ev_raster);
+    if (e != hipSuccess) {                                // (as a failed enqueue_kernels: the slot is left empty)
+        s.reset();
+        return set_err(DG_ERR_HIP, std::string("launch_labels: ") + hipGetErrorString(e));
     }
     s.harvested = true;
     s.raster_recorded = true;
@@ -1207,7 +1268,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     c->d_palette.reset(); c->d_texel_idx.reset(); c->d_texel_opq.reset();
     c->d_flats = nullptr;               // inside d_texel_idx's allocation
     // the slots' prepared records point into the device scene that was just freed: nothing may be replayed from them
-    for (Slot &s : c->slots) s.reset();
+    for (Slot &s : c->slots) { s.reset(); s.d_boxes.reset(); s.box_mobjs = 0; }   // (the box table is sized by the scene's map objects)
     c->d_walk_tables.reset();           // dg_ctx_locate_walks is synchronous: nothing of it is in flight
     c->map_layer_ok = false;            // the map view's linedef layer belongs to the old scene   // (a new scene may reuse the old one's address and revision)
     uint32_t pal[256];
@@ -1482,7 +1543,7 @@ int dg_readback_depth(dg_ctx *c, int slot, int first, int count, int16_t *distan
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if (!s.holds_depth()) return set_err(DG_ERR_INVALID, "dg_readback_depth: the slot's last submission is not a depth submission");
+    if (!s.holds_depth()) return set_err(DG_ERR_INVALID, "dg_readback_depth: the slot's last submission is not a depth submission");   // (a label slot included)
     if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     if (count == 0) return DG_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -1512,6 +1573,72 @@ int dg_depth_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, int n, int
     if (rc) return rc;
     if (!frames) return set_err(DG_ERR_INVALID, "null frames");
     return read_depth_or_wait(c, slot, submit_depth(c, slot, nullptr, frames, n, nullptr), n, distance, kind);
+}
+
+int dg_submit_label_views(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, int n) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!views) return set_err(DG_ERR_INVALID, "null views");
+    rc = check_view_states(states, n);
+    if (rc) return rc;
+    return submit_labels(c, slot, views, nullptr, nullptr, n, states);
+}
+
+int dg_readback_labels(dg_ctx *c, int slot, int first, int count, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.holds_labels()) return set_err(DG_ERR_INVALID, "dg_readback_labels: the slot's last submission is not a label submission");
+    if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
+    if (count == 0) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    rc = make_final(c, s, Copy::Leave);
+    if (rc) return rc;
+    const int W = c->cfg.width, H = c->cfg.height;
+    const size_t px = (size_t)W * (size_t)H;
+    const uint16_t *const d_id = reinterpret_cast<const uint16_t *>(s.d_fb.get());
+    const uint8_t *const d_cls = s.d_fb.get() + 2 * (size_t)s.n_frames * px;
+    std::vector<LabelRawBox> raw(boxes ? (size_t)count * s.box_mobjs : 0);
+    if (id) HIP_TRY(hipMemcpyAsync(id, d_id + (size_t)first * px, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream));
+    if (cls) HIP_TRY(hipMemcpyAsync(cls, d_cls + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream));
+    if (!raw.empty()) HIP_TRY(hipMemcpyAsync(raw.data(), s.d_boxes.get() + (size_t)first * s.box_mobjs, raw.size() * sizeof(LabelRawBox), hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(slot_sync(s));
+    for (size_t i = 0; i < raw.size(); i++) {
+        int32_t x0, y0, x1, y1;
+        label_box_finish(raw[i], W, H, boxes[i].pixels, x0, y0, x1, y1);
+        boxes[i].x0 = (int16_t)x0; boxes[i].y0 = (int16_t)y0; boxes[i].x1 = (int16_t)x1; boxes[i].y1 = (int16_t)y1;
+    }
+    return DG_OK;
+}
+
+// The synchronous label calls' tail, given what their submission returned: the n frames' planes and boxes into the outputs, or just its end.
+static int read_labels_or_wait(dg_ctx *c, int slot, int rc, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
+    if (rc) return rc;
+    return id || cls || boxes ? dg_readback_labels(c, slot, 0, n, id, cls, boxes) : dg_wait(c, slot);
+}
+
+int dg_render_label_views(dg_ctx *c, const dg_view *views, const dg_view_state *states, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
+    return read_labels_or_wait(c, 0, dg_submit_label_views(c, 0, views, states, n), n, id, cls, boxes);
+}
+
+int dg_label_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uint32_t *const *owners, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!frames || !owners) return set_err(DG_ERR_INVALID, "null frames or owners");
+    return read_labels_or_wait(c, slot, submit_labels(c, slot, nullptr, frames, owners, n, nullptr), n, id, cls, boxes);
+}
+
+int dg_slot_label_timing(dg_ctx *c, int slot, float *tiles_ms, float *boxes_ms) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.holds_labels() || !s.has_run()) return set_err(DG_ERR_INVALID, "dg_slot_label_timing: the slot's last submission is not a label submission that ran");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    rc = make_final(c, s, Copy::Leave);
+    if (rc) return rc;
+    if (tiles_ms) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_rstart, s.ev_setup));
+    if (boxes_ms) HIP_TRY(hipEventElapsedTime(boxes_ms, s.ev_setup, s.ev_raster));
+    return DG_OK;
 }
 
 int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
@@ -1636,7 +1763,7 @@ int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
     std::memset(out, 0, sizeof *out);
     out->front_end = s.front_end;
     HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
-    if (s.front_end != DG_FE_DEPTH && (s.front_end != DG_FE_MAP || s.map_built)) {   // (a map submission has a front-end half only when it built the map layer, a depth submission none)
+    if (s.front_end != DG_FE_DEPTH && s.front_end != DG_FE_LABELS && (s.front_end != DG_FE_MAP || s.map_built)) {   // (a map submission has a front-end half only when it built the map layer, a depth or label submission none)
         HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
         HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));
     } else {

@@ -36,6 +36,7 @@ struct FrameArena::Rec {                                             // bitmap_r
     int16_t light, offset_x, offset_y;
     uint8_t state, ext_bottom, ext_top, draw_ceiling;
     int16_t sort_key;              // map objects: line.start.x as i16 (bitmap_render.rs:168-174)
+    uint32_t owner;                // host-list mode: the seg or map object that made the record (doomgpu.h: class << 16 | index)
 };
 
 FrameArena::FrameArena() : recs(new std::vector<Rec>()) {}
@@ -120,6 +121,7 @@ struct Walker {
     const WallFx *fx = nullptr;             // the wall effects to draw with (nullptr: none)
     const LightFx *lfx = nullptr;           // the light effects to draw with (nullptr: none)
     const MobjFx *mfx = nullptr;            // the map-object thinkers to draw with (nullptr: none)
+    uint32_t cur_owner = 0;                 // owner tag of the seg / map object being processed (host-list mode)
     static constexpr int32_t kNoOverride = INT32_MIN;
 
     // sector.light_level / map object state as the reference's thinkers would have left them before this frame
@@ -212,6 +214,7 @@ struct Walker {
             o.first_column = r.first_col; o.n_columns = r.n_cols;
             r.out_index = (int32_t)A.renders.size();
             A.renders.push_back(o);
+            A.owners.push_back(r.owner);
         }
         A.order.push_back(dg_draw_cmd{0u, (uint32_t)r.out_index});
     }
@@ -281,6 +284,7 @@ struct Walker {
         r.ext_top = f.upper || (!f.two_sided_mid && full_height);
         r.draw_ceiling = f.draw_ceiling;
         r.sort_key = 0;
+        r.owner = cur_owner;
 
         const bool planes_here = !f.two_sided_mid && (full_height || f.only_occlusions);
         // Columns that an earlier full-height solid part spans are horizontally occluded whatever that part's own
@@ -352,6 +356,7 @@ struct Walker {
     // Segs::process_seg, segs.rs:353-590: fs_seg (fs_core.h) classifies the seg and lists its process_sidedef calls
     void process_seg(size_t seg_index) {
         FsSeg sg = sc.fs_segs[seg_index];
+        cur_owner = ((uint32_t)DG_LABEL_WALL << 16) | (uint32_t)(seg_index & 0xffffu);
         if (fx) fs_seg_fx(sg, fx->seg[seg_index], fx->lists.data(), view.timestamp);
         FsSegOut so;
         const int16_t light = sg.front_sector >= 0 ? sector_light(sg.front_sector) : (int16_t)0;
@@ -532,6 +537,7 @@ struct Walker {
             r.light = light; r.offset_x = 0; r.offset_y = 0;
             r.state = ST_MAPOBJECT; r.ext_bottom = r.ext_top = r.draw_ceiling = 0;
             r.sort_key = (int16_t)f32_as_i16(cl.line.a.x);
+            r.owner = ((uint32_t)DG_LABEL_MOBJ << 16) | (uint32_t)(mi & 0xffffu);
             float bottom_delta = ((float)bot.sy - (float)bot.ey) / ((float)bot.sx - (float)bot.ex);
             float top_delta = ((float)top.sy - (float)top.ey) / ((float)top.sx - (float)top.ex);
             for (int x = x0; x < x1; x++) {
@@ -595,7 +601,7 @@ struct Walker {
 
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const SceneFx *fx) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
-    A.renders.clear(); A.columns.clear(); A.visplanes.clear(); A.plane_tb.clear(); A.order.clear();
+    A.renders.clear(); A.owners.clear(); A.columns.clear(); A.visplanes.clear(); A.plane_tb.clear(); A.order.clear();
     A.recs->clear(); A.floor_tb.clear(); A.ceil_tb.clear();
     A.hor_ocl.assign((size_t)W, 0);                                  // Segs::new, segs.rs:97-99
     A.floor_ocl.assign((size_t)W, (int16_t)H);

@@ -27,6 +27,7 @@ FrameConsts make_consts(int W, int H);
 // Reusable per-thread storage: one build() call fills it, the dg_frame_lists view points into it.
 struct FrameArena {
     std::vector<dg_bitmap_render> renders;
+    std::vector<uint32_t> owners;       // per render: the owner tag of the seg or map object that made it (doomgpu.h: dg_build_lists_owners)
     std::vector<dg_bitmap_column> columns;
     std::vector<dg_visplane> visplanes;
     std::vector<int16_t> plane_tb;

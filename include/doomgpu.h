@@ -376,6 +376,55 @@ int dg_readback_depth(dg_ctx *ctx, int slot, int first, int count, int16_t *dist
  * DG_ERR_RENDER / DG_ERR_CAPACITY as dg_draw_lists.  Either output may be NULL. */
 int dg_depth_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, int n, int16_t *distance, uint8_t *kind);
 
+/* ---- object-label frames and per-object screen boxes ---------------------------------------------------------------------- */
+/* The fourth picture of a view: per pixel, WHICH thing owns it — the map object or the wall seg whose draw call wrote the pixel last —
+ * and per map object how many pixels it owns and their bounding box (what ViZDoom's users know as the labels buffer and the labels
+ * list).  Exact, like the depth planes, and under the same rules: draw order (the later Pixels::set wins), transparent texels write
+ * nothing so the pixel keeps its earlier owner, the row clamps, the `bottom - top <= 1` skip of draw_visplane, columns at x >= W dropped.
+ *   uint8_t  cls[H][W]   DG_LABEL_NONE  no draw call wrote the pixel
+ *                        DG_LABEL_WALL  a wall seg's draw call (inline wall or masked middle texture)
+ *                        DG_LABEL_MOBJ  a map object's draw call
+ *                        DG_LABEL_FLAT  a floor or ceiling (no id: visplanes merge sectors)
+ *                        DG_LABEL_SKY   the sky, exactly where the depth frame's kind is DG_KIND_SKY
+ *   uint16_t id[H][W]    DG_LABEL_WALL: the seg's index in SEGS;  DG_LABEL_MOBJ: the map object's index (the one dg_scene_set_mobj_state
+ *                        and dg_scene_mobj_states_at use);  otherwise 0.
+ * An owner tag names the thing a draw record (dg_bitmap_render) belongs to: class << 16 | index, class DG_LABEL_WALL or DG_LABEL_MOBJ.
+ * Layout in the slot's framebuffer slab (dg_slot_framebuffer), as for depth: for a submission of n frames  uint16 id[n][H][W]  at the
+ * slab's base, then  uint8 cls[n][H][W]  at byte offset 2*n*W*H.
+ * boxes[frame][mobj], for every map object of the uploaded scene (dg_scene_mobj_count): `pixels` counts the frame's pixels with class
+ * DG_LABEL_MOBJ and that id, x0, y0, x1, y1 is their inclusive bounding box — visible pixels only, occluded and transparent ones are not
+ * in it; pixels == 0 gives x0 = y0 = x1 = y1 = -1. */
+enum { DG_LABEL_NONE = 0, DG_LABEL_WALL = 1, DG_LABEL_MOBJ = 2, DG_LABEL_FLAT = 3, DG_LABEL_SKY = 4 };
+/* dg_timing.front_end of a label submission; never a dg_config.front_end. */
+enum { DG_FE_LABELS = 6 };
+typedef struct dg_label_box { uint32_t pixels; int16_t x0, y0, x1, y1; } dg_label_box;
+/* dg_build_lists with (*owners)[i] set to the owner tag of out->renders[i] (out->n_renders tags; same arena, same lifetime).  The lists
+ * are dg_build_lists' byte for byte.  DG_ERR_CAPACITY: the scene has more than 65 536 segs or map objects (an index would not fit). */
+int dg_build_lists_owners(const dg_scene *s, int width, int height, const dg_view *view, dg_frame_lists *out, const uint32_t **owners);
+/* Asynchronous, like dg_submit_depth_views, and like it always through the host list route whatever front end the ctx has (the device
+ * front ends' records carry no owner): wall effects, light effects, map-object thinkers and per-view snapshots apply exactly as to a
+ * colour frame.  On a label slot dg_wait, dg_slot_timing (front_end = DG_FE_LABELS, raster_ms = dg_label_tiles + dg_label_boxes,
+ * setup_ms = 0), dg_slot_framebuffer, dg_upload_scene and every new submission work as usual; dg_readback(_async),
+ * dg_readback_reduced(_async), dg_frame_checksums, dg_replay_slot and dg_readback_depth return DG_ERR_INVALID and leave the planes
+ * intact.  The slot's owner array and box table (max_batch x map objects) are device memory of the slot, allocated by its first label
+ * submission and again after a dg_upload_scene. */
+int dg_submit_label_views(dg_ctx *ctx, int slot, const dg_view *views, const dg_view_state *states, int n);
+/* Synchronous, slot 0: n*W*H uint16 into id, n*W*H bytes into cls, n * dg_scene_mobj_count boxes into boxes; any may be NULL. */
+int dg_render_label_views(dg_ctx *ctx, const dg_view *views, const dg_view_state *states, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes);
+/* Synchronous, for caller-built lists: owners[f] holds frames[f].n_renders owner tags.  DG_ERR_INVALID, before anything is launched: a
+ * NULL owners or owners[f] (with n_renders > 0), a tag whose class is not DG_LABEL_WALL or DG_LABEL_MOBJ, a map-object index not below
+ * the scene's map-object count, a seg index not below its seg count. */
+int dg_label_lists(dg_ctx *ctx, int slot, const dg_frame_lists *frames, const uint32_t *const *owners, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes);
+/* D2H copy of the planes and box rows of frames [first, first+count) of a label slot; any output may be NULL; count = 0 does nothing.
+ * Waits for the slot like dg_readback.  DG_ERR_INVALID: a bad range, a slot whose last submission is not a label submission. */
+int dg_readback_labels(dg_ctx *ctx, int slot, int first, int count, uint16_t *id, uint8_t *cls, dg_label_box *boxes);
+/* GPU time of the two label kernels of the slot's last (label) submission, from the events attached to their dispatches; either may be NULL. */
+int dg_slot_label_timing(dg_ctx *ctx, int slot, float *tiles_ms, float *boxes_ms);
+/* The same planes and boxes on the CPU: needs no ctx and no GPU, and is what the GPU path is tested against.  Errors as dg_label_lists
+ * and dg_depth_lists_host.  Any output may be NULL. */
+int dg_label_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, const uint32_t *const *owners, int n,
+                        uint16_t *id, uint8_t *cls, dg_label_box *boxes);
+
 /* ---- 2-D map view (reference: Game::render with viewing_map, src/game.rs:491-499, 229-309) --------------------------------- */
 /* What the window holds after render() in map mode, RGB24 like every frame: black; every linedef without DONTDRAW (flags & 128) in
  * LINEDEFS order, yellow (255, 255, 0) when TWOSIDED (flags & 4) else red (255, 0, 0); then the player arrow in yellow: P->E, R->E, L->E.
@@ -441,7 +490,7 @@ const char *dg_last_error(void); /* thread-local message of the last failing cal
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
@@ -451,7 +500,7 @@ typedef struct dg_timing {
     float host_ms;            /* host list generation + binning + packing of that submission (wall clock) */
     uint64_t n_spans, n_frames, covered_pixels;
     uint64_t n_walls, n_planes, list_bytes; /* drawn records / visplanes, bytes of lists copied to HBM */
-    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH): what that submission actually used; with DG_FE_DEVICE setup_ms is
+    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH, DG_FE_LABELS): what that submission actually used; with DG_FE_DEVICE setup_ms is
                                  the column walk (dg_fe_columns, dg_fe_gaps, dg_fe_scan, dg_fe_scatter), n_walls = wall records,
                                  n_planes = sprites, covered_pixels is not tracked (0) */
 } dg_timing;
