@@ -155,17 +155,27 @@ int emul_render_state(void *scene, int W, int H, const dg_view *view_in, const d
     const dg_view_state st{lights, n_lights, mobjs, n_mobjs};
     return emul_render_impl(scene, W, H, view_in, &st, rgb, nullptr);
 }
+static int draw_frame_lists(const Scene &sc, int W, int H, const dg_frame_lists &fl, uint8_t *rgb, uint64_t *stats);
 static int emul_render_impl(void *scene, int W, int H, const dg_view *view_in, const dg_view_state *state, uint8_t *rgb, uint64_t *stats) {
     const Scene &sc = *(const Scene *)scene;
     dg_view view = *view_in;
     fill_view_trig(view);
     static thread_local FrameArena arena;
-    static thread_local BinnedFrame bf;
     dg_frame_lists fl;
     int rc = build_frame_lists(sc, W, H, view, arena, fl, g_err, state);
     if (rc) return rc;
+    return draw_frame_lists(sc, W, H, fl, rgb, stats);
+}
+// Given lists (what dg_draw_lists takes) through the binner and the kernel bodies: the lists need not come from the product's front end.
+int emul_draw_lists(void *scene, int W, int H, const dg_frame_lists *lists, uint8_t *rgb, uint64_t *stats) {
+    dg_frame_lists fl = *lists;
+    fill_view_trig(fl.view);
+    return draw_frame_lists(*(const Scene *)scene, W, H, fl, rgb, stats);
+}
+static int draw_frame_lists(const Scene &sc, int W, int H, const dg_frame_lists &fl, uint8_t *rgb, uint64_t *stats) {
+    static thread_local BinnedFrame bf;
     FrameConsts fk = make_consts(W, H);
-    rc = bin_frame(sc, fk, fl, bf, g_err);
+    int rc = bin_frame(sc, fk, fl, bf, g_err);
     if (rc) return rc;
 
     std::vector<uint32_t> pal(256);

@@ -26,6 +26,7 @@ def lib():
         L.emul_last_error.restype = ctypes.c_char_p
         L.emul_render.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
         L.emul_render_fe.argtypes = L.emul_render.argtypes
+        L.emul_draw_lists.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
         L.emul_render_state.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                         ctypes.c_uint32, ctypes.c_void_p]
         L.emul_fs_frame.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(ctypes.c_uint64)]
@@ -70,6 +71,16 @@ class EmulScene:
         buf = np.empty(3 * W * H, dtype=np.uint8)
         st = (ctypes.c_uint64 * 4)()
         rc = lib().emul_render(self._h, W, H, ctypes.byref(v), buf.ctypes.data_as(ctypes.c_void_p), st)
+        if rc:
+            raise RuntimeError(f"emul rc {rc}: {lib().emul_last_error().decode()}")
+        return buf.tobytes(), list(st)
+
+    def draw_lists(self, W, H, frame_lists):
+        """One dg_frame_lists (the ctypes structure of the package, as test_edge_kats.to_dg_lists makes it) through the binner and the
+        kernel bodies: what dg_draw_lists takes.  The texture and flat ids are those of the same WAD loaded by the product."""
+        buf = np.empty(3 * W * H, dtype=np.uint8)
+        st = (ctypes.c_uint64 * 4)()
+        rc = lib().emul_draw_lists(self._h, W, H, ctypes.byref(frame_lists), buf.ctypes.data_as(ctypes.c_void_p), st)
         if rc:
             raise RuntimeError(f"emul rc {rc}: {lib().emul_last_error().decode()}")
         return buf.tobytes(), list(st)

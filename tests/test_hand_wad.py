@@ -10,6 +10,7 @@ animated floor (flats.rs:30-111: NUKAGE1-3), a sky ceiling, a rotating sprite (e
 References: src/wad.rs:57-63,86-195 (header, directory, map lumps by position), src/map/*.rs (record layouts),
 src/graphics/pictures.rs:66-147 (picture / post format), src/graphics/textures.rs:182-255 (PNAMES / TEXTURE1),
 src/graphics/flats.rs:116-136, src/graphics/sprites.rs:26-97, src/map_objects.rs:25-59 (things -> map objects)."""
+import hashlib
 import math
 import os
 import struct
@@ -82,14 +83,27 @@ VERT = {"a0": (0, 0), "a1": (-64, 320), "p1": (384, 96), "p2": (320, 400), "b1":
 VORDER = ["a0", "a1", "p1", "p2", "b1", "b2"]
 
 
-def _graphics():
+def sky_texel(x, y):
+    """The hand WAD's own sky: opaque everywhere."""
+    return (x // 2 + y) % 64 + 150
+
+
+# the sky of _graphics: (patches {name: (w, h, texel(x, y) -> palette index or None)}, the SKY1 definition (w, h, [(ox, oy, patch name)]))
+DEFAULT_SKY = ({"PSKY": (256, 128, sky_texel)}, (256, 128, [(0, 0, "PSKY")]))
+HAND_IWAD_SHA256 = "e94b1cbc975748b3948d815d8dcf1dab2254486468d70b07b3ade3762cbe615e"      # build_hand_iwad() before the sky became a parameter
+POLYGON_IWAD_SHA256 = "f0e152e63ba49e718ca686f59b6d9a2beecd408023273941217649af6f08e2c3"   # build_polygon_iwad() likewise
+
+
+def _graphics(sky=DEFAULT_SKY):
+    sky_patches, (sky_w, sky_h, sky_def) = sky
     playpal = bytes(v for i in range(256) for v in ((i * 7 + 3) % 256, (i * 13 + 40) % 256, (255 - i * 5) % 256))
     patches = {
         "PWALL": _picture(64, 128, 0, 0, lambda x, y: (x * 3 + y * 5) % 251 + 1),
         "PHOLE": _picture(64, 128, 0, 0, lambda x, y: None if (x // 8 + y // 8) % 3 == 0 else (x + 2 * y) % 200 + 20),
         "PSMALL": _picture(32, 64, 0, 0, lambda x, y: None if (x // 4 + y // 4) % 2 == 0 else (7 * x + y) % 100 + 100),
-        "PSKY": _picture(256, 128, 0, 0, lambda x, y: (x // 2 + y) % 64 + 150),
     }
+    for name, (w, h, texel) in sky_patches.items():
+        patches[name] = _picture(w, h, 0, 0, texel)
     pnames_list = list(patches)
     pnames = struct.pack("<I", len(pnames_list)) + b"".join(_name8(n) for n in pnames_list)
     texture1 = _texture1([
@@ -97,7 +111,7 @@ def _graphics():
         ("TWOP", 64, 128, [(0, 0, "PWALL"), (16, 32, "PSMALL")]),          # the second patch's transparent texels overwrite the first's
         ("MASKED", 64, 128, [(0, 0, "PHOLE")]),
         ("STEP", 64, 128, [(0, 0, "PWALL"), (32, 64, "PWALL"), (-8, 100, "PSMALL")]),
-        ("SKY1", 256, 128, [(0, 0, "PSKY")]),
+        ("SKY1", sky_w, sky_h, sky_def),
     ], pnames_list)
     flats = {
         "FLOORA": bytes((x * 2 + y * 3) % 97 + 1 for y in range(64) for x in range(64)),
@@ -128,13 +142,13 @@ def _pack_iwad(playpal, pnames, texture1, patches, flats, sprites, map_lumps) ->
     return b"IWAD" + struct.pack("<II", len(lumps), 12 + len(body)) + body + directory
 
 
-def build_hand_iwad() -> bytes:
+def build_hand_iwad(sky=DEFAULT_SKY) -> bytes:
     vi = {n: i for i, n in enumerate(VORDER)}
     A, B = ["a0", "p1", "p2", "a1"], ["p1", "b1", "b2", "p2"]
     for poly in (A, B):                                       # convex and counter-clockwise, so each is one BSP leaf
         for i in range(4):
             assert _cross(VERT[poly[i]], VERT[poly[(i + 1) % 4]], VERT[poly[(i + 2) % 4]]) > 0
-    playpal, pnames, texture1, patches, flats, sprites = _graphics()
+    playpal, pnames, texture1, patches, flats, sprites = _graphics(sky)
     # ---- the map -------------------------------------------------------------------------------------------------------------------
     # sectors (26 B: floor, ceiling, floor flat[8], ceiling flat[8], light, special, tag)
     sectors = struct.pack("<hh", 0, 128) + _name8("FLOORA") + _name8("CEILA") + struct.pack("<hhh", 160, 0, 0) + \
@@ -230,6 +244,14 @@ def _views(campath_mod, osc):
         rec = campath_mod.view_record(np.float32(x), np.float32(y), np.float32(a), np.float32(osc.floor_height_at(x, y, 0.0)))
         out.append((np.concatenate([rec, np.array([ts], dtype=np.float32)]), ts))
     return out
+
+
+def test_the_default_sky_reproduces_the_pinned_wad_bytes():
+    """The sky of _graphics is a parameter (tests/sky_cases.py builds holey and small ones); left alone, both WADs are byte for byte what
+    they were before it became one, so the tests below pin what they always pinned."""
+    assert hashlib.sha256(build_hand_iwad()).hexdigest() == HAND_IWAD_SHA256
+    assert hashlib.sha256(build_hand_iwad(DEFAULT_SKY)).hexdigest() == HAND_IWAD_SHA256
+    assert hashlib.sha256(build_polygon_iwad()).hexdigest() == POLYGON_IWAD_SHA256
 
 
 def test_hand_assembled_wad_oracle_equals_numpy_renderer(campath_mod):
