@@ -27,6 +27,8 @@ DG_FE_DEPTH = 5  # dg_timing.front_end of a depth submission
 DG_KIND_NONE, DG_KIND_COLUMN, DG_KIND_FLAT, DG_KIND_SKY = 0, 1, 2, 3   # the kind plane of a depth frame
 DG_FE_LABELS = 6  # dg_timing.front_end of a label submission
 DG_LABEL_NONE, DG_LABEL_WALL, DG_LABEL_MOBJ, DG_LABEL_FLAT, DG_LABEL_SKY = 0, 1, 2, 3, 4   # the class plane of a label frame / the class of an owner tag
+DG_FE_BUNDLE = 7  # dg_timing.front_end of a bundle submission
+DG_BUNDLE_COLOUR, DG_BUNDLE_DEPTH, DG_BUNDLE_LABELS = 1, 2, 4   # the parts of a bundle submission (`what`)
 # dg_label_box as a numpy record: boxes come back as an (n, map objects) array of these
 LABEL_BOX_DTYPE = np.dtype([("pixels", "<u4"), ("x0", "<i2"), ("y0", "<i2"), ("x1", "<i2"), ("y1", "<i2")])
 DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
@@ -77,6 +79,10 @@ class DgWalkDesc(ctypes.Structure):
 
 class DgReduceDesc(ctypes.Structure):
     _fields_ = [("fx", ctypes.c_uint32), ("fy", ctypes.c_uint32), ("format", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class DgBundleOffsets(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in "colour distance kind id cls total".split()]
 
 
 class DgConfig(ctypes.Structure):
@@ -203,6 +209,12 @@ _SIGNATURES = {
     "dg_readback_labels": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
     "dg_slot_label_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "dg_label_lists_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.POINTER(_P), ctypes.c_int, _P, _P, _P]),
+    "dg_bundle_layout": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(DgBundleOffsets)]),
+    "dg_bundle_capacity": (ctypes.c_int, [_P, ctypes.c_uint32]),
+    "dg_submit_bundle_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int, ctypes.c_uint32]),
+    "dg_bundle_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.POINTER(_P), ctypes.c_int, ctypes.c_uint32]),
+    "dg_bundle_lists_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.POINTER(_P), ctypes.c_int, _P, _P, _P, _P, _P]),
+    "dg_slot_bundle_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
     "dg_walk_free": (None, [_P]),
     "dg_walk_tics": (ctypes.c_int, [_P]),
@@ -311,6 +323,27 @@ def label_lists_host(scene, width: int, height: int, frames, owners, id: bool = 
     op, keep = owner_pointers(owners)
     _check(lib().dg_label_lists_host(scene._h, width, height, frames, op, n, *ptrs))
     return out
+
+
+def bundle_layout(width: int, height: int, n: int, what: int) -> dict:
+    """dg_bundle_layout: the byte offsets of a bundle's parts in the slot's framebuffer slab (colour, distance, kind, id, cls) and `total`;
+    a part not in `what` has offset == total.  No ctx, no GPU."""
+    o = DgBundleOffsets()
+    _check(lib().dg_bundle_layout(width, height, n, what, ctypes.byref(o)))
+    return {k: getattr(o, k) for k, _ in o._fields_}
+
+
+def bundle_lists_host(scene, width: int, height: int, frames, owners=None, distance: bool = True, kind: bool = True, id: bool = True, cls: bool = True,
+                      boxes: bool = True):
+    """dg_bundle_lists_host: the planes and boxes a bundle's fused kernel writes, for caller-built lists, on the CPU (no ctx, no GPU).
+    owners (per frame the owner tags of its render records) is needed when id, cls or boxes is asked for.  Returns (distance, kind, id,
+    cls, boxes) as depth_lists_host and label_lists_host give them, None for what was not asked for."""
+    n = len(frames)
+    d, k, dp, kp = _depth_planes(n, height, width, distance, kind)
+    out, ptrs = _label_outputs(n, height, width, scene.mobj_count(), id, cls, boxes)
+    op, keep = owner_pointers(owners) if owners is not None else (None, None)
+    _check(lib().dg_bundle_lists_host(scene._h, width, height, frames, op, n, dp, kp, *ptrs))
+    return (d, k) + tuple(out)
 
 
 def make_view_states(states):
@@ -589,6 +622,26 @@ class Context:
         t, b = ctypes.c_float(), ctypes.c_float()
         _check(lib().dg_slot_label_timing(self._h, slot, ctypes.byref(t), ctypes.byref(b)))
         return {"tiles_ms": t.value, "boxes_ms": b.value}
+
+    def submit_bundle(self, slot: int, views, what: int, n=None, states=None):
+        """dg_submit_bundle_views: the parts `what` names (DG_BUNDLE_*) of the same views into the slot from one list build, asynchronously;
+        read them back with readback / frame_checksums / readback_reduced, readback_depth and readback_labels."""
+        _check(lib().dg_submit_bundle_views(self._h, slot, views, states, len(views) if n is None else n, what))
+
+    def bundle_lists(self, slot: int, frames, owners, what: int):
+        """dg_bundle_lists: a bundle of caller-built lists (owners: their owner tags, needed with DG_BUNDLE_LABELS, else None); waits."""
+        op, keep = owner_pointers(owners) if owners is not None else (None, None)
+        _check(lib().dg_bundle_lists(self._h, slot, frames, op, len(frames), what))
+
+    def bundle_capacity(self, what: int) -> int:
+        """dg_bundle_capacity: the largest n one bundle submission of `what` may carry."""
+        return _check(lib().dg_bundle_capacity(self._h, what))
+
+    def bundle_timing(self, slot: int) -> dict:
+        """dg_slot_bundle_timing: GPU time (ms) of the colour kernels and of dg_bundle_tiles of the slot's last (bundle) submission."""
+        a, b, t = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        _check(lib().dg_slot_bundle_timing(self._h, slot, ctypes.byref(a), ctypes.byref(b), ctypes.byref(t)))
+        return {"setup_ms": a.value, "raster_ms": b.value, "tiles_ms": t.value}
 
     def wait(self, slot: int):
         _check(lib().dg_wait(self._h, slot))

@@ -15,6 +15,8 @@
 //             label frames (DG_FE_LABELS): likewise, the framebuffer slab holds uint16 id[F][H][W], then uint8 cls[F][H][W]; the owner tags
 //             parallel to the list slab's wall records and the box table [max_batch][map objects] are buffers of the slot's own,
 //             allocated by its first label submission (the box table again after dg_upload_scene)
+//             bundles (DG_FE_BUNDLE): the host lists in the list slab; the framebuffer slab holds the requested parts, RGB24 frames first,
+//             as slab_layout.h's bundle_layout places them; owner tags and box table as for label frames
 //   per ctx : 2-D map view layer 3*W*H bytes RGB24 (allocated by the first map submission, rebuilt after every dg_upload_scene)
 //             DG_FE_DEVICE column scratch [F][slot][W]: compact spans 16 B (48 slots), wall-record columns 8 B (48 slots),
 //             counts, sky event bits — shared by the slots because their kernels run back to back
@@ -36,6 +38,7 @@
 #include "../../include/doomgpu.h"
 #include "api_common.hpp"
 #include "binner.hpp"
+#include "bundle_kernels.hpp"
 #include "depth_kernels.hpp"
 #include "fe_kernels.hpp"
 #include "fs_kernels.hpp"
@@ -68,6 +71,9 @@ struct Slot {
     // timing events, attached to the dispatches themselves (kernels.hpp): first / last front-end kernel, raster launch; ev_raster is also
     // what "the slot's kernels are done" is waited on
     hipEvent_t ev_start = nullptr, ev_setup = nullptr, ev_rstart = nullptr, ev_raster = nullptr, ev_h2d = nullptr;
+    // bundles: the end of the colour raster launch when dg_bundle_tiles follows it (ev_raster is then that kernel's end: always the end of
+    // the submission's LAST kernel), and dg_bundle_tiles' start
+    hipEvent_t ev_cend = nullptr, ev_tiles = nullptr;
     // ev_raster has been recorded at least once: slot_sync waits only on an event that has.  Not part of the phase below, because it is
     // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
     bool raster_recorded = false;
@@ -127,8 +133,10 @@ struct Slot {
     // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
     // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP (2-D map frames: arrow lines at the start of d_lists) or
     // DG_FE_DEPTH (host lists walked by dg_depth_tiles: the framebuffer slab holds the two planes, not RGB24) or DG_FE_LABELS (host lists
-    // walked by dg_label_tiles: the slab holds the id and class planes)
+    // walked by dg_label_tiles: the slab holds the id and class planes) or DG_FE_BUNDLE (host lists run through the colour kernels and / or
+    // dg_bundle_tiles: the slab holds the parts bundle_what names, laid out by bundle_layout)
     int32_t front_end = DG_FE_HOST;
+    uint32_t bundle_what = 0;     // DG_BUNDLE_* of the last submission when it was a bundle
     // A new submission of n frames through front end fe, `bytes` of lists or records uploaded for it (span statistics: the host list path's alone)
     void describe(int32_t fe, int n, uint64_t bytes, uint64_t walls, uint64_t planes) {
         front_end = fe; phase = Phase::Prepared; n_frames = n; list_bytes = bytes; n_walls = walls; n_planes = planes;
@@ -138,6 +146,8 @@ struct Slot {
     bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
     bool holds_depth() const { return front_end == DG_FE_DEPTH && phase != Phase::Empty; }     // the framebuffer slab is the two depth planes
     bool holds_labels() const { return front_end == DG_FE_LABELS && phase != Phase::Empty; }   // ... the two label planes
+    bool holds_bundle() const { return front_end == DG_FE_BUNDLE && phase != Phase::Empty; }   // ... the parts of a bundle (bundle_what)
+    bool bundle_has(uint32_t part) const { return holds_bundle() && (bundle_what & part) != 0; }
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
     bool map_built = false;       // a map submission whose enqueue built the ctx's map layer (ev_start .. ev_setup time that)
     std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
@@ -309,7 +319,7 @@ void free_ctx(dg_ctx *c) {
     for (Slot &s : c->slots) {
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         if (s.copy_stream) (void)hipStreamSynchronize(s.copy_stream);
-        for (hipEvent_t ev : {s.ev_start, s.ev_setup, s.ev_raster, s.ev_rstart, s.ev_h2d})
+        for (hipEvent_t ev : {s.ev_start, s.ev_setup, s.ev_raster, s.ev_rstart, s.ev_h2d, s.ev_cend, s.ev_tiles})
             if (ev) (void)hipEventDestroy(ev);
         if (s.copy_stream) (void)hipStreamDestroy(s.copy_stream);
         if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -389,17 +399,18 @@ void fill_walk_params(dg_ctx *c, Slot &s, int n) {
 }
 
 // Build + bin the lists of n views in parallel, pack them into the slot's pinned slab, fill slot.P.  fe: what the submission is described
-// as — DG_FE_HOST, DG_FE_DEPTH when dg_depth_tiles will walk the lists, or DG_FE_LABELS when dg_label_tiles will: then the owner tags of
-// the wall records go into the slot's owner array as well (the caller has allocated it), from given_owners[i] for the caller's lists.
+// as — DG_FE_HOST, DG_FE_DEPTH when dg_depth_tiles will walk the lists, DG_FE_LABELS when dg_label_tiles will, or DG_FE_BUNDLE.  A label
+// submission, and a bundle that says so (want_owners), needs owner tags: the tags of the wall records then go into the slot's owner array
+// as well (the caller has allocated it), from given_owners[i] for the caller's lists.
 int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, int32_t fe = DG_FE_HOST,
-                     const uint32_t *const *given_owners = nullptr) {
+                     const uint32_t *const *given_owners = nullptr, bool want_owners = false) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
     const int W = c->cfg.width, H = c->cfg.height;
     std::vector<int> rc((size_t)n, 0);
     std::vector<std::string> errs((size_t)n);
-    const bool labels = fe == DG_FE_LABELS;
+    const bool labels = fe == DG_FE_LABELS || want_owners;         // this submission needs owner tags
     if (labels && c->label_tags.size() < (size_t)n) c->label_tags.resize((size_t)n);
     c->pool->parallel_for(n, [&](int i, int wid) {
         BinnedFrame &bf = c->binned[(size_t)i];
@@ -1059,8 +1070,12 @@ int check_slot(dg_ctx *c, int slot) {
 }
 
 // The calls that read the framebuffer slab as RGB24 frames, or run the colour kernels again, on a slot whose last submission was depth.
-// ... or a label submission.
+// ... or a label submission, or a bundle without colour.
 int refuse_depth(const Slot &s, const char *what) {
+    if (s.holds_bundle()) {                               // a bundle's colour frames sit at the slab's base, as after a colour submission
+        if (s.bundle_has(BUNDLE_COLOUR)) return DG_OK;
+        return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds a bundle without a colour part (DG_BUNDLE_COLOUR)");
+    }
     if (s.holds_labels()) return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds label planes, not RGB24 frames (dg_readback_labels)");
     if (!s.holds_depth()) return DG_OK;
     return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds depth planes, not RGB24 frames (dg_readback_depth)");
@@ -1120,6 +1135,84 @@ int submit_labels(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     s.raster_recorded = true;
     s.phase = Slot::Phase::Queued;
     return DG_OK;
+}
+
+int check_bundle_what(uint32_t what) {
+    if (what == 0 || (what & ~BUNDLE_ALL)) return set_err(DG_ERR_INVALID, "what must be a non-empty set of DG_BUNDLE_COLOUR, DG_BUNDLE_DEPTH, DG_BUNDLE_LABELS");
+    return DG_OK;
+}
+
+int bundle_capacity_of(const dg_ctx *c, uint32_t what) {
+    return (int)bundle_capacity((size_t)c->cfg.max_batch, (size_t)c->cfg.width, (size_t)c->cfg.height, what);
+}
+
+// The kernels of the bundle the slot describes (build_batch_host has queued its uploads on the slot's stream), on the ctx's kernel
+// stream behind every earlier submission's, as enqueue_kernels does: the colour kernels of the host list route when colour is asked
+// for — P.fb is the slab's base — then the clearing of the box rows and dg_bundle_tiles when a plane is.  ev_raster goes to whichever
+// kernel is the last.  A HIP call that fails half way leaves the slot empty.
+int enqueue_bundle(dg_ctx *c, Slot &s) {
+    hipStream_t ks = c->kstream;
+    struct Invalidate {
+        Slot &s; bool armed = true;
+        ~Invalidate() { if (armed) s.reset(); }
+    } guard{s};
+    const uint32_t what = s.bundle_what;
+    const bool colour = (what & BUNDLE_COLOUR) != 0, tiles = (what & (BUNDLE_DEPTH | BUNDLE_LABELS)) != 0;
+    HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
+    HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
+    if (colour) {
+        HIP_TRY(launch_setup(s.P, s.max_spans, ks, s.ev_start, s.ev_setup));
+        HIP_TRY(launch_raster(s.P, ks, s.ev_rstart, tiles ? s.ev_cend : s.ev_raster));
+    }
+    if (tiles) {
+        const BundleLayout L = bundle_layout((size_t)s.n_frames, (size_t)c->cfg.width, (size_t)c->cfg.height, what);
+        uint8_t *const fb = s.d_fb.get();
+        BundlePlanes out{};
+        if (what & BUNDLE_DEPTH) { out.dist = reinterpret_cast<int16_t *>(fb + L.distance); out.kind = fb + L.kind; }
+        if (what & BUNDLE_LABELS) {
+            out.id = reinterpret_cast<uint16_t *>(fb + L.id); out.cls = fb + L.cls;
+            out.boxes = s.d_boxes.get(); out.n_mobjs = (uint32_t)s.box_mobjs;
+        }
+        HIP_TRY(launch_bundle(s.P, s.d_owners.get(), out, what, ks, s.ev_tiles, s.ev_raster));
+    }
+    guard.armed = false;
+    s.harvested = true;                                   // (never DG_FE_AUTO's measurement)
+    s.raster_recorded = true;
+    s.phase = Slot::Phase::Queued;
+    return DG_OK;
+}
+
+// Slot `slot` for a bundle of n views (or of the caller's lists, with their owner tags when labels are asked for): the host list path
+// whatever front end the ctx has, one list build and one upload for every part.
+int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, const uint32_t *const *owners, int n, const dg_view_state *states,
+                  uint32_t what) {
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    Slot &s = c->slots[(size_t)slot];
+    if (const int bad = check_batch(c, n)) return bad;
+    if (n > bundle_capacity_of(c, what)) return set_err(DG_ERR_CAPACITY, "bundle: the parts of that many views do not fit the slot's framebuffer slab (dg_bundle_capacity)");
+    const bool labels = (what & BUNDLE_LABELS) != 0;
+    std::string err;
+    int rc;
+    if (labels && (rc = check_label_scene(*c->scene, err))) return set_err(rc, err);
+    if ((rc = take_slot(c, s))) return rc;
+    if (labels) {
+        const size_t n_mobjs = c->scene->mobjs.size();
+        if (!s.d_owners) {
+            HIP_TRY(hip_alloc(s.h_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
+            HIP_TRY(hip_alloc(s.d_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
+        }
+        if (!s.d_boxes || s.box_mobjs != n_mobjs) {
+            HIP_TRY(hip_alloc(s.d_boxes, std::max<size_t>((size_t)c->cfg.max_batch * n_mobjs, 1) * sizeof(LabelRawBox)));
+            s.box_mobjs = n_mobjs;
+        }
+    }
+    rc = build_batch_host(c, s, views, given, n, states, DG_FE_BUNDLE, owners, labels);
+    if (rc) {
+        if (s.phase == Slot::Phase::Prepared && s.front_end == DG_FE_BUNDLE) s.reset();   // (described, then an upload failed: nothing says yet which parts it has)
+        return rc;
+    }
+    s.bundle_what = what;
+    return enqueue_bundle(c, s);
 }
 
 int check_view_states(const dg_view_state *states, int n) {
@@ -1222,7 +1315,7 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
     }
     for (Slot &s : c->slots) {
         CTX_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-        for (hipEvent_t *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart}) CTX_TRY(hipEventCreate(ev));
+        for (hipEvent_t *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles}) CTX_TRY(hipEventCreate(ev));
         CTX_TRY(hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming));
         CTX_TRY(hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking));
         CTX_TRY(hip_alloc(s.h_lists, lists_cap));
@@ -1512,6 +1605,7 @@ int dg_replay_slot(dg_ctx *c, int slot) {
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
     if (s.phase == Slot::Phase::Empty) return set_err(DG_ERR_INVALID, "slot has no prepared lists");
+    if (s.holds_bundle()) return set_err(DG_ERR_INVALID, "dg_replay_slot: the slot holds a bundle (submit it again)");
     if ((rc = refuse_depth(s, "dg_replay_slot"))) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
     // A dg_readback_async may still be reading the framebuffer these kernels are about to overwrite, and a column-walk submission that
@@ -1543,15 +1637,21 @@ int dg_readback_depth(dg_ctx *c, int slot, int first, int count, int16_t *distan
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if (!s.holds_depth()) return set_err(DG_ERR_INVALID, "dg_readback_depth: the slot's last submission is not a depth submission");   // (a label slot included)
+    if (s.holds_bundle() && !s.bundle_has(BUNDLE_DEPTH)) return set_err(DG_ERR_INVALID, "dg_readback_depth: the slot's bundle has no depth part (DG_BUNDLE_DEPTH)");
+    if (!s.holds_depth() && !s.holds_bundle()) return set_err(DG_ERR_INVALID, "dg_readback_depth: the slot's last submission is not a depth submission");   // (a label slot included)
     if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     if (count == 0) return DG_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
     rc = make_final(c, s, Copy::Leave);
     if (rc) return rc;
     const size_t px = (size_t)c->cfg.width * (size_t)c->cfg.height;
-    const int16_t *const d_dist = reinterpret_cast<const int16_t *>(s.d_fb.get());
-    const uint8_t *const d_kind = s.d_fb.get() + 2 * (size_t)s.n_frames * px;
+    size_t at_dist = 0, at_kind = 2 * (size_t)s.n_frames * px;          // a depth submission's planes; a bundle's are where its layout puts them
+    if (s.holds_bundle()) {
+        const BundleLayout L = bundle_layout((size_t)s.n_frames, (size_t)c->cfg.width, (size_t)c->cfg.height, s.bundle_what);
+        at_dist = L.distance; at_kind = L.kind;
+    }
+    const int16_t *const d_dist = reinterpret_cast<const int16_t *>(s.d_fb.get() + at_dist);
+    const uint8_t *const d_kind = s.d_fb.get() + at_kind;
     if (distance) HIP_TRY(hipMemcpyAsync(distance, d_dist + (size_t)first * px, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream));
     if (kind) HIP_TRY(hipMemcpyAsync(kind, d_kind + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(slot_sync(s));
@@ -1588,7 +1688,8 @@ int dg_readback_labels(dg_ctx *c, int slot, int first, int count, uint16_t *id, 
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if (!s.holds_labels()) return set_err(DG_ERR_INVALID, "dg_readback_labels: the slot's last submission is not a label submission");
+    if (s.holds_bundle() && !s.bundle_has(BUNDLE_LABELS)) return set_err(DG_ERR_INVALID, "dg_readback_labels: the slot's bundle has no label part (DG_BUNDLE_LABELS)");
+    if (!s.holds_labels() && !s.holds_bundle()) return set_err(DG_ERR_INVALID, "dg_readback_labels: the slot's last submission is not a label submission");
     if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     if (count == 0) return DG_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -1596,8 +1697,13 @@ int dg_readback_labels(dg_ctx *c, int slot, int first, int count, uint16_t *id, 
     if (rc) return rc;
     const int W = c->cfg.width, H = c->cfg.height;
     const size_t px = (size_t)W * (size_t)H;
-    const uint16_t *const d_id = reinterpret_cast<const uint16_t *>(s.d_fb.get());
-    const uint8_t *const d_cls = s.d_fb.get() + 2 * (size_t)s.n_frames * px;
+    size_t at_id = 0, at_cls = 2 * (size_t)s.n_frames * px;             // a label submission's planes; a bundle's are where its layout puts them
+    if (s.holds_bundle()) {
+        const BundleLayout L = bundle_layout((size_t)s.n_frames, (size_t)W, (size_t)H, s.bundle_what);
+        at_id = L.id; at_cls = L.cls;
+    }
+    const uint16_t *const d_id = reinterpret_cast<const uint16_t *>(s.d_fb.get() + at_id);
+    const uint8_t *const d_cls = s.d_fb.get() + at_cls;
     std::vector<LabelRawBox> raw(boxes ? (size_t)count * s.box_mobjs : 0);
     if (id) HIP_TRY(hipMemcpyAsync(id, d_id + (size_t)first * px, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream));
     if (cls) HIP_TRY(hipMemcpyAsync(cls, d_cls + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream));
@@ -1638,6 +1744,47 @@ int dg_slot_label_timing(dg_ctx *c, int slot, float *tiles_ms, float *boxes_ms) 
     if (rc) return rc;
     if (tiles_ms) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_rstart, s.ev_setup));
     if (boxes_ms) HIP_TRY(hipEventElapsedTime(boxes_ms, s.ev_setup, s.ev_raster));
+    return DG_OK;
+}
+
+int dg_bundle_capacity(const dg_ctx *c, uint32_t what) {
+    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
+    const int rc = check_bundle_what(what);
+    return rc ? rc : bundle_capacity_of(c, what);
+}
+
+int dg_submit_bundle_views(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, int n, uint32_t what) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!views) return set_err(DG_ERR_INVALID, "null views");
+    if ((rc = check_bundle_what(what))) return rc;
+    rc = check_view_states(states, n);
+    if (rc) return rc;
+    return submit_bundle(c, slot, views, nullptr, nullptr, n, states, what);
+}
+
+int dg_bundle_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uint32_t *const *owners, int n, uint32_t what) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!frames) return set_err(DG_ERR_INVALID, "null frames");
+    if ((rc = check_bundle_what(what))) return rc;
+    if ((what & BUNDLE_LABELS) && !owners) return set_err(DG_ERR_INVALID, "null owners: DG_BUNDLE_LABELS needs the owner tags");
+    rc = submit_bundle(c, slot, nullptr, frames, owners, n, nullptr, what);
+    return rc ? rc : dg_wait(c, slot);
+}
+
+int dg_slot_bundle_timing(dg_ctx *c, int slot, float *setup_ms, float *raster_ms, float *tiles_ms) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.holds_bundle() || !s.has_run()) return set_err(DG_ERR_INVALID, "dg_slot_bundle_timing: the slot's last submission is not a bundle that ran");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    rc = make_final(c, s, Copy::Leave);
+    if (rc) return rc;
+    const bool colour = (s.bundle_what & BUNDLE_COLOUR) != 0, tiles = (s.bundle_what & (BUNDLE_DEPTH | BUNDLE_LABELS)) != 0;
+    if (setup_ms) { *setup_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(setup_ms, s.ev_start, s.ev_setup)); }
+    if (raster_ms) { *raster_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(raster_ms, s.ev_rstart, tiles ? s.ev_cend : s.ev_raster)); }
+    if (tiles_ms) { *tiles_ms = 0.0f; if (tiles) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_tiles, s.ev_raster)); }
     return DG_OK;
 }
 
@@ -1762,11 +1909,19 @@ int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
     if (rc) return rc;
     std::memset(out, 0, sizeof *out);
     out->front_end = s.front_end;
-    HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
-    if (s.front_end != DG_FE_DEPTH && s.front_end != DG_FE_LABELS && (s.front_end != DG_FE_MAP || s.map_built)) {   // (a map submission has a front-end half only when it built the map layer, a depth or label submission none)
+    if (s.front_end == DG_FE_BUNDLE) {                    // setup_ms / raster_ms: the colour kernels (0 without colour); total_ms: first kernel's start .. last kernel's end
+        const bool colour = (s.bundle_what & BUNDLE_COLOUR) != 0, tiles = (s.bundle_what & (BUNDLE_DEPTH | BUNDLE_LABELS)) != 0;
+        if (colour) {
+            HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
+            HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, tiles ? s.ev_cend : s.ev_raster));
+        }
+        HIP_TRY(hipEventElapsedTime(&out->total_ms, colour ? s.ev_start : s.ev_tiles, s.ev_raster));
+    } else if (s.front_end != DG_FE_DEPTH && s.front_end != DG_FE_LABELS && (s.front_end != DG_FE_MAP || s.map_built)) {   // (a map submission has a front-end half only when it built the map layer, a depth or label submission none)
+        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
         HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
         HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));
     } else {
+        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
         out->total_ms = out->raster_ms;
     }
     out->n_spans = s.n_spans; out->n_frames = (uint64_t)s.n_frames; out->covered_pixels = s.covered;

@@ -46,6 +46,36 @@ inline ListLayout list_layout(size_t n_frames, size_t W, size_t walls, size_t pl
     return L;
 }
 
+// Framebuffer slab of a bundle submission (include/doomgpu.h: dg_bundle_*) of n frames: the parts `what` names (bit 0 colour, bit 1
+// depth, bit 2 labels: DG_BUNDLE_*), in this order — RGB24 colour 3nWH | int16 distance 2nWH | uint8 kind nWH | uint16 id 2nWH | uint8 cls
+// nWH.  Each part starts on the slab's boundary, which also keeps the 16-bit planes aligned when 3nWH is odd.  A part that is not there
+// has offset == total.
+struct BundleLayout { size_t colour, distance, kind, id, cls, total; };
+inline BundleLayout bundle_layout(size_t n, size_t W, size_t H, uint32_t what) {
+    const size_t px = n * W * H;
+    const bool colour = (what & 1u) != 0, depth = (what & 2u) != 0, labels = (what & 4u) != 0;
+    SlabCursor c;
+    BundleLayout L{};
+    if (colour) L.colour = c.take(3 * px);
+    if (depth) { L.distance = c.take(2 * px); L.kind = c.take(px); }
+    if (labels) { L.id = c.take(2 * px); L.cls = c.take(px); }
+    L.total = c.end();
+    if (!colour) L.colour = L.total;
+    if (!depth) L.distance = L.kind = L.total;
+    if (!labels) L.id = L.cls = L.total;
+    return L;
+}
+// The largest n <= max_batch whose bundle fits a framebuffer slab of max_batch RGB24 frames (0: not even one frame does).
+inline size_t bundle_capacity(size_t max_batch, size_t W, size_t H, uint32_t what) {
+    const size_t slab = max_batch * 3 * W * H;
+    size_t lo = 0, hi = max_batch;                           // bundle_layout(lo) fits; total grows with n
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo + 1) / 2;
+        if (bundle_layout(mid, W, H, what).total <= slab) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 // Record slab of the device column walk as the host walker packs it (DG_FE_DEVICE): one H2D copy of [0, total).
 struct FeLayout { size_t frames, fframes, parts, sprites, behind, sky, bin_off, sbin_off, bins, sbins, order, total; };
 inline FeLayout fe_layout(size_t n_frames, size_t W, size_t parts, size_t sprites, size_t behind, size_t skies, size_t bins, size_t sbins) {

@@ -425,6 +425,54 @@ int dg_slot_label_timing(dg_ctx *ctx, int slot, float *tiles_ms, float *boxes_ms
 int dg_label_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, const uint32_t *const *owners, int n,
                         uint16_t *id, uint8_t *cls, dg_label_box *boxes);
 
+/* ---- bundle submissions: colour, depth and labels of the same views from one list build -------------------------------------------- */
+/* A caller who wants more than one picture of a view pays host list generation, the upload and a walk over the spans once per picture
+ * when each is a submission of its own.  A bundle is ONE submission for any non-empty subset `what` of
+ *   DG_BUNDLE_COLOUR  the RGB24 frames of dg_submit_views_state
+ *   DG_BUNDLE_DEPTH   the distance and kind planes of a depth submission
+ *   DG_BUNDLE_LABELS  the id and class planes and the boxes of a label submission
+ * of the same n views: one list build, one upload, the colour kernels of the host list route (only with DG_BUNDLE_COLOUR), and one
+ * kernel, dg_bundle_tiles, that walks the spans once for all the other planes and the boxes.  Every part is byte for byte what its own
+ * submission gives.
+ * Layout in the slot's framebuffer slab (dg_slot_framebuffer), which keeps its size of max_batch * 3*W*H bytes: the requested parts in
+ * the order  RGB24 colour 3nWH | int16 distance 2nWH | uint8 kind nWH | uint16 id 2nWH | uint8 cls nWH,  each starting on a 256-byte
+ * boundary; dg_bundle_layout gives the byte offsets, a part not in `what` has offset == total.  One submission therefore carries at most
+ * dg_bundle_capacity(ctx, what) views: the largest n <= max_batch whose total fits the slab — max_batch for colour alone, about
+ * max_batch / 3 for all three parts (it can be 0 for a small max_batch).
+ * A bundle always takes the host list route, like depth and label submissions; the box table and the owner array are the slot's lazily
+ * allocated ones of the label route.  There is no readback call of its own.  On a slot that holds a bundle:
+ *   dg_readback(_async), dg_frame_checksums, dg_readback_reduced(_async)   see the colour frames; DG_ERR_INVALID when `what` has no colour
+ *   dg_readback_depth, dg_readback_labels   read the bundle's planes (and boxes); DG_ERR_INVALID when that part was not asked for
+ *   dg_replay_slot                          DG_ERR_INVALID (dg_prepare_views is a new submission and replaces the bundle, as on a depth slot)
+ *   dg_slot_timing                          front_end = DG_FE_BUNDLE, setup_ms / raster_ms = the colour kernels (0 without colour),
+ *                                           total_ms = first kernel's start .. last kernel's end
+ *   dg_wait, dg_slot_framebuffer, dg_upload_scene and every new submission work as usual. */
+#define DG_FE_BUNDLE 7                      /* dg_timing.front_end of a bundle submission; never a dg_config.front_end */
+#define DG_BUNDLE_COLOUR 1u
+#define DG_BUNDLE_DEPTH  2u                 /* distance + kind planes   */
+#define DG_BUNDLE_LABELS 4u                 /* id + cls planes + boxes  */
+typedef struct dg_bundle_offsets { uint64_t colour, distance, kind, id, cls, total; } dg_bundle_offsets;   /* byte offsets in the slot's slab */
+/* Pure: no ctx, no GPU.  DG_ERR_INVALID: out == NULL, width or height outside [1, 16384], n <= 0, what == 0 or with unknown bits. */
+int dg_bundle_layout(int width, int height, int n, uint32_t what, dg_bundle_offsets *out);
+/* The largest n one bundle submission of `what` may carry on this ctx (>= 0); DG_ERR_INVALID: a NULL ctx, a bad `what`. */
+int dg_bundle_capacity(const dg_ctx *ctx, uint32_t what);
+/* Asynchronous, like dg_submit_views_state (states may be NULL): effects, thinkers and per-view snapshots apply as everywhere.
+ * DG_ERR_CAPACITY, before the slot is touched: n outside [1, dg_bundle_capacity(ctx, what)]; with DG_BUNDLE_LABELS also dg_label_lists'
+ * scene limit.  DG_ERR_INVALID: a bad `what`, NULL views. */
+int dg_submit_bundle_views(dg_ctx *ctx, int slot, const dg_view *views, const dg_view_state *states, int n, uint32_t what);
+/* The same for caller-built lists; owners (dg_label_lists' owner tags) is needed iff `what` has DG_BUNDLE_LABELS and is not read
+ * otherwise.  Refused tags are DG_ERR_INVALID before anything is launched: the slot keeps its earlier content.  Synchronous like
+ * dg_draw_lists, up to and including dg_wait: what is left to do is the readback of the parts. */
+int dg_bundle_lists(dg_ctx *ctx, int slot, const dg_frame_lists *frames, const uint32_t *const *owners, int n, uint32_t what);
+/* The fused per-pixel rule on the CPU: the planes and boxes the bundle's kernel writes, for caller-built lists; needs no ctx and no GPU
+ * and is what the kernel is tested against next to dg_depth_lists_host and dg_label_lists_host, which it equals.  Any output may be
+ * NULL; owners is needed iff id, cls or boxes is asked for.  Errors as those two calls. */
+int dg_bundle_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, const uint32_t *const *owners, int n,
+                         int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes);
+/* GPU time of the slot's last (bundle) submission from the events attached to its dispatches: the two colour kernels (0 without
+ * DG_BUNDLE_COLOUR) and dg_bundle_tiles (0 for colour alone); any output may be NULL. */
+int dg_slot_bundle_timing(dg_ctx *ctx, int slot, float *setup_ms, float *raster_ms, float *tiles_ms);
+
 /* ---- 2-D map view (reference: Game::render with viewing_map, src/game.rs:491-499, 229-309) --------------------------------- */
 /* What the window holds after render() in map mode, RGB24 like every frame: black; every linedef without DONTDRAW (flags & 128) in
  * LINEDEFS order, yellow (255, 255, 0) when TWOSIDED (flags & 4) else red (255, 0, 0); then the player arrow in yellow: P->E, R->E, L->E.
@@ -490,7 +538,7 @@ const char *dg_last_error(void); /* thread-local message of the last failing cal
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
@@ -500,7 +548,7 @@ typedef struct dg_timing {
     float host_ms;            /* host list generation + binning + packing of that submission (wall clock) */
     uint64_t n_spans, n_frames, covered_pixels;
     uint64_t n_walls, n_planes, list_bytes; /* drawn records / visplanes, bytes of lists copied to HBM */
-    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH, DG_FE_LABELS): what that submission actually used; with DG_FE_DEVICE setup_ms is
+    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH, DG_FE_LABELS, DG_FE_BUNDLE): what that submission actually used; with DG_FE_DEVICE setup_ms is
                                  the column walk (dg_fe_columns, dg_fe_gaps, dg_fe_scan, dg_fe_scatter), n_walls = wall records,
                                  n_planes = sprites, covered_pixels is not tracked (0) */
 } dg_timing;
