@@ -1,7 +1,7 @@
 // api_scene.cpp — the entry points of the C-ABI (include/doomgpu.h) that need no GPU: the error string and the version, the scene
 // (dg_scene_*), one frame's lists and map lines on the host, the recorded walks, the box downscale on the host (dg_reduced_size,
-// dg_reduce_host), the depth planes and the label planes and boxes of caller-built lists on the host (dg_depth_lists_host,
-// dg_label_lists_host), a bundle's slab layout and its fused rule on the host (dg_bundle_layout, dg_bundle_lists_host).  Everything that
+// dg_reduce_host), the depth planes, the label planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host,
+// dg_label_lists_host, dg_bundle_lists_host: one rule, plane_lists_host), a bundle's slab layout (dg_bundle_layout).  Everything that
 // takes a dg_ctx: context.cpp.
 #include <algorithm>
 #include <cstring>
@@ -10,10 +10,8 @@
 
 #include "api_common.hpp"
 #include "binner.hpp"
-#include "bundle_core.h"
-#include "depth_core.h"
 #include "frontend.hpp"
-#include "label_core.h"
+#include "plane_core.h"
 #include "reduce_core.h"
 #include "slab_layout.h"
 #include "walk.hpp"
@@ -28,25 +26,93 @@ static FrameArena &lists_arena() {
     return arena;
 }
 
-// The spans of a column laid on in draw order as in dg_depth_lists_host and dg_label_lists_host, bundle_core.h per pixel — the rule
-// dg_bundle_tiles evaluates, with the parts the outputs ask for — then the boxes by a plain scan of the label planes.
+// The spans of a column laid on in draw order, each row of a span that writes overwriting what is there (the plane walk of
+// plane_kernels.hip reads the same order backwards): plane_core.h per pixel, with the parts the outputs ask for.
 template <bool DEPTH, bool LABELS>
-static void bundle_frame_host(const BinnedFrame &bf, const uint32_t *tags, const DevScene &ds, const DevConsts &dk, size_t W, int16_t *dist, uint8_t *kd,
-                              uint16_t *idp, uint8_t *clp) {
+static void plane_frame_host(const BinnedFrame &bf, const uint32_t *tags, const DevScene &ds, const DevConsts &dk, size_t W, int16_t *dist, uint8_t *kd,
+                             uint16_t *idp, uint8_t *clp) {
     for (size_t x = 0; x < W; x++)
         for (uint32_t j = bf.col_off[x]; j < bf.col_off[x + 1]; j++) {
             const DevSpan &sp = bf.spans[j];
-            const BundleRSpan r = bundle_resolve_span<DEPTH, LABELS>(sp, bf.hdr, bf.walls.data(), bf.planes.data(), tags, ds, dk);
+            const PlaneSpan<DEPTH, LABELS> r = plane_resolve_span<DEPTH, LABELS>(sp, bf.hdr, bf.walls.data(), bf.planes.data(), tags, ds, dk);
             for (int32_t y = sp.ctop; y <= sp.cbot; y++) {
                 int32_t d;
                 uint32_t k, label;
-                if (!bundle_span_writes<DEPTH>(r, ds, dk, y, d, k, label)) continue;
+                if (!plane_span_writes<DEPTH>(r, ds, dk, y, d, k, label)) continue;
                 const size_t px = (size_t)y * W + x;
                 if (dist) dist[px] = (int16_t)d;
                 if (kd) kd[px] = (uint8_t)k;
                 if (LABELS) { idp[px] = (uint16_t)label_index(label); clp[px] = (uint8_t)label_class(label); }
             }
         }
+}
+
+// dg_depth_lists_host, dg_label_lists_host and dg_bundle_lists_host: the binner (the same column-major, draw-ordered spans the GPU
+// walks) and plane_frame_host for any subset of the five outputs, then the boxes by a plain scan of the label planes.  `labels`: the
+// caller's lists come with owner tags, which are then checked (and the scene with them) whether or not a label output is there.  Every
+// frame is checked before anything is written.
+static int plane_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, const uint32_t *const *owners, int n, bool labels,
+                            int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
+    const bool depth = distance || kind;
+    if (!s || !frames) return set_err(DG_ERR_INVALID, "null argument");
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384]");
+    if (n < 0) return set_err(DG_ERR_INVALID, "bad frame count");
+    const Scene &sc = *s->sc;
+    std::string err;
+    int rc = labels ? check_label_scene(sc, err) : DG_OK;
+    if (rc) return set_err(rc, err);
+    const FrameConsts fk = make_consts(width, height);
+    const DevConsts dk{fk.ARC, fk.GCFX, fk.CFX, fk.CFY, width, height};
+    const BitmapInfo &sky = sc.bitmaps[(size_t)sc.sky_bitmap];
+    const DevScene ds{nullptr, nullptr, sc.texel_idx.data(), sc.texel_opq.data(), nullptr, sky.texel_off, sky.w, sky.h, sky.has_holes};
+    const size_t W = (size_t)width, H = (size_t)height, px = W * H, n_mobjs = sc.mobjs.size();
+    std::vector<BinnedFrame> binned((size_t)n);
+    std::vector<std::vector<uint32_t>> tags((size_t)n);
+    for (int f = 0; f < n; f++) {
+        dg_frame_lists fl = frames[f];
+        fill_view_trig(fl.view);
+        rc = bin_frame(sc, fk, fl, binned[(size_t)f], err);
+        if (!rc && labels) rc = wall_owners(sc, fl, owners[f], tags[(size_t)f], err);
+        if (rc) return set_err(rc, "frame " + std::to_string(f) + ": " + err);
+    }
+    std::vector<uint16_t> idp(labels ? px : 0);
+    std::vector<uint8_t> clp(labels ? px : 0);
+    std::vector<LabelRawBox> raw(n_mobjs);
+    for (int f = 0; f < n; f++) {
+        BinnedFrame &bf = binned[(size_t)f];
+        bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
+        int16_t *const dist = distance ? distance + (size_t)f * px : nullptr;
+        uint8_t *const kd = kind ? kind + (size_t)f * px : nullptr;
+        for (size_t i = 0; i < px; i++) {
+            if (dist) dist[i] = (int16_t)DEPTH_FAR;
+            if (kd) kd[i] = (uint8_t)KIND_NONE;
+        }
+        std::fill(idp.begin(), idp.end(), (uint16_t)0);
+        std::fill(clp.begin(), clp.end(), (uint8_t)LABEL_NONE);
+        const uint32_t *const t = tags[(size_t)f].data();
+        if (depth && labels) plane_frame_host<true, true>(bf, t, ds, dk, W, dist, kd, idp.data(), clp.data());
+        else if (depth) plane_frame_host<true, false>(bf, t, ds, dk, W, dist, kd, nullptr, nullptr);
+        else if (labels) plane_frame_host<false, true>(bf, t, ds, dk, W, nullptr, nullptr, idp.data(), clp.data());
+        if (id) std::memcpy(id + (size_t)f * px, idp.data(), px * sizeof(uint16_t));
+        if (cls) std::memcpy(cls + (size_t)f * px, clp.data(), px);
+        if (!boxes) continue;
+        std::memset(raw.data(), 0, n_mobjs * sizeof(LabelRawBox));
+        for (size_t y = 0; y < H; y++)
+            for (size_t x = 0; x < W; x++) {
+                if (clp[y * W + x] != (uint8_t)LABEL_MOBJ) continue;
+                uint32_t *const b = raw[idp[y * W + x]].w;
+                b[0]++;
+                b[1] = std::max(b[1], (uint32_t)x + 1); b[2] = std::max(b[2], (uint32_t)y + 1);
+                b[3] = std::max(b[3], (uint32_t)(W - x)); b[4] = std::max(b[4], (uint32_t)(H - y));
+            }
+        for (size_t m = 0; m < n_mobjs; m++) {
+            int32_t x0, y0, x1, y1;
+            dg_label_box &o = boxes[(size_t)f * n_mobjs + m];
+            label_box_finish(raw[m], width, height, o.pixels, x0, y0, x1, y1);
+            o.x0 = (int16_t)x0; o.y0 = (int16_t)y0; o.x1 = (int16_t)x1; o.y1 = (int16_t)y1;
+        }
+    }
+    return DG_OK;
 }
 
 extern "C" {
@@ -257,111 +323,14 @@ int dg_reduce_host(const uint8_t *src_rgb24, int width, int height, int n_frames
     return DG_OK;
 }
 
-// The binner (the same column-major, draw-ordered spans the GPU walks) and depth_core.h per pixel; here the spans of a column are laid
-// on in draw order, each row of a span that writes overwriting what is there — dg_depth_tiles reads the same order backwards.
 int dg_depth_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, int n, int16_t *distance, uint8_t *kind) {
-    if (!s || !frames) return set_err(DG_ERR_INVALID, "null argument");
-    if (width < 1 || height < 1 || width > 16384 || height > 16384) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384]");
-    if (n < 0) return set_err(DG_ERR_INVALID, "bad frame count");
-    const Scene &sc = *s->sc;
-    const FrameConsts fk = make_consts(width, height);
-    const DevConsts dk{fk.ARC, fk.GCFX, fk.CFX, fk.CFY, width, height};
-    const BitmapInfo &sky = sc.bitmaps[(size_t)sc.sky_bitmap];
-    const DevScene ds{nullptr, nullptr, sc.texel_idx.data(), sc.texel_opq.data(), nullptr, sky.texel_off, sky.w, sky.h, sky.has_holes};
-    const size_t W = (size_t)width, px = W * (size_t)height;
-    BinnedFrame bf;
-    std::string err;
-    for (int f = 0; f < n; f++) {
-        dg_frame_lists fl = frames[f];
-        fill_view_trig(fl.view);
-        const int rc = bin_frame(sc, fk, fl, bf, err);
-        if (rc) return set_err(rc, "frame " + std::to_string(f) + ": " + err);
-        bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
-        int16_t *const dist = distance ? distance + (size_t)f * px : nullptr;
-        uint8_t *const kd = kind ? kind + (size_t)f * px : nullptr;
-        for (size_t i = 0; i < px; i++) {
-            if (dist) dist[i] = (int16_t)DEPTH_FAR;
-            if (kd) kd[i] = (uint8_t)KIND_NONE;
-        }
-        for (size_t x = 0; x < W; x++)
-            for (uint32_t j = bf.col_off[x]; j < bf.col_off[x + 1]; j++) {
-                const DevSpan &sp = bf.spans[j];
-                const DevRSpan r = depth_resolve_span(sp, bf.hdr, bf.walls.data(), bf.planes.data(), ds, dk);
-                for (int32_t y = sp.ctop; y <= sp.cbot; y++) {
-                    int32_t d;
-                    uint32_t k;
-                    if (!depth_span_writes(r, ds, dk, y, d, k)) continue;
-                    if (dist) dist[(size_t)y * W + x] = (int16_t)d;
-                    if (kd) kd[(size_t)y * W + x] = (uint8_t)k;
-                }
-            }
-    }
-    return DG_OK;
+    return plane_lists_host(s, width, height, frames, nullptr, n, false, distance, kind, nullptr, nullptr, nullptr);
 }
 
-// As dg_depth_lists_host: the binner's spans laid on per column in draw order, label_core.h per pixel; then the boxes of the planes.
 int dg_label_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, const uint32_t *const *owners, int n,
                         uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
     if (!s || !frames || !owners) return set_err(DG_ERR_INVALID, "null argument");
-    if (width < 1 || height < 1 || width > 16384 || height > 16384) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384]");
-    if (n < 0) return set_err(DG_ERR_INVALID, "bad frame count");
-    const Scene &sc = *s->sc;
-    std::string err;
-    int rc = check_label_scene(sc, err);
-    if (rc) return set_err(rc, err);
-    const FrameConsts fk = make_consts(width, height);
-    const DevConsts dk{fk.ARC, fk.GCFX, fk.CFX, fk.CFY, width, height};
-    const BitmapInfo &sky = sc.bitmaps[(size_t)sc.sky_bitmap];
-    const DevScene ds{nullptr, nullptr, sc.texel_idx.data(), sc.texel_opq.data(), nullptr, sky.texel_off, sky.w, sky.h, sky.has_holes};
-    const size_t W = (size_t)width, H = (size_t)height, px = W * H, n_mobjs = sc.mobjs.size();
-    std::vector<BinnedFrame> binned((size_t)n);
-    std::vector<std::vector<uint32_t>> tags((size_t)n);
-    for (int f = 0; f < n; f++) {                                  // every frame is checked before anything is written
-        dg_frame_lists fl = frames[f];
-        fill_view_trig(fl.view);
-        rc = bin_frame(sc, fk, fl, binned[(size_t)f], err);
-        if (!rc) rc = wall_owners(sc, fl, owners[f], tags[(size_t)f], err);
-        if (rc) return set_err(rc, "frame " + std::to_string(f) + ": " + err);
-    }
-    std::vector<uint16_t> idp(px);
-    std::vector<uint8_t> clp(px);
-    std::vector<LabelRawBox> raw(n_mobjs);
-    for (int f = 0; f < n; f++) {
-        BinnedFrame &bf = binned[(size_t)f];
-        bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
-        std::fill(idp.begin(), idp.end(), (uint16_t)0);
-        std::fill(clp.begin(), clp.end(), (uint8_t)LABEL_NONE);
-        for (size_t x = 0; x < W; x++)
-            for (uint32_t j = bf.col_off[x]; j < bf.col_off[x + 1]; j++) {
-                const DevSpan &sp = bf.spans[j];
-                const DevRSpan r = label_resolve_span(sp, bf.hdr, bf.walls.data(), tags[(size_t)f].data(), ds, dk);
-                for (int32_t y = sp.ctop; y <= sp.cbot; y++) {
-                    uint32_t label;
-                    if (!label_span_writes(r, ds, dk, y, label)) continue;
-                    idp[(size_t)y * W + x] = (uint16_t)label_index(label);
-                    clp[(size_t)y * W + x] = (uint8_t)label_class(label);
-                }
-            }
-        if (id) std::memcpy(id + (size_t)f * px, idp.data(), px * sizeof(uint16_t));
-        if (cls) std::memcpy(cls + (size_t)f * px, clp.data(), px);
-        if (!boxes) continue;
-        std::memset(raw.data(), 0, n_mobjs * sizeof(LabelRawBox));
-        for (size_t y = 0; y < H; y++)
-            for (size_t x = 0; x < W; x++) {
-                if (clp[y * W + x] != (uint8_t)LABEL_MOBJ) continue;
-                uint32_t *const b = raw[idp[y * W + x]].w;
-                b[0]++;
-                b[1] = std::max(b[1], (uint32_t)x + 1); b[2] = std::max(b[2], (uint32_t)y + 1);
-                b[3] = std::max(b[3], (uint32_t)(W - x)); b[4] = std::max(b[4], (uint32_t)(H - y));
-            }
-        for (size_t m = 0; m < n_mobjs; m++) {
-            int32_t x0, y0, x1, y1;
-            dg_label_box &o = boxes[(size_t)f * n_mobjs + m];
-            label_box_finish(raw[m], width, height, o.pixels, x0, y0, x1, y1);
-            o.x0 = (int16_t)x0; o.y0 = (int16_t)y0; o.x1 = (int16_t)x1; o.y1 = (int16_t)y1;
-        }
-    }
-    return DG_OK;
+    return plane_lists_host(s, width, height, frames, owners, n, true, nullptr, nullptr, id, cls, boxes);
 }
 
 int dg_bundle_layout(int width, int height, int n, uint32_t what, dg_bundle_offsets *out) {
@@ -376,67 +345,10 @@ int dg_bundle_layout(int width, int height, int n, uint32_t what, dg_bundle_offs
 
 int dg_bundle_lists_host(const dg_scene *s, int width, int height, const dg_frame_lists *frames, const uint32_t *const *owners, int n,
                          int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
-    const bool depth = distance || kind, labels = id || cls || boxes;
+    const bool labels = id || cls || boxes;
     if (!s || !frames) return set_err(DG_ERR_INVALID, "null argument");
     if (labels && !owners) return set_err(DG_ERR_INVALID, "null owners: the label outputs need the owner tags");
-    if (width < 1 || height < 1 || width > 16384 || height > 16384) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384]");
-    if (n < 0) return set_err(DG_ERR_INVALID, "bad frame count");
-    const Scene &sc = *s->sc;
-    std::string err;
-    int rc = labels ? check_label_scene(sc, err) : DG_OK;
-    if (rc) return set_err(rc, err);
-    const FrameConsts fk = make_consts(width, height);
-    const DevConsts dk{fk.ARC, fk.GCFX, fk.CFX, fk.CFY, width, height};
-    const BitmapInfo &sky = sc.bitmaps[(size_t)sc.sky_bitmap];
-    const DevScene ds{nullptr, nullptr, sc.texel_idx.data(), sc.texel_opq.data(), nullptr, sky.texel_off, sky.w, sky.h, sky.has_holes};
-    const size_t W = (size_t)width, H = (size_t)height, px = W * H, n_mobjs = sc.mobjs.size();
-    std::vector<BinnedFrame> binned((size_t)n);
-    std::vector<std::vector<uint32_t>> tags((size_t)n);
-    for (int f = 0; f < n; f++) {                                  // every frame is checked before anything is written
-        dg_frame_lists fl = frames[f];
-        fill_view_trig(fl.view);
-        rc = bin_frame(sc, fk, fl, binned[(size_t)f], err);
-        if (!rc && labels) rc = wall_owners(sc, fl, owners[f], tags[(size_t)f], err);
-        if (rc) return set_err(rc, "frame " + std::to_string(f) + ": " + err);
-    }
-    std::vector<uint16_t> idp(labels ? px : 0);
-    std::vector<uint8_t> clp(labels ? px : 0);
-    std::vector<LabelRawBox> raw(n_mobjs);
-    for (int f = 0; f < n; f++) {
-        BinnedFrame &bf = binned[(size_t)f];
-        bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
-        int16_t *const dist = distance ? distance + (size_t)f * px : nullptr;
-        uint8_t *const kd = kind ? kind + (size_t)f * px : nullptr;
-        for (size_t i = 0; i < px; i++) {
-            if (dist) dist[i] = (int16_t)DEPTH_FAR;
-            if (kd) kd[i] = (uint8_t)KIND_NONE;
-        }
-        std::fill(idp.begin(), idp.end(), (uint16_t)0);
-        std::fill(clp.begin(), clp.end(), (uint8_t)LABEL_NONE);
-        const uint32_t *const t = tags[(size_t)f].data();
-        if (depth && labels) bundle_frame_host<true, true>(bf, t, ds, dk, W, dist, kd, idp.data(), clp.data());
-        else if (depth) bundle_frame_host<true, false>(bf, t, ds, dk, W, dist, kd, nullptr, nullptr);
-        else if (labels) bundle_frame_host<false, true>(bf, t, ds, dk, W, nullptr, nullptr, idp.data(), clp.data());
-        if (id) std::memcpy(id + (size_t)f * px, idp.data(), px * sizeof(uint16_t));
-        if (cls) std::memcpy(cls + (size_t)f * px, clp.data(), px);
-        if (!boxes) continue;
-        std::memset(raw.data(), 0, n_mobjs * sizeof(LabelRawBox));
-        for (size_t y = 0; y < H; y++)
-            for (size_t x = 0; x < W; x++) {
-                if (clp[y * W + x] != (uint8_t)LABEL_MOBJ) continue;
-                uint32_t *const b = raw[idp[y * W + x]].w;
-                b[0]++;
-                b[1] = std::max(b[1], (uint32_t)x + 1); b[2] = std::max(b[2], (uint32_t)y + 1);
-                b[3] = std::max(b[3], (uint32_t)(W - x)); b[4] = std::max(b[4], (uint32_t)(H - y));
-            }
-        for (size_t m = 0; m < n_mobjs; m++) {
-            int32_t x0, y0, x1, y1;
-            dg_label_box &o = boxes[(size_t)f * n_mobjs + m];
-            label_box_finish(raw[m], width, height, o.pixels, x0, y0, x1, y1);
-            o.x0 = (int16_t)x0; o.y0 = (int16_t)y0; o.x1 = (int16_t)x1; o.y1 = (int16_t)y1;
-        }
-    }
-    return DG_OK;
+    return plane_lists_host(s, width, height, frames, owners, n, labels, distance, kind, id, cls, boxes);
 }
 
 }  // extern "C"

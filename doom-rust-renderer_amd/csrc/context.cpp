@@ -38,8 +38,6 @@
 #include "../../include/doomgpu.h"
 #include "api_common.hpp"
 #include "binner.hpp"
-#include "bundle_kernels.hpp"
-#include "depth_kernels.hpp"
 #include "fe_kernels.hpp"
 #include "fs_kernels.hpp"
 #include "light_fx_kernels.hpp"
@@ -47,8 +45,8 @@
 #include "frontend.hpp"
 #include "hip_mem.hpp"
 #include "kernels.hpp"
-#include "label_kernels.hpp"
 #include "map_kernels.hpp"
+#include "plane_kernels.hpp"
 #include "pool.hpp"
 #include "reduce_kernels.hpp"
 #include "scene.hpp"
@@ -144,10 +142,21 @@ struct Slot {
     }
     bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
     bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
-    bool holds_depth() const { return front_end == DG_FE_DEPTH && phase != Phase::Empty; }     // the framebuffer slab is the two depth planes
-    bool holds_labels() const { return front_end == DG_FE_LABELS && phase != Phase::Empty; }   // ... the two label planes
-    bool holds_bundle() const { return front_end == DG_FE_BUNDLE && phase != Phase::Empty; }   // ... the parts of a bundle (bundle_what)
-    bool bundle_has(uint32_t part) const { return holds_bundle() && (bundle_what & part) != 0; }
+    bool holds_bundle() const { return front_end == DG_FE_BUNDLE && phase != Phase::Empty; }
+    // Which parts the framebuffer slab holds (BUNDLE_*: RGB24 colour frames, the two depth planes, the two label planes) ...
+    uint32_t parts() const {
+        if (phase == Phase::Empty) return 0;
+        if (front_end == DG_FE_BUNDLE) return bundle_what;
+        return front_end == DG_FE_DEPTH ? BUNDLE_DEPTH : front_end == DG_FE_LABELS ? BUNDLE_LABELS : BUNDLE_COLOUR;
+    }
+    bool holds(uint32_t part) const { return (parts() & part) != 0; }
+    // ... and where each sits.  A bundle's parts are where bundle_layout puts them, each on the slab's boundary; the one part of any
+    // other submission starts at the slab's base, its 8-bit plane right behind its 16-bit plane (include/doomgpu.h promises 2 n W H).
+    BundleLayout layout(size_t W, size_t H) const {
+        if (front_end == DG_FE_BUNDLE) return bundle_layout((size_t)n_frames, W, H, bundle_what);
+        const size_t px = (size_t)n_frames * W * H;
+        return BundleLayout{0, 0, 2 * px, 0, 2 * px, 3 * px};
+    }
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
     bool map_built = false;       // a map submission whose enqueue built the ctx's map layer (ev_start .. ev_setup time that)
     std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
@@ -818,6 +827,20 @@ int build_map_layer(dg_ctx *c, Slot &s) {
 
 constexpr size_t kOverlapMaxPixels = 500000;          // frames up to this size overlap their raster launch with the next batch's front end (dg_create)
 
+// A submission's last step: its kernels are enqueued.  harvested: DG_FE_AUTO has nothing to read from it.
+int queued(Slot &s, bool harvested = true) {
+    s.harvested = harvested;
+    s.raster_recorded = true;
+    s.phase = Slot::Phase::Queued;
+    return DG_OK;
+}
+
+// A launch that fails leaves the slot empty: later calls on it return DG_ERR_INVALID instead of reading what nobody wrote.
+struct Invalidate {
+    Slot &s; bool armed = true;
+    ~Invalidate() { if (armed) s.reset(); }
+};
+
 int enqueue_kernels(dg_ctx *c, Slot &s) {
     // All kernels of all slots run on ONE in-order stream (highest priority, so that it gets a hardware queue of its own): column walk
     // i, rasteriser i, column walk i + 1, ...  The slot's own stream carries its H2D copy (queued already; it overlaps the previous
@@ -827,12 +850,7 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     // written by the kernels directly: nothing is queued behind the raster launch, so no stream ever holds a barrier that another
     // slot's upload could get stuck behind (streams share hardware queues).
     hipStream_t ks = c->kstream;
-    // A HIP call that fails half way leaves the slot empty: later calls on it return DG_ERR_INVALID instead of reading status words
-    // nobody wrote.
-    struct Invalidate {
-        Slot &s; bool armed = true;
-        ~Invalidate() { if (armed) s.reset(); }
-    } guard{s};
+    Invalidate guard{s};                                  // (a HIP call that fails half way: nobody wrote the status words)
     const bool fe_mode = s.column_walk();
     HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
     HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
@@ -874,10 +892,7 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     }
     if (fe_mode) s.walk_state_clean = true;               // everything was enqueued: dg_fe_scan will have cleaned up by the slot's next batch
     guard.armed = false;
-    s.harvested = !fe_mode;                               // (only a column-walk batch is DG_FE_AUTO's measurement)
-    s.raster_recorded = true;
-    s.phase = Slot::Phase::Queued;
-    return DG_OK;
+    return queued(s, !fe_mode);                           // (only a column-walk batch is DG_FE_AUTO's measurement)
 }
 
 // One frame of a device-column-walk batch again, through the host list path, into its place in the slot's framebuffer.  The
@@ -1057,10 +1072,15 @@ int submit(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *give
     return rc ? rc : enqueue_kernels(c, s);
 }
 
-// The synchronous calls' tail, given what their submission returned: its n frames into `out`, or just its end.
-int read_or_wait(dg_ctx *c, int slot, int rc, int n, uint8_t *out) {
+// The synchronous calls' tail, given what their submission returned: its results through `read` when an output was handed over, or
+// just its end.
+template <class Read>
+int read_or_wait(dg_ctx *c, int slot, int rc, bool wanted, Read read) {
     if (rc) return rc;
-    return out ? dg_readback(c, slot, 0, n, out) : dg_wait(c, slot);
+    return wanted ? read() : dg_wait(c, slot);
+}
+int read_or_wait(dg_ctx *c, int slot, int rc, int n, uint8_t *out) {
+    return read_or_wait(c, slot, rc, out != nullptr, [&] { return dg_readback(c, slot, 0, n, out); });
 }
 
 int check_slot(dg_ctx *c, int slot) {
@@ -1069,16 +1089,47 @@ int check_slot(dg_ctx *c, int slot) {
     return DG_OK;
 }
 
-// The calls that read the framebuffer slab as RGB24 frames, or run the colour kernels again, on a slot whose last submission was depth.
-// ... or a label submission, or a bundle without colour.
-int refuse_depth(const Slot &s, const char *what) {
-    if (s.holds_bundle()) {                               // a bundle's colour frames sit at the slab's base, as after a colour submission
-        if (s.bundle_has(BUNDLE_COLOUR)) return DG_OK;
-        return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds a bundle without a colour part (DG_BUNDLE_COLOUR)");
-    }
-    if (s.holds_labels()) return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds label planes, not RGB24 frames (dg_readback_labels)");
-    if (!s.holds_depth()) return DG_OK;
+// The calls that read the framebuffer slab as RGB24 frames, or run the colour kernels again: the slot has no colour part.  (An empty
+// slot is the callers' to refuse.)
+int refuse_no_colour(const Slot &s, const char *what) {
+    if (s.parts() == 0 || s.holds(BUNDLE_COLOUR)) return DG_OK;   // (a bundle's colour frames sit at the slab's base, as after a colour submission)
+    if (s.holds_bundle()) return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds a bundle without a colour part (DG_BUNDLE_COLOUR)");
+    if (s.holds(BUNDLE_LABELS)) return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds label planes, not RGB24 frames (dg_readback_labels)");
     return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds depth planes, not RGB24 frames (dg_readback_depth)");
+}
+
+// What a submission with a label part needs of the slot: the owner tags' staging and HBM, and a box table for the scene's map objects.
+int ensure_label_buffers(dg_ctx *c, Slot &s) {
+    const size_t n_mobjs = c->scene->mobjs.size();
+    if (!s.d_owners) {
+        HIP_TRY(hip_alloc(s.h_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
+        HIP_TRY(hip_alloc(s.d_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
+    }
+    if (!s.d_boxes || s.box_mobjs != n_mobjs) {
+        HIP_TRY(hip_alloc(s.d_boxes, std::max<size_t>((size_t)c->cfg.max_batch * n_mobjs, 1) * sizeof(LabelRawBox)));
+        s.box_mobjs = n_mobjs;
+    }
+    return DG_OK;
+}
+
+// Where the plane kernels write the slot's submission: the parts it holds, at their places in the framebuffer slab.
+BundlePlanes planes_of(const dg_ctx *c, Slot &s) {
+    const BundleLayout L = s.layout((size_t)c->cfg.width, (size_t)c->cfg.height);
+    uint8_t *const fb = s.d_fb.get();
+    BundlePlanes out{};
+    if (s.holds(BUNDLE_DEPTH)) { out.dist = reinterpret_cast<int16_t *>(fb + L.distance); out.kind = fb + L.kind; }
+    if (s.holds(BUNDLE_LABELS)) {
+        out.id = reinterpret_cast<uint16_t *>(fb + L.id); out.cls = fb + L.cls;
+        out.boxes = s.d_boxes.get(); out.n_mobjs = (uint32_t)s.box_mobjs;
+    }
+    return out;
+}
+
+// A depth or label submission's launch on the slot's own stream has returned e.
+int launched(Slot &s, hipError_t e, const char *what) {
+    if (e == hipSuccess) return queued(s);
+    s.reset();                                            // (as a failed enqueue_kernels: the slot is left empty)
+    return set_err(DG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
 // Slot `slot` for a depth submission of n views (or of the caller's lists): always the host list path, whatever front end the ctx has;
@@ -1090,16 +1141,8 @@ int submit_depth(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists
     if (rc) return rc;
     rc = build_batch_host(c, s, views, given, n, states, DG_FE_DEPTH);
     if (rc) return rc;
-    const size_t plane = (size_t)n * (size_t)c->cfg.width * (size_t)c->cfg.height;
-    const hipError_t e = launch_depth(s.P, reinterpret_cast<int16_t *>(s.d_fb.get()), s.d_fb.get() + 2 * plane, s.stream, s.ev_rstart, s.ev_raster);
-    if (e != hipSuccess) {                                // (as a failed enqueue_kernels: the slot is left empty)
-        s.reset();
-        return set_err(DG_ERR_HIP, std::string("launch_depth: ") + hipGetErrorString(e));
-    }
-    s.harvested = true;
-    s.raster_recorded = true;
-    s.phase = Slot::Phase::Queued;
-    return DG_OK;
+    const BundlePlanes out = planes_of(c, s);
+    return launched(s, launch_depth(s.P, out.dist, out.kind, s.stream, s.ev_rstart, s.ev_raster), "launch_depth");
 }
 
 // Slot `slot` for a label submission of n views (or of the caller's lists with their owner tags): the host list path like depth;
@@ -1113,28 +1156,11 @@ int submit_labels(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     if (const int bad = check_batch(c, n)) return bad;
     std::string err;
     if ((rc = check_label_scene(*c->scene, err))) return set_err(rc, err);
-    const size_t n_mobjs = c->scene->mobjs.size();
-    if (!s.d_owners) {
-        HIP_TRY(hip_alloc(s.h_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
-        HIP_TRY(hip_alloc(s.d_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
-    }
-    if (!s.d_boxes || s.box_mobjs != n_mobjs) {
-        HIP_TRY(hip_alloc(s.d_boxes, std::max<size_t>((size_t)c->cfg.max_batch * n_mobjs, 1) * sizeof(LabelRawBox)));
-        s.box_mobjs = n_mobjs;
-    }
+    if ((rc = ensure_label_buffers(c, s))) return rc;
     rc = build_batch_host(c, s, views, given, n, states, DG_FE_LABELS, owners);
     if (rc) return rc;
-    const size_t plane = (size_t)n * (size_t)c->cfg.width * (size_t)c->cfg.height;
-    const hipError_t e = launch_labels(s.P, s.d_owners.get(), reinterpret_cast<uint16_t *>(s.d_fb.get()), s.d_fb.get() + 2 * plane, s.d_boxes.get(), (uint32_t)n_mobjs,
-                                       s.stream, s.ev_rstart, s.ev_setup, s.ev_raster);
-    if (e != hipSuccess) {                                // (as a failed enqueue_kernels: the slot is left empty)
-        s.reset();
-        return set_err(DG_ERR_HIP, std::string("launch_labels: ") + hipGetErrorString(e));
-    }
-    s.harvested = true;
-    s.raster_recorded = true;
-    s.phase = Slot::Phase::Queued;
-    return DG_OK;
+    const BundlePlanes out = planes_of(c, s);
+    return launched(s, launch_labels(s.P, s.d_owners.get(), out.id, out.cls, out.boxes, out.n_mobjs, s.stream, s.ev_rstart, s.ev_setup, s.ev_raster), "launch_labels");
 }
 
 int check_bundle_what(uint32_t what) {
@@ -1152,10 +1178,7 @@ int bundle_capacity_of(const dg_ctx *c, uint32_t what) {
 // kernel is the last.  A HIP call that fails half way leaves the slot empty.
 int enqueue_bundle(dg_ctx *c, Slot &s) {
     hipStream_t ks = c->kstream;
-    struct Invalidate {
-        Slot &s; bool armed = true;
-        ~Invalidate() { if (armed) s.reset(); }
-    } guard{s};
+    Invalidate guard{s};
     const uint32_t what = s.bundle_what;
     const bool colour = (what & BUNDLE_COLOUR) != 0, tiles = (what & (BUNDLE_DEPTH | BUNDLE_LABELS)) != 0;
     HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
@@ -1164,22 +1187,9 @@ int enqueue_bundle(dg_ctx *c, Slot &s) {
         HIP_TRY(launch_setup(s.P, s.max_spans, ks, s.ev_start, s.ev_setup));
         HIP_TRY(launch_raster(s.P, ks, s.ev_rstart, tiles ? s.ev_cend : s.ev_raster));
     }
-    if (tiles) {
-        const BundleLayout L = bundle_layout((size_t)s.n_frames, (size_t)c->cfg.width, (size_t)c->cfg.height, what);
-        uint8_t *const fb = s.d_fb.get();
-        BundlePlanes out{};
-        if (what & BUNDLE_DEPTH) { out.dist = reinterpret_cast<int16_t *>(fb + L.distance); out.kind = fb + L.kind; }
-        if (what & BUNDLE_LABELS) {
-            out.id = reinterpret_cast<uint16_t *>(fb + L.id); out.cls = fb + L.cls;
-            out.boxes = s.d_boxes.get(); out.n_mobjs = (uint32_t)s.box_mobjs;
-        }
-        HIP_TRY(launch_bundle(s.P, s.d_owners.get(), out, what, ks, s.ev_tiles, s.ev_raster));
-    }
+    if (tiles) HIP_TRY(launch_bundle(s.P, s.d_owners.get(), planes_of(c, s), what, ks, s.ev_tiles, s.ev_raster));
     guard.armed = false;
-    s.harvested = true;                                   // (never DG_FE_AUTO's measurement)
-    s.raster_recorded = true;
-    s.phase = Slot::Phase::Queued;
-    return DG_OK;
+    return queued(s);                                     // (never DG_FE_AUTO's measurement)
 }
 
 // Slot `slot` for a bundle of n views (or of the caller's lists, with their owner tags when labels are asked for): the host list path
@@ -1195,17 +1205,7 @@ int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     int rc;
     if (labels && (rc = check_label_scene(*c->scene, err))) return set_err(rc, err);
     if ((rc = take_slot(c, s))) return rc;
-    if (labels) {
-        const size_t n_mobjs = c->scene->mobjs.size();
-        if (!s.d_owners) {
-            HIP_TRY(hip_alloc(s.h_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
-            HIP_TRY(hip_alloc(s.d_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
-        }
-        if (!s.d_boxes || s.box_mobjs != n_mobjs) {
-            HIP_TRY(hip_alloc(s.d_boxes, std::max<size_t>((size_t)c->cfg.max_batch * n_mobjs, 1) * sizeof(LabelRawBox)));
-            s.box_mobjs = n_mobjs;
-        }
-    }
+    if (labels && (rc = ensure_label_buffers(c, s))) return rc;
     rc = build_batch_host(c, s, views, given, n, states, DG_FE_BUNDLE, owners, labels);
     if (rc) {
         if (s.phase == Slot::Phase::Prepared && s.front_end == DG_FE_BUNDLE) s.reset();   // (described, then an upload failed: nothing says yet which parts it has)
@@ -1434,7 +1434,7 @@ static int readback_async(dg_ctx *c, int slot, int first, int count, const dg_re
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if ((rc = refuse_depth(s, desc ? "dg_readback_reduced_async" : "dg_readback_async"))) return rc;
+    if ((rc = refuse_no_colour(s, desc ? "dg_readback_reduced_async" : "dg_readback_async"))) return rc;
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     if (s.copy_pending) return set_err(DG_ERR_INVALID, "the slot already has a readback in flight (dg_wait it first)");
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -1471,7 +1471,7 @@ int dg_readback_reduced(dg_ctx *c, int slot, int first, int count, const dg_redu
     if (!rc) rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if ((rc = refuse_depth(s, "dg_readback_reduced"))) return rc;
+    if ((rc = refuse_no_colour(s, "dg_readback_reduced"))) return rc;
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     if (count == 0) return DG_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -1539,7 +1539,7 @@ int dg_readback(dg_ctx *c, int slot, int first, int count, uint8_t *out) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if ((rc = refuse_depth(s, "dg_readback"))) return rc;
+    if ((rc = refuse_no_colour(s, "dg_readback"))) return rc;
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     HIP_TRY(hipSetDevice(c->cfg.device));
     const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
@@ -1554,7 +1554,7 @@ int dg_frame_checksums(dg_ctx *c, int slot, int first, int count, uint64_t *out)
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if ((rc = refuse_depth(s, "dg_frame_checksums"))) return rc;
+    if ((rc = refuse_no_colour(s, "dg_frame_checksums"))) return rc;
     if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad frame range");
     if (count == 0) return DG_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -1606,7 +1606,7 @@ int dg_replay_slot(dg_ctx *c, int slot) {
     Slot &s = c->slots[(size_t)slot];
     if (s.phase == Slot::Phase::Empty) return set_err(DG_ERR_INVALID, "slot has no prepared lists");
     if (s.holds_bundle()) return set_err(DG_ERR_INVALID, "dg_replay_slot: the slot holds a bundle (submit it again)");
-    if ((rc = refuse_depth(s, "dg_replay_slot"))) return rc;
+    if ((rc = refuse_no_colour(s, "dg_replay_slot"))) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
     // A dg_readback_async may still be reading the framebuffer these kernels are about to overwrite, and a column-walk submission that
     // was never waited for has its overflow flags looked at before the walk clears them.  A host-list submission still in flight is not
@@ -1633,46 +1633,47 @@ int dg_submit_depth_views(dg_ctx *c, int slot, const dg_view *views, const dg_vi
     return submit_depth(c, slot, views, nullptr, n, states);
 }
 
-int dg_readback_depth(dg_ctx *c, int slot, int first, int count, int16_t *distance, uint8_t *kind) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (s.holds_bundle() && !s.bundle_has(BUNDLE_DEPTH)) return set_err(DG_ERR_INVALID, "dg_readback_depth: the slot's bundle has no depth part (DG_BUNDLE_DEPTH)");
-    if (!s.holds_depth() && !s.holds_bundle()) return set_err(DG_ERR_INVALID, "dg_readback_depth: the slot's last submission is not a depth submission");   // (a label slot included)
+// What dg_readback_depth and dg_readback_labels do alike once each has ruled on what the slot holds: frames [first, first + count) of
+// a 16-bit plane at byte `at16` of the framebuffer slab and of the 8-bit plane at `at8` into the outputs that are there, and with `raw`
+// the same frames' rows of the box table.
+static int read_planes(dg_ctx *c, Slot &s, int first, int count, size_t at16, void *out16, size_t at8, uint8_t *out8, std::vector<LabelRawBox> *raw = nullptr) {
     if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
     if (count == 0) return DG_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    rc = make_final(c, s, Copy::Leave);
+    const int rc = make_final(c, s, Copy::Leave);
     if (rc) return rc;
     const size_t px = (size_t)c->cfg.width * (size_t)c->cfg.height;
-    size_t at_dist = 0, at_kind = 2 * (size_t)s.n_frames * px;          // a depth submission's planes; a bundle's are where its layout puts them
-    if (s.holds_bundle()) {
-        const BundleLayout L = bundle_layout((size_t)s.n_frames, (size_t)c->cfg.width, (size_t)c->cfg.height, s.bundle_what);
-        at_dist = L.distance; at_kind = L.kind;
+    const uint8_t *const fb = s.d_fb.get();
+    if (out16) HIP_TRY(hipMemcpyAsync(out16, fb + at16 + (size_t)first * px * 2, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream));
+    if (out8) HIP_TRY(hipMemcpyAsync(out8, fb + at8 + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream));
+    if (raw) {
+        raw->resize((size_t)count * s.box_mobjs);
+        if (!raw->empty()) HIP_TRY(hipMemcpyAsync(raw->data(), s.d_boxes.get() + (size_t)first * s.box_mobjs, raw->size() * sizeof(LabelRawBox), hipMemcpyDeviceToHost, s.stream));
     }
-    const int16_t *const d_dist = reinterpret_cast<const int16_t *>(s.d_fb.get() + at_dist);
-    const uint8_t *const d_kind = s.d_fb.get() + at_kind;
-    if (distance) HIP_TRY(hipMemcpyAsync(distance, d_dist + (size_t)first * px, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream));
-    if (kind) HIP_TRY(hipMemcpyAsync(kind, d_kind + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(slot_sync(s));
     return DG_OK;
 }
 
-// The synchronous depth calls' tail, given what their submission returned: the n frames' planes into the outputs, or just its end.
-static int read_depth_or_wait(dg_ctx *c, int slot, int rc, int n, int16_t *distance, uint8_t *kind) {
+int dg_readback_depth(dg_ctx *c, int slot, int first, int count, int16_t *distance, uint8_t *kind) {
+    int rc = check_slot(c, slot);
     if (rc) return rc;
-    return distance || kind ? dg_readback_depth(c, slot, 0, n, distance, kind) : dg_wait(c, slot);
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.holds(BUNDLE_DEPTH))                           // (a label slot included)
+        return set_err(DG_ERR_INVALID, s.holds_bundle() ? "dg_readback_depth: the slot's bundle has no depth part (DG_BUNDLE_DEPTH)"
+                                                        : "dg_readback_depth: the slot's last submission is not a depth submission");
+    const BundleLayout L = s.layout((size_t)c->cfg.width, (size_t)c->cfg.height);
+    return read_planes(c, s, first, count, L.distance, distance, L.kind, kind);
 }
 
 int dg_render_depth_views(dg_ctx *c, const dg_view *views, const dg_view_state *states, int n, int16_t *distance, uint8_t *kind) {
-    return read_depth_or_wait(c, 0, dg_submit_depth_views(c, 0, views, states, n), n, distance, kind);
+    return read_or_wait(c, 0, dg_submit_depth_views(c, 0, views, states, n), distance || kind, [&] { return dg_readback_depth(c, 0, 0, n, distance, kind); });
 }
 
 int dg_depth_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, int n, int16_t *distance, uint8_t *kind) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!frames) return set_err(DG_ERR_INVALID, "null frames");
-    return read_depth_or_wait(c, slot, submit_depth(c, slot, nullptr, frames, n, nullptr), n, distance, kind);
+    return read_or_wait(c, slot, submit_depth(c, slot, nullptr, frames, n, nullptr), distance || kind, [&] { return dg_readback_depth(c, slot, 0, n, distance, kind); });
 }
 
 int dg_submit_label_views(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, int n) {
@@ -1688,27 +1689,13 @@ int dg_readback_labels(dg_ctx *c, int slot, int first, int count, uint16_t *id, 
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if (s.holds_bundle() && !s.bundle_has(BUNDLE_LABELS)) return set_err(DG_ERR_INVALID, "dg_readback_labels: the slot's bundle has no label part (DG_BUNDLE_LABELS)");
-    if (!s.holds_labels() && !s.holds_bundle()) return set_err(DG_ERR_INVALID, "dg_readback_labels: the slot's last submission is not a label submission");
-    if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
-    if (count == 0) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    rc = make_final(c, s, Copy::Leave);
-    if (rc) return rc;
+    if (!s.holds(BUNDLE_LABELS))
+        return set_err(DG_ERR_INVALID, s.holds_bundle() ? "dg_readback_labels: the slot's bundle has no label part (DG_BUNDLE_LABELS)"
+                                                        : "dg_readback_labels: the slot's last submission is not a label submission");
     const int W = c->cfg.width, H = c->cfg.height;
-    const size_t px = (size_t)W * (size_t)H;
-    size_t at_id = 0, at_cls = 2 * (size_t)s.n_frames * px;             // a label submission's planes; a bundle's are where its layout puts them
-    if (s.holds_bundle()) {
-        const BundleLayout L = bundle_layout((size_t)s.n_frames, (size_t)W, (size_t)H, s.bundle_what);
-        at_id = L.id; at_cls = L.cls;
-    }
-    const uint16_t *const d_id = reinterpret_cast<const uint16_t *>(s.d_fb.get() + at_id);
-    const uint8_t *const d_cls = s.d_fb.get() + at_cls;
-    std::vector<LabelRawBox> raw(boxes ? (size_t)count * s.box_mobjs : 0);
-    if (id) HIP_TRY(hipMemcpyAsync(id, d_id + (size_t)first * px, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream));
-    if (cls) HIP_TRY(hipMemcpyAsync(cls, d_cls + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream));
-    if (!raw.empty()) HIP_TRY(hipMemcpyAsync(raw.data(), s.d_boxes.get() + (size_t)first * s.box_mobjs, raw.size() * sizeof(LabelRawBox), hipMemcpyDeviceToHost, s.stream));
-    HIP_TRY(slot_sync(s));
+    const BundleLayout L = s.layout((size_t)W, (size_t)H);
+    std::vector<LabelRawBox> raw;
+    if ((rc = read_planes(c, s, first, count, L.id, id, L.cls, cls, boxes ? &raw : nullptr))) return rc;
     for (size_t i = 0; i < raw.size(); i++) {
         int32_t x0, y0, x1, y1;
         label_box_finish(raw[i], W, H, boxes[i].pixels, x0, y0, x1, y1);
@@ -1717,28 +1704,22 @@ int dg_readback_labels(dg_ctx *c, int slot, int first, int count, uint16_t *id, 
     return DG_OK;
 }
 
-// The synchronous label calls' tail, given what their submission returned: the n frames' planes and boxes into the outputs, or just its end.
-static int read_labels_or_wait(dg_ctx *c, int slot, int rc, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
-    if (rc) return rc;
-    return id || cls || boxes ? dg_readback_labels(c, slot, 0, n, id, cls, boxes) : dg_wait(c, slot);
-}
-
 int dg_render_label_views(dg_ctx *c, const dg_view *views, const dg_view_state *states, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
-    return read_labels_or_wait(c, 0, dg_submit_label_views(c, 0, views, states, n), n, id, cls, boxes);
+    return read_or_wait(c, 0, dg_submit_label_views(c, 0, views, states, n), id || cls || boxes, [&] { return dg_readback_labels(c, 0, 0, n, id, cls, boxes); });
 }
 
 int dg_label_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uint32_t *const *owners, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!frames || !owners) return set_err(DG_ERR_INVALID, "null frames or owners");
-    return read_labels_or_wait(c, slot, submit_labels(c, slot, nullptr, frames, owners, n, nullptr), n, id, cls, boxes);
+    return read_or_wait(c, slot, submit_labels(c, slot, nullptr, frames, owners, n, nullptr), id || cls || boxes, [&] { return dg_readback_labels(c, slot, 0, n, id, cls, boxes); });
 }
 
 int dg_slot_label_timing(dg_ctx *c, int slot, float *tiles_ms, float *boxes_ms) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     Slot &s = c->slots[(size_t)slot];
-    if (!s.holds_labels() || !s.has_run()) return set_err(DG_ERR_INVALID, "dg_slot_label_timing: the slot's last submission is not a label submission that ran");
+    if (s.front_end != DG_FE_LABELS || !s.has_run()) return set_err(DG_ERR_INVALID, "dg_slot_label_timing: the slot's last submission is not a label submission that ran");
     HIP_TRY(hipSetDevice(c->cfg.device));
     rc = make_final(c, s, Copy::Leave);
     if (rc) return rc;
@@ -1770,7 +1751,7 @@ int dg_bundle_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uin
     if ((rc = check_bundle_what(what))) return rc;
     if ((what & BUNDLE_LABELS) && !owners) return set_err(DG_ERR_INVALID, "null owners: DG_BUNDLE_LABELS needs the owner tags");
     rc = submit_bundle(c, slot, nullptr, frames, owners, n, nullptr, what);
-    return rc ? rc : dg_wait(c, slot);
+    return rc ? rc : dg_wait(c, slot);                    // (no output of its own: the parts are the readbacks' to fetch)
 }
 
 int dg_slot_bundle_timing(dg_ctx *c, int slot, float *setup_ms, float *raster_ms, float *tiles_ms) {

@@ -6,7 +6,7 @@ Test infrastructure.  np_mappers is not edited: its three mappers run as they ar
   * a Wad whose palette() returns the sky sentinel for every entry, so that draw_sky's direct `palette[texel]` write decodes to
     (32767, 3).
 Frame.px then holds the two planes.  Overwrite order, transparency, clamps and the column rules are np_mappers' own and share nothing
-with csrc/depth_core.h.  `Tracker` is a Frame that also records who wrote each pixel last.
+with csrc/plane_core.h.  `Tracker` is a Frame that also records who wrote each pixel last.
 """
 import contextlib
 import struct

@@ -4,7 +4,7 @@ Test infrastructure, in two independent halves.
 
   who owns a pixel   np_depth.depth_of_frame_lists replays a dg_frame_lists through np_mappers.py and records, per pixel, the index into
                      `order` of the draw command that wrote it last (overwrite order, transparency, clamps and the column rules are
-                     np_mappers' own and share nothing with csrc/label_core.h).  `labels_of_frame_lists` maps that index through
+                     np_mappers' own and share nothing with csrc/plane_core.h).  `labels_of_frame_lists` maps that index through
                      order -> render -> owner tag for the class and id of a column pixel; the class of flat and sky pixels comes from the
                      model's kind plane.  Boxes are plain numpy over the two planes.
 

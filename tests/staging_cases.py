@@ -1,4 +1,4 @@
-"""Hand-built lists aimed at the staging limit of dg_depth_tiles / dg_label_tiles (16 spans per column in LDS; span 16 and later are
+"""Hand-built lists aimed at the staging limit of dg_depth_tiles / dg_label_tiles / dg_bundle_tiles (16 spans per column in LDS; span 16 and later are
 resolved from the list slab inside the row loop) and at the run and piece boundaries of dg_label_boxes.  Beside tests/depth_cases.py, in
 the same list-dict form; shared by tests/test_staging_cases_host.py (host entries == the numpy models) and tests/test_plane_shapes_gpu.py.
 Both builders work at any W x H >= 1 x 1.
@@ -20,6 +20,11 @@ SYNTH = {"opaque": ["BRICK1", "STONE2", "METAL2", "PANEL2"], "holey": ["HOLEY1",
 HAND = {"opaque": ["WALLA"], "holey": ["MASKED", "TWOP"], "flat": ["FLOORA", "CEILA", "NUKAGE1"]}      # tests/test_hand_wad.py
 LADDER_VIEW = (310.0, -95.5, 1.9, 8.0)
 BOX_VIEW = (0.0, 0.0, -2.1, 16.0)
+
+
+def bundle_batch_for(dg, W, H, n, what=7):
+    """The smallest max_batch whose framebuffer slab holds a bundle of n frames with the parts `what` (default: all three)."""
+    return max(n, -(-dg.bundle_layout(W, H, n, what)["total"] // (3 * W * H)))
 
 
 def ladder_count(x):

@@ -19,6 +19,7 @@ import pytest
 
 import depth_cases
 import mobj_fx as mf
+from staging_cases import bundle_batch_for as _batch_for
 from test_edge_kats import to_dg_lists, view_dict
 from test_labels_host import hand_owners
 
@@ -40,11 +41,6 @@ def _same(names, got, want, what):
 def _same_colour(got, want, what):
     bad = np.argwhere(np.any(got != want, axis=3))
     assert len(bad) == 0, f"{what}: {len(bad)} colour pixels differ, first at (frame, y, x) {bad[0].tolist()}: bundle {got[tuple(bad[0])]} colour route {want[tuple(bad[0])]}"
-
-
-def _batch_for(dg, W, H, n, what=ALL):
-    """The smallest max_batch whose framebuffer slab holds a bundle of n frames."""
-    return max(n, -(-dg.bundle_layout(W, H, n, what)["total"] // (3 * W * H)))
 
 
 def _capacity(dg, W, H, max_batch, what):

@@ -1,7 +1,8 @@
-"""CPU tier of the bundle submission: dg_bundle_lists_host (the binner + csrc/bundle_core.h on the CPU — the fused rule dg_bundle_tiles
+"""CPU tier of the bundle submission: dg_bundle_lists_host (the binner + csrc/plane_core.h on the CPU — the rule dg_bundle_tiles
 evaluates, and what the GPU path is tested against in test_bundle_gpu.py) must equal dg_depth_lists_host and dg_label_lists_host, which
-test_depth_host.py and test_labels_host.py hold against the numpy models, plane for plane and box for box; and dg_bundle_layout must be the
-layout DESIGN.md §8i states.
+test_depth_host.py and test_labels_host.py hold against the numpy models, plane for plane and box for box; the three share their code, so
+the hand-built lists are also held against the numpy models (np_depth, np_labels) directly; and dg_bundle_layout must be the layout
+DESIGN.md §8i states.
 
   whole frames    dg_build_lists_owners output of the light map, the vanilla-shaped map and the hand-packed IWAD at 160x100, 131x67, 5x9
   hand-built      every case of tests/depth_cases.py with test_labels_host's hand-given owners: the 70-span column, 24 records per column,
@@ -93,6 +94,24 @@ def test_hand_built_lists_equal_the_two_host_functions(dg, hand_built):
     frames, owners, want, names = cases[(64, 40)]
     hz = want[0][names.index("horizon")][20]
     assert {-32768, 32767, 0} <= set(hz.tolist())
+
+
+def test_hand_built_lists_equal_the_numpy_models(dg, hand_built, wad1993):
+    """All five outputs of one dg_bundle_lists_host call against np_depth / np_labels, which share nothing with the library."""
+    import np_depth
+    import np_front_end as nf
+    import np_labels as nl
+    cases, scene = hand_built
+    names, n_mobjs = np_depth.SceneNames(dg, scene, wad1993, nf), scene.mobj_count()
+    for (W, H), (frames, owners, _want, case_names) in cases.items():
+        got = dg.bundle_lists_host(scene, W, H, frames, owners)
+        for i, name in enumerate(case_names):
+            dist, kind, _tr = np_depth.depth_of_frame_lists(names, "SKY1", W, H, frames[i])
+            ids, cls, boxes, _tr, kind2 = nl.labels_of_frame_lists(names, "SKY1", W, H, frames[i], owners[i], n_mobjs)
+            assert np.array_equal(kind, kind2)
+            for plane, g, w in zip(NAMES, got, (dist, kind, ids, cls, boxes)):
+                bad = np.argwhere(g[i] != w)
+                assert g[i].shape == w.shape and len(bad) == 0, f"{name} {W}x{H} {plane}: {len(bad)} differ from the numpy model, first at {bad[:1].tolist()}"
 
 
 def test_each_output_may_be_left_out_and_each_may_stand_alone(dg, hand_built):

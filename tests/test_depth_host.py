@@ -1,6 +1,6 @@
-"""CPU tier of the depth / surface-kind frame: dg_depth_lists_host (the binner + csrc/depth_core.h on the CPU, what the GPU path is
+"""CPU tier of the depth / surface-kind frame: dg_depth_lists_host (the binner + csrc/plane_core.h on the CPU, what the GPU path is
 tested against in test_depth_gpu.py) must equal tests/np_depth.py byte for byte — the model that drives np_mappers.py with a patched
-diminish_color and shares nothing with depth_core.h.
+diminish_color and shares nothing with plane_core.h.
 
   whole frames    dg_build_lists output of the light map (seed 1993), the vanilla-shaped map (1995) and the hand-packed IWAD of
                   test_hand_wad.py: five views each at 160x100, one at 131x67 and one at 5x9 — masked walls, sprites, sky, and a sprite

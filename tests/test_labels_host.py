@@ -1,4 +1,4 @@
-"""CPU tier of the object-label frame: dg_label_lists_host (the binner + csrc/label_core.h on the CPU, what the GPU path is tested against
+"""CPU tier of the object-label frame: dg_label_lists_host (the binner + csrc/plane_core.h on the CPU, what the GPU path is tested against
 in test_labels_gpu.py) must equal tests/np_labels.py — np_mappers' own overwrite order mapped through the owner tags — byte for byte,
 and the owner tags dg_build_lists_owners hands out must be the ones leave-one-in runs of np_front_end.py give.
 

@@ -1,10 +1,12 @@
-"""GPU tier for the launch shapes of dg_depth_tiles / dg_label_tiles / dg_label_boxes and for skies with transparent texels.
+"""GPU tier for the launch shapes of the plane walk (csrc/plane_kernels.hip: dg_depth_tiles / dg_label_tiles / dg_bundle_tiles, and
+dg_label_boxes) and for skies with transparent texels.
 
-  launch shapes    the grid of both tile kernels is ceil(W/64) x ceil(H/128) x n and dg_label_boxes walks 32-row pieces: one frame size per
+  launch shapes    the grid of every tile kernel is ceil(W/64) x ceil(H/128) x n and dg_label_boxes walks 32-row pieces: one frame size per
                    decision (SIZES).  At each, the tests/depth_cases.py cases plus staging_cases.ladder and box_edges go through
-                   dg_depth_lists and dg_label_lists as one batch, forwards and in reversed order, and are compared with the numpy models
-                   (np_depth, np_labels) directly and with the host entries.  Before every compared submission another batch goes through
-                   the same slot — a wall owned by a map object over the whole frame: kind, distance, class and id all differ from what an
+                   dg_depth_lists, dg_label_lists and dg_bundle_lists (depth + labels: the nine-word span and the fused boxes; labels
+                   alone) as one batch, forwards and in reversed order, and are compared with the numpy models (np_depth, np_labels)
+                   directly and with the host entries.  Before every compared submission another batch goes through the same slot by the
+                   same route — a wall owned by a map object over the whole frame: kind, distance, class and id all differ from what an
                    uncovered pixel holds — so a row or pixel a kernel fails to write cannot pass on stale content.
   holey skies      sky_cases.sky_lists through dg_draw_lists, dg_depth_lists and dg_label_lists for the hand WAD variants at 64x40, 131x67
                    and 65x129 against the models; the two small variants are refused by the binner (DG_ERR_RENDER) and the slot stays
@@ -106,8 +108,11 @@ def test_every_launch_shape_equals_the_models(dg, campath_mod, world, size):
     stale = list(dg.depth_lists_host(scene, W, H, other)) + list(dg.label_lists_host(scene, W, H, other, other_owners))
     # the other batch differs from what an uncovered pixel holds (far, kind 0, id 0, class 0) in every plane, everywhere
     assert (stale[0] != 32767).all() and (stale[1] == 1).all() and (stale[2] == scene.mobj_count() - 2).all() and (stale[3] == nl.MOBJ).all()
+    both = dg.DG_BUNDLE_DEPTH | dg.DG_BUNDLE_LABELS
     ctx = dg.Context(W, H, max_batch=n, slots=1)
     ctx.upload_scene(scene)
+    bctx = dg.Context(W, H, max_batch=sc.bundle_batch_for(dg, W, H, n, both), slots=1)       # (a slab that holds the bundle's parts)
+    bctx.upload_scene(scene)
     for order in (list(range(n)), list(range(n))[::-1]):
         fr = (dg.DgFrameLists * n)(*[frames[i] for i in order])
         ow = [owners[i] for i in order]
@@ -124,8 +129,18 @@ def test_every_launch_shape_equals_the_models(dg, campath_mod, world, size):
         for j, plane in enumerate(("id", "cls", "boxes")):
             _diff(got[j], model[2 + j][order], f"{what} {plane} against the model (frames {[case_names[i] for i in order]})")
             _diff(got[j], host[2 + j][order], f"{what} {plane} against the host entry")
-    assert ctx.fallbacks() == ZERO
+        for parts, first in ((both, 0), (dg.DG_BUNDLE_LABELS, 2)):       # the bundle route: every plane of the slab dirty, then the batch
+            bctx.bundle_lists(0, other, other_owners, both)
+            for g, w in zip(tuple(bctx.readback_depth(0, 0, n)) + tuple(bctx.readback_labels(0, 0, n)), stale):
+                _diff(g, w, f"{what}: the other batch as a bundle")
+            bctx.bundle_lists(0, fr, ow, parts)
+            got = (tuple(bctx.readback_depth(0, 0, n)) if first == 0 else (None, None)) + tuple(bctx.readback_labels(0, 0, n))
+            for j, plane in list(enumerate(("distance", "kind", "id", "cls", "boxes")))[first:]:
+                _diff(got[j], model[j][order], f"{what} bundle {parts} {plane} against the model (frames {[case_names[i] for i in order]})")
+                _diff(got[j], host[j][order], f"{what} bundle {parts} {plane} against the host entry")
+    assert ctx.fallbacks() == ZERO and bctx.fallbacks() == ZERO
     ctx.close()
+    bctx.close()
     del keep, keep2
 
 
