@@ -36,6 +36,7 @@ DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
 DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
 DG_MOBJ_KILL, DG_MOBJ_EXPLODE, DG_MOBJ_RESPAWN = 1, 2, 3   # dg_scene_mobj_event
 DG_REDUCE_RGB24, DG_REDUCE_GRAY8 = 0, 1  # dg_reduce_desc.format
+DG_PLANE_POINT, DG_PLANE_NEAREST = 0, 1  # dg_plane_reduce_desc.rule
 DG_KEY_LEFT, DG_KEY_RIGHT, DG_KEY_UP, DG_KEY_DOWN, DG_KEY_ALT, DG_KEY_SHIFT = 1, 2, 4, 8, 16, 32   # dg_walk_desc.keys
 
 
@@ -79,6 +80,10 @@ class DgWalkDesc(ctypes.Structure):
 
 class DgReduceDesc(ctypes.Structure):
     _fields_ = [("fx", ctypes.c_uint32), ("fy", ctypes.c_uint32), ("format", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class DgPlaneReduceDesc(ctypes.Structure):
+    _fields_ = [("fx", ctypes.c_uint32), ("fy", ctypes.c_uint32), ("rule", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class DgBundleOffsets(ctypes.Structure):
@@ -215,6 +220,12 @@ _SIGNATURES = {
     "dg_bundle_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.POINTER(_P), ctypes.c_int, ctypes.c_uint32]),
     "dg_bundle_lists_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.POINTER(_P), ctypes.c_int, _P, _P, _P, _P, _P]),
     "dg_slot_bundle_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "dg_plane_reduced_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dg_reduce_planes_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 8),
+    "dg_reduce_planes_device": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 8),
+    "dg_ctx_plane_reduce_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    "dg_readback_planes_reduced": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 5),
+    "dg_readback_planes_reduced_async": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 5),
     "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
     "dg_walk_free": (None, [_P]),
     "dg_walk_tics": (ctypes.c_int, [_P]),
@@ -275,6 +286,39 @@ def reduce_host(frames, desc) -> np.ndarray:
     n, h, w, _ = src.shape
     out = _reduced_array(n, w, h, d)
     _check(lib().dg_reduce_host(src.ctypes.data_as(_P), w, h, n, ctypes.byref(d), out.ctypes.data_as(_P)))
+    return out
+
+
+PLANE_NAMES = ("distance", "kind", "id", "cls")
+PLANE_DTYPES = {"distance": np.int16, "kind": np.uint8, "id": np.uint16, "cls": np.uint8}
+
+
+def _plane_reduce_desc(desc) -> DgPlaneReduceDesc:
+    """A DgPlaneReduceDesc as it is, or one from (fx, fy) / (fx, fy, rule)."""
+    return desc if isinstance(desc, DgPlaneReduceDesc) else DgPlaneReduceDesc(int(desc[0]), int(desc[1]), int(desc[2]) if len(desc) > 2 else DG_PLANE_POINT, 0)
+
+
+def plane_reduced_size(width: int, height: int, desc):
+    """dg_plane_reduced_size: (oW, oH) of a width x height plane under desc (a DgPlaneReduceDesc, or (fx, fy[, rule]))."""
+    w, h = ctypes.c_int(), ctypes.c_int()
+    _check(lib().dg_plane_reduced_size(width, height, ctypes.byref(_plane_reduce_desc(desc)), ctypes.byref(w), ctypes.byref(h)))
+    return w.value, h.value
+
+
+def reduce_planes_host(desc, distance=None, kind=None, id=None, cls=None) -> dict:
+    """dg_reduce_planes_host: the planes that are given, each (n, H, W) — distance int16, kind uint8, id uint16, cls uint8 — reduced on
+    the CPU under desc (a DgPlaneReduceDesc, or (fx, fy[, rule])); returns {name: (n, oH, oW) array} for the planes given."""
+    d = _plane_reduce_desc(desc)
+    src = {k: np.ascontiguousarray(v, dtype=PLANE_DTYPES[k]) for k, v in zip(PLANE_NAMES, (distance, kind, id, cls)) if v is not None}
+    if not src:
+        raise ValueError("no plane given")
+    n, h, w = next(iter(src.values())).shape
+    if any(a.shape != (n, h, w) for a in src.values()):
+        raise ValueError("the planes must have one shape (n, H, W)")
+    ow, oh = plane_reduced_size(w, h, d)
+    out = {k: np.empty((n, oh, ow), dtype=PLANE_DTYPES[k]) for k in src}
+    ptr = lambda arrs: [arrs[k].ctypes.data_as(_P) if k in arrs else None for k in PLANE_NAMES]
+    _check(lib().dg_reduce_planes_host(w, h, n, ctypes.byref(d), *ptr(src), *ptr(out)))
     return out
 
 
@@ -682,6 +726,38 @@ class Context:
         """dg_reduce_device: n_frames RGB24 frames at device address src_ptr downscaled into device address dst_ptr (synchronous; a slot's
         framebuffer_ptr or a tensor's data_ptr(), any alignment).  Touches no slot."""
         _check(lib().dg_reduce_device(self._h, _P(src_ptr), width, height, n_frames, ctypes.byref(_reduce_desc(desc)), _P(dst_ptr)))
+
+    def readback_planes_reduced(self, slot: int, first: int, count: int, desc, distance: bool = True, kind: bool = True, id: bool = True,
+                                cls: bool = True, boxes: bool = True) -> dict:
+        """dg_readback_planes_reduced: the planes asked for of frames [first, first + count) of a depth, label or bundle slot, reduced on the
+        GPU under desc (a DgPlaneReduceDesc, or (fx, fy[, rule])), and the full-size boxes; {name: array} for what was asked for."""
+        d = _plane_reduce_desc(desc)
+        ow, oh = plane_reduced_size(self.width, self.height, d)
+        out = {k: np.empty((count, oh, ow), dtype=PLANE_DTYPES[k]) for k, want in zip(PLANE_NAMES, (distance, kind, id, cls)) if want}
+        if boxes:
+            out["boxes"] = np.empty((count, self._scene.mobj_count()), dtype=LABEL_BOX_DTYPE)
+        ptrs = [out[k].ctypes.data_as(_P) if k in out else None for k in PLANE_NAMES + ("boxes",)]
+        _check(lib().dg_readback_planes_reduced(self._h, slot, first, count, ctypes.byref(d), *ptrs))
+        return out
+
+    def readback_planes_reduced_async(self, slot: int, first: int, count: int, desc, distance: int = 0, kind: int = 0, id: int = 0, cls: int = 0,
+                                      boxes: int = 0):
+        """dg_readback_planes_reduced_async: the reduction and the copies queued behind the slot's kernels; each output is a host address
+        (0: not asked for) and is complete after wait(slot)."""
+        ptrs = [_P(p) if p else None for p in (distance, kind, id, cls, boxes)]
+        _check(lib().dg_readback_planes_reduced_async(self._h, slot, first, count, ctypes.byref(_plane_reduce_desc(desc)), *ptrs))
+
+    def reduce_planes_device(self, width: int, height: int, n_frames: int, desc, src: dict, dst: dict):
+        """dg_reduce_planes_device: n_frames planes at the device addresses src[name] reduced into the device addresses dst[name]
+        (names of PLANE_NAMES; synchronous; planes of a finished slot's framebuffer_ptr or tensors' data_ptr()).  Touches no slot."""
+        ptr = lambda d: [_P(d[k]) if d.get(k) else None for k in PLANE_NAMES]
+        _check(lib().dg_reduce_planes_device(self._h, width, height, n_frames, ctypes.byref(_plane_reduce_desc(desc)), *ptr(src), *ptr(dst)))
+
+    def plane_reduce_kernel_ms(self) -> float:
+        """dg_ctx_plane_reduce_kernel_ms: GPU time of the last reduce_planes_device call's kernel."""
+        ms = ctypes.c_float()
+        _check(lib().dg_ctx_plane_reduce_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def reduce_kernel_ms(self) -> float:
         """dg_ctx_reduce_kernel_ms: GPU time of the last reduce_device call's kernel."""

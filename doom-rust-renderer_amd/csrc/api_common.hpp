@@ -3,9 +3,28 @@
 #include <string>
 
 #include "../../include/doomgpu.h"
+#include "plane_reduce_core.h"
 #include "scene.hpp"
 
 extern thread_local std::string t_err;          // what dg_last_error reports (defined next to it, in api_scene.cpp)
 inline int set_err(int code, const std::string &m) { t_err = m; return code; }
 
 struct dg_scene { dg::Scene *sc; };
+
+// What every reduced-planes call checks first (dg_plane_reduced_size, dg_reduce_planes_host / _device; the readbacks take the frame
+// size from their ctx): the descriptor, the frame size, the frame count.
+inline int check_plane_reduce(int width, int height, int n_frames, const dg_plane_reduce_desc *desc) {
+    if (!desc) return set_err(DG_ERR_INVALID, "null argument");
+    if (!dg::plane_reduce_desc_ok(*desc)) return set_err(DG_ERR_INVALID, "plane reduce descriptor: fx and fy in 1..16, a known rule, reserved 0");
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384]");
+    if (n_frames < 0) return set_err(DG_ERR_INVALID, "bad frame count");
+    return DG_OK;
+}
+// ... and of its eight planes: a source and its destination come together, and DG_PLANE_NEAREST needs the distance plane.
+inline int check_plane_pairs(const dg_plane_reduce_desc &desc, const void *distance, const void *kind, const void *id, const void *cls,
+                             const void *o_distance, const void *o_kind, const void *o_id, const void *o_cls) {
+    if (!distance != !o_distance || !kind != !o_kind || !id != !o_id || !cls != !o_cls)
+        return set_err(DG_ERR_INVALID, "a source plane without its destination, or a destination without its source");
+    if (desc.rule == DG_PLANE_NEAREST && !distance) return set_err(DG_ERR_INVALID, "DG_PLANE_NEAREST needs the distance plane");
+    return DG_OK;
+}

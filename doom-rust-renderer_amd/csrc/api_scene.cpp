@@ -1,6 +1,6 @@
 // api_scene.cpp — the entry points of the C-ABI (include/doomgpu.h) that need no GPU: the error string and the version, the scene
 // (dg_scene_*), one frame's lists and map lines on the host, the recorded walks, the box downscale on the host (dg_reduced_size,
-// dg_reduce_host), the depth planes, the label planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host,
+// dg_reduce_host) and the reduced depth and label planes (dg_plane_reduced_size, dg_reduce_planes_host), the depth planes, the label planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host,
 // dg_label_lists_host, dg_bundle_lists_host: one rule, plane_lists_host), a bundle's slab layout (dg_bundle_layout).  Everything that
 // takes a dg_ctx: context.cpp.
 #include <algorithm>
@@ -12,6 +12,7 @@
 #include "binner.hpp"
 #include "frontend.hpp"
 #include "plane_core.h"
+#include "plane_reduce_core.h"
 #include "reduce_core.h"
 #include "slab_layout.h"
 #include "walk.hpp"
@@ -317,6 +318,49 @@ int dg_reduce_host(const uint8_t *src_rgb24, int width, int height, int n_frames
                 }
                 if (gray) *dst++ = (uint8_t)reduce_luma(px[0], px[1], px[2]);
                 else { *dst++ = (uint8_t)px[0]; *dst++ = (uint8_t)px[1]; *dst++ = (uint8_t)px[2]; }
+            }
+        }
+    }
+    return DG_OK;
+}
+
+int dg_plane_reduced_size(int width, int height, const dg_plane_reduce_desc *desc, int *out_w, int *out_h) {
+    const int rc = check_plane_reduce(width, height, 0, desc);
+    if (rc) return rc;
+    if (out_w) *out_w = (int)reduce_out_dim((uint32_t)width, desc->fx);
+    if (out_h) *out_h = (int)reduce_out_dim((uint32_t)height, desc->fy);
+    return DG_OK;
+}
+
+int dg_reduce_planes_host(int width, int height, int n_frames, const dg_plane_reduce_desc *desc,
+                          const int16_t *distance, const uint8_t *kind, const uint16_t *id, const uint8_t *cls,
+                          int16_t *o_distance, uint8_t *o_kind, uint16_t *o_id, uint8_t *o_cls) {
+    int rc = check_plane_reduce(width, height, n_frames, desc);
+    if (!rc) rc = check_plane_pairs(*desc, distance, kind, id, cls, o_distance, o_kind, o_id, o_cls);
+    if (rc) return rc;
+    const uint32_t W = (uint32_t)width, H = (uint32_t)height, fx = desc->fx, fy = desc->fy;
+    const uint32_t oW = reduce_out_dim(W, fx), oH = reduce_out_dim(H, fy);
+    const size_t px = (size_t)W * H;
+    size_t o = 0;
+    for (int f = 0; f < n_frames; f++) {
+        const size_t base = (size_t)f * px;
+        for (uint32_t oy = 0; oy < oH; oy++) {
+            uint32_t y0;
+            const uint32_t ny = reduce_box(oy, fy, H, y0);
+            for (uint32_t ox = 0; ox < oW; ox++, o++) {
+                uint32_t x0, x, y;
+                const uint32_t nx = reduce_box(ox, fx, W, x0);
+                if (desc->rule == DG_PLANE_NEAREST) {
+                    const uint32_t key = plane_nearest_key(distance + base, W, x0, nx, y0, ny);
+                    x = x0 + plane_key_rx(key); y = y0 + plane_key_ry(key);
+                } else {
+                    x = plane_point(ox, fx, W); y = plane_point(oy, fy, H);
+                }
+                const size_t s = base + (size_t)y * W + x;
+                if (o_distance) o_distance[o] = distance[s];
+                if (o_kind) o_kind[o] = kind[s];
+                if (o_id) o_id[o] = id[s];
+                if (o_cls) o_cls[o] = cls[s];
             }
         }
     }

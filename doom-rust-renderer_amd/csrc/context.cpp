@@ -47,6 +47,7 @@
 #include "kernels.hpp"
 #include "map_kernels.hpp"
 #include "plane_kernels.hpp"
+#include "plane_reduce_kernels.hpp"
 #include "pool.hpp"
 #include "reduce_kernels.hpp"
 #include "scene.hpp"
@@ -75,17 +76,27 @@ struct Slot {
     // ev_raster has been recorded at least once: slot_sync waits only on an event that has.  Not part of the phase below, because it is
     // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
     bool raster_recorded = false;
-    hipStream_t copy_stream = nullptr;   // dg_readback_async / dg_readback_reduced_async: D2H of this slot's frames while another slot's kernels run
-    // What a readback moves: frames [first, first + count) to host memory `out`, as they are or reduced by `desc` on the way
+    hipStream_t copy_stream = nullptr;   // dg_readback_async / dg_readback_reduced_async / dg_readback_planes_reduced_async: D2H of this slot's frames while another slot's kernels run
+    // What a readback moves: frames [first, first + count) to host memory `out`, as they are or reduced by `desc` on the way; or
+    // (planes) the depth and label planes of those frames reduced by `pdesc` to the outputs that are there, and their box rows
     struct Readback {
         uint8_t *out = nullptr;
         int first = 0, count = 0;
-        bool reduced = false;
+        bool reduced = false;            // goes through the slot's scratch (d_reduced)
         dg_reduce_desc desc{};
+        bool planes = false;             // dg_readback_planes_reduced*: always with `reduced`
+        dg_plane_reduce_desc pdesc{};
+        int16_t *distance = nullptr;
+        uint8_t *kind = nullptr;
+        uint16_t *id = nullptr;
+        uint8_t *cls = nullptr;
+        dg_label_box *boxes = nullptr;   // filled from h_rawboxes when the copy has finished (finish_readback)
     } copy;                              // the pending asynchronous one (issued again if the batch has to be redone)
     bool copy_pending = false;
     DevPtr<uint8_t> d_reduced;           // reduced readbacks: the kernel's output, allocated by the first one, grown when a later one needs more
     size_t reduced_cap = 0;
+    PinnedPtr<LabelRawBox> h_rawboxes;   // reduced plane readbacks that ask for boxes: the box rows as the kernels left them, likewise
+    size_t rawbox_cap = 0;               // (entries)
     PinnedPtr<uint8_t> h_lists;   // pinned staging
     DevPtr<uint8_t> d_lists;
     DevPtr<DevRSpan> d_rspans;
@@ -294,6 +305,9 @@ struct dg_ctx {
     hipStream_t xstream = nullptr;
     hipEvent_t ev_reduce0 = nullptr, ev_reduce1 = nullptr;
     bool reduce_timed = false;
+    // dg_reduce_planes_device: the same stream, events of its own
+    hipEvent_t ev_preduce0 = nullptr, ev_preduce1 = nullptr;
+    bool plane_reduce_timed = false;
 };
 
 namespace {
@@ -337,7 +351,7 @@ void free_ctx(dg_ctx *c) {
     if (c->rstream) (void)hipStreamDestroy(c->rstream);
     if (c->wstream) { (void)hipStreamSynchronize(c->wstream); (void)hipStreamDestroy(c->wstream); }
     if (c->xstream) { (void)hipStreamSynchronize(c->xstream); (void)hipStreamDestroy(c->xstream); }
-    for (hipEvent_t ev : {c->ev_reduce0, c->ev_reduce1})
+    for (hipEvent_t ev : {c->ev_reduce0, c->ev_reduce1, c->ev_preduce0, c->ev_preduce1})
         if (ev) (void)hipEventDestroy(ev);
     delete c;
 }
@@ -988,8 +1002,83 @@ int reserve_reduced(Slot &s, size_t bytes) {
     return DG_OK;
 }
 
+// Room for `entries` raw box rows in the slot's pinned staging, under the same rule.
+int reserve_rawboxes(Slot &s, size_t entries) {
+    if (entries <= s.rawbox_cap) return DG_OK;
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    HIP_TRY(hipStreamSynchronize(s.copy_stream));
+    s.rawbox_cap = 0;
+    HIP_TRY(hip_alloc(s.h_rawboxes, entries * sizeof(LabelRawBox)));
+    s.rawbox_cap = entries;
+    return DG_OK;
+}
+
+// Where a reduced plane readback of `count` frames puts its outputs in the slot's scratch: the 16-bit planes first, every plane on a
+// 256-byte boundary, whether it is asked for or not (the scratch is sized for all four).
+struct PlaneScratch { size_t px, distance, id, kind, cls, total; };   // px: elements of one plane, byte offsets, bytes in all
+PlaneScratch plane_scratch(const dg_ctx *c, const dg_plane_reduce_desc &d, int count) {
+    const size_t px = (size_t)count * reduce_out_dim((uint32_t)c->cfg.width, d.fx) * reduce_out_dim((uint32_t)c->cfg.height, d.fy);
+    SlabCursor cur;
+    PlaneScratch p{};
+    p.px = px;
+    p.distance = cur.take(2 * px); p.id = cur.take(2 * px); p.kind = cur.take(px); p.cls = cur.take(px);
+    p.total = cur.next;
+    return p;
+}
+
+// A reduced plane readback on `stream`: dg_plane_nearest / dg_plane_point from the slot's planes into its scratch, the copies of the
+// planes asked for, and the box rows into the slot's pinned staging.
+int issue_plane_readback(dg_ctx *c, Slot &s, const Slot::Readback &r, hipStream_t stream) {
+    const size_t W = (size_t)c->cfg.width, H = (size_t)c->cfg.height, at = (size_t)r.first * W * H;
+    const BundleLayout L = s.layout(W, H);
+    const uint8_t *const fb = s.d_fb.get();
+    const PlaneScratch sc = plane_scratch(c, r.pdesc, r.count);
+    if (sc.total > s.reduced_cap) return set_err(DG_ERR_INVALID, "reduced readback: no scratch reserved");
+    uint8_t *const out = s.d_reduced.get();
+    PlaneReduceSrc src{};
+    PlaneReduceDst dst{};
+    if (s.holds(BUNDLE_DEPTH)) {
+        src.distance = reinterpret_cast<const int16_t *>(fb + L.distance) + at;        // (DG_PLANE_NEAREST reads it whatever is asked for)
+        src.kind = fb + L.kind + at;
+        if (r.distance) dst.distance = reinterpret_cast<int16_t *>(out + sc.distance);
+        if (r.kind) dst.kind = out + sc.kind;
+    }
+    if (s.holds(BUNDLE_LABELS)) {
+        src.id = reinterpret_cast<const uint16_t *>(fb + L.id) + at;
+        src.cls = fb + L.cls + at;
+        if (r.id) dst.id = reinterpret_cast<uint16_t *>(out + sc.id);
+        if (r.cls) dst.cls = out + sc.cls;
+    }
+    if (dst.distance || dst.kind || dst.id || dst.cls) {
+        HIP_TRY(launch_plane_reduce(src, c->cfg.width, c->cfg.height, r.count, r.pdesc, dst, stream));
+        const size_t px = sc.px;                               // (elements of one reduced plane over the count frames)
+        if (dst.distance) HIP_TRY(hipMemcpyAsync(r.distance, dst.distance, 2 * px, hipMemcpyDeviceToHost, stream));
+        if (dst.kind) HIP_TRY(hipMemcpyAsync(r.kind, dst.kind, px, hipMemcpyDeviceToHost, stream));
+        if (dst.id) HIP_TRY(hipMemcpyAsync(r.id, dst.id, 2 * px, hipMemcpyDeviceToHost, stream));
+        if (dst.cls) HIP_TRY(hipMemcpyAsync(r.cls, dst.cls, px, hipMemcpyDeviceToHost, stream));
+    }
+    const size_t n_boxes = (size_t)r.count * s.box_mobjs;
+    if (r.boxes && n_boxes) {
+        if (n_boxes > s.rawbox_cap) return set_err(DG_ERR_INVALID, "reduced readback: no box staging reserved");
+        HIP_TRY(hipMemcpyAsync(s.h_rawboxes.get(), s.d_boxes.get() + (size_t)r.first * s.box_mobjs, n_boxes * sizeof(LabelRawBox), hipMemcpyDeviceToHost, stream));
+    }
+    return DG_OK;
+}
+
+// What is left to do on the host once readback r's copies have finished: the box rows in the form the caller sees.
+void finish_readback(const dg_ctx *c, const Slot &s, const Slot::Readback &r) {
+    if (!r.planes || !r.boxes) return;
+    const size_t n_boxes = (size_t)r.count * s.box_mobjs;
+    for (size_t i = 0; i < n_boxes; i++) {
+        int32_t x0, y0, x1, y1;
+        label_box_finish(s.h_rawboxes.get()[i], c->cfg.width, c->cfg.height, r.boxes[i].pixels, x0, y0, x1, y1);
+        r.boxes[i].x0 = (int16_t)x0; r.boxes[i].y0 = (int16_t)y0; r.boxes[i].x1 = (int16_t)x1; r.boxes[i].y1 = (int16_t)y1;
+    }
+}
+
 // Readback r of the slot's frames on `stream`: the D2H copy of the frames themselves, or dg_reduce into the slot's scratch
-// (reserve_reduced) and the copy of that.  The caller has ordered `stream` behind the slot's kernels.
+// (reserve_reduced) and the copy of that, or the reduced planes (issue_plane_readback).  The caller has ordered `stream` behind the
+// slot's kernels.
 int issue_readback(dg_ctx *c, Slot &s, const Slot::Readback &r, hipStream_t stream) {
     const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
     const uint8_t *const frames = s.d_fb.get() + (size_t)r.first * fsz;
@@ -998,6 +1087,7 @@ int issue_readback(dg_ctx *c, Slot &s, const Slot::Readback &r, hipStream_t stre
         return DG_OK;
     }
     if (r.count == 0) return DG_OK;
+    if (r.planes) return issue_plane_readback(c, s, r, stream);
     const size_t bytes = (size_t)r.count * reduce_frame_bytes((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, r.desc);
     if (bytes > s.reduced_cap) return set_err(DG_ERR_INVALID, "reduced readback: no scratch reserved");
     HIP_TRY(launch_reduce(frames, c->cfg.width, c->cfg.height, r.count, r.desc, s.d_reduced.get(), stream));
@@ -1051,6 +1141,7 @@ int make_final(dg_ctx *c, Slot &s, Copy copy) {
             if (rc) return rc;
             HIP_TRY(hipStreamSynchronize(s.copy_stream));
         }
+        finish_readback(c, s, s.copy);
         s.copy_pending = false;
     }
     return DG_OK;
@@ -1355,6 +1446,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
         if (c->scene) (void)take_slot(c, s);
         HIP_TRY(slot_sync(s));
         HIP_TRY(hipStreamSynchronize(s.copy_stream));
+        if (s.copy_pending) finish_readback(c, s, s.copy);     // (a slot that was only drained: its copies have run all the same)
         s.copy_pending = false;
     }
     const Scene &sc = *scene->sc;
@@ -1701,6 +1793,108 @@ int dg_readback_labels(dg_ctx *c, int slot, int first, int count, uint16_t *id, 
         label_box_finish(raw[i], W, H, boxes[i].pixels, x0, y0, x1, y1);
         boxes[i].x0 = (int16_t)x0; boxes[i].y0 = (int16_t)y0; boxes[i].x1 = (int16_t)x1; boxes[i].y1 = (int16_t)y1;
     }
+    return DG_OK;
+}
+
+// What dg_readback_planes_reduced and its asynchronous twin check alike, in this order: the descriptor, the slot, what the slot holds
+// against what is asked for, the frame range.  *nothing: the call is valid and has nothing to do.
+static int check_plane_readback(dg_ctx *c, int slot, int first, int count, const dg_plane_reduce_desc *desc, const Slot::Readback &r, bool *nothing) {
+    if (!desc) return set_err(DG_ERR_INVALID, "null argument");
+    if (!plane_reduce_desc_ok(*desc)) return set_err(DG_ERR_INVALID, "plane reduce descriptor: fx and fy in 1..16, a known rule, reserved 0");
+    const int rc = check_slot(c, slot);
+    if (rc) return rc;
+    const Slot &s = c->slots[(size_t)slot];
+    if (!s.holds(BUNDLE_DEPTH) && !s.holds(BUNDLE_LABELS)) return set_err(DG_ERR_INVALID, "reduced planes: the slot holds neither depth nor label planes");
+    if ((r.distance || r.kind) && !s.holds(BUNDLE_DEPTH)) return set_err(DG_ERR_INVALID, "reduced planes: the slot has no depth part (distance, kind)");
+    if ((r.id || r.cls || r.boxes) && !s.holds(BUNDLE_LABELS)) return set_err(DG_ERR_INVALID, "reduced planes: the slot has no label part (id, cls, boxes)");
+    if (desc->rule == DG_PLANE_NEAREST && !s.holds(BUNDLE_DEPTH)) return set_err(DG_ERR_INVALID, "reduced planes: DG_PLANE_NEAREST needs a slot with a depth part");
+    if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
+    *nothing = count == 0 || !(r.distance || r.kind || r.id || r.cls || r.boxes);
+    return DG_OK;
+}
+
+// The scratch and the box staging readback r needs.
+static int reserve_plane_readback(dg_ctx *c, Slot &s, const Slot::Readback &r) {
+    const int rc = reserve_reduced(s, plane_scratch(c, r.pdesc, r.count).total);
+    if (rc) return rc;
+    return r.boxes ? reserve_rawboxes(s, (size_t)r.count * s.box_mobjs) : DG_OK;
+}
+
+static Slot::Readback plane_readback(int first, int count, const dg_plane_reduce_desc *desc, int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls,
+                                     dg_label_box *boxes) {
+    Slot::Readback r;
+    r.first = first; r.count = count; r.reduced = true; r.planes = true;
+    if (desc) r.pdesc = *desc;
+    r.distance = distance; r.kind = kind; r.id = id; r.cls = cls; r.boxes = boxes;
+    return r;
+}
+
+int dg_readback_planes_reduced_async(dg_ctx *c, int slot, int first, int count, const dg_plane_reduce_desc *desc,
+                                     int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
+    const Slot::Readback r = plane_readback(first, count, desc, distance, kind, id, cls, boxes);
+    bool nothing = false;
+    int rc = check_plane_readback(c, slot, first, count, desc, r, &nothing);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (s.copy_pending) return set_err(DG_ERR_INVALID, "the slot already has a readback in flight (dg_wait it first)");
+    if (nothing) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if ((rc = reserve_plane_readback(c, s, r))) return rc;
+    s.copy = r;
+    rc = enqueue_copy(c, s);
+    if (rc) return rc;
+    s.copy_pending = true;
+    return DG_OK;
+}
+
+int dg_readback_planes_reduced(dg_ctx *c, int slot, int first, int count, const dg_plane_reduce_desc *desc,
+                               int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
+    const Slot::Readback r = plane_readback(first, count, desc, distance, kind, id, cls, boxes);
+    bool nothing = false;
+    int rc = check_plane_readback(c, slot, first, count, desc, r, &nothing);
+    if (rc || nothing) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    // (a pending asynchronous reduced readback owns the slot's scratch and box staging: it is completed first)
+    rc = make_final(c, s, s.copy_pending && s.copy.reduced ? Copy::Complete : Copy::Leave);
+    if (rc) return rc;
+    if ((rc = reserve_plane_readback(c, s, r))) return rc;
+    rc = issue_readback(c, s, r, s.stream);
+    if (rc) return rc;
+    HIP_TRY(slot_sync(s));
+    finish_readback(c, s, r);
+    return DG_OK;
+}
+
+int dg_reduce_planes_device(dg_ctx *c, int width, int height, int n_frames, const dg_plane_reduce_desc *desc,
+                            const int16_t *distance, const uint8_t *kind, const uint16_t *id, const uint8_t *cls,
+                            int16_t *o_distance, uint8_t *o_kind, uint16_t *o_id, uint8_t *o_cls) {
+    if (!c) return set_err(DG_ERR_INVALID, "null argument");
+    int rc = check_plane_reduce(width, height, n_frames, desc);
+    if (!rc) rc = check_plane_pairs(*desc, distance, kind, id, cls, o_distance, o_kind, o_id, o_cls);
+    if (rc) return rc;
+    for (const void *p : {(const void *)distance, (const void *)id, (const void *)o_distance, (const void *)o_id})
+        if (reinterpret_cast<uintptr_t>(p) % 2u) return set_err(DG_ERR_INVALID, "dg_reduce_planes_device: a 16-bit plane must be 2-byte aligned");
+    if (n_frames == 0 || !(distance || kind || id || cls)) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!c->xstream) HIP_TRY(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
+    if (!c->ev_preduce0) HIP_TRY(hipEventCreate(&c->ev_preduce0));
+    if (!c->ev_preduce1) HIP_TRY(hipEventCreate(&c->ev_preduce1));
+    c->plane_reduce_timed = false;
+    hipError_t e = launch_plane_reduce(PlaneReduceSrc{distance, kind, id, cls}, width, height, n_frames, *desc, PlaneReduceDst{o_distance, o_kind, o_id, o_cls},
+                                       c->xstream, c->ev_preduce0, c->ev_preduce1);
+    const hipError_t es = hipStreamSynchronize(c->xstream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_reduce_planes_device: ") + hipGetErrorString(e));
+    c->plane_reduce_timed = true;
+    return DG_OK;
+}
+
+int dg_ctx_plane_reduce_kernel_ms(dg_ctx *c, float *ms) {
+    if (!c || !ms) return set_err(DG_ERR_INVALID, "null argument");
+    if (!c->plane_reduce_timed) return set_err(DG_ERR_INVALID, "no dg_reduce_planes_device call has launched yet");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipEventElapsedTime(ms, c->ev_preduce0, c->ev_preduce1));
     return DG_OK;
 }
 

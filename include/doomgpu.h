@@ -473,6 +473,60 @@ int dg_bundle_lists_host(const dg_scene *s, int width, int height, const dg_fram
  * DG_BUNDLE_COLOUR) and dg_bundle_tiles (0 for colour alone); any output may be NULL. */
 int dg_slot_bundle_timing(dg_ctx *ctx, int slot, float *setup_ms, float *raster_ms, float *tiles_ms);
 
+/* ---- reduced-size depth and label planes ------------------------------------------------------------------------------------------ */
+/* The reduced readback of the planes: dg_readback_reduced for distance, kind, id and cls, so that 1/(fx*fy) of their 6 bytes per pixel
+ * cross PCIe.  A mean of two object ids, or of a wall and the sky, is meaningless, so no value is computed: every box has ONE
+ * representative source pixel and every requested output plane takes that pixel's value unchanged — the distance, kind, id and cls of
+ * one output pixel always describe one real source pixel, and the planes stay consistent with each other.
+ *   Box geometry is dg_reduce_desc's: oW = ceil(W / fx), oH = ceil(H / fy); box (ox, oy) covers source columns [ox*fx, min(W, ox*fx + fx))
+ *   and rows likewise; a box at the right or bottom edge holds only the pixels that exist.
+ *   DG_PLANE_POINT    the representative is (min(W-1, ox*fx + fx/2), min(H-1, oy*fy + fy/2)), integer division.
+ *   DG_PLANE_NEAREST  the representative is the box pixel with the smallest `distance`, compared as the signed int16 it is stored as;
+ *                     ties go to the lowest row, then the lowest column.  Sky and unwritten pixels carry 32767, so any surface in a box
+ *                     wins over them; saturated and negative distances take part as stored.  This rule needs a distance plane.
+ * fx = fy = 1 is a copy under both rules.  Output: frame-major, rows top down, tightly packed, oW*oH elements per frame and plane.
+ * Boxes (dg_label_box) are NOT reduced: they are copied as they are, in full-size pixel coordinates.
+ * Out of scope: any pooling other than these two rules, and more than one readback in flight per slot — the colour of a bundle reduced
+ * asynchronously plus its planes reduced asynchronously is one asynchronous call and one blocking call. */
+enum { DG_PLANE_POINT = 0, DG_PLANE_NEAREST = 1 };
+typedef struct dg_plane_reduce_desc {
+    uint32_t fx, fy;             /* box size in source pixels, each 1..16 */
+    uint32_t rule;               /* DG_PLANE_POINT or DG_PLANE_NEAREST */
+    uint32_t reserved;           /* must be 0 */
+} dg_plane_reduce_desc;
+/* What every call below refuses with DG_ERR_INVALID: a NULL desc, a factor outside 1..16, an unknown rule, reserved != 0, width or height
+ * outside [1, 16384], n_frames < 0 or a bad frame range, a source plane without its destination or the reverse, DG_PLANE_NEAREST without
+ * a distance plane. */
+/* Size of a width x height plane reduced by desc (each pointer may be NULL).  Pure: no ctx, no GPU. */
+int dg_plane_reduced_size(int width, int height, const dg_plane_reduce_desc *desc, int *out_w, int *out_h);
+/* The rule on the CPU: n_frames planes of width x height (host memory) into their reduced twins.  Needs no ctx and no GPU, and is what
+ * the GPU paths below are tested against.  Any source / destination pair may be NULL together. */
+int dg_reduce_planes_host(int width, int height, int n_frames, const dg_plane_reduce_desc *desc,
+                          const int16_t *distance, const uint8_t *kind, const uint16_t *id, const uint8_t *cls,
+                          int16_t *o_distance, uint8_t *o_kind, uint16_t *o_id, uint8_t *o_cls);
+/* Device to device, synchronous, on the ctx's stream that belongs to no slot (dg_reduce_device's): the same eight pointers in the ctx's
+ * device memory — planes inside dg_slot_framebuffer of a finished slot, tensors' data pointers.  Touches no slot.  The 16-bit planes
+ * must be 2-byte aligned (else DG_ERR_INVALID); otherwise any alignment is accepted. */
+int dg_reduce_planes_device(dg_ctx *ctx, int width, int height, int n_frames, const dg_plane_reduce_desc *desc,
+                            const int16_t *distance, const uint8_t *kind, const uint16_t *id, const uint8_t *cls,
+                            int16_t *o_distance, uint8_t *o_kind, uint16_t *o_id, uint8_t *o_cls);
+/* GPU time of the last dg_reduce_planes_device call's kernel in milliseconds, from events attached to the dispatch itself.
+ * DG_ERR_INVALID: a NULL argument, no dg_reduce_planes_device call that launched yet. */
+int dg_ctx_plane_reduce_kernel_ms(dg_ctx *ctx, float *ms);
+/* dg_readback_depth / dg_readback_labels with the reduction in front of the copy, on a depth slot, a label slot or a bundle slot:
+ * frames [first, first+count) are reduced on the GPU into the slot's scratch buffer (dg_readback_reduced's) and count reduced planes are
+ * copied to each output that is not NULL; `boxes` receives count * dg_scene_mobj_count full-size boxes.  distance and kind need a depth
+ * part, id, cls and boxes a label part, DG_PLANE_NEAREST a depth part whatever is asked for: DG_ERR_INVALID otherwise, and on a slot that
+ * holds neither part (a colour submission, a bundle of colour alone).  All outputs NULL, or count == 0: DG_OK, nothing is done.
+ * Waits for the slot like dg_readback, and leaves the slot's planes as they are. */
+int dg_readback_planes_reduced(dg_ctx *ctx, int slot, int first, int count, const dg_plane_reduce_desc *desc,
+                               int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes);
+/* The same without waiting, under every rule of dg_readback_reduced_async: the kernel and the copies are queued behind the slot's
+ * kernels on the slot's copy stream; the outputs should be page-locked and are complete after dg_wait(slot); a new submission into the
+ * slot and dg_upload_scene complete it first.  One readback in flight per slot, of any kind: a second one is DG_ERR_INVALID. */
+int dg_readback_planes_reduced_async(dg_ctx *ctx, int slot, int first, int count, const dg_plane_reduce_desc *desc,
+                                     int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes);
+
 /* ---- 2-D map view (reference: Game::render with viewing_map, src/game.rs:491-499, 229-309) --------------------------------- */
 /* What the window holds after render() in map mode, RGB24 like every frame: black; every linedef without DONTDRAW (flags & 128) in
  * LINEDEFS order, yellow (255, 255, 0) when TWOSIDED (flags & 4) else red (255, 0, 0); then the player arrow in yellow: P->E, R->E, L->E.
@@ -538,7 +592,7 @@ const char *dg_last_error(void); /* thread-local message of the last failing cal
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
