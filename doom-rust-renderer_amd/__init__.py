@@ -31,6 +31,7 @@ DG_FE_BUNDLE = 7  # dg_timing.front_end of a bundle submission
 DG_BUNDLE_COLOUR, DG_BUNDLE_DEPTH, DG_BUNDLE_LABELS = 1, 2, 4   # the parts of a bundle submission (`what`)
 # dg_label_box as a numpy record: boxes come back as an (n, map objects) array of these
 LABEL_BOX_DTYPE = np.dtype([("pixels", "<u4"), ("x0", "<i2"), ("y0", "<i2"), ("x1", "<i2"), ("y1", "<i2")])
+DG_FE_MAP_EXPLORED = 8  # dg_timing.front_end of an explored-map submission
 DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
 DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
@@ -226,6 +227,15 @@ _SIGNATURES = {
     "dg_ctx_plane_reduce_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "dg_readback_planes_reduced": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 5),
     "dg_readback_planes_reduced_async": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 5),
+    "dg_seen_words": (ctypes.c_int, [_P]),
+    "dg_seen_lines_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "dg_seen_accumulate_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_P] * 6),
+    "dg_explored_map_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), _P, _P]),
+    "dg_seen_lines_device": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "dg_slot_seen_lines": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_P] * 5),
+    "dg_ctx_seen_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "dg_submit_explored_map_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int, _P]),
+    "dg_render_explored_map_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, _P, _P]),
     "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
     "dg_walk_free": (None, [_P]),
     "dg_walk_tics": (ctypes.c_int, [_P]),
@@ -388,6 +398,52 @@ def bundle_lists_host(scene, width: int, height: int, frames, owners=None, dista
     op, keep = owner_pointers(owners) if owners is not None else (None, None)
     _check(lib().dg_bundle_lists_host(scene._h, width, height, frames, op, n, dp, kp, *ptrs))
     return (d, k) + tuple(out)
+
+
+def seen_words(scene) -> int:
+    """dg_seen_words: the uint32 words of one seen row of the scene (ceil(linedefs / 32))."""
+    return _check(lib().dg_seen_words(scene._h))
+
+
+def seen_lines_host(scene, id, cls) -> np.ndarray:
+    """dg_seen_lines_host: the seen rows (n, words) uint32 of label planes id (n, H, W) uint16 and cls (n, H, W) uint8, on the CPU."""
+    i = np.ascontiguousarray(id, dtype=np.uint16)
+    c = np.ascontiguousarray(cls, dtype=np.uint8)
+    if i.ndim != 3 or c.shape != i.shape:
+        raise ValueError("id and cls must have one shape (n, H, W)")
+    n, h, w = i.shape
+    out = np.empty((n, seen_words(scene)), dtype=np.uint32)
+    _check(lib().dg_seen_lines_host(scene._h, w, h, n, i.ctypes.data_as(_P), c.ctypes.data_as(_P), out.ctypes.data_as(_P)))
+    return out
+
+
+def _seen_outputs(count: int, runs: int, words: int, want):
+    """The outputs of an accumulation to fill, {name: array} for the names in `want`, and the four pointers to hand over."""
+    shapes = {"upto": (count, words), "total": (count,), "fresh": (count,), "carry_out": (runs, words)}
+    out = {k: np.empty(shapes[k], dtype=np.uint32) for k in shapes if k in want}
+    return out, [out[k].ctypes.data_as(_P) if k in out else None for k in shapes]
+
+
+SEEN_OUTPUTS = ("upto", "total", "fresh", "carry_out")
+
+
+def seen_accumulate_host(seen, run_len: int, carry_in=None, want=SEEN_OUTPUTS) -> dict:
+    """dg_seen_accumulate_host: the running OR of the rows `seen` (n, words) along runs of run_len frames; carry_in (n / run_len, words)
+    or None.  Returns {name: array} for the outputs named in `want` (upto, total, fresh, carry_out)."""
+    sn = np.ascontiguousarray(seen, dtype=np.uint32)
+    n, words = sn.shape
+    ci = None if carry_in is None else np.ascontiguousarray(carry_in, dtype=np.uint32)
+    out, ptrs = _seen_outputs(n, n // run_len if run_len > 0 else 0, words, want)
+    _check(lib().dg_seen_accumulate_host(words, n, run_len, None if ci is None else ci.ctypes.data_as(_P), sn.ctypes.data_as(_P), *ptrs))
+    return out
+
+
+def explored_map_host(scene, width: int, height: int, view, mask_row) -> np.ndarray:
+    """dg_explored_map_host: one explored map frame (H, W, 3) uint8 by the literal rule; view None: no arrow."""
+    m = np.ascontiguousarray(mask_row, dtype=np.uint32)
+    out = np.empty((height, width, 3), dtype=np.uint8)
+    _check(lib().dg_explored_map_host(scene._h, width, height, ctypes.byref(view) if view is not None else None, m.ctypes.data_as(_P), out.ctypes.data_as(_P)))
+    return out
 
 
 def make_view_states(states):
@@ -603,6 +659,39 @@ class Context:
         out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
         _check(lib().dg_render_map_views(self._h, views, n, out.ctypes.data_as(_P)))
         return out
+
+    def submit_explored_map(self, slot: int, views, mask, n=None):
+        """dg_submit_explored_map_views: map frames that show only the linedefs whose bit is set in mask (n, words) uint32, asynchronously."""
+        m = np.ascontiguousarray(mask, dtype=np.uint32)
+        _check(lib().dg_submit_explored_map_views(self._h, slot, views, len(views) if n is None else n, m.ctypes.data_as(_P)))
+
+    def render_explored_map(self, views, mask) -> np.ndarray:
+        """dg_render_explored_map_views: synchronous through slot 0; returns (n, H, W, 3) uint8."""
+        n = len(views)
+        m = np.ascontiguousarray(mask, dtype=np.uint32)
+        out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
+        _check(lib().dg_render_explored_map_views(self._h, views, n, m.ctypes.data_as(_P), out.ctypes.data_as(_P)))
+        return out
+
+    def seen_lines_device(self, width: int, height: int, n_frames: int, id_ptr: int, cls_ptr: int, seen_ptr: int):
+        """dg_seen_lines_device: the seen rows of n_frames label planes at the device addresses id_ptr / cls_ptr into device address seen_ptr
+        (synchronous; planes of a finished slot's framebuffer_ptr or tensors' data_ptr()).  Touches no slot."""
+        _check(lib().dg_seen_lines_device(self._h, width, height, n_frames, _P(id_ptr), _P(cls_ptr), _P(seen_ptr)))
+
+    def slot_seen_lines(self, slot: int, first: int, count: int, run_len: int, carry_in=None, want=SEEN_OUTPUTS) -> dict:
+        """dg_slot_seen_lines: the seen rows of frames [first, first + count) of a label slot (or a bundle slot with labels), accumulated along
+        runs of run_len frames; carry_in (count / run_len, words) or None.  Returns {name: array} for the outputs named in `want`."""
+        words = seen_words(self._scene)
+        ci = None if carry_in is None else np.ascontiguousarray(carry_in, dtype=np.uint32)
+        out, ptrs = _seen_outputs(count, count // run_len if run_len > 0 else 0, words, want)
+        _check(lib().dg_slot_seen_lines(self._h, slot, first, count, run_len, None if ci is None else ci.ctypes.data_as(_P), *ptrs))
+        return out
+
+    def seen_kernel_ms(self) -> dict:
+        """dg_ctx_seen_kernel_ms: GPU time (ms) of the last seen_lines_device / slot_seen_lines call's kernels."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(lib().dg_ctx_seen_kernel_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return {"lines_ms": a.value, "accumulate_ms": b.value}
 
     def render_state(self, views, states) -> np.ndarray:
         """render() with one game-state snapshot per view (make_view_states)."""

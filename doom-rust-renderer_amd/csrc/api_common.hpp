@@ -3,6 +3,7 @@
 #include <string>
 
 #include "../../include/doomgpu.h"
+#include "binner.hpp"
 #include "plane_reduce_core.h"
 #include "scene.hpp"
 
@@ -26,5 +27,24 @@ inline int check_plane_pairs(const dg_plane_reduce_desc &desc, const void *dista
     if (!distance != !o_distance || !kind != !o_kind || !id != !o_id || !cls != !o_cls)
         return set_err(DG_ERR_INVALID, "a source plane without its destination, or a destination without its source");
     if (desc.rule == DG_PLANE_NEAREST && !distance) return set_err(DG_ERR_INVALID, "DG_PLANE_NEAREST needs the distance plane");
+    return DG_OK;
+}
+
+// What dg_seen_lines_host and dg_seen_lines_device check alike: the scene (label frames' limit included), the plane size, the frame
+// count, the three pointers.
+inline int check_seen_lines(const dg::Scene *sc, int width, int height, int n, const void *id, const void *cls, const void *seen) {
+    if (!sc) return set_err(DG_ERR_INVALID, "null scene");
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384]");
+    if (n < 0) return set_err(DG_ERR_INVALID, "bad frame count");
+    if (!id || !cls || !seen) return set_err(DG_ERR_INVALID, "null argument");
+    std::string err;
+    const int rc = dg::check_label_scene(*sc, err);
+    return rc ? set_err(rc, err) : DG_OK;
+}
+// ... and dg_seen_accumulate_host and dg_slot_seen_lines: count frames as whole runs of run_len.
+inline int check_seen_runs(int words, int count, int run_len) {
+    if (words < 1) return set_err(DG_ERR_INVALID, "a seen row has at least one word");
+    if (count < 0) return set_err(DG_ERR_INVALID, "bad frame count");
+    if (run_len < 1 || count % run_len) return set_err(DG_ERR_INVALID, "the frames must be whole runs of run_len >= 1");
     return DG_OK;
 }

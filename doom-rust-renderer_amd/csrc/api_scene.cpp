@@ -1,8 +1,9 @@
 // api_scene.cpp — the entry points of the C-ABI (include/doomgpu.h) that need no GPU: the error string and the version, the scene
 // (dg_scene_*), one frame's lists and map lines on the host, the recorded walks, the box downscale on the host (dg_reduced_size,
-// dg_reduce_host) and the reduced depth and label planes (dg_plane_reduced_size, dg_reduce_planes_host), the depth planes, the label planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host,
-// dg_label_lists_host, dg_bundle_lists_host: one rule, plane_lists_host), a bundle's slab layout (dg_bundle_layout).  Everything that
-// takes a dg_ctx: context.cpp.
+// dg_reduce_host) and the reduced depth and label planes (dg_plane_reduced_size, dg_reduce_planes_host), the depth planes, the label
+// planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host, dg_label_lists_host,
+// dg_bundle_lists_host: one rule, plane_lists_host), a bundle's slab layout (dg_bundle_layout), and the explored-map frames' host rules
+// (dg_seen_words, dg_seen_lines_host, dg_seen_accumulate_host, dg_explored_map_host).  Everything that takes a dg_ctx: context.cpp.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -10,6 +11,7 @@
 
 #include "api_common.hpp"
 #include "binner.hpp"
+#include "explored_cover.hpp"
 #include "frontend.hpp"
 #include "plane_core.h"
 #include "plane_reduce_core.h"
@@ -393,6 +395,81 @@ int dg_bundle_lists_host(const dg_scene *s, int width, int height, const dg_fram
     if (!s || !frames) return set_err(DG_ERR_INVALID, "null argument");
     if (labels && !owners) return set_err(DG_ERR_INVALID, "null owners: the label outputs need the owner tags");
     return plane_lists_host(s, width, height, frames, owners, n, labels, distance, kind, id, cls, boxes);
+}
+
+int dg_seen_words(const dg_scene *s) {
+    if (!s) return set_err(DG_ERR_INVALID, "null scene");
+    return (int)seen_words((uint32_t)s->sc->linedefs.size());
+}
+
+int dg_seen_lines_host(const dg_scene *s, int width, int height, int n, const uint16_t *id, const uint8_t *cls, uint32_t *seen) {
+    const int rc = check_seen_lines(s ? s->sc : nullptr, width, height, n, id, cls, seen);
+    if (rc) return rc;
+    const Scene &sc = *s->sc;
+    const size_t px = (size_t)width * (size_t)height, words = seen_words((uint32_t)sc.linedefs.size());
+    const uint32_t n_segs = (uint32_t)sc.segs.size();
+    std::memset(seen, 0, (size_t)n * words * sizeof(uint32_t));
+    for (int f = 0; f < n; f++) {
+        uint32_t *const row = seen + (size_t)f * words;
+        for (size_t p = (size_t)f * px; p < (size_t)(f + 1) * px; p++) {
+            if (!seen_pixel(cls[p], id[p], n_segs)) continue;
+            const uint32_t line = (uint32_t)sc.segs[id[p]].linedef;
+            row[line >> 5] |= 1u << (line & 31u);
+        }
+    }
+    return DG_OK;
+}
+
+int dg_seen_accumulate_host(int words, int n, int run_len, const uint32_t *carry_in, const uint32_t *seen, uint32_t *upto, uint32_t *total,
+                            uint32_t *fresh, uint32_t *carry_out) {
+    const int rc = check_seen_runs(words, n, run_len);
+    if (rc) return rc;
+    if (n > 0 && !seen) return set_err(DG_ERR_INVALID, "null seen rows");
+    const size_t Wd = (size_t)words;
+    std::vector<uint32_t> acc(Wd);
+    for (int run = 0; run < n / run_len; run++) {
+        for (size_t w = 0; w < Wd; w++) acc[w] = carry_in ? carry_in[(size_t)run * Wd + w] : 0u;
+        for (int f = run * run_len; f < (run + 1) * run_len; f++) {
+            uint32_t t = 0, fr = 0;
+            for (size_t w = 0; w < Wd; w++) {
+                const uint32_t next = acc[w] | seen[(size_t)f * Wd + w];
+                fr += popcount32(next & ~acc[w]);
+                t += popcount32(next);
+                acc[w] = next;
+                if (upto) upto[(size_t)f * Wd + w] = next;
+            }
+            if (total) total[f] = t;
+            if (fresh) fresh[f] = fr;
+        }
+        if (carry_out) std::memcpy(carry_out + (size_t)run * Wd, acc.data(), Wd * sizeof(uint32_t));
+    }
+    return DG_OK;
+}
+
+// The literal rule: black, the drawn linedefs whose bit is set in LINEDEFS order, then the arrow, every point through map_seg_point.
+int dg_explored_map_host(const dg_scene *s, int width, int height, const dg_view *view, const uint32_t *mask_row, uint8_t *rgb24_out) {
+    if (!s || !mask_row || !rgb24_out) return set_err(DG_ERR_INVALID, "null argument");
+    dg_view v{};
+    if (view) { v = *view; fill_view_trig(v); }
+    std::vector<dg_map_line> lines;
+    std::string err;
+    const int rc = map_frame_lines(*s->sc, width, height, view ? &v : nullptr, lines, err);
+    if (rc) return set_err(rc, err);
+    const std::vector<uint32_t> ids = explored_line_ids(*s->sc);
+    std::memset(rgb24_out, 0, (size_t)3 * (size_t)width * (size_t)height);
+    for (size_t k = 0; k < lines.size(); k++) {
+        if (k < ids.size() && !((mask_row[ids[k] >> 5] >> (ids[k] & 31u)) & 1u)) continue;       // (k >= ids.size(): the arrow)
+        const dg_map_line &l = lines[k];
+        const MapSeg sg = map_seg_make(l.x0, l.y0, l.x1, l.y1, l.rgb, width, height);
+        for (int32_t i = 0; i < sg.count; i++) {
+            int32_t x, y;
+            map_seg_point(sg, (int64_t)sg.first + i, x, y);
+            if ((uint32_t)x >= (uint32_t)width || (uint32_t)y >= (uint32_t)height) continue;
+            uint8_t *const px = rgb24_out + 3 * ((size_t)y * (size_t)width + (size_t)x);
+            px[0] = (uint8_t)l.rgb; px[1] = (uint8_t)(l.rgb >> 8); px[2] = (uint8_t)(l.rgb >> 16);
+        }
+    }
+    return DG_OK;
 }
 
 }  // extern "C"

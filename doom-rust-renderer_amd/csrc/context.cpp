@@ -45,6 +45,8 @@
 #include "frontend.hpp"
 #include "hip_mem.hpp"
 #include "kernels.hpp"
+#include "explored_cover.hpp"
+#include "explored_kernels.hpp"
 #include "map_kernels.hpp"
 #include "plane_kernels.hpp"
 #include "plane_reduce_kernels.hpp"
@@ -108,6 +110,11 @@ struct Slot {
     DevPtr<uint32_t> d_owners;
     DevPtr<LabelRawBox> d_boxes;
     size_t box_mobjs = 0;
+    // explored-map frames: the mask rows of the last such submission (staging + HBM, max_batch x mask_words), kept for dg_replay_slot — none
+    // of it exists before the slot's first explored submission; dg_upload_scene drops it (the row length is the scene's)
+    PinnedPtr<uint32_t> h_masks;
+    DevPtr<uint32_t> d_masks;
+    size_t mask_words = 0;
     // last submission
     RasterParams P{};
     uint32_t max_spans = 0;
@@ -153,6 +160,7 @@ struct Slot {
     }
     bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
     bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
+    bool map_frames() const { return front_end == DG_FE_MAP || front_end == DG_FE_MAP_EXPLORED; }   // arrow lines at the start of d_lists
     bool holds_bundle() const { return front_end == DG_FE_BUNDLE && phase != Phase::Empty; }
     // Which parts the framebuffer slab holds (BUNDLE_*: RGB24 colour frames, the two depth planes, the two label planes) ...
     uint32_t parts() const {
@@ -308,6 +316,18 @@ struct dg_ctx {
     // dg_reduce_planes_device: the same stream, events of its own
     hipEvent_t ev_preduce0 = nullptr, ev_preduce1 = nullptr;
     bool plane_reduce_timed = false;
+    // explored-map frames.  dg_seen_lines_device / dg_slot_seen_lines: the uploaded scene's seg -> linedef table (uploaded by the first call
+    // after dg_upload_scene), the scratch rows of dg_slot_seen_lines (allocated at first use, sized by max_batch and the scene's row
+    // length) and the events of the last call's kernels, all on xstream.  dg_submit_explored_map_views: the cover and its chains
+    // (explored_core.h), built by the first such submission after dg_upload_scene.
+    DevPtr<uint32_t> d_seg_line;
+    bool seg_line_ok = false;
+    DevPtr<uint32_t> d_seen_scratch;
+    size_t seen_scratch_words = 0;      // the row length the scratch was laid out for (0: none)
+    hipEvent_t ev_seen0 = nullptr, ev_seen1 = nullptr, ev_seen2 = nullptr, ev_seen3 = nullptr;
+    bool seen_timed = false, seen_acc_timed = false;
+    DevPtr<uint32_t> d_cover, d_chains;
+    bool cover_ok = false;
 };
 
 namespace {
@@ -351,7 +371,7 @@ void free_ctx(dg_ctx *c) {
     if (c->rstream) (void)hipStreamDestroy(c->rstream);
     if (c->wstream) { (void)hipStreamSynchronize(c->wstream); (void)hipStreamDestroy(c->wstream); }
     if (c->xstream) { (void)hipStreamSynchronize(c->xstream); (void)hipStreamDestroy(c->xstream); }
-    for (hipEvent_t ev : {c->ev_reduce0, c->ev_reduce1, c->ev_preduce0, c->ev_preduce1})
+    for (hipEvent_t ev : {c->ev_reduce0, c->ev_reduce1, c->ev_preduce0, c->ev_preduce1, c->ev_seen0, c->ev_seen1, c->ev_seen2, c->ev_seen3})
         if (ev) (void)hipEventDestroy(ev);
     delete c;
 }
@@ -839,6 +859,24 @@ int build_map_layer(dg_ctx *c, Slot &s) {
     return DG_OK;
 }
 
+// The explored-map frames' cover of the uploaded scene at the ctx's frame size: built on the host (explored_cover.hpp) and copied on the
+// kernel stream between the slot's ev_start / ev_setup.
+int upload_explored_cover(dg_ctx *c, Slot &s) {
+    ExploredCover cv;
+    std::string err;
+    const int rc = build_explored_cover(*c->scene, c->cfg.width, c->cfg.height, cv, err);
+    if (rc) return set_err(rc, err);
+    HIP_TRY(hip_alloc(c->d_cover, cv.cover.size() * 4));
+    HIP_TRY(hip_alloc(c->d_chains, cv.chains.size() * 4));
+    HIP_TRY(hipEventRecord(s.ev_start, c->kstream));
+    HIP_TRY(hipMemcpyAsync(c->d_cover.get(), cv.cover.data(), cv.cover.size() * 4, hipMemcpyHostToDevice, c->kstream));
+    HIP_TRY(hipMemcpyAsync(c->d_chains.get(), cv.chains.data(), cv.chains.size() * 4, hipMemcpyHostToDevice, c->kstream));
+    HIP_TRY(hipEventRecord(s.ev_setup, c->kstream));
+    HIP_TRY(hipStreamSynchronize(c->kstream));           // (before the host copy goes)
+    c->cover_ok = true;
+    return DG_OK;
+}
+
 constexpr size_t kOverlapMaxPixels = 500000;          // frames up to this size overlap their raster launch with the next batch's front end (dg_create)
 
 // A submission's last step: its kernels are enqueued.  harvested: DG_FE_AUTO has nothing to read from it.
@@ -868,11 +906,18 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     const bool fe_mode = s.column_walk();
     HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
     HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
-    const bool map = s.front_end == DG_FE_MAP;
+    const bool map = s.front_end == DG_FE_MAP, explored = s.front_end == DG_FE_MAP_EXPLORED;
     if (map) {                                            // 2-D map frames: the layer (once per scene upload), then copy + arrow per frame
         s.map_built = false;
         if (!c->map_layer_ok) {
             const int rc = build_map_layer(c, s);
+            if (rc) return rc;
+            s.map_built = true;
+        }
+    } else if (explored) {                                // explored map frames: the cover (once per scene upload), then pick + arrow per frame
+        s.map_built = false;
+        if (!c->cover_ok) {
+            const int rc = upload_explored_cover(c, s);
             if (rc) return rc;
             s.map_built = true;
         }
@@ -898,6 +943,9 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     if (map) {
         HIP_TRY(launch_map_frames(c->d_map_layer.get(), reinterpret_cast<const MapSeg *>(s.d_lists.get()), s.n_frames, s.d_fb.get(), c->cfg.width, c->cfg.height,
                                   ks, s.ev_rstart, s.ev_raster));
+    } else if (explored) {
+        HIP_TRY(launch_explored_frames(c->d_cover.get(), c->d_chains.get(), s.d_masks.get(), (uint32_t)s.mask_words, reinterpret_cast<const MapSeg *>(s.d_lists.get()),
+                                       s.n_frames, s.d_fb.get(), c->cfg.width, c->cfg.height, ks, s.ev_rstart, s.ev_raster));
     } else if (c->raster_overlap && fe_mode) {                   // the front end of the next batch may start while this launch runs (the column scratch is the front end's alone)
         HIP_TRY(hipStreamWaitEvent(c->rstream, s.ev_setup, 0));
         HIP_TRY(launch_raster(s.P, c->rstream, s.ev_rstart, s.ev_raster));
@@ -1453,7 +1501,13 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     c->d_palette.reset(); c->d_texel_idx.reset(); c->d_texel_opq.reset();
     c->d_flats = nullptr;               // inside d_texel_idx's allocation
     // the slots' prepared records point into the device scene that was just freed: nothing may be replayed from them
-    for (Slot &s : c->slots) { s.reset(); s.d_boxes.reset(); s.box_mobjs = 0; }   // (the box table is sized by the scene's map objects)
+    for (Slot &s : c->slots) {                                                    // (the box table is sized by the scene's map objects, a mask row by its linedefs)
+        s.reset(); s.d_boxes.reset(); s.box_mobjs = 0;
+        s.d_masks.reset(); s.h_masks.reset(); s.mask_words = 0;
+    }
+    c->seg_line_ok = false;             // dg_seen_lines_device / dg_slot_seen_lines are synchronous: nothing of them is in flight
+    c->d_seen_scratch.reset(); c->seen_scratch_words = 0;
+    c->cover_ok = false;                // the explored map's cover belongs to the old scene
     c->d_walk_tables.reset();           // dg_ctx_locate_walks is synchronous: nothing of it is in flight
     c->map_layer_ok = false;            // the map view's linedef layer belongs to the old scene   // (a new scene may reuse the old one's address and revision)
     uint32_t pal[256];
@@ -1999,6 +2053,147 @@ int dg_render_map_views(dg_ctx *c, const dg_view *views, int n, uint8_t *out) {
     return read_or_wait(c, 0, dg_submit_map_views(c, 0, views, n), n, out);
 }
 
+int dg_submit_explored_map_views(dg_ctx *c, int slot, const dg_view *views, int n, const uint32_t *mask) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!views || !mask) return set_err(DG_ERR_INVALID, "null views or mask");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    const int W = c->cfg.width, H = c->cfg.height;
+    if (W < 40 || H < 40) return set_err(DG_ERR_INVALID, "map frames need width and height >= 40");
+    if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
+    const size_t words = seen_words((uint32_t)c->scene->linedefs.size());
+    if (words > EXPLORED_MAX_WORDS) return set_err(DG_ERR_CAPACITY, "explored map frames: more than 65536 linedefs");
+    if (words == 0) return set_err(DG_ERR_INVALID, "explored map frames: the scene has no linedefs");
+    const size_t bytes = (size_t)n * 3 * sizeof(MapSeg), mask_bytes = (size_t)n * words * sizeof(uint32_t);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    Slot &s = c->slots[(size_t)slot];
+    rc = take_slot(c, s);
+    if (rc) return rc;
+    if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
+    if (!s.d_masks) {                                     // (the slot is ours: whatever replayed the old rows has finished)
+        HIP_TRY(slot_sync(s));
+        HIP_TRY(hip_alloc(s.h_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
+        HIP_TRY(hip_alloc(s.d_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
+        s.mask_words = words;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
+    std::string err;
+    for (int i = 0; i < n; i++) {
+        dg_view v = views[i];
+        fill_view_trig(v);
+        dg_map_line l[3];
+        rc = map_arrow_lines(*c->scene, W, H, v, l, err);
+        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
+        for (int k = 0; k < 3; k++) h[3 * i + k] = map_seg_make(l[k].x0, l[k].y0, l[k].x1, l[k].y1, l[k].rgb, W, H);
+    }
+    std::memcpy(s.h_masks.get(), mask, mask_bytes);
+    s.describe(DG_FE_MAP_EXPLORED, n, bytes + mask_bytes, 0, 0);
+    s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.d_masks.get(), s.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream));
+    return enqueue_kernels(c, s);
+}
+
+int dg_render_explored_map_views(dg_ctx *c, const dg_view *views, int n, const uint32_t *mask, uint8_t *out) {
+    return read_or_wait(c, 0, dg_submit_explored_map_views(c, 0, views, n, mask), n, out);
+}
+
+// What dg_seen_lines_device and dg_slot_seen_lines need of the ctx: the no-slot stream, their events, the uploaded scene's seg -> linedef table.
+static int ensure_seen(dg_ctx *c) {
+    if (!c->xstream) HIP_TRY(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
+    for (hipEvent_t *ev : {&c->ev_seen0, &c->ev_seen1, &c->ev_seen2, &c->ev_seen3})
+        if (!*ev) HIP_TRY(hipEventCreate(ev));
+    if (!c->seg_line_ok) {
+        const Scene &sc = *c->scene;
+        std::vector<uint32_t> table(std::max<size_t>(sc.segs.size(), 4), 0u);
+        for (size_t k = 0; k < sc.segs.size(); k++) table[k] = (uint32_t)sc.segs[k].linedef;
+        HIP_TRY(hip_alloc(c->d_seg_line, table.size() * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(c->d_seg_line.get(), table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        c->seg_line_ok = true;
+    }
+    return DG_OK;
+}
+
+int dg_seen_lines_device(dg_ctx *c, int width, int height, int n, const uint16_t *id, const uint8_t *cls, uint32_t *seen) {
+    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    int rc = check_seen_lines(c->scene, width, height, n, id, cls, seen);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(id) % 2u || reinterpret_cast<uintptr_t>(seen) % 4u)
+        return set_err(DG_ERR_INVALID, "dg_seen_lines_device: the id plane must be 2-byte aligned, the seen rows 4-byte aligned");
+    const uint32_t words = seen_words((uint32_t)c->scene->linedefs.size());
+    if (n == 0 || words == 0) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if ((rc = ensure_seen(c))) return rc;
+    c->seen_timed = false; c->seen_acc_timed = false;
+    hipError_t e = hipMemsetAsync(seen, 0, (size_t)n * words * sizeof(uint32_t), c->xstream);
+    if (e == hipSuccess)
+        e = launch_seen_lines(id, cls, width, height, n, c->d_seg_line.get(), (uint32_t)c->scene->segs.size(), seen, words, c->xstream, c->ev_seen0, c->ev_seen1);
+    const hipError_t es = hipStreamSynchronize(c->xstream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_seen_lines_device: ") + hipGetErrorString(e));
+    c->seen_timed = true;
+    return DG_OK;
+}
+
+int dg_slot_seen_lines(dg_ctx *c, int slot, int first, int count, int run_len, const uint32_t *carry_in, uint32_t *upto, uint32_t *total,
+                       uint32_t *fresh, uint32_t *carry_out) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.holds(BUNDLE_LABELS))
+        return set_err(DG_ERR_INVALID, s.holds_bundle() ? "dg_slot_seen_lines: the slot's bundle has no label part (DG_BUNDLE_LABELS)"
+                                                        : "dg_slot_seen_lines: the slot's last submission is not a label submission");
+    if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad frame range");
+    const size_t words = seen_words((uint32_t)c->scene->linedefs.size());
+    if ((rc = check_seen_runs((int)std::max<size_t>(words, 1), count, run_len))) return rc;
+    if (count == 0 || words == 0) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if ((rc = make_final(c, s, Copy::Leave))) return rc;
+    if ((rc = ensure_seen(c))) return rc;
+    // scratch rows: seen | upto | carry_in | carry_out (max_batch rows each), then total | fresh (max_batch entries each)
+    const size_t rows = (size_t)c->cfg.max_batch, block = rows * words;
+    if (c->seen_scratch_words != words) {
+        c->seen_scratch_words = 0;
+        HIP_TRY(hip_alloc(c->d_seen_scratch, (4 * block + 2 * rows) * sizeof(uint32_t)));
+        c->seen_scratch_words = words;
+    }
+    uint32_t *const d_seen = c->d_seen_scratch.get(), *const d_upto = d_seen + block, *const d_cin = d_upto + block, *const d_cout = d_cin + block;
+    uint32_t *const d_total = d_cout + block, *const d_fresh = d_total + rows;
+    const size_t W = (size_t)c->cfg.width, H = (size_t)c->cfg.height, runs = (size_t)(count / run_len);
+    const BundleLayout L = s.layout(W, H);
+    const uint16_t *const id = reinterpret_cast<const uint16_t *>(s.d_fb.get() + L.id) + (size_t)first * W * H;
+    const uint8_t *const cls = s.d_fb.get() + L.cls + (size_t)first * W * H;
+    hipStream_t xs = c->xstream;
+    c->seen_timed = false; c->seen_acc_timed = false;
+    hipError_t e = hipMemsetAsync(d_seen, 0, (size_t)count * words * sizeof(uint32_t), xs);
+    if (e == hipSuccess && carry_in) e = hipMemcpyAsync(d_cin, carry_in, runs * words * sizeof(uint32_t), hipMemcpyHostToDevice, xs);
+    if (e == hipSuccess)
+        e = launch_seen_lines(id, cls, (int)W, (int)H, count, c->d_seg_line.get(), (uint32_t)c->scene->segs.size(), d_seen, (uint32_t)words, xs, c->ev_seen0, c->ev_seen1);
+    if (e == hipSuccess)
+        e = launch_seen_accumulate(d_seen, (uint32_t)words, count, run_len, carry_in ? d_cin : nullptr, d_upto, total ? d_total : nullptr,
+                                   fresh ? d_fresh : nullptr, carry_out ? d_cout : nullptr, xs, c->ev_seen2, c->ev_seen3);
+    if (e == hipSuccess && upto) e = hipMemcpyAsync(upto, d_upto, (size_t)count * words * sizeof(uint32_t), hipMemcpyDeviceToHost, xs);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(total, d_total, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, xs);
+    if (e == hipSuccess && fresh) e = hipMemcpyAsync(fresh, d_fresh, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, xs);
+    if (e == hipSuccess && carry_out) e = hipMemcpyAsync(carry_out, d_cout, runs * words * sizeof(uint32_t), hipMemcpyDeviceToHost, xs);
+    const hipError_t es = hipStreamSynchronize(xs);       // before the caller's rows are read or reused, whatever was queued has run
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_slot_seen_lines: ") + hipGetErrorString(e));
+    c->seen_timed = true; c->seen_acc_timed = true;
+    return DG_OK;
+}
+
+int dg_ctx_seen_kernel_ms(dg_ctx *c, float *lines_ms, float *accumulate_ms) {
+    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
+    if (!c->seen_timed) return set_err(DG_ERR_INVALID, "no dg_seen_lines_device or dg_slot_seen_lines call has launched yet");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (lines_ms) HIP_TRY(hipEventElapsedTime(lines_ms, c->ev_seen0, c->ev_seen1));
+    if (accumulate_ms) { *accumulate_ms = 0.0f; if (c->seen_acc_timed) HIP_TRY(hipEventElapsedTime(accumulate_ms, c->ev_seen2, c->ev_seen3)); }
+    return DG_OK;
+}
+
 int dg_ctx_locate_walks(dg_ctx *c, dg_walk *const *walks, int n_walks) {
     if (!c || n_walks < 0 || (n_walks > 0 && !walks)) return set_err(DG_ERR_INVALID, "null argument");
     if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded");
@@ -2091,7 +2286,7 @@ int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
             HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, tiles ? s.ev_cend : s.ev_raster));
         }
         HIP_TRY(hipEventElapsedTime(&out->total_ms, colour ? s.ev_start : s.ev_tiles, s.ev_raster));
-    } else if (s.front_end != DG_FE_DEPTH && s.front_end != DG_FE_LABELS && (s.front_end != DG_FE_MAP || s.map_built)) {   // (a map submission has a front-end half only when it built the map layer, a depth or label submission none)
+    } else if (s.front_end != DG_FE_DEPTH && s.front_end != DG_FE_LABELS && (!s.map_frames() || s.map_built)) {   // (a map submission has a front-end half only when it built the map layer or uploaded the cover, a depth or label submission none)
         HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
         HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
         HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));

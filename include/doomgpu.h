@@ -548,6 +548,72 @@ int dg_submit_map_views(dg_ctx *ctx, int slot, const dg_view *views, int n);
 /* Synchronous, slot 0: if rgb24_out != NULL copy n*3*W*H bytes to host memory. */
 int dg_render_map_views(dg_ctx *ctx, const dg_view *views, int n, uint8_t *rgb24_out);
 
+/* ---- explored-map frames: the linedefs a session has had on screen, from its label planes ------------------ */
+/* dg_submit_map_views draws every linedef, always.  An agent's map observation shows only the lines the agent has seen so far (vanilla's
+ * ML_MAPPED, ViZDoom's NORMAL automap mode), and "how many lines did this frame reveal" is the standard exploration signal.  Three pieces,
+ * all exact and integer only:
+ *   the seen set of a frame   L = linedef count, words = ceil(L / 32) = dg_seen_words.  A row is uint32 seen[words]: bit l & 31 of word
+ *                             l >> 5 stands for linedef l, the bits at and above L are 0.  Linedef l is seen by a frame when at least one pixel
+ *                             of its label planes has cls == DG_LABEL_WALL and id == k for a seg k of that linedef.  Pixels of any other
+ *                             class are ignored whatever their id, and so is a wall pixel whose id is not below the seg count.  DONTDRAW
+ *                             lines can be seen (they are never drawn).  This is stricter than vanilla's ML_MAPPED, which marks a line
+ *                             when its seg is walked: here a wall wholly covered by sprites (or by nearer walls) is not seen.
+ *   the accumulation          the frames of a call are count / run_len consecutive runs of run_len frames, each run one session in time order:
+ *                               upto[f]  = carry_in[run] | OR of seen[g] for g <= f in the same run     (carry_in == NULL: all zero)
+ *                               total[f] = popcount(upto[f])
+ *                               fresh[f] = popcount(upto[f] & ~prev), prev = the run's previous upto row, carry_in[run] for its first frame
+ *                               carry_out[run] = the run's last upto row
+ *                             count % run_len != 0 or run_len < 1: DG_ERR_INVALID.
+ *   the explored map frame    what dg_render_map_views gives (black, LINEDEFS order, a later line over an earlier one, DONTDRAW skipped, the
+ *                             colours, the arrow, the 40 x 40 minimum, the +-2^24 rule), except that a linedef is drawn only if its bit is
+ *                             set in the frame's mask row.  A mask of all ones gives dg_render_map_views' bytes; where the topmost line at
+ *                             a pixel is unseen, the pixel shows the topmost seen line that covers it.
+ * The masks travel through the host on purpose (64 bytes per frame for a 500-line map): a caller may pass any mask — all ones, a computer-map
+ * pickup — and no slot depends on another slot's stream. */
+/* dg_timing.front_end of an explored-map submission; never a dg_config.front_end. */
+enum { DG_FE_MAP_EXPLORED = 8 };
+/* Host only (no ctx, no GPU), and what the GPU paths are tested against. */
+/* words of one seen row of the scene (>= 0); DG_ERR_INVALID: a NULL scene. */
+int dg_seen_words(const dg_scene *s);
+/* seen[n][words] of n label frames id[n][H][W], cls[n][H][W].  DG_ERR_INVALID: a NULL argument, width or height outside [1, 16384], n < 0;
+ * DG_ERR_CAPACITY: the scene limit of label frames (65 536 segs or map objects). */
+int dg_seen_lines_host(const dg_scene *s, int width, int height, int n, const uint16_t *id, const uint8_t *cls, uint32_t *seen);
+/* The accumulation of n rows of `words` words; carry_in / carry_out hold n / run_len rows; any output may be NULL.  DG_ERR_INVALID: words < 1,
+ * n < 0, a bad run_len, seen == NULL with n > 0. */
+int dg_seen_accumulate_host(int words, int n, int run_len, const uint32_t *carry_in, const uint32_t *seen, uint32_t *upto, uint32_t *total,
+                            uint32_t *fresh, uint32_t *carry_out);
+/* One explored map frame (3*W*H bytes) by the literal rule: the lines of dg_map_lines whose linedef's bit is set in mask_row, drawn in order
+ * (view == NULL: no arrow).  Errors as dg_map_lines; a NULL scene, mask_row or rgb24_out: DG_ERR_INVALID. */
+int dg_explored_map_host(const dg_scene *s, int width, int height, const dg_view *view, const uint32_t *mask_row, uint8_t *rgb24_out);
+/* Device to device: seen_dev[n][words] of the planes id_dev[n][H][W], cls_dev[n][H][W] — planes inside dg_slot_framebuffer of a finished
+ * slot, tensors' data pointers (the planes are the caller's: an id at or beyond the seg count is ignored).  Synchronous, on the ctx's stream
+ * that belongs to no slot (dg_reduce_device's); touches no slot.  id_dev must be 2-byte and seen_dev 4-byte aligned (else DG_ERR_INVALID),
+ * cls_dev sits anywhere.  Needs an uploaded scene (DG_ERR_INVALID without one); the seg -> linedef table is uploaded by the first call
+ * after dg_upload_scene.  Other errors as dg_seen_lines_host. */
+int dg_seen_lines_device(dg_ctx *ctx, int width, int height, int n, const uint16_t *id_dev, const uint8_t *cls_dev, uint32_t *seen_dev);
+/* The seen rows of frames [first, first + count) of a label slot, or of a bundle slot with a label part, accumulated as above: the slot is
+ * made final as by dg_readback_labels, both kernels run over the slot's planes on the no-slot stream (the planes stay as they are), and the
+ * small rows are copied back.  All pointers are host pointers: carry_in / carry_out count / run_len rows, upto count rows, total / fresh count
+ * entries; any output may be NULL.  The scratch rows (max_batch x words) are the ctx's, allocated at first use.  DG_ERR_INVALID: any other
+ * slot content, a bad range, a bad run_len.  count == 0: DG_OK, nothing is done. */
+int dg_slot_seen_lines(dg_ctx *ctx, int slot, int first, int count, int run_len, const uint32_t *carry_in, uint32_t *upto, uint32_t *total,
+                       uint32_t *fresh, uint32_t *carry_out);
+/* GPU time of the last dg_seen_lines_device / dg_slot_seen_lines call's kernels in milliseconds, from events attached to the dispatches:
+ * dg_seen_lines, and dg_seen_accumulate + dg_seen_counts (0 after dg_seen_lines_device).  Either output may be NULL.  DG_ERR_INVALID: a NULL
+ * ctx, no such call that launched yet. */
+int dg_ctx_seen_kernel_ms(dg_ctx *ctx, float *lines_ms, float *accumulate_ms);
+/* Asynchronous, exactly like dg_submit_map_views, with mask = host uint32 [n][words] (copied before the call returns): n explored map frames
+ * into the slot's framebuffer slab.  It is a colour frame: dg_wait, dg_readback(_async), dg_frame_checksums, dg_readback_reduced(_async),
+ * dg_slot_framebuffer work unchanged; dg_slot_timing gives front_end = DG_FE_MAP_EXPLORED, raster_ms = the per-frame kernels (dg_map_explored
+ * and the arrow), setup_ms = the cover upload when this submission made one, else 0.  The cover (4*W*H bytes and the chains of the pixels
+ * that several lines cover) does not depend on the view or the mask: the first explored submission after dg_upload_scene builds it on the
+ * host and uploads it, the ctx keeps it.  dg_replay_slot re-runs the per-frame kernels: the slot keeps the mask rows in device memory
+ * (max_batch x words, allocated by its first such submission).  Errors as dg_submit_map_views; a NULL mask: DG_ERR_INVALID; a scene with more
+ * than 65 536 linedefs: DG_ERR_CAPACITY. */
+int dg_submit_explored_map_views(dg_ctx *ctx, int slot, const dg_view *views, int n, const uint32_t *mask);
+/* Synchronous, slot 0: if rgb24_out != NULL copy n*3*W*H bytes to host memory. */
+int dg_render_explored_map_views(dg_ctx *ctx, const dg_view *views, int n, const uint32_t *mask, uint8_t *rgb24_out);
+
 /* ---- player movement from recorded keys (reference: Game::process_down_keys + update_current_player_height, src/game.rs:314-389) -- */
 /* A walk is a play-through as the reference would move it: a start pose, --turbo, and one key mask per 35 Hz tic.  The state after t tics
  * (t = 0: Game::new) is process_down_keys applied t times, literally in f32 (DESIGN.md section 8e states the order and the operands); the
@@ -592,7 +658,7 @@ const char *dg_last_error(void); /* thread-local message of the last failing cal
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
@@ -602,7 +668,7 @@ typedef struct dg_timing {
     float host_ms;            /* host list generation + binning + packing of that submission (wall clock) */
     uint64_t n_spans, n_frames, covered_pixels;
     uint64_t n_walls, n_planes, list_bytes; /* drawn records / visplanes, bytes of lists copied to HBM */
-    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH, DG_FE_LABELS, DG_FE_BUNDLE): what that submission actually used; with DG_FE_DEVICE setup_ms is
+    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH, DG_FE_LABELS, DG_FE_BUNDLE, DG_FE_MAP_EXPLORED): what that submission actually used; with DG_FE_DEVICE setup_ms is
                                  the column walk (dg_fe_columns, dg_fe_gaps, dg_fe_scan, dg_fe_scatter), n_walls = wall records,
                                  n_planes = sprites, covered_pixels is not tracked (0) */
 } dg_timing;
