@@ -32,6 +32,8 @@ DG_BUNDLE_COLOUR, DG_BUNDLE_DEPTH, DG_BUNDLE_LABELS = 1, 2, 4   # the parts of a
 # dg_label_box as a numpy record: boxes come back as an (n, map objects) array of these
 LABEL_BOX_DTYPE = np.dtype([("pixels", "<u4"), ("x0", "<i2"), ("y0", "<i2"), ("x1", "<i2"), ("y1", "<i2")])
 DG_FE_MAP_EXPLORED = 8  # dg_timing.front_end of an explored-map submission
+DG_FE_MAP_EGO = 9  # dg_timing.front_end of a player-centred map submission
+DG_EGO_ROTATE, DG_EGO_ARROW = 1, 2   # dg_ego_map.flags
 DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
 DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
@@ -105,6 +107,10 @@ class DgTiming(ctypes.Structure):
 
 class DgMapLine(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in "x0 y0 x1 y1".split()] + [("rgb", ctypes.c_uint32)]
+
+
+class DgEgoMap(ctypes.Structure):
+    _fields_ = [("scale", ctypes.c_float), ("flags", ctypes.c_uint32)]
 
 
 class DgBitmapColumn(ctypes.Structure):
@@ -236,6 +242,10 @@ _SIGNATURES = {
     "dg_ctx_seen_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "dg_submit_explored_map_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int, _P]),
     "dg_render_explored_map_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, _P, _P]),
+    "dg_ego_map_lines": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgEgoMap), ctypes.POINTER(DgMapLine), ctypes.c_int]),
+    "dg_ego_map_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgEgoMap), _P, _P]),
+    "dg_submit_ego_map_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P]),
+    "dg_render_ego_map_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, _P]),
     "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
     "dg_walk_free": (None, [_P]),
     "dg_walk_tics": (ctypes.c_int, [_P]),
@@ -443,6 +453,40 @@ def explored_map_host(scene, width: int, height: int, view, mask_row) -> np.ndar
     m = np.ascontiguousarray(mask_row, dtype=np.uint32)
     out = np.empty((height, width, 3), dtype=np.uint8)
     _check(lib().dg_explored_map_host(scene._h, width, height, ctypes.byref(view) if view is not None else None, m.ctypes.data_as(_P), out.ctypes.data_as(_P)))
+    return out
+
+
+def _ego_params(params) -> DgEgoMap:
+    """A DgEgoMap as it is, or one from (scale, flags)."""
+    return params if isinstance(params, DgEgoMap) else DgEgoMap(float(params[0]), int(params[1]))
+
+
+def _mask_ptr(mask):
+    """(keep-alive array, pointer) of mask rows, or (None, None)."""
+    if mask is None:
+        return None, None
+    m = np.ascontiguousarray(mask, dtype=np.uint32)
+    return m, m.ctypes.data_as(_P)
+
+
+def ego_map_lines(scene, width: int, height: int, view, params) -> np.ndarray:
+    """dg_ego_map_lines: the lines of one player-centred map frame in draw order, (n, 5) int64 rows [x0, y0, x1, y1, rgb]; params a
+    DgEgoMap or (scale, flags)."""
+    p = _ego_params(params)
+    n = _check(lib().dg_ego_map_lines(scene._h, width, height, ctypes.byref(view), ctypes.byref(p), None, 0))
+    arr = (DgMapLine * max(1, n))()
+    _check(lib().dg_ego_map_lines(scene._h, width, height, ctypes.byref(view), ctypes.byref(p), arr, n))
+    rows = np.frombuffer(arr, dtype=np.int32, count=5 * n).reshape(n, 5).astype(np.int64)
+    rows[:, 4] &= 0xFFFFFFFF
+    return rows
+
+
+def ego_map_host(scene, width: int, height: int, view, params, mask_row=None) -> np.ndarray:
+    """dg_ego_map_host: one player-centred map frame (H, W, 3) uint8 by the literal rule; mask_row None: every line."""
+    p = _ego_params(params)
+    _keep, mp = _mask_ptr(mask_row)
+    out = np.empty((height, width, 3), dtype=np.uint8)
+    _check(lib().dg_ego_map_host(scene._h, width, height, ctypes.byref(view), ctypes.byref(p), mp, out.ctypes.data_as(_P)))
     return out
 
 
@@ -671,6 +715,22 @@ class Context:
         m = np.ascontiguousarray(mask, dtype=np.uint32)
         out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
         _check(lib().dg_render_explored_map_views(self._h, views, n, m.ctypes.data_as(_P), out.ctypes.data_as(_P)))
+        return out
+
+    def submit_ego_map(self, slot: int, views, params, mask=None, n=None):
+        """dg_submit_ego_map_views: player-centred map frames (params a DgEgoMap or (scale, flags); mask (n, words) uint32 or None: every
+        line), asynchronously."""
+        p = _ego_params(params)
+        _keep, mp = _mask_ptr(mask)
+        _check(lib().dg_submit_ego_map_views(self._h, slot, views, len(views) if n is None else n, ctypes.byref(p), mp))
+
+    def render_ego_map(self, views, params, mask=None) -> np.ndarray:
+        """dg_render_ego_map_views: synchronous through slot 0; returns (n, H, W, 3) uint8."""
+        n = len(views)
+        p = _ego_params(params)
+        _keep, mp = _mask_ptr(mask)
+        out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
+        _check(lib().dg_render_ego_map_views(self._h, views, n, ctypes.byref(p), mp, out.ctypes.data_as(_P)))
         return out
 
     def seen_lines_device(self, width: int, height: int, n_frames: int, id_ptr: int, cls_ptr: int, seen_ptr: int):

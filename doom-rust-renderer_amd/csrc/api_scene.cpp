@@ -3,7 +3,8 @@
 // dg_reduce_host) and the reduced depth and label planes (dg_plane_reduced_size, dg_reduce_planes_host), the depth planes, the label
 // planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host, dg_label_lists_host,
 // dg_bundle_lists_host: one rule, plane_lists_host), a bundle's slab layout (dg_bundle_layout), and the explored-map frames' host rules
-// (dg_seen_words, dg_seen_lines_host, dg_seen_accumulate_host, dg_explored_map_host).  Everything that takes a dg_ctx: context.cpp.
+// (dg_seen_words, dg_seen_lines_host, dg_seen_accumulate_host, dg_explored_map_host) and the player-centred map frames' (dg_ego_map_lines,
+// dg_ego_map_host).  Everything that takes a dg_ctx: context.cpp.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -11,6 +12,7 @@
 
 #include "api_common.hpp"
 #include "binner.hpp"
+#include "ego_host.hpp"
 #include "explored_cover.hpp"
 #include "frontend.hpp"
 #include "plane_core.h"
@@ -460,6 +462,49 @@ int dg_explored_map_host(const dg_scene *s, int width, int height, const dg_view
     for (size_t k = 0; k < lines.size(); k++) {
         if (k < ids.size() && !((mask_row[ids[k] >> 5] >> (ids[k] & 31u)) & 1u)) continue;       // (k >= ids.size(): the arrow)
         const dg_map_line &l = lines[k];
+        const MapSeg sg = map_seg_make(l.x0, l.y0, l.x1, l.y1, l.rgb, width, height);
+        for (int32_t i = 0; i < sg.count; i++) {
+            int32_t x, y;
+            map_seg_point(sg, (int64_t)sg.first + i, x, y);
+            if ((uint32_t)x >= (uint32_t)width || (uint32_t)y >= (uint32_t)height) continue;
+            uint8_t *const px = rgb24_out + 3 * ((size_t)y * (size_t)width + (size_t)x);
+            px[0] = (uint8_t)l.rgb; px[1] = (uint8_t)(l.rgb >> 8); px[2] = (uint8_t)(l.rgb >> 16);
+        }
+    }
+    return DG_OK;
+}
+
+// What dg_ego_map_lines and dg_ego_map_host do alike: the contract's checks, then the frame's lines (ego_host.hpp).
+static int ego_lines_checked(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const uint32_t *mask_row,
+                             std::vector<dg_map_line> &lines) {
+    if (!s || !view || !params) return set_err(DG_ERR_INVALID, "null argument");
+    std::string err;
+    int rc = ego_check_call(*s->sc, width, height, params, err);
+    if (rc) return set_err(rc, err);
+    dg_view v = *view;
+    fill_view_trig(v);
+    rc = ego_check_view(v, err);
+    if (!rc) rc = ego_frame_lines(*s->sc, width, height, v, *params, mask_row, lines, err);
+    return rc ? set_err(rc, err) : DG_OK;
+}
+
+int dg_ego_map_lines(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, dg_map_line *out, int cap) {
+    static thread_local std::vector<dg_map_line> lines;
+    const int rc = ego_lines_checked(s, width, height, view, params, nullptr, lines);
+    if (rc) return rc;
+    if (out && cap >= 0 && (size_t)cap >= lines.size() && !lines.empty()) std::memcpy(out, lines.data(), lines.size() * sizeof(dg_map_line));
+    return (int)lines.size();
+}
+
+// The literal rule: black, the surviving lines in draw order, every point through map_seg_point.
+int dg_ego_map_host(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const uint32_t *mask_row,
+                    uint8_t *rgb24_out) {
+    if (!rgb24_out) return set_err(DG_ERR_INVALID, "null argument");
+    std::vector<dg_map_line> lines;
+    const int rc = ego_lines_checked(s, width, height, view, params, mask_row, lines);
+    if (rc) return rc;
+    std::memset(rgb24_out, 0, (size_t)3 * (size_t)width * (size_t)height);
+    for (const dg_map_line &l : lines) {
         const MapSeg sg = map_seg_make(l.x0, l.y0, l.x1, l.y1, l.rgb, width, height);
         for (int32_t i = 0; i < sg.count; i++) {
             int32_t x, y;

@@ -45,6 +45,8 @@
 #include "frontend.hpp"
 #include "hip_mem.hpp"
 #include "kernels.hpp"
+#include "ego_host.hpp"
+#include "ego_kernels.hpp"
 #include "explored_cover.hpp"
 #include "explored_kernels.hpp"
 #include "map_kernels.hpp"
@@ -110,11 +112,15 @@ struct Slot {
     DevPtr<uint32_t> d_owners;
     DevPtr<LabelRawBox> d_boxes;
     size_t box_mobjs = 0;
-    // explored-map frames: the mask rows of the last such submission (staging + HBM, max_batch x mask_words), kept for dg_replay_slot — none
-    // of it exists before the slot's first explored submission; dg_upload_scene drops it (the row length is the scene's)
+    // explored-map and player-centred map frames: the mask rows of the last such submission (staging + HBM, max_batch x mask_words), kept
+    // for dg_replay_slot — none of it exists before the slot's first submission with a mask; dg_upload_scene drops it (the row length is the scene's)
     PinnedPtr<uint32_t> h_masks;
     DevPtr<uint32_t> d_masks;
     size_t mask_words = 0;
+    // player-centred map frames: what the last such submission's kernel takes besides the device copies (d_lists: the arrow lines, then
+    // the views; d_masks), kept for dg_replay_slot
+    dg_ego_map ego{};
+    bool ego_masked = false;
     // last submission
     RasterParams P{};
     uint32_t max_spans = 0;
@@ -147,7 +153,7 @@ struct Slot {
     LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
     MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
     // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
-    // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP (2-D map frames: arrow lines at the start of d_lists) or
+    // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP / DG_FE_MAP_EXPLORED / DG_FE_MAP_EGO (2-D map frames: arrow lines at the start of d_lists) or
     // DG_FE_DEPTH (host lists walked by dg_depth_tiles: the framebuffer slab holds the two planes, not RGB24) or DG_FE_LABELS (host lists
     // walked by dg_label_tiles: the slab holds the id and class planes) or DG_FE_BUNDLE (host lists run through the colour kernels and / or
     // dg_bundle_tiles: the slab holds the parts bundle_what names, laid out by bundle_layout)
@@ -160,7 +166,7 @@ struct Slot {
     }
     bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
     bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
-    bool map_frames() const { return front_end == DG_FE_MAP || front_end == DG_FE_MAP_EXPLORED; }   // arrow lines at the start of d_lists
+    bool map_frames() const { return front_end == DG_FE_MAP || front_end == DG_FE_MAP_EXPLORED || front_end == DG_FE_MAP_EGO; }   // arrow lines at the start of d_lists
     bool holds_bundle() const { return front_end == DG_FE_BUNDLE && phase != Phase::Empty; }
     // Which parts the framebuffer slab holds (BUNDLE_*: RGB24 colour frames, the two depth planes, the two label planes) ...
     uint32_t parts() const {
@@ -328,6 +334,11 @@ struct dg_ctx {
     bool seen_timed = false, seen_acc_timed = false;
     DevPtr<uint32_t> d_cover, d_chains;
     bool cover_ok = false;
+    // player-centred map frames: the uploaded scene's line table (ego_line_table: EgoLine per linedef, then a word per linedef), uploaded
+    // by the first such submission after dg_upload_scene
+    DevPtr<uint8_t> d_ego_table;
+    uint32_t ego_lines = 0;
+    bool ego_table_ok = false;
 };
 
 namespace {
@@ -877,6 +888,26 @@ int upload_explored_cover(dg_ctx *c, Slot &s) {
     return DG_OK;
 }
 
+// The player-centred map frames' line table of the uploaded scene, copied on the kernel stream between the slot's ev_start / ev_setup.
+int upload_ego_table(dg_ctx *c, Slot &s) {
+    std::vector<EgoLine> lines;
+    std::vector<uint32_t> words;
+    ego_line_table(*c->scene, lines, words);
+    const size_t L = lines.size();
+    HIP_TRY(hip_alloc(c->d_ego_table, L * (sizeof(EgoLine) + sizeof(uint32_t))));
+    HIP_TRY(hipEventRecord(s.ev_start, c->kstream));
+    HIP_TRY(hipMemcpyAsync(c->d_ego_table.get(), lines.data(), L * sizeof(EgoLine), hipMemcpyHostToDevice, c->kstream));
+    HIP_TRY(hipMemcpyAsync(c->d_ego_table.get() + L * sizeof(EgoLine), words.data(), L * sizeof(uint32_t), hipMemcpyHostToDevice, c->kstream));
+    HIP_TRY(hipEventRecord(s.ev_setup, c->kstream));
+    HIP_TRY(hipStreamSynchronize(c->kstream));           // (before the host copy goes)
+    c->ego_lines = (uint32_t)L;
+    c->ego_table_ok = true;
+    return DG_OK;
+}
+
+// Where a player-centred submission of n frames keeps its arrow lines and its views in the slot's list slab.
+size_t ego_views_at(int n) { return (size_t)n * 3 * sizeof(MapSeg); }
+
 constexpr size_t kOverlapMaxPixels = 500000;          // frames up to this size overlap their raster launch with the next batch's front end (dg_create)
 
 // A submission's last step: its kernels are enqueued.  harvested: DG_FE_AUTO has nothing to read from it.
@@ -906,7 +937,7 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     const bool fe_mode = s.column_walk();
     HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
     HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
-    const bool map = s.front_end == DG_FE_MAP, explored = s.front_end == DG_FE_MAP_EXPLORED;
+    const bool map = s.front_end == DG_FE_MAP, explored = s.front_end == DG_FE_MAP_EXPLORED, ego = s.front_end == DG_FE_MAP_EGO;
     if (map) {                                            // 2-D map frames: the layer (once per scene upload), then copy + arrow per frame
         s.map_built = false;
         if (!c->map_layer_ok) {
@@ -918,6 +949,13 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
         s.map_built = false;
         if (!c->cover_ok) {
             const int rc = upload_explored_cover(c, s);
+            if (rc) return rc;
+            s.map_built = true;
+        }
+    } else if (ego) {                                     // player-centred map frames: the line table (once per scene upload), then one kernel
+        s.map_built = false;
+        if (!c->ego_table_ok) {
+            const int rc = upload_ego_table(c, s);
             if (rc) return rc;
             s.map_built = true;
         }
@@ -946,6 +984,19 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     } else if (explored) {
         HIP_TRY(launch_explored_frames(c->d_cover.get(), c->d_chains.get(), s.d_masks.get(), (uint32_t)s.mask_words, reinterpret_cast<const MapSeg *>(s.d_lists.get()),
                                        s.n_frames, s.d_fb.get(), c->cfg.width, c->cfg.height, ks, s.ev_rstart, s.ev_raster));
+    } else if (ego) {
+        EgoParams E{};
+        E.lines = reinterpret_cast<const EgoLine *>(c->d_ego_table.get());
+        E.words = reinterpret_cast<const uint32_t *>(c->d_ego_table.get() + (size_t)c->ego_lines * sizeof(EgoLine));
+        E.n_lines = c->ego_lines;
+        E.views = reinterpret_cast<const EgoView *>(s.d_lists.get() + ego_views_at(s.n_frames));
+        E.arrow = (s.ego.flags & EGO_ARROW) ? reinterpret_cast<const MapSeg *>(s.d_lists.get()) : nullptr;
+        E.masks = s.ego_masked ? s.d_masks.get() : nullptr;
+        E.mask_words = (uint32_t)s.mask_words;
+        E.scale = s.ego.scale; E.rotate = s.ego.flags & EGO_ROTATE;
+        E.W = c->cfg.width; E.H = c->cfg.height;
+        E.fb = s.d_fb.get(); E.n_frames = s.n_frames;
+        HIP_TRY(launch_ego_tiles(E, ks, s.ev_rstart, s.ev_raster));
     } else if (c->raster_overlap && fe_mode) {                   // the front end of the next batch may start while this launch runs (the column scratch is the front end's alone)
         HIP_TRY(hipStreamWaitEvent(c->rstream, s.ev_setup, 0));
         HIP_TRY(launch_raster(s.P, c->rstream, s.ev_rstart, s.ev_raster));
@@ -1508,6 +1559,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     c->seg_line_ok = false;             // dg_seen_lines_device / dg_slot_seen_lines are synchronous: nothing of them is in flight
     c->d_seen_scratch.reset(); c->seen_scratch_words = 0;
     c->cover_ok = false;                // the explored map's cover belongs to the old scene
+    c->ego_table_ok = false; c->d_ego_table.reset(); c->ego_lines = 0;     // ... and the player-centred map's line table
     c->d_walk_tables.reset();           // dg_ctx_locate_walks is synchronous: nothing of it is in flight
     c->map_layer_ok = false;            // the map view's linedef layer belongs to the old scene   // (a new scene may reuse the old one's address and revision)
     uint32_t pal[256];
@@ -2053,6 +2105,16 @@ int dg_render_map_views(dg_ctx *c, const dg_view *views, int n, uint8_t *out) {
     return read_or_wait(c, 0, dg_submit_map_views(c, 0, views, n), n, out);
 }
 
+// The slot's mask rows (max_batch x words), there from its first submission with a mask after dg_upload_scene on.
+static int ensure_slot_masks(dg_ctx *c, Slot &s, size_t words) {
+    if (s.d_masks) return DG_OK;
+    HIP_TRY(slot_sync(s));                                // (the slot is ours: whatever replayed the old rows has finished)
+    HIP_TRY(hip_alloc(s.h_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
+    HIP_TRY(hip_alloc(s.d_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
+    s.mask_words = words;
+    return DG_OK;
+}
+
 int dg_submit_explored_map_views(dg_ctx *c, int slot, const dg_view *views, int n, const uint32_t *mask) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
@@ -2070,12 +2132,8 @@ int dg_submit_explored_map_views(dg_ctx *c, int slot, const dg_view *views, int 
     rc = take_slot(c, s);
     if (rc) return rc;
     if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
-    if (!s.d_masks) {                                     // (the slot is ours: whatever replayed the old rows has finished)
-        HIP_TRY(slot_sync(s));
-        HIP_TRY(hip_alloc(s.h_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
-        HIP_TRY(hip_alloc(s.d_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
-        s.mask_words = words;
-    }
+    rc = ensure_slot_masks(c, s, words);
+    if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
     std::string err;
@@ -2097,6 +2155,52 @@ int dg_submit_explored_map_views(dg_ctx *c, int slot, const dg_view *views, int 
 
 int dg_render_explored_map_views(dg_ctx *c, const dg_view *views, int n, const uint32_t *mask, uint8_t *out) {
     return read_or_wait(c, 0, dg_submit_explored_map_views(c, 0, views, n, mask), n, out);
+}
+
+int dg_submit_ego_map_views(dg_ctx *c, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!views || !params) return set_err(DG_ERR_INVALID, "null views or params");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    const int W = c->cfg.width, H = c->cfg.height;
+    std::string err;
+    rc = ego_check_call(*c->scene, W, H, params, err);
+    if (rc) return set_err(rc, err);
+    if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
+    const bool arrow = (params->flags & EGO_ARROW) != 0;
+    const size_t words = seen_words((uint32_t)c->scene->linedefs.size());
+    const size_t bytes = ego_views_at(n) + (size_t)n * sizeof(EgoView), mask_bytes = mask ? (size_t)n * words * sizeof(uint32_t) : 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    Slot &s = c->slots[(size_t)slot];
+    rc = take_slot(c, s);
+    if (rc) return rc;
+    if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
+    if (mask && (rc = ensure_slot_masks(c, s, words))) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    // per view: the contract's checks, the arrow's three lines clipped to the frame (the host owns the libm trig) and what the points depend on
+    MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
+    EgoView *hv = reinterpret_cast<EgoView *>(s.h_lists.get() + ego_views_at(n));
+    for (int i = 0; i < n; i++) {
+        dg_view v = views[i];
+        fill_view_trig(v);
+        rc = ego_check_view(v, err);
+        dg_map_line l[3] = {};
+        if (!rc && arrow) rc = ego_arrow_lines(W, H, v, *params, l, err);
+        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
+        for (int k = 0; k < 3; k++) h[3 * i + k] = map_seg_make(l[k].x0, l[k].y0, l[k].x1, l[k].y1, l[k].rgb, W, H);
+        hv[i] = ego_view(v);
+    }
+    if (mask) std::memcpy(s.h_masks.get(), mask, mask_bytes);
+    s.ego = *params; s.ego_masked = mask != nullptr;
+    s.describe(DG_FE_MAP_EGO, n, bytes + mask_bytes, 0, 0);
+    s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream));
+    if (mask) HIP_TRY(hipMemcpyAsync(s.d_masks.get(), s.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream));
+    return enqueue_kernels(c, s);
+}
+
+int dg_render_ego_map_views(dg_ctx *c, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, uint8_t *out) {
+    return read_or_wait(c, 0, dg_submit_ego_map_views(c, 0, views, n, params, mask), n, out);
 }
 
 // What dg_seen_lines_device and dg_slot_seen_lines need of the ctx: the no-slot stream, their events, the uploaded scene's seg -> linedef table.

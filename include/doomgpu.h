@@ -614,6 +614,54 @@ int dg_submit_explored_map_views(dg_ctx *ctx, int slot, const dg_view *views, in
 /* Synchronous, slot 0: if rgb24_out != NULL copy n*3*W*H bytes to host memory. */
 int dg_render_explored_map_views(dg_ctx *ctx, const dg_view *views, int n, const uint32_t *mask, uint8_t *rgb24_out);
 
+/* ---- player-centred map frames: the map around the player at a fixed scale, rasterised per frame ------------ */
+/* dg_submit_map_views fits the whole level to the frame.  An agent's map observation is the map centred on the player at a fixed number
+ * of pixels per map unit, usually heading up (ViZDoom's am_followplayer + am_rotate + am_scale, the egocentric top-down map): every
+ * line's position then depends on the view, and the lines are rasterised per frame.  Everything is exact.
+ *   the point of a map vertex (vx, vy)   every operation in f32 in this order, no contraction:
+ *                             dx = vx - view.x, dy = vy - view.y
+ *                             DG_EGO_ROTATE:  r = dx*sin_a - dy*cos_a,  f = dx*cos_a + dy*sin_a     without it:  r = dx, f = dy
+ *                             X = f32_as_i32(floorf((float)(W/2) + r*scale)),  Y = f32_as_i32(floorf((float)(H/2) - f*scale))
+ *                             (W/2, H/2: integer divisions; floorf, so that the column and row left of 0 do not fold onto 0).  The player
+ *                             sits at pixel (W/2, H/2).  view.floor_height and view.timestamp are not used; trig_valid = 0 is filled as
+ *                             everywhere else.
+ *   the frame                 black; the linedefs in LINEDEFS order, DONTDRAW (flags & 128) skipped, a later line over an earlier one, yellow
+ *                             when TWOSIDED else red (the map view's colours), each from the point of v1 to the point of v2 by the SDL line
+ *                             rule of the map view, points outside the frame dropped.  With a mask row (uint32[dg_seen_words], the layout of
+ *                             the explored-map frames) a linedef is drawn only if its bit is set; no mask: every line.
+ *   the arrow                 DG_EGO_ARROW: the three lines P->E, R->E, L->E last, in yellow.  Their four map-space points are the map view's
+ *                             (Vertex::rotate literally, the host's cosf / sinf for the two head angles) with the lengths
+ *                             len = ((float)W / 16.0f) / scale and alen = ((float)W / 32.0f) / scale, then through the point rule.  The libm
+ *                             caveat of the map view applies to the arrow and to nothing else.
+ * In contract, checked on the host per call and per view (anything else: DG_ERR_INVALID, the frame index in the message): W, H in
+ * [16, 16384]; scale finite and in [2^-10, 64]; no unknown flag bits; view.x, view.y finite with |x|, |y| <= 65536; cos_a, sin_a finite
+ * with |cos_a|, |sin_a| <= 1.  Consequence: WAD vertices are i16, so |r|, |f| <= 2 * 98304 and every transformed coordinate lies within
+ * +-2^24 — the line rule's precondition holds for every line of every in-contract view, and no per-line error can arise on the device.
+ * A scene with more than 65 535 linedefs: DG_ERR_CAPACITY; one with no linedefs: DG_ERR_INVALID. */
+typedef struct dg_ego_map { float scale; uint32_t flags; } dg_ego_map;   /* scale: pixels per map unit */
+enum { DG_EGO_ROTATE = 1u,   /* heading up; without it north up, as the reference's map */
+       DG_EGO_ARROW  = 2u }; /* the player arrow on top */
+/* dg_timing.front_end of a player-centred map submission; never a dg_config.front_end. */
+enum { DG_FE_MAP_EGO = 9 };
+/* The lines of one frame in draw order: the drawn linedefs, then the arrow's three if the flags ask for them.  Returns the count; sizing
+ * and overflow as dg_map_lines (`out` is written only when cap holds them all).  A NULL scene, view or params: DG_ERR_INVALID. */
+int dg_ego_map_lines(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, dg_map_line *out, int cap);
+/* One frame (3*W*H bytes) by the literal rule: the lines above whose linedef's bit is set in mask_row (NULL: all), drawn in order point by
+ * point.  A NULL scene, view, params or rgb24_out: DG_ERR_INVALID. */
+int dg_ego_map_host(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const uint32_t *mask_row,
+                    uint8_t *rgb24_out);
+/* Asynchronous, exactly like dg_submit_map_views: n frames at the ctx's size into the slot's framebuffer slab, one dg_ego_map for the whole
+ * submission, mask = NULL (every line) or host uint32 [n][dg_seen_words] (copied before the call returns).  It is a colour frame: dg_wait,
+ * dg_readback(_async), dg_frame_checksums, dg_readback_reduced(_async), dg_slot_framebuffer work unchanged; dg_slot_timing gives
+ * front_end = DG_FE_MAP_EGO, raster_ms = the per-frame kernel (dg_ego_tiles), setup_ms = the line-table upload when this submission made
+ * one, else 0.  The table (20 bytes per linedef) is uploaded by the first such submission after dg_upload_scene; nothing is allocated at
+ * dg_create.  dg_replay_slot re-runs the kernel: the slot keeps the views, the arrow lines and the mask rows in device memory (the mask
+ * buffers of the explored-map frames).  These submissions never feed DG_FE_AUTO's measurements or the fallback counters.  Errors as
+ * above, and as dg_submit_map_views for the slot, the batch size and the scene. */
+int dg_submit_ego_map_views(dg_ctx *ctx, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask);
+/* Synchronous, slot 0: if rgb24_out != NULL copy n*3*W*H bytes to host memory. */
+int dg_render_ego_map_views(dg_ctx *ctx, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, uint8_t *rgb24_out);
+
 /* ---- player movement from recorded keys (reference: Game::process_down_keys + update_current_player_height, src/game.rs:314-389) -- */
 /* A walk is a play-through as the reference would move it: a start pose, --turbo, and one key mask per 35 Hz tic.  The state after t tics
  * (t = 0: Game::new) is process_down_keys applied t times, literally in f32 (DESIGN.md section 8e states the order and the operands); the
@@ -658,7 +706,7 @@ const char *dg_last_error(void); /* thread-local message of the last failing cal
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
@@ -668,7 +716,7 @@ typedef struct dg_timing {
     float host_ms;            /* host list generation + binning + packing of that submission (wall clock) */
     uint64_t n_spans, n_frames, covered_pixels;
     uint64_t n_walls, n_planes, list_bytes; /* drawn records / visplanes, bytes of lists copied to HBM */
-    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH, DG_FE_LABELS, DG_FE_BUNDLE, DG_FE_MAP_EXPLORED): what that submission actually used; with DG_FE_DEVICE setup_ms is
+    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH, DG_FE_LABELS, DG_FE_BUNDLE, DG_FE_MAP_EXPLORED, DG_FE_MAP_EGO): what that submission actually used; with DG_FE_DEVICE setup_ms is
                                  the column walk (dg_fe_columns, dg_fe_gaps, dg_fe_scan, dg_fe_scatter), n_walls = wall records,
                                  n_planes = sprites, covered_pixels is not tracked (0) */
 } dg_timing;
