@@ -458,19 +458,8 @@ int dg_explored_map_host(const dg_scene *s, int width, int height, const dg_view
     const int rc = map_frame_lines(*s->sc, width, height, view ? &v : nullptr, lines, err);
     if (rc) return set_err(rc, err);
     const std::vector<uint32_t> ids = explored_line_ids(*s->sc);
-    std::memset(rgb24_out, 0, (size_t)3 * (size_t)width * (size_t)height);
-    for (size_t k = 0; k < lines.size(); k++) {
-        if (k < ids.size() && !((mask_row[ids[k] >> 5] >> (ids[k] & 31u)) & 1u)) continue;       // (k >= ids.size(): the arrow)
-        const dg_map_line &l = lines[k];
-        const MapSeg sg = map_seg_make(l.x0, l.y0, l.x1, l.y1, l.rgb, width, height);
-        for (int32_t i = 0; i < sg.count; i++) {
-            int32_t x, y;
-            map_seg_point(sg, (int64_t)sg.first + i, x, y);
-            if ((uint32_t)x >= (uint32_t)width || (uint32_t)y >= (uint32_t)height) continue;
-            uint8_t *const px = rgb24_out + 3 * ((size_t)y * (size_t)width + (size_t)x);
-            px[0] = (uint8_t)l.rgb; px[1] = (uint8_t)(l.rgb >> 8); px[2] = (uint8_t)(l.rgb >> 16);
-        }
-    }
+    map_draw_lines_host(lines.data(), lines.size(), width, height, rgb24_out,
+                        [&](size_t k) { return k >= ids.size() || ((mask_row[ids[k] >> 5] >> (ids[k] & 31u)) & 1u); });       // (k >= ids.size(): the arrow)
     return DG_OK;
 }
 
@@ -503,17 +492,7 @@ int dg_ego_map_host(const dg_scene *s, int width, int height, const dg_view *vie
     std::vector<dg_map_line> lines;
     const int rc = ego_lines_checked(s, width, height, view, params, mask_row, lines);
     if (rc) return rc;
-    std::memset(rgb24_out, 0, (size_t)3 * (size_t)width * (size_t)height);
-    for (const dg_map_line &l : lines) {
-        const MapSeg sg = map_seg_make(l.x0, l.y0, l.x1, l.y1, l.rgb, width, height);
-        for (int32_t i = 0; i < sg.count; i++) {
-            int32_t x, y;
-            map_seg_point(sg, (int64_t)sg.first + i, x, y);
-            if ((uint32_t)x >= (uint32_t)width || (uint32_t)y >= (uint32_t)height) continue;
-            uint8_t *const px = rgb24_out + 3 * ((size_t)y * (size_t)width + (size_t)x);
-            px[0] = (uint8_t)l.rgb; px[1] = (uint8_t)(l.rgb >> 8); px[2] = (uint8_t)(l.rgb >> 16);
-        }
-    }
+    map_draw_lines_host(lines.data(), lines.size(), width, height, rgb24_out, [](size_t) { return true; });
     return DG_OK;
 }
 

@@ -106,21 +106,26 @@ struct Slot {
     DevPtr<DevRSpan> d_rspans;
     DevPtr<uint8_t> d_fb;
     size_t lists_cap = 0;
-    // label frames: owner tags parallel to the wall records of d_lists (staging + HBM, wall_cap_per_batch entries) and the box table
-    // max_batch x box_mobjs — none of it exists before the slot's first label submission; dg_upload_scene drops the box table
+    // label frames: owner tags parallel to the wall records of d_lists (staging + HBM, wall_cap_per_batch entries) — they do not exist
+    // before the slot's first label submission
     PinnedPtr<uint32_t> h_owners;
     DevPtr<uint32_t> d_owners;
-    DevPtr<LabelRawBox> d_boxes;
-    size_t box_mobjs = 0;
-    // explored-map and player-centred map frames: the mask rows of the last such submission (staging + HBM, max_batch x mask_words), kept
-    // for dg_replay_slot — none of it exists before the slot's first submission with a mask; dg_upload_scene drops it (the row length is the scene's)
-    PinnedPtr<uint32_t> h_masks;
-    DevPtr<uint32_t> d_masks;
-    size_t mask_words = 0;
-    // player-centred map frames: what the last such submission's kernel takes besides the device copies (d_lists: the arrow lines, then
-    // the views; d_masks), kept for dg_replay_slot
-    dg_ego_map ego{};
-    bool ego_masked = false;
+    // The buffers whose size is the uploaded scene's: dg_upload_scene drops them, the first submission that needs one allocates it.
+    struct PerScene {
+        DevPtr<LabelRawBox> d_boxes;     // label frames: the box table max_batch x box_mobjs
+        size_t box_mobjs = 0;
+        PinnedPtr<uint32_t> h_masks;     // map frames: the mask rows of the last submission that had any (staging + HBM, max_batch x
+        DevPtr<uint32_t> d_masks;        // mask_words), kept for dg_replay_slot
+        size_t mask_words = 0;
+        void drop() { *this = PerScene{}; }
+    } per_scene;
+    // What a map submission (front_end DG_FE_MAP*) leaves for its kernels and for dg_replay_slot besides d_lists (the arrow lines, then a
+    // player-centred submission's views) and the mask rows above: written as a whole by every such submission.
+    struct MapState {
+        dg_ego_map ego{};                // DG_FE_MAP_EGO: scale and flags
+        bool masked = false;             // the kernel reads the slot's mask rows (a player-centred submission may come without)
+        bool built = false;              // the enqueue built the kind's per-scene table: ev_start .. ev_setup time that
+    } map;
     // last submission
     RasterParams P{};
     uint32_t max_spans = 0;
@@ -167,6 +172,9 @@ struct Slot {
     bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
     bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
     bool map_frames() const { return front_end == DG_FE_MAP || front_end == DG_FE_MAP_EXPLORED || front_end == DG_FE_MAP_EGO; }   // arrow lines at the start of d_lists
+    // This submission has a timed front half (ev_start .. ev_setup): a depth or label submission has none, a map submission only when it
+    // built its kind's per-scene table.
+    bool timed_front_half() const { return front_end != DG_FE_DEPTH && front_end != DG_FE_LABELS && (!map_frames() || map.built); }
     bool holds_bundle() const { return front_end == DG_FE_BUNDLE && phase != Phase::Empty; }
     // Which parts the framebuffer slab holds (BUNDLE_*: RGB24 colour frames, the two depth planes, the two label planes) ...
     uint32_t parts() const {
@@ -183,7 +191,6 @@ struct Slot {
         return BundleLayout{0, 0, 2 * px, 0, 2 * px, 3 * px};
     }
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
-    bool map_built = false;       // a map submission whose enqueue built the ctx's map layer (ev_start .. ev_setup time that)
     std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
     // ... and a private copy of their game-state snapshots (the caller's arrays need not outlive the call)
     std::vector<dg_view_state> states;
@@ -306,15 +313,21 @@ struct dg_ctx {
     DevPtr<uint32_t> d_fe_cnt;
     DevPtr<FeU4> d_fe_cspans;
     DevPtr<FeColRec> d_fe_recs;
-    // 2-D map view: every drawn linedef of the uploaded scene, RGB24, built by the first map submission after dg_upload_scene
-    DevPtr<uint8_t> d_map_layer;
-    bool map_layer_ok = false;
-    // dg_ctx_locate_walks: the uploaded scene's node and leaf tables (walk_core.h), uploaded by the first call after dg_upload_scene, and
-    // a stream of its own, created by the first call of all — the slots' streams and the kernel stream are not touched
-    DevPtr<uint8_t> d_walk_tables;
-    const WalkNode *d_walk_nodes = nullptr;
-    const WalkLeaf *d_walk_leaves = nullptr;
-    hipStream_t wstream = nullptr;
+    // Device tables derived from the uploaded scene.  Each is made by the first call that needs it after dg_upload_scene, which drops
+    // them all: a table is valid exactly when its pointer is set (each is assigned only once it is complete).
+    struct PerScene {
+        DevPtr<uint8_t> map_layer;          // 2-D map view: every drawn linedef at the ctx's frame size, RGB24 (build_map_layer)
+        DevPtr<uint32_t> cover, chains;     // explored-map frames: explored_core.h's cover and its chains (upload_explored_cover)
+        DevPtr<uint8_t> ego_table;          // player-centred map frames: EgoLine per linedef, then a word per linedef (upload_ego_table)
+        uint32_t ego_lines = 0;
+        DevPtr<uint32_t> seg_line;          // dg_seen_lines_device / dg_slot_seen_lines: seg -> linedef (ensure_seen)
+        DevPtr<uint32_t> seen_scratch;      // dg_slot_seen_lines: its scratch rows, sized by max_batch and the scene's row length
+        DevPtr<uint8_t> walk_tables;        // dg_ctx_locate_walks: the node and leaf tables (walk_core.h)
+        const WalkNode *walk_nodes = nullptr;
+        const WalkLeaf *walk_leaves = nullptr;
+        void drop() { *this = PerScene{}; }
+    } per_scene;
+    hipStream_t wstream = nullptr;      // dg_ctx_locate_walks: a stream of its own, created by the first call — the slots' streams and the kernel stream are not touched
     // dg_reduce_device: likewise a stream of its own and the events attached to its last call's kernel, created by the first call
     hipStream_t xstream = nullptr;
     hipEvent_t ev_reduce0 = nullptr, ev_reduce1 = nullptr;
@@ -322,23 +335,9 @@ struct dg_ctx {
     // dg_reduce_planes_device: the same stream, events of its own
     hipEvent_t ev_preduce0 = nullptr, ev_preduce1 = nullptr;
     bool plane_reduce_timed = false;
-    // explored-map frames.  dg_seen_lines_device / dg_slot_seen_lines: the uploaded scene's seg -> linedef table (uploaded by the first call
-    // after dg_upload_scene), the scratch rows of dg_slot_seen_lines (allocated at first use, sized by max_batch and the scene's row
-    // length) and the events of the last call's kernels, all on xstream.  dg_submit_explored_map_views: the cover and its chains
-    // (explored_core.h), built by the first such submission after dg_upload_scene.
-    DevPtr<uint32_t> d_seg_line;
-    bool seg_line_ok = false;
-    DevPtr<uint32_t> d_seen_scratch;
-    size_t seen_scratch_words = 0;      // the row length the scratch was laid out for (0: none)
+    // dg_seen_lines_device / dg_slot_seen_lines: the events of the last call's kernels, on xstream
     hipEvent_t ev_seen0 = nullptr, ev_seen1 = nullptr, ev_seen2 = nullptr, ev_seen3 = nullptr;
     bool seen_timed = false, seen_acc_timed = false;
-    DevPtr<uint32_t> d_cover, d_chains;
-    bool cover_ok = false;
-    // player-centred map frames: the uploaded scene's line table (ego_line_table: EgoLine per linedef, then a word per linedef), uploaded
-    // by the first such submission after dg_upload_scene
-    DevPtr<uint8_t> d_ego_table;
-    uint32_t ego_lines = 0;
-    bool ego_table_ok = false;
 };
 
 namespace {
@@ -853,10 +852,10 @@ int build_map_layer(dg_ctx *c, Slot &s) {
     }
     if (total >= (1ull << 31)) return set_err(DG_ERR_CAPACITY, "map layer: too many line steps");
     base[n] = (uint32_t)total;
-    if (!c->d_map_layer) HIP_TRY(hip_alloc(c->d_map_layer, (size_t)3 * (size_t)W * (size_t)H));
+    DevPtr<uint8_t> layer, tmp;
+    HIP_TRY(hip_alloc(layer, (size_t)3 * (size_t)W * (size_t)H));
     SlabCursor cur;
     const size_t off_owner = cur.take((size_t)W * (size_t)H * 4), off_segs = cur.take(segs.size() * sizeof(MapSeg)), off_base = cur.take(base.size() * 4);
-    DevPtr<uint8_t> tmp;
     HIP_TRY(hip_alloc(tmp, cur.end()));
     uint32_t *owner = reinterpret_cast<uint32_t *>(tmp.get() + off_owner);
     MapSeg *d_segs = reinterpret_cast<MapSeg *>(tmp.get() + off_segs);
@@ -864,48 +863,65 @@ int build_map_layer(dg_ctx *c, Slot &s) {
     HIP_TRY(hipMemcpy(d_segs, segs.data(), segs.size() * sizeof(MapSeg), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_base, base.data(), base.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(owner, 0, (size_t)W * (size_t)H * 4, c->kstream));
-    HIP_TRY(launch_map_layer(d_segs, d_base, (uint32_t)n, (uint32_t)total, owner, c->d_map_layer.get(), W, H, c->kstream, s.ev_start, s.ev_setup));
+    HIP_TRY(launch_map_layer(d_segs, d_base, (uint32_t)n, (uint32_t)total, owner, layer.get(), W, H, c->kstream, s.ev_start, s.ev_setup));
     HIP_TRY(hipStreamSynchronize(c->kstream));           // (before the transient buffers go)
-    c->map_layer_ok = true;
+    c->per_scene.map_layer = std::move(layer);
     return DG_OK;
 }
 
-// The explored-map frames' cover of the uploaded scene at the ctx's frame size: built on the host (explored_cover.hpp) and copied on the
-// kernel stream between the slot's ev_start / ev_setup.
+// Host tables into device memory on the kernel stream, between the slot's ev_start / ev_setup; done when it returns (the host copies may go).
+struct TableCopy { void *dst; const void *src; size_t bytes; };
+int upload_timed(dg_ctx *c, Slot &s, std::initializer_list<TableCopy> copies) {
+    HIP_TRY(hipEventRecord(s.ev_start, c->kstream));
+    for (const TableCopy &k : copies) HIP_TRY(hipMemcpyAsync(k.dst, k.src, k.bytes, hipMemcpyHostToDevice, c->kstream));
+    HIP_TRY(hipEventRecord(s.ev_setup, c->kstream));
+    HIP_TRY(hipStreamSynchronize(c->kstream));
+    return DG_OK;
+}
+
+// The explored-map frames' cover of the uploaded scene at the ctx's frame size, built on the host (explored_cover.hpp).
 int upload_explored_cover(dg_ctx *c, Slot &s) {
     ExploredCover cv;
     std::string err;
     const int rc = build_explored_cover(*c->scene, c->cfg.width, c->cfg.height, cv, err);
     if (rc) return set_err(rc, err);
-    HIP_TRY(hip_alloc(c->d_cover, cv.cover.size() * 4));
-    HIP_TRY(hip_alloc(c->d_chains, cv.chains.size() * 4));
-    HIP_TRY(hipEventRecord(s.ev_start, c->kstream));
-    HIP_TRY(hipMemcpyAsync(c->d_cover.get(), cv.cover.data(), cv.cover.size() * 4, hipMemcpyHostToDevice, c->kstream));
-    HIP_TRY(hipMemcpyAsync(c->d_chains.get(), cv.chains.data(), cv.chains.size() * 4, hipMemcpyHostToDevice, c->kstream));
-    HIP_TRY(hipEventRecord(s.ev_setup, c->kstream));
-    HIP_TRY(hipStreamSynchronize(c->kstream));           // (before the host copy goes)
-    c->cover_ok = true;
+    DevPtr<uint32_t> cover, chains;
+    HIP_TRY(hip_alloc(cover, cv.cover.size() * 4));
+    HIP_TRY(hip_alloc(chains, cv.chains.size() * 4));
+    if (const int bad = upload_timed(c, s, {{cover.get(), cv.cover.data(), cv.cover.size() * 4}, {chains.get(), cv.chains.data(), cv.chains.size() * 4}})) return bad;
+    c->per_scene.chains = std::move(chains);
+    c->per_scene.cover = std::move(cover);
     return DG_OK;
 }
 
-// The player-centred map frames' line table of the uploaded scene, copied on the kernel stream between the slot's ev_start / ev_setup.
+// The player-centred map frames' line table of the uploaded scene (ego_line_table).
 int upload_ego_table(dg_ctx *c, Slot &s) {
     std::vector<EgoLine> lines;
     std::vector<uint32_t> words;
     ego_line_table(*c->scene, lines, words);
     const size_t L = lines.size();
-    HIP_TRY(hip_alloc(c->d_ego_table, L * (sizeof(EgoLine) + sizeof(uint32_t))));
-    HIP_TRY(hipEventRecord(s.ev_start, c->kstream));
-    HIP_TRY(hipMemcpyAsync(c->d_ego_table.get(), lines.data(), L * sizeof(EgoLine), hipMemcpyHostToDevice, c->kstream));
-    HIP_TRY(hipMemcpyAsync(c->d_ego_table.get() + L * sizeof(EgoLine), words.data(), L * sizeof(uint32_t), hipMemcpyHostToDevice, c->kstream));
-    HIP_TRY(hipEventRecord(s.ev_setup, c->kstream));
-    HIP_TRY(hipStreamSynchronize(c->kstream));           // (before the host copy goes)
-    c->ego_lines = (uint32_t)L;
-    c->ego_table_ok = true;
+    DevPtr<uint8_t> table;
+    HIP_TRY(hip_alloc(table, L * (sizeof(EgoLine) + sizeof(uint32_t))));
+    if (const int bad = upload_timed(c, s, {{table.get(), lines.data(), L * sizeof(EgoLine)}, {table.get() + L * sizeof(EgoLine), words.data(), L * sizeof(uint32_t)}})) return bad;
+    c->per_scene.ego_lines = (uint32_t)L;
+    c->per_scene.ego_table = std::move(table);
     return DG_OK;
 }
 
-// Where a player-centred submission of n frames keeps its arrow lines and its views in the slot's list slab.
+// The per-scene table of the slot's map kind: built by the first such submission after dg_upload_scene, which then has a timed front half.
+int ensure_map_table(dg_ctx *c, Slot &s) {
+    s.map.built = false;
+    int rc;
+    switch (s.front_end) {
+    case DG_FE_MAP: if (c->per_scene.map_layer) return DG_OK; rc = build_map_layer(c, s); break;
+    case DG_FE_MAP_EXPLORED: if (c->per_scene.cover) return DG_OK; rc = upload_explored_cover(c, s); break;
+    default: if (c->per_scene.ego_table) return DG_OK; rc = upload_ego_table(c, s); break;
+    }
+    s.map.built = rc == DG_OK;
+    return rc;
+}
+
+// Where a map submission of n frames keeps what follows its arrow lines in the slot's list slab: a player-centred submission's views.
 size_t ego_views_at(int n) { return (size_t)n * 3 * sizeof(MapSeg); }
 
 constexpr size_t kOverlapMaxPixels = 500000;          // frames up to this size overlap their raster launch with the next batch's front end (dg_create)
@@ -924,7 +940,42 @@ struct Invalidate {
     ~Invalidate() { if (armed) s.reset(); }
 };
 
+// The kernels of the map submission the slot describes, on the ctx's kernel stream behind its upload: the kind's per-scene table if it
+// is not there yet, then the kind's frame kernels.  A HIP call that fails half way leaves the slot empty.
+int enqueue_map_frames(dg_ctx *c, Slot &s) {
+    hipStream_t ks = c->kstream;
+    Invalidate guard{s};
+    HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
+    HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
+    if (const int rc = ensure_map_table(c, s)) return rc;
+    const dg_ctx::PerScene &t = c->per_scene;
+    const MapSeg *const arrow = reinterpret_cast<const MapSeg *>(s.d_lists.get());
+    const int W = c->cfg.width, H = c->cfg.height;
+    if (s.front_end == DG_FE_MAP) {                       // the layer copied + the arrow, per frame
+        HIP_TRY(launch_map_frames(t.map_layer.get(), arrow, s.n_frames, s.d_fb.get(), W, H, ks, s.ev_rstart, s.ev_raster));
+    } else if (s.front_end == DG_FE_MAP_EXPLORED) {       // the cover picked through the frame's mask row + the arrow, per frame
+        HIP_TRY(launch_explored_frames(t.cover.get(), t.chains.get(), s.per_scene.d_masks.get(), (uint32_t)s.per_scene.mask_words, arrow, s.n_frames, s.d_fb.get(),
+                                       W, H, ks, s.ev_rstart, s.ev_raster));
+    } else {                                              // player-centred: one kernel
+        EgoParams E{};
+        E.lines = reinterpret_cast<const EgoLine *>(t.ego_table.get());
+        E.words = reinterpret_cast<const uint32_t *>(t.ego_table.get() + (size_t)t.ego_lines * sizeof(EgoLine));
+        E.n_lines = t.ego_lines;
+        E.views = reinterpret_cast<const EgoView *>(s.d_lists.get() + ego_views_at(s.n_frames));
+        E.arrow = (s.map.ego.flags & EGO_ARROW) ? arrow : nullptr;
+        E.masks = s.map.masked ? s.per_scene.d_masks.get() : nullptr;
+        E.mask_words = (uint32_t)s.per_scene.mask_words;
+        E.scale = s.map.ego.scale; E.rotate = s.map.ego.flags & EGO_ROTATE;
+        E.W = W; E.H = H;
+        E.fb = s.d_fb.get(); E.n_frames = s.n_frames;
+        HIP_TRY(launch_ego_tiles(E, ks, s.ev_rstart, s.ev_raster));
+    }
+    guard.armed = false;
+    return queued(s);                                     // (never DG_FE_AUTO's measurement)
+}
+
 int enqueue_kernels(dg_ctx *c, Slot &s) {
+    if (s.map_frames()) return enqueue_map_frames(c, s);
     // All kernels of all slots run on ONE in-order stream (highest priority, so that it gets a hardware queue of its own): column walk
     // i, rasteriser i, column walk i + 1, ...  The slot's own stream carries its H2D copy (queued already; it overlaps the previous
     // slots' kernels), tied in with an event.  Letting the walk of batch i + 1 overlap the raster launch of batch i was measured to buy
@@ -937,29 +988,7 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     const bool fe_mode = s.column_walk();
     HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
     HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
-    const bool map = s.front_end == DG_FE_MAP, explored = s.front_end == DG_FE_MAP_EXPLORED, ego = s.front_end == DG_FE_MAP_EGO;
-    if (map) {                                            // 2-D map frames: the layer (once per scene upload), then copy + arrow per frame
-        s.map_built = false;
-        if (!c->map_layer_ok) {
-            const int rc = build_map_layer(c, s);
-            if (rc) return rc;
-            s.map_built = true;
-        }
-    } else if (explored) {                                // explored map frames: the cover (once per scene upload), then pick + arrow per frame
-        s.map_built = false;
-        if (!c->cover_ok) {
-            const int rc = upload_explored_cover(c, s);
-            if (rc) return rc;
-            s.map_built = true;
-        }
-    } else if (ego) {                                     // player-centred map frames: the line table (once per scene upload), then one kernel
-        s.map_built = false;
-        if (!c->ego_table_ok) {
-            const int rc = upload_ego_table(c, s);
-            if (rc) return rc;
-            s.map_built = true;
-        }
-    } else if (fe_mode) {
+    if (fe_mode) {
         std::memset(s.h_status.get(), 0, (size_t)2 * (size_t)c->cfg.max_batch * 4);
         // the overflow flags, the launch-order counters and the event bits behind them start from zero: dg_fe_scan leaves them so (its
         // last lines), and only a slot that is new or whose last enqueue failed half way is cleared here, whole
@@ -978,26 +1007,7 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     } else {
         HIP_TRY(launch_setup(s.P, s.max_spans, ks, s.ev_start, s.ev_setup));
     }
-    if (map) {
-        HIP_TRY(launch_map_frames(c->d_map_layer.get(), reinterpret_cast<const MapSeg *>(s.d_lists.get()), s.n_frames, s.d_fb.get(), c->cfg.width, c->cfg.height,
-                                  ks, s.ev_rstart, s.ev_raster));
-    } else if (explored) {
-        HIP_TRY(launch_explored_frames(c->d_cover.get(), c->d_chains.get(), s.d_masks.get(), (uint32_t)s.mask_words, reinterpret_cast<const MapSeg *>(s.d_lists.get()),
-                                       s.n_frames, s.d_fb.get(), c->cfg.width, c->cfg.height, ks, s.ev_rstart, s.ev_raster));
-    } else if (ego) {
-        EgoParams E{};
-        E.lines = reinterpret_cast<const EgoLine *>(c->d_ego_table.get());
-        E.words = reinterpret_cast<const uint32_t *>(c->d_ego_table.get() + (size_t)c->ego_lines * sizeof(EgoLine));
-        E.n_lines = c->ego_lines;
-        E.views = reinterpret_cast<const EgoView *>(s.d_lists.get() + ego_views_at(s.n_frames));
-        E.arrow = (s.ego.flags & EGO_ARROW) ? reinterpret_cast<const MapSeg *>(s.d_lists.get()) : nullptr;
-        E.masks = s.ego_masked ? s.d_masks.get() : nullptr;
-        E.mask_words = (uint32_t)s.mask_words;
-        E.scale = s.ego.scale; E.rotate = s.ego.flags & EGO_ROTATE;
-        E.W = c->cfg.width; E.H = c->cfg.height;
-        E.fb = s.d_fb.get(); E.n_frames = s.n_frames;
-        HIP_TRY(launch_ego_tiles(E, ks, s.ev_rstart, s.ev_raster));
-    } else if (c->raster_overlap && fe_mode) {                   // the front end of the next batch may start while this launch runs (the column scratch is the front end's alone)
+    if (c->raster_overlap && fe_mode) {                   // the front end of the next batch may start while this launch runs (the column scratch is the front end's alone)
         HIP_TRY(hipStreamWaitEvent(c->rstream, s.ev_setup, 0));
         HIP_TRY(launch_raster(s.P, c->rstream, s.ev_rstart, s.ev_raster));
     } else {
@@ -1156,10 +1166,10 @@ int issue_plane_readback(dg_ctx *c, Slot &s, const Slot::Readback &r, hipStream_
         if (dst.id) HIP_TRY(hipMemcpyAsync(r.id, dst.id, 2 * px, hipMemcpyDeviceToHost, stream));
         if (dst.cls) HIP_TRY(hipMemcpyAsync(r.cls, dst.cls, px, hipMemcpyDeviceToHost, stream));
     }
-    const size_t n_boxes = (size_t)r.count * s.box_mobjs;
+    const size_t n_boxes = (size_t)r.count * s.per_scene.box_mobjs;
     if (r.boxes && n_boxes) {
         if (n_boxes > s.rawbox_cap) return set_err(DG_ERR_INVALID, "reduced readback: no box staging reserved");
-        HIP_TRY(hipMemcpyAsync(s.h_rawboxes.get(), s.d_boxes.get() + (size_t)r.first * s.box_mobjs, n_boxes * sizeof(LabelRawBox), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(s.h_rawboxes.get(), s.per_scene.d_boxes.get() + (size_t)r.first * s.per_scene.box_mobjs, n_boxes * sizeof(LabelRawBox), hipMemcpyDeviceToHost, stream));
     }
     return DG_OK;
 }
@@ -1167,7 +1177,7 @@ int issue_plane_readback(dg_ctx *c, Slot &s, const Slot::Readback &r, hipStream_
 // What is left to do on the host once readback r's copies have finished: the box rows in the form the caller sees.
 void finish_readback(const dg_ctx *c, const Slot &s, const Slot::Readback &r) {
     if (!r.planes || !r.boxes) return;
-    const size_t n_boxes = (size_t)r.count * s.box_mobjs;
+    const size_t n_boxes = (size_t)r.count * s.per_scene.box_mobjs;
     for (size_t i = 0; i < n_boxes; i++) {
         int32_t x0, y0, x1, y1;
         label_box_finish(s.h_rawboxes.get()[i], c->cfg.width, c->cfg.height, r.boxes[i].pixels, x0, y0, x1, y1);
@@ -1295,9 +1305,9 @@ int ensure_label_buffers(dg_ctx *c, Slot &s) {
         HIP_TRY(hip_alloc(s.h_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
         HIP_TRY(hip_alloc(s.d_owners, std::max<size_t>(c->wall_cap_per_batch, 4) * sizeof(uint32_t)));
     }
-    if (!s.d_boxes || s.box_mobjs != n_mobjs) {
-        HIP_TRY(hip_alloc(s.d_boxes, std::max<size_t>((size_t)c->cfg.max_batch * n_mobjs, 1) * sizeof(LabelRawBox)));
-        s.box_mobjs = n_mobjs;
+    if (!s.per_scene.d_boxes) {
+        HIP_TRY(hip_alloc(s.per_scene.d_boxes, std::max<size_t>((size_t)c->cfg.max_batch * n_mobjs, 1) * sizeof(LabelRawBox)));
+        s.per_scene.box_mobjs = n_mobjs;
     }
     return DG_OK;
 }
@@ -1310,7 +1320,7 @@ BundlePlanes planes_of(const dg_ctx *c, Slot &s) {
     if (s.holds(BUNDLE_DEPTH)) { out.dist = reinterpret_cast<int16_t *>(fb + L.distance); out.kind = fb + L.kind; }
     if (s.holds(BUNDLE_LABELS)) {
         out.id = reinterpret_cast<uint16_t *>(fb + L.id); out.cls = fb + L.cls;
-        out.boxes = s.d_boxes.get(); out.n_mobjs = (uint32_t)s.box_mobjs;
+        out.boxes = s.per_scene.d_boxes.get(); out.n_mobjs = (uint32_t)s.per_scene.box_mobjs;
     }
     return out;
 }
@@ -1410,6 +1420,54 @@ int check_view_states(const dg_view_state *states, int n) {
         for (int i = 0; i < n; i++)
             if ((states[i].n_lights && !states[i].lights) || (states[i].n_mobjs && !states[i].mobjs)) return set_err(DG_ERR_INVALID, "view state with a null array");
     return DG_OK;
+}
+
+// The slot's mask rows (max_batch x words), there from its first submission with a mask after dg_upload_scene on.
+int ensure_slot_masks(dg_ctx *c, Slot &s, size_t words) {
+    Slot::PerScene &b = s.per_scene;
+    if (b.d_masks) return DG_OK;
+    HIP_TRY(slot_sync(s));                                // (the slot is ours: whatever replayed the old rows has finished)
+    HIP_TRY(hip_alloc(b.h_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
+    HIP_TRY(hip_alloc(b.d_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
+    b.mask_words = words;
+    return DG_OK;
+}
+
+// What the three map submissions do alike once each has checked its own arguments: slot `slot` for n map frames of kind fe, and their
+// kernels enqueued.  arrow_lines(v, l, err): the kind's per-view checks and the arrow's three lines of view v (trig filled; the host owns
+// the libm trig: dg_view has no field for the head angles) into l, which starts as three empty lines.  ego: a player-centred submission's
+// parameters (else null): its views follow the arrow lines.  mask: n rows of the scene's row length, or null.
+template <class ArrowLines>
+int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int n, const dg_ego_map *ego, const uint32_t *mask, ArrowLines arrow_lines) {
+    const int W = c->cfg.width, H = c->cfg.height;
+    const size_t words = seen_words((uint32_t)c->scene->linedefs.size());
+    const size_t bytes = ego_views_at(n) + (ego ? (size_t)n * sizeof(EgoView) : 0), mask_bytes = mask ? (size_t)n * words * sizeof(uint32_t) : 0;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    Slot &s = c->slots[(size_t)slot];
+    int rc = take_slot(c, s);
+    if (rc) return rc;
+    if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
+    if (mask && (rc = ensure_slot_masks(c, s, words))) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
+    EgoView *hv = reinterpret_cast<EgoView *>(s.h_lists.get() + ego_views_at(n));
+    std::string err;
+    for (int i = 0; i < n; i++) {
+        dg_view v = views[i];
+        fill_view_trig(v);
+        dg_map_line l[3] = {};
+        rc = arrow_lines(v, l, err);
+        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
+        for (int k = 0; k < 3; k++) h[3 * i + k] = map_seg_make(l[k].x0, l[k].y0, l[k].x1, l[k].y1, l[k].rgb, W, H);   // clipped to the frame
+        if (ego) hv[i] = ego_view(v);
+    }
+    if (mask) std::memcpy(s.per_scene.h_masks.get(), mask, mask_bytes);
+    s.map = Slot::MapState{ego ? *ego : dg_ego_map{}, mask != nullptr, false};
+    s.describe(fe, n, bytes + mask_bytes, 0, 0);
+    s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream));
+    if (mask) HIP_TRY(hipMemcpyAsync(s.per_scene.d_masks.get(), s.per_scene.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream));
+    return enqueue_kernels(c, s);
 }
 
 }  // namespace
@@ -1552,16 +1610,10 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     c->d_palette.reset(); c->d_texel_idx.reset(); c->d_texel_opq.reset();
     c->d_flats = nullptr;               // inside d_texel_idx's allocation
     // the slots' prepared records point into the device scene that was just freed: nothing may be replayed from them
-    for (Slot &s : c->slots) {                                                    // (the box table is sized by the scene's map objects, a mask row by its linedefs)
-        s.reset(); s.d_boxes.reset(); s.box_mobjs = 0;
-        s.d_masks.reset(); s.h_masks.reset(); s.mask_words = 0;
-    }
-    c->seg_line_ok = false;             // dg_seen_lines_device / dg_slot_seen_lines are synchronous: nothing of them is in flight
-    c->d_seen_scratch.reset(); c->seen_scratch_words = 0;
-    c->cover_ok = false;                // the explored map's cover belongs to the old scene
-    c->ego_table_ok = false; c->d_ego_table.reset(); c->ego_lines = 0;     // ... and the player-centred map's line table
-    c->d_walk_tables.reset();           // dg_ctx_locate_walks is synchronous: nothing of it is in flight
-    c->map_layer_ok = false;            // the map view's linedef layer belongs to the old scene   // (a new scene may reuse the old one's address and revision)
+    for (Slot &s : c->slots) { s.reset(); s.per_scene.drop(); }                   // (the box table is sized by the scene's map objects, a mask row by its linedefs)
+    // ... and what was derived from the old scene goes (a new scene may reuse the old one's address and revision).  The slots are drained;
+    // dg_seen_lines_device, dg_slot_seen_lines and dg_ctx_locate_walks are synchronous: nothing of them is in flight.
+    c->per_scene.drop();
     uint32_t pal[256];
     for (int i = 0; i < 256; i++) pal[i] = (uint32_t)sc.palette[3 * i] | ((uint32_t)sc.palette[3 * i + 1] << 8) | ((uint32_t)sc.palette[3 * i + 2] << 16);
     const size_t nt = std::max<size_t>(sc.texel_idx.size(), 16), nf = std::max<size_t>(sc.flat_pool.size(), 16);
@@ -1845,8 +1897,8 @@ static int read_planes(dg_ctx *c, Slot &s, int first, int count, size_t at16, vo
     if (out16) HIP_TRY(hipMemcpyAsync(out16, fb + at16 + (size_t)first * px * 2, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream));
     if (out8) HIP_TRY(hipMemcpyAsync(out8, fb + at8 + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream));
     if (raw) {
-        raw->resize((size_t)count * s.box_mobjs);
-        if (!raw->empty()) HIP_TRY(hipMemcpyAsync(raw->data(), s.d_boxes.get() + (size_t)first * s.box_mobjs, raw->size() * sizeof(LabelRawBox), hipMemcpyDeviceToHost, s.stream));
+        raw->resize((size_t)count * s.per_scene.box_mobjs);
+        if (!raw->empty()) HIP_TRY(hipMemcpyAsync(raw->data(), s.per_scene.d_boxes.get() + (size_t)first * s.per_scene.box_mobjs, raw->size() * sizeof(LabelRawBox), hipMemcpyDeviceToHost, s.stream));
     }
     HIP_TRY(slot_sync(s));
     return DG_OK;
@@ -1923,7 +1975,7 @@ static int check_plane_readback(dg_ctx *c, int slot, int first, int count, const
 static int reserve_plane_readback(dg_ctx *c, Slot &s, const Slot::Readback &r) {
     const int rc = reserve_reduced(s, plane_scratch(c, r.pdesc, r.count).total);
     if (rc) return rc;
-    return r.boxes ? reserve_rawboxes(s, (size_t)r.count * s.box_mobjs) : DG_OK;
+    return r.boxes ? reserve_rawboxes(s, (size_t)r.count * s.per_scene.box_mobjs) : DG_OK;
 }
 
 static Slot::Readback plane_readback(int first, int count, const dg_plane_reduce_desc *desc, int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls,
@@ -2077,42 +2129,12 @@ int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
     const int W = c->cfg.width, H = c->cfg.height;
     if (W < 40 || H < 40) return set_err(DG_ERR_INVALID, "map frames need width and height >= 40");
     if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
-    const size_t bytes = (size_t)n * 3 * sizeof(MapSeg);
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    Slot &s = c->slots[(size_t)slot];
-    rc = take_slot(c, s);
-    if (rc) return rc;
-    if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
-    const auto t0 = std::chrono::steady_clock::now();
-    // the arrow's three lines per view, clipped to the frame (the host owns the libm trig: dg_view has no field for the head angles)
-    MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
-    std::string err;
-    for (int i = 0; i < n; i++) {
-        dg_view v = views[i];
-        fill_view_trig(v);
-        dg_map_line l[3];
-        rc = map_arrow_lines(*c->scene, W, H, v, l, err);
-        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
-        for (int k = 0; k < 3; k++) h[3 * i + k] = map_seg_make(l[k].x0, l[k].y0, l[k].x1, l[k].y1, l[k].rgb, W, H);
-    }
-    s.describe(DG_FE_MAP, n, bytes, 0, 0);
-    s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream));
-    return enqueue_kernels(c, s);
+    return submit_map_frames(c, slot, DG_FE_MAP, views, n, nullptr, nullptr,
+                             [&](const dg_view &v, dg_map_line *l, std::string &err) { return map_arrow_lines(*c->scene, W, H, v, l, err); });
 }
 
 int dg_render_map_views(dg_ctx *c, const dg_view *views, int n, uint8_t *out) {
     return read_or_wait(c, 0, dg_submit_map_views(c, 0, views, n), n, out);
-}
-
-// The slot's mask rows (max_batch x words), there from its first submission with a mask after dg_upload_scene on.
-static int ensure_slot_masks(dg_ctx *c, Slot &s, size_t words) {
-    if (s.d_masks) return DG_OK;
-    HIP_TRY(slot_sync(s));                                // (the slot is ours: whatever replayed the old rows has finished)
-    HIP_TRY(hip_alloc(s.h_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
-    HIP_TRY(hip_alloc(s.d_masks, (size_t)c->cfg.max_batch * words * sizeof(uint32_t)));
-    s.mask_words = words;
-    return DG_OK;
 }
 
 int dg_submit_explored_map_views(dg_ctx *c, int slot, const dg_view *views, int n, const uint32_t *mask) {
@@ -2126,31 +2148,8 @@ int dg_submit_explored_map_views(dg_ctx *c, int slot, const dg_view *views, int 
     const size_t words = seen_words((uint32_t)c->scene->linedefs.size());
     if (words > EXPLORED_MAX_WORDS) return set_err(DG_ERR_CAPACITY, "explored map frames: more than 65536 linedefs");
     if (words == 0) return set_err(DG_ERR_INVALID, "explored map frames: the scene has no linedefs");
-    const size_t bytes = (size_t)n * 3 * sizeof(MapSeg), mask_bytes = (size_t)n * words * sizeof(uint32_t);
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    Slot &s = c->slots[(size_t)slot];
-    rc = take_slot(c, s);
-    if (rc) return rc;
-    if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
-    rc = ensure_slot_masks(c, s, words);
-    if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
-    std::string err;
-    for (int i = 0; i < n; i++) {
-        dg_view v = views[i];
-        fill_view_trig(v);
-        dg_map_line l[3];
-        rc = map_arrow_lines(*c->scene, W, H, v, l, err);
-        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
-        for (int k = 0; k < 3; k++) h[3 * i + k] = map_seg_make(l[k].x0, l[k].y0, l[k].x1, l[k].y1, l[k].rgb, W, H);
-    }
-    std::memcpy(s.h_masks.get(), mask, mask_bytes);
-    s.describe(DG_FE_MAP_EXPLORED, n, bytes + mask_bytes, 0, 0);
-    s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream));
-    HIP_TRY(hipMemcpyAsync(s.d_masks.get(), s.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream));
-    return enqueue_kernels(c, s);
+    return submit_map_frames(c, slot, DG_FE_MAP_EXPLORED, views, n, nullptr, mask,
+                             [&](const dg_view &v, dg_map_line *l, std::string &err) { return map_arrow_lines(*c->scene, W, H, v, l, err); });
 }
 
 int dg_render_explored_map_views(dg_ctx *c, const dg_view *views, int n, const uint32_t *mask, uint8_t *out) {
@@ -2168,35 +2167,10 @@ int dg_submit_ego_map_views(dg_ctx *c, int slot, const dg_view *views, int n, co
     if (rc) return set_err(rc, err);
     if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
     const bool arrow = (params->flags & EGO_ARROW) != 0;
-    const size_t words = seen_words((uint32_t)c->scene->linedefs.size());
-    const size_t bytes = ego_views_at(n) + (size_t)n * sizeof(EgoView), mask_bytes = mask ? (size_t)n * words * sizeof(uint32_t) : 0;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    Slot &s = c->slots[(size_t)slot];
-    rc = take_slot(c, s);
-    if (rc) return rc;
-    if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
-    if (mask && (rc = ensure_slot_masks(c, s, words))) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    // per view: the contract's checks, the arrow's three lines clipped to the frame (the host owns the libm trig) and what the points depend on
-    MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
-    EgoView *hv = reinterpret_cast<EgoView *>(s.h_lists.get() + ego_views_at(n));
-    for (int i = 0; i < n; i++) {
-        dg_view v = views[i];
-        fill_view_trig(v);
-        rc = ego_check_view(v, err);
-        dg_map_line l[3] = {};
-        if (!rc && arrow) rc = ego_arrow_lines(W, H, v, *params, l, err);
-        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
-        for (int k = 0; k < 3; k++) h[3 * i + k] = map_seg_make(l[k].x0, l[k].y0, l[k].x1, l[k].y1, l[k].rgb, W, H);
-        hv[i] = ego_view(v);
-    }
-    if (mask) std::memcpy(s.h_masks.get(), mask, mask_bytes);
-    s.ego = *params; s.ego_masked = mask != nullptr;
-    s.describe(DG_FE_MAP_EGO, n, bytes + mask_bytes, 0, 0);
-    s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream));
-    if (mask) HIP_TRY(hipMemcpyAsync(s.d_masks.get(), s.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream));
-    return enqueue_kernels(c, s);
+    return submit_map_frames(c, slot, DG_FE_MAP_EGO, views, n, params, mask, [&](const dg_view &v, dg_map_line *l, std::string &why) {
+        const int bad = ego_check_view(v, why);               // (the contract's checks, whether or not an arrow is drawn)
+        return bad || !arrow ? bad : ego_arrow_lines(W, H, v, *params, l, why);
+    });
 }
 
 int dg_render_ego_map_views(dg_ctx *c, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, uint8_t *out) {
@@ -2208,13 +2182,14 @@ static int ensure_seen(dg_ctx *c) {
     if (!c->xstream) HIP_TRY(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
     for (hipEvent_t *ev : {&c->ev_seen0, &c->ev_seen1, &c->ev_seen2, &c->ev_seen3})
         if (!*ev) HIP_TRY(hipEventCreate(ev));
-    if (!c->seg_line_ok) {
+    if (!c->per_scene.seg_line) {
         const Scene &sc = *c->scene;
         std::vector<uint32_t> table(std::max<size_t>(sc.segs.size(), 4), 0u);
         for (size_t k = 0; k < sc.segs.size(); k++) table[k] = (uint32_t)sc.segs[k].linedef;
-        HIP_TRY(hip_alloc(c->d_seg_line, table.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(c->d_seg_line.get(), table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        c->seg_line_ok = true;
+        DevPtr<uint32_t> d_table;
+        HIP_TRY(hip_alloc(d_table, table.size() * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(d_table.get(), table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        c->per_scene.seg_line = std::move(d_table);
     }
     return DG_OK;
 }
@@ -2233,7 +2208,7 @@ int dg_seen_lines_device(dg_ctx *c, int width, int height, int n, const uint16_t
     c->seen_timed = false; c->seen_acc_timed = false;
     hipError_t e = hipMemsetAsync(seen, 0, (size_t)n * words * sizeof(uint32_t), c->xstream);
     if (e == hipSuccess)
-        e = launch_seen_lines(id, cls, width, height, n, c->d_seg_line.get(), (uint32_t)c->scene->segs.size(), seen, words, c->xstream, c->ev_seen0, c->ev_seen1);
+        e = launch_seen_lines(id, cls, width, height, n, c->per_scene.seg_line.get(), (uint32_t)c->scene->segs.size(), seen, words, c->xstream, c->ev_seen0, c->ev_seen1);
     const hipError_t es = hipStreamSynchronize(c->xstream);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_seen_lines_device: ") + hipGetErrorString(e));
@@ -2258,12 +2233,8 @@ int dg_slot_seen_lines(dg_ctx *c, int slot, int first, int count, int run_len, c
     if ((rc = ensure_seen(c))) return rc;
     // scratch rows: seen | upto | carry_in | carry_out (max_batch rows each), then total | fresh (max_batch entries each)
     const size_t rows = (size_t)c->cfg.max_batch, block = rows * words;
-    if (c->seen_scratch_words != words) {
-        c->seen_scratch_words = 0;
-        HIP_TRY(hip_alloc(c->d_seen_scratch, (4 * block + 2 * rows) * sizeof(uint32_t)));
-        c->seen_scratch_words = words;
-    }
-    uint32_t *const d_seen = c->d_seen_scratch.get(), *const d_upto = d_seen + block, *const d_cin = d_upto + block, *const d_cout = d_cin + block;
+    if (!c->per_scene.seen_scratch) HIP_TRY(hip_alloc(c->per_scene.seen_scratch, (4 * block + 2 * rows) * sizeof(uint32_t)));
+    uint32_t *const d_seen = c->per_scene.seen_scratch.get(), *const d_upto = d_seen + block, *const d_cin = d_upto + block, *const d_cout = d_cin + block;
     uint32_t *const d_total = d_cout + block, *const d_fresh = d_total + rows;
     const size_t W = (size_t)c->cfg.width, H = (size_t)c->cfg.height, runs = (size_t)(count / run_len);
     const BundleLayout L = s.layout(W, H);
@@ -2274,7 +2245,7 @@ int dg_slot_seen_lines(dg_ctx *c, int slot, int first, int count, int run_len, c
     hipError_t e = hipMemsetAsync(d_seen, 0, (size_t)count * words * sizeof(uint32_t), xs);
     if (e == hipSuccess && carry_in) e = hipMemcpyAsync(d_cin, carry_in, runs * words * sizeof(uint32_t), hipMemcpyHostToDevice, xs);
     if (e == hipSuccess)
-        e = launch_seen_lines(id, cls, (int)W, (int)H, count, c->d_seg_line.get(), (uint32_t)c->scene->segs.size(), d_seen, (uint32_t)words, xs, c->ev_seen0, c->ev_seen1);
+        e = launch_seen_lines(id, cls, (int)W, (int)H, count, c->per_scene.seg_line.get(), (uint32_t)c->scene->segs.size(), d_seen, (uint32_t)words, xs, c->ev_seen0, c->ev_seen1);
     if (e == hipSuccess)
         e = launch_seen_accumulate(d_seen, (uint32_t)words, count, run_len, carry_in ? d_cin : nullptr, d_upto, total ? d_total : nullptr,
                                    fresh ? d_fresh : nullptr, carry_out ? d_cout : nullptr, xs, c->ev_seen2, c->ev_seen3);
@@ -2322,13 +2293,15 @@ int dg_ctx_locate_walks(dg_ctx *c, dg_walk *const *walks, int n_walks) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     const Scene &sc = *c->scene;
     if (!c->wstream) HIP_TRY(hipStreamCreateWithFlags(&c->wstream, hipStreamNonBlocking));
-    if (!c->d_walk_tables) {
+    if (!c->per_scene.walk_tables) {
         TablePack t;
         const size_t nodes = t.add(sc.walk_nodes), leaves = t.add(sc.walk_leaves);
-        const hipError_t e = t.upload(c->d_walk_tables);
-        if (e != hipSuccess) { c->d_walk_tables.reset(); return set_err(DG_ERR_HIP, std::string("walk tables: ") + hipGetErrorString(e)); }
-        c->d_walk_nodes = t.at<WalkNode>(nodes);
-        c->d_walk_leaves = t.at<WalkLeaf>(leaves);
+        DevPtr<uint8_t> d_tables;
+        const hipError_t e = t.upload(d_tables);
+        if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("walk tables: ") + hipGetErrorString(e));
+        c->per_scene.walk_tables = std::move(d_tables);
+        c->per_scene.walk_nodes = t.at<WalkNode>(nodes);
+        c->per_scene.walk_leaves = t.at<WalkLeaf>(leaves);
     }
     // one slab: the probes of all walks, concatenated, go up in one copy; the floors come back in one
     const WalkLayout L = walk_layout((size_t)probes, (size_t)entries);
@@ -2349,7 +2322,7 @@ int dg_ctx_locate_walks(dg_ctx *c, dg_walk *const *walks, int n_walks) {
     HIP_TRY(hip_alloc(d_slab, L.total));
     uint8_t *const d = d_slab.get();
     WalkParams P{};
-    P.nodes = c->d_walk_nodes; P.leaves = c->d_walk_leaves;
+    P.nodes = c->per_scene.walk_nodes; P.leaves = c->per_scene.walk_leaves;
     P.x = reinterpret_cast<const float *>(d + L.x); P.y = reinterpret_cast<const float *>(d + L.y);
     P.first = d + L.first; P.end_of_tic = reinterpret_cast<const uint32_t *>(d + L.end_of_tic);
     P.value = reinterpret_cast<float *>(d + L.value); P.last = reinterpret_cast<uint32_t *>(d + L.last);
@@ -2390,7 +2363,7 @@ int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
             HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, tiles ? s.ev_cend : s.ev_raster));
         }
         HIP_TRY(hipEventElapsedTime(&out->total_ms, colour ? s.ev_start : s.ev_tiles, s.ev_raster));
-    } else if (s.front_end != DG_FE_DEPTH && s.front_end != DG_FE_LABELS && (!s.map_frames() || s.map_built)) {   // (a map submission has a front-end half only when it built the map layer or uploaded the cover, a depth or label submission none)
+    } else if (s.timed_front_half()) {
         HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
         HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
         HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));

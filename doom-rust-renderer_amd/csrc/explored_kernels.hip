@@ -13,13 +13,14 @@
 //                      (L2 / Infinity Cache resident: 4 MB at 1280x800) and non-temporal stores in the widest form that keeps every frame
 //                      start aligned: <16, 2> 16 pixels = four 16-byte cover loads and three 16-byte stores per item, <4, 4> 4 pixels = three
 //                      dword stores (3 W H a multiple of 4), <1, 4> bytes.  Every item is bounds-checked against the frame.
-// dg_map_explored_arrow   the arrow on top, the rule of map_kernels.hip's arrow kernel (that unit's kernels are file-local).
+// The arrow on top is map_kernels.hip's dg_map_arrow (launch_map_arrow).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
 #include <algorithm>
 
 #include "explored_kernels.hpp"
+#include "map_kernels.hpp"
 
 namespace dg {
 
@@ -191,22 +192,6 @@ __global__ void __launch_bounds__(kThreads) dg_map_explored(const uint32_t *__re
     }
 }
 
-// The arrow: line blockIdx.x of frame blockIdx.y, its clipped steps over the block's lanes.
-// KEEP IN STEP with dg_map_arrow of map_kernels.hip: this is that kernel's body, restated because that unit keeps its kernels file-local
-// and has no launcher for the arrow alone.  A change to the arrow rule has to be made in both; test_explored_gpu.py holds the two against
-// each other (an all-ones mask must give dg_render_map_views' bytes, arrow included).
-__global__ void __launch_bounds__(kThreads) dg_map_explored_arrow(const MapSeg *__restrict__ arrow, uint8_t *__restrict__ fb, int W, int H) {
-    const MapSeg s = arrow[3 * blockIdx.y + blockIdx.x];
-    uint8_t *frame = fb + (size_t)blockIdx.y * 3 * (size_t)W * (size_t)H;
-    for (int32_t k = (int32_t)threadIdx.x; k < s.count; k += kThreads) {
-        int32_t x, y;
-        map_seg_point(s, (int64_t)s.first + k, x, y);
-        if ((uint32_t)x >= (uint32_t)W || (uint32_t)y >= (uint32_t)H) continue;
-        uint8_t *px = frame + 3 * ((size_t)y * (size_t)W + (size_t)x);
-        px[0] = (uint8_t)s.rgb; px[1] = (uint8_t)(s.rgb >> 8); px[2] = (uint8_t)(s.rgb >> 16);
-    }
-}
-
 unsigned blocks_for(size_t items, size_t cap) {
     return (unsigned)std::max<size_t>(1, std::min<size_t>((items + kThreads - 1) / kThreads, cap));
 }
@@ -268,8 +253,8 @@ hipError_t launch_explored_frames(const uint32_t *cover, const uint32_t *chains,
             hipExtLaunchKernelGGL((dg_map_explored<4, 4>), blocks(px / 4u, 4), dim3(kThreads), 0, stream, ev0, nullptr, 0, cover, chains, m0, words, fb0, px);
         else
             hipExtLaunchKernelGGL((dg_map_explored<1, 4>), blocks(px, 4), dim3(kThreads), 0, stream, ev0, nullptr, 0, cover, chains, m0, words, fb0, px);
-        hipExtLaunchKernelGGL(dg_map_explored_arrow, dim3(3, (unsigned)nf), dim3(kThreads), 0, stream, nullptr, ev1, 0, arrow + (size_t)3 * f0, fb0, W, H);
-        const hipError_t e = hipGetLastError();
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = launch_map_arrow(arrow + (size_t)3 * f0, nf, fb0, W, H, stream, nullptr, ev1);   // (this chunk's lines into this chunk's frames)
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -10,6 +10,9 @@
 // steps the minor axis and r_{i+1} = r_i + 2b - 2a, else r_{i+1} = r_i + 2b; with b <= a both stay in [0, 2a).  So 0 <= r_i < 2a, which is the
 // floor above.  m_i never decreases, so the steps whose point lies inside the frame form one range: map_seg_make finds it analytically.
 #pragma once
+#include <cstddef>
+#include <cstring>
+
 #include "rust_num.h"
 
 namespace dg {
@@ -62,6 +65,24 @@ DG_HD MapSeg map_seg_make(int32_t x0, int32_t y0, int32_t x1, int32_t y1, uint32
     s.count = hi >= lo ? (int32_t)(hi - lo + 1) : 0;
     if (s.count == 0) s.first = 0;
     return s;
+}
+
+// The literal rule of a whole frame, on the host: black, then lines[k] (x0, y0, x1, y1, rgb: dg_map_line) for every k with keep(k), in
+// order, each point of its clipped steps as RGB bytes into the W x H RGB24 frame.
+template <class Line, class Keep>
+inline void map_draw_lines_host(const Line *lines, size_t n, int32_t W, int32_t H, uint8_t *rgb24, Keep keep) {
+    std::memset(rgb24, 0, (size_t)3 * (size_t)W * (size_t)H);
+    for (size_t k = 0; k < n; k++) {
+        if (!keep(k)) continue;
+        const MapSeg sg = map_seg_make(lines[k].x0, lines[k].y0, lines[k].x1, lines[k].y1, lines[k].rgb, W, H);
+        for (int32_t i = 0; i < sg.count; i++) {
+            int32_t x, y;
+            map_seg_point(sg, (int64_t)sg.first + i, x, y);
+            if ((uint32_t)x >= (uint32_t)W || (uint32_t)y >= (uint32_t)H) continue;
+            uint8_t *const px = rgb24 + 3 * ((size_t)y * (size_t)W + (size_t)x);
+            px[0] = (uint8_t)sg.rgb; px[1] = (uint8_t)(sg.rgb >> 8); px[2] = (uint8_t)(sg.rgb >> 16);
+        }
+    }
 }
 
 }  // namespace dg

@@ -98,7 +98,11 @@ hipError_t launch_map_frames(const uint8_t *layer, const MapSeg *arrow, int n_fr
         hipExtLaunchKernelGGL(dg_map_copy<uint8_t>, dim3(grid_for((ne + 7) / 8, 4096), (unsigned)n_frames), dim3(kThreads), 0, stream, start, nullptr, 0,
                               layer, fb, ne);
     }
-    hipExtLaunchKernelGGL(dg_map_arrow, dim3(3, (unsigned)n_frames), dim3(kThreads), 0, stream, nullptr, stop, 0, arrow, fb, W, H);
+    return launch_map_arrow(arrow, n_frames, fb, W, H, stream, nullptr, stop);
+}
+
+hipError_t launch_map_arrow(const MapSeg *arrow, int n_frames, uint8_t *fb, int W, int H, hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
+    hipExtLaunchKernelGGL(dg_map_arrow, dim3(3, (unsigned)n_frames), dim3(kThreads), 0, stream, start, stop, 0, arrow, fb, W, H);
     return hipGetLastError();
 }
 
