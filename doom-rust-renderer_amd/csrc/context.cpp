@@ -1,7 +1,8 @@
 // context.cpp — dg_ctx: one GPU's resident scene, per-slot list slabs / framebuffer slabs / streams, the batch builders that run on
 // the host thread pool (pool.hpp), and a slot's way from one submission to the next (Slot::Phase, take_slot, make_final).  Implements
-// the entry points of the C-ABI (include/doomgpu.h) that take a dg_ctx; those that need no GPU are in api_scene.cpp, the memory owners
-// and TablePack in hip_mem.hpp.
+// the entry points of the C-ABI (include/doomgpu.h) that take a dg_ctx and a slot of it; those that run on a stream of the ctx's own
+// and return when done are in api_device.cpp, those that need no GPU in api_scene.cpp.  Slot and dg_ctx themselves: context.hpp; the
+// owners of memory, streams and events and TablePack: hip_mem.hpp.
 //
 // HBM layout (sized once at dg_create for 288 GB parts: nothing is reallocated on the submit path):
 //   scene   : palette 1 KB | texel index plane | texel opacity plane | flats (4 KB each)      immutable per map
@@ -35,310 +36,27 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/doomgpu.h"
-#include "api_common.hpp"
-#include "binner.hpp"
-#include "fe_kernels.hpp"
-#include "fs_kernels.hpp"
-#include "light_fx_kernels.hpp"
-#include "mobj_fx_kernels.hpp"
-#include "frontend.hpp"
-#include "hip_mem.hpp"
-#include "kernels.hpp"
+#include "context.hpp"
 #include "ego_host.hpp"
 #include "ego_kernels.hpp"
 #include "explored_cover.hpp"
 #include "explored_kernels.hpp"
 #include "map_kernels.hpp"
-#include "plane_kernels.hpp"
 #include "plane_reduce_kernels.hpp"
-#include "pool.hpp"
 #include "reduce_kernels.hpp"
-#include "scene.hpp"
-#include "slab_layout.h"
-#include "walk.hpp"
-#include "walk_kernels.hpp"
 
 using namespace dg;
 
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return set_err(DG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+hipError_t dg::slot_sync(Slot &s) {
+    if (s.raster_recorded) { const hipError_t e = hipEventSynchronize(s.ev_raster.get()); if (e != hipSuccess) return e; }
+    return hipStreamSynchronize(s.stream.get());
+}
 
-namespace {
-
-struct Slot {
-    hipStream_t stream = nullptr;
-    // timing events, attached to the dispatches themselves (kernels.hpp): first / last front-end kernel, raster launch; ev_raster is also
-    // what "the slot's kernels are done" is waited on
-    hipEvent_t ev_start = nullptr, ev_setup = nullptr, ev_rstart = nullptr, ev_raster = nullptr, ev_h2d = nullptr;
-    // bundles: the end of the colour raster launch when dg_bundle_tiles follows it (ev_raster is then that kernel's end: always the end of
-    // the submission's LAST kernel), and dg_bundle_tiles' start
-    hipEvent_t ev_cend = nullptr, ev_tiles = nullptr;
-    // ev_raster has been recorded at least once: slot_sync waits only on an event that has.  Not part of the phase below, because it is
-    // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
-    bool raster_recorded = false;
-    hipStream_t copy_stream = nullptr;   // dg_readback_async / dg_readback_reduced_async / dg_readback_planes_reduced_async: D2H of this slot's frames while another slot's kernels run
-    // What a readback moves: frames [first, first + count) to host memory `out`, as they are or reduced by `desc` on the way; or
-    // (planes) the depth and label planes of those frames reduced by `pdesc` to the outputs that are there, and their box rows
-    struct Readback {
-        uint8_t *out = nullptr;
-        int first = 0, count = 0;
-        bool reduced = false;            // goes through the slot's scratch (d_reduced)
-        dg_reduce_desc desc{};
-        bool planes = false;             // dg_readback_planes_reduced*: always with `reduced`
-        dg_plane_reduce_desc pdesc{};
-        int16_t *distance = nullptr;
-        uint8_t *kind = nullptr;
-        uint16_t *id = nullptr;
-        uint8_t *cls = nullptr;
-        dg_label_box *boxes = nullptr;   // filled from h_rawboxes when the copy has finished (finish_readback)
-    } copy;                              // the pending asynchronous one (issued again if the batch has to be redone)
-    bool copy_pending = false;
-    DevPtr<uint8_t> d_reduced;           // reduced readbacks: the kernel's output, allocated by the first one, grown when a later one needs more
-    size_t reduced_cap = 0;
-    PinnedPtr<LabelRawBox> h_rawboxes;   // reduced plane readbacks that ask for boxes: the box rows as the kernels left them, likewise
-    size_t rawbox_cap = 0;               // (entries)
-    PinnedPtr<uint8_t> h_lists;   // pinned staging
-    DevPtr<uint8_t> d_lists;
-    DevPtr<DevRSpan> d_rspans;
-    DevPtr<uint8_t> d_fb;
-    size_t lists_cap = 0;
-    // label frames: owner tags parallel to the wall records of d_lists (staging + HBM, wall_cap_per_batch entries) — they do not exist
-    // before the slot's first label submission
-    PinnedPtr<uint32_t> h_owners;
-    DevPtr<uint32_t> d_owners;
-    // The buffers whose size is the uploaded scene's: dg_upload_scene drops them, the first submission that needs one allocates it.
-    struct PerScene {
-        DevPtr<LabelRawBox> d_boxes;     // label frames: the box table max_batch x box_mobjs
-        size_t box_mobjs = 0;
-        PinnedPtr<uint32_t> h_masks;     // map frames: the mask rows of the last submission that had any (staging + HBM, max_batch x
-        DevPtr<uint32_t> d_masks;        // mask_words), kept for dg_replay_slot
-        size_t mask_words = 0;
-        void drop() { *this = PerScene{}; }
-    } per_scene;
-    // What a map submission (front_end DG_FE_MAP*) leaves for its kernels and for dg_replay_slot besides d_lists (the arrow lines, then a
-    // player-centred submission's views) and the mask rows above: written as a whole by every such submission.
-    struct MapState {
-        dg_ego_map ego{};                // DG_FE_MAP_EGO: scale and flags
-        bool masked = false;             // the kernel reads the slot's mask rows (a player-centred submission may come without)
-        bool built = false;              // the enqueue built the kind's per-scene table: ev_start .. ev_setup time that
-    } map;
-    // last submission
-    RasterParams P{};
-    uint32_t max_spans = 0;
-    uint64_t n_spans = 0, covered = 0, list_bytes = 0, n_walls = 0, n_planes = 0;
-    int n_frames = 0;
-    float host_ms = 0.0f;         // list generation + binning + packing of the last submission
-    // Where that submission stands.  Each step is written once: describe() (-> prepared), enqueue_kernels (-> queued, or
-    // -> empty when it fails), make_final (queued -> settled) and reset() (-> empty).
-    enum class Phase {
-        Empty,                    // no submission (n_frames == 0): a fresh slot, every slot after dg_upload_scene, one whose enqueue failed half way
-        Prepared,                 // lists or records are resident and have not run since they were built
-        Queued,                   // kernels are enqueued: nobody has waited for them or looked at the overflow flags
-        Settled                   // they have finished, frames that overflowed a capacity are redone: the framebuffer is final, the records still there to replay
-    } phase = Phase::Empty;
-    bool has_run() const { return phase >= Phase::Queued; }                        // the timing events are this submission's
-    bool unchecked() const { return phase == Phase::Queued && column_walk(); }     // its overflow flags still have to be looked at
-    void reset() { phase = Phase::Empty; n_frames = 0; snap_scene = nullptr; }     // (nothing may be replayed or redone from what the slot holds)
-    // device column walk (DG_FE_DEVICE)
-    PinnedPtr<uint8_t> h_fe;                    // record slab: pinned staging
-    DevPtr<uint8_t> d_fe;                       // ... and HBM
-    DevPtr<uint32_t> d_fe_coloff;
-    PinnedPtr<uint32_t> h_status;               // pinned host memory the walk's kernels write: [F] overflow flags, [F] spans per frame
-    uint64_t *d_events = nullptr;               // sky event bits (fe_event_words), zeroed before every walk: inside d_flags' allocation
-    size_t walk_state_bytes = 0;                // that whole allocation (dg_create)
-    bool walk_state_clean = false;              // d_flags .. is all zero (dg_fe_scan cleans up after the walk; enqueue_kernels clears a slot that is not)
-    DevPtr<uint32_t> d_order;                   // dg_fe_columns' launch-order lists as dg_fs_frame builds them (FsParams::order_list)
-    DevPtr<uint32_t> d_flags;                   // [F] overflow flags the walk's kernels OR into; sits in front of d_events (one memset clears both)
-    FeParams FP{};
-    FsParams FSP{};               // DG_FE_DEVICE_SEGS: the device seg walk in front of the column walk
-    LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
-    MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
-    // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
-    // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP / DG_FE_MAP_EXPLORED / DG_FE_MAP_EGO (2-D map frames: arrow lines at the start of d_lists) or
-    // DG_FE_DEPTH (host lists walked by dg_depth_tiles: the framebuffer slab holds the two planes, not RGB24) or DG_FE_LABELS (host lists
-    // walked by dg_label_tiles: the slab holds the id and class planes) or DG_FE_BUNDLE (host lists run through the colour kernels and / or
-    // dg_bundle_tiles: the slab holds the parts bundle_what names, laid out by bundle_layout)
-    int32_t front_end = DG_FE_HOST;
-    uint32_t bundle_what = 0;     // DG_BUNDLE_* of the last submission when it was a bundle
-    // A new submission of n frames through front end fe, `bytes` of lists or records uploaded for it (span statistics: the host list path's alone)
-    void describe(int32_t fe, int n, uint64_t bytes, uint64_t walls, uint64_t planes) {
-        front_end = fe; phase = Phase::Prepared; n_frames = n; list_bytes = bytes; n_walls = walls; n_planes = planes;
-        max_spans = 0; n_spans = 0; covered = 0;
-    }
-    bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
-    bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
-    bool map_frames() const { return front_end == DG_FE_MAP || front_end == DG_FE_MAP_EXPLORED || front_end == DG_FE_MAP_EGO; }   // arrow lines at the start of d_lists
-    // This submission has a timed front half (ev_start .. ev_setup): a depth or label submission has none, a map submission only when it
-    // built its kind's per-scene table.
-    bool timed_front_half() const { return front_end != DG_FE_DEPTH && front_end != DG_FE_LABELS && (!map_frames() || map.built); }
-    bool holds_bundle() const { return front_end == DG_FE_BUNDLE && phase != Phase::Empty; }
-    // Which parts the framebuffer slab holds (BUNDLE_*: RGB24 colour frames, the two depth planes, the two label planes) ...
-    uint32_t parts() const {
-        if (phase == Phase::Empty) return 0;
-        if (front_end == DG_FE_BUNDLE) return bundle_what;
-        return front_end == DG_FE_DEPTH ? BUNDLE_DEPTH : front_end == DG_FE_LABELS ? BUNDLE_LABELS : BUNDLE_COLOUR;
-    }
-    bool holds(uint32_t part) const { return (parts() & part) != 0; }
-    // ... and where each sits.  A bundle's parts are where bundle_layout puts them, each on the slab's boundary; the one part of any
-    // other submission starts at the slab's base, its 8-bit plane right behind its 16-bit plane (include/doomgpu.h promises 2 n W H).
-    BundleLayout layout(size_t W, size_t H) const {
-        if (front_end == DG_FE_BUNDLE) return bundle_layout((size_t)n_frames, W, H, bundle_what);
-        const size_t px = (size_t)n_frames * W * H;
-        return BundleLayout{0, 0, 2 * px, 0, 2 * px, 3 * px};
-    }
-    bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
-    std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
-    // ... and a private copy of their game-state snapshots (the caller's arrays need not outlive the call)
-    std::vector<dg_view_state> states;
-    std::vector<dg_sector_light> state_lights;
-    std::vector<dg_mobj_state> state_mobjs;
-    // The scene's own light levels and map-object states as they were when the batch was submitted: a frame that overflows a capacity is
-    // redone at dg_wait time from the host walker, and dg_scene_set_sector_light / _mobj_state may have moved the scene on by then
-    // (lights.rs:47-259 and map_objects.rs:63-121 run between two submissions of a pipelined caller).
-    const Scene *snap_scene = nullptr;
-    uint64_t snap_rev = 0;
-    std::vector<dg_sector_light> snap_lights;
-    std::vector<dg_mobj_state> snap_mobjs;
-    void snapshot_scene(const Scene &sc) {
-        if (snap_scene == &sc && snap_rev == sc.revision && snap_lights.size() == sc.sectors.size() && snap_mobjs.size() == sc.mobjs.size()) return;
-        snap_lights.resize(sc.sectors.size()); snap_mobjs.resize(sc.mobjs.size());
-        for (size_t i = 0; i < sc.sectors.size(); i++) snap_lights[i] = dg_sector_light{(int32_t)i, (int32_t)sc.sectors[i].light};
-        for (size_t i = 0; i < sc.mobjs.size(); i++) snap_mobjs[i] = dg_mobj_state{(int32_t)i, sc.mobjs[i].sprite_frame, sc.mobjs[i].full_bright ? 1 : 0, 0};
-        snap_scene = &sc; snap_rev = sc.revision;
-    }
-    // The game state frame i of the last submission was rendered with, for the host walker: nullptr = the scene as it is (unchanged since the
-    // submission, no per-view snapshot); else the submit-time scene state with the view's own entries on top (later entries win).
-    struct RedoState { std::vector<dg_sector_light> lights; std::vector<dg_mobj_state> mobjs; dg_view_state st{}; };
-    // fx: the effects the frame was drawn with — the light effects' sectors keep the effect's level and the objects the thinkers drive
-    // their state, so the snapshot does not list them.
-    const dg_view_state *state_for_redo(const Scene &sc, int i, RedoState &tmp, const SceneFx &fx) const {
-        const dg_view_state *own = states.empty() ? nullptr : &states[(size_t)i];
-        if (snap_scene != &sc || snap_rev == sc.revision) return own;
-        tmp.lights.clear();
-        const bool lfx = fx.light.fits(sc), mfx = fx.mobj.fits(sc);      // (the snapshot has the scene's sizes: snapshot_scene)
-        for (const dg_sector_light &l : snap_lights)
-            if (!lfx || fx.light.rec_of[(size_t)l.sector] < 0) tmp.lights.push_back(l);
-        tmp.mobjs.clear();
-        for (const dg_mobj_state &m : snap_mobjs)
-            if (!mfx || fx.mobj.type_of[(size_t)m.mobj] < 0) tmp.mobjs.push_back(m);
-        if (own) { tmp.lights.insert(tmp.lights.end(), own->lights, own->lights + own->n_lights); tmp.mobjs.insert(tmp.mobjs.end(), own->mobjs, own->mobjs + own->n_mobjs); }
-        tmp.st = dg_view_state{tmp.lights.data(), (uint32_t)tmp.lights.size(), tmp.mobjs.data(), (uint32_t)tmp.mobjs.size()};
-        return &tmp.st;
-    }
-    void keep_states(const dg_view_state *st, int n) {
-        states.clear(); state_lights.clear(); state_mobjs.clear();
-        if (!st) return;
-        for (int i = 0; i < n; i++) { state_lights.insert(state_lights.end(), st[i].lights, st[i].lights + st[i].n_lights); state_mobjs.insert(state_mobjs.end(), st[i].mobjs, st[i].mobjs + st[i].n_mobjs); }
-        size_t lo = 0, mo = 0;
-        for (int i = 0; i < n; i++) {
-            states.push_back(dg_view_state{state_lights.data() + lo, st[i].n_lights, state_mobjs.data() + mo, st[i].n_mobjs});
-            lo += st[i].n_lights; mo += st[i].n_mobjs;
-        }
-    }
-};
-
-struct FeFrameOut {               // parts-mode output of one frame, owned per batch index
-    std::vector<FePart> parts;
-    std::vector<FeSprite> sprites;
-    std::vector<uint32_t> behind, sky_parts, bin_off, sbin_off;
-    std::vector<uint16_t> bin_parts, sbin_sprites;
-    uint32_t behind_words = 0, n_sky_slots = 0;
-    DevFrame hdr{};
-};
-
-}  // namespace
-
-struct dg_ctx {
-    dg_config cfg{};
-    FrameConsts fk{};
-    DevConsts dk{};
-    const Scene *scene = nullptr;
-    size_t uploaded_texels = 0;         // texel pool size at dg_upload_scene time (grows when new sprite bitmaps are decoded)
-    // device scene
-    DevPtr<uint32_t> d_palette;         // 256 x u32 RGBX, followed by 256 x (r, g, b, 0) f32
-    DevPtr<uint8_t> d_texel_idx, d_texel_opq;
-    uint8_t *d_flats = nullptr;         // inside d_texel_idx's allocation
-    DevPtr<unsigned long long> d_checksums;      // dg_frame_checksums scratch, max_batch entries
-    DevPtr<uint4> d_row_tab;            // per-row constants of the flat / sky mappers (dg_row_table), rebuilt per scene upload
-    DevScene dscene{};
-    std::vector<Slot> slots;
-    hipStream_t kstream = nullptr;      // every kernel of every slot, in submission order (enqueue_kernels)
-    hipStream_t rstream = nullptr;      // raster_overlap: the raster launches, so that the next batch's front-end kernels (kstream) run next to them
-    bool raster_overlap = false;
-    std::unique_ptr<Pool> pool;
-    std::vector<std::unique_ptr<FrameArena>> arenas;   // one per worker (+ caller)
-    std::vector<BinnedFrame> binned;                   // one per frame of a batch
-    std::vector<std::vector<uint32_t>> label_tags;     // label submissions: the owner tag of every wall record of binned[i]
-    size_t span_cap_per_batch = 0, wall_cap_per_batch = 0, plane_cap_per_batch = 0;
-    int n_threads = 1;
-    // device column walk
-    bool fe_enabled = false;            // cfg.front_end asks for it
-    bool fe_scene_ok = false;           // ... and the uploaded scene allows it (sky bitmap >= 256x128, see bin_frame)
-    // device seg walk (DG_FE_DEVICE_SEGS): the scene's per-seg tables + BSP tables in one allocation, per-batch scratch sized by the scene
-    bool fs_enabled = false, fs_scene_ok = false;
-    bool fs_rows_dirty = true;          // the seg walk's candidate rows may hold entries (fresh allocation, or a launch that failed half way)
-    bool preparing = false;             // inside dg_prepare_views: the records are built once and replayed — host time is not in the loop
-    bool fs_forced = false;             // DG_FE_DEVICE_SEGS: always; DG_FE_AUTO: when it is the faster way for the batch at hand (choose_fs)
-    // what DG_FE_AUTO decides by (running means over batches of >= 64 frames, ms per frame): the host's per-seg half, and the whole of the
-    // GPU work of a batch with / without the seg walk in it
-    double ema_host = -1.0, ema_gpu_dev = -1.0, ema_gpu_fs = -1.0;
-    int host_samples = 0;               // batches the host walker was timed on (the first one pays for cold caches and arena growth: not counted)
-    int since_probe = 0;                // seg-walk batches since the host walker was last timed (it is timed again every 32 batches)
-    int since_fs_probe = 0;             // host-walker batches since the seg walk was last timed (likewise)
-    int gpu_samples[2] = {0, 0};        // finished batches seen per mode (host per-seg half / seg walk): the first of each runs on cold caches and clocks, not counted
-    DevPtr<uint8_t> d_fs_scene;
-    // the scene's effects as of dg_upload_scene (every front end draws with this copy), and for the seg walk the device tables of each
-    // effect that is on (only while the seg walk is uploaded)
-    SceneFx fx;
-    DevPtr<uint8_t> d_wall_fx;          // FsSegFx per seg | the live animation lists
-    FsFx fs_fx{};
-    DevPtr<uint8_t> d_light_fx;         // LfxRec per effect sector | rec_of per sector | tables
-    LfxRows lfx_proto{};                // its pointers and the seed, filled at upload
-    DevPtr<uint8_t> d_mobj_fx;          // steps | chains | types | type_of per map object | events
-    MfxRows mfx_proto{};                // its pointers and counts, filled at upload
-    DevPtr<uint8_t> d_fs_scratch;       // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
-    size_t fs_zero_bytes = 0;
-    FsParams fs_proto{};                // scene pointers and counts, filled at upload
-    uint64_t fallbacks_fe = 0;          // batches in which frames were redone because a device-side capacity was exceeded (dg_ctx_fallbacks)
-    uint64_t redone_frames = 0;         // frames redone through the host list path, one at a time (dg_ctx_redone_frames)
-    DevPtr<DevRSpan> d_redo_rspans;     // resolved spans of ONE frame being redone (allocated on first use)
-    size_t redo_span_cap = 0;
-    std::vector<FeFrameOut> fe_out;     // one per frame of a batch
-    uint32_t fe_col_slots = FE_DEFAULT_COL_SLOTS;
-    size_t fe_part_cap = 0, fe_sprite_cap = 0, fe_behind_cap = 0, fe_bin_cap = 0, fe_sbin_cap = 0, fe_slab_cap = 0;
-    DevPtr<uint32_t> d_fe_cnt;
-    DevPtr<FeU4> d_fe_cspans;
-    DevPtr<FeColRec> d_fe_recs;
-    // Device tables derived from the uploaded scene.  Each is made by the first call that needs it after dg_upload_scene, which drops
-    // them all: a table is valid exactly when its pointer is set (each is assigned only once it is complete).
-    struct PerScene {
-        DevPtr<uint8_t> map_layer;          // 2-D map view: every drawn linedef at the ctx's frame size, RGB24 (build_map_layer)
-        DevPtr<uint32_t> cover, chains;     // explored-map frames: explored_core.h's cover and its chains (upload_explored_cover)
-        DevPtr<uint8_t> ego_table;          // player-centred map frames: EgoLine per linedef, then a word per linedef (upload_ego_table)
-        uint32_t ego_lines = 0;
-        DevPtr<uint32_t> seg_line;          // dg_seen_lines_device / dg_slot_seen_lines: seg -> linedef (ensure_seen)
-        DevPtr<uint32_t> seen_scratch;      // dg_slot_seen_lines: its scratch rows, sized by max_batch and the scene's row length
-        DevPtr<uint8_t> walk_tables;        // dg_ctx_locate_walks: the node and leaf tables (walk_core.h)
-        const WalkNode *walk_nodes = nullptr;
-        const WalkLeaf *walk_leaves = nullptr;
-        void drop() { *this = PerScene{}; }
-    } per_scene;
-    hipStream_t wstream = nullptr;      // dg_ctx_locate_walks: a stream of its own, created by the first call — the slots' streams and the kernel stream are not touched
-    // dg_reduce_device: likewise a stream of its own and the events attached to its last call's kernel, created by the first call
-    hipStream_t xstream = nullptr;
-    hipEvent_t ev_reduce0 = nullptr, ev_reduce1 = nullptr;
-    bool reduce_timed = false;
-    // dg_reduce_planes_device: the same stream, events of its own
-    hipEvent_t ev_preduce0 = nullptr, ev_preduce1 = nullptr;
-    bool plane_reduce_timed = false;
-    // dg_seen_lines_device / dg_slot_seen_lines: the events of the last call's kernels, on xstream
-    hipEvent_t ev_seen0 = nullptr, ev_seen1 = nullptr, ev_seen2 = nullptr, ev_seen3 = nullptr;
-    bool seen_timed = false, seen_acc_timed = false;
-};
+int dg::check_slot(dg_ctx *c, int slot) {
+    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
+    if (slot < 0 || slot >= (int)c->slots.size()) return set_err(DG_ERR_INVALID, "slot out of range");
+    return DG_OK;
+}
 
 namespace {
 
@@ -355,35 +73,6 @@ int cgroup_cpu_quota() {
     }
     if (quota <= 0 || period <= 0) return 0;
     return (int)((quota + period - 1) / period);
-}
-
-// Everything queued for the slot so far has finished (its kernels run on the ctx's kernel stream, the rest on its own).
-hipError_t slot_sync(Slot &s) {
-    if (s.raster_recorded) { const hipError_t e = hipEventSynchronize(s.ev_raster); if (e != hipSuccess) return e; }
-    return hipStreamSynchronize(s.stream);
-}
-
-// The members' owners free the memory: with the ctx's device current, and only after every stream that may still use it has drained.
-void free_ctx(dg_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->cfg.device);
-    if (c->kstream) (void)hipStreamSynchronize(c->kstream);        // every slot's kernels, before anything they use is freed
-    if (c->rstream) (void)hipStreamSynchronize(c->rstream);
-    for (Slot &s : c->slots) {
-        if (s.stream) (void)hipStreamSynchronize(s.stream);
-        if (s.copy_stream) (void)hipStreamSynchronize(s.copy_stream);
-        for (hipEvent_t ev : {s.ev_start, s.ev_setup, s.ev_raster, s.ev_rstart, s.ev_h2d, s.ev_cend, s.ev_tiles})
-            if (ev) (void)hipEventDestroy(ev);
-        if (s.copy_stream) (void)hipStreamDestroy(s.copy_stream);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-    }
-    if (c->kstream) (void)hipStreamDestroy(c->kstream);
-    if (c->rstream) (void)hipStreamDestroy(c->rstream);
-    if (c->wstream) { (void)hipStreamSynchronize(c->wstream); (void)hipStreamDestroy(c->wstream); }
-    if (c->xstream) { (void)hipStreamSynchronize(c->xstream); (void)hipStreamDestroy(c->xstream); }
-    for (hipEvent_t ev : {c->ev_reduce0, c->ev_reduce1, c->ev_preduce0, c->ev_preduce1, c->ev_seen0, c->ev_seen1, c->ev_seen2, c->ev_seen3})
-        if (ev) (void)hipEventDestroy(ev);
-    delete c;
 }
 
 // What every batch builder checks first: a scene is resident, the batch fits, the resident texels are still the scene's.
@@ -507,8 +196,8 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
     s.describe(fe, n, L.total, walls, planes);
     s.max_spans = max_spans; s.n_spans = spans; s.covered = covered;
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), L.total, hipMemcpyHostToDevice, s.stream));
-    if (labels && walls) HIP_TRY(hipMemcpyAsync(s.d_owners.get(), s.h_owners.get(), walls * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), L.total, hipMemcpyHostToDevice, s.stream.get()));
+    if (labels && walls) HIP_TRY(hipMemcpyAsync(s.d_owners.get(), s.h_owners.get(), walls * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
 
@@ -604,7 +293,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         const double v = (double)s.host_ms / n;
         c->ema_host = c->host_samples == 2 ? v : 0.75 * c->ema_host + 0.25 * v;
     }
-    HIP_TRY(hipMemcpyAsync(s.d_fe.get(), s.h_fe.get(), L.total, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.d_fe.get(), s.h_fe.get(), L.total, hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
 
@@ -816,7 +505,7 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     s.keep_states(states, n);
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(d, h, L.upload, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(d, h, L.upload, hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
 
@@ -862,9 +551,9 @@ int build_map_layer(dg_ctx *c, Slot &s) {
     uint32_t *d_base = reinterpret_cast<uint32_t *>(tmp.get() + off_base);
     HIP_TRY(hipMemcpy(d_segs, segs.data(), segs.size() * sizeof(MapSeg), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_base, base.data(), base.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(owner, 0, (size_t)W * (size_t)H * 4, c->kstream));
-    HIP_TRY(launch_map_layer(d_segs, d_base, (uint32_t)n, (uint32_t)total, owner, layer.get(), W, H, c->kstream, s.ev_start, s.ev_setup));
-    HIP_TRY(hipStreamSynchronize(c->kstream));           // (before the transient buffers go)
+    HIP_TRY(hipMemsetAsync(owner, 0, (size_t)W * (size_t)H * 4, c->kstream.get()));
+    HIP_TRY(launch_map_layer(d_segs, d_base, (uint32_t)n, (uint32_t)total, owner, layer.get(), W, H, c->kstream.get(), s.ev_start.get(), s.ev_setup.get()));
+    HIP_TRY(hipStreamSynchronize(c->kstream.get()));           // (before the transient buffers go)
     c->per_scene.map_layer = std::move(layer);
     return DG_OK;
 }
@@ -872,10 +561,10 @@ int build_map_layer(dg_ctx *c, Slot &s) {
 // Host tables into device memory on the kernel stream, between the slot's ev_start / ev_setup; done when it returns (the host copies may go).
 struct TableCopy { void *dst; const void *src; size_t bytes; };
 int upload_timed(dg_ctx *c, Slot &s, std::initializer_list<TableCopy> copies) {
-    HIP_TRY(hipEventRecord(s.ev_start, c->kstream));
-    for (const TableCopy &k : copies) HIP_TRY(hipMemcpyAsync(k.dst, k.src, k.bytes, hipMemcpyHostToDevice, c->kstream));
-    HIP_TRY(hipEventRecord(s.ev_setup, c->kstream));
-    HIP_TRY(hipStreamSynchronize(c->kstream));
+    HIP_TRY(hipEventRecord(s.ev_start.get(), c->kstream.get()));
+    for (const TableCopy &k : copies) HIP_TRY(hipMemcpyAsync(k.dst, k.src, k.bytes, hipMemcpyHostToDevice, c->kstream.get()));
+    HIP_TRY(hipEventRecord(s.ev_setup.get(), c->kstream.get()));
+    HIP_TRY(hipStreamSynchronize(c->kstream.get()));
     return DG_OK;
 }
 
@@ -934,6 +623,13 @@ int queued(Slot &s, bool harvested = true) {
     return DG_OK;
 }
 
+// The slot's kernels go on stream ks behind its upload, which is queued on the slot's own stream.
+int after_upload(Slot &s, hipStream_t ks) {
+    HIP_TRY(hipEventRecord(s.ev_h2d.get(), s.stream.get()));
+    HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d.get(), 0));
+    return DG_OK;
+}
+
 // A launch that fails leaves the slot empty: later calls on it return DG_ERR_INVALID instead of reading what nobody wrote.
 struct Invalidate {
     Slot &s; bool armed = true;
@@ -943,19 +639,18 @@ struct Invalidate {
 // The kernels of the map submission the slot describes, on the ctx's kernel stream behind its upload: the kind's per-scene table if it
 // is not there yet, then the kind's frame kernels.  A HIP call that fails half way leaves the slot empty.
 int enqueue_map_frames(dg_ctx *c, Slot &s) {
-    hipStream_t ks = c->kstream;
+    hipStream_t ks = c->kstream.get();
     Invalidate guard{s};
-    HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
-    HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
+    if (const int rc = after_upload(s, ks)) return rc;
     if (const int rc = ensure_map_table(c, s)) return rc;
     const dg_ctx::PerScene &t = c->per_scene;
     const MapSeg *const arrow = reinterpret_cast<const MapSeg *>(s.d_lists.get());
     const int W = c->cfg.width, H = c->cfg.height;
     if (s.front_end == DG_FE_MAP) {                       // the layer copied + the arrow, per frame
-        HIP_TRY(launch_map_frames(t.map_layer.get(), arrow, s.n_frames, s.d_fb.get(), W, H, ks, s.ev_rstart, s.ev_raster));
+        HIP_TRY(launch_map_frames(t.map_layer.get(), arrow, s.n_frames, s.d_fb.get(), W, H, ks, s.ev_rstart.get(), s.ev_raster.get()));
     } else if (s.front_end == DG_FE_MAP_EXPLORED) {       // the cover picked through the frame's mask row + the arrow, per frame
         HIP_TRY(launch_explored_frames(t.cover.get(), t.chains.get(), s.per_scene.d_masks.get(), (uint32_t)s.per_scene.mask_words, arrow, s.n_frames, s.d_fb.get(),
-                                       W, H, ks, s.ev_rstart, s.ev_raster));
+                                       W, H, ks, s.ev_rstart.get(), s.ev_raster.get()));
     } else {                                              // player-centred: one kernel
         EgoParams E{};
         E.lines = reinterpret_cast<const EgoLine *>(t.ego_table.get());
@@ -968,7 +663,7 @@ int enqueue_map_frames(dg_ctx *c, Slot &s) {
         E.scale = s.map.ego.scale; E.rotate = s.map.ego.flags & EGO_ROTATE;
         E.W = W; E.H = H;
         E.fb = s.d_fb.get(); E.n_frames = s.n_frames;
-        HIP_TRY(launch_ego_tiles(E, ks, s.ev_rstart, s.ev_raster));
+        HIP_TRY(launch_ego_tiles(E, ks, s.ev_rstart.get(), s.ev_raster.get()));
     }
     guard.armed = false;
     return queued(s);                                     // (never DG_FE_AUTO's measurement)
@@ -983,11 +678,10 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
     // (profiles/r03_column_walk.md) — for small frames it does pay, and the raster launches then go to a second stream (raster_overlap).  The walk's per-frame status words (overflow flags, span totals) live in pinned host memory and are
     // written by the kernels directly: nothing is queued behind the raster launch, so no stream ever holds a barrier that another
     // slot's upload could get stuck behind (streams share hardware queues).
-    hipStream_t ks = c->kstream;
+    hipStream_t ks = c->kstream.get();
     Invalidate guard{s};                                  // (a HIP call that fails half way: nobody wrote the status words)
     const bool fe_mode = s.column_walk();
-    HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
-    HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
+    if (const int rc = after_upload(s, ks)) return rc;
     if (fe_mode) {
         std::memset(s.h_status.get(), 0, (size_t)2 * (size_t)c->cfg.max_batch * 4);
         // the overflow flags, the launch-order counters and the event bits behind them start from zero: dg_fe_scan leaves them so (its
@@ -997,21 +691,21 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
         if (s.seg_walk()) {                                                                             // the seg walk writes what the column walk reads
             if (c->fs_rows_dirty) HIP_TRY(hipMemsetAsync(c->d_fs_scratch.get(), 0, c->fs_zero_bytes, ks));    // (dg_fs_frame leaves its rows clean)
             c->fs_rows_dirty = true;
-            hipEvent_t fs_start = s.ev_start;
+            hipEvent_t fs_start = s.ev_start.get();
             if (s.LR.n_frames > 0) { HIP_TRY(launch_light_rows(s.LR, ks, fs_start)); fs_start = nullptr; }     // the rows dg_fs_* read
             if (s.MR.n_frames > 0) { HIP_TRY(launch_mobj_rows(s.MR, ks, fs_start)); fs_start = nullptr; }
             HIP_TRY(c->fx.wall.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
             c->fs_rows_dirty = false;
         }
-        HIP_TRY(launch_fe(s.FP, ks, s.seg_walk() ? nullptr : s.ev_start, s.ev_setup));
+        HIP_TRY(launch_fe(s.FP, ks, s.seg_walk() ? nullptr : s.ev_start.get(), s.ev_setup.get()));
     } else {
-        HIP_TRY(launch_setup(s.P, s.max_spans, ks, s.ev_start, s.ev_setup));
+        HIP_TRY(launch_setup(s.P, s.max_spans, ks, s.ev_start.get(), s.ev_setup.get()));
     }
     if (c->raster_overlap && fe_mode) {                   // the front end of the next batch may start while this launch runs (the column scratch is the front end's alone)
-        HIP_TRY(hipStreamWaitEvent(c->rstream, s.ev_setup, 0));
-        HIP_TRY(launch_raster(s.P, c->rstream, s.ev_rstart, s.ev_raster));
+        HIP_TRY(hipStreamWaitEvent(c->rstream.get(), s.ev_setup.get(), 0));
+        HIP_TRY(launch_raster(s.P, c->rstream.get(), s.ev_rstart.get(), s.ev_raster.get()));
     } else {
-        HIP_TRY(launch_raster(s.P, ks, s.ev_rstart, s.ev_raster));
+        HIP_TRY(launch_raster(s.P, ks, s.ev_rstart.get(), s.ev_raster.get()));
     }
     if (fe_mode) s.walk_state_clean = true;               // everything was enqueued: dg_fe_scan will have cleaned up by the slot's next batch
     guard.armed = false;
@@ -1043,20 +737,17 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     }
     if (bf.spans.size() > c->redo_span_cap) return DG_ERR_CAPACITY;
     pack_binned(s.h_lists.get(), L, bf, 0, (size_t)W);
-    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), L.total, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), L.total, hipMemcpyHostToDevice, s.stream.get()));
     RasterParams Q = s.P;
     point_at_lists(Q, s.d_lists.get(), L);
     Q.rspans = c->d_redo_rspans.get();
     Q.fb = s.d_fb.get() + (size_t)i * (size_t)3 * (size_t)W * (size_t)H;
     Q.n_frames = 1;
-    HIP_TRY(launch_setup(Q, (uint32_t)bf.spans.size(), s.stream));
-    HIP_TRY(launch_raster(Q, s.stream));
+    HIP_TRY(launch_setup(Q, (uint32_t)bf.spans.size(), s.stream.get()));
+    HIP_TRY(launch_raster(Q, s.stream.get()));
     HIP_TRY(slot_sync(s));                                 // the host slab is reused by the next frame
     return DG_OK;
 }
-
-enum class Copy { Leave, Complete };                   // what make_final does about the slot's pending dg_readback_async
-int make_final(dg_ctx *c, Slot &s, Copy copy);
 
 // The overflow flags of a column-walk submission whose kernels have finished (make_final): a batch that overflowed a per-column /
 // per-frame capacity is redone through the host list path (which has the larger limits).
@@ -1103,8 +794,8 @@ int redo_overflowed(dg_ctx *c, Slot &s) {
 // after a sync of the slot's streams.
 int reserve_reduced(Slot &s, size_t bytes) {
     if (bytes <= s.reduced_cap) return DG_OK;
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    HIP_TRY(hipStreamSynchronize(s.copy_stream));
+    HIP_TRY(hipStreamSynchronize(s.stream.get()));
+    HIP_TRY(hipStreamSynchronize(s.copy_stream.get()));
     s.reduced_cap = 0;
     HIP_TRY(hip_alloc(s.d_reduced, bytes));
     s.reduced_cap = bytes;
@@ -1114,8 +805,8 @@ int reserve_reduced(Slot &s, size_t bytes) {
 // Room for `entries` raw box rows in the slot's pinned staging, under the same rule.
 int reserve_rawboxes(Slot &s, size_t entries) {
     if (entries <= s.rawbox_cap) return DG_OK;
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    HIP_TRY(hipStreamSynchronize(s.copy_stream));
+    HIP_TRY(hipStreamSynchronize(s.stream.get()));
+    HIP_TRY(hipStreamSynchronize(s.copy_stream.get()));
     s.rawbox_cap = 0;
     HIP_TRY(hip_alloc(s.h_rawboxes, entries * sizeof(LabelRawBox)));
     s.rawbox_cap = entries;
@@ -1206,34 +897,36 @@ int issue_readback(dg_ctx *c, Slot &s, const Slot::Readback &r, hipStream_t stre
 
 // The slot's pending readback onto its copy stream, behind the slot's kernels.
 int enqueue_copy(dg_ctx *c, Slot &s) {
-    HIP_TRY(hipStreamWaitEvent(s.copy_stream, s.ev_raster, 0));
-    return issue_readback(c, s, s.copy, s.copy_stream);
+    HIP_TRY(hipStreamWaitEvent(s.copy_stream.get(), s.ev_raster.get(), 0));
+    return issue_readback(c, s, s.copy, s.copy_stream.get());
 }
 
 // DG_FE_AUTO's measurement of the GPU side: the span of a finished submission's kernels (never waits)
 void harvest_gpu_time(dg_ctx *c, Slot &s) {
     if (s.harvested || !s.has_run() || !s.column_walk() || s.n_frames < 64 || c->fs_forced || !c->fs_enabled) return;
-    if (hipEventQuery(s.ev_raster) != hipSuccess) return;
+    if (hipEventQuery(s.ev_raster.get()) != hipSuccess) return;
     s.harvested = true;
     float ms = 0.0f;
     if (c->raster_overlap) {                               // the raster launch may have waited behind the previous batch's: the two halves' own durations
         float fe_ms = 0.0f, r_ms = 0.0f;
-        if (hipEventElapsedTime(&fe_ms, s.ev_start, s.ev_setup) != hipSuccess || hipEventElapsedTime(&r_ms, s.ev_rstart, s.ev_raster) != hipSuccess) return;
+        if (hipEventElapsedTime(&fe_ms, s.ev_start.get(), s.ev_setup.get()) != hipSuccess || hipEventElapsedTime(&r_ms, s.ev_rstart.get(), s.ev_raster.get()) != hipSuccess) return;
         ms = std::max(fe_ms, r_ms);                        // (they overlap with the neighbouring batches': the longer one sets the pace)
         if (!(ms > 0.0f)) return;
-    } else if (hipEventElapsedTime(&ms, s.ev_start, s.ev_raster) != hipSuccess || !(ms > 0.0f)) return;
+    } else if (hipEventElapsedTime(&ms, s.ev_start.get(), s.ev_raster.get()) != hipSuccess || !(ms > 0.0f)) return;
     if (c->gpu_samples[s.seg_walk() ? 1 : 0]++ == 0) return;  // (the first batch of a mode: cold caches, code not yet resident, clocks down — a seg walk judged by it alone was never tried again)
     double &ema = s.seg_walk() ? c->ema_gpu_fs : c->ema_gpu_dev;
     const double v = (double)ms / s.n_frames;
     ema = ema < 0.0 ? v : 0.75 * ema + 0.25 * v;
 }
 
+}  // namespace
+
 // Making the last submission's results final, the one way from queued to settled: everything queued for the slot has finished, and the
 // overflow flags of a column-walk batch are looked at, once per enqueue (frames that overflowed are redone here).  On a slot that is
 // not queued this only waits, for a prepared slot's upload.  Copy::Complete is the wait path (dg_wait, take_slot): it owns the slot's
 // pending asynchronous readback as well — completed, and issued again after a redo, because its first copy took frames of the overflowed
 // run — and it is where DG_FE_AUTO reads the batch's GPU time.  Copy::Leave leaves both alone.
-int make_final(dg_ctx *c, Slot &s, Copy copy) {
+int dg::make_final(dg_ctx *c, Slot &s, Copy copy) {
     HIP_TRY(slot_sync(s));
     if (copy == Copy::Complete) harvest_gpu_time(c, s);
     const uint64_t redone = c->fallbacks_fe;
@@ -1244,17 +937,19 @@ int make_final(dg_ctx *c, Slot &s, Copy copy) {
         if (rc) return rc;
     }
     if (copy == Copy::Complete && s.copy_pending) {
-        HIP_TRY(hipStreamSynchronize(s.copy_stream));
+        HIP_TRY(hipStreamSynchronize(s.copy_stream.get()));
         if (c->fallbacks_fe != redone) {
             const int rc = enqueue_copy(c, s);
             if (rc) return rc;
-            HIP_TRY(hipStreamSynchronize(s.copy_stream));
+            HIP_TRY(hipStreamSynchronize(s.copy_stream.get()));
         }
         finish_readback(c, s, s.copy);
         s.copy_pending = false;
     }
     return DG_OK;
 }
+
+namespace {
 
 // Taking the slot for a new submission: what is in flight is finished first, a pending asynchronous readback included (it reads the
 // framebuffer the new submission overwrites).  After that the slot is the builder's.
@@ -1281,12 +976,6 @@ int read_or_wait(dg_ctx *c, int slot, int rc, bool wanted, Read read) {
 }
 int read_or_wait(dg_ctx *c, int slot, int rc, int n, uint8_t *out) {
     return read_or_wait(c, slot, rc, out != nullptr, [&] { return dg_readback(c, slot, 0, n, out); });
-}
-
-int check_slot(dg_ctx *c, int slot) {
-    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
-    if (slot < 0 || slot >= (int)c->slots.size()) return set_err(DG_ERR_INVALID, "slot out of range");
-    return DG_OK;
 }
 
 // The calls that read the framebuffer slab as RGB24 frames, or run the colour kernels again: the slot has no colour part.  (An empty
@@ -1342,7 +1031,7 @@ int submit_depth(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists
     rc = build_batch_host(c, s, views, given, n, states, DG_FE_DEPTH);
     if (rc) return rc;
     const BundlePlanes out = planes_of(c, s);
-    return launched(s, launch_depth(s.P, out.dist, out.kind, s.stream, s.ev_rstart, s.ev_raster), "launch_depth");
+    return launched(s, launch_depth(s.P, out.dist, out.kind, s.stream.get(), s.ev_rstart.get(), s.ev_raster.get()), "launch_depth");
 }
 
 // Slot `slot` for a label submission of n views (or of the caller's lists with their owner tags): the host list path like depth;
@@ -1360,7 +1049,7 @@ int submit_labels(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     rc = build_batch_host(c, s, views, given, n, states, DG_FE_LABELS, owners);
     if (rc) return rc;
     const BundlePlanes out = planes_of(c, s);
-    return launched(s, launch_labels(s.P, s.d_owners.get(), out.id, out.cls, out.boxes, out.n_mobjs, s.stream, s.ev_rstart, s.ev_setup, s.ev_raster), "launch_labels");
+    return launched(s, launch_labels(s.P, s.d_owners.get(), out.id, out.cls, out.boxes, out.n_mobjs, s.stream.get(), s.ev_rstart.get(), s.ev_setup.get(), s.ev_raster.get()), "launch_labels");
 }
 
 int check_bundle_what(uint32_t what) {
@@ -1377,17 +1066,16 @@ int bundle_capacity_of(const dg_ctx *c, uint32_t what) {
 // for — P.fb is the slab's base — then the clearing of the box rows and dg_bundle_tiles when a plane is.  ev_raster goes to whichever
 // kernel is the last.  A HIP call that fails half way leaves the slot empty.
 int enqueue_bundle(dg_ctx *c, Slot &s) {
-    hipStream_t ks = c->kstream;
+    hipStream_t ks = c->kstream.get();
     Invalidate guard{s};
     const uint32_t what = s.bundle_what;
     const bool colour = (what & BUNDLE_COLOUR) != 0, tiles = (what & (BUNDLE_DEPTH | BUNDLE_LABELS)) != 0;
-    HIP_TRY(hipEventRecord(s.ev_h2d, s.stream));
-    HIP_TRY(hipStreamWaitEvent(ks, s.ev_h2d, 0));
+    if (const int rc = after_upload(s, ks)) return rc;
     if (colour) {
-        HIP_TRY(launch_setup(s.P, s.max_spans, ks, s.ev_start, s.ev_setup));
-        HIP_TRY(launch_raster(s.P, ks, s.ev_rstart, tiles ? s.ev_cend : s.ev_raster));
+        HIP_TRY(launch_setup(s.P, s.max_spans, ks, s.ev_start.get(), s.ev_setup.get()));
+        HIP_TRY(launch_raster(s.P, ks, s.ev_rstart.get(), tiles ? s.ev_cend.get() : s.ev_raster.get()));
     }
-    if (tiles) HIP_TRY(launch_bundle(s.P, s.d_owners.get(), planes_of(c, s), what, ks, s.ev_tiles, s.ev_raster));
+    if (tiles) HIP_TRY(launch_bundle(s.P, s.d_owners.get(), planes_of(c, s), what, ks, s.ev_tiles.get(), s.ev_raster.get()));
     guard.armed = false;
     return queued(s);                                     // (never DG_FE_AUTO's measurement)
 }
@@ -1413,6 +1101,16 @@ int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     }
     s.bundle_what = what;
     return enqueue_bundle(c, s);
+}
+
+// The times of the bundle the slot has run, into the outputs that are there: setup and raster are the colour kernels' (the raster
+// launch ends at ev_cend when dg_bundle_tiles follows it), tiles is dg_bundle_tiles'; 0 for a part the bundle does not have.
+int bundle_times(const Slot &s, float *setup_ms, float *raster_ms, float *tiles_ms) {
+    const bool colour = (s.bundle_what & BUNDLE_COLOUR) != 0, tiles = (s.bundle_what & (BUNDLE_DEPTH | BUNDLE_LABELS)) != 0;
+    if (setup_ms) { *setup_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(setup_ms, s.ev_start.get(), s.ev_setup.get())); }
+    if (raster_ms) { *raster_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(raster_ms, s.ev_rstart.get(), tiles ? s.ev_cend.get() : s.ev_raster.get())); }
+    if (tiles_ms) { *tiles_ms = 0.0f; if (tiles) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_tiles.get(), s.ev_raster.get())); }
+    return DG_OK;
 }
 
 int check_view_states(const dg_view_state *states, int n) {
@@ -1465,8 +1163,8 @@ int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int
     s.map = Slot::MapState{ego ? *ego : dg_ego_map{}, mask != nullptr, false};
     s.describe(fe, n, bytes + mask_bytes, 0, 0);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream));
-    if (mask) HIP_TRY(hipMemcpyAsync(s.per_scene.d_masks.get(), s.per_scene.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream.get()));
+    if (mask) HIP_TRY(hipMemcpyAsync(s.per_scene.d_masks.get(), s.per_scene.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream.get()));
     return enqueue_kernels(c, s);
 }
 
@@ -1490,7 +1188,7 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
         return set_err(DG_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this build targets gfx950 only");
     HIP_TRY(hipSetDevice(cfg->device));
 
-    dg_ctx *c = new dg_ctx();
+    std::unique_ptr<dg_ctx> c(new dg_ctx());     // (an error below destroys it half built: ~dg_ctx)
     c->cfg = *cfg;
     c->fk = make_consts(cfg->width, cfg->height);
     c->dk = DevConsts{c->fk.ARC, c->fk.GCFX, c->fk.CFX, c->fk.CFY, cfg->width, cfg->height};
@@ -1541,56 +1239,53 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
         c->fe_slab_cap = fe_layout(F, W, c->fe_part_cap, c->fe_sprite_cap, c->fe_behind_cap, F * FE_MAX_SKY_SLOTS, c->fe_bin_cap, c->fe_sbin_cap).total + 1024;
     }
     c->slots.resize((size_t)cfg->slots);
-    hipError_t e;
-#define CTX_TRY(expr) if ((e = (expr)) != hipSuccess) { std::string m = std::string(#expr) + ": " + hipGetErrorString(e); free_ctx(c); return set_err(DG_ERR_HIP, m); }
-    CTX_TRY(hip_alloc(c->d_checksums, F * 8));
+    HIP_TRY(hip_alloc(c->d_checksums, F * 8));
     if (c->fe_enabled) {
-        CTX_TRY(hip_alloc(c->d_fe_cspans, F * c->fe_col_slots * W * sizeof(FeU4)));
-        CTX_TRY(hip_alloc(c->d_fe_recs, F * c->fe_col_slots * W * sizeof(FeColRec)));
-        CTX_TRY(hip_alloc(c->d_fe_cnt, F * W * 4));
+        HIP_TRY(hip_alloc(c->d_fe_cspans, F * c->fe_col_slots * W * sizeof(FeU4)));
+        HIP_TRY(hip_alloc(c->d_fe_recs, F * c->fe_col_slots * W * sizeof(FeColRec)));
+        HIP_TRY(hip_alloc(c->d_fe_cnt, F * W * 4));
     }
     {
         int lo = 0, hi = 0;
-        CTX_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        CTX_TRY(hipStreamCreateWithPriority(&c->kstream, hipStreamNonBlocking, hi));
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        HIP_TRY(stream_create(c->kstream, &hi));
         // Small frames: the front-end kernels of a batch are chains of dependent steps that leave most of the chip idle, and at 320x200 they
         // last as long as the raster launch itself — letting the next batch's front end run next to this batch's raster launch (two streams,
         // tied by the front end's last dispatch event) is worth 17 % there (2.57 -> 3.02 M frames/s), 7 % at 640x400, 2 % at 800x600.  From 1024x768 up the raster launch
         // fills the chip and the overlap costs 1-2 % (profiles/r03_column_walk.md, r05_seg_walk.md).  DOOMGPU_RASTER_OVERLAP=0 / 1 overrides.
         c->raster_overlap = (size_t)cfg->width * (size_t)cfg->height <= kOverlapMaxPixels;
         if (const char *e = std::getenv("DOOMGPU_RASTER_OVERLAP")) c->raster_overlap = std::atoi(e) != 0;
-        if (c->raster_overlap) CTX_TRY(hipStreamCreateWithPriority(&c->rstream, hipStreamNonBlocking, hi));
+        if (c->raster_overlap) HIP_TRY(stream_create(c->rstream, &hi));
     }
     for (Slot &s : c->slots) {
-        CTX_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-        for (hipEvent_t *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles}) CTX_TRY(hipEventCreate(ev));
-        CTX_TRY(hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming));
-        CTX_TRY(hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking));
-        CTX_TRY(hip_alloc(s.h_lists, lists_cap));
-        CTX_TRY(hip_alloc(s.d_lists, lists_cap));
-        CTX_TRY(hip_alloc(s.d_rspans, c->span_cap_per_batch * sizeof(DevRSpan)));
-        CTX_TRY(hip_alloc(s.d_fb, F * 3 * W * H));
+        HIP_TRY(stream_create(s.stream));
+        for (Event *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles}) HIP_TRY(event_create(*ev));
+        HIP_TRY(event_create(s.ev_h2d, false));            // (it only orders streams)
+        HIP_TRY(stream_create(s.copy_stream));
+        HIP_TRY(hip_alloc(s.h_lists, lists_cap));
+        HIP_TRY(hip_alloc(s.d_lists, lists_cap));
+        HIP_TRY(hip_alloc(s.d_rspans, c->span_cap_per_batch * sizeof(DevRSpan)));
+        HIP_TRY(hip_alloc(s.d_fb, F * 3 * W * H));
         if (c->fe_enabled) {
-            CTX_TRY(hip_alloc(s.h_fe, c->fe_slab_cap));
-            CTX_TRY(hip_alloc(s.d_fe, c->fe_slab_cap));
-            CTX_TRY(hip_alloc(s.d_fe_coloff, F * (W + 1) * 4));
-            CTX_TRY(hip_alloc(s.d_order, FS_ORDER_CLASSES * F * fe_col_groups(W) * 4));
+            HIP_TRY(hip_alloc(s.h_fe, c->fe_slab_cap));
+            HIP_TRY(hip_alloc(s.d_fe, c->fe_slab_cap));
+            HIP_TRY(hip_alloc(s.d_fe_coloff, F * (W + 1) * 4));
+            HIP_TRY(hip_alloc(s.d_order, FS_ORDER_CLASSES * F * fe_col_groups(W) * 4));
             SlabCursor ws;
             ws.take(F * 4 + FS_ORDER_CLASSES * 4);                              // the flag words, then the seg walk's launch-order counters
             const size_t off_events = ws.take(F * FE_MAX_SKY_SLOTS * 3 * ((W + 63) / 64) * 8);
             s.walk_state_bytes = ws.end();
-            CTX_TRY(hip_alloc(s.d_flags, s.walk_state_bytes));
+            HIP_TRY(hip_alloc(s.d_flags, s.walk_state_bytes));
             s.d_events = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(s.d_flags.get()) + off_events);
-            CTX_TRY(hip_alloc(s.h_status, 2 * F * 4));
+            HIP_TRY(hip_alloc(s.h_status, 2 * F * 4));
         }
         s.lists_cap = lists_cap;
     }
-#undef CTX_TRY
-    *out = c;
+    *out = c.release();
     return DG_OK;
 }
 
-void dg_destroy(dg_ctx *ctx) { free_ctx(ctx); }
+void dg_destroy(dg_ctx *ctx) { delete ctx; }
 int dg_ctx_host_threads(const dg_ctx *ctx) { return ctx ? ctx->n_threads : DG_ERR_INVALID; }
 
 int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
@@ -1602,7 +1297,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
         // impossible — the old scene object itself was changed since its upload — the slot is just drained.)
         if (c->scene) (void)take_slot(c, s);
         HIP_TRY(slot_sync(s));
-        HIP_TRY(hipStreamSynchronize(s.copy_stream));
+        HIP_TRY(hipStreamSynchronize(s.copy_stream.get()));
         if (s.copy_pending) finish_readback(c, s, s.copy);     // (a slot that was only drained: its copies have run all the same)
         s.copy_pending = false;
     }
@@ -1702,13 +1397,6 @@ static int readback_async(dg_ctx *c, int slot, int first, int count, const dg_re
     return DG_OK;
 }
 
-// What the reduced readbacks check before anything else.
-static int check_reduce_desc(const dg_reduce_desc *desc) {
-    if (!desc) return set_err(DG_ERR_INVALID, "null argument");
-    if (!reduce_desc_ok(*desc)) return set_err(DG_ERR_INVALID, "reduce descriptor: fx and fy in 1..16, a known format, reserved 0");
-    return DG_OK;
-}
-
 int dg_readback_async(dg_ctx *c, int slot, int first, int count, uint8_t *out) { return readback_async(c, slot, first, count, nullptr, out); }
 
 int dg_readback_reduced_async(dg_ctx *c, int slot, int first, int count, const dg_reduce_desc *desc, uint8_t *out) {
@@ -1732,36 +1420,9 @@ int dg_readback_reduced(dg_ctx *c, int slot, int first, int count, const dg_redu
     r.out = out; r.first = first; r.count = count; r.reduced = true; r.desc = *desc;
     rc = reserve_reduced(s, (size_t)count * reduce_frame_bytes((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, *desc));
     if (rc) return rc;
-    rc = issue_readback(c, s, r, s.stream);
+    rc = issue_readback(c, s, r, s.stream.get());
     if (rc) return rc;
     HIP_TRY(slot_sync(s));
-    return DG_OK;
-}
-
-int dg_reduce_device(dg_ctx *c, const void *src, int width, int height, int n_frames, const dg_reduce_desc *desc, void *dst) {
-    if (!c || !src || !dst) return set_err(DG_ERR_INVALID, "null argument");
-    const int rc = check_reduce_desc(desc);
-    if (rc) return rc;
-    if (width < 1 || height < 1 || width > 16384 || height > 16384 || n_frames < 0) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384], n_frames >= 0");
-    if (n_frames == 0) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->xstream) HIP_TRY(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
-    if (!c->ev_reduce0) HIP_TRY(hipEventCreate(&c->ev_reduce0));
-    if (!c->ev_reduce1) HIP_TRY(hipEventCreate(&c->ev_reduce1));
-    c->reduce_timed = false;
-    hipError_t e = launch_reduce(static_cast<const uint8_t *>(src), width, height, n_frames, *desc, static_cast<uint8_t *>(dst), c->xstream, c->ev_reduce0, c->ev_reduce1);
-    const hipError_t es = hipStreamSynchronize(c->xstream);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_reduce_device: ") + hipGetErrorString(e));
-    c->reduce_timed = true;
-    return DG_OK;
-}
-
-int dg_ctx_reduce_kernel_ms(dg_ctx *c, float *ms) {
-    if (!c || !ms) return set_err(DG_ERR_INVALID, "null argument");
-    if (!c->reduce_timed) return set_err(DG_ERR_INVALID, "no dg_reduce_device call has launched yet");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(hipEventElapsedTime(ms, c->ev_reduce0, c->ev_reduce1));
     return DG_OK;
 }
 
@@ -1795,7 +1456,7 @@ int dg_readback(dg_ctx *c, int slot, int first, int count, uint8_t *out) {
     const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
     rc = make_final(c, s, Copy::Leave);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, s.d_fb.get() + (size_t)first * fsz, (size_t)count * fsz, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(hipMemcpyAsync(out, s.d_fb.get() + (size_t)first * fsz, (size_t)count * fsz, hipMemcpyDeviceToHost, s.stream.get()));
     HIP_TRY(slot_sync(s));
     return DG_OK;
 }
@@ -1812,9 +1473,9 @@ int dg_frame_checksums(dg_ctx *c, int slot, int first, int count, uint64_t *out)
     if (rc) return rc;
     const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
     unsigned long long *d_sum = c->d_checksums.get();      // max_batch entries, allocated at dg_create
-    hipError_t e = hipMemsetAsync(d_sum, 0, (size_t)count * 8, s.stream);
-    if (e == hipSuccess) e = launch_checksums(s.d_fb.get() + (size_t)first * fsz, fsz, count, d_sum, s.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_sum, (size_t)count * 8, hipMemcpyDeviceToHost, s.stream);
+    hipError_t e = hipMemsetAsync(d_sum, 0, (size_t)count * 8, s.stream.get());
+    if (e == hipSuccess) e = launch_checksums(s.d_fb.get() + (size_t)first * fsz, fsz, count, d_sum, s.stream.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_sum, (size_t)count * 8, hipMemcpyDeviceToHost, s.stream.get());
     if (e == hipSuccess) e = slot_sync(s);
     if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_frame_checksums: ") + hipGetErrorString(e));
     return DG_OK;
@@ -1894,11 +1555,11 @@ static int read_planes(dg_ctx *c, Slot &s, int first, int count, size_t at16, vo
     if (rc) return rc;
     const size_t px = (size_t)c->cfg.width * (size_t)c->cfg.height;
     const uint8_t *const fb = s.d_fb.get();
-    if (out16) HIP_TRY(hipMemcpyAsync(out16, fb + at16 + (size_t)first * px * 2, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream));
-    if (out8) HIP_TRY(hipMemcpyAsync(out8, fb + at8 + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream));
+    if (out16) HIP_TRY(hipMemcpyAsync(out16, fb + at16 + (size_t)first * px * 2, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream.get()));
+    if (out8) HIP_TRY(hipMemcpyAsync(out8, fb + at8 + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream.get()));
     if (raw) {
         raw->resize((size_t)count * s.per_scene.box_mobjs);
-        if (!raw->empty()) HIP_TRY(hipMemcpyAsync(raw->data(), s.per_scene.d_boxes.get() + (size_t)first * s.per_scene.box_mobjs, raw->size() * sizeof(LabelRawBox), hipMemcpyDeviceToHost, s.stream));
+        if (!raw->empty()) HIP_TRY(hipMemcpyAsync(raw->data(), s.per_scene.d_boxes.get() + (size_t)first * s.per_scene.box_mobjs, raw->size() * sizeof(LabelRawBox), hipMemcpyDeviceToHost, s.stream.get()));
     }
     HIP_TRY(slot_sync(s));
     return DG_OK;
@@ -2017,42 +1678,10 @@ int dg_readback_planes_reduced(dg_ctx *c, int slot, int first, int count, const 
     rc = make_final(c, s, s.copy_pending && s.copy.reduced ? Copy::Complete : Copy::Leave);
     if (rc) return rc;
     if ((rc = reserve_plane_readback(c, s, r))) return rc;
-    rc = issue_readback(c, s, r, s.stream);
+    rc = issue_readback(c, s, r, s.stream.get());
     if (rc) return rc;
     HIP_TRY(slot_sync(s));
     finish_readback(c, s, r);
-    return DG_OK;
-}
-
-int dg_reduce_planes_device(dg_ctx *c, int width, int height, int n_frames, const dg_plane_reduce_desc *desc,
-                            const int16_t *distance, const uint8_t *kind, const uint16_t *id, const uint8_t *cls,
-                            int16_t *o_distance, uint8_t *o_kind, uint16_t *o_id, uint8_t *o_cls) {
-    if (!c) return set_err(DG_ERR_INVALID, "null argument");
-    int rc = check_plane_reduce(width, height, n_frames, desc);
-    if (!rc) rc = check_plane_pairs(*desc, distance, kind, id, cls, o_distance, o_kind, o_id, o_cls);
-    if (rc) return rc;
-    for (const void *p : {(const void *)distance, (const void *)id, (const void *)o_distance, (const void *)o_id})
-        if (reinterpret_cast<uintptr_t>(p) % 2u) return set_err(DG_ERR_INVALID, "dg_reduce_planes_device: a 16-bit plane must be 2-byte aligned");
-    if (n_frames == 0 || !(distance || kind || id || cls)) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (!c->xstream) HIP_TRY(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
-    if (!c->ev_preduce0) HIP_TRY(hipEventCreate(&c->ev_preduce0));
-    if (!c->ev_preduce1) HIP_TRY(hipEventCreate(&c->ev_preduce1));
-    c->plane_reduce_timed = false;
-    hipError_t e = launch_plane_reduce(PlaneReduceSrc{distance, kind, id, cls}, width, height, n_frames, *desc, PlaneReduceDst{o_distance, o_kind, o_id, o_cls},
-                                       c->xstream, c->ev_preduce0, c->ev_preduce1);
-    const hipError_t es = hipStreamSynchronize(c->xstream);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_reduce_planes_device: ") + hipGetErrorString(e));
-    c->plane_reduce_timed = true;
-    return DG_OK;
-}
-
-int dg_ctx_plane_reduce_kernel_ms(dg_ctx *c, float *ms) {
-    if (!c || !ms) return set_err(DG_ERR_INVALID, "null argument");
-    if (!c->plane_reduce_timed) return set_err(DG_ERR_INVALID, "no dg_reduce_planes_device call has launched yet");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(hipEventElapsedTime(ms, c->ev_preduce0, c->ev_preduce1));
     return DG_OK;
 }
 
@@ -2075,8 +1704,8 @@ int dg_slot_label_timing(dg_ctx *c, int slot, float *tiles_ms, float *boxes_ms) 
     HIP_TRY(hipSetDevice(c->cfg.device));
     rc = make_final(c, s, Copy::Leave);
     if (rc) return rc;
-    if (tiles_ms) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_rstart, s.ev_setup));
-    if (boxes_ms) HIP_TRY(hipEventElapsedTime(boxes_ms, s.ev_setup, s.ev_raster));
+    if (tiles_ms) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_rstart.get(), s.ev_setup.get()));
+    if (boxes_ms) HIP_TRY(hipEventElapsedTime(boxes_ms, s.ev_setup.get(), s.ev_raster.get()));
     return DG_OK;
 }
 
@@ -2113,12 +1742,7 @@ int dg_slot_bundle_timing(dg_ctx *c, int slot, float *setup_ms, float *raster_ms
     if (!s.holds_bundle() || !s.has_run()) return set_err(DG_ERR_INVALID, "dg_slot_bundle_timing: the slot's last submission is not a bundle that ran");
     HIP_TRY(hipSetDevice(c->cfg.device));
     rc = make_final(c, s, Copy::Leave);
-    if (rc) return rc;
-    const bool colour = (s.bundle_what & BUNDLE_COLOUR) != 0, tiles = (s.bundle_what & (BUNDLE_DEPTH | BUNDLE_LABELS)) != 0;
-    if (setup_ms) { *setup_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(setup_ms, s.ev_start, s.ev_setup)); }
-    if (raster_ms) { *raster_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(raster_ms, s.ev_rstart, tiles ? s.ev_cend : s.ev_raster)); }
-    if (tiles_ms) { *tiles_ms = 0.0f; if (tiles) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_tiles, s.ev_raster)); }
-    return DG_OK;
+    return rc ? rc : bundle_times(s, setup_ms, raster_ms, tiles_ms);
 }
 
 int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
@@ -2177,174 +1801,6 @@ int dg_render_ego_map_views(dg_ctx *c, const dg_view *views, int n, const dg_ego
     return read_or_wait(c, 0, dg_submit_ego_map_views(c, 0, views, n, params, mask), n, out);
 }
 
-// What dg_seen_lines_device and dg_slot_seen_lines need of the ctx: the no-slot stream, their events, the uploaded scene's seg -> linedef table.
-static int ensure_seen(dg_ctx *c) {
-    if (!c->xstream) HIP_TRY(hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
-    for (hipEvent_t *ev : {&c->ev_seen0, &c->ev_seen1, &c->ev_seen2, &c->ev_seen3})
-        if (!*ev) HIP_TRY(hipEventCreate(ev));
-    if (!c->per_scene.seg_line) {
-        const Scene &sc = *c->scene;
-        std::vector<uint32_t> table(std::max<size_t>(sc.segs.size(), 4), 0u);
-        for (size_t k = 0; k < sc.segs.size(); k++) table[k] = (uint32_t)sc.segs[k].linedef;
-        DevPtr<uint32_t> d_table;
-        HIP_TRY(hip_alloc(d_table, table.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(d_table.get(), table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        c->per_scene.seg_line = std::move(d_table);
-    }
-    return DG_OK;
-}
-
-int dg_seen_lines_device(dg_ctx *c, int width, int height, int n, const uint16_t *id, const uint8_t *cls, uint32_t *seen) {
-    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
-    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
-    int rc = check_seen_lines(c->scene, width, height, n, id, cls, seen);
-    if (rc) return rc;
-    if (reinterpret_cast<uintptr_t>(id) % 2u || reinterpret_cast<uintptr_t>(seen) % 4u)
-        return set_err(DG_ERR_INVALID, "dg_seen_lines_device: the id plane must be 2-byte aligned, the seen rows 4-byte aligned");
-    const uint32_t words = seen_words((uint32_t)c->scene->linedefs.size());
-    if (n == 0 || words == 0) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if ((rc = ensure_seen(c))) return rc;
-    c->seen_timed = false; c->seen_acc_timed = false;
-    hipError_t e = hipMemsetAsync(seen, 0, (size_t)n * words * sizeof(uint32_t), c->xstream);
-    if (e == hipSuccess)
-        e = launch_seen_lines(id, cls, width, height, n, c->per_scene.seg_line.get(), (uint32_t)c->scene->segs.size(), seen, words, c->xstream, c->ev_seen0, c->ev_seen1);
-    const hipError_t es = hipStreamSynchronize(c->xstream);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_seen_lines_device: ") + hipGetErrorString(e));
-    c->seen_timed = true;
-    return DG_OK;
-}
-
-int dg_slot_seen_lines(dg_ctx *c, int slot, int first, int count, int run_len, const uint32_t *carry_in, uint32_t *upto, uint32_t *total,
-                       uint32_t *fresh, uint32_t *carry_out) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (!s.holds(BUNDLE_LABELS))
-        return set_err(DG_ERR_INVALID, s.holds_bundle() ? "dg_slot_seen_lines: the slot's bundle has no label part (DG_BUNDLE_LABELS)"
-                                                        : "dg_slot_seen_lines: the slot's last submission is not a label submission");
-    if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad frame range");
-    const size_t words = seen_words((uint32_t)c->scene->linedefs.size());
-    if ((rc = check_seen_runs((int)std::max<size_t>(words, 1), count, run_len))) return rc;
-    if (count == 0 || words == 0) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if ((rc = make_final(c, s, Copy::Leave))) return rc;
-    if ((rc = ensure_seen(c))) return rc;
-    // scratch rows: seen | upto | carry_in | carry_out (max_batch rows each), then total | fresh (max_batch entries each)
-    const size_t rows = (size_t)c->cfg.max_batch, block = rows * words;
-    if (!c->per_scene.seen_scratch) HIP_TRY(hip_alloc(c->per_scene.seen_scratch, (4 * block + 2 * rows) * sizeof(uint32_t)));
-    uint32_t *const d_seen = c->per_scene.seen_scratch.get(), *const d_upto = d_seen + block, *const d_cin = d_upto + block, *const d_cout = d_cin + block;
-    uint32_t *const d_total = d_cout + block, *const d_fresh = d_total + rows;
-    const size_t W = (size_t)c->cfg.width, H = (size_t)c->cfg.height, runs = (size_t)(count / run_len);
-    const BundleLayout L = s.layout(W, H);
-    const uint16_t *const id = reinterpret_cast<const uint16_t *>(s.d_fb.get() + L.id) + (size_t)first * W * H;
-    const uint8_t *const cls = s.d_fb.get() + L.cls + (size_t)first * W * H;
-    hipStream_t xs = c->xstream;
-    c->seen_timed = false; c->seen_acc_timed = false;
-    hipError_t e = hipMemsetAsync(d_seen, 0, (size_t)count * words * sizeof(uint32_t), xs);
-    if (e == hipSuccess && carry_in) e = hipMemcpyAsync(d_cin, carry_in, runs * words * sizeof(uint32_t), hipMemcpyHostToDevice, xs);
-    if (e == hipSuccess)
-        e = launch_seen_lines(id, cls, (int)W, (int)H, count, c->per_scene.seg_line.get(), (uint32_t)c->scene->segs.size(), d_seen, (uint32_t)words, xs, c->ev_seen0, c->ev_seen1);
-    if (e == hipSuccess)
-        e = launch_seen_accumulate(d_seen, (uint32_t)words, count, run_len, carry_in ? d_cin : nullptr, d_upto, total ? d_total : nullptr,
-                                   fresh ? d_fresh : nullptr, carry_out ? d_cout : nullptr, xs, c->ev_seen2, c->ev_seen3);
-    if (e == hipSuccess && upto) e = hipMemcpyAsync(upto, d_upto, (size_t)count * words * sizeof(uint32_t), hipMemcpyDeviceToHost, xs);
-    if (e == hipSuccess && total) e = hipMemcpyAsync(total, d_total, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, xs);
-    if (e == hipSuccess && fresh) e = hipMemcpyAsync(fresh, d_fresh, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost, xs);
-    if (e == hipSuccess && carry_out) e = hipMemcpyAsync(carry_out, d_cout, runs * words * sizeof(uint32_t), hipMemcpyDeviceToHost, xs);
-    const hipError_t es = hipStreamSynchronize(xs);       // before the caller's rows are read or reused, whatever was queued has run
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_slot_seen_lines: ") + hipGetErrorString(e));
-    c->seen_timed = true; c->seen_acc_timed = true;
-    return DG_OK;
-}
-
-int dg_ctx_seen_kernel_ms(dg_ctx *c, float *lines_ms, float *accumulate_ms) {
-    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
-    if (!c->seen_timed) return set_err(DG_ERR_INVALID, "no dg_seen_lines_device or dg_slot_seen_lines call has launched yet");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if (lines_ms) HIP_TRY(hipEventElapsedTime(lines_ms, c->ev_seen0, c->ev_seen1));
-    if (accumulate_ms) { *accumulate_ms = 0.0f; if (c->seen_acc_timed) HIP_TRY(hipEventElapsedTime(accumulate_ms, c->ev_seen2, c->ev_seen3)); }
-    return DG_OK;
-}
-
-int dg_ctx_locate_walks(dg_ctx *c, dg_walk *const *walks, int n_walks) {
-    if (!c || n_walks < 0 || (n_walks > 0 && !walks)) return set_err(DG_ERR_INVALID, "null argument");
-    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded");
-    for (int i = 0; i < n_walks; i++) {
-        if (!walks[i]) return set_err(DG_ERR_INVALID, "null walk");
-        if (walks[i]->sc != c->scene) return set_err(DG_ERR_INVALID, "a walk was created on another scene than the one uploaded");
-    }
-    // the walks still to locate, each once, and what they add up to
-    std::vector<dg_walk *> todo;
-    uint64_t probes = 0, entries = 0;
-    for (int i = 0; i < n_walks; i++) {
-        dg_walk *w = walks[i];
-        if (w->located || w->queued) continue;
-        w->queued = true;
-        todo.push_back(w);
-        probes += w->px.size();
-        entries += w->pose.size();
-    }
-    for (dg_walk *w : todo) w->queued = false;
-    if (todo.empty()) return DG_OK;
-    if (probes > WALK_MAX_PROBES) return set_err(DG_ERR_CAPACITY, "more than 1 << 26 probes in one call");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const Scene &sc = *c->scene;
-    if (!c->wstream) HIP_TRY(hipStreamCreateWithFlags(&c->wstream, hipStreamNonBlocking));
-    if (!c->per_scene.walk_tables) {
-        TablePack t;
-        const size_t nodes = t.add(sc.walk_nodes), leaves = t.add(sc.walk_leaves);
-        DevPtr<uint8_t> d_tables;
-        const hipError_t e = t.upload(d_tables);
-        if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("walk tables: ") + hipGetErrorString(e));
-        c->per_scene.walk_tables = std::move(d_tables);
-        c->per_scene.walk_nodes = t.at<WalkNode>(nodes);
-        c->per_scene.walk_leaves = t.at<WalkLeaf>(leaves);
-    }
-    // one slab: the probes of all walks, concatenated, go up in one copy; the floors come back in one
-    const WalkLayout L = walk_layout((size_t)probes, (size_t)entries);
-    std::vector<uint8_t> staged(L.upload);
-    float *hx = reinterpret_cast<float *>(staged.data() + L.x), *hy = reinterpret_cast<float *>(staged.data() + L.y);
-    uint8_t *hfirst = staged.data() + L.first;
-    uint32_t *heot = reinterpret_cast<uint32_t *>(staged.data() + L.end_of_tic);
-    size_t pi = 0, ei = 0;
-    for (const dg_walk *w : todo) {
-        const size_t np = w->px.size(), ne = w->pose.size();
-        std::memcpy(hx + pi, w->px.data(), np * 4);
-        std::memcpy(hy + pi, w->py.data(), np * 4);
-        hfirst[pi] = 1;
-        for (size_t t = 0; t < ne; t++) heot[ei + t] = (uint32_t)pi + w->end_of_tic[t];
-        pi += np; ei += ne;
-    }
-    DevPtr<uint8_t> d_slab;
-    HIP_TRY(hip_alloc(d_slab, L.total));
-    uint8_t *const d = d_slab.get();
-    WalkParams P{};
-    P.nodes = c->per_scene.walk_nodes; P.leaves = c->per_scene.walk_leaves;
-    P.x = reinterpret_cast<const float *>(d + L.x); P.y = reinterpret_cast<const float *>(d + L.y);
-    P.first = d + L.first; P.end_of_tic = reinterpret_cast<const uint32_t *>(d + L.end_of_tic);
-    P.value = reinterpret_cast<float *>(d + L.value); P.last = reinterpret_cast<uint32_t *>(d + L.last);
-    P.sums = reinterpret_cast<uint32_t *>(d + L.sums); P.floors = reinterpret_cast<float *>(d + L.floors);
-    P.root = (int32_t)sc.walk_nodes.size() - 1;
-    P.n_probes = (uint32_t)probes; P.n_blocks = (uint32_t)walk_scan_blocks((size_t)probes); P.n_entries = entries;
-    std::vector<float> floors((size_t)entries);
-    hipError_t e = hipMemcpyAsync(d, staged.data(), L.upload, hipMemcpyHostToDevice, c->wstream);
-    if (e == hipSuccess) e = launch_walk_locate(P, c->wstream);
-    if (e == hipSuccess) e = hipMemcpyAsync(floors.data(), d + L.floors, (size_t)entries * 4, hipMemcpyDeviceToHost, c->wstream);
-    const hipError_t es = hipStreamSynchronize(c->wstream);     // before d_slab and the staging go, whatever was queued has run
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_ctx_locate_walks: ") + hipGetErrorString(e));
-    ei = 0;
-    for (dg_walk *w : todo) {
-        w->floors.assign(floors.begin() + (ptrdiff_t)ei, floors.begin() + (ptrdiff_t)(ei + w->pose.size()));
-        w->located = true;
-        ei += w->pose.size();
-    }
-    return DG_OK;
-}
-
 int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
@@ -2357,18 +1813,14 @@ int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
     std::memset(out, 0, sizeof *out);
     out->front_end = s.front_end;
     if (s.front_end == DG_FE_BUNDLE) {                    // setup_ms / raster_ms: the colour kernels (0 without colour); total_ms: first kernel's start .. last kernel's end
-        const bool colour = (s.bundle_what & BUNDLE_COLOUR) != 0, tiles = (s.bundle_what & (BUNDLE_DEPTH | BUNDLE_LABELS)) != 0;
-        if (colour) {
-            HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
-            HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, tiles ? s.ev_cend : s.ev_raster));
-        }
-        HIP_TRY(hipEventElapsedTime(&out->total_ms, colour ? s.ev_start : s.ev_tiles, s.ev_raster));
+        if ((rc = bundle_times(s, &out->setup_ms, &out->raster_ms, nullptr))) return rc;
+        HIP_TRY(hipEventElapsedTime(&out->total_ms, (s.bundle_what & BUNDLE_COLOUR) ? s.ev_start.get() : s.ev_tiles.get(), s.ev_raster.get()));
     } else if (s.timed_front_half()) {
-        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
-        HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start, s.ev_setup));
-        HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start, s.ev_raster));
+        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart.get(), s.ev_raster.get()));
+        HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start.get(), s.ev_setup.get()));
+        HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start.get(), s.ev_raster.get()));
     } else {
-        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart, s.ev_raster));
+        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart.get(), s.ev_raster.get()));
         out->total_ms = out->raster_ms;
     }
     out->n_spans = s.n_spans; out->n_frames = (uint64_t)s.n_frames; out->covered_pixels = s.covered;
