@@ -289,10 +289,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     s.keep_states(states, n);
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (n >= 64 && !states && c->host_samples++ > 0) {        // DG_FE_AUTO's measurement of the host side (the first batch pays for cold caches: not counted)
-        const double v = (double)s.host_ms / n;
-        c->ema_host = c->host_samples == 2 ? v : 0.75 * c->ema_host + 0.25 * v;
-    }
+    if (n >= 64 && !states) c->fe_auto.host_batch((double)s.host_ms, n);      // DG_FE_AUTO's measurement of the host side
     HIP_TRY(hipMemcpyAsync(s.d_fe.get(), s.h_fe.get(), L.total, hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
@@ -366,11 +363,9 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
     return DG_OK;
 }
 
-// DG_FE_AUTO: should this batch's per-seg half run on the GPU?  The host does it for free as long as it is done before the GPU has
-// finished the batches queued ahead (its time hides under theirs); the GPU pays for it (dg_fs_*: ~0.1 ms per 1 000 frames) but needs
-// no host time.  So: when nothing is in flight the host's time would be exposed in full — the GPU does it, unless the batch is so small
-// that the kernels' fixed latency exceeds the host's few microseconds per frame; in a filled pipeline the GPU does it when the host has
-// been measured to be the slower of the two (few host threads, small frames).  Small batches (< 64 frames) always go to the host walker.
+// DG_FE_AUTO: should this batch's per-seg half run on the GPU?  The rule and what it has measured are fe_auto.hpp's; here: what is forced,
+// the measuring, and what is in flight.  Small batches (< 64 frames: the kernels' fixed latency exceeds the host's few microseconds per
+// frame) and prepared ones always go to the host walker.
 void harvest_gpu_time(dg_ctx *c, Slot &s);
 // First guess of the host walker's speed without spending a whole batch on it: a dozen of the batch's views on the calling thread
 // (four untimed ones first), scaled by the pool size.  Whole batches that do go through the host walker refine it (build_batch_fe).
@@ -383,25 +378,15 @@ void calibrate_host(dg_ctx *c, const dg_view *views, int n) {
     const auto t0 = std::chrono::steady_clock::now();
     for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx); }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->ema_host = ms / timed / std::max(1, c->n_threads) * 1.25;     // (the pool does not scale perfectly)
-    c->host_samples = std::max(c->host_samples, 2);
+    c->fe_auto.calibrated(ms, timed, c->n_threads);
 }
 bool choose_fs(dg_ctx *c, const dg_view *views, int n) {
     if (c->fs_forced) return true;
     if (n < 64 || c->preparing) return false;
-    if (c->ema_host < 0.0) calibrate_host(c, views, n);
+    if (c->fe_auto.ema_host < 0.0) calibrate_host(c, views, n);
     bool in_flight = false;
     for (Slot &s : c->slots) { harvest_gpu_time(c, s); in_flight |= s.phase == Slot::Phase::Queued; }
-    if (!in_flight) return true;
-    // No seg-walk batch timed yet: the GPU keeps the per-seg half until one has been (it costs the GPU ~0.1 ms per 1 000 frames; a batch on a
-    // host that turns out to be the slower side costs the pipeline a millisecond).  From then on: whoever is the slower side of the pipeline.
-    bool fs = c->ema_gpu_fs < 0.0 ? true : c->ema_host > c->ema_gpu_fs;
-    // time the other side again now and then (the host's speed depends on who else uses the CPUs, the first seg-walk samples may have been
-    // taken on a cold GPU); the host rarely when it was far behind
-    if (fs && ++c->since_probe >= (c->ema_gpu_fs > 0.0 && c->ema_host > 2.0 * c->ema_gpu_fs ? 256 : 32)) fs = false;
-    else if (!fs && ++c->since_fs_probe >= 32) fs = true;
-    if (!fs) c->since_probe = 0; else c->since_fs_probe = 0;
-    return fs;
+    return c->fe_auto.seg_walk_next(in_flight);
 }
 
 // dg_light_rows / dg_mobj_rows complete the rows the seg walk reads (Rows: LfxRows / MfxRows, whose fields carry the same names).  R
@@ -913,10 +898,7 @@ void harvest_gpu_time(dg_ctx *c, Slot &s) {
         ms = std::max(fe_ms, r_ms);                        // (they overlap with the neighbouring batches': the longer one sets the pace)
         if (!(ms > 0.0f)) return;
     } else if (hipEventElapsedTime(&ms, s.ev_start.get(), s.ev_raster.get()) != hipSuccess || !(ms > 0.0f)) return;
-    if (c->gpu_samples[s.seg_walk() ? 1 : 0]++ == 0) return;  // (the first batch of a mode: cold caches, code not yet resident, clocks down — a seg walk judged by it alone was never tried again)
-    double &ema = s.seg_walk() ? c->ema_gpu_fs : c->ema_gpu_dev;
-    const double v = (double)ms / s.n_frames;
-    ema = ema < 0.0 ? v : 0.75 * ema + 0.25 * v;
+    c->fe_auto.gpu_batch(s.seg_walk(), (double)ms, s.n_frames);
 }
 
 }  // namespace

@@ -13,6 +13,7 @@
 #include "../../include/doomgpu.h"
 #include "api_common.hpp"
 #include "binner.hpp"
+#include "fe_auto.hpp"
 #include "fe_kernels.hpp"
 #include "frontend.hpp"
 #include "fs_kernels.hpp"
@@ -253,13 +254,7 @@ struct dg_ctx {
     bool fs_rows_dirty = true;          // the seg walk's candidate rows may hold entries (fresh allocation, or a launch that failed half way)
     bool preparing = false;             // inside dg_prepare_views: the records are built once and replayed — host time is not in the loop
     bool fs_forced = false;             // DG_FE_DEVICE_SEGS: always; DG_FE_AUTO: when it is the faster way for the batch at hand (choose_fs)
-    // what DG_FE_AUTO decides by (running means over batches of >= 64 frames, ms per frame): the host's per-seg half, and the whole of the
-    // GPU work of a batch with / without the seg walk in it
-    double ema_host = -1.0, ema_gpu_dev = -1.0, ema_gpu_fs = -1.0;
-    int host_samples = 0;               // batches the host walker was timed on (the first one pays for cold caches and arena growth: not counted)
-    int since_probe = 0;                // seg-walk batches since the host walker was last timed (it is timed again every 32 batches)
-    int since_fs_probe = 0;             // host-walker batches since the seg walk was last timed (likewise)
-    int gpu_samples[2] = {0, 0};        // finished batches seen per mode (host per-seg half / seg walk): the first of each runs on cold caches and clocks, not counted
+    FeAuto fe_auto;                     // what DG_FE_AUTO has measured and decides by
     DevPtr<uint8_t> d_fs_scene;
     // the scene's effects as of dg_upload_scene (every front end draws with this copy), and for the seg walk the device tables of each
     // effect that is on (only while the seg walk is uploaded)

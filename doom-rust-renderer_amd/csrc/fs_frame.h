@@ -17,7 +17,8 @@
 // A frame the reference would panic on, or one that exceeds a capacity below, is flagged (FE_OVF_SEGS) and redone by the host.
 //
 // The phases are plain functions of (lane, shared state): inside a phase the 64 lanes touch disjoint data (or use atomics), between
-// phases stands a barrier.  tests/emul runs them on the CPU — lanes one after another — against the host walker's records.
+// phases stands a barrier.  Their order and the barriers are stated once, at the end of this file (FS_FRAME_PHASES): the kernels expand it
+// for their own lane, tests/emul runs it on the CPU — lanes one after another — against the host walker's records.
 #pragma once
 #include "../../include/doomgpu.h"
 #include "fe_core.h"
@@ -617,3 +618,35 @@ DG_HD void fs_ph_header(const FsParams &P, FsShared &S, int f) {
 }
 
 }  // namespace dg
+
+// ---- the frame's phases in order: the one statement of what dg_fs_frame, dg_wfx_frame and tests/emul run -----------------------------
+// What runs between two barriers is one step.  Expanded where P, S, f and fx are in scope (fx: FsNoFx or FsFx, what fs_seg_lane was given);
+// STEP(...) gets the statements of a step, written for `lane` and that lane's FsSpriteTmp `T`, and supplies both:
+//   a kernel        runs them for its own lane, then the workgroup's barrier (fs_kernels.hpp FS_KERNEL_STEP);
+//   tests/emul      runs them for lanes 0 .. FS_LANES - 1 in turn, one of the interleavings a barrier allows, and needs no barrier.
+// LAST(...) is the final step: no barrier follows it.  n_before is read between two steps, by every lane alike.
+#define FS_FRAME_PHASES(STEP, LAST)                                                     \
+    STEP(if (lane == 0) fs_ph_init(S))                                                  \
+    STEP(fs_ph_cand_count(P, S, f, lane))                                               \
+    STEP(fs_ph_block_sums(S, lane))                                                     \
+    STEP(fs_ph_cand_stage(P, S, f, lane); fs_ph_first_clear(P, S, lane))                \
+    STEP(fs_ph_solids(P, S, f, lane))                                                   \
+    STEP(fs_ph_keep(P, S, f, lane))                                                     \
+    STEP(fs_ph_kept_count(P, S, f, lane))                                               \
+    STEP(fs_ph_block_sums(S, lane))                                                     \
+    STEP(fs_ph_kept_place(P, S, f, lane))                                               \
+    STEP(fs_ph_emit(P, S, f, lane, fx))                                                 \
+    for (uint32_t base = 0; base < P.n_mobjs; base += FS_LANES) {                       \
+        const uint32_t n_before = S.n_sprites;                                          \
+        STEP(fs_ph_mobj(P, S, f, base, lane, T))                                        \
+        STEP(fs_ph_block_sums(S, lane))                                                 \
+        STEP(fs_ph_mobj_emit(P, S, f, lane, T, n_before))                               \
+    }                                                                                   \
+    STEP(fs_ph_behind(P, S, f, lane); fs_ph_sprite_order(S, lane))                      \
+    STEP(fs_ph_masked_when(S, lane))                                                    \
+    STEP(fs_ph_seq(P, S, f, lane); fs_ph_bin_clear(P, S, lane))                         \
+    STEP(fs_ph_bin_mark(P, S, lane))                                                    \
+    STEP(fs_ph_bin_count(P, S, lane))                                                   \
+    STEP(if (lane == 0) fs_ph_bin_prefix(P, S, f))                                      \
+    STEP(fs_ph_bin_fill(P, S, f, lane))                                                 \
+    LAST(fs_ph_clean(P, f, lane); if (lane == 0) fs_ph_header(P, S, f))

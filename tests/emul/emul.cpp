@@ -144,6 +144,7 @@ int emul_set_mobj_state(void *s, int mobj, const char *sprite, uint8_t frame, in
     return 0;
 }
 
+int emul_set_wall_effects(void *s, uint32_t flags) { return ((Scene *)s)->set_wall_effects(flags, g_err); }
 int emul_sprite_frame(void *s, const char *sprite, uint8_t frame) { return ((Scene *)s)->find_or_add_sprite_frame(sprite, frame, g_err); }
 
 static int emul_render_impl(void *scene, int W, int H, const dg_view *view_in, const dg_view_state *state, uint8_t *rgb, uint64_t *stats);
@@ -533,6 +534,18 @@ int emul_frame_parts(void *scene, int W, int H, const dg_view *view_in, uint32_t
     return n;
 }
 
+// The same records whole (sizeof(FePart) bytes each, the wall and plane constants included), drawn with the scene's wall effects.
+int emul_frame_part_records(void *scene, int W, int H, const dg_view *view_in, uint8_t *out, int cap) {
+    const Scene &sc = *(const Scene *)scene;
+    dg_view view = *view_in;
+    fill_view_trig(view);
+    static thread_local FrameArena arena;
+    if (build_frame_parts(sc, W, H, view, arena, g_err, nullptr, &sc.fx)) return -1;
+    if (arena.parts.size() > (size_t)cap) return -2;
+    std::memcpy(out, arena.parts.data(), arena.parts.size() * sizeof(FePart));
+    return (int)arena.parts.size();
+}
+
 // The host list builder's output for one frame, flattened for Python (the layout of include/doomgpu.h dg_frame_lists):
 //   renders: 4 ints each = start_x, end_x, first_column, n_columns;  columns: 5 int16 each;  visplanes: 4 ints = left, right, first_entry, flat;
 //   plane_tb: int16 pairs;  order: 2 uints.  counts[5] = how many of each.  Returns 0, or -2 when a buffer is too small.
@@ -556,8 +569,9 @@ int emul_frame_lists(void *scene, int W, int H, const dg_view *view_in, int32_t 
 }
 
 // ---- the device seg walk (fs_frame.h) on the CPU ------------------------------------------------------------------------------------
-// Runs the bodies of dg_fs_segs / dg_fs_frame for one frame — the "lanes" of every phase one after another, a barrier
-// between phases — and compares what they produce with the host walker's parts mode (build_frame_parts), record by record:
+// Runs the bodies of dg_fs_segs / dg_fs_frame for one frame — fs_frame.h's phase sequence, the "lanes" of every step one after another —
+// with the scene's wall effects when they are on (emul_set_wall_effects: the dg_wfx_ pair), and compares what they produce with the host
+// walker's parts mode (build_frame_parts), record by record:
 // every FePart byte for byte, every FeSprite (but its behind_off: the row stride differs), the behind bits, the sky slot table, both
 // column-bin tables.  Returns 0 and stats = [parts, sprites, sky slots, flags, capacities exceeded, candidates], 1 when the host walker
 // itself refuses the frame (then the device walk must have flagged it), 2 when the device walk gave the frame up because it exceeds a
@@ -571,7 +585,7 @@ extern "C" int emul_fs_frame(void *scene, int W, int H, const dg_view *view_in, 
     dg_view view = *view_in;
     fill_view_trig(view);
     static thread_local FrameArena arena;
-    const int host_rc = build_frame_parts(sc, W, H, view, arena, g_err);
+    const int host_rc = build_frame_parts(sc, W, H, view, arena, g_err, nullptr, &sc.fx);
     FrameConsts fk = make_consts(W, H);
     const uint32_t nb = (uint32_t)(W + FE_BIN_W - 1) / FE_BIN_W;
     std::vector<int16_t> lights(sc.sectors.size());
@@ -604,41 +618,18 @@ extern "C" int emul_fs_frame(void *scene, int W, int H, const dg_view *view_in, 
     P.fframes = ffr.data(); P.parts = parts.data(); P.sprites = sprites.data(); P.behind = behind.data(); P.sky_parts = sky_parts.data();
     P.bin_off = bin_off.data(); P.bin_parts = bin_parts.data(); P.sbin_off = sbin_off.data(); P.sbin_sprites = sbin_sprites.data();
 
-    for (uint32_t s = 0; s < P.n_segs; s++) if (P.seg_leaf[s] != 0xffffu) fs_seg_lane(P, 0, s);             // dg_fs_segs
     uint32_t n_cand = 0;                                                                                   // process_sidedef calls that reach their column loop
-    for (uint32_t w : occ) n_cand += (uint32_t)__builtin_popcount(w);
-    static thread_local FsShared S;                                                                        // dg_fs_frame
-    static thread_local FsSpriteTmp T[FS_LANES];
-#define LANES(body) for (int lane = 0; lane < FS_LANES; lane++) { body; }
-    fs_ph_init(S);
-    LANES(fs_ph_cand_count(P, S, 0, lane))
-    LANES(fs_ph_block_sums(S, lane))
-    LANES(fs_ph_cand_stage(P, S, 0, lane))
-    LANES(fs_ph_first_clear(P, S, lane))
-    LANES(fs_ph_solids(P, S, 0, lane))
-    LANES(fs_ph_keep(P, S, 0, lane))
-    LANES(fs_ph_kept_count(P, S, 0, lane))
-    LANES(fs_ph_block_sums(S, lane))
-    LANES(fs_ph_kept_place(P, S, 0, lane))
-    LANES(fs_ph_emit(P, S, 0, lane))
-    for (uint32_t base = 0; base < P.n_mobjs; base += FS_LANES) {
-        const uint32_t n_before = S.n_sprites;
-        LANES(fs_ph_mobj(P, S, 0, base, lane, T[lane]))
-        LANES(fs_ph_block_sums(S, lane))
-        LANES(fs_ph_mobj_emit(P, S, 0, lane, T[lane], n_before))
-    }
-    LANES(fs_ph_behind(P, S, 0, lane))
-    LANES(fs_ph_sprite_order(S, lane))
-    LANES(fs_ph_masked_when(S, lane))
-    LANES(fs_ph_seq(P, S, 0, lane))
-    LANES(fs_ph_bin_clear(P, S, lane))
-    LANES(fs_ph_bin_mark(P, S, lane))
-    LANES(fs_ph_bin_count(P, S, lane))
-    fs_ph_bin_prefix(P, S, 0);
-    LANES(fs_ph_bin_fill(P, S, 0, lane))
-    LANES(fs_ph_clean(P, 0, lane))
-    fs_ph_header(P, S, 0);
-#undef LANES
+    static thread_local FsShared S;
+    static thread_local FsSpriteTmp lane_tmp[FS_LANES];
+    const int f = 0;
+    const auto walk = [&](const auto &fx) {                                                                // fx: what both kernels of the pair are given
+        for (uint32_t s = 0; s < P.n_segs; s++) if (P.seg_leaf[s] != 0xffffu) fs_seg_lane(P, f, s, fx);    // dg_fs_segs / dg_wfx_segs
+        for (uint32_t w : occ) n_cand += (uint32_t)__builtin_popcount(w);
+#define EMUL_STEP(...) for (int lane = 0; lane < FS_LANES; lane++) { FsSpriteTmp &T = lane_tmp[lane]; (void)T; __VA_ARGS__; }
+        FS_FRAME_PHASES(EMUL_STEP, EMUL_STEP)                                                              // dg_fs_frame / dg_wfx_frame
+#undef EMUL_STEP
+    };
+    if (sc.fx.wall.on()) walk(FsFx{sc.fx.wall.seg.data(), sc.fx.wall.lists.data()}); else walk(FsNoFx());
     for (uint32_t w : occ) if (w) { g_err = "dg_fs_frame left an occupancy row dirty"; return -3; }
     const FeFrame &ff = ffr[0];
     if (stats) { stats[0] = ff.n_parts; stats[1] = ff.n_sprites; stats[2] = ff.n_sky_slots; stats[3] = flags[0]; stats[4] = 0; stats[5] = n_cand; }
@@ -696,7 +687,7 @@ extern "C" int emul_fs_kept_counts(const uint32_t *survivors, const uint32_t *sk
     std::vector<uint2> lite(1, uint2{0xdeadbeefu, 0xdeadbeefu});
     P.cl_rows = cl.data(); P.keep_rows = keep.data(); P.occ = occ.data(); P.lite = lite.data();
     static thread_local FsShared S;
-    fs_ph_init(S);
+    S = FsShared{};                                                        // (what phase 0 resets, and the rest)
     S.cl_big = 1;
     S.n_cl = total;
     for (uint32_t l = 0, k = 0; l < (uint32_t)FS_LANES; l++) {

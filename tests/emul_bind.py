@@ -30,10 +30,12 @@ def lib():
         L.emul_render_state.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                         ctypes.c_uint32, ctypes.c_void_p]
         L.emul_fs_frame.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(ctypes.c_uint64)]
+        L.emul_frame_part_records.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.c_int]
         L.emul_fs_no_cl_rows.argtypes = [ctypes.c_int]
         L.emul_fs_no_cl_rows.restype = None
         L.emul_fs_kept_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.emul_sprite_frame.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint8]
+        L.emul_set_wall_effects.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.emul_set_sector_light.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int16]
         L.emul_set_mobj_state.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_int]
         _lib = L
@@ -60,6 +62,11 @@ class EmulScene:
 
     def set_sector_light(self, sector, light):
         lib().emul_set_sector_light(self._h, sector, light)
+
+    def set_wall_effects(self, flags):
+        """Scene::set_wall_effects (dg_scene_set_wall_effects): fs_frame then runs the seg walk's wall-effect variant."""
+        if lib().emul_set_wall_effects(self._h, flags):
+            raise RuntimeError(lib().emul_last_error().decode())
 
     def set_mobj_state(self, mobj, sprite, frame=0, full_bright=False):
         if lib().emul_set_mobj_state(self._h, mobj, sprite.encode() if sprite else None, frame, int(full_bright)):
@@ -116,6 +123,16 @@ class EmulScene:
         if rc < 0:
             raise RuntimeError(f"emul_fs_frame rc {rc}: {lib().emul_last_error().decode()}")
         return rc, list(st)
+
+    def frame_parts(self, W, H, rec, timestamp=0.0):
+        """The host walker's FePart records of one view, whole (128 bytes each), with the scene's wall effects."""
+        v = DgView(float(rec[0]), float(rec[1]), float(rec[2]), float(rec[7]), float(rec[3]), float(rec[4]), float(rec[5]), float(rec[6]),
+                   float(timestamp), 1)
+        out = np.zeros(128 * 4096, dtype=np.uint8)
+        n = lib().emul_frame_part_records(self._h, W, H, ctypes.byref(v), out.ctypes.data, 4096)
+        if n < 0:
+            raise RuntimeError(f"emul_frame_part_records rc {n}: {lib().emul_last_error().decode()}")
+        return out[:128 * n].tobytes()
 
     def render_fe(self, W, H, rec, timestamp=0.0):
         """Same frame through the device column walk's bodies (fe_core.h) on the CPU.  stats = [spans, parts, sprites, overflow
