@@ -15,7 +15,6 @@ namespace dg {
 
 namespace {
 
-const float kPi = 3.14159265358979323846f;
 const float kEye = 41.0f;  // PLAYER_EYE_HEIGHT, src/renderer/constants.rs:3
 
 // (V2, Seg2, clip_to_viewport, project, ... : fs_core.h — shared with the GPU's per-seg kernels)
@@ -168,6 +167,7 @@ struct Walker {
         if (status == DG_OK) { status = kPartsUnsupported; err = m; }
         return status;
     }
+    int fail_fs(int32_t code) { return code == FS_FAIL_PARTS ? fail_parts(fs_message(code)) : fail(fs_message(code)); }   // an FS_* failure of fs_core.h
 
     void occlude(int x) {                                           // segs.rs:113-117
         A.hor_ocl[(size_t)x] = 1;
@@ -196,12 +196,17 @@ struct Walker {
         p.used = false;
     }
 
-    struct Side {                                                   // SideDefDetails, segs.rs:42-51
-        const Clipped *cl;
-        int16_t offset_x, floor_h, ceil_h, light;
-        int floor_flat, ceil_flat;
-    };
     struct Flags { bool only_occlusions, lower, upper, draw_ceiling, two_sided_mid; };   // segs.rs:53-59
+
+    static Rec make_rec(const Seg2 &line, uint8_t state) {          // what every record starts from
+        Rec r;
+        std::memset(&r, 0, sizeof r);
+        r.line = line;
+        r.min_x = std::fmin(line.a.x, line.b.x); r.max_x = std::fmax(line.a.x, line.b.x);
+        r.state = state;
+        r.out_index = -1;
+        return r;
+    }
 
     void emit_draw(Rec &r) {
         if (r.out_index < 0) {
@@ -219,79 +224,53 @@ struct Walker {
         A.order.push_back(dg_draw_cmd{0u, (uint32_t)r.out_index});
     }
 
-    // Segs::process_sidedef, segs.rs:121-350
-    void process_sidedef(const FsSegOut &so, const FsCall &call) {
-        const int W = k.W, H = k.H;
-        const Clipped *cl = &so.cl;
-        const Side s{cl, so.seg_offset, so.floor_h, so.ceil_h, so.light, so.floor_flat, so.ceil_flat};
-        const float bottom_height = call.bottom_height, top_height = call.top_height;
-        const int32_t offset_y = call.offset_y;
-        const int tex = call.tex;
+    // Segs::process_sidedef, segs.rs:121-350.  s: the seg's SideDefDetails (segs.rs:42-51).  The geometry and the reference's panics are
+    // fs_core.h's in both modes: parts mode takes the whole record (fs_part), list mode the part of it that comes before the fill.
+    void process_sidedef(const FsSegOut &s, const FsCall &call) {
+        const int H = k.H;
         const Flags f{(call.flags & FEP_ONLY_OCCL) != 0, (call.flags & FEP_LOWER) != 0, (call.flags & FEP_UPPER) != 0, (call.flags & FEP_DRAW_CEILING) != 0,
                       (call.flags & FEP_TWO_SIDED_MID) != 0};
+        FePart p;
+        FsPartGeom g{};
+        if (parts_mode) std::memset(&p, 0, sizeof p);
+        const int32_t st = parts_mode ? fs_part(k, s, call, sc.fs_bitmaps.data(), sc.flat_sky.data(), view.floor_height, p) : fs_part_geom(k, s, call, g);
+        if (st == FS_SKIP) return;
+        if (st != FS_OK) { fail_fs(st); return; }
+        const int sx = parts_mode ? p.sx : g.bot.sx, ex = parts_mode ? p.ex : g.bot.ex;
+        // Columns that an earlier full-height solid part spans are horizontally occluded whatever that part's own
+        // visibility was (segs.rs:341-344 runs for every column of the part).  A part lying entirely inside them can
+        // neither draw, clip, add a visplane entry nor occlude anything new (segs.rs:211,337-341): it is dropped here.
+        if (solid_cols.covers(sx, ex)) return;
+        if (fs_part_is_solid(call.flags) && sx <= ex) solid_cols.add(sx, ex);
+        Rec r = make_rec(s.cl.line, f.two_sided_mid ? ST_TWOSIDED : ST_SOLID);
         if (parts_mode) {                                            // the per-column half runs on the GPU: record the part
-            FePart p;
-            std::memset(&p, 0, sizeof p);
-            const int32_t st = fs_part(k, so, call, sc.fs_bitmaps.data(), sc.flat_sky.data(), view.floor_height, p);
-            if (st == FS_SKIP) return;
-            if (st == FS_FAIL_PARTS) { fail_parts(fs_message(st)); return; }
-            if (st != FS_OK) { fail(fs_message(st)); return; }
-            // Columns that an earlier full-height solid part spans are horizontally occluded whatever that part's own
-            // visibility was (segs.rs:341-344 runs for every column of the part).  A part lying entirely inside them can
-            // neither draw, clip, add a visplane entry nor occlude anything new (segs.rs:211,337-341): it is dropped here.
-            if (solid_cols.covers(p.sx, p.ex)) return;
-            if (fs_part_is_solid(p.flags) && p.sx <= p.ex) solid_cols.add(p.sx, p.ex);
             if (fs_part_wants_sky_slot(p.flags)) {
                 p.sky_slot = (int32_t)A.n_sky_slots++;
                 A.sky_parts.push_back((uint32_t)A.parts.size());
             }
             if (A.parts.size() >= 65535) { fail_parts("more than 65535 wall records in a frame"); return; }
             A.parts.push_back(p);
-            Rec r;
-            std::memset(&r, 0, sizeof r);
-            r.line = cl->line;
-            r.min_x = std::fmin(r.line.a.x, r.line.b.x); r.max_x = std::fmax(r.line.a.x, r.line.b.x);
-            r.state = f.two_sided_mid ? ST_TWOSIDED : ST_SOLID;
-            r.out_index = -1;
             recs.push_back(r);
             return;
         }
-        ScreenLine bot = project(k, s.cl->line, bottom_height);
-        ScreenLine top = project(k, s.cl->line, top_height);
-        if (tex == TEX_UNKNOWN) { fail("Unknown texture (Textures::get panics, textures.rs:158)"); return; }
-        if (bot.sx != top.sx || bot.ex != top.ex) { fail("Wall start not vertical (segs.rs:140-145)"); return; }
-        if (wrap_i16(bot.sx) == wrap_i16(bot.ex) || wrap_i16(top.sx) == wrap_i16(top.ex)) return;
-        if (bot.sx < 0 || bot.sx >= W || bot.ex < 0 || bot.ex >= W) { fail("Invalid line x (segs.rs:103-111)"); return; }
-
-        float bottom_delta = ((float)bot.sy - (float)bot.ey) / ((float)bot.sx - (float)bot.ex);
-        float top_delta = ((float)top.sy - (float)top.ey) / ((float)top.sx - (float)top.ex);
-
+        const ScreenLine &bot = g.bot, &top = g.top;
+        const float bottom_delta = g.bottom_delta, top_delta = g.top_delta;
+        const int tex = call.tex;
+        const bool full_height = !f.lower && !f.upper && !f.only_occlusions;
+        const bool planes_here = !f.two_sided_mid && (full_height || f.only_occlusions);
         PlaneBuilder pb, pt;
-        bool full_height = !f.lower && !f.upper && !f.only_occlusions;
 
-        Rec r;
-        r.line = s.cl->line;
-        r.start_offset = s.cl->start_offset;
-        r.bottom_height = bottom_height; r.top_height = top_height;
-        r.min_x = std::fmin(r.line.a.x, r.line.b.x); r.max_x = std::fmax(r.line.a.x, r.line.b.x);
+        r.start_offset = s.cl.start_offset;
+        r.bottom_height = call.bottom_height; r.top_height = call.top_height;
         r.start_x = bot.sx; r.end_x = bot.ex; r.bitmap = tex;
-        r.first_col = (uint32_t)A.columns.size(); r.n_cols = 0; r.out_index = -1;
+        r.first_col = (uint32_t)A.columns.size();
         r.light = s.light;
-        r.offset_x = (int16_t)wrap_i16(f32_as_i16(so.sd_xoff) + s.offset_x);
-        r.offset_y = (int16_t)wrap_i16(f32_as_i16(so.sd_yoff) + wrap_i16(offset_y));
-        r.state = f.two_sided_mid ? ST_TWOSIDED : ST_SOLID;
+        fs_part_offsets(s, call, r.offset_x, r.offset_y);
         r.ext_bottom = f.lower || (!f.two_sided_mid && full_height);
         r.ext_top = f.upper || (!f.two_sided_mid && full_height);
         r.draw_ceiling = f.draw_ceiling;
-        r.sort_key = 0;
         r.owner = cur_owner;
 
-        const bool planes_here = !f.two_sided_mid && (full_height || f.only_occlusions);
-        // Columns that an earlier full-height solid part spans are horizontally occluded whatever that part's own
-        // visibility was (segs.rs:341-344 runs for every column of the part).  A part lying entirely inside them can
-        // neither draw, clip, add a visplane entry nor occlude anything new (segs.rs:211,337-341): it is dropped here.
-        if (solid_cols.covers(bot.sx, bot.ex)) return;
-        if (!f.two_sided_mid && full_height && bot.sx <= bot.ex) solid_cols.add(bot.sx, bot.ex);
         const int16_t hm1 = (int16_t)(H - 1);
         for (int x = bot.sx; x <= bot.ex; x++) {
             if (!A.hor_ocl[(size_t)x]) {
@@ -362,7 +341,7 @@ struct Walker {
         const int16_t light = sg.front_sector >= 0 ? sector_light(sg.front_sector) : (int16_t)0;
         const int32_t st = fs_seg(k, sg, sc.fs_sectors.data(), sc.fs_anims.data(), ppos, view.cos_na, view.sin_na, player_height, view.timestamp, light, so);
         if (st == FS_SKIP) return;
-        if (st != FS_OK) { fail(fs_message(st)); return; }
+        if (st != FS_OK) { fail_fs(st); return; }
         for (int i = 0; i < so.n_calls && !status; i++)
             if ((so.call_mask >> i) & 1u) process_sidedef(so, so.call[i]);
     }
@@ -431,39 +410,52 @@ struct Walker {
         }
     }
 
-    static bool behind(const Rec &r, V2 v) {                         // is_behind_vertex, bitmap_render.rs:137-165
-        if (r.min_x > v.x) return true;
-        if (r.max_x > v.x && !left_of(v, r.line)) return true;
-        return false;
+    static bool behind(const Rec &r, V2 v) { return fs_behind(r.line, r.min_x, r.max_x, v); }   // is_behind_vertex, bitmap_render.rs:137-165
+
+    // The sprite / masked-wall interleave (map_objects.rs:218-241) and draw_remaining_segs after it (segs.rs:593-597): in front of each
+    // sprite of mo (far to near) go the two-sided middles behind its centre that are not drawn yet, after the last sprite the rest.
+    // `segs` was reversed before (mod.rs:124): wall records go back to front.
+    template <typename DrawWall, typename DrawSprite>
+    void interleave(const std::vector<uint32_t> &mo, size_t n_wall_recs, DrawWall draw_wall, DrawSprite draw_sprite) {
+        for (size_t i = 0; i <= mo.size(); i++) {
+            const bool rest = i == mo.size();
+            const Seg2 l = rest ? Seg2{} : recs[mo[i]].line;
+            const V2 v{(l.a.x + l.b.x) / 2.0f, (l.a.y + l.b.y) / 2.0f};
+            for (size_t ri = n_wall_recs; ri-- > 0;) {
+                Rec &r = recs[ri];
+                if (r.state != ST_TWOSIDED || (!rest && !behind(r, v))) continue;
+                draw_wall(ri);
+                r.state = ST_DRAWN;
+            }
+            if (!rest) draw_sprite(mo[i]);
+        }
     }
 
-    // draw_map_objects, renderer/map_objects.rs:19-241
+    // draw_map_objects, renderer/map_objects.rs:19-241.  As in process_sidedef, the geometry and the panics are fs_core.h's in both modes.
     void map_objects() {
-        const int W = k.W, H = k.H;
+        const int H = k.H;
         const size_t n_wall_recs = recs.size();
         if (parts_mode) A.behind_words = (uint32_t)((n_wall_recs + 31) / 32);
         std::vector<uint32_t> mo;   // indices of map-object records in recs
         for (size_t mi = 0; mi < sc.mobjs.size(); mi++) {
-            const MapObjectRec &m = sc.mobjs[mi];
             int32_t m_sprite_frame, m_full_bright;
             mobj_state(mi, m_sprite_frame, m_full_bright);
             if (m_sprite_frame < 0) continue;                         // S_NULL
-            if (parts_mode) {                                         // the per-column half runs on the GPU: record the sprite (fs_core.h)
-                FsSpriteOut so;
-                std::memset(&so.sp, 0, sizeof so.sp);
-                const FsMobj &fm = sc.fs_mobjs[mi];
-                const int32_t st = fs_mobj(k, fm, sc.sprite_frames_fs()[(size_t)m_sprite_frame], sc.fs_bitmaps.data(), sc.fs_sectors.data(), ppos, view.angle,
-                                           view.cos_na, view.sin_na, player_height, m_full_bright, fm.sector >= 0 ? sector_light(fm.sector) : (int16_t)0, so);
-                if (st == FS_SKIP) continue;
-                if (st == FS_FAIL_PARTS) { fail_parts(fs_message(st)); return; }
-                if (st != FS_OK) { fail(fs_message(st)); return; }
-                Rec r;
-                std::memset(&r, 0, sizeof r);
-                r.line = so.line;
-                r.min_x = std::fmin(r.line.a.x, r.line.b.x); r.max_x = std::fmax(r.line.a.x, r.line.b.x);
-                r.first_col = (uint32_t)A.sprites.size(); r.out_index = -1;   // first_col: index into A.sprites
-                r.state = ST_MAPOBJECT;
-                r.sort_key = (int16_t)so.sort_key;
+            const FsMobj &fm = sc.fs_mobjs[mi];
+            const FsSpriteFrame &sf = sc.sprite_frames_fs()[(size_t)m_sprite_frame];
+            const int16_t light = fm.sector >= 0 ? sector_light(fm.sector) : (int16_t)0;
+            FsSpriteOut so;
+            FsMobjGeom g{};
+            if (parts_mode) std::memset(&so.sp, 0, sizeof so.sp);
+            const int32_t st = parts_mode ? fs_mobj(k, fm, sf, sc.fs_bitmaps.data(), sc.fs_sectors.data(), ppos, view.angle, view.cos_na, view.sin_na, player_height, m_full_bright, light, so)
+                                          : fs_mobj_geom(k, fm, sf, sc.fs_bitmaps.data(), sc.fs_sectors.data(), ppos, view.angle, view.cos_na, view.sin_na, player_height, m_full_bright, light, g);
+            if (st == FS_SKIP) continue;
+            if (st != FS_OK) { fail_fs(st); return; }
+            Rec r = make_rec(parts_mode ? so.line : g.cl.line, ST_MAPOBJECT);
+            r.sort_key = (int16_t)(parts_mode ? so.sort_key : g.sort_key);
+            mo.push_back((uint32_t)recs.size());
+            if (parts_mode) {                                         // the per-column half runs on the GPU: record the sprite
+                r.first_col = (uint32_t)A.sprites.size();             // first_col: index into A.sprites
                 // which wall records clip this sprite (the ones NOT behind its centre, map_objects.rs:138-140)
                 const size_t row = A.behind.size();
                 A.behind.resize(row + A.behind_words, 0u);
@@ -471,42 +463,12 @@ struct Walker {
                     if (behind(recs[ri], so.centre)) A.behind[row + (ri >> 5)] |= 1u << (ri & 31);
                 so.sp.behind_off = (uint32_t)row;
                 A.sprites.push_back(so.sp);
-                mo.push_back((uint32_t)recs.size());
                 recs.push_back(r);
                 continue;
             }
-            float angle = view.angle - m.angle - kPi;
-            angle += kPi / 16.0f;
-            angle = std::fmod(angle, 2.0f * kPi);
-            if (angle < 0.0f) angle += 2.0f * kPi;
-            angle = std::fmod(angle, 2.0f * kPi);
-            int rotation = f32_as_u8(angle * 8.0f / (2.0f * kPi));
-            if (rotation > 7) { fail("Invalid rotation (sprites.rs:106-108)"); return; }
-            const SpriteFrameRec &sf = sc.sprite_frames[(size_t)m_sprite_frame];
-            int bitmap = sf.rotate ? sf.bitmap[rotation] : sf.bitmap[0];
-            const BitmapInfo &bi = sc.bitmaps[(size_t)bitmap];
-
-            V2 vpv = rot(sub(V2{m.x, m.y}, ppos), view.cos_na, view.sin_na);
-            int16_t width = (int16_t)bi.w;
-            V2 a = sub(vpv, V2{0.0f, (float)(int16_t)(-width) / 2.0f});
-            V2 b = sub(vpv, V2{0.0f, (float)width / 2.0f});
-            Clipped cl;
-            if (!clip_to_viewport(Seg2{a, b}, cl)) continue;
-            if (cl.line.a.x < -0.01f) { fail("Clipped line x < -0.01 (map_objects.rs:92-97)"); return; }
-            if (m.sector < 0) continue;                               // "Thing is outside map"
-            const SectorRec &sec = sc.sectors[(size_t)m.sector];
-            int16_t light = m_full_bright ? (int16_t)255 : sector_light(m.sector);
-
-            int16_t bh = (int16_t)bi.h;
-            float bottom_height = (float)sec.floor_h - player_height;
-            float top_height = (float)sec.floor_h + (float)bh - 1.0f - player_height;
-            bottom_height += (float)bi.top_offset - (float)bh;
-            top_height += (float)bi.top_offset - (float)bh;
-            ScreenLine bot = project(k, cl.line, bottom_height);
-            ScreenLine top = project(k, cl.line, top_height);
-
-            int x0 = wrap_i16(bot.sx), x1 = wrap_i16(bot.ex);        // columns [x0, x1)
-            if (x0 < x1 && (x0 < 0 || x1 > W)) { fail("map object column out of range (index panic)"); return; }
+            const V2 vpv = g.vpv;
+            const ScreenLine &bot = g.bot, &top = g.top;
+            const int x0 = g.x0, x1 = g.x1;
             for (int x = x0; x < x1; x++) { A.top_clip[(size_t)x] = -1; A.bottom_clip[(size_t)x] = (int16_t)H; }
             if (x0 < x1) {
                 for (size_t ri = 0; ri < n_wall_recs; ri++) {         // :135-166 (only x in [x0,x1) is ever read back)
@@ -528,18 +490,13 @@ struct Walker {
                     }
                 }
             }
-            Rec r;
-            r.line = cl.line; r.start_offset = cl.start_offset;
-            r.bottom_height = bottom_height; r.top_height = top_height;
-            r.min_x = std::fmin(r.line.a.x, r.line.b.x); r.max_x = std::fmax(r.line.a.x, r.line.b.x);
-            r.start_x = bot.sx; r.end_x = bot.ex; r.bitmap = bitmap;
-            r.first_col = (uint32_t)A.columns.size(); r.n_cols = 0; r.out_index = -1;
-            r.light = light; r.offset_x = 0; r.offset_y = 0;
-            r.state = ST_MAPOBJECT; r.ext_bottom = r.ext_top = r.draw_ceiling = 0;
-            r.sort_key = (int16_t)f32_as_i16(cl.line.a.x);
+            r.start_offset = g.cl.start_offset;
+            r.bottom_height = g.bottom_height; r.top_height = g.top_height;
+            r.start_x = bot.sx; r.end_x = bot.ex; r.bitmap = g.bitmap;
+            r.first_col = (uint32_t)A.columns.size();
+            r.light = g.light;
             r.owner = ((uint32_t)DG_LABEL_MOBJ << 16) | (uint32_t)(mi & 0xffffu);
-            float bottom_delta = ((float)bot.sy - (float)bot.ey) / ((float)bot.sx - (float)bot.ex);
-            float top_delta = ((float)top.sy - (float)top.ey) / ((float)top.sx - (float)top.ex);
+            const float bottom_delta = fs_slope(bot), top_delta = fs_slope(top);
             for (int x = x0; x < x1; x++) {
                 int16_t bottom_y = (int16_t)f32_as_i16((float)bot.sy + ((float)x - (float)bot.sx) * bottom_delta);
                 int16_t top_y = (int16_t)f32_as_i16((float)top.sy + ((float)x - (float)top.sx) * top_delta);
@@ -548,51 +505,18 @@ struct Walker {
                 A.columns.push_back(dg_bitmap_column{(int16_t)x, ct, cb, bottom_y, top_y});
                 r.n_cols++;
             }
-            mo.push_back((uint32_t)recs.size());
             recs.push_back(r);
         }
         // sort() is stable ascending on the key, then reverse()  (map_objects.rs:216-217)
         std::stable_sort(mo.begin(), mo.end(), [&](uint32_t p, uint32_t q) { return recs[p].sort_key < recs[q].sort_key; });
         std::reverse(mo.begin(), mo.end());
 
-        if (parts_mode) {                                            // same interleave, recorded as sequence numbers
+        if (parts_mode) {                                            // "draw" = the record's place in the sequence
             uint32_t seq = 0;
-            for (uint32_t mi : mo) {
-                const Rec &m = recs[mi];
-                V2 v{(m.line.a.x + m.line.b.x) / 2.0f, (m.line.a.y + m.line.b.y) / 2.0f};
-                for (size_t ri = n_wall_recs; ri-- > 0;) {
-                    Rec &r = recs[ri];
-                    if (r.state != ST_TWOSIDED || !behind(r, v)) continue;
-                    A.parts[ri].seq = seq++;
-                    r.state = ST_DRAWN;
-                }
-                A.sprites[m.first_col].seq = seq++;
-            }
-            for (size_t ri = n_wall_recs; ri-- > 0;) {
-                Rec &r = recs[ri];
-                if (r.state != ST_TWOSIDED) continue;
-                A.parts[ri].seq = seq++;
-                r.state = ST_DRAWN;
-            }
-            return;
-        }
-        // `segs` was reversed before this call (mod.rs:124): iterate wall records back to front
-        for (uint32_t mi : mo) {
-            const Rec &m = recs[mi];
-            V2 v{(m.line.a.x + m.line.b.x) / 2.0f, (m.line.a.y + m.line.b.y) / 2.0f};
-            for (size_t ri = n_wall_recs; ri-- > 0;) {
-                Rec &r = recs[ri];
-                if (r.state != ST_TWOSIDED || !behind(r, v)) continue;
-                if (r.bitmap >= 0 && r.n_cols > 0) emit_draw(r);
-                r.state = ST_DRAWN;
-            }
-            if (recs[mi].n_cols > 0) emit_draw(recs[mi]);
-        }
-        for (size_t ri = n_wall_recs; ri-- > 0;) {                   // draw_remaining_segs, segs.rs:593-597
-            Rec &r = recs[ri];
-            if (r.state != ST_TWOSIDED) continue;
-            if (r.bitmap >= 0 && r.n_cols > 0) emit_draw(r);
-            r.state = ST_DRAWN;
+            interleave(mo, n_wall_recs, [&](size_t ri) { A.parts[ri].seq = seq++; }, [&](uint32_t mi) { A.sprites[recs[mi].first_col].seq = seq++; });
+        } else {
+            const auto draw = [&](size_t i) { if (recs[i].bitmap >= 0 && recs[i].n_cols > 0) emit_draw(recs[i]); };   // (a sprite always has a bitmap)
+            interleave(mo, n_wall_recs, draw, draw);
         }
     }
 };

@@ -1,8 +1,10 @@
 // fs_core.h — the per-seg and per-sprite half of the reference's front end as host/device inline functions: what
 // Segs::process_seg (src/renderer/segs.rs:353-590) and Segs::process_sidedef (:121-200) do BEFORE the column loop, clip_to_viewport and
 // the projection (src/renderer/misc.rs:13-161, src/geometry.rs:56-86, src/map/vertexes.rs:20-34) and the per-object part of
-// draw_map_objects (src/renderer/map_objects.rs:34-129).  Two callers execute these bodies:
-//   * frontend.cpp  Walker (host, parts mode): one thread per frame walks the BSP in order (DG_FE_DEVICE);
+// draw_map_objects (src/renderer/map_objects.rs:34-129).  Three callers execute these bodies:
+//   * frontend.cpp  Walker (host, list mode): dg_build_lists, DG_FE_HOST, depth / labels / bundles, every frame a device front end hands
+//     back.  It takes the geometry (fs_seg, fs_part_geom, fs_part_offsets, fs_mobj_geom) and runs its own column loops after it;
+//   * frontend.cpp  Walker (host, parts mode): one thread per frame walks the BSP in order and records fs_part / fs_mobj (DG_FE_DEVICE);
 //   * fs_kernels.hip (GPU, DG_FE_DEVICE_SEGS): one lane per (frame, seg) / (frame, map object), order restored afterwards —
 // and tests/emul runs the GPU's bodies on the CPU against the host walker, record by record.
 // Arithmetic contract as everywhere: IEEE f32 in the reference's operand order, no contraction, Rust `as` casts through rust_num.h.
@@ -86,13 +88,16 @@ template <typename K> DG_HD ScreenLine project(const K &k, const Seg2 &l, float 
     return o;
 }
 
-// BitmapRender::is_behind_vertex (bitmap_render.rs:137-165) for a record's clipped line
-DG_HD bool fs_behind(const Seg2 &line, V2 v) {
-    const float min_x = fs_fmin(line.a.x, line.b.x), max_x = fs_fmax(line.a.x, line.b.x);
+// The slope of a projected edge, in rows per column (segs.rs:147-150, map_objects.rs:121-124)
+DG_HD float fs_slope(const ScreenLine &l) { return ((float)l.sy - (float)l.ey) / ((float)l.sx - (float)l.ex); }
+
+// BitmapRender::is_behind_vertex (bitmap_render.rs:137-165) for a record's clipped line; min_x / max_x: of its two ends (the host keeps them)
+DG_HD bool fs_behind(const Seg2 &line, float min_x, float max_x, V2 v) {
     if (min_x > v.x) return true;
     if (max_x > v.x && !left_of(v, line)) return true;
     return false;
 }
+DG_HD bool fs_behind(const Seg2 &line, V2 v) { return fs_behind(line, fs_fmin(line.a.x, line.b.x), fs_fmax(line.a.x, line.b.x), v); }
 
 // What the texture mapper needs of a bitmap (scene.hpp BitmapInfo; the GPU holds a table of these)
 struct FsBitmap { uint32_t texel_off; int16_t w, h; int16_t top_offset; uint16_t has_holes; };
@@ -291,6 +296,16 @@ template <typename K> DG_HD void project_x(const K &k, const Seg2 &l, int32_t &s
     sx = sx < k.W - 1 ? sx : k.W - 1;
     ex = ex < k.W - 1 ? ex : k.W - 1;
 }
+// A part's FEP_* flags: the call's own, whether it draws a bitmap, and whether its sector's flats are sky.  flat_sky[flat]: the name contains "SKY".
+DG_HD uint32_t fs_part_flags(const FsSegOut &s, const FsCall &c, const uint8_t *flat_sky) {
+    const bool fsky = flat_sky[s.floor_flat] != 0, csky = flat_sky[s.ceil_flat] != 0;
+    return c.flags | (c.tex >= 0 ? FEP_HAS_BITMAP : 0u) | (fsky ? FEP_FLOOR_SKY : 0u) | (csky ? FEP_CEIL_SKY : 0u);
+}
+// The texture offsets a part is drawn with: the sidedef's plus the seg's in x, the sidedef's plus the call's pegging offset in y (segs.rs:158-175)
+DG_HD void fs_part_offsets(const FsSegOut &s, const FsCall &c, int16_t &offset_x, int16_t &offset_y) {
+    offset_x = (int16_t)wrap_i16(f32_as_i16(s.sd_xoff) + s.seg_offset);
+    offset_y = (int16_t)wrap_i16(f32_as_i16(s.sd_yoff) + wrap_i16(c.offset_y));
+}
 // The tests of Segs::process_sidedef (segs.rs:121-157) that decide whether a call reaches its column loop, and what the hidden-part
 // culling needs of it: columns [sx, ex] and the FEP_* flags.  (Both edges of a part project to the same columns — the x of
 // perspective_transform does not see the height — so the reference's "Wall start not vertical" panic cannot fire; fs_part keeps the test.)
@@ -301,16 +316,19 @@ DG_HD int32_t fs_part_head(const K &k, const FsSegOut &s, const FsCall &c, const
     if (wrap_i16(sx) == wrap_i16(ex)) return FS_SKIP;
     if (sx < 0 || sx >= k.W || ex < 0 || ex >= k.W) return FS_FAIL_LINE_X;
     if (c.tex >= 0 && (bitmaps[c.tex].w <= 0 || bitmaps[c.tex].h <= 0)) return FS_FAIL_PARTS;
-    const bool fsky = flat_sky[s.floor_flat] != 0, csky = flat_sky[s.ceil_flat] != 0;
-    flags = c.flags | (c.tex >= 0 ? FEP_HAS_BITMAP : 0u) | (fsky ? FEP_FLOOR_SKY : 0u) | (csky ? FEP_CEIL_SKY : 0u);
+    flags = fs_part_flags(s, c, flat_sky);
     return FS_OK;
 }
 
 // Segs::process_sidedef (segs.rs:121-200) up to its column loop, for one call of a seg: the FePart the device column walk consumes,
 // without the two fields that depend on what came before in BSP order (sky_slot, seq: left -1 / 0).  FS_SKIP: a zero-width part.
 // view_floor_height: player.floor_height (visplanes.rs:112).  flat_sky[flat]: the flat's name contains "SKY".
-template <typename K>
-DG_HD int32_t fs_part(const K &k, const FsSegOut &s, const FsCall &c, const FsBitmap *bitmaps, const uint8_t *flat_sky, float view_floor_height, FePart &p) {
+// The body is stated once for two callers: kGeomOnly stops in front of the FS_FAIL_PARTS test with the geometry in g (fs_part_geom: the
+// host's list mode, which carries on with a zero-sized bitmap and reads none of the record); otherwise it fills p (fs_part).
+struct FsPartGeom { ScreenLine bot, top; float bottom_delta, top_delta; };
+template <bool kGeomOnly, typename K>
+DG_HD int32_t fs_part_body(const K &k, const FsSegOut &s, const FsCall &c, const FsBitmap *bitmaps, const uint8_t *flat_sky, float view_floor_height, FsPartGeom *g,
+                           FePart *pp) {
     const Seg2 &line = s.cl.line;
     const ScreenLine bot = project(k, line, c.bottom_height);
     const ScreenLine top = project(k, line, c.top_height);
@@ -318,16 +336,16 @@ DG_HD int32_t fs_part(const K &k, const FsSegOut &s, const FsCall &c, const FsBi
     if (bot.sx != top.sx || bot.ex != top.ex) return FS_FAIL_VERTICAL;
     if (wrap_i16(bot.sx) == wrap_i16(bot.ex) || wrap_i16(top.sx) == wrap_i16(top.ex)) return FS_SKIP;
     if (bot.sx < 0 || bot.sx >= k.W || bot.ex < 0 || bot.ex >= k.W) return FS_FAIL_LINE_X;
-    const float bottom_delta = ((float)bot.sy - (float)bot.ey) / ((float)bot.sx - (float)bot.ex);
-    const float top_delta = ((float)top.sy - (float)top.ey) / ((float)top.sx - (float)top.ex);
+    const float bottom_delta = fs_slope(bot), top_delta = fs_slope(top);
+    if constexpr (kGeomOnly) { *g = FsPartGeom{bot, top, bottom_delta, top_delta}; return FS_OK; }
+    FePart &p = *pp;
     if (c.tex >= 0 && (bitmaps[c.tex].w <= 0 || bitmaps[c.tex].h <= 0)) return FS_FAIL_PARTS;
-    const int16_t offset_x = (int16_t)wrap_i16(f32_as_i16(s.sd_xoff) + s.seg_offset);
-    const int16_t offset_y = (int16_t)wrap_i16(f32_as_i16(s.sd_yoff) + wrap_i16(c.offset_y));
+    int16_t offset_x, offset_y;
+    fs_part_offsets(s, c, offset_x, offset_y);
     p.sx = bot.sx; p.ex = bot.ex;
     p.bsy = (float)bot.sy; p.bsx = (float)bot.sx; p.bdelta = bottom_delta;
     p.tsy = (float)top.sy; p.tsx = (float)top.sx; p.tdelta = top_delta;
-    const bool fsky = flat_sky[s.floor_flat] != 0, csky = flat_sky[s.ceil_flat] != 0;
-    p.flags = c.flags | (c.tex >= 0 ? FEP_HAS_BITMAP : 0u) | (fsky ? FEP_FLOOR_SKY : 0u) | (csky ? FEP_CEIL_SKY : 0u);
+    p.flags = fs_part_flags(s, c, flat_sky);
     p.sky_slot = -1;
     p.seq = 0;
     p.pad = 0;
@@ -348,6 +366,13 @@ DG_HD int32_t fs_part(const K &k, const FsSegOut &s, const FsCall &c, const FsBi
     p.ceil_plane.flat_off = (uint32_t)s.ceil_flat * 4096u;
     return FS_OK;
 }
+template <typename K>
+DG_HD int32_t fs_part(const K &k, const FsSegOut &s, const FsCall &c, const FsBitmap *bitmaps, const uint8_t *flat_sky, float view_floor_height, FePart &p) {
+    return fs_part_body<false>(k, s, c, bitmaps, flat_sky, view_floor_height, nullptr, &p);
+}
+template <typename K> DG_HD int32_t fs_part_geom(const K &k, const FsSegOut &s, const FsCall &c, FsPartGeom &g) {
+    return fs_part_body<true>(k, s, c, nullptr, nullptr, 0.0f, &g, nullptr);
+}
 // Does a part with these flags open / extend visplanes (segs.rs:263-318), and may it therefore need a sky event slot?
 DG_HD bool fs_part_wants_sky_slot(uint32_t flags) {
     const bool full_height = !(flags & (FEP_LOWER | FEP_UPPER | FEP_ONLY_OCCL));
@@ -367,9 +392,20 @@ enum : int32_t { FS_FAIL_ROTATION = 8, FS_FAIL_MOBJ_CLIP_X = 9, FS_FAIL_MOBJ_COL
 struct FsSpriteOut { FeSprite sp; Seg2 line; V2 centre; int32_t sort_key; };
 // draw_map_objects (map_objects.rs:34-129, 168-209) for one object whose state shows (sprite_frame >= 0): FS_OK with the FeSprite
 // (seq / behind_off left 0), FS_SKIP, or a failure.  light: the object's sector's current light level.
-template <typename K>
-DG_HD int32_t fs_mobj(const K &k, const FsMobj &m, const FsSpriteFrame &sf, const FsBitmap *bitmaps, const FsSector *sectors, V2 ppos, float view_angle,
-                      float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsSpriteOut &o) {
+// The body is stated once for two callers, like fs_part_body: kGeomOnly stops in front of the FS_FAIL_PARTS test with the geometry in g
+// (fs_mobj_geom: the host's list mode; vpv is the object in view space, what is_behind_vertex is asked about); otherwise it fills o (fs_mobj).
+struct FsMobjGeom {
+    int32_t bitmap;
+    Clipped cl;
+    V2 vpv;
+    float bottom_height, top_height;
+    ScreenLine bot, top;
+    int32_t x0, x1;                                               // columns [x0, x1)
+    int16_t light, sort_key;
+};
+template <bool kGeomOnly, typename K>
+DG_HD int32_t fs_mobj_body(const K &k, const FsMobj &m, const FsSpriteFrame &sf, const FsBitmap *bitmaps, const FsSector *sectors, V2 ppos, float view_angle,
+                           float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsMobjGeom *g, FsSpriteOut *out) {
     const float kPi = 3.14159265358979323846f;
     float angle = view_angle - m.angle - kPi;
     angle += kPi / 16.0f;
@@ -401,19 +437,33 @@ DG_HD int32_t fs_mobj(const K &k, const FsMobj &m, const FsSpriteFrame &sf, cons
     const ScreenLine top = project(k, cl.line, top_height);
     const int x0 = wrap_i16(bot.sx), x1 = wrap_i16(bot.ex);       // columns [x0, x1)
     if (x0 < x1 && (x0 < 0 || x1 > k.W)) return FS_FAIL_MOBJ_COLUMN;
+    if constexpr (kGeomOnly) {
+        *g = FsMobjGeom{bitmap, cl, vpv, bottom_height, top_height, bot, top, x0, x1, light, (int16_t)f32_as_i16(cl.line.a.x)};   // sort key: bitmap_render.rs:168-174
+        return FS_OK;
+    }
     if (bi.w <= 0 || bi.h <= 0) return FS_FAIL_PARTS;
+    FsSpriteOut &o = *out;
     FeSprite &sp = o.sp;
     sp.x0 = x0; sp.x1 = x1;
-    sp.bsy = (float)bot.sy; sp.bsx = (float)bot.sx;
-    sp.bdelta = ((float)bot.sy - (float)bot.ey) / ((float)bot.sx - (float)bot.ex);
-    sp.tsy = (float)top.sy; sp.tsx = (float)top.sx;
-    sp.tdelta = ((float)top.sy - (float)top.ey) / ((float)top.sx - (float)top.ex);
+    sp.bsy = (float)bot.sy; sp.bsx = (float)bot.sx; sp.bdelta = fs_slope(bot);
+    sp.tsy = (float)top.sy; sp.tsx = (float)top.sx; sp.tdelta = fs_slope(top);
     sp.seq = 0; sp.behind_off = 0; sp.pad[0] = sp.pad[1] = 0;
     sp.wall = fs_wall_rec(bi, cl.line.a.x, cl.line.a.y, cl.line.b.x, cl.line.b.y, cl.start_offset, bot.sx, bot.ex, bottom_height, top_height, 0, 0, light);
     o.line = cl.line;
     o.centre = vpv;
     o.sort_key = f32_as_i16(cl.line.a.x);                         // bitmap_render.rs:168-174
     return FS_OK;
+}
+
+template <typename K>
+DG_HD int32_t fs_mobj(const K &k, const FsMobj &m, const FsSpriteFrame &sf, const FsBitmap *bitmaps, const FsSector *sectors, V2 ppos, float view_angle,
+                      float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsSpriteOut &o) {
+    return fs_mobj_body<false>(k, m, sf, bitmaps, sectors, ppos, view_angle, cos_na, sin_na, player_height, full_bright, sector_light, nullptr, &o);
+}
+template <typename K>
+DG_HD int32_t fs_mobj_geom(const K &k, const FsMobj &m, const FsSpriteFrame &sf, const FsBitmap *bitmaps, const FsSector *sectors, V2 ppos, float view_angle,
+                           float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsMobjGeom &g) {
+    return fs_mobj_body<true>(k, m, sf, bitmaps, sectors, ppos, view_angle, cos_na, sin_na, player_height, full_bright, sector_light, &g, nullptr);
 }
 
 }  // namespace dg

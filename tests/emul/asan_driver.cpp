@@ -1,8 +1,9 @@
 // tests/emul/asan_driver.cpp — sanitizer stress for the product's HOST code (scene loader, list generation, binner),
 // built with -fsanitize=address,undefined by tests/test_sanitizers.py (GPU sanitizers are not available on this pool).
-//   usage: asan_driver <wad file> <camera path .f32> <map name>
+//   usage: asan_driver <wad file> <camera path .f32> <map name> [<failure wad file> ...]
 // Renders lists for path frames at several sizes, for random off-map viewpoints, and loads truncated / bit-flipped
-// copies of the WAD: every call must either succeed or fail with a clean error, never touch memory out of bounds.
+// copies of the WAD: every call must either succeed or fail with a clean error, never touch memory out of bounds.  The failure WADs
+// (tests/test_walker_failures.py: hand-packed maps in which the reference panics) are walked in both modes from their player start at 64x40.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -81,6 +82,30 @@ static int walk_parts_on_host(const Scene &sc, int W, int H, const dg_view &v, F
     return 0;
 }
 
+// One failure WAD from its player start: what list mode, the binner and parts mode each say.  n[0..3] count list-mode refusals, binner
+// refusals, parts-mode refusals and kPartsUnsupported.
+static bool failure_wad(const char *file, const char *map_name, int n[4]) {
+    std::ifstream f(file, std::ios::binary);
+    std::vector<uint8_t> wad((std::istreambuf_iterator<char>(f)), {});
+    std::string err;
+    Scene *sc = load_scene_from_wad(wad.data(), wad.size(), map_name, err);
+    if (!sc) { std::printf("load of %s failed: %s\n", file, err.c_str()); return false; }
+    dg_view v{sc->start_x, sc->start_y, sc->start_angle, 0.0f, 0, 0, 0, 0, 0.0f, 0};
+    fill_view_trig(v);
+    FrameArena arena, parts_arena;
+    BinnedFrame bf;
+    dg_frame_lists fl;
+    int rc = build_frame_lists(*sc, 64, 40, v, arena, fl, err);
+    if (rc) n[0]++;
+    else if (bin_frame(*sc, make_consts(64, 40), fl, bf, err)) n[1]++;
+    rc = build_frame_parts(*sc, 64, 40, v, parts_arena, err);
+    if (rc == kPartsUnsupported) n[3]++;
+    else if (rc) n[2]++;
+    else if (walk_parts_on_host(*sc, 64, 40, v, parts_arena)) return false;
+    delete sc;
+    return true;
+}
+
 int main(int argc, char **argv) {
     if (argc < 4) return 2;
     std::ifstream f(argv[1], std::ios::binary);
@@ -92,7 +117,7 @@ int main(int argc, char **argv) {
     Scene *sc = load_scene_from_wad(wad.data(), wad.size(), argv[3], err);
     if (!sc) { std::printf("load failed: %s\n", err.c_str()); return 1; }
     int ok = 0, refused = 0;
-    const int sizes[][2] = {{320, 200}, {1280, 800}, {64, 48}, {132, 67}, {4, 4}, {16384, 8}};
+    const int sizes[][2] = {{320, 200}, {1280, 800}, {64, 48}, {64, 40}, {132, 67}, {4, 4}, {16384, 8}};
     for (auto &s : sizes)
         for (int i = 0; i < 1000; i += 53) {
             const float *r = &path[(size_t)i * 8];
@@ -128,6 +153,10 @@ int main(int argc, char **argv) {
         delete s2;
     }
     delete sc;
+    int n[4] = {0, 0, 0, 0};
+    for (int i = 4; i < argc; i++)
+        if (!failure_wad(argv[i], argv[3], n)) return 1;
+    std::printf("failure wads: %d refused by list mode, %d by the binner, %d by parts mode, %d left to list mode\n", n[0], n[1], n[2], n[3]);
     std::printf("SANITIZER DRIVER OK lists ok=%d refused=%d wads loaded=%d rejected=%d\n", ok, refused, loaded, rejected);
     return 0;
 }

@@ -534,6 +534,15 @@ int emul_frame_parts(void *scene, int W, int H, const dg_view *view_in, uint32_t
     return n;
 }
 
+// build_frame_parts' own return code for one view (DG_OK, DG_ERR_RENDER, kPartsUnsupported = 1000); emul_last_error has its message.
+int emul_build_parts(void *scene, int W, int H, const dg_view *view_in) {
+    dg_view view = *view_in;
+    fill_view_trig(view);
+    static thread_local FrameArena arena;
+    g_err.clear();
+    return build_frame_parts(*(const Scene *)scene, W, H, view, arena, g_err);
+}
+
 // The same records whole (sizeof(FePart) bytes each, the wall and plane constants included), drawn with the scene's wall effects.
 int emul_frame_part_records(void *scene, int W, int H, const dg_view *view_in, uint8_t *out, int cap) {
     const Scene &sc = *(const Scene *)scene;

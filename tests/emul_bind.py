@@ -31,6 +31,7 @@ def lib():
                                         ctypes.c_uint32, ctypes.c_void_p]
         L.emul_fs_frame.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(ctypes.c_uint64)]
         L.emul_frame_part_records.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.c_int]
+        L.emul_build_parts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView)]
         L.emul_fs_no_cl_rows.argtypes = [ctypes.c_int]
         L.emul_fs_no_cl_rows.restype = None
         L.emul_fs_kept_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -123,6 +124,13 @@ class EmulScene:
         if rc < 0:
             raise RuntimeError(f"emul_fs_frame rc {rc}: {lib().emul_last_error().decode()}")
         return rc, list(st)
+
+    def build_parts(self, W, H, rec, timestamp=0.0):
+        """build_frame_parts (the host walker's parts mode) for one view -> (its return code, its error text)."""
+        v = DgView(float(rec[0]), float(rec[1]), float(rec[2]), float(rec[7]), float(rec[3]), float(rec[4]), float(rec[5]), float(rec[6]),
+                   float(timestamp), 1)
+        rc = lib().emul_build_parts(self._h, W, H, ctypes.byref(v))
+        return rc, lib().emul_last_error().decode()
 
     def frame_parts(self, W, H, rec, timestamp=0.0):
         """The host walker's FePart records of one view, whole (128 bytes each), with the scene's wall effects."""
