@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DOOMGPU_LIB") or os.path.join(_HERE, "libdoomgpu.so")   # override only for kernel-variant experiments
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include", "doomgpu.h")
 
-DG_OK, DG_ERR_INVALID, DG_ERR_NO_DEVICE, DG_ERR_HIP, DG_ERR_WAD, DG_ERR_RENDER, DG_ERR_CAPACITY = 0, -1, -2, -3, -4, -5, -6
+DG_OK, DG_ERR_INVALID, DG_ERR_NO_DEVICE, DG_ERR_HIP, DG_ERR_WAD, DG_ERR_RENDER, DG_ERR_CAPACITY, DG_ERR_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 DG_FE_AUTO, DG_FE_HOST, DG_FE_DEVICE, DG_FE_DEVICE_SEGS = 0, 1, 2, 3
 DG_FE_MAP = 4   # dg_timing.front_end of a 2-D map submission
 DG_FE_DEPTH = 5  # dg_timing.front_end of a depth submission
@@ -74,6 +74,22 @@ class DgMobjInfoRec(ctypes.Structure):
 class DgViewState(ctypes.Structure):
     _fields_ = [("lights", ctypes.POINTER(DgSectorLight)), ("n_lights", ctypes.c_uint32),
                 ("mobjs", ctypes.POINTER(DgMobjState)), ("n_mobjs", ctypes.c_uint32)]
+
+
+class DgMobjPose(ctypes.Structure):
+    _fields_ = [("mobj", ctypes.c_int32), ("x", ctypes.c_float), ("y", ctypes.c_float), ("angle", ctypes.c_float)]
+
+
+class DgViewPoses(ctypes.Structure):
+    _fields_ = [("poses", ctypes.POINTER(DgMobjPose)), ("n", ctypes.c_uint32)]
+
+
+class DgMobjPlaced(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_float), ("y", ctypes.c_float), ("angle", ctypes.c_float), ("sector", ctypes.c_int32)]
+
+
+# a row of dg_mobj_placed as numpy sees it (dg_scene_mobj_poses, dg_slot_mobj_poses)
+MOBJ_PLACED_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("angle", "<f4"), ("sector", "<i4")])
 
 
 class DgWalkDesc(ctypes.Structure):
@@ -214,6 +230,14 @@ _SIGNATURES = {
     "dg_depth_lists": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P, _P]),
     "dg_readback_depth": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
     "dg_depth_lists_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgFrameLists), ctypes.c_int, _P, _P]),
+    "dg_build_lists_poses": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgFrameLists), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32))]),
+    "dg_scene_sectors_at": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P]),
+    "dg_scene_mobj_poses": (ctypes.c_int, [_P, _P, ctypes.c_int]),
+    "dg_submit_views_poses": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.c_int]),
+    "dg_render_views_poses": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.c_int, _P]),
+    "dg_submit_bundle_views_poses": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.c_int, ctypes.c_uint32]),
+    "dg_slot_mobj_poses": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "dg_slot_mobj_pose_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "dg_build_lists_owners": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgFrameLists), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32))]),
     "dg_submit_label_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int]),
     "dg_render_label_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int, _P, _P, _P]),
@@ -503,6 +527,18 @@ def make_view_states(states):
     return arr, keep
 
 
+def make_view_poses(poses):
+    """poses: one list per view of (mobj, x, y, angle) entries (dg_mobj_pose; the floats are taken as float32).
+    Returns (ctypes array of dg_view_poses, keep-alive list)."""
+    arr = (DgViewPoses * max(1, len(poses)))()
+    keep = []
+    for i, entries in enumerate(poses):
+        pa = (DgMobjPose * max(1, len(entries)))(*[DgMobjPose(int(m), float(x), float(y), float(a)) for m, x, y, a in entries])
+        keep.append(pa)
+        arr[i] = DgViewPoses(pa, len(entries))
+    return arr, keep
+
+
 def make_views(records, timestamp: float = 0.0):
     """camera_path records (n, 8) f32 [x, y, angle, cos, sin, cos(-a), sin(-a), floor] -> ctypes array of dg_view."""
     recs = np.asarray(records, dtype=np.float32).reshape(-1, 8)
@@ -600,6 +636,32 @@ class Scene:
         _check(lib().dg_build_lists_owners(self._h, W, H, ctypes.byref(view), ctypes.byref(fl), ctypes.byref(own)))
         return fl, np.array(own[:fl.n_renders], dtype=np.uint32)
 
+    def build_lists_poses(self, W: int, H: int, view: DgView, poses=None, owners: bool = False):
+        """dg_build_lists_poses: dg_build_lists for a view whose map objects stand where `poses` says ([(mobj, x, y, angle), ...] or
+        None); with owners=True returns (lists, owner tags) as build_lists_owners does."""
+        fl = DgFrameLists()
+        vp, _keep = make_view_poses([poses]) if poses is not None else (None, None)
+        own = ctypes.POINTER(ctypes.c_uint32)()
+        _check(lib().dg_build_lists_poses(self._h, W, H, ctypes.byref(view), vp, ctypes.byref(fl), ctypes.byref(own) if owners else None))
+        return (fl, np.array(own[:fl.n_renders], dtype=np.uint32)) if owners else fl
+
+    def sectors_at(self, x, y) -> np.ndarray:
+        """dg_scene_sectors_at: get_sector_from_vertex of every point (float32 arrays x, y) as an int32 array, -1 for None."""
+        xs = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        ys = np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
+        if xs.size != ys.size:
+            raise ValueError("x and y differ in length")
+        out = np.empty(xs.size, dtype=np.int32)
+        _check(lib().dg_scene_sectors_at(self._h, xs.ctypes.data_as(_P), ys.ctypes.data_as(_P), xs.size, out.ctypes.data_as(_P)))
+        return out
+
+    def mobj_poses(self) -> np.ndarray:
+        """dg_scene_mobj_poses: every map object's pose and sector as loaded (MOBJ_PLACED_DTYPE array)."""
+        n = lib().dg_scene_mobj_count(self._h)
+        out = np.zeros(max(n, 0), dtype=MOBJ_PLACED_DTYPE)
+        _check(lib().dg_scene_mobj_poses(self._h, out.ctypes.data_as(_P), n))
+        return out
+
     def map_lines(self, W: int, H: int, view=None) -> np.ndarray:
         """dg_map_lines: the lines of one 2-D map frame in draw order, (n, 5) int64 rows [x0, y0, x1, y1, rgb] (rgb = r | g<<8 | b<<16);
         view None: the linedefs only."""
@@ -692,6 +754,34 @@ class Context:
             _check(lib().dg_submit_views(self._h, slot, views, len(views) if n is None else n))
         else:
             _check(lib().dg_submit_views_state(self._h, slot, views, states, len(views) if n is None else n))
+
+    def submit_poses(self, slot: int, views, poses, n=None, states=None):
+        """dg_submit_views_poses: submit() with a dg_view_poses per view (make_view_poses; None: none)."""
+        _check(lib().dg_submit_views_poses(self._h, slot, views, states, poses, len(views) if n is None else n))
+
+    def render_poses(self, views, poses, states=None) -> np.ndarray:
+        """dg_render_views_poses: synchronous, slot 0; returns (n, H, W, 3) uint8."""
+        n = len(views)
+        out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
+        _check(lib().dg_render_views_poses(self._h, views, states, poses, n, out.ctypes.data_as(_P)))
+        return out
+
+    def submit_bundle_poses(self, slot: int, views, what: int, poses, n=None, states=None):
+        """dg_submit_bundle_views_poses: submit_bundle() with a dg_view_poses per view."""
+        _check(lib().dg_submit_bundle_views_poses(self._h, slot, views, states, poses, len(views) if n is None else n, what))
+
+    def slot_mobj_poses(self, slot: int, first: int, count: int) -> np.ndarray:
+        """dg_slot_mobj_poses: the pose rows (count, map objects) of MOBJ_PLACED_DTYPE the slot's frames were drawn with."""
+        n = lib().dg_scene_mobj_count(self._scene._h) if self._scene is not None else 0
+        out = np.zeros((max(count, 0), max(n, 0)), dtype=MOBJ_PLACED_DTYPE)
+        _check(lib().dg_slot_mobj_poses(self._h, slot, first, count, out.ctypes.data_as(_P)))
+        return out
+
+    def mobj_pose_timing(self, slot: int) -> float:
+        """dg_slot_mobj_pose_timing: GPU time (ms) of the pose kernels of the slot's last submission (0: none ran)."""
+        t = ctypes.c_float()
+        _check(lib().dg_slot_mobj_pose_timing(self._h, slot, ctypes.byref(t)))
+        return t.value
 
     def submit_map(self, slot: int, views, n=None):
         """dg_submit_map_views: 2-D map frames (the reference's viewing_map) into the slot, asynchronously."""

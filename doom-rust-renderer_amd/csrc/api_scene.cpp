@@ -245,6 +245,34 @@ int dg_build_lists_owners(const dg_scene *s, int width, int height, const dg_vie
     return DG_OK;
 }
 
+int dg_build_lists_poses(const dg_scene *s, int width, int height, const dg_view *view, const dg_view_poses *poses, dg_frame_lists *out, const uint32_t **owners) {
+    if (!s || !view || !out) return set_err(DG_ERR_INVALID, "null argument");
+    if (poses && poses->n && !poses->poses) return set_err(DG_ERR_INVALID, "view poses with a null array");
+    std::string err;
+    int rc = owners ? check_label_scene(*s->sc, err) : DG_OK;
+    if (rc) return set_err(rc, err);
+    dg_view v = *view;
+    fill_view_trig(v);
+    rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, nullptr, &s->sc->fx, poses);
+    if (rc) return set_err(rc, err);
+    if (owners) *owners = lists_arena().owners.data();
+    return DG_OK;
+}
+
+int dg_scene_sectors_at(const dg_scene *s, const float *x, const float *y, int n, int32_t *sector_out) {
+    if (!s || n < 0 || (n > 0 && (!x || !y || !sector_out))) return set_err(DG_ERR_INVALID, n < 0 ? "n must not be negative" : "null argument");
+    for (int i = 0; i < n; i++) sector_out[i] = s->sc->sector_from_vertex(x[i], y[i]);
+    return DG_OK;
+}
+
+int dg_scene_mobj_poses(const dg_scene *s, dg_mobj_placed *out, int n) {
+    if (!s || !out) return set_err(DG_ERR_INVALID, "null argument");
+    const Scene &sc = *s->sc;
+    if (n < 0 || (size_t)n != sc.mobjs.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_mobj_count");
+    for (size_t i = 0; i < sc.mobjs.size(); i++) out[i] = dg_mobj_placed{sc.mobjs[i].x, sc.mobjs[i].y, sc.mobjs[i].angle, sc.mobjs[i].sector};
+    return DG_OK;
+}
+
 int dg_scene_sprite_frame(dg_scene *s, const char *sprite, uint8_t frame) {
     if (!s || !sprite) return set_err(DG_ERR_INVALID, "null argument");
     std::string err;

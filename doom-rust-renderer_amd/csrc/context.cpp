@@ -145,7 +145,7 @@ void fill_walk_params(dg_ctx *c, Slot &s, int n) {
 // submission, and a bundle that says so (want_owners), needs owner tags: the tags of the wall records then go into the slot's owner array
 // as well (the caller has allocated it), from given_owners[i] for the caller's lists.
 int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, int32_t fe = DG_FE_HOST,
-                     const uint32_t *const *given_owners = nullptr, bool want_owners = false) {
+                     const uint32_t *const *given_owners = nullptr, bool want_owners = false, const dg_view_poses *poses = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -165,7 +165,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
             dg_view v = views[i];
             fill_view_trig(v);
             dg_frame_lists fl;
-            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx);
+            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr);
             if (!rc[(size_t)i]) rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
             if (labels && !rc[(size_t)i]) rc[(size_t)i] = wall_owners(sc, fl, c->arenas[(size_t)wid]->owners.data(), c->label_tags[(size_t)i], errs[(size_t)i]);
         }
@@ -203,7 +203,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
 
 // DG_FE_DEVICE: build the per-seg / per-sprite records of n views in parallel, pack them into the slot's record slab,
 // fill slot.FP / slot.P.  Returns kPartsUnsupported when the batch has to go through build_batch_host instead.
-int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states) {
+int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -215,7 +215,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         FeFrameOut &o = c->fe_out[(size_t)i];
         dg_view v = views[i];
         fill_view_trig(v);
-        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx);
+        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr);
         if (rc[(size_t)i]) return;
         o.parts.swap(A.parts); o.sprites.swap(A.sprites); o.behind.swap(A.behind); o.sky_parts.swap(A.sky_parts);
         o.bin_off.swap(A.bin_off); o.bin_parts.swap(A.bin_parts); o.sbin_off.swap(A.sbin_off); o.sbin_sprites.swap(A.sbin_sprites);
@@ -289,7 +289,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     s.keep_states(states, n);
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (n >= 64 && !states) c->fe_auto.host_batch((double)s.host_ms, n);      // DG_FE_AUTO's measurement of the host side
+    if (n >= 64 && !states && !poses) c->fe_auto.host_batch((double)s.host_ms, n);      // DG_FE_AUTO's measurement of the host side
     HIP_TRY(hipMemcpyAsync(s.d_fe.get(), s.h_fe.get(), L.total, hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
@@ -337,6 +337,7 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
     const size_t segs = t.add(sc.fs_segs), leaf = t.add(sc.fs_seg_leaf), first = t.add(sc.fs_leaf_first), sectors = t.add(sc.fs_sectors);
     const size_t anims = t.add(sc.fs_anims), bitmaps = t.add(sc.fs_bitmaps), sky = t.add(sc.flat_sky), mobjs = t.add(sc.fs_mobjs);
     const size_t sframes = t.add(sc.sprite_frames), aoff = t.add(sc.fs_anc_off), anc = t.add(sc.fs_anc);
+    const size_t wnodes = t.add(sc.walk_nodes), wleaf = t.add(sc.walk_leaf_sector);       // the pose kernels' descent (mobj_pose_core.h)
     HIP_TRY(t.upload(c->d_fs_scene));
     FsParams &P = c->fs_proto;
     P = FsParams{};
@@ -359,6 +360,24 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
     P.cl_rows = reinterpret_cast<uint32_t *>(d + L.cl_rows);
     P.keep_rows = reinterpret_cast<uint32_t *>(d + L.keep_rows);
     P.cl_row_cap = L.cl_row_cap;
+    // per-view poses: the scene's pointers of the pose kernels, and every slot's rows and entry staging, sized by the scene like the
+    // scratch above.  A slot whose buffers cannot be had sends its batches with poses through the host walker (build_batch_fs).
+    c->pose_proto = PoseParams{};
+    if (P.n_mobjs && !sc.walk_nodes.empty()) {
+        PoseParams &Z = c->pose_proto;
+        Z.scene_rows = P.mobjs; Z.nodes = t.at<WalkNode>(wnodes); Z.leaf_sector = t.at<int32_t>(wleaf);
+        Z.root = (int32_t)sc.walk_nodes.size() - 1;
+        Z.n_mobjs = P.n_mobjs;
+        const size_t cells = (size_t)c->cfg.max_batch * P.n_mobjs;
+        for (Slot &s : c->slots) {
+            Slot::PerScene &b = s.per_scene;
+            if (hip_alloc(b.d_pose_rows, cells * sizeof(FsMobj)) != hipSuccess || hip_alloc(b.h_pose_entries, cells * sizeof(PoseEntry)) != hipSuccess ||
+                hip_alloc(b.d_pose_entries, cells * sizeof(PoseEntry)) != hipSuccess) {
+                b.d_pose_rows.reset(); b.h_pose_entries.reset(); b.d_pose_entries.reset();
+                (void)hipGetLastError();
+            }
+        }
+    }
     c->fs_scene_ok = true;
     return DG_OK;
 }
@@ -409,7 +428,7 @@ void wire_rows(Rows &R, const Rows &proto, const dg_view *views, int n_frames, c
 // DG_FE_DEVICE_SEGS: nothing of the front end runs on the host.  Per frame it ships the view (trig filled) and the DevFrame header,
 // per batch the scene's current light levels and map-object states; dg_fs_* then write the same record arrays build_batch_fe packs,
 // with fixed per-frame strides (fs_frame.h), into the slot's record slab.
-int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states) {
+int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -428,6 +447,24 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     const size_t mmask_words = (sc.mobjs.size() + 31) / 32;
     const FsLayout L = fs_layout((size_t)n, (size_t)W, sc.sectors.size(), sc.mobjs.size(), states != nullptr, lfx, mfx, c->fs_proto.sprite_stride, c->fs_proto.sbin_stride);
     if (L.total > c->fe_slab_cap) return kPartsUnsupported;
+    // per-view poses: the entries that stand, frame after frame, into the slot's staging; the pose kernels write the rows from them.
+    // Without the slot's pose buffers (their allocation failed at dg_upload_scene) the batch takes the host walker, and is counted.
+    uint32_t n_pose_entries = 0;
+    const bool pose_rows = poses && !sc.mobjs.empty();
+    if (poses && sc.mobjs.empty())                                    // (no entry can be valid)
+        for (int i = 0; i < n; i++)
+            if (poses[i].n) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": view poses: map object index out of range");
+    if (pose_rows) {
+        if (!s.per_scene.d_pose_rows || !c->pose_proto.nodes || (uint64_t)n * sc.mobjs.size() >= (1ull << 31)) { c->fallbacks_fe++; return kPartsUnsupported; }
+        FrameArena &A = *c->arenas[0];
+        PoseEntry *const he = s.per_scene.h_pose_entries.get();
+        for (int i = 0; i < n; i++) {
+            const bool ok = resolve_view_poses(sc, poses[i], A.pose_of, A.poses);
+            for (const dg_mobj_pose &p : A.poses) he[n_pose_entries++] = PoseEntry{i, p.mobj, p.x, p.y, p.angle};     // (at most one per object and frame: the staging holds them)
+            release_view_poses(A.pose_of, A.poses);
+            if (!ok) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": view poses: map object index out of range");
+        }
+    }
     uint8_t *const h = s.h_fe.get(), *const d = s.d_fe.get();
     s.views.assign(views, views + n);
     c->pool->parallel_for(n, [&](int i, int) {
@@ -469,6 +506,13 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     Q.mstate_stride = states ? (uint32_t)sc.mobjs.size() : 0u;
     Q.views = reinterpret_cast<const dg_view *>(d + L.views);
     Q.n_frames = n;
+    s.PP = PoseParams{};
+    if (pose_rows) {                                       // the seg walk reads the rows dg_mobj_pose_fill / _place write
+        s.PP = c->pose_proto;
+        s.PP.entries = s.per_scene.d_pose_entries.get(); s.PP.rows = s.per_scene.d_pose_rows.get();
+        s.PP.n_frames = (uint32_t)n; s.PP.n_entries = n_pose_entries;
+        Q.mobjs = s.PP.rows; Q.mobj_stride = s.PP.n_mobjs;
+    }
     s.LR = LfxRows{};
     if (lfx) wire_rows(s.LR, c->lfx_proto, Q.views, n, states ? reinterpret_cast<const uint32_t *>(d + L.lmask) : nullptr,
                        reinterpret_cast<int16_t *>(d + (states ? L.lights : L.lrows)), sc.sectors.size(), Q.sector_light, Q.light_stride);
@@ -491,19 +535,20 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(d, h, L.upload, hipMemcpyHostToDevice, s.stream.get()));
+    if (n_pose_entries) HIP_TRY(hipMemcpyAsync(s.per_scene.d_pose_entries.get(), s.per_scene.h_pose_entries.get(), (size_t)n_pose_entries * sizeof(PoseEntry), hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
 
-int build_batch(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr) {
+int build_batch(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, const dg_view_poses *poses = nullptr) {
     if (!given && c->fs_enabled && c->fs_scene_ok && choose_fs(c, views, n)) {
-        const int rc = build_batch_fs(c, s, views, n, states);
+        const int rc = build_batch_fs(c, s, views, n, states, poses);
         if (rc != kPartsUnsupported) return rc;
     }
     if (!given && c->fe_enabled && c->fe_scene_ok) {
-        const int rc = build_batch_fe(c, s, views, n, states);
+        const int rc = build_batch_fe(c, s, views, n, states, poses);
         if (rc != kPartsUnsupported) return rc;
     }
-    return build_batch_host(c, s, views, given, n, states);
+    return build_batch_host(c, s, views, given, n, states, DG_FE_HOST, nullptr, false, poses);
 }
 
 // The 2-D map view's linedef layer of the uploaded scene, on the kernel stream (timed by the slot's ev_start / ev_setup).  The line records
@@ -677,6 +722,7 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
             if (c->fs_rows_dirty) HIP_TRY(hipMemsetAsync(c->d_fs_scratch.get(), 0, c->fs_zero_bytes, ks));    // (dg_fs_frame leaves its rows clean)
             c->fs_rows_dirty = true;
             hipEvent_t fs_start = s.ev_start.get();
+            if (s.PP.n_frames > 0) { HIP_TRY(launch_mobj_poses(s.PP, ks, fs_start, s.ev_pose.get())); fs_start = nullptr; }   // the rows dg_fs_frame's map-object phase reads
             if (s.LR.n_frames > 0) { HIP_TRY(launch_light_rows(s.LR, ks, fs_start)); fs_start = nullptr; }     // the rows dg_fs_* read
             if (s.MR.n_frames > 0) { HIP_TRY(launch_mobj_rows(s.MR, ks, fs_start)); fs_start = nullptr; }
             HIP_TRY(c->fx.wall.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
@@ -710,7 +756,7 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     fill_view_trig(v);
     dg_frame_lists fl;
     Slot::RedoState redo_state;
-    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->fx), &c->fx);
+    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->fx), &c->fx, s.poses_of(i));
     if (!rc) rc = bin_frame(sc, c->fk, fl, bf, err);
     if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
@@ -768,7 +814,7 @@ int redo_overflowed(dg_ctx *c, Slot &s) {
         any_state |= st != nullptr;
         sts.push_back(st ? *st : dg_view_state{nullptr, 0, nullptr, 0});
     }
-    int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), any_state ? sts.data() : nullptr);
+    int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), any_state ? sts.data() : nullptr, DG_FE_HOST, nullptr, false, s.poses_of(0));
     if (rc) return rc;
     rc = enqueue_kernels(c, s);
     if (rc) return rc;
@@ -939,14 +985,23 @@ int take_slot(dg_ctx *c, Slot &s) {
     return s.phase == Slot::Phase::Queued || s.copy_pending ? make_final(c, s, Copy::Complete) : DG_OK;
 }
 
+// What a submission built for the slot leaves for later: whether it came from views, and then a copy of their poses (the caller's
+// arrays need not outlive the call).
+void built_from(Slot &s, const dg_view *views, const dg_view_poses *poses, int n) {
+    s.from_views = views != nullptr;
+    s.keep_poses(views ? poses : nullptr, n);
+}
+
 // Slot `slot` for a new submission of n views (or of the caller's lists), and its kernels enqueued.
-int submit(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states) {
+int submit(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states, const dg_view_poses *poses = nullptr) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     int rc = take_slot(c, s);
     if (rc) return rc;
-    rc = build_batch(c, s, views, given, n, states);
-    return rc ? rc : enqueue_kernels(c, s);
+    rc = build_batch(c, s, views, given, n, states, poses);
+    if (rc) return rc;
+    built_from(s, views, poses, n);
+    return enqueue_kernels(c, s);
 }
 
 // The synchronous calls' tail, given what their submission returned: its results through `read` when an output was handed over, or
@@ -1012,6 +1067,7 @@ int submit_depth(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists
     if (rc) return rc;
     rc = build_batch_host(c, s, views, given, n, states, DG_FE_DEPTH);
     if (rc) return rc;
+    built_from(s, views, nullptr, n);
     const BundlePlanes out = planes_of(c, s);
     return launched(s, launch_depth(s.P, out.dist, out.kind, s.stream.get(), s.ev_rstart.get(), s.ev_raster.get()), "launch_depth");
 }
@@ -1030,6 +1086,7 @@ int submit_labels(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     if ((rc = ensure_label_buffers(c, s))) return rc;
     rc = build_batch_host(c, s, views, given, n, states, DG_FE_LABELS, owners);
     if (rc) return rc;
+    built_from(s, views, nullptr, n);
     const BundlePlanes out = planes_of(c, s);
     return launched(s, launch_labels(s.P, s.d_owners.get(), out.id, out.cls, out.boxes, out.n_mobjs, s.stream.get(), s.ev_rstart.get(), s.ev_setup.get(), s.ev_raster.get()), "launch_labels");
 }
@@ -1065,7 +1122,7 @@ int enqueue_bundle(dg_ctx *c, Slot &s) {
 // Slot `slot` for a bundle of n views (or of the caller's lists, with their owner tags when labels are asked for): the host list path
 // whatever front end the ctx has, one list build and one upload for every part.
 int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, const uint32_t *const *owners, int n, const dg_view_state *states,
-                  uint32_t what) {
+                  uint32_t what, const dg_view_poses *poses = nullptr) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     if (const int bad = check_batch(c, n)) return bad;
@@ -1076,11 +1133,12 @@ int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     if (labels && (rc = check_label_scene(*c->scene, err))) return set_err(rc, err);
     if ((rc = take_slot(c, s))) return rc;
     if (labels && (rc = ensure_label_buffers(c, s))) return rc;
-    rc = build_batch_host(c, s, views, given, n, states, DG_FE_BUNDLE, owners, labels);
+    rc = build_batch_host(c, s, views, given, n, states, DG_FE_BUNDLE, owners, labels, poses);
     if (rc) {
         if (s.phase == Slot::Phase::Prepared && s.front_end == DG_FE_BUNDLE) s.reset();   // (described, then an upload failed: nothing says yet which parts it has)
         return rc;
     }
+    built_from(s, views, poses, n);
     s.bundle_what = what;
     return enqueue_bundle(c, s);
 }
@@ -1092,6 +1150,13 @@ int bundle_times(const Slot &s, float *setup_ms, float *raster_ms, float *tiles_
     if (setup_ms) { *setup_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(setup_ms, s.ev_start.get(), s.ev_setup.get())); }
     if (raster_ms) { *raster_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(raster_ms, s.ev_rstart.get(), tiles ? s.ev_cend.get() : s.ev_raster.get())); }
     if (tiles_ms) { *tiles_ms = 0.0f; if (tiles) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_tiles.get(), s.ev_raster.get())); }
+    return DG_OK;
+}
+
+int check_view_poses(const dg_view_poses *poses, int n) {
+    if (poses)
+        for (int i = 0; i < n; i++)
+            if (poses[i].n && !poses[i].poses) return set_err(DG_ERR_INVALID, "view poses with a null array");
     return DG_OK;
 }
 
@@ -1144,6 +1209,7 @@ int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int
     if (mask) std::memcpy(s.per_scene.h_masks.get(), mask, mask_bytes);
     s.map = Slot::MapState{ego ? *ego : dg_ego_map{}, mask != nullptr, false};
     s.describe(fe, n, bytes + mask_bytes, 0, 0);
+    built_from(s, nullptr, nullptr, n);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream.get()));
     if (mask) HIP_TRY(hipMemcpyAsync(s.per_scene.d_masks.get(), s.per_scene.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream.get()));
@@ -1241,7 +1307,7 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
     }
     for (Slot &s : c->slots) {
         HIP_TRY(stream_create(s.stream));
-        for (Event *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles}) HIP_TRY(event_create(*ev));
+        for (Event *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles, &s.ev_pose}) HIP_TRY(event_create(*ev));
         HIP_TRY(event_create(s.ev_h2d, false));            // (it only orders streams)
         HIP_TRY(stream_create(s.copy_stream));
         HIP_TRY(hip_alloc(s.h_lists, lists_cap));
@@ -1341,12 +1407,67 @@ int dg_render_views_state(dg_ctx *c, const dg_view *views, const dg_view_state *
 }
 
 int dg_submit_views_state(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, int n) {
+    return dg_submit_views_poses(c, slot, views, states, nullptr, n);
+}
+
+int dg_submit_views_poses(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, int n) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
     rc = check_view_states(states, n);
+    if (!rc) rc = check_view_poses(poses, n);
     if (rc) return rc;
-    return submit(c, slot, views, nullptr, n, states);
+    return submit(c, slot, views, nullptr, n, states, poses);
+}
+
+int dg_render_views_poses(dg_ctx *c, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, int n, uint8_t *out) {
+    return read_or_wait(c, 0, dg_submit_views_poses(c, 0, views, states, poses, n), n, out);
+}
+
+int dg_slot_mobj_poses(dg_ctx *c, int slot, int first, int count, dg_mobj_placed *out) {
+    static_assert(sizeof(dg_mobj_placed) == sizeof(FsMobj) && offsetof(dg_mobj_placed, sector) == offsetof(FsMobj, sector), "dg_mobj_placed / FsMobj");
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (s.phase == Slot::Phase::Empty || !s.from_views || !c->scene) return set_err(DG_ERR_STATE, "dg_slot_mobj_poses: the slot holds no view submission");
+    if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad frame range");
+    if (count == 0) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    rc = make_final(c, s, Copy::Leave);                    // (a seg-walk batch redone as a whole is a host-list batch from here on)
+    if (rc) return rc;
+    const Scene &sc = *c->scene;
+    const size_t n_mobjs = sc.mobjs.size();
+    if (n_mobjs == 0) return DG_OK;
+    if (s.seg_walk() && s.PP.n_frames > 0) {               // the rows the pose kernels wrote
+        HIP_TRY(hipMemcpyAsync(out, s.PP.rows + (size_t)first * n_mobjs, (size_t)count * n_mobjs * sizeof(FsMobj), hipMemcpyDeviceToHost, s.stream.get()));
+        HIP_TRY(slot_sync(s));
+        return DG_OK;
+    }
+    FrameArena &A = *c->arenas[0];                         // the host walker's rule (Walker::mobj_placed) over the kept entries
+    for (int i = 0; i < count; i++) {
+        dg_mobj_placed *row = out + (size_t)i * n_mobjs;
+        std::memcpy(row, sc.fs_mobjs.data(), n_mobjs * sizeof(FsMobj));
+        const dg_view_poses *vp = s.poses_of(first + i);
+        if (!vp) continue;
+        (void)resolve_view_poses(sc, *vp, A.pose_of, A.poses);
+        for (const dg_mobj_pose &p : A.poses) row[p.mobj] = dg_mobj_placed{p.x, p.y, p.angle, sc.sector_from_vertex(p.x, p.y)};
+        release_view_poses(A.pose_of, A.poses);
+    }
+    return DG_OK;
+}
+
+int dg_slot_mobj_pose_timing(dg_ctx *c, int slot, float *ms) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!ms) return set_err(DG_ERR_INVALID, "null argument");
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    rc = make_final(c, s, Copy::Leave);
+    if (rc) return rc;
+    *ms = 0.0f;
+    if (s.seg_walk() && s.PP.n_frames > 0) HIP_TRY(hipEventElapsedTime(ms, s.ev_start.get(), s.ev_pose.get()));
+    return DG_OK;
 }
 
 int dg_wait(dg_ctx *c, int slot) {
@@ -1486,6 +1607,7 @@ int dg_prepare_views(dg_ctx *c, int slot, const dg_view *views, int n) {
     rc = build_batch(c, s, views, nullptr, n);
     c->preparing = false;
     if (rc) return rc;
+    built_from(s, views, nullptr, n);
     if (s.column_walk()) {        // run the column walk once so that a batch that has to go through the host list path as a whole
         rc = enqueue_kernels(c, s);   // is re-prepared that way now, not on a replay
         if (rc) return rc;
@@ -1698,13 +1820,18 @@ int dg_bundle_capacity(const dg_ctx *c, uint32_t what) {
 }
 
 int dg_submit_bundle_views(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, int n, uint32_t what) {
+    return dg_submit_bundle_views_poses(c, slot, views, states, nullptr, n, what);
+}
+
+int dg_submit_bundle_views_poses(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, int n, uint32_t what) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
     if ((rc = check_bundle_what(what))) return rc;
     rc = check_view_states(states, n);
+    if (!rc) rc = check_view_poses(poses, n);
     if (rc) return rc;
-    return submit_bundle(c, slot, views, nullptr, nullptr, n, states, what);
+    return submit_bundle(c, slot, views, nullptr, nullptr, n, states, what, poses);
 }
 
 int dg_bundle_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uint32_t *const *owners, int n, uint32_t what) {

@@ -21,6 +21,7 @@
 #include "kernels.hpp"
 #include "light_fx_kernels.hpp"
 #include "mobj_fx_kernels.hpp"
+#include "mobj_pose_kernels.hpp"
 #include "plane_kernels.hpp"
 #include "pool.hpp"
 #include "reduce_core.h"
@@ -44,6 +45,7 @@ struct Slot {
     // bundles: the end of the colour raster launch when dg_bundle_tiles follows it (ev_raster is then that kernel's end: always the end of
     // the submission's LAST kernel), and dg_bundle_tiles' start
     Event ev_cend, ev_tiles;
+    Event ev_pose;                // the end of the pose kernels, which are the first of a seg-walk batch with poses (ev_start is their start)
     // ev_raster has been recorded at least once: slot_sync waits only on an event that has.  Not part of the phase below, because it is
     // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
     bool raster_recorded = false;
@@ -84,6 +86,12 @@ struct Slot {
         PinnedPtr<uint32_t> h_masks;     // map frames: the mask rows of the last submission that had any (staging + HBM, max_batch x
         DevPtr<uint32_t> d_masks;        // mask_words), kept for dg_replay_slot
         size_t mask_words = 0;
+        // per-view map-object poses through the seg walk: the rows max_batch x map objects the pose kernels write, and
+        // the de-duplicated entries' staging + HBM (as many at the most).  Unlike the others these are taken at dg_upload_scene
+        // (upload_fs_scene), so that nothing is allocated on the submit path; empty: batches with poses take the host walker.
+        DevPtr<FsMobj> d_pose_rows;
+        PinnedPtr<PoseEntry> h_pose_entries;
+        DevPtr<PoseEntry> d_pose_entries;
         void drop() { *this = PerScene{}; }
     } per_scene;
     // What a map submission (front_end DG_FE_MAP*) leaves for its kernels and for dg_replay_slot besides d_lists (the arrow lines, then a
@@ -109,7 +117,7 @@ struct Slot {
     } phase = Phase::Empty;
     bool has_run() const { return phase >= Phase::Queued; }                        // the timing events are this submission's
     bool unchecked() const { return phase == Phase::Queued && column_walk(); }     // its overflow flags still have to be looked at
-    void reset() { phase = Phase::Empty; n_frames = 0; snap_scene = nullptr; }     // (nothing may be replayed or redone from what the slot holds)
+    void reset() { phase = Phase::Empty; n_frames = 0; snap_scene = nullptr; from_views = false; }     // (nothing may be replayed or redone from what the slot holds)
     // device column walk (DG_FE_DEVICE)
     PinnedPtr<uint8_t> h_fe;                    // record slab: pinned staging
     DevPtr<uint8_t> d_fe;                       // ... and HBM
@@ -124,6 +132,7 @@ struct Slot {
     FsParams FSP{};               // DG_FE_DEVICE_SEGS: the device seg walk in front of the column walk
     LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
     MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
+    PoseParams PP{};              // ... and, for a batch with poses, dg_mobj_pose_fill / _place in front of them all (PP.n_frames 0: not launched)
     // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
     // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP / DG_FE_MAP_EXPLORED / DG_FE_MAP_EGO (2-D map frames: arrow lines at the start of d_lists) or
     // DG_FE_DEPTH (host lists walked by dg_depth_tiles: the framebuffer slab holds the two planes, not RGB24) or DG_FE_LABELS (host lists
@@ -163,6 +172,20 @@ struct Slot {
     std::vector<dg_view_state> states;
     std::vector<dg_sector_light> state_lights;
     std::vector<dg_mobj_state> state_mobjs;
+    // ... and of their poses, kept by every view submission whatever its front end: a frame redone on the host is drawn with them,
+    // and dg_slot_mobj_poses derives the rows of a host-walker submission from them.  from_views: the slot's submission was built from
+    // views (not from the caller's lists, not a 2-D map submission) — the submit functions say so once it is built.
+    std::vector<dg_view_poses> poses;
+    std::vector<dg_mobj_pose> pose_entries;
+    bool from_views = false;
+    const dg_view_poses *poses_of(int i) const { return poses.empty() ? nullptr : &poses[(size_t)i]; }
+    void keep_poses(const dg_view_poses *ps, int n) {
+        poses.clear(); pose_entries.clear();
+        if (!ps) return;
+        for (int i = 0; i < n; i++) pose_entries.insert(pose_entries.end(), ps[i].poses, ps[i].poses + ps[i].n);
+        size_t o = 0;
+        for (int i = 0; i < n; i++) { poses.push_back(dg_view_poses{pose_entries.data() + o, ps[i].n}); o += ps[i].n; }
+    }
     // The scene's own light levels and map-object states as they were when the batch was submitted: a frame that overflows a capacity is
     // redone at dg_wait time from the host walker, and dg_scene_set_sector_light / _mobj_state may have moved the scene on by then
     // (lights.rs:47-259 and map_objects.rs:63-121 run between two submissions of a pipelined caller).
@@ -268,6 +291,7 @@ struct dg_ctx {
     DevPtr<uint8_t> d_fs_scratch;       // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
     size_t fs_zero_bytes = 0;
     FsParams fs_proto{};                // scene pointers and counts, filled at upload
+    PoseParams pose_proto{};            // the pose kernels' scene pointers (the scene's rows, the BSP, the leaves' sectors), filled at upload
     uint64_t fallbacks_fe = 0;          // batches in which frames were redone because a device-side capacity was exceeded (dg_ctx_fallbacks)
     uint64_t redone_frames = 0;         // frames redone through the host list path, one at a time (dg_ctx_redone_frames)
     DevPtr<DevRSpan> d_redo_rspans;     // resolved spans of ONE frame being redone (allocated on first use)

@@ -120,6 +120,7 @@ struct Walker {
     const WallFx *fx = nullptr;             // the wall effects to draw with (nullptr: none)
     const LightFx *lfx = nullptr;           // the light effects to draw with (nullptr: none)
     const MobjFx *mfx = nullptr;            // the map-object thinkers to draw with (nullptr: none)
+    const dg_view_poses *poses = nullptr;   // where this view's map objects are (nullptr: where the scene has them)
     uint32_t cur_owner = 0;                 // owner tag of the seg / map object being processed (host-list mode)
     static constexpr int32_t kNoOverride = INT32_MIN;
 
@@ -127,9 +128,9 @@ struct Walker {
     // (src/lights.rs:47-259, src/map_objects.rs:63-121): the view's snapshot entry if there is one, else the light effect's level
     //  or the map-object thinker's state (§8d), else the scene's value.  The arena's two rows hold what overrides the
     // scene: the effects' values, every effect sector and driven object once per frame, then the view's entries on top.
-    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const SceneFx *f)
+    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const SceneFx *f, const dg_view_poses *ps)
         : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e), state(st), fx(f && f->wall.on() ? &f->wall : nullptr),
-          lfx(f && f->light.fits(s) ? &f->light : nullptr), mfx(f && f->mobj.fits(s) ? &f->mobj : nullptr) {
+          lfx(f && f->light.fits(s) ? &f->light : nullptr), mfx(f && f->mobj.fits(s) ? &f->mobj : nullptr), poses(ps) {
         ppos = V2{v.x, v.y};
         player_height = v.floor_height + kEye;
         if (A.light_row.size() != sc.sectors.size()) A.light_row.assign(sc.sectors.size(), kNoOverride);
@@ -138,6 +139,7 @@ struct Walker {
             for (size_t r = 0; r < lfx->recs.size(); r++) A.light_row[lfx->recs[r].sector] = lfx->level(r, v.timestamp);
         if (mfx)
             for (uint32_t i : mfx->driven) A.mobj_row[i] = mfx->value(i, v.timestamp);
+        if (poses && !resolve_view_poses(sc, *poses, A.pose_of, A.poses)) { status = DG_ERR_INVALID; err = "view poses: map object index out of range"; }
         if (!state) return;
         const unsigned bad = apply_view_state(sc, *state, [&](size_t i, int32_t level) { A.light_row[i] = level; }, [&](size_t i, int32_t val) { A.mobj_row[i] = val; });
         if (bad) { status = DG_ERR_INVALID; err = bad & 2u ? "view state: map object or sprite frame index out of range" : "view state: sector index out of range"; }
@@ -148,6 +150,15 @@ struct Walker {
         if (mfx)
             for (uint32_t i : mfx->driven) A.mobj_row[i] = kNoOverride;
         if (state) apply_view_state(sc, *state, [&](size_t i, int32_t) { A.light_row[i] = kNoOverride; }, [&](size_t i, int32_t) { A.mobj_row[i] = kNoOverride; });
+        if (poses) release_view_poses(A.pose_of, A.poses);
+    }
+    // MapObject.position / .angle and get_sector_from_vertex(position) as draw_map_objects reads them for this frame
+    // (renderer/map_objects.rs:55,74,99-116): the view's pose if it has one for the object, else the scene's row.
+    FsMobj mobj_placed(size_t i) const {
+        const int32_t at = poses ? A.pose_of[i] : -1;
+        if (at < 0) return sc.fs_mobjs[i];
+        const dg_mobj_pose &p = A.poses[(size_t)at];
+        return FsMobj{p.x, p.y, p.angle, sc.sector_from_vertex(p.x, p.y)};
     }
     int16_t sector_light(int sector) const {
         const int32_t v = A.light_row[(size_t)sector];
@@ -441,7 +452,7 @@ struct Walker {
             int32_t m_sprite_frame, m_full_bright;
             mobj_state(mi, m_sprite_frame, m_full_bright);
             if (m_sprite_frame < 0) continue;                         // S_NULL
-            const FsMobj &fm = sc.fs_mobjs[mi];
+            const FsMobj fm = mobj_placed(mi);
             const FsSpriteFrame &sf = sc.sprite_frames_fs()[(size_t)m_sprite_frame];
             const int16_t light = fm.sector >= 0 ? sector_light(fm.sector) : (int16_t)0;
             FsSpriteOut so;
@@ -523,7 +534,8 @@ struct Walker {
 
 }  // namespace
 
-int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const SceneFx *fx) {
+int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const SceneFx *fx,
+                      const dg_view_poses *poses) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.renders.clear(); A.owners.clear(); A.columns.clear(); A.visplanes.clear(); A.plane_tb.clear(); A.order.clear();
     A.recs->clear(); A.floor_tb.clear(); A.ceil_tb.clear();
@@ -533,7 +545,7 @@ int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameA
     A.top_clip.resize((size_t)W);
     A.bottom_clip.resize((size_t)W);
 
-    Walker wk(sc, W, H, view, A, err, state, fx);
+    Walker wk(sc, W, H, view, A, err, state, fx, poses);
     if (wk.status) return wk.status;
     wk.walk_bsp();
     if (wk.status) return wk.status;
@@ -581,11 +593,12 @@ void bin_by_columns(const std::vector<T> &recs, int W, Range range, std::vector<
 }
 }  // namespace
 
-int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state, const SceneFx *fx) {
+int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state, const SceneFx *fx,
+                      const dg_view_poses *poses) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.parts.clear(); A.sprites.clear(); A.behind.clear(); A.sky_parts.clear(); A.behind_words = 0; A.n_sky_slots = 0;
     A.recs->clear();
-    Walker wk(sc, W, H, view, A, err, state, fx);
+    Walker wk(sc, W, H, view, A, err, state, fx, poses);
     if (wk.status) return wk.status;
     wk.parts_mode = true;
     wk.walk_bsp();

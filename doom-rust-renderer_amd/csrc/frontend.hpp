@@ -49,6 +49,9 @@ struct FrameArena {
     // per sector / per map object: the value this view draws with (its snapshot entry, else the effect's value at its tics) or "no
     // override"; the Walker writes the entries of one frame and takes them back
     std::vector<int32_t> light_row, mobj_row;
+    // per map object: its entry in `poses`, the view's poses as they stand (resolve_view_poses), or -1; written and taken back likewise
+    std::vector<int32_t> pose_of;
+    std::vector<dg_mobj_pose> poses;
     FrameArena();
     ~FrameArena();
     FrameArena(const FrameArena &) = delete;
@@ -59,8 +62,9 @@ struct FrameArena {
 // reference would panic.  `view` must have its trig fields filled.
 // `state` (optional): the view's game-state snapshot (include/doomgpu.h dg_view_state).
 // `fx` (optional): the effects to draw with (Scene::fx, or the copy a dg_ctx uploaded); nullptr: none.
+// `poses` (optional): where the view's map objects are (include/doomgpu.h dg_view_poses); nullptr: where the scene has them.
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, dg_frame_lists &out, std::string &err,
-                      const dg_view_state *state = nullptr, const SceneFx *fx = nullptr);
+                      const dg_view_state *state = nullptr, const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr);
 
 // Checks a view's snapshot against the scene's ranges and hands every valid entry, in order (later entries win), to light(sector, level)
 // or mobj(map object, mfx_encode'd state).  Returns 0, or bit 0: a sector index was out of range, bit 1: a map object or sprite frame
@@ -81,6 +85,27 @@ unsigned apply_view_state(const Scene &sc, const dg_view_state &st, LightFn ligh
     return bad;
 }
 
+// A view's poses as they stand: every entry is checked against the scene's range, and of two entries for one object the later wins.
+// out: one entry per moved object, in the order of the objects' first entries; pose_of[object]: its place in out, else -1.  pose_of
+// must come in all -1 (or empty) and is handed back so by release_view_poses.  Returns false when an object index was out of range
+// (the entries that are in range still stand).  The host walker, build_batch_fs (context.cpp) and dg_slot_mobj_poses all go through it.
+inline bool resolve_view_poses(const Scene &sc, const dg_view_poses &vp, std::vector<int32_t> &pose_of, std::vector<dg_mobj_pose> &out) {
+    out.clear();
+    if (pose_of.size() != sc.mobjs.size()) pose_of.assign(sc.mobjs.size(), -1);
+    bool ok = true;
+    for (uint32_t i = 0; i < vp.n; i++) {
+        const dg_mobj_pose &p = vp.poses[i];
+        if (p.mobj < 0 || (size_t)p.mobj >= sc.mobjs.size()) { ok = false; continue; }
+        int32_t &at = pose_of[(size_t)p.mobj];
+        if (at < 0) { at = (int32_t)out.size(); out.push_back(p); }
+        else out[(size_t)at] = p;
+    }
+    return ok;
+}
+inline void release_view_poses(std::vector<int32_t> &pose_of, const std::vector<dg_mobj_pose> &out) {
+    for (const dg_mobj_pose &p : out) pose_of[(size_t)p.mobj] = -1;
+}
+
 void fill_view_trig(dg_view &v);
 
 // Parts mode: the per-seg and per-sprite half only (BSP order, transform, clip, projection, pegging, sprite sorting and the
@@ -89,7 +114,7 @@ void fill_view_trig(dg_view &v);
 // host list path can judge: the caller redoes the frame with build_frame_lists).
 constexpr int kPartsUnsupported = 1000;
 int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, std::string &err, const dg_view_state *state = nullptr,
-                      const SceneFx *fx = nullptr);
+                      const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr);
 
 // Per-record constants of render_vertical_bitmap_line (bitmap_render.rs:233-251), shared by the binner and the parts builder.
 DevWallRec make_wall_rec(const BitmapInfo &bi, float lsx, float lsy, float lex, float ley, float start_offset, int32_t start_x, int32_t end_x,

@@ -383,7 +383,7 @@ DG_HD bool fs_part_wants_sky_slot(uint32_t flags) {
 DG_HD bool fs_part_is_solid(uint32_t flags) { return !(flags & (FEP_LOWER | FEP_UPPER | FEP_ONLY_OCCL | FEP_TWO_SIDED_MID)); }
 
 // ---- one map object ----------------------------------------------------------------------------------------------------------------
-struct FsMobj { float x, y, angle; int32_t sector; };            // the immutable part (position never changes in the reference); sector < 0: outside the map
+struct FsMobj { float x, y, angle; int32_t sector; };            // where the object is: as loaded, or a view's pose (mobj_pose_core.h); sector < 0: outside the map
 static_assert(sizeof(FsMobj) == 16, "FsMobj layout");
 struct FsSpriteFrame { int32_t rotate; int32_t bitmap[8]; };     // sprites.rs:20-23
 

@@ -65,6 +65,7 @@ struct FsParams {
     const int16_t *sector_light;               // [n_sectors] for the whole batch (light_stride 0), or [n_frames][light_stride]: per-view game state
     const int32_t *mobj_state;                 // [n_mobjs] / [n_frames][mstate_stride]: sprite_frame * 2 + full_bright, negative: S_NULL
     uint32_t light_stride, mstate_stride;      // elements per frame of the two arrays above; 0: one array for every frame (lights.rs:47-259, map_objects.rs:63-121)
+    uint32_t mobj_stride;                      // elements per frame of `mobjs`: 0: the scene's table for every frame; n_mobjs: per-view pose rows (mobj_pose_core.h)
     // per frame
     const dg_view *views;                      // [n_frames], trig filled
     int32_t n_frames;
@@ -423,7 +424,7 @@ DG_HD void fs_ph_mobj(const FsParams &P, FsShared &S, int f, uint32_t base, int 
     const int32_t st = P.mobj_state[(size_t)f * P.mstate_stride + mi];
     if (st < 0) return;                                                // S_NULL (renderer/map_objects.rs:37)
     const dg_view &v = P.views[f];
-    const FsMobj &m = P.mobjs[mi];
+    const FsMobj &m = P.mobjs[(size_t)f * P.mobj_stride + mi];
     T.status = fs_mobj(P.k, m, P.sframes[st >> 1], P.bitmaps, P.sectors, V2{v.x, v.y}, v.angle, v.cos_na, v.sin_na, v.floor_height + 41.0f, st & 1,
                        m.sector >= 0 ? P.sector_light[(size_t)f * P.light_stride + (size_t)m.sector] : (int16_t)0, T.so);
     if (T.status == FS_OK) S.lane_cnt[lane] = 1;

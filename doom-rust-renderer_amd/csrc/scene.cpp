@@ -342,6 +342,7 @@ void Scene::build_walk_tables() {
         walk_nodes[i] = WalkNode{n.x, n.y, n.dx, n.dy, {child(n.rchild), child(n.lchild)}};
     }
     walk_leaves.assign(subsectors.size(), WalkLeaf{0.0f, 1u});
+    walk_leaf_sector.assign(subsectors.size(), -1);
     for (size_t l = 0; l < subsectors.size(); l++) {
         const SubSectorRec &ss = subsectors[l];
         for (int k = 0; k < ss.count; k++) {
@@ -350,6 +351,7 @@ void Scene::build_walk_tables() {
             const int sd = sg.direction ? ld.back : ld.front;
             if (sd < 0) continue;
             walk_leaves[l] = WalkLeaf{(float)sectors[(size_t)sidedefs[(size_t)sd].sector].floor_h, 0u};
+            walk_leaf_sector[l] = sidedefs[(size_t)sd].sector;
             break;
         }
     }

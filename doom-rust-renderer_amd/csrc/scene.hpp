@@ -55,7 +55,7 @@ struct MapObjectRec {                                            // map_objects.
     float x, y, angle;
     int32_t sprite_frame;   // index into Scene::sprite_frames, -1 = state S_NULL (skipped: renderer/map_objects.rs:37)
     int32_t full_bright;
-    int32_t sector;         // get_sector_from_vertex(position) — position is immutable in the reference
+    int32_t sector;         // get_sector_from_vertex(position) as loaded; a view's pose (dg_view_poses) moves the object and derives it again
 };
 struct AnimList { int32_t n; int32_t flat[4]; };
 struct Scene;
@@ -163,6 +163,7 @@ struct Scene {
     // none, by the rule of sector_from_vertex.  Built once at load; dg_ctx_locate_walks uploads them.
     std::vector<WalkNode> walk_nodes;
     std::vector<WalkLeaf> walk_leaves;
+    std::vector<int32_t> walk_leaf_sector;          // per leaf the sector that rule names (-1: none): what the pose rows' descent ends in (mobj_pose_core.h)
     void build_walk_tables();
     const FsSpriteFrame *sprite_frames_fs() const { return reinterpret_cast<const FsSpriteFrame *>(sprite_frames.data()); }
     void rebuild_fs_tables();

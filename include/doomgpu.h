@@ -37,7 +37,8 @@ typedef enum dg_status {
     DG_ERR_HIP = -3,         /* HIP runtime error, see dg_last_error */
     DG_ERR_WAD = -4,         /* WAD/map parse error (reference: panic in src/wad.rs, src/map/, src/graphics/) */
     DG_ERR_RENDER = -5,      /* a condition on which the reference renderer panics */
-    DG_ERR_CAPACITY = -6     /* batch / list larger than the ctx was created for */
+    DG_ERR_CAPACITY = -6,    /* batch / list larger than the ctx was created for */
+    DG_ERR_STATE = -7        /* the slot does not hold what the call reads (dg_slot_mobj_poses) */
 } dg_status;
 
 typedef struct dg_scene dg_scene; /* host-side immutable world: Map + Palette + Textures + Flats + Sprites + MapObjects */
@@ -174,7 +175,8 @@ typedef struct dg_config {
  *                      (same pixels either way).
  *   DG_FE_DEVICE_SEGS  the per-seg half runs on the GPU too (one lane per seg / map object, one wavefront per frame for what depends on
  *                      the BSP order): the host ships 88 bytes per view and nothing else (with per-view game state,
- *                      dg_submit_views_state: plus one copy of the sector lights and map-object states per view).  Frames it cannot
+ *                      dg_submit_views_state: plus one copy of the sector lights and map-object states per view; with per-view poses,
+ *                      dg_submit_views_poses: plus 20 bytes per moved object).  Frames it cannot
  *                      judge (a reference panic, a per-frame capacity: 256 parts after culling, 512 map objects in view, 2 560 columns)
  *                      and maps in which a texture / flat lookup would panic fall back to DG_FE_DEVICE / DG_FE_HOST transparently.
  *                      Costs device memory per ctx: max_batch x segs x 41 B of candidate rows + occupancy bits, plus max_batch x segs x 21 B for maps with
@@ -701,12 +703,58 @@ int  dg_walk_views(dg_walk *w, const float *timestamps, int n, dg_view *out);
  * than 1 << 26 probes in one call.  The first call after dg_upload_scene uploads the scene's node and leaf tables. */
 int  dg_ctx_locate_walks(dg_ctx *ctx, dg_walk *const *walks, int n_walks);
 
+/* ---- per-view map-object poses (reference: MapObject.position / .angle, src/map_objects.rs:11-17) ---------- */
+/* The reference's draw_map_objects reads every object's position and angle on every frame and asks get_sector_from_vertex for the
+ * position's sector on every frame (src/renderer/map_objects.rs:55,74,99-116): a caller who moves a monster, a projectile or another
+ * player sees it move.  A dg_view_poses says where the objects of ONE view are, on top of where the THINGS lump put them:
+ *   an entry overrides the object's x, y and angle for that view only; every object without an entry stands as loaded;
+ *   what follows from the position is derived again by the reference's rule: sector = get_sector_from_vertex(x, y), hence the light
+ *     level the object is drawn with (unless full-bright) and its z = sector.floor_height;
+ *   an object whose sector is None is not drawn in that view (map_objects.rs:100-104);
+ *   of two entries for one object in one view the later wins, as in dg_view_state;
+ *   an object index out of range is DG_ERR_INVALID, the frame named in the message;
+ *   the floats are taken as given, NaN and infinities included — the BSP descent still ends: a NaN comparison takes the right child
+ *     every time;
+ *   dg_view_state entries, the map-object thinkers, the light effects and the wall effects compose unchanged; a dg_view_state entry and
+ *     a pose entry for the same object are independent (one says what it looks like, the other where it is).
+ * The 2-D map submissions draw no objects and take no poses.  Every front end gives the same pixels; with DG_FE_DEVICE_SEGS (and
+ * DG_FE_AUTO when it picks the seg walk) the host ships only the entries, and two kernels in front of the seg walk write the batch's
+ * rows [frame][object] and find the moved objects' sectors on the GPU (device memory per slot: max_batch x map objects x 16 B of rows
+ * and 20 B of entry staging, taken at dg_upload_scene; when that allocation fails, batches with poses take the host walker — same
+ * pixels, counted by dg_ctx_fallbacks). */
+typedef struct dg_mobj_pose  { int32_t mobj; float x, y, angle; } dg_mobj_pose;   /* MapObject.position / .angle for ONE view */
+typedef struct dg_view_poses { const dg_mobj_pose *poses; uint32_t n; } dg_view_poses;
+typedef struct dg_mobj_placed { float x, y, angle; int32_t sector; } dg_mobj_placed; /* sector < 0: get_sector_from_vertex gave None */
+/* dg_submit_views_state / dg_render_views_state with poses[i] for views[i].  states may be NULL; poses == NULL behaves exactly as
+ * those two calls.  DG_ERR_INVALID also for an entry array that is NULL with n > 0. */
+int dg_submit_views_poses(dg_ctx *ctx, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, int n);
+int dg_render_views_poses(dg_ctx *ctx, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, int n, uint8_t *rgb24_out);
+/* dg_submit_bundle_views with poses (NULL: exactly that call).  A bundle of one part is the depth or the label submission. */
+int dg_submit_bundle_views_poses(dg_ctx *ctx, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, int n, uint32_t what);
+/* dg_build_lists / dg_build_lists_owners for a view with poses (poses may be NULL: none; owners may be NULL: not wanted).  The owner
+ * tag of a moved object keeps the object's index.  Feeds dg_draw_lists and the dg_*_lists_host functions; host only. */
+int dg_build_lists_poses(const dg_scene *s, int width, int height, const dg_view *view, const dg_view_poses *poses, dg_frame_lists *out, const uint32_t **owners);
+/* get_sector_from_vertex for n points on the host: sector_out[i] = the sector index of (x[i], y[i]), or -1 for None.  n = 0 does
+ * nothing.  DG_ERR_INVALID: a NULL argument, n < 0. */
+int dg_scene_sectors_at(const dg_scene *s, const float *x, const float *y, int n, int32_t *sector_out);
+/* Every map object's pose and sector as loaded.  n must equal dg_scene_mobj_count. */
+int dg_scene_mobj_poses(const dg_scene *s, dg_mobj_placed *out, int n);
+/* The pose rows the frames [first, first + count) of the slot's last submission were drawn with: out[count][dg_scene_mobj_count], read
+ * from wherever that submission's front end keeps them — after a seg-walk batch with poses the rows its two kernels wrote in device
+ * memory, otherwise the rows the host walker derives from the kept entries.  Waits for the slot like dg_readback; count = 0 does
+ * nothing.  DG_ERR_STATE: a slot that holds no view submission (an empty slot, a 2-D map submission, caller-built lists);
+ * DG_ERR_INVALID: a NULL out, a bad range. */
+int dg_slot_mobj_poses(dg_ctx *ctx, int slot, int first, int count, dg_mobj_placed *out);
+/* GPU time of the two pose kernels (dg_mobj_pose_fill, dg_mobj_pose_place) of the slot's last submission, from the events attached
+ * to their dispatches; 0 when that submission launched neither (no poses, or not the seg walk). */
+int dg_slot_mobj_pose_timing(dg_ctx *ctx, int slot, float *ms);
+
 /* ---- misc ----------------------------------------------------------------------------------------------------- */
 const char *dg_last_error(void); /* thread-local message of the last failing call */
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's

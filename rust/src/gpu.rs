@@ -98,7 +98,7 @@ extern "C" {
 }
 
 /// Drop-in for `Renderer`: same life cycle as src/renderer/mod.rs:37-58,118-136 (built per frame, borrows Pixels).
-pub struct GpuRenderer<'a> { ctx: *mut dg_ctx, pixels: &'a mut super::Pixels, view: dg_view }
+pub struct GpuRenderer<'a> { ctx: *mut dg_ctx, pixels: &'a mut super::Pixels, view: dg_view, poses: Vec<dg_mobj_pose> }
 
 impl<'a> GpuRenderer<'a> {
     pub fn new(ctx: *mut dg_ctx, pixels: &'a mut super::Pixels, player: &crate::game::Player, timestamp: f32) -> Self {
@@ -106,10 +106,13 @@ impl<'a> GpuRenderer<'a> {
         GpuRenderer { ctx, pixels, view: dg_view {
             x: player.position.x, y: player.position.y, angle: a, floor_height: player.floor_height,
             cos_a: a.cos(), sin_a: a.sin(), cos_na: (-a).cos(), sin_na: (-a).sin(),   // what Vertex::rotate computes (vertexes.rs:20-25)
-            timestamp, trig_valid: 1 } }
+            timestamp, trig_valid: 1 }, poses: Vec::new() }
     }
+    /// Where this tick's map objects are (what `sync_state` returned): without it every object stands where the THINGS lump put it.
+    pub fn with_poses(mut self, poses: Vec<dg_mobj_pose>) -> Self { self.poses = poses; self }
     pub fn render(&mut self) {
-        let rc = unsafe { dg_render_views(self.ctx, &self.view, 1, self.pixels.pixels.as_mut_ptr()) };
+        let vp = dg_view_poses { poses: self.poses.as_ptr(), n: self.poses.len() as u32 };
+        let rc = unsafe { dg_render_views_poses(self.ctx, &self.view, std::ptr::null(), &vp, 1, self.pixels.pixels.as_mut_ptr()) };
         if rc != 0 { panic!("doomgpu: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }  // the reference panics too
     }
     /// The `viewing_map` branch of Game::render (src/game.rs:491-499): black, draw_map_linedefs, draw_map_player — into the same
@@ -174,8 +177,11 @@ pub fn preload_sprite_frames(scene: *mut dg_scene) {
     }
 }
 
-/// `Game::render`, before `GpuRenderer::new(..).render()`: push the light levels and map-object states of this tick.
-pub fn sync_state(scene: *mut dg_scene, map: &crate::map::Map, map_objects: &crate::map_objects::MapObjects) {
+/// `Game::render`, before `GpuRenderer::new(..).render()`: push the light levels and map-object states of this tick, and return where
+/// the map objects are.  Light levels and states live in the scene; positions and angles travel per view (dg_view_poses, DESIGN.md
+/// section 8m) — `MapObject.position` / `.angle` are what draw_map_objects reads on every frame (src/renderer/map_objects.rs:55,74), and
+/// the library derives the sector, hence light and z, from the position as the reference does (:99-116).
+pub fn sync_state(scene: *mut dg_scene, map: &crate::map::Map, map_objects: &crate::map_objects::MapObjects) -> Vec<dg_mobj_pose> {
     for (i, sector) in map.sectors.iter().enumerate() {
         let rc = unsafe { dg_scene_set_sector_light(scene, i as c_int, sector.borrow().light_level) };
         if rc != 0 { panic!("doomgpu: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
@@ -190,6 +196,20 @@ pub fn sync_state(scene: *mut dg_scene, map: &crate::map::Map, map_objects: &cra
         };
         if rc != 0 { panic!("doomgpu: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }
     }
+    map_objects.objects.iter().enumerate().map(|(i, object)| {
+        let o = object.borrow();
+        dg_mobj_pose { mobj: i as i32, x: o.position.x, y: o.position.y, angle: o.angle }
+    }).collect()
+}
+
+// ---- per-view map-object poses (include/doomgpu.h dg_view_poses): MapObject.position / .angle of ONE view ---------------
+#[repr(C)] #[derive(Clone, Copy)] pub struct dg_mobj_pose { pub mobj: i32, pub x: f32, pub y: f32, pub angle: f32 }
+#[repr(C)] #[derive(Clone, Copy)] pub struct dg_view_poses { pub poses: *const dg_mobj_pose, pub n: u32 }
+#[repr(C)] #[derive(Clone, Copy)] pub struct dg_mobj_placed { pub x: f32, pub y: f32, pub angle: f32, pub sector: i32 }
+extern "C" {
+    pub fn dg_render_views_poses(ctx: *mut dg_ctx, views: *const dg_view, states: *const dg_view_state, poses: *const dg_view_poses, n: c_int, rgb24_out: *mut u8) -> c_int;
+    pub fn dg_submit_views_poses(ctx: *mut dg_ctx, slot: c_int, views: *const dg_view, states: *const dg_view_state, poses: *const dg_view_poses, n: c_int) -> c_int;
+    pub fn dg_slot_mobj_poses(ctx: *mut dg_ctx, slot: c_int, first: c_int, count: c_int, out: *mut dg_mobj_placed) -> c_int;
 }
 
 // ---- per-view game state (include/doomgpu.h dg_view_state): what the thinkers changed before a frame ------------------
