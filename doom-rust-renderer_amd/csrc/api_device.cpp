@@ -2,7 +2,8 @@
 // runs on a stream of the ctx's own, created by its first use, and returns when its work is done.  The box downscale of frames in device
 // memory (dg_reduce_device), the reduced depth and label planes (dg_reduce_planes_device), the linedefs seen in label planes
 // (dg_seen_lines_device, dg_slot_seen_lines — the one call here that reads a slot, once its submission is final), the floor heights of
-// recorded walks (dg_ctx_locate_walks), and the getters of their kernels' times.  Slot, dg_ctx and the slot helpers: context.hpp.
+// recorded walks (dg_ctx_locate_walks), and the getters of their kernels' times.  The readbacks of a slot's frames and planes:
+// api_readback.cpp.  Slot, dg_ctx and the slot helpers: context.hpp.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>

@@ -4,8 +4,8 @@
 // planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host, dg_label_lists_host,
 // dg_bundle_lists_host: one rule, plane_lists_host), a bundle's slab layout (dg_bundle_layout), and the explored-map frames' host rules
 // (dg_seen_words, dg_seen_lines_host, dg_seen_accumulate_host, dg_explored_map_host) and the player-centred map frames' (dg_ego_map_lines,
-// dg_ego_map_host).  Everything that takes a dg_ctx: context.cpp (a slot's submissions and readbacks) and api_device.cpp (the calls on
-// a stream of the ctx's own).
+// dg_ego_map_host).  Everything that takes a dg_ctx: context.cpp (a slot's submissions), api_readback.cpp (what reads a slot) and
+// api_device.cpp (the calls on a stream of the ctx's own).
 #include <algorithm>
 #include <cstring>
 #include <string>

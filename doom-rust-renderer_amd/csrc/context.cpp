@@ -1,8 +1,9 @@
 // context.cpp — dg_ctx: one GPU's resident scene, per-slot list slabs / framebuffer slabs / streams, the batch builders that run on
 // the host thread pool (pool.hpp), and a slot's way from one submission to the next (Slot::Phase, take_slot, make_final).  Implements
-// the entry points of the C-ABI (include/doomgpu.h) that take a dg_ctx and a slot of it; those that run on a stream of the ctx's own
-// and return when done are in api_device.cpp, those that need no GPU in api_scene.cpp.  Slot and dg_ctx themselves: context.hpp; the
-// owners of memory, streams and events and TablePack: hip_mem.hpp.
+// the entry points of the C-ABI (include/doomgpu.h) that give a slot of a dg_ctx its submission or wait for it; those that read what
+// the submission left (the readbacks, the checksums, the timing getters) are in api_readback.cpp, those that run on a stream of the
+// ctx's own and return when done in api_device.cpp, those that need no GPU in api_scene.cpp.  Slot and dg_ctx themselves: context.hpp;
+// the owners of memory, streams and events and TablePack: hip_mem.hpp.
 //
 // HBM layout (sized once at dg_create for 288 GB parts: nothing is reallocated on the submit path):
 //   scene   : palette 1 KB | texel index plane | texel opacity plane | flats (4 KB each)      immutable per map
@@ -42,8 +43,6 @@
 #include "explored_cover.hpp"
 #include "explored_kernels.hpp"
 #include "map_kernels.hpp"
-#include "plane_reduce_kernels.hpp"
-#include "reduce_kernels.hpp"
 
 using namespace dg;
 
@@ -821,117 +820,6 @@ int redo_overflowed(dg_ctx *c, Slot &s) {
     return make_final(c, s, Copy::Leave);                  // (a host-list batch now: it is waited for, there are no flags to look at)
 }
 
-// Room for `bytes` of reduced frames in the slot's scratch.  It only ever grows, and only when nothing of the slot can be using it:
-// after a sync of the slot's streams.
-int reserve_reduced(Slot &s, size_t bytes) {
-    if (bytes <= s.reduced_cap) return DG_OK;
-    HIP_TRY(hipStreamSynchronize(s.stream.get()));
-    HIP_TRY(hipStreamSynchronize(s.copy_stream.get()));
-    s.reduced_cap = 0;
-    HIP_TRY(hip_alloc(s.d_reduced, bytes));
-    s.reduced_cap = bytes;
-    return DG_OK;
-}
-
-// Room for `entries` raw box rows in the slot's pinned staging, under the same rule.
-int reserve_rawboxes(Slot &s, size_t entries) {
-    if (entries <= s.rawbox_cap) return DG_OK;
-    HIP_TRY(hipStreamSynchronize(s.stream.get()));
-    HIP_TRY(hipStreamSynchronize(s.copy_stream.get()));
-    s.rawbox_cap = 0;
-    HIP_TRY(hip_alloc(s.h_rawboxes, entries * sizeof(LabelRawBox)));
-    s.rawbox_cap = entries;
-    return DG_OK;
-}
-
-// Where a reduced plane readback of `count` frames puts its outputs in the slot's scratch: the 16-bit planes first, every plane on a
-// 256-byte boundary, whether it is asked for or not (the scratch is sized for all four).
-struct PlaneScratch { size_t px, distance, id, kind, cls, total; };   // px: elements of one plane, byte offsets, bytes in all
-PlaneScratch plane_scratch(const dg_ctx *c, const dg_plane_reduce_desc &d, int count) {
-    const size_t px = (size_t)count * reduce_out_dim((uint32_t)c->cfg.width, d.fx) * reduce_out_dim((uint32_t)c->cfg.height, d.fy);
-    SlabCursor cur;
-    PlaneScratch p{};
-    p.px = px;
-    p.distance = cur.take(2 * px); p.id = cur.take(2 * px); p.kind = cur.take(px); p.cls = cur.take(px);
-    p.total = cur.next;
-    return p;
-}
-
-// A reduced plane readback on `stream`: dg_plane_nearest / dg_plane_point from the slot's planes into its scratch, the copies of the
-// planes asked for, and the box rows into the slot's pinned staging.
-int issue_plane_readback(dg_ctx *c, Slot &s, const Slot::Readback &r, hipStream_t stream) {
-    const size_t W = (size_t)c->cfg.width, H = (size_t)c->cfg.height, at = (size_t)r.first * W * H;
-    const BundleLayout L = s.layout(W, H);
-    const uint8_t *const fb = s.d_fb.get();
-    const PlaneScratch sc = plane_scratch(c, r.pdesc, r.count);
-    if (sc.total > s.reduced_cap) return set_err(DG_ERR_INVALID, "reduced readback: no scratch reserved");
-    uint8_t *const out = s.d_reduced.get();
-    PlaneReduceSrc src{};
-    PlaneReduceDst dst{};
-    if (s.holds(BUNDLE_DEPTH)) {
-        src.distance = reinterpret_cast<const int16_t *>(fb + L.distance) + at;        // (DG_PLANE_NEAREST reads it whatever is asked for)
-        src.kind = fb + L.kind + at;
-        if (r.distance) dst.distance = reinterpret_cast<int16_t *>(out + sc.distance);
-        if (r.kind) dst.kind = out + sc.kind;
-    }
-    if (s.holds(BUNDLE_LABELS)) {
-        src.id = reinterpret_cast<const uint16_t *>(fb + L.id) + at;
-        src.cls = fb + L.cls + at;
-        if (r.id) dst.id = reinterpret_cast<uint16_t *>(out + sc.id);
-        if (r.cls) dst.cls = out + sc.cls;
-    }
-    if (dst.distance || dst.kind || dst.id || dst.cls) {
-        HIP_TRY(launch_plane_reduce(src, c->cfg.width, c->cfg.height, r.count, r.pdesc, dst, stream));
-        const size_t px = sc.px;                               // (elements of one reduced plane over the count frames)
-        if (dst.distance) HIP_TRY(hipMemcpyAsync(r.distance, dst.distance, 2 * px, hipMemcpyDeviceToHost, stream));
-        if (dst.kind) HIP_TRY(hipMemcpyAsync(r.kind, dst.kind, px, hipMemcpyDeviceToHost, stream));
-        if (dst.id) HIP_TRY(hipMemcpyAsync(r.id, dst.id, 2 * px, hipMemcpyDeviceToHost, stream));
-        if (dst.cls) HIP_TRY(hipMemcpyAsync(r.cls, dst.cls, px, hipMemcpyDeviceToHost, stream));
-    }
-    const size_t n_boxes = (size_t)r.count * s.per_scene.box_mobjs;
-    if (r.boxes && n_boxes) {
-        if (n_boxes > s.rawbox_cap) return set_err(DG_ERR_INVALID, "reduced readback: no box staging reserved");
-        HIP_TRY(hipMemcpyAsync(s.h_rawboxes.get(), s.per_scene.d_boxes.get() + (size_t)r.first * s.per_scene.box_mobjs, n_boxes * sizeof(LabelRawBox), hipMemcpyDeviceToHost, stream));
-    }
-    return DG_OK;
-}
-
-// What is left to do on the host once readback r's copies have finished: the box rows in the form the caller sees.
-void finish_readback(const dg_ctx *c, const Slot &s, const Slot::Readback &r) {
-    if (!r.planes || !r.boxes) return;
-    const size_t n_boxes = (size_t)r.count * s.per_scene.box_mobjs;
-    for (size_t i = 0; i < n_boxes; i++) {
-        int32_t x0, y0, x1, y1;
-        label_box_finish(s.h_rawboxes.get()[i], c->cfg.width, c->cfg.height, r.boxes[i].pixels, x0, y0, x1, y1);
-        r.boxes[i].x0 = (int16_t)x0; r.boxes[i].y0 = (int16_t)y0; r.boxes[i].x1 = (int16_t)x1; r.boxes[i].y1 = (int16_t)y1;
-    }
-}
-
-// Readback r of the slot's frames on `stream`: the D2H copy of the frames themselves, or dg_reduce into the slot's scratch
-// (reserve_reduced) and the copy of that, or the reduced planes (issue_plane_readback).  The caller has ordered `stream` behind the
-// slot's kernels.
-int issue_readback(dg_ctx *c, Slot &s, const Slot::Readback &r, hipStream_t stream) {
-    const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
-    const uint8_t *const frames = s.d_fb.get() + (size_t)r.first * fsz;
-    if (!r.reduced) {
-        HIP_TRY(hipMemcpyAsync(r.out, frames, (size_t)r.count * fsz, hipMemcpyDeviceToHost, stream));
-        return DG_OK;
-    }
-    if (r.count == 0) return DG_OK;
-    if (r.planes) return issue_plane_readback(c, s, r, stream);
-    const size_t bytes = (size_t)r.count * reduce_frame_bytes((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, r.desc);
-    if (bytes > s.reduced_cap) return set_err(DG_ERR_INVALID, "reduced readback: no scratch reserved");
-    HIP_TRY(launch_reduce(frames, c->cfg.width, c->cfg.height, r.count, r.desc, s.d_reduced.get(), stream));
-    HIP_TRY(hipMemcpyAsync(r.out, s.d_reduced.get(), bytes, hipMemcpyDeviceToHost, stream));
-    return DG_OK;
-}
-
-// The slot's pending readback onto its copy stream, behind the slot's kernels.
-int enqueue_copy(dg_ctx *c, Slot &s) {
-    HIP_TRY(hipStreamWaitEvent(s.copy_stream.get(), s.ev_raster.get(), 0));
-    return issue_readback(c, s, s.copy, s.copy_stream.get());
-}
-
 // DG_FE_AUTO's measurement of the GPU side: the span of a finished submission's kernels (never waits)
 void harvest_gpu_time(dg_ctx *c, Slot &s) {
     if (s.harvested || !s.has_run() || !s.column_walk() || s.n_frames < 64 || c->fs_forced || !c->fs_enabled) return;
@@ -1013,15 +901,6 @@ int read_or_wait(dg_ctx *c, int slot, int rc, bool wanted, Read read) {
 }
 int read_or_wait(dg_ctx *c, int slot, int rc, int n, uint8_t *out) {
     return read_or_wait(c, slot, rc, out != nullptr, [&] { return dg_readback(c, slot, 0, n, out); });
-}
-
-// The calls that read the framebuffer slab as RGB24 frames, or run the colour kernels again: the slot has no colour part.  (An empty
-// slot is the callers' to refuse.)
-int refuse_no_colour(const Slot &s, const char *what) {
-    if (s.parts() == 0 || s.holds(BUNDLE_COLOUR)) return DG_OK;   // (a bundle's colour frames sit at the slab's base, as after a colour submission)
-    if (s.holds_bundle()) return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds a bundle without a colour part (DG_BUNDLE_COLOUR)");
-    if (s.holds(BUNDLE_LABELS)) return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds label planes, not RGB24 frames (dg_readback_labels)");
-    return set_err(DG_ERR_INVALID, std::string(what) + ": the slot holds depth planes, not RGB24 frames (dg_readback_depth)");
 }
 
 // What a submission with a label part needs of the slot: the owner tags' staging and HBM, and a box table for the scene's map objects.
@@ -1141,16 +1020,6 @@ int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     built_from(s, views, poses, n);
     s.bundle_what = what;
     return enqueue_bundle(c, s);
-}
-
-// The times of the bundle the slot has run, into the outputs that are there: setup and raster are the colour kernels' (the raster
-// launch ends at ev_cend when dg_bundle_tiles follows it), tiles is dg_bundle_tiles'; 0 for a part the bundle does not have.
-int bundle_times(const Slot &s, float *setup_ms, float *raster_ms, float *tiles_ms) {
-    const bool colour = (s.bundle_what & BUNDLE_COLOUR) != 0, tiles = (s.bundle_what & (BUNDLE_DEPTH | BUNDLE_LABELS)) != 0;
-    if (setup_ms) { *setup_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(setup_ms, s.ev_start.get(), s.ev_setup.get())); }
-    if (raster_ms) { *raster_ms = 0.0f; if (colour) HIP_TRY(hipEventElapsedTime(raster_ms, s.ev_rstart.get(), tiles ? s.ev_cend.get() : s.ev_raster.get())); }
-    if (tiles_ms) { *tiles_ms = 0.0f; if (tiles) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_tiles.get(), s.ev_raster.get())); }
-    return DG_OK;
 }
 
 int check_view_poses(const dg_view_poses *poses, int n) {
@@ -1424,109 +1293,11 @@ int dg_render_views_poses(dg_ctx *c, const dg_view *views, const dg_view_state *
     return read_or_wait(c, 0, dg_submit_views_poses(c, 0, views, states, poses, n), n, out);
 }
 
-int dg_slot_mobj_poses(dg_ctx *c, int slot, int first, int count, dg_mobj_placed *out) {
-    static_assert(sizeof(dg_mobj_placed) == sizeof(FsMobj) && offsetof(dg_mobj_placed, sector) == offsetof(FsMobj, sector), "dg_mobj_placed / FsMobj");
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (s.phase == Slot::Phase::Empty || !s.from_views || !c->scene) return set_err(DG_ERR_STATE, "dg_slot_mobj_poses: the slot holds no view submission");
-    if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad frame range");
-    if (count == 0) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    rc = make_final(c, s, Copy::Leave);                    // (a seg-walk batch redone as a whole is a host-list batch from here on)
-    if (rc) return rc;
-    const Scene &sc = *c->scene;
-    const size_t n_mobjs = sc.mobjs.size();
-    if (n_mobjs == 0) return DG_OK;
-    if (s.seg_walk() && s.PP.n_frames > 0) {               // the rows the pose kernels wrote
-        HIP_TRY(hipMemcpyAsync(out, s.PP.rows + (size_t)first * n_mobjs, (size_t)count * n_mobjs * sizeof(FsMobj), hipMemcpyDeviceToHost, s.stream.get()));
-        HIP_TRY(slot_sync(s));
-        return DG_OK;
-    }
-    FrameArena &A = *c->arenas[0];                         // the host walker's rule (Walker::mobj_placed) over the kept entries
-    for (int i = 0; i < count; i++) {
-        dg_mobj_placed *row = out + (size_t)i * n_mobjs;
-        std::memcpy(row, sc.fs_mobjs.data(), n_mobjs * sizeof(FsMobj));
-        const dg_view_poses *vp = s.poses_of(first + i);
-        if (!vp) continue;
-        (void)resolve_view_poses(sc, *vp, A.pose_of, A.poses);
-        for (const dg_mobj_pose &p : A.poses) row[p.mobj] = dg_mobj_placed{p.x, p.y, p.angle, sc.sector_from_vertex(p.x, p.y)};
-        release_view_poses(A.pose_of, A.poses);
-    }
-    return DG_OK;
-}
-
-int dg_slot_mobj_pose_timing(dg_ctx *c, int slot, float *ms) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    if (!ms) return set_err(DG_ERR_INVALID, "null argument");
-    Slot &s = c->slots[(size_t)slot];
-    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    rc = make_final(c, s, Copy::Leave);
-    if (rc) return rc;
-    *ms = 0.0f;
-    if (s.seg_walk() && s.PP.n_frames > 0) HIP_TRY(hipEventElapsedTime(ms, s.ev_start.get(), s.ev_pose.get()));
-    return DG_OK;
-}
-
 int dg_wait(dg_ctx *c, int slot) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->cfg.device));
     return make_final(c, c->slots[(size_t)slot], Copy::Complete);
-}
-
-// dg_readback_async and dg_readback_reduced_async (desc != nullptr, checked): the readback becomes the slot's pending one.
-static int readback_async(dg_ctx *c, int slot, int first, int count, const dg_reduce_desc *desc, uint8_t *out) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if ((rc = refuse_no_colour(s, desc ? "dg_readback_reduced_async" : "dg_readback_async"))) return rc;
-    if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
-    if (s.copy_pending) return set_err(DG_ERR_INVALID, "the slot already has a readback in flight (dg_wait it first)");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    Slot::Readback r;
-    r.out = out; r.first = first; r.count = count;
-    if (desc) {
-        r.reduced = true; r.desc = *desc;
-        rc = reserve_reduced(s, (size_t)count * reduce_frame_bytes((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, *desc));
-        if (rc) return rc;
-    }
-    s.copy = r;
-    rc = enqueue_copy(c, s);
-    if (rc) return rc;
-    s.copy_pending = true;
-    return DG_OK;
-}
-
-int dg_readback_async(dg_ctx *c, int slot, int first, int count, uint8_t *out) { return readback_async(c, slot, first, count, nullptr, out); }
-
-int dg_readback_reduced_async(dg_ctx *c, int slot, int first, int count, const dg_reduce_desc *desc, uint8_t *out) {
-    const int rc = check_reduce_desc(desc);
-    return rc ? rc : readback_async(c, slot, first, count, desc, out);
-}
-
-int dg_readback_reduced(dg_ctx *c, int slot, int first, int count, const dg_reduce_desc *desc, uint8_t *out) {
-    int rc = check_reduce_desc(desc);
-    if (!rc) rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if ((rc = refuse_no_colour(s, "dg_readback_reduced"))) return rc;
-    if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
-    if (count == 0) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    // (a pending asynchronous reduced readback owns the slot's scratch: it is completed first)
-    rc = make_final(c, s, s.copy_pending && s.copy.reduced ? Copy::Complete : Copy::Leave);
-    if (rc) return rc;
-    Slot::Readback r;
-    r.out = out; r.first = first; r.count = count; r.reduced = true; r.desc = *desc;
-    rc = reserve_reduced(s, (size_t)count * reduce_frame_bytes((uint32_t)c->cfg.width, (uint32_t)c->cfg.height, *desc));
-    if (rc) return rc;
-    rc = issue_readback(c, s, r, s.stream.get());
-    if (rc) return rc;
-    HIP_TRY(slot_sync(s));
-    return DG_OK;
 }
 
 int dg_ctx_redone_frames(const dg_ctx *c, uint64_t *frames) {
@@ -1538,49 +1309,6 @@ int dg_ctx_redone_frames(const dg_ctx *c, uint64_t *frames) {
 int dg_ctx_fallbacks(const dg_ctx *c, uint64_t *front_end) {
     if (!c || !front_end) return set_err(DG_ERR_INVALID, "null argument");
     *front_end = c->fallbacks_fe;
-    return DG_OK;
-}
-
-int dg_slot_framebuffer(dg_ctx *c, int slot, void **p) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    if (!p) return set_err(DG_ERR_INVALID, "null argument");
-    *p = c->slots[(size_t)slot].d_fb.get();
-    return DG_OK;
-}
-
-int dg_readback(dg_ctx *c, int slot, int first, int count, uint8_t *out) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if ((rc = refuse_no_colour(s, "dg_readback"))) return rc;
-    if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
-    rc = make_final(c, s, Copy::Leave);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, s.d_fb.get() + (size_t)first * fsz, (size_t)count * fsz, hipMemcpyDeviceToHost, s.stream.get()));
-    HIP_TRY(slot_sync(s));
-    return DG_OK;
-}
-
-int dg_frame_checksums(dg_ctx *c, int slot, int first, int count, uint64_t *out) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if ((rc = refuse_no_colour(s, "dg_frame_checksums"))) return rc;
-    if (!out || first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad frame range");
-    if (count == 0) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    rc = make_final(c, s, Copy::Leave);          // (the kernels run on the ctx's kernel stream: the copy below is not ordered behind them by its stream)
-    if (rc) return rc;
-    const size_t fsz = (size_t)3 * (size_t)c->cfg.width * (size_t)c->cfg.height;
-    unsigned long long *d_sum = c->d_checksums.get();      // max_batch entries, allocated at dg_create
-    hipError_t e = hipMemsetAsync(d_sum, 0, (size_t)count * 8, s.stream.get());
-    if (e == hipSuccess) e = launch_checksums(s.d_fb.get() + (size_t)first * fsz, fsz, count, d_sum, s.stream.get());
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_sum, (size_t)count * 8, hipMemcpyDeviceToHost, s.stream.get());
-    if (e == hipSuccess) e = slot_sync(s);
-    if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("dg_frame_checksums: ") + hipGetErrorString(e));
     return DG_OK;
 }
 
@@ -1648,38 +1376,6 @@ int dg_submit_depth_views(dg_ctx *c, int slot, const dg_view *views, const dg_vi
     return submit_depth(c, slot, views, nullptr, n, states);
 }
 
-// What dg_readback_depth and dg_readback_labels do alike once each has ruled on what the slot holds: frames [first, first + count) of
-// a 16-bit plane at byte `at16` of the framebuffer slab and of the 8-bit plane at `at8` into the outputs that are there, and with `raw`
-// the same frames' rows of the box table.
-static int read_planes(dg_ctx *c, Slot &s, int first, int count, size_t at16, void *out16, size_t at8, uint8_t *out8, std::vector<LabelRawBox> *raw = nullptr) {
-    if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
-    if (count == 0) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    const int rc = make_final(c, s, Copy::Leave);
-    if (rc) return rc;
-    const size_t px = (size_t)c->cfg.width * (size_t)c->cfg.height;
-    const uint8_t *const fb = s.d_fb.get();
-    if (out16) HIP_TRY(hipMemcpyAsync(out16, fb + at16 + (size_t)first * px * 2, (size_t)count * px * 2, hipMemcpyDeviceToHost, s.stream.get()));
-    if (out8) HIP_TRY(hipMemcpyAsync(out8, fb + at8 + (size_t)first * px, (size_t)count * px, hipMemcpyDeviceToHost, s.stream.get()));
-    if (raw) {
-        raw->resize((size_t)count * s.per_scene.box_mobjs);
-        if (!raw->empty()) HIP_TRY(hipMemcpyAsync(raw->data(), s.per_scene.d_boxes.get() + (size_t)first * s.per_scene.box_mobjs, raw->size() * sizeof(LabelRawBox), hipMemcpyDeviceToHost, s.stream.get()));
-    }
-    HIP_TRY(slot_sync(s));
-    return DG_OK;
-}
-
-int dg_readback_depth(dg_ctx *c, int slot, int first, int count, int16_t *distance, uint8_t *kind) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (!s.holds(BUNDLE_DEPTH))                           // (a label slot included)
-        return set_err(DG_ERR_INVALID, s.holds_bundle() ? "dg_readback_depth: the slot's bundle has no depth part (DG_BUNDLE_DEPTH)"
-                                                        : "dg_readback_depth: the slot's last submission is not a depth submission");
-    const BundleLayout L = s.layout((size_t)c->cfg.width, (size_t)c->cfg.height);
-    return read_planes(c, s, first, count, L.distance, distance, L.kind, kind);
-}
-
 int dg_render_depth_views(dg_ctx *c, const dg_view *views, const dg_view_state *states, int n, int16_t *distance, uint8_t *kind) {
     return read_or_wait(c, 0, dg_submit_depth_views(c, 0, views, states, n), distance || kind, [&] { return dg_readback_depth(c, 0, 0, n, distance, kind); });
 }
@@ -1700,95 +1396,6 @@ int dg_submit_label_views(dg_ctx *c, int slot, const dg_view *views, const dg_vi
     return submit_labels(c, slot, views, nullptr, nullptr, n, states);
 }
 
-int dg_readback_labels(dg_ctx *c, int slot, int first, int count, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (!s.holds(BUNDLE_LABELS))
-        return set_err(DG_ERR_INVALID, s.holds_bundle() ? "dg_readback_labels: the slot's bundle has no label part (DG_BUNDLE_LABELS)"
-                                                        : "dg_readback_labels: the slot's last submission is not a label submission");
-    const int W = c->cfg.width, H = c->cfg.height;
-    const BundleLayout L = s.layout((size_t)W, (size_t)H);
-    std::vector<LabelRawBox> raw;
-    if ((rc = read_planes(c, s, first, count, L.id, id, L.cls, cls, boxes ? &raw : nullptr))) return rc;
-    for (size_t i = 0; i < raw.size(); i++) {
-        int32_t x0, y0, x1, y1;
-        label_box_finish(raw[i], W, H, boxes[i].pixels, x0, y0, x1, y1);
-        boxes[i].x0 = (int16_t)x0; boxes[i].y0 = (int16_t)y0; boxes[i].x1 = (int16_t)x1; boxes[i].y1 = (int16_t)y1;
-    }
-    return DG_OK;
-}
-
-// What dg_readback_planes_reduced and its asynchronous twin check alike, in this order: the descriptor, the slot, what the slot holds
-// against what is asked for, the frame range.  *nothing: the call is valid and has nothing to do.
-static int check_plane_readback(dg_ctx *c, int slot, int first, int count, const dg_plane_reduce_desc *desc, const Slot::Readback &r, bool *nothing) {
-    if (!desc) return set_err(DG_ERR_INVALID, "null argument");
-    if (!plane_reduce_desc_ok(*desc)) return set_err(DG_ERR_INVALID, "plane reduce descriptor: fx and fy in 1..16, a known rule, reserved 0");
-    const int rc = check_slot(c, slot);
-    if (rc) return rc;
-    const Slot &s = c->slots[(size_t)slot];
-    if (!s.holds(BUNDLE_DEPTH) && !s.holds(BUNDLE_LABELS)) return set_err(DG_ERR_INVALID, "reduced planes: the slot holds neither depth nor label planes");
-    if ((r.distance || r.kind) && !s.holds(BUNDLE_DEPTH)) return set_err(DG_ERR_INVALID, "reduced planes: the slot has no depth part (distance, kind)");
-    if ((r.id || r.cls || r.boxes) && !s.holds(BUNDLE_LABELS)) return set_err(DG_ERR_INVALID, "reduced planes: the slot has no label part (id, cls, boxes)");
-    if (desc->rule == DG_PLANE_NEAREST && !s.holds(BUNDLE_DEPTH)) return set_err(DG_ERR_INVALID, "reduced planes: DG_PLANE_NEAREST needs a slot with a depth part");
-    if (first < 0 || count < 0 || first + count > s.n_frames) return set_err(DG_ERR_INVALID, "bad readback range");
-    *nothing = count == 0 || !(r.distance || r.kind || r.id || r.cls || r.boxes);
-    return DG_OK;
-}
-
-// The scratch and the box staging readback r needs.
-static int reserve_plane_readback(dg_ctx *c, Slot &s, const Slot::Readback &r) {
-    const int rc = reserve_reduced(s, plane_scratch(c, r.pdesc, r.count).total);
-    if (rc) return rc;
-    return r.boxes ? reserve_rawboxes(s, (size_t)r.count * s.per_scene.box_mobjs) : DG_OK;
-}
-
-static Slot::Readback plane_readback(int first, int count, const dg_plane_reduce_desc *desc, int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls,
-                                     dg_label_box *boxes) {
-    Slot::Readback r;
-    r.first = first; r.count = count; r.reduced = true; r.planes = true;
-    if (desc) r.pdesc = *desc;
-    r.distance = distance; r.kind = kind; r.id = id; r.cls = cls; r.boxes = boxes;
-    return r;
-}
-
-int dg_readback_planes_reduced_async(dg_ctx *c, int slot, int first, int count, const dg_plane_reduce_desc *desc,
-                                     int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
-    const Slot::Readback r = plane_readback(first, count, desc, distance, kind, id, cls, boxes);
-    bool nothing = false;
-    int rc = check_plane_readback(c, slot, first, count, desc, r, &nothing);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (s.copy_pending) return set_err(DG_ERR_INVALID, "the slot already has a readback in flight (dg_wait it first)");
-    if (nothing) return DG_OK;
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    if ((rc = reserve_plane_readback(c, s, r))) return rc;
-    s.copy = r;
-    rc = enqueue_copy(c, s);
-    if (rc) return rc;
-    s.copy_pending = true;
-    return DG_OK;
-}
-
-int dg_readback_planes_reduced(dg_ctx *c, int slot, int first, int count, const dg_plane_reduce_desc *desc,
-                               int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
-    const Slot::Readback r = plane_readback(first, count, desc, distance, kind, id, cls, boxes);
-    bool nothing = false;
-    int rc = check_plane_readback(c, slot, first, count, desc, r, &nothing);
-    if (rc || nothing) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    // (a pending asynchronous reduced readback owns the slot's scratch and box staging: it is completed first)
-    rc = make_final(c, s, s.copy_pending && s.copy.reduced ? Copy::Complete : Copy::Leave);
-    if (rc) return rc;
-    if ((rc = reserve_plane_readback(c, s, r))) return rc;
-    rc = issue_readback(c, s, r, s.stream.get());
-    if (rc) return rc;
-    HIP_TRY(slot_sync(s));
-    finish_readback(c, s, r);
-    return DG_OK;
-}
-
 int dg_render_label_views(dg_ctx *c, const dg_view *views, const dg_view_state *states, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
     return read_or_wait(c, 0, dg_submit_label_views(c, 0, views, states, n), id || cls || boxes, [&] { return dg_readback_labels(c, 0, 0, n, id, cls, boxes); });
 }
@@ -1798,19 +1405,6 @@ int dg_label_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uint
     if (rc) return rc;
     if (!frames || !owners) return set_err(DG_ERR_INVALID, "null frames or owners");
     return read_or_wait(c, slot, submit_labels(c, slot, nullptr, frames, owners, n, nullptr), id || cls || boxes, [&] { return dg_readback_labels(c, slot, 0, n, id, cls, boxes); });
-}
-
-int dg_slot_label_timing(dg_ctx *c, int slot, float *tiles_ms, float *boxes_ms) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (s.front_end != DG_FE_LABELS || !s.has_run()) return set_err(DG_ERR_INVALID, "dg_slot_label_timing: the slot's last submission is not a label submission that ran");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    rc = make_final(c, s, Copy::Leave);
-    if (rc) return rc;
-    if (tiles_ms) HIP_TRY(hipEventElapsedTime(tiles_ms, s.ev_rstart.get(), s.ev_setup.get()));
-    if (boxes_ms) HIP_TRY(hipEventElapsedTime(boxes_ms, s.ev_setup.get(), s.ev_raster.get()));
-    return DG_OK;
 }
 
 int dg_bundle_capacity(const dg_ctx *c, uint32_t what) {
@@ -1842,16 +1436,6 @@ int dg_bundle_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uin
     if ((what & BUNDLE_LABELS) && !owners) return set_err(DG_ERR_INVALID, "null owners: DG_BUNDLE_LABELS needs the owner tags");
     rc = submit_bundle(c, slot, nullptr, frames, owners, n, nullptr, what);
     return rc ? rc : dg_wait(c, slot);                    // (no output of its own: the parts are the readbacks' to fetch)
-}
-
-int dg_slot_bundle_timing(dg_ctx *c, int slot, float *setup_ms, float *raster_ms, float *tiles_ms) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (!s.holds_bundle() || !s.has_run()) return set_err(DG_ERR_INVALID, "dg_slot_bundle_timing: the slot's last submission is not a bundle that ran");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    rc = make_final(c, s, Copy::Leave);
-    return rc ? rc : bundle_times(s, setup_ms, raster_ms, tiles_ms);
 }
 
 int dg_submit_map_views(dg_ctx *c, int slot, const dg_view *views, int n) {
@@ -1908,34 +1492,6 @@ int dg_submit_ego_map_views(dg_ctx *c, int slot, const dg_view *views, int n, co
 
 int dg_render_ego_map_views(dg_ctx *c, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, uint8_t *out) {
     return read_or_wait(c, 0, dg_submit_ego_map_views(c, 0, views, n, params, mask), n, out);
-}
-
-int dg_slot_timing(dg_ctx *c, int slot, dg_timing *out) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    if (!out) return set_err(DG_ERR_INVALID, "null argument");
-    Slot &s = c->slots[(size_t)slot];
-    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    rc = make_final(c, s, Copy::Leave);
-    if (rc) return rc;
-    std::memset(out, 0, sizeof *out);
-    out->front_end = s.front_end;
-    if (s.front_end == DG_FE_BUNDLE) {                    // setup_ms / raster_ms: the colour kernels (0 without colour); total_ms: first kernel's start .. last kernel's end
-        if ((rc = bundle_times(s, &out->setup_ms, &out->raster_ms, nullptr))) return rc;
-        HIP_TRY(hipEventElapsedTime(&out->total_ms, (s.bundle_what & BUNDLE_COLOUR) ? s.ev_start.get() : s.ev_tiles.get(), s.ev_raster.get()));
-    } else if (s.timed_front_half()) {
-        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart.get(), s.ev_raster.get()));
-        HIP_TRY(hipEventElapsedTime(&out->setup_ms, s.ev_start.get(), s.ev_setup.get()));
-        HIP_TRY(hipEventElapsedTime(&out->total_ms, s.ev_start.get(), s.ev_raster.get()));
-    } else {
-        HIP_TRY(hipEventElapsedTime(&out->raster_ms, s.ev_rstart.get(), s.ev_raster.get()));
-        out->total_ms = out->raster_ms;
-    }
-    out->n_spans = s.n_spans; out->n_frames = (uint64_t)s.n_frames; out->covered_pixels = s.covered;
-    out->host_ms = s.host_ms; out->list_bytes = s.list_bytes;
-    out->n_walls = s.n_walls; out->n_planes = s.n_planes;
-    return DG_OK;
 }
 
 }  // extern "C"

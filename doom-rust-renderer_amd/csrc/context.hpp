@@ -1,6 +1,6 @@
 // context.hpp — what the files that implement the C-ABI's dg_ctx entry points share (context.cpp: a slot's way from one submission
-// to the next; api_device.cpp: the calls that run on a stream of the ctx's own and return when done): Slot, dg_ctx, HIP_TRY, and the
-// few slot helpers the second needs of the first, with the headers both need.  Private to csrc/.
+// to the next; api_readback.cpp: what reads a slot; api_device.cpp: the calls that run on a stream of the ctx's own and return when
+// done): Slot, dg_ctx, HIP_TRY, and the few slot helpers one of them needs of another, with the headers all need.  Private to csrc/.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -50,20 +50,22 @@ struct Slot {
     // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
     bool raster_recorded = false;
     Stream copy_stream;   // dg_readback_async / dg_readback_reduced_async / dg_readback_planes_reduced_async: D2H of this slot's frames while another slot's kernels run
-    // What a readback moves: frames [first, first + count) to host memory `out`, as they are or reduced by `desc` on the way; or
-    // (planes) the depth and label planes of those frames reduced by `pdesc` to the outputs that are there, and their box rows
+    // What a readback moves (api_readback.cpp): frames [first, first + count) to host memory `out`, as they are or reduced by `desc` on
+    // the way; or (planes) the depth and label planes of those frames to the outputs that are there, as they are or reduced by `pdesc`
+    // on the way, and their box rows
     struct Readback {
         uint8_t *out = nullptr;
         int first = 0, count = 0;
         bool reduced = false;            // goes through the slot's scratch (d_reduced)
         dg_reduce_desc desc{};
-        bool planes = false;             // dg_readback_planes_reduced*: always with `reduced`
+        bool planes = false;             // the planes, not the RGB24 frames
         dg_plane_reduce_desc pdesc{};
         int16_t *distance = nullptr;
         uint8_t *kind = nullptr;
         uint16_t *id = nullptr;
         uint8_t *cls = nullptr;
-        dg_label_box *boxes = nullptr;   // filled from h_rawboxes when the copy has finished (finish_readback)
+        dg_label_box *boxes = nullptr;   // filled from `raw` when the copy has finished (finish_readback)
+        LabelRawBox *raw = nullptr;      // where the box rows land as the kernels left them: h_rawboxes, or memory of a synchronous call's own
     } copy;                              // the pending asynchronous one (issued again if the batch has to be redone)
     bool copy_pending = false;
     DevPtr<uint8_t> d_reduced;           // reduced readbacks: the kernel's output, allocated by the first one, grown when a later one needs more
@@ -244,7 +246,7 @@ struct FeFrameOut {               // parts-mode output of one frame, owned per b
 
 }  // namespace dg
 
-using namespace dg;                    // (as the two files that include this do)
+using namespace dg;                    // (as the files that include this do)
 
 struct dg_ctx {
     dg_config cfg{};
@@ -342,6 +344,11 @@ hipError_t slot_sync(Slot &s);
 int check_slot(dg_ctx *c, int slot);
 enum class Copy { Leave, Complete };                   // what make_final does about the slot's pending dg_readback_async
 int make_final(dg_ctx *c, Slot &s, Copy copy);
+// api_readback.cpp's, for make_final and dg_upload_scene: the slot's pending readback queued on its copy stream behind its kernels, and
+// what is left to do on the host once a readback's copies have finished; for dg_replay_slot: a slot without a colour part is refused.
+int enqueue_copy(dg_ctx *c, Slot &s);
+void finish_readback(const dg_ctx *c, const Slot &s, const Slot::Readback &r);
+int refuse_no_colour(const Slot &s, const char *what);
 
 // What the reduced readbacks and dg_reduce_device check before anything else.
 inline int check_reduce_desc(const dg_reduce_desc *desc) {
