@@ -88,6 +88,14 @@ class DgMobjPlaced(ctypes.Structure):
     _fields_ = [("x", ctypes.c_float), ("y", ctypes.c_float), ("angle", ctypes.c_float), ("sector", ctypes.c_int32)]
 
 
+class DgSectorHeights(ctypes.Structure):
+    _fields_ = [("sector", ctypes.c_int32), ("floor_height", ctypes.c_int32), ("ceiling_height", ctypes.c_int32)]
+
+
+class DgViewSectors(ctypes.Structure):
+    _fields_ = [("heights", ctypes.POINTER(DgSectorHeights)), ("n", ctypes.c_uint32)]
+
+
 # a row of dg_mobj_placed as numpy sees it (dg_scene_mobj_poses, dg_slot_mobj_poses)
 MOBJ_PLACED_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("angle", "<f4"), ("sector", "<i4")])
 
@@ -238,6 +246,13 @@ _SIGNATURES = {
     "dg_submit_bundle_views_poses": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.c_int, ctypes.c_uint32]),
     "dg_slot_mobj_poses": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "dg_slot_mobj_pose_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "dg_build_lists_sectors": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.POINTER(DgFrameLists), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32))]),
+    "dg_scene_sector_heights": (ctypes.c_int, [_P, _P, _P, ctypes.c_int]),
+    "dg_submit_views_sectors": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.c_int]),
+    "dg_render_views_sectors": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.c_int, _P]),
+    "dg_submit_bundle_views_sectors": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.c_int, ctypes.c_uint32]),
+    "dg_slot_sector_heights": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "dg_slot_sector_height_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "dg_build_lists_owners": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgFrameLists), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32))]),
     "dg_submit_label_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int]),
     "dg_render_label_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int, _P, _P, _P]),
@@ -539,6 +554,18 @@ def make_view_poses(poses):
     return arr, keep
 
 
+def make_view_sectors(sectors):
+    """sectors: one list per view of (sector, floor_height, ceiling_height) entries (dg_sector_heights).
+    Returns (ctypes array of dg_view_sectors, keep-alive list)."""
+    arr = (DgViewSectors * max(1, len(sectors)))()
+    keep = []
+    for i, entries in enumerate(sectors):
+        ha = (DgSectorHeights * max(1, len(entries)))(*[DgSectorHeights(int(s), int(f), int(c)) for s, f, c in entries])
+        keep.append(ha)
+        arr[i] = DgViewSectors(ha, len(entries))
+    return arr, keep
+
+
 def make_views(records, timestamp: float = 0.0):
     """camera_path records (n, 8) f32 [x, y, angle, cos, sin, cos(-a), sin(-a), floor] -> ctypes array of dg_view."""
     recs = np.asarray(records, dtype=np.float32).reshape(-1, 8)
@@ -644,6 +671,24 @@ class Scene:
         own = ctypes.POINTER(ctypes.c_uint32)()
         _check(lib().dg_build_lists_poses(self._h, W, H, ctypes.byref(view), vp, ctypes.byref(fl), ctypes.byref(own) if owners else None))
         return (fl, np.array(own[:fl.n_renders], dtype=np.uint32)) if owners else fl
+
+    def build_lists_sectors(self, W: int, H: int, view: DgView, sectors=None, poses=None, owners: bool = False):
+        """dg_build_lists_sectors: build_lists_poses for a view whose sectors have the heights `sectors` says
+        ([(sector, floor, ceiling), ...] or None)."""
+        fl = DgFrameLists()
+        vp, _keep = make_view_poses([poses]) if poses is not None else (None, None)
+        vs, _keep2 = make_view_sectors([sectors]) if sectors is not None else (None, None)
+        own = ctypes.POINTER(ctypes.c_uint32)()
+        _check(lib().dg_build_lists_sectors(self._h, W, H, ctypes.byref(view), vp, vs, ctypes.byref(fl), ctypes.byref(own) if owners else None))
+        return (fl, np.array(own[:fl.n_renders], dtype=np.uint32)) if owners else fl
+
+    def sector_heights(self) -> np.ndarray:
+        """dg_scene_sector_heights: every sector's (floor, ceiling) as loaded, an (n, 2) int16 array."""
+        n = lib().dg_scene_sector_count(self._h)
+        fl = np.zeros(max(n, 0), dtype=np.int16)
+        ce = np.zeros(max(n, 0), dtype=np.int16)
+        _check(lib().dg_scene_sector_heights(self._h, fl.ctypes.data_as(_P), ce.ctypes.data_as(_P), n))
+        return np.stack([fl, ce], axis=1)
 
     def sectors_at(self, x, y) -> np.ndarray:
         """dg_scene_sectors_at: get_sector_from_vertex of every point (float32 arrays x, y) as an int32 array, -1 for None."""
@@ -781,6 +826,34 @@ class Context:
         """dg_slot_mobj_pose_timing: GPU time (ms) of the pose kernels of the slot's last submission (0: none ran)."""
         t = ctypes.c_float()
         _check(lib().dg_slot_mobj_pose_timing(self._h, slot, ctypes.byref(t)))
+        return t.value
+
+    def submit_sectors(self, slot: int, views, sectors, n=None, states=None, poses=None):
+        """dg_submit_views_sectors: submit_poses() with a dg_view_sectors per view (make_view_sectors; None: none)."""
+        _check(lib().dg_submit_views_sectors(self._h, slot, views, states, poses, sectors, len(views) if n is None else n))
+
+    def render_sectors(self, views, sectors, states=None, poses=None) -> np.ndarray:
+        """dg_render_views_sectors: synchronous, slot 0; returns (n, H, W, 3) uint8."""
+        n = len(views)
+        out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
+        _check(lib().dg_render_views_sectors(self._h, views, states, poses, sectors, n, out.ctypes.data_as(_P)))
+        return out
+
+    def submit_bundle_sectors(self, slot: int, views, what: int, sectors, n=None, states=None, poses=None):
+        """dg_submit_bundle_views_sectors: submit_bundle_poses() with a dg_view_sectors per view."""
+        _check(lib().dg_submit_bundle_views_sectors(self._h, slot, views, states, poses, sectors, len(views) if n is None else n, what))
+
+    def slot_sector_heights(self, slot: int, first: int, count: int) -> np.ndarray:
+        """dg_slot_sector_heights: the (count, sectors, 2) int16 heights (floor, ceiling) the slot's frames were drawn with."""
+        n = lib().dg_scene_sector_count(self._scene._h) if self._scene is not None else 0
+        out = np.zeros((max(count, 0), max(n, 0), 2), dtype=np.int16)
+        _check(lib().dg_slot_sector_heights(self._h, slot, first, count, out.ctypes.data_as(_P)))
+        return out
+
+    def sector_height_timing(self, slot: int) -> float:
+        """dg_slot_sector_height_timing: GPU time (ms) of the row kernels of the slot's last submission (0: none ran)."""
+        t = ctypes.c_float()
+        _check(lib().dg_slot_sector_height_timing(self._h, slot, ctypes.byref(t)))
         return t.value
 
     def submit_map(self, slot: int, views, n=None):

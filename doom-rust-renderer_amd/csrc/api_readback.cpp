@@ -358,6 +358,47 @@ int dg_slot_mobj_poses(dg_ctx *c, int slot, int first, int count, dg_mobj_placed
     return DG_OK;
 }
 
+int dg_slot_sector_heights(dg_ctx *c, int slot, int first, int count, int16_t *out) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (s.phase == Slot::Phase::Empty || !s.from_views || !c->scene) return set_err(DG_ERR_STATE, "dg_slot_sector_heights: the slot holds no view submission");
+    if ((rc = check_range(s, first, count, out != nullptr, "bad frame range"))) return rc;
+    if (count == 0) return DG_OK;
+    if ((rc = settle(c, s, Copy::Leave))) return rc;       // (a seg-walk batch redone as a whole is a host-list batch from here on)
+    const Scene &sc = *c->scene;
+    const size_t n_sectors = sc.sectors.size();
+    if (n_sectors == 0) return DG_OK;
+    if (s.seg_walk() && s.HR.n_frames > 0) {               // the rows the row kernels wrote
+        HIP_TRY(hipMemcpyAsync(out, s.HR.rows + (size_t)first * n_sectors, (size_t)count * n_sectors * sizeof(FsHeights), hipMemcpyDeviceToHost, s.stream.get()));
+        HIP_TRY(slot_sync(s));
+        return DG_OK;
+    }
+    FrameArena &A = *c->arenas[0];                         // the host walker's rule over the kept entries
+    for (int i = 0; i < count; i++) {
+        FsHeights *row = reinterpret_cast<FsHeights *>(out) + (size_t)i * n_sectors;
+        std::memcpy(row, sc.fs_heights.data(), n_sectors * sizeof(FsHeights));
+        const dg_view_sectors *vs = s.sectors_of(first + i);
+        if (!vs) continue;
+        (void)resolve_view_sectors(sc, *vs, A.height_of, A.heights);
+        for (const dg_sector_heights &h : A.heights) sector_row_place(row, h.sector, h.floor_height, h.ceiling_height);
+        release_view_sectors(A.height_of, A.heights);
+    }
+    return DG_OK;
+}
+
+int dg_slot_sector_height_timing(dg_ctx *c, int slot, float *ms) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!ms) return set_err(DG_ERR_INVALID, "null argument");
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
+    if ((rc = settle(c, s, Copy::Leave))) return rc;
+    *ms = 0.0f;
+    if (s.seg_walk() && s.HR.n_frames > 0) HIP_TRY(hipEventElapsedTime(ms, (s.hrow_from_start ? s.ev_start : s.ev_hrow0).get(), s.ev_hrow.get()));
+    return DG_OK;
+}
+
 int dg_slot_framebuffer(dg_ctx *c, int slot, void **p) {
     int rc = check_slot(c, slot);
     if (rc) return rc;

@@ -246,14 +246,28 @@ int dg_build_lists_owners(const dg_scene *s, int width, int height, const dg_vie
 }
 
 int dg_build_lists_poses(const dg_scene *s, int width, int height, const dg_view *view, const dg_view_poses *poses, dg_frame_lists *out, const uint32_t **owners) {
+    return dg_build_lists_sectors(s, width, height, view, poses, nullptr, out, owners);
+}
+
+int dg_scene_sector_heights(const dg_scene *s, int16_t *floor, int16_t *ceiling, int n) {
+    if (!s || !floor || !ceiling) return set_err(DG_ERR_INVALID, "null argument");
+    const Scene &sc = *s->sc;
+    if (n < 0 || (size_t)n != sc.sectors.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_sector_count");
+    for (size_t i = 0; i < sc.sectors.size(); i++) { floor[i] = sc.sectors[i].floor_h; ceiling[i] = sc.sectors[i].ceil_h; }
+    return DG_OK;
+}
+
+int dg_build_lists_sectors(const dg_scene *s, int width, int height, const dg_view *view, const dg_view_poses *poses, const dg_view_sectors *sectors, dg_frame_lists *out,
+                           const uint32_t **owners) {
     if (!s || !view || !out) return set_err(DG_ERR_INVALID, "null argument");
     if (poses && poses->n && !poses->poses) return set_err(DG_ERR_INVALID, "view poses with a null array");
+    if (sectors && sectors->n && !sectors->heights) return set_err(DG_ERR_INVALID, "view sectors with a null array");
     std::string err;
     int rc = owners ? check_label_scene(*s->sc, err) : DG_OK;
     if (rc) return set_err(rc, err);
     dg_view v = *view;
     fill_view_trig(v);
-    rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, nullptr, &s->sc->fx, poses);
+    rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, nullptr, &s->sc->fx, poses, sectors);
     if (rc) return set_err(rc, err);
     if (owners) *owners = lists_arena().owners.data();
     return DG_OK;

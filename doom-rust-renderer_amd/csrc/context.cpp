@@ -144,7 +144,8 @@ void fill_walk_params(dg_ctx *c, Slot &s, int n) {
 // submission, and a bundle that says so (want_owners), needs owner tags: the tags of the wall records then go into the slot's owner array
 // as well (the caller has allocated it), from given_owners[i] for the caller's lists.
 int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, int32_t fe = DG_FE_HOST,
-                     const uint32_t *const *given_owners = nullptr, bool want_owners = false, const dg_view_poses *poses = nullptr) {
+                     const uint32_t *const *given_owners = nullptr, bool want_owners = false, const dg_view_poses *poses = nullptr,
+                     const dg_view_sectors *sectors = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -164,7 +165,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
             dg_view v = views[i];
             fill_view_trig(v);
             dg_frame_lists fl;
-            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr);
+            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr, sectors ? &sectors[i] : nullptr);
             if (!rc[(size_t)i]) rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
             if (labels && !rc[(size_t)i]) rc[(size_t)i] = wall_owners(sc, fl, c->arenas[(size_t)wid]->owners.data(), c->label_tags[(size_t)i], errs[(size_t)i]);
         }
@@ -202,7 +203,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
 
 // DG_FE_DEVICE: build the per-seg / per-sprite records of n views in parallel, pack them into the slot's record slab,
 // fill slot.FP / slot.P.  Returns kPartsUnsupported when the batch has to go through build_batch_host instead.
-int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses) {
+int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -214,7 +215,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         FeFrameOut &o = c->fe_out[(size_t)i];
         dg_view v = views[i];
         fill_view_trig(v);
-        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr);
+        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr, sectors ? &sectors[i] : nullptr);
         if (rc[(size_t)i]) return;
         o.parts.swap(A.parts); o.sprites.swap(A.sprites); o.behind.swap(A.behind); o.sky_parts.swap(A.sky_parts);
         o.bin_off.swap(A.bin_off); o.bin_parts.swap(A.bin_parts); o.sbin_off.swap(A.sbin_off); o.sbin_sprites.swap(A.sbin_sprites);
@@ -288,7 +289,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     s.keep_states(states, n);
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (n >= 64 && !states && !poses) c->fe_auto.host_batch((double)s.host_ms, n);      // DG_FE_AUTO's measurement of the host side
+    if (n >= 64 && !states && !poses && !sectors) c->fe_auto.host_batch((double)s.host_ms, n);      // DG_FE_AUTO's measurement of the host side
     HIP_TRY(hipMemcpyAsync(s.d_fe.get(), s.h_fe.get(), L.total, hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
@@ -337,6 +338,7 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
     const size_t anims = t.add(sc.fs_anims), bitmaps = t.add(sc.fs_bitmaps), sky = t.add(sc.flat_sky), mobjs = t.add(sc.fs_mobjs);
     const size_t sframes = t.add(sc.sprite_frames), aoff = t.add(sc.fs_anc_off), anc = t.add(sc.fs_anc);
     const size_t wnodes = t.add(sc.walk_nodes), wleaf = t.add(sc.walk_leaf_sector);       // the pose kernels' descent (mobj_pose_core.h)
+    const size_t heights = t.add(sc.fs_heights);                                         // what the sector height rows start as (sector_rows_core.h)
     HIP_TRY(t.upload(c->d_fs_scene));
     FsParams &P = c->fs_proto;
     P = FsParams{};
@@ -373,6 +375,19 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
             if (hip_alloc(b.d_pose_rows, cells * sizeof(FsMobj)) != hipSuccess || hip_alloc(b.h_pose_entries, cells * sizeof(PoseEntry)) != hipSuccess ||
                 hip_alloc(b.d_pose_entries, cells * sizeof(PoseEntry)) != hipSuccess) {
                 b.d_pose_rows.reset(); b.h_pose_entries.reset(); b.d_pose_entries.reset();
+                (void)hipGetLastError();
+            }
+        }
+    }
+    // per-view sector heights, by the same rule: every slot's rows and entry staging (slab_layout.h SectorRowLayout)
+    c->d_scene_heights = sc.sectors.empty() ? nullptr : t.at<FsHeights>(heights);
+    if (c->d_scene_heights) {
+        const SectorRowLayout H = sector_row_layout((size_t)c->cfg.max_batch, sc.sectors.size());
+        for (Slot &s : c->slots) {
+            Slot::PerScene &b = s.per_scene;
+            if (hip_alloc(b.d_height_rows, H.rows) != hipSuccess || hip_alloc(b.h_height_entries, H.entries) != hipSuccess ||
+                hip_alloc(b.d_height_entries, H.entries) != hipSuccess) {
+                b.d_height_rows.reset(); b.h_height_entries.reset(); b.d_height_entries.reset();
                 (void)hipGetLastError();
             }
         }
@@ -427,7 +442,7 @@ void wire_rows(Rows &R, const Rows &proto, const dg_view *views, int n_frames, c
 // DG_FE_DEVICE_SEGS: nothing of the front end runs on the host.  Per frame it ships the view (trig filled) and the DevFrame header,
 // per batch the scene's current light levels and map-object states; dg_fs_* then write the same record arrays build_batch_fe packs,
 // with fixed per-frame strides (fs_frame.h), into the slot's record slab.
-int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses) {
+int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -462,6 +477,19 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
             for (const dg_mobj_pose &p : A.poses) he[n_pose_entries++] = PoseEntry{i, p.mobj, p.x, p.y, p.angle};     // (at most one per object and frame: the staging holds them)
             release_view_poses(A.pose_of, A.poses);
             if (!ok) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": view poses: map object index out of range");
+        }
+    }
+    // per-view sector heights, likewise: the entries that stand into the slot's staging; the row kernels write the rows from them
+    uint32_t n_height_entries = 0;
+    if (sectors) {
+        if (!s.per_scene.d_height_rows || !c->d_scene_heights || (uint64_t)n * sc.sectors.size() >= (1ull << 31)) { c->fallbacks_fe++; return kPartsUnsupported; }
+        FrameArena &A = *c->arenas[0];
+        SectorEntry *const he = s.per_scene.h_height_entries.get();
+        for (int i = 0; i < n; i++) {
+            const unsigned bad = resolve_view_sectors(sc, sectors[i], A.height_of, A.heights);
+            for (const dg_sector_heights &e : A.heights) he[n_height_entries++] = SectorEntry{i, e.sector, (int16_t)e.floor_height, (int16_t)e.ceiling_height};   // (at most one per sector and frame: the staging holds them)
+            release_view_sectors(A.height_of, A.heights);
+            if (bad) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": " + view_sectors_error(bad));
         }
     }
     uint8_t *const h = s.h_fe.get(), *const d = s.d_fe.get();
@@ -512,6 +540,11 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         s.PP.n_frames = (uint32_t)n; s.PP.n_entries = n_pose_entries;
         Q.mobjs = s.PP.rows; Q.mobj_stride = s.PP.n_mobjs;
     }
+    s.HR = SectorRowParams{};
+    if (sectors) {                                         // the row-reading seg walk reads the rows dg_sector_row_fill / _scatter write
+        s.HR = SectorRowParams{c->d_scene_heights, s.per_scene.d_height_entries.get(), s.per_scene.d_height_rows.get(), (uint32_t)sc.sectors.size(), (uint32_t)n,
+                               n_height_entries};
+    }
     s.LR = LfxRows{};
     if (lfx) wire_rows(s.LR, c->lfx_proto, Q.views, n, states ? reinterpret_cast<const uint32_t *>(d + L.lmask) : nullptr,
                        reinterpret_cast<int16_t *>(d + (states ? L.lights : L.lrows)), sc.sectors.size(), Q.sector_light, Q.light_stride);
@@ -535,19 +568,21 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(d, h, L.upload, hipMemcpyHostToDevice, s.stream.get()));
     if (n_pose_entries) HIP_TRY(hipMemcpyAsync(s.per_scene.d_pose_entries.get(), s.per_scene.h_pose_entries.get(), (size_t)n_pose_entries * sizeof(PoseEntry), hipMemcpyHostToDevice, s.stream.get()));
+    if (n_height_entries) HIP_TRY(hipMemcpyAsync(s.per_scene.d_height_entries.get(), s.per_scene.h_height_entries.get(), (size_t)n_height_entries * sizeof(SectorEntry), hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
 
-int build_batch(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, const dg_view_poses *poses = nullptr) {
+int build_batch(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, const dg_view_poses *poses = nullptr,
+                const dg_view_sectors *sectors = nullptr) {
     if (!given && c->fs_enabled && c->fs_scene_ok && choose_fs(c, views, n)) {
-        const int rc = build_batch_fs(c, s, views, n, states, poses);
+        const int rc = build_batch_fs(c, s, views, n, states, poses, sectors);
         if (rc != kPartsUnsupported) return rc;
     }
     if (!given && c->fe_enabled && c->fe_scene_ok) {
-        const int rc = build_batch_fe(c, s, views, n, states, poses);
+        const int rc = build_batch_fe(c, s, views, n, states, poses, sectors);
         if (rc != kPartsUnsupported) return rc;
     }
-    return build_batch_host(c, s, views, given, n, states, DG_FE_HOST, nullptr, false, poses);
+    return build_batch_host(c, s, views, given, n, states, DG_FE_HOST, nullptr, false, poses, sectors);
 }
 
 // The 2-D map view's linedef layer of the uploaded scene, on the kernel stream (timed by the slot's ev_start / ev_setup).  The line records
@@ -724,7 +759,14 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
             if (s.PP.n_frames > 0) { HIP_TRY(launch_mobj_poses(s.PP, ks, fs_start, s.ev_pose.get())); fs_start = nullptr; }   // the rows dg_fs_frame's map-object phase reads
             if (s.LR.n_frames > 0) { HIP_TRY(launch_light_rows(s.LR, ks, fs_start)); fs_start = nullptr; }     // the rows dg_fs_* read
             if (s.MR.n_frames > 0) { HIP_TRY(launch_mobj_rows(s.MR, ks, fs_start)); fs_start = nullptr; }
-            HIP_TRY(c->fx.wall.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
+            if (s.HR.n_frames > 0) {                                                                    // the height rows, then the pair that reads them
+                s.hrow_from_start = fs_start != nullptr;
+                HIP_TRY(launch_sector_rows(s.HR, ks, fs_start ? fs_start : s.ev_hrow0.get(), s.ev_hrow.get()));
+                const FsRows R{s.HR.rows, s.HR.n_sectors};
+                HIP_TRY(c->fx.wall.on() ? launch_fs_rows_fx(s.FSP, FsRowsFx{c->fs_fx, R.rows, R.stride}, ks) : launch_fs_rows(s.FSP, R, ks));
+            } else {
+                HIP_TRY(c->fx.wall.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
+            }
             c->fs_rows_dirty = false;
         }
         HIP_TRY(launch_fe(s.FP, ks, s.seg_walk() ? nullptr : s.ev_start.get(), s.ev_setup.get()));
@@ -755,7 +797,7 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     fill_view_trig(v);
     dg_frame_lists fl;
     Slot::RedoState redo_state;
-    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->fx), &c->fx, s.poses_of(i));
+    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->fx), &c->fx, s.poses_of(i), s.sectors_of(i));
     if (!rc) rc = bin_frame(sc, c->fk, fl, bf, err);
     if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
@@ -813,7 +855,7 @@ int redo_overflowed(dg_ctx *c, Slot &s) {
         any_state |= st != nullptr;
         sts.push_back(st ? *st : dg_view_state{nullptr, 0, nullptr, 0});
     }
-    int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), any_state ? sts.data() : nullptr, DG_FE_HOST, nullptr, false, s.poses_of(0));
+    int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), any_state ? sts.data() : nullptr, DG_FE_HOST, nullptr, false, s.poses_of(0), s.sectors_of(0));
     if (rc) return rc;
     rc = enqueue_kernels(c, s);
     if (rc) return rc;
@@ -875,20 +917,22 @@ int take_slot(dg_ctx *c, Slot &s) {
 
 // What a submission built for the slot leaves for later: whether it came from views, and then a copy of their poses (the caller's
 // arrays need not outlive the call).
-void built_from(Slot &s, const dg_view *views, const dg_view_poses *poses, int n) {
+void built_from(Slot &s, const dg_view *views, const dg_view_poses *poses, int n, const dg_view_sectors *sectors = nullptr) {
     s.from_views = views != nullptr;
     s.keep_poses(views ? poses : nullptr, n);
+    s.keep_sectors(views ? sectors : nullptr, n);
 }
 
 // Slot `slot` for a new submission of n views (or of the caller's lists), and its kernels enqueued.
-int submit(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states, const dg_view_poses *poses = nullptr) {
+int submit(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states, const dg_view_poses *poses = nullptr,
+           const dg_view_sectors *sectors = nullptr) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     int rc = take_slot(c, s);
     if (rc) return rc;
-    rc = build_batch(c, s, views, given, n, states, poses);
+    rc = build_batch(c, s, views, given, n, states, poses, sectors);
     if (rc) return rc;
-    built_from(s, views, poses, n);
+    built_from(s, views, poses, n, sectors);
     return enqueue_kernels(c, s);
 }
 
@@ -1001,7 +1045,7 @@ int enqueue_bundle(dg_ctx *c, Slot &s) {
 // Slot `slot` for a bundle of n views (or of the caller's lists, with their owner tags when labels are asked for): the host list path
 // whatever front end the ctx has, one list build and one upload for every part.
 int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, const uint32_t *const *owners, int n, const dg_view_state *states,
-                  uint32_t what, const dg_view_poses *poses = nullptr) {
+                  uint32_t what, const dg_view_poses *poses = nullptr, const dg_view_sectors *sectors = nullptr) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     if (const int bad = check_batch(c, n)) return bad;
@@ -1012,12 +1056,12 @@ int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     if (labels && (rc = check_label_scene(*c->scene, err))) return set_err(rc, err);
     if ((rc = take_slot(c, s))) return rc;
     if (labels && (rc = ensure_label_buffers(c, s))) return rc;
-    rc = build_batch_host(c, s, views, given, n, states, DG_FE_BUNDLE, owners, labels, poses);
+    rc = build_batch_host(c, s, views, given, n, states, DG_FE_BUNDLE, owners, labels, poses, sectors);
     if (rc) {
         if (s.phase == Slot::Phase::Prepared && s.front_end == DG_FE_BUNDLE) s.reset();   // (described, then an upload failed: nothing says yet which parts it has)
         return rc;
     }
-    built_from(s, views, poses, n);
+    built_from(s, views, poses, n, sectors);
     s.bundle_what = what;
     return enqueue_bundle(c, s);
 }
@@ -1026,6 +1070,13 @@ int check_view_poses(const dg_view_poses *poses, int n) {
     if (poses)
         for (int i = 0; i < n; i++)
             if (poses[i].n && !poses[i].poses) return set_err(DG_ERR_INVALID, "view poses with a null array");
+    return DG_OK;
+}
+
+int check_view_sectors(const dg_view_sectors *sectors, int n) {
+    if (sectors)
+        for (int i = 0; i < n; i++)
+            if (sectors[i].n && !sectors[i].heights) return set_err(DG_ERR_INVALID, "view sectors with a null array");
     return DG_OK;
 }
 
@@ -1176,7 +1227,7 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
     }
     for (Slot &s : c->slots) {
         HIP_TRY(stream_create(s.stream));
-        for (Event *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles, &s.ev_pose}) HIP_TRY(event_create(*ev));
+        for (Event *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles, &s.ev_pose, &s.ev_hrow0, &s.ev_hrow}) HIP_TRY(event_create(*ev));
         HIP_TRY(event_create(s.ev_h2d, false));            // (it only orders streams)
         HIP_TRY(stream_create(s.copy_stream));
         HIP_TRY(hip_alloc(s.h_lists, lists_cap));
@@ -1280,13 +1331,22 @@ int dg_submit_views_state(dg_ctx *c, int slot, const dg_view *views, const dg_vi
 }
 
 int dg_submit_views_poses(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, int n) {
+    return dg_submit_views_sectors(c, slot, views, states, poses, nullptr, n);
+}
+
+int dg_submit_views_sectors(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, int n) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
     rc = check_view_states(states, n);
     if (!rc) rc = check_view_poses(poses, n);
+    if (!rc) rc = check_view_sectors(sectors, n);
     if (rc) return rc;
-    return submit(c, slot, views, nullptr, n, states, poses);
+    return submit(c, slot, views, nullptr, n, states, poses, sectors);
+}
+
+int dg_render_views_sectors(dg_ctx *c, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, int n, uint8_t *out) {
+    return read_or_wait(c, 0, dg_submit_views_sectors(c, 0, views, states, poses, sectors, n), n, out);
 }
 
 int dg_render_views_poses(dg_ctx *c, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, int n, uint8_t *out) {
@@ -1418,14 +1478,20 @@ int dg_submit_bundle_views(dg_ctx *c, int slot, const dg_view *views, const dg_v
 }
 
 int dg_submit_bundle_views_poses(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, int n, uint32_t what) {
+    return dg_submit_bundle_views_sectors(c, slot, views, states, poses, nullptr, n, what);
+}
+
+int dg_submit_bundle_views_sectors(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, int n,
+                                   uint32_t what) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
     if ((rc = check_bundle_what(what))) return rc;
     rc = check_view_states(states, n);
     if (!rc) rc = check_view_poses(poses, n);
+    if (!rc) rc = check_view_sectors(sectors, n);
     if (rc) return rc;
-    return submit_bundle(c, slot, views, nullptr, nullptr, n, states, what, poses);
+    return submit_bundle(c, slot, views, nullptr, nullptr, n, states, what, poses, sectors);
 }
 
 int dg_bundle_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uint32_t *const *owners, int n, uint32_t what) {

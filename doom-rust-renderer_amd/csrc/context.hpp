@@ -22,6 +22,7 @@
 #include "light_fx_kernels.hpp"
 #include "mobj_fx_kernels.hpp"
 #include "mobj_pose_kernels.hpp"
+#include "sector_rows_kernels.hpp"
 #include "plane_kernels.hpp"
 #include "pool.hpp"
 #include "reduce_core.h"
@@ -45,6 +46,8 @@ struct Slot {
     // bundles: the end of the colour raster launch when dg_bundle_tiles follows it (ev_raster is then that kernel's end: always the end of
     // the submission's LAST kernel), and dg_bundle_tiles' start
     Event ev_cend, ev_tiles;
+    bool hrow_from_start = false; // their start is ev_start (they were the batch's first kernels), not ev_hrow0
+    Event ev_hrow0, ev_hrow;      // start and end of the sector height row kernels of a seg-walk batch with sector entries
     Event ev_pose;                // the end of the pose kernels, which are the first of a seg-walk batch with poses (ev_start is their start)
     // ev_raster has been recorded at least once: slot_sync waits only on an event that has.  Not part of the phase below, because it is
     // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
@@ -94,6 +97,10 @@ struct Slot {
         DevPtr<FsMobj> d_pose_rows;
         PinnedPtr<PoseEntry> h_pose_entries;
         DevPtr<PoseEntry> d_pose_entries;
+        // per-view sector heights through the seg walk, by the same rule: slab_layout.h's SectorRowLayout
+        DevPtr<FsHeights> d_height_rows;
+        PinnedPtr<SectorEntry> h_height_entries;
+        DevPtr<SectorEntry> d_height_entries;
         void drop() { *this = PerScene{}; }
     } per_scene;
     // What a map submission (front_end DG_FE_MAP*) leaves for its kernels and for dg_replay_slot besides d_lists (the arrow lines, then a
@@ -134,6 +141,7 @@ struct Slot {
     FsParams FSP{};               // DG_FE_DEVICE_SEGS: the device seg walk in front of the column walk
     LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
     MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
+    SectorRowParams HR{};         // ... and, for a batch with sector entries, dg_sector_row_fill / _scatter; the seg walk is then the row-reading pair (HR.n_frames 0: neither)
     PoseParams PP{};              // ... and, for a batch with poses, dg_mobj_pose_fill / _place in front of them all (PP.n_frames 0: not launched)
     // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
     // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP / DG_FE_MAP_EXPLORED / DG_FE_MAP_EGO (2-D map frames: arrow lines at the start of d_lists) or
@@ -181,6 +189,17 @@ struct Slot {
     std::vector<dg_mobj_pose> pose_entries;
     bool from_views = false;
     const dg_view_poses *poses_of(int i) const { return poses.empty() ? nullptr : &poses[(size_t)i]; }
+    // ... and of their sector heights, kept likewise (dg_slot_sector_heights derives a host-walker submission's rows from them)
+    std::vector<dg_view_sectors> sectors;
+    std::vector<dg_sector_heights> sector_entries;
+    const dg_view_sectors *sectors_of(int i) const { return sectors.empty() ? nullptr : &sectors[(size_t)i]; }
+    void keep_sectors(const dg_view_sectors *vs, int n) {
+        sectors.clear(); sector_entries.clear();
+        if (!vs) return;
+        for (int i = 0; i < n; i++) sector_entries.insert(sector_entries.end(), vs[i].heights, vs[i].heights + vs[i].n);
+        size_t o = 0;
+        for (int i = 0; i < n; i++) { sectors.push_back(dg_view_sectors{sector_entries.data() + o, vs[i].n}); o += vs[i].n; }
+    }
     void keep_poses(const dg_view_poses *ps, int n) {
         poses.clear(); pose_entries.clear();
         if (!ps) return;
@@ -293,6 +312,7 @@ struct dg_ctx {
     DevPtr<uint8_t> d_fs_scratch;       // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
     size_t fs_zero_bytes = 0;
     FsParams fs_proto{};                // scene pointers and counts, filled at upload
+    const FsHeights *d_scene_heights = nullptr;   // the scene's heights as loaded, in d_fs_scene: what the height rows start as
     PoseParams pose_proto{};            // the pose kernels' scene pointers (the scene's rows, the BSP, the leaves' sectors), filled at upload
     uint64_t fallbacks_fe = 0;          // batches in which frames were redone because a device-side capacity was exceeded (dg_ctx_fallbacks)
     uint64_t redone_frames = 0;         // frames redone through the host list path, one at a time (dg_ctx_redone_frames)

@@ -32,7 +32,9 @@ struct Color { uint8_t r, g, b, a; };            // sdl2::pixels::Color as the r
 struct Vertex { float x, y; };                   // src/map/vertexes.rs:9-13
 struct Player { Vertex position; float floor_height; float angle; };   // src/game.rs:40-45
 // What the renderer reads of the game state that thinkers mutate between frames:
-struct Sector { int16_t light_level; };                                                          // src/map/sectors.rs:8-17 (src/lights.rs:47-259 writes it)
+// floor_height / ceiling_height: what doors, lifts and crushers move; kAsLoaded (the default): the height the SECTORS lump gave.
+constexpr int32_t kAsLoaded = INT32_MIN;
+struct Sector { int16_t light_level; int32_t floor_height = kAsLoaded, ceiling_height = kAsLoaded; };   // src/map/sectors.rs:8-17 (src/lights.rs:47-259 writes the level)
 struct State { const char *sprite; uint8_t frame; bool full_bright; bool is_null; };             // src/info.rs:1265-1273; sprite = "{:?}" of SpriteId; is_null: StateId::S_NULL
 struct MapObject { State state; };                                                               // src/map_objects.rs:10-17 (MapObjectThinker :63-121 writes it)
 
@@ -101,15 +103,41 @@ public:
         out.resize((size_t)dg_scene_mobj_count(h_));
         check(dg_scene_mobj_states_at(h_, timestamp, out.data(), (int)out.size()));
     }
+    // map.sectors as loaded: every sector's light level as drawn at timestamp 0 and its two heights (the start of a caller's own copy).
+    std::vector<Sector> sectors() const {
+        const size_t n = (size_t)dg_scene_sector_count(h_);
+        std::vector<int16_t> light(n), fl(n), ce(n);
+        check(dg_scene_sector_lights_at(h_, 0.0f, light.data(), (int)n));
+        check(dg_scene_sector_heights(h_, fl.data(), ce.data(), (int)n));
+        std::vector<Sector> out(n);
+        for (size_t i = 0; i < n; i++) out[i] = Sector{light[i], fl[i], ce[i]};
+        return out;
+    }
+    // The sectors whose heights sync_state last found moved: what Renderer::render passes as the view's entries.
+    const std::vector<dg_sector_heights> &moved_sectors() const { return moved_; }
+    void set_moved_sectors(const std::vector<Sector> &sectors) {
+        const size_t n = (size_t)dg_scene_sector_count(h_);
+        std::vector<int16_t> fl(n), ce(n);
+        if (n) check(dg_scene_sector_heights(h_, fl.data(), ce.data(), (int)n));
+        moved_.clear();
+        for (size_t i = 0; i < sectors.size() && i < n; i++) {
+            const int32_t f = sectors[i].floor_height == kAsLoaded ? fl[i] : sectors[i].floor_height;
+            const int32_t c = sectors[i].ceiling_height == kAsLoaded ? ce[i] : sectors[i].ceiling_height;
+            if (f != fl[i] || c != ce[i]) moved_.push_back(dg_sector_heights{(int32_t)i, f, c});
+        }
+    }
     bool sector_floor_height(const Vertex &v, float &out) const { return dg_scene_floor_height_at(h_, v.x, v.y, &out) == 0; }  // bsp.rs:9-44
     dg_scene *handle() const { return h_; }
 private:
     dg_scene *h_ = nullptr;
+    std::vector<dg_sector_heights> moved_;
 };
 
 // Game::render, before Renderer(..).render(): the light levels and map-object states of this tick (rust/src/gpu.rs sync_state).
-// Index = position in `map.sectors` / `map_objects.objects`.
+// Index = position in `map.sectors` / `map_objects.objects`.  The sectors' heights that differ from the loaded ones are kept in the
+// World for the next Renderer (a per-view entry each: the scene's own table does not change).
 inline void sync_state(World &world, const std::vector<Sector> &sectors, const std::vector<MapObject> &objects) {
+    world.set_moved_sectors(sectors);
     for (size_t i = 0; i < sectors.size(); i++) check(dg_scene_set_sector_light(world.handle(), (int)i, sectors[i].light_level));
     for (size_t i = 0; i < objects.size(); i++) {
         const State &st = objects[i].state;
@@ -175,20 +203,25 @@ private:
 class Renderer {
 public:
     Renderer(Pixels &pixels, const World &world, const Player &player, float timestamp, Device &dev)
-        : pixels_(pixels), dev_(dev) {
-        (void)world;   // the device already holds the uploaded world; kept in the signature to mirror Renderer::new
+        : pixels_(pixels), dev_(dev), world_(world) {
+        // (the device already holds the uploaded world; what the Renderer reads of it are the sector heights sync_state found moved)
         // Vertex::rotate (src/map/vertexes.rs:20-25) evaluates f32::cos / f32::sin of +-angle: the same libm calls, made here,
         // so that the library consumes the caller's bits (trig_valid = 1) instead of evaluating its own
         const float a = player.angle;
         view_ = dg_view{player.position.x, player.position.y, a, player.floor_height, std::cos(a), std::sin(a), std::cos(-a), std::sin(-a), timestamp, 1};
     }
-    void render() { check(dg_render_views(dev_.handle(), &view_, 1, pixels_.pixels.data())); }
+    void render() {
+        const std::vector<dg_sector_heights> &moved = world_.moved_sectors();
+        const dg_view_sectors vs{moved.data(), (uint32_t)moved.size()};
+        check(dg_render_views_sectors(dev_.handle(), &view_, nullptr, nullptr, moved.empty() ? nullptr : &vs, 1, pixels_.pixels.data()));
+    }
     // The viewing_map branch of Game::render (src/game.rs:491-499): canvas.clear() to black, draw_map_linedefs, draw_map_player, into
     // the same Pixels.  Reads the player's position and angle only.
     void render_map() { check(dg_render_map_views(dev_.handle(), &view_, 1, pixels_.pixels.data())); }
 private:
     Pixels &pixels_;
     Device &dev_;
+    const World &world_;
     dg_view view_;
 };
 

@@ -121,6 +121,7 @@ struct Walker {
     const LightFx *lfx = nullptr;           // the light effects to draw with (nullptr: none)
     const MobjFx *mfx = nullptr;            // the map-object thinkers to draw with (nullptr: none)
     const dg_view_poses *poses = nullptr;   // where this view's map objects are (nullptr: where the scene has them)
+    const FsHeights *hrow = nullptr;        // this view's sector heights, [sector] (nullptr: the scene's, as loaded)
     uint32_t cur_owner = 0;                 // owner tag of the seg / map object being processed (host-list mode)
     static constexpr int32_t kNoOverride = INT32_MIN;
 
@@ -128,7 +129,8 @@ struct Walker {
     // (src/lights.rs:47-259, src/map_objects.rs:63-121): the view's snapshot entry if there is one, else the light effect's level
     //  or the map-object thinker's state (§8d), else the scene's value.  The arena's two rows hold what overrides the
     // scene: the effects' values, every effect sector and driven object once per frame, then the view's entries on top.
-    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const SceneFx *f, const dg_view_poses *ps)
+    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const SceneFx *f, const dg_view_poses *ps,
+           const dg_view_sectors *vs)
         : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e), state(st), fx(f && f->wall.on() ? &f->wall : nullptr),
           lfx(f && f->light.fits(s) ? &f->light : nullptr), mfx(f && f->mobj.fits(s) ? &f->mobj : nullptr), poses(ps) {
         ppos = V2{v.x, v.y};
@@ -140,6 +142,14 @@ struct Walker {
         if (mfx)
             for (uint32_t i : mfx->driven) A.mobj_row[i] = mfx->value(i, v.timestamp);
         if (poses && !resolve_view_poses(sc, *poses, A.pose_of, A.poses)) { status = DG_ERR_INVALID; err = "view poses: map object index out of range"; }
+        if (vs) {                                                    // the scene's heights with the view's entries on top, a row of this frame alone
+            const unsigned bad = resolve_view_sectors(sc, *vs, A.height_of, A.heights);
+            A.height_row.assign(sc.fs_heights.begin(), sc.fs_heights.end());
+            for (const dg_sector_heights &h : A.heights) sector_row_place(A.height_row.data(), h.sector, h.floor_height, h.ceiling_height);
+            release_view_sectors(A.height_of, A.heights);
+            hrow = A.height_row.data();
+            if (bad) { status = DG_ERR_INVALID; err = view_sectors_error(bad); }
+        }
         if (!state) return;
         const unsigned bad = apply_view_state(sc, *state, [&](size_t i, int32_t level) { A.light_row[i] = level; }, [&](size_t i, int32_t val) { A.mobj_row[i] = val; });
         if (bad) { status = DG_ERR_INVALID; err = bad & 2u ? "view state: map object or sprite frame index out of range" : "view state: sector index out of range"; }
@@ -350,7 +360,8 @@ struct Walker {
         if (fx) fs_seg_fx(sg, fx->seg[seg_index], fx->lists.data(), view.timestamp);
         FsSegOut so;
         const int16_t light = sg.front_sector >= 0 ? sector_light(sg.front_sector) : (int16_t)0;
-        const int32_t st = fs_seg(k, sg, sc.fs_sectors.data(), sc.fs_anims.data(), ppos, view.cos_na, view.sin_na, player_height, view.timestamp, light, so);
+        const int32_t st = hrow ? fs_seg(k, sg, sc.fs_sectors.data(), sc.fs_anims.data(), ppos, view.cos_na, view.sin_na, player_height, view.timestamp, light, so, FsNoFx(), 0, FsRowHeights{hrow})
+                                : fs_seg(k, sg, sc.fs_sectors.data(), sc.fs_anims.data(), ppos, view.cos_na, view.sin_na, player_height, view.timestamp, light, so);
         if (st == FS_SKIP) return;
         if (st != FS_OK) { fail_fs(st); return; }
         for (int i = 0; i < so.n_calls && !status; i++)
@@ -458,8 +469,11 @@ struct Walker {
             FsSpriteOut so;
             FsMobjGeom g{};
             if (parts_mode) std::memset(&so.sp, 0, sizeof so.sp);
-            const int32_t st = parts_mode ? fs_mobj(k, fm, sf, sc.fs_bitmaps.data(), sc.fs_sectors.data(), ppos, view.angle, view.cos_na, view.sin_na, player_height, m_full_bright, light, so)
-                                          : fs_mobj_geom(k, fm, sf, sc.fs_bitmaps.data(), sc.fs_sectors.data(), ppos, view.angle, view.cos_na, view.sin_na, player_height, m_full_bright, light, g);
+            const auto placed = [&](const auto &ht) {                 // z = the sector's floor height as this view has it
+                return parts_mode ? fs_mobj(k, fm, sf, sc.fs_bitmaps.data(), sc.fs_sectors.data(), ppos, view.angle, view.cos_na, view.sin_na, player_height, m_full_bright, light, so, ht)
+                                  : fs_mobj_geom(k, fm, sf, sc.fs_bitmaps.data(), sc.fs_sectors.data(), ppos, view.angle, view.cos_na, view.sin_na, player_height, m_full_bright, light, g, ht);
+            };
+            const int32_t st = hrow ? placed(FsRowHeights{hrow}) : placed(FsOwnHeights());
             if (st == FS_SKIP) continue;
             if (st != FS_OK) { fail_fs(st); return; }
             Rec r = make_rec(parts_mode ? so.line : g.cl.line, ST_MAPOBJECT);
@@ -535,7 +549,7 @@ struct Walker {
 }  // namespace
 
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const SceneFx *fx,
-                      const dg_view_poses *poses) {
+                      const dg_view_poses *poses, const dg_view_sectors *sectors) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.renders.clear(); A.owners.clear(); A.columns.clear(); A.visplanes.clear(); A.plane_tb.clear(); A.order.clear();
     A.recs->clear(); A.floor_tb.clear(); A.ceil_tb.clear();
@@ -545,7 +559,7 @@ int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameA
     A.top_clip.resize((size_t)W);
     A.bottom_clip.resize((size_t)W);
 
-    Walker wk(sc, W, H, view, A, err, state, fx, poses);
+    Walker wk(sc, W, H, view, A, err, state, fx, poses, sectors);
     if (wk.status) return wk.status;
     wk.walk_bsp();
     if (wk.status) return wk.status;
@@ -594,11 +608,11 @@ void bin_by_columns(const std::vector<T> &recs, int W, Range range, std::vector<
 }  // namespace
 
 int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state, const SceneFx *fx,
-                      const dg_view_poses *poses) {
+                      const dg_view_poses *poses, const dg_view_sectors *sectors) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.parts.clear(); A.sprites.clear(); A.behind.clear(); A.sky_parts.clear(); A.behind_words = 0; A.n_sky_slots = 0;
     A.recs->clear();
-    Walker wk(sc, W, H, view, A, err, state, fx, poses);
+    Walker wk(sc, W, H, view, A, err, state, fx, poses, sectors);
     if (wk.status) return wk.status;
     wk.parts_mode = true;
     wk.walk_bsp();

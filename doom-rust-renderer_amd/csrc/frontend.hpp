@@ -15,6 +15,7 @@
 #include "../../include/doomgpu.h"
 #include "fe_dev.h"
 #include "scene.hpp"
+#include "sector_rows_core.h"
 
 namespace dg {
 
@@ -52,6 +53,11 @@ struct FrameArena {
     // per map object: its entry in `poses`, the view's poses as they stand (resolve_view_poses), or -1; written and taken back likewise
     std::vector<int32_t> pose_of;
     std::vector<dg_mobj_pose> poses;
+    // per sector: its entry in `heights`, the view's sector entries as they stand (resolve_view_sectors), or -1, likewise; height_row:
+    // the heights one view is drawn with, [sector] — the scene's with those entries on top, written whole by every Walker that has entries
+    std::vector<int32_t> height_of;
+    std::vector<dg_sector_heights> heights;
+    std::vector<FsHeights> height_row;
     FrameArena();
     ~FrameArena();
     FrameArena(const FrameArena &) = delete;
@@ -63,8 +69,10 @@ struct FrameArena {
 // `state` (optional): the view's game-state snapshot (include/doomgpu.h dg_view_state).
 // `fx` (optional): the effects to draw with (Scene::fx, or the copy a dg_ctx uploaded); nullptr: none.
 // `poses` (optional): where the view's map objects are (include/doomgpu.h dg_view_poses); nullptr: where the scene has them.
+// `sectors` (optional): the view's sector floor / ceiling heights (dg_view_sectors); nullptr: as loaded.
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, dg_frame_lists &out, std::string &err,
-                      const dg_view_state *state = nullptr, const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr);
+                      const dg_view_state *state = nullptr, const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr,
+                      const dg_view_sectors *sectors = nullptr);
 
 // Checks a view's snapshot against the scene's ranges and hands every valid entry, in order (later entries win), to light(sector, level)
 // or mobj(map object, mfx_encode'd state).  Returns 0, or bit 0: a sector index was out of range, bit 1: a map object or sprite frame
@@ -106,6 +114,31 @@ inline void release_view_poses(std::vector<int32_t> &pose_of, const std::vector<
     for (const dg_mobj_pose &p : out) pose_of[(size_t)p.mobj] = -1;
 }
 
+// A view's sector heights as they stand, by the same rules: of two entries for one sector the later wins; out holds one entry per
+// sector in the order of the sectors' first entries, height_of[sector] its place in out, else -1 (in all -1 or empty, handed back so by
+// release_view_sectors).  Returns 0, or bit 0: a sector index out of range, bit 1: a height outside int16 (the other entries still
+// stand).  The host walker, build_batch_fs (context.cpp) and dg_slot_sector_heights all go through it.
+inline unsigned resolve_view_sectors(const Scene &sc, const dg_view_sectors &vs, std::vector<int32_t> &height_of, std::vector<dg_sector_heights> &out) {
+    out.clear();
+    if (height_of.size() != sc.sectors.size()) height_of.assign(sc.sectors.size(), -1);
+    unsigned bad = 0;
+    for (uint32_t i = 0; i < vs.n; i++) {
+        const dg_sector_heights &h = vs.heights[i];
+        if (h.sector < 0 || (size_t)h.sector >= sc.sectors.size()) { bad |= 1u; continue; }
+        if (h.floor_height < -32768 || h.floor_height > 32767 || h.ceiling_height < -32768 || h.ceiling_height > 32767) { bad |= 2u; continue; }
+        int32_t &at = height_of[(size_t)h.sector];
+        if (at < 0) { at = (int32_t)out.size(); out.push_back(h); }
+        else out[(size_t)at] = h;
+    }
+    return bad;
+}
+inline void release_view_sectors(std::vector<int32_t> &height_of, const std::vector<dg_sector_heights> &out) {
+    for (const dg_sector_heights &h : out) height_of[(size_t)h.sector] = -1;
+}
+inline const char *view_sectors_error(unsigned bad) {
+    return bad & 1u ? "view sectors: sector index out of range" : "view sectors: height outside int16";
+}
+
 void fill_view_trig(dg_view &v);
 
 // Parts mode: the per-seg and per-sprite half only (BSP order, transform, clip, projection, pegging, sprite sorting and the
@@ -114,7 +147,7 @@ void fill_view_trig(dg_view &v);
 // host list path can judge: the caller redoes the frame with build_frame_lists).
 constexpr int kPartsUnsupported = 1000;
 int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, std::string &err, const dg_view_state *state = nullptr,
-                      const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr);
+                      const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr, const dg_view_sectors *sectors = nullptr);
 
 // Per-record constants of render_vertical_bitmap_line (bitmap_render.rs:233-251), shared by the binner and the parts builder.
 DevWallRec make_wall_rec(const BitmapInfo &bi, float lsx, float lsy, float lex, float ley, float start_offset, int32_t start_x, int32_t end_x,

@@ -137,8 +137,8 @@ struct FsSeg {
     uint16_t ld_flags;                      // linedef flags: 4 two-sided, 8 upper unpegged, 16 lower unpegged (linedefs.rs:10-18)
 };
 static_assert(sizeof(FsSeg) == 48, "FsSeg layout");
-struct FsSector {                           // the immutable part of a sector (its light level is game state)
-    int16_t floor_h, ceil_h;
+struct FsSector {                           // a sector as loaded (its light level is game state, and so are its two heights: a view may
+    int16_t floor_h, ceil_h;                // bring its own through FsRowHeights below; these are the loaded ones)
     int32_t floor_flat, ceil_flat;          // flat id (>= 0) when not animated, FLAT_MISSING (-2) when the lump does not exist
     int32_t floor_anim, ceil_anim;          // index into the animation lists, or -1
     uint32_t ceil_tex_sky;                  // sector.ceiling_texture.contains("SKY") (segs.rs:463-469)
@@ -191,6 +191,27 @@ struct FsFx {
     }
 };
 
+// Where fs_seg / fs_mobj read a sector's floor and ceiling heights (Sector.floor_height / .ceiling_height, game state in the reference:
+// segs.rs:376-402,463-484, map_objects.rs:115).  FsOwnHeights: the scene table's own fields, the heights as loaded — the default, and what
+// every caller without per-view heights compiles to.  FsRowHeights: the view's row [sector] (dg_view_sectors, sector_rows_core.h).
+// Both take the sector's record and its index, and hand back one height: stated so, the default reads exactly the field the caller
+// read before there was a policy.
+struct alignas(4) FsHeights { int16_t floor_h, ceil_h; };
+static_assert(sizeof(FsHeights) == 4, "FsHeights layout");
+struct FsOwnHeights {
+    DG_HD int16_t floor(const FsSector &s, int32_t) const { return s.floor_h; }
+    DG_HD int16_t ceil(const FsSector &s, int32_t) const { return s.ceil_h; }
+};
+struct FsRowHeights {
+    const FsHeights *row;                        // [n_sectors] of the frame
+    DG_HD int16_t floor(const FsSector &, int32_t i) const { return row[i].floor_h; }
+    DG_HD int16_t ceil(const FsSector &, int32_t i) const { return row[i].ceil_h; }
+};
+// The heights policy an effects policy carries: none (FsOwnHeights) unless it is an FsWithRows.
+template <typename Fx> struct FsWithRows : Fx { FsRowHeights ht; };
+template <typename Fx> DG_HD FsOwnHeights fs_heights_of(const Fx &) { return FsOwnHeights(); }
+template <typename Fx> DG_HD FsRowHeights fs_heights_of(const FsWithRows<Fx> &x) { return x.ht; }
+
 enum : int32_t {                             // outcome of fs_seg / fs_part
     FS_OK = 0,
     FS_SKIP = 1,                             // nothing to record (not an error)
@@ -222,9 +243,9 @@ DG_HD FsCall fs_call(const FsSegOut &o, uint32_t i) { return i == 0u ? o.call[0]
 // Segs::process_seg, segs.rs:353-590, for a viewer at ppos looking along (cos_na, sin_na) = (cos, sin)(-angle).  light: the front
 // sector's CURRENT light level.  Returns FS_OK with 1 .. 5 calls, FS_SKIP, or a failure.  fx / si: the wall effects and the seg's index
 // (applied past the clip and back-face tests, so that the segs turned away there never look at them).
-template <typename K, typename Fx = FsNoFx>
+template <typename K, typename Fx = FsNoFx, typename Ht = FsOwnHeights>
 DG_HD int32_t fs_seg(const K &k, const FsSeg &sg, const FsSector *sectors, const FsAnim *anims, V2 ppos, float cos_na, float sin_na, float player_height,
-                     float timestamp, int16_t light, FsSegOut &o, const Fx &fx = Fx(), uint32_t si = 0) {
+                     float timestamp, int16_t light, FsSegOut &o, const Fx &fx = Fx(), uint32_t si = 0, const Ht &ht = Ht()) {
     if (sg.front_sector < 0) return FS_SKIP;
     // (the clip comes first here: it needs the seg's two vertices only and turns away most segs of a map; the sector heights the
     // reference reads before it — segs.rs:364-402 — have no side effects and are read below, by the segs that are left)
@@ -235,12 +256,13 @@ DG_HD int32_t fs_seg(const K &k, const FsSeg &sg, const FsSector *sectors, const
 
     const FsSector &fs = sectors[sg.front_sector];
     const FsSector *bs = sg.back_sector >= 0 ? &sectors[sg.back_sector] : nullptr;
-    float floor_height = (float)fs.floor_h, ceiling_height = (float)fs.ceil_h;
+    const int16_t fs_floor_h = ht.floor(fs, sg.front_sector), fs_ceil_h = ht.ceil(fs, sg.front_sector);
+    float floor_height = (float)fs_floor_h, ceiling_height = (float)fs_ceil_h;
     bool has_pb = false, has_pt = false;
     float pb_h = 0.0f, pt_h = 0.0f;
     if (bs) {
-        if (bs->floor_h > fs.floor_h) { has_pb = true; pb_h = (float)bs->floor_h; }
-        if (bs->ceil_h < fs.ceil_h) { has_pt = true; pt_h = (float)bs->ceil_h; }
+        if (ht.floor(*bs, sg.back_sector) > fs_floor_h) { has_pb = true; pb_h = (float)ht.floor(*bs, sg.back_sector); }
+        if (ht.ceil(*bs, sg.back_sector) < fs_ceil_h) { has_pt = true; pt_h = (float)ht.ceil(*bs, sg.back_sector); }
     }
     const bool two_sided = (sg.ld_flags & 4) != 0, top_unpegged = (sg.ld_flags & 8) != 0, bottom_unpegged = (sg.ld_flags & 16) != 0;
 
@@ -255,10 +277,10 @@ DG_HD int32_t fs_seg(const K &k, const FsSeg &sg, const FsSector *sectors, const
     bool draw_ceiling = true;
     if (bs && fs.ceil_tex_sky && bs->ceil_tex_sky) {              // sky hack, segs.rs:463-477
         has_pt = false;
-        ceiling_height = fs_fmin((float)bs->ceil_h, ceiling_height);
+        ceiling_height = fs_fmin((float)ht.ceil(*bs, sg.back_sector), ceiling_height);
         draw_ceiling = false;
     }
-    o.seg_offset = sg.seg_offset; o.floor_h = fs.floor_h; o.ceil_h = fs.ceil_h; o.light = light;
+    o.seg_offset = sg.seg_offset; o.floor_h = fs_floor_h; o.ceil_h = fs_ceil_h; o.light = light;
     o.sd_xoff = sw.sd_xoff; o.sd_yoff = sg.sd_yoff;
     const uint32_t dc = draw_ceiling ? FEP_DRAW_CEILING : 0u;
     if (!two_sided) {
@@ -403,9 +425,9 @@ struct FsMobjGeom {
     int32_t x0, x1;                                               // columns [x0, x1)
     int16_t light, sort_key;
 };
-template <bool kGeomOnly, typename K>
+template <bool kGeomOnly, typename K, typename Ht>
 DG_HD int32_t fs_mobj_body(const K &k, const FsMobj &m, const FsSpriteFrame &sf, const FsBitmap *bitmaps, const FsSector *sectors, V2 ppos, float view_angle,
-                           float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsMobjGeom *g, FsSpriteOut *out) {
+                           float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsMobjGeom *g, FsSpriteOut *out, const Ht &ht) {
     const float kPi = 3.14159265358979323846f;
     float angle = view_angle - m.angle - kPi;
     angle += kPi / 16.0f;
@@ -426,11 +448,12 @@ DG_HD int32_t fs_mobj_body(const K &k, const FsMobj &m, const FsSpriteFrame &sf,
     if (cl.line.a.x < -0.01f) return FS_FAIL_MOBJ_CLIP_X;
     if (m.sector < 0) return FS_SKIP;                             // "Thing is outside map"
     const FsSector &sec = sectors[m.sector];
+    const int16_t sec_floor_h = ht.floor(sec, m.sector);
     const int16_t light = full_bright ? (int16_t)255 : sector_light;
 
     const int16_t bh = bi.h;
-    float bottom_height = (float)sec.floor_h - player_height;
-    float top_height = (float)sec.floor_h + (float)bh - 1.0f - player_height;
+    float bottom_height = (float)sec_floor_h - player_height;
+    float top_height = (float)sec_floor_h + (float)bh - 1.0f - player_height;
     bottom_height += (float)bi.top_offset - (float)bh;
     top_height += (float)bi.top_offset - (float)bh;
     const ScreenLine bot = project(k, cl.line, bottom_height);
@@ -455,15 +478,15 @@ DG_HD int32_t fs_mobj_body(const K &k, const FsMobj &m, const FsSpriteFrame &sf,
     return FS_OK;
 }
 
-template <typename K>
+template <typename K, typename Ht = FsOwnHeights>
 DG_HD int32_t fs_mobj(const K &k, const FsMobj &m, const FsSpriteFrame &sf, const FsBitmap *bitmaps, const FsSector *sectors, V2 ppos, float view_angle,
-                      float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsSpriteOut &o) {
-    return fs_mobj_body<false>(k, m, sf, bitmaps, sectors, ppos, view_angle, cos_na, sin_na, player_height, full_bright, sector_light, nullptr, &o);
+                      float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsSpriteOut &o, const Ht &ht = Ht()) {
+    return fs_mobj_body<false>(k, m, sf, bitmaps, sectors, ppos, view_angle, cos_na, sin_na, player_height, full_bright, sector_light, nullptr, &o, ht);
 }
-template <typename K>
+template <typename K, typename Ht = FsOwnHeights>
 DG_HD int32_t fs_mobj_geom(const K &k, const FsMobj &m, const FsSpriteFrame &sf, const FsBitmap *bitmaps, const FsSector *sectors, V2 ppos, float view_angle,
-                           float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsMobjGeom &g) {
-    return fs_mobj_body<true>(k, m, sf, bitmaps, sectors, ppos, view_angle, cos_na, sin_na, player_height, full_bright, sector_light, &g, nullptr);
+                           float cos_na, float sin_na, float player_height, int32_t full_bright, int16_t sector_light, FsMobjGeom &g, const Ht &ht = Ht()) {
+    return fs_mobj_body<true>(k, m, sf, bitmaps, sectors, ppos, view_angle, cos_na, sin_na, player_height, full_bright, sector_light, &g, nullptr, ht);
 }
 
 }  // namespace dg

@@ -189,7 +189,7 @@ template <typename Fx = FsNoFx> DG_HD void fs_seg_lane(const FsParams &P, int f,
     const FsSeg sg = fs_load_seg(P.segs + si);
     FsSegOut so;
     // (the sector's light level is not read here: nothing below looks at it, fs_ph_emit fetches it for the parts that are kept)
-    const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, (int16_t)0, so, fx, si);
+    const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, (int16_t)0, so, fx, si, fs_heights_of(fx));
     if (st == FS_SKIP || leaf == 0xffffu) return;                             // (a seg of no reachable leaf is never visited; asked here, after the
                                                                               // clip, so that the seg's record is not fetched behind its leaf's)
     if (st != FS_OK) { fs_flag(P, f, FE_OVF_SEGS); return; }
@@ -406,7 +406,7 @@ template <typename Fx = FsNoFx> DG_HD void fs_ph_emit(const FsParams &P, FsShare
         FsSegOut so;
         FePart p;
         const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, P.sector_light[(size_t)f * P.light_stride + (size_t)sg.front_sector], so,
-                                  fx, src >> 3);
+                                  fx, src >> 3, fs_heights_of(fx));
         if (st != FS_OK || fs_part(P.k, so, fs_call(so, src & 7u), P.bitmaps, P.flat_sky, v.floor_height, p) != FS_OK) { fs_or_u32(&S.fail, 1u); continue; }   // (cannot happen: dg_fs_segs passed it)
         p.sky_slot = S.kept_sky[o];
         P.parts[(size_t)f * FS_PART_CAP + o] = p;
@@ -416,7 +416,7 @@ template <typename Fx = FsNoFx> DG_HD void fs_ph_emit(const FsParams &P, FsShare
 }
 // phase 4a: lane l looks at map object base + l (draw_map_objects' per-object part); lane_cnt = 1 when it shows
 struct FsSpriteTmp { FsSpriteOut so; int32_t status; };
-DG_HD void fs_ph_mobj(const FsParams &P, FsShared &S, int f, uint32_t base, int lane, FsSpriteTmp &T) {
+template <typename Fx = FsNoFx> DG_HD void fs_ph_mobj(const FsParams &P, FsShared &S, int f, uint32_t base, int lane, FsSpriteTmp &T, const Fx &fx = Fx()) {
     S.lane_cnt[lane] = 0;
     T.status = FS_SKIP;
     const uint32_t mi = base + (uint32_t)lane;
@@ -426,7 +426,7 @@ DG_HD void fs_ph_mobj(const FsParams &P, FsShared &S, int f, uint32_t base, int 
     const dg_view &v = P.views[f];
     const FsMobj &m = P.mobjs[(size_t)f * P.mobj_stride + mi];
     T.status = fs_mobj(P.k, m, P.sframes[st >> 1], P.bitmaps, P.sectors, V2{v.x, v.y}, v.angle, v.cos_na, v.sin_na, v.floor_height + 41.0f, st & 1,
-                       m.sector >= 0 ? P.sector_light[(size_t)f * P.light_stride + (size_t)m.sector] : (int16_t)0, T.so);
+                       m.sector >= 0 ? P.sector_light[(size_t)f * P.light_stride + (size_t)m.sector] : (int16_t)0, T.so, fs_heights_of(fx));
     if (T.status == FS_OK) S.lane_cnt[lane] = 1;
     else if (T.status != FS_SKIP) fs_or_u32(&S.fail, 1u);              // a failure (any lane may see one)
 }
@@ -621,7 +621,7 @@ DG_HD void fs_ph_header(const FsParams &P, FsShared &S, int f) {
 }  // namespace dg
 
 // ---- the frame's phases in order: the one statement of what dg_fs_frame, dg_wfx_frame and tests/emul run -----------------------------
-// What runs between two barriers is one step.  Expanded where P, S, f and fx are in scope (fx: FsNoFx or FsFx, what fs_seg_lane was given);
+// What runs between two barriers is one step.  Expanded where P, S, f and fx are in scope (fx: FsNoFx or FsFx, or either as FsWithRows with the frame's height row — what fs_seg_lane was given);
 // STEP(...) gets the statements of a step, written for `lane` and that lane's FsSpriteTmp `T`, and supplies both:
 //   a kernel        runs them for its own lane, then the workgroup's barrier (fs_kernels.hpp FS_KERNEL_STEP);
 //   tests/emul      runs them for lanes 0 .. FS_LANES - 1 in turn, one of the interleavings a barrier allows, and needs no barrier.
@@ -639,7 +639,7 @@ DG_HD void fs_ph_header(const FsParams &P, FsShared &S, int f) {
     STEP(fs_ph_emit(P, S, f, lane, fx))                                                 \
     for (uint32_t base = 0; base < P.n_mobjs; base += FS_LANES) {                       \
         const uint32_t n_before = S.n_sprites;                                          \
-        STEP(fs_ph_mobj(P, S, f, base, lane, T))                                        \
+        STEP(fs_ph_mobj(P, S, f, base, lane, T, fx))                                    \
         STEP(fs_ph_block_sums(S, lane))                                                 \
         STEP(fs_ph_mobj_emit(P, S, f, lane, T, n_before))                               \
     }                                                                                   \

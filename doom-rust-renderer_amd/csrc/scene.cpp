@@ -702,6 +702,8 @@ void Scene::rebuild_fs_tables() {
         const SectorRec &s = sectors[i];
         fs_sectors[i] = FsSector{s.floor_h, s.ceil_h, s.floor_flat, s.ceil_flat, s.floor_anim, s.ceil_anim, s.ceil_tex_sky};
     }
+    fs_heights.resize(sectors.size());
+    for (size_t i = 0; i < sectors.size(); i++) fs_heights[i] = FsHeights{sectors[i].floor_h, sectors[i].ceil_h};
     fs_anims.resize(anim.size());
     for (size_t i = 0; i < anim.size(); i++) {
         fs_anims[i].n = anim[i].n;

@@ -150,6 +150,7 @@ struct Scene {
     std::vector<FsSeg> fs_segs;                     // one per seg
     std::vector<uint16_t> fs_seg_leaf;              // subsector of every seg
     std::vector<FsSector> fs_sectors;
+    std::vector<FsHeights> fs_heights;               // the sectors' heights as loaded, compact: what a view's height row starts as (sector_rows_core.h)
     std::vector<FsAnim> fs_anims;
     std::vector<FsBitmap> fs_bitmaps;
     std::vector<FsMobj> fs_mobjs;

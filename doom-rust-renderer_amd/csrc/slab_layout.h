@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "fs_frame.h"
+#include "sector_rows_core.h"
 #include "walk_core.h"
 
 namespace dg {
@@ -155,6 +156,19 @@ inline FsScratchLayout fs_scratch_layout(size_t max_batch, uint32_t n_segs) {
     L.cl_rows = c.take(max_batch * (size_t)L.cl_row_cap * 4);
     L.keep_rows = c.take(max_batch * (size_t)(L.cl_row_cap / 32) * 4);
     L.total = c.end();
+    return L;
+}
+
+// Per-slot buffers of the per-view sector heights through the seg walk (sector_rows_core.h), sized by the scene at dg_upload_scene:
+// the rows [max_batch][n_sectors] the row kernels write and the seg walk reads, in HBM only, and the de-duplicated entries — at the
+// most one per cell — as pinned staging and as their HBM copy (two allocations of `entries` bytes: one H2D copy of what a batch has).
+// cells is the capacity that follows: entries a batch can stage, and elements its rows hold.
+struct SectorRowLayout { size_t cells, rows, entries; };
+inline SectorRowLayout sector_row_layout(size_t max_batch, size_t n_sectors) {
+    SectorRowLayout L;
+    L.cells = max_batch * n_sectors;
+    L.rows = L.cells * sizeof(FsHeights);
+    L.entries = L.cells * sizeof(SectorEntry);
     return L;
 }
 

@@ -749,12 +749,53 @@ int dg_slot_mobj_poses(dg_ctx *ctx, int slot, int first, int count, dg_mobj_plac
  * to their dispatches; 0 when that submission launched neither (no poses, or not the seg walk). */
 int dg_slot_mobj_pose_timing(dg_ctx *ctx, int slot, float *ms);
 
+/* ---- per-view sector heights (reference: Sector.floor_height / .ceiling_height, src/map/sectors.rs) --------- */
+/* The reference reads every sector's floor and ceiling height again on every frame (src/renderer/segs.rs:376-402,463-484,
+ * src/renderer/map_objects.rs:115): a caller who opens a door, runs a lift or a crusher sees it move.  A dg_view_sectors says what the
+ * heights of ONE view are, on top of what the SECTORS lump loaded:
+ *   an entry overrides both heights of one sector for that view only; every sector without an entry stands as loaded;
+ *   what follows from the heights is derived again by the reference's rule: the portal tests and the upper / lower walls, the
+ *     unpegged y offsets (differences of heights), the sky hack's min, the visplane heights, and a map object's z = its sector's floor;
+ *   of two entries for one sector in one view the later wins, as in dg_view_poses;
+ *   a sector index out of range, or a height outside int16, is DG_ERR_INVALID, the frame named in the message;
+ *   ceiling < floor is legal: the reference renders it;
+ *   dg_view.floor_height stays the caller's; dg_walk's floors stay the loaded ones;
+ *   dg_view_state entries, poses (a moved object stands on its new sector's floor as THIS view has it) and the three effects compose
+ *     unchanged.
+ * The 2-D map submissions draw no heights and take none.  Every front end gives the same pixels; with DG_FE_DEVICE_SEGS (and DG_FE_AUTO
+ * when it picks the seg walk) the host ships only the entries, 12 bytes each, and two kernels in front of the seg walk write the
+ * batch's rows [frame][sector] of 4 bytes, which a row-reading variant of the seg-walk kernels then takes the heights from (device
+ * memory per slot: max_batch x sectors x 4 B of rows and 12 B of entry staging, taken at dg_upload_scene; when that allocation fails,
+ * batches with sector entries take the host walker — same pixels, counted by dg_ctx_fallbacks).  A batch without sector entries
+ * launches exactly the kernels it launched before. */
+typedef struct dg_sector_heights { int32_t sector; int32_t floor_height; int32_t ceiling_height; } dg_sector_heights;
+typedef struct dg_view_sectors   { const dg_sector_heights *heights; uint32_t n; } dg_view_sectors;
+/* dg_submit_views_poses / dg_render_views_poses with sectors[i] for views[i].  states and poses may be NULL; sectors == NULL behaves
+ * exactly as those two calls.  DG_ERR_INVALID also for an entry array that is NULL with n > 0. */
+int dg_submit_views_sectors(dg_ctx *ctx, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, int n);
+int dg_render_views_sectors(dg_ctx *ctx, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, int n, uint8_t *rgb24_out);
+/* dg_submit_bundle_views_poses with sector heights (NULL: exactly that call).  A bundle of one part is the depth or the label submission. */
+int dg_submit_bundle_views_sectors(dg_ctx *ctx, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, int n, uint32_t what);
+/* dg_build_lists_poses for a view with sector heights (poses, sectors and owners may each be NULL).  Feeds dg_draw_lists and the
+ * dg_*_lists_host functions; host only. */
+int dg_build_lists_sectors(const dg_scene *s, int width, int height, const dg_view *view, const dg_view_poses *poses, const dg_view_sectors *sectors, dg_frame_lists *out, const uint32_t **owners);
+/* Every sector's floor and ceiling height as loaded.  n must equal dg_scene_sector_count. */
+int dg_scene_sector_heights(const dg_scene *s, int16_t *floor, int16_t *ceiling, int n);
+/* The heights the frames [first, first + count) of the slot's last submission were drawn with: out[count][dg_scene_sector_count][2]
+ * (floor, ceiling), read from wherever that submission's front end keeps them — after a seg-walk batch with sector entries the rows
+ * its two kernels wrote in device memory, otherwise the rows the host walker derives from the kept entries.  Waits and fails like
+ * dg_slot_mobj_poses. */
+int dg_slot_sector_heights(dg_ctx *ctx, int slot, int first, int count, int16_t *out);
+/* GPU time of the row kernels (dg_sector_row_fill, dg_sector_row_scatter) of the slot's last submission, from the events attached to
+ * their dispatches; 0 when that submission launched neither (no sector entries, or not the seg walk). */
+int dg_slot_sector_height_timing(dg_ctx *ctx, int slot, float *ms);
+
 /* ---- misc ----------------------------------------------------------------------------------------------------- */
 const char *dg_last_error(void); /* thread-local message of the last failing call */
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's

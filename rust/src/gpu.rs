@@ -98,7 +98,7 @@ extern "C" {
 }
 
 /// Drop-in for `Renderer`: same life cycle as src/renderer/mod.rs:37-58,118-136 (built per frame, borrows Pixels).
-pub struct GpuRenderer<'a> { ctx: *mut dg_ctx, pixels: &'a mut super::Pixels, view: dg_view, poses: Vec<dg_mobj_pose> }
+pub struct GpuRenderer<'a> { ctx: *mut dg_ctx, pixels: &'a mut super::Pixels, view: dg_view, poses: Vec<dg_mobj_pose>, sectors: Vec<dg_sector_heights> }
 
 impl<'a> GpuRenderer<'a> {
     pub fn new(ctx: *mut dg_ctx, pixels: &'a mut super::Pixels, player: &crate::game::Player, timestamp: f32) -> Self {
@@ -106,13 +106,16 @@ impl<'a> GpuRenderer<'a> {
         GpuRenderer { ctx, pixels, view: dg_view {
             x: player.position.x, y: player.position.y, angle: a, floor_height: player.floor_height,
             cos_a: a.cos(), sin_a: a.sin(), cos_na: (-a).cos(), sin_na: (-a).sin(),   // what Vertex::rotate computes (vertexes.rs:20-25)
-            timestamp, trig_valid: 1 }, poses: Vec::new() }
+            timestamp, trig_valid: 1 }, poses: Vec::new(), sectors: Vec::new() }
     }
     /// Where this tick's map objects are (what `sync_state` returned): without it every object stands where the THINGS lump put it.
     pub fn with_poses(mut self, poses: Vec<dg_mobj_pose>) -> Self { self.poses = poses; self }
+    /// This tick's sector heights (what `sector_heights` returned): without it every floor and ceiling stands as the SECTORS lump loaded it.
+    pub fn with_sectors(mut self, sectors: Vec<dg_sector_heights>) -> Self { self.sectors = sectors; self }
     pub fn render(&mut self) {
         let vp = dg_view_poses { poses: self.poses.as_ptr(), n: self.poses.len() as u32 };
-        let rc = unsafe { dg_render_views_poses(self.ctx, &self.view, std::ptr::null(), &vp, 1, self.pixels.pixels.as_mut_ptr()) };
+        let vs = dg_view_sectors { heights: self.sectors.as_ptr(), n: self.sectors.len() as u32 };
+        let rc = unsafe { dg_render_views_sectors(self.ctx, &self.view, std::ptr::null(), &vp, &vs, 1, self.pixels.pixels.as_mut_ptr()) };
         if rc != 0 { panic!("doomgpu: {}", unsafe { CStr::from_ptr(dg_last_error()) }.to_string_lossy()); }  // the reference panics too
     }
     /// The `viewing_map` branch of Game::render (src/game.rs:491-499): black, draw_map_linedefs, draw_map_player — into the same
@@ -210,6 +213,25 @@ extern "C" {
     pub fn dg_render_views_poses(ctx: *mut dg_ctx, views: *const dg_view, states: *const dg_view_state, poses: *const dg_view_poses, n: c_int, rgb24_out: *mut u8) -> c_int;
     pub fn dg_submit_views_poses(ctx: *mut dg_ctx, slot: c_int, views: *const dg_view, states: *const dg_view_state, poses: *const dg_view_poses, n: c_int) -> c_int;
     pub fn dg_slot_mobj_poses(ctx: *mut dg_ctx, slot: c_int, first: c_int, count: c_int, out: *mut dg_mobj_placed) -> c_int;
+}
+
+// ---- per-view sector heights (include/doomgpu.h dg_view_sectors): Sector.floor_height / .ceiling_height of ONE view ----
+#[repr(C)] #[derive(Clone, Copy)] pub struct dg_sector_heights { pub sector: i32, pub floor_height: i32, pub ceiling_height: i32 }
+#[repr(C)] #[derive(Clone, Copy)] pub struct dg_view_sectors { pub heights: *const dg_sector_heights, pub n: u32 }
+extern "C" {
+    pub fn dg_render_views_sectors(ctx: *mut dg_ctx, views: *const dg_view, states: *const dg_view_state, poses: *const dg_view_poses, sectors: *const dg_view_sectors, n: c_int, rgb24_out: *mut u8) -> c_int;
+    pub fn dg_submit_views_sectors(ctx: *mut dg_ctx, slot: c_int, views: *const dg_view, states: *const dg_view_state, poses: *const dg_view_poses, sectors: *const dg_view_sectors, n: c_int) -> c_int;
+    pub fn dg_scene_sector_heights(scene: *const dg_scene, floor: *mut i16, ceiling: *mut i16, n: c_int) -> c_int;
+    pub fn dg_slot_sector_heights(ctx: *mut dg_ctx, slot: c_int, first: c_int, count: c_int, out: *mut i16) -> c_int;
+}
+/// `Game::render`, next to `sync_state`: every sector's current heights as the view's entries — doors, lifts and
+/// crushers move `Sector.floor_height` / `.ceiling_height`, which process_seg reads on every frame (src/renderer/segs.rs:376-402).
+/// An entry equal to the loaded heights changes nothing, so all sectors may be sent; the heights are i16 in the reference.
+pub fn sector_heights(map: &crate::map::Map) -> Vec<dg_sector_heights> {
+    map.sectors.iter().enumerate().map(|(i, sector)| {
+        let s = sector.borrow();
+        dg_sector_heights { sector: i as i32, floor_height: s.floor_height as i32, ceiling_height: s.ceiling_height as i32 }
+    }).collect()
 }
 
 // ---- per-view game state (include/doomgpu.h dg_view_state): what the thinkers changed before a frame ------------------
