@@ -40,6 +40,8 @@ DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
 DG_MOBJ_KILL, DG_MOBJ_EXPLODE, DG_MOBJ_RESPAWN = 1, 2, 3   # dg_scene_mobj_event
 DG_REDUCE_RGB24, DG_REDUCE_GRAY8 = 0, 1  # dg_reduce_desc.format
 DG_PLANE_POINT, DG_PLANE_NEAREST = 0, 1  # dg_plane_reduce_desc.rule
+DG_OBS_RGB, DG_OBS_GRAY, DG_OBS_DISTANCE = 0, 1, 2  # dg_obs_desc.source
+DG_OBS_U8, DG_OBS_F16, DG_OBS_BF16, DG_OBS_F32 = 0, 1, 2, 3  # dg_obs_desc.dtype
 DG_KEY_LEFT, DG_KEY_RIGHT, DG_KEY_UP, DG_KEY_DOWN, DG_KEY_ALT, DG_KEY_SHIFT = 1, 2, 4, 8, 16, 32   # dg_walk_desc.keys
 
 
@@ -111,6 +113,11 @@ class DgReduceDesc(ctypes.Structure):
 
 class DgPlaneReduceDesc(ctypes.Structure):
     _fields_ = [("fx", ctypes.c_uint32), ("fy", ctypes.c_uint32), ("rule", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class DgObsDesc(ctypes.Structure):
+    _fields_ = [("fx", ctypes.c_uint32), ("fy", ctypes.c_uint32), ("source", ctypes.c_uint32), ("rule", ctypes.c_uint32), ("dtype", ctypes.c_uint32),
+                ("lo", ctypes.c_int32), ("hi", ctypes.c_int32), ("scale", ctypes.c_float), ("bias", ctypes.c_float), ("reserved", ctypes.c_uint32)]
 
 
 class DgBundleOffsets(ctypes.Structure):
@@ -270,6 +277,10 @@ _SIGNATURES = {
     "dg_reduce_planes_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 8),
     "dg_reduce_planes_device": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 8),
     "dg_ctx_plane_reduce_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    "dg_observed_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgObsDesc)] + [ctypes.POINTER(ctypes.c_int)] * 4),
+    "dg_observe_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgObsDesc), _P, ctypes.POINTER(ctypes.c_int64)]),
+    "dg_observe_device": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgObsDesc), _P, ctypes.POINTER(ctypes.c_int64)]),
+    "dg_ctx_observe_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "dg_readback_planes_reduced": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 5),
     "dg_readback_planes_reduced_async": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 5),
     "dg_seen_words": (ctypes.c_int, [_P]),
@@ -362,6 +373,33 @@ def plane_reduced_size(width: int, height: int, desc):
     w, h = ctypes.c_int(), ctypes.c_int()
     _check(lib().dg_plane_reduced_size(width, height, ctypes.byref(_plane_reduce_desc(desc)), ctypes.byref(w), ctypes.byref(h)))
     return w.value, h.value
+
+
+# dg_obs_desc.dtype -> what observe_host returns (BF16: the bit patterns), and the name a tensor's dtype ends in (observe_into)
+OBS_NP_DTYPES = {DG_OBS_U8: np.uint8, DG_OBS_F16: np.float16, DG_OBS_BF16: np.uint16, DG_OBS_F32: np.float32}
+OBS_DTYPE_NAMES = {DG_OBS_U8: "uint8", DG_OBS_F16: "float16", DG_OBS_BF16: "bfloat16", DG_OBS_F32: "float32"}
+
+
+def observed_size(width: int, height: int, desc: DgObsDesc):
+    """dg_observed_size: (channels, oH, oW, element bytes) of the observation of a width x height source under desc."""
+    c, h, w, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _check(lib().dg_observed_size(width, height, ctypes.byref(desc), ctypes.byref(c), ctypes.byref(h), ctypes.byref(w), ctypes.byref(b)))
+    return c.value, h.value, w.value, b.value
+
+
+def observe_host(src, desc: DgObsDesc) -> np.ndarray:
+    """dg_observe_host: frames (n, H, W, 3) uint8 (DG_OBS_RGB, DG_OBS_GRAY) or distance planes (n, H, W) int16 (DG_OBS_DISTANCE) observed
+    on the CPU; returns a contiguous (n, C, oH, oW) array of uint8, float16 or float32, and for DG_OBS_BF16 uint16 bit patterns."""
+    colour = desc.source != DG_OBS_DISTANCE
+    src = np.ascontiguousarray(src, dtype=np.uint8 if colour else np.int16)
+    if src.ndim != (4 if colour else 3) or (colour and src.shape[3] != 3):
+        raise ValueError("src must be (n, H, W, 3) uint8 frames, or (n, H, W) int16 distance planes for DG_OBS_DISTANCE")
+    n, h, w = src.shape[:3]
+    c, oh, ow, _ = observed_size(w, h, desc)
+    out = np.empty((n, c, oh, ow), dtype=OBS_NP_DTYPES[desc.dtype])
+    strides = (ctypes.c_int64 * 4)(c * oh * ow, oh * ow, ow, 1)
+    _check(lib().dg_observe_host(src.ctypes.data_as(_P), w, h, n, ctypes.byref(desc), out.ctypes.data_as(_P), strides))
+    return out
 
 
 def reduce_planes_host(desc, distance=None, kind=None, id=None, cls=None) -> dict:
@@ -1064,6 +1102,28 @@ class Context:
         (names of PLANE_NAMES; synchronous; planes of a finished slot's framebuffer_ptr or tensors' data_ptr()).  Touches no slot."""
         ptr = lambda d: [_P(d[k]) if d.get(k) else None for k in PLANE_NAMES]
         _check(lib().dg_reduce_planes_device(self._h, width, height, n_frames, ctypes.byref(_plane_reduce_desc(desc)), *ptr(src), *ptr(dst)))
+
+    def observe_device(self, src_ptr: int, width: int, height: int, n_frames: int, desc: DgObsDesc, dst_ptr: int, strides):
+        """dg_observe_device: n_frames sources at device address src_ptr observed under desc into the (N, C, H, W) destination at device
+        address dst_ptr whose strides, in elements, are `strides` (synchronous; touches no slot)."""
+        _check(lib().dg_observe_device(self._h, _P(src_ptr), width, height, n_frames, ctypes.byref(desc), _P(dst_ptr), (ctypes.c_int64 * 4)(*[int(v) for v in strides])))
+
+    def observe_into(self, src_ptr: int, width: int, height: int, n_frames: int, desc: DgObsDesc, tensor):
+        """observe_device into a tensor, or a view of one, of shape (n_frames, C, oH, oW) and the descriptor's dtype: anything with
+        .shape, .stride() in elements, .data_ptr() and a dtype whose name ends in uint8 / float16 / bfloat16 / float32.  ValueError when
+        shape or dtype are not what observed_size says."""
+        c, oh, ow, _ = observed_size(width, height, desc)
+        if tuple(int(v) for v in tensor.shape) != (n_frames, c, oh, ow):
+            raise ValueError(f"observe_into: the tensor's shape {tuple(tensor.shape)} is not {(n_frames, c, oh, ow)}")
+        if str(tensor.dtype).split(".")[-1] != OBS_DTYPE_NAMES[desc.dtype]:
+            raise ValueError(f"observe_into: the tensor's dtype {tensor.dtype} is not {OBS_DTYPE_NAMES[desc.dtype]}")
+        self.observe_device(src_ptr, width, height, n_frames, desc, tensor.data_ptr(), tensor.stride())
+
+    def observe_kernel_ms(self) -> float:
+        """dg_ctx_observe_kernel_ms: GPU time of the last observe_device call's kernel."""
+        ms = ctypes.c_float()
+        _check(lib().dg_ctx_observe_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def plane_reduce_kernel_ms(self) -> float:
         """dg_ctx_plane_reduce_kernel_ms: GPU time of the last reduce_planes_device call's kernel."""

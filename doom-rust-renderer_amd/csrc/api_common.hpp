@@ -4,6 +4,7 @@
 
 #include "../../include/doomgpu.h"
 #include "binner.hpp"
+#include "observe_core.h"
 #include "plane_reduce_core.h"
 #include "scene.hpp"
 
@@ -27,6 +28,29 @@ inline int check_plane_pairs(const dg_plane_reduce_desc &desc, const void *dista
     if (!distance != !o_distance || !kind != !o_kind || !id != !o_id || !cls != !o_cls)
         return set_err(DG_ERR_INVALID, "a source plane without its destination, or a destination without its source");
     if (desc.rule == DG_PLANE_NEAREST && !distance) return set_err(DG_ERR_INVALID, "DG_PLANE_NEAREST needs the distance plane");
+    return DG_OK;
+}
+
+// What dg_observed_size, dg_observe_host and dg_observe_device check alike, in this order: the descriptor, the frame size.
+inline int check_observe(int width, int height, const dg_obs_desc *desc) {
+    if (!desc) return set_err(DG_ERR_INVALID, "null argument");
+    if (!dg::obs_desc_ok(*desc))
+        return set_err(DG_ERR_INVALID, "observation descriptor: fx and fy in 1..16, a known source, rule (0 for colour) and dtype, reserved 0, "
+                                       "lo <= hi inside int16, finite scale and bias, and for DG_OBS_U8 scale 1, bias 0, 0 <= lo, hi <= 255");
+    if (width < 1 || height < 1 || width > 16384 || height > 16384) return set_err(DG_ERR_INVALID, "width/height must be in [1, 16384]");
+    return DG_OK;
+}
+// ... and the two that write, after it: the frame count, the pointers and their alignment, the strides.
+inline int check_observe_call(const void *src, int width, int height, int n_frames, const dg_obs_desc *desc, const void *dst, const int64_t strides[4]) {
+    const int rc = check_observe(width, height, desc);
+    if (rc) return rc;
+    if (!src || !dst || !strides) return set_err(DG_ERR_INVALID, "null argument");
+    if (n_frames < 0) return set_err(DG_ERR_INVALID, "bad frame count");
+    if (desc->source == DG_OBS_DISTANCE && reinterpret_cast<uintptr_t>(src) % 2u) return set_err(DG_ERR_INVALID, "observe: a distance source must be 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(dst) % dg::obs_element_bytes(desc->dtype)) return set_err(DG_ERR_INVALID, "observe: dst must be aligned to its element size");
+    const uint32_t extent[4] = {(uint32_t)n_frames, dg::obs_channels(desc->source), dg::reduce_out_dim((uint32_t)height, desc->fy), dg::reduce_out_dim((uint32_t)width, desc->fx)};
+    if (!dg::obs_strides_ok(strides, extent))
+        return set_err(DG_ERR_INVALID, "observe: every stride >= 1 and, sorted, each >= the one before times its extent (no two elements share an address)");
     return DG_OK;
 }
 

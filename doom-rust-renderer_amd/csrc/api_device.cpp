@@ -1,7 +1,7 @@
 // api_device.cpp — the entry points of the C-ABI (include/doomgpu.h) that take a dg_ctx and are no part of a slot's lifecycle: each
 // runs on a stream of the ctx's own, created by its first use, and returns when its work is done.  The box downscale of frames in device
-// memory (dg_reduce_device), the reduced depth and label planes (dg_reduce_planes_device), the linedefs seen in label planes
-// (dg_seen_lines_device, dg_slot_seen_lines — the one call here that reads a slot, once its submission is final), the floor heights of
+// memory (dg_reduce_device), the reduced depth and label planes (dg_reduce_planes_device), the observation tensors
+// (dg_observe_device), the linedefs seen in label planes (dg_seen_lines_device, dg_slot_seen_lines — the one call here that reads a slot, once its submission is final), the floor heights of
 // recorded walks (dg_ctx_locate_walks), and the getters of their kernels' times.  The readbacks of a slot's frames and planes:
 // api_readback.cpp.  Slot, dg_ctx and the slot helpers: context.hpp.
 #include <hip/hip_runtime_api.h>
@@ -13,6 +13,7 @@
 
 #include "context.hpp"
 #include "explored_kernels.hpp"
+#include "observe_kernels.hpp"
 #include "plane_reduce_kernels.hpp"
 #include "reduce_kernels.hpp"
 #include "walk.hpp"
@@ -84,6 +85,29 @@ int dg_ctx_plane_reduce_kernel_ms(dg_ctx *c, float *ms) {
     if (!c->plane_reduce.measured) return set_err(DG_ERR_INVALID, "no dg_reduce_planes_device call has launched yet");
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(c->plane_reduce.elapsed(ms));
+    return DG_OK;
+}
+
+int dg_observe_device(dg_ctx *c, const void *src, int width, int height, int n_frames, const dg_obs_desc *desc, void *dst, const int64_t strides[4]) {
+    if (!c) return set_err(DG_ERR_INVALID, "null argument");
+    int rc = check_observe_call(src, width, height, n_frames, desc, dst, strides);
+    if (rc) return rc;
+    if (n_frames == 0) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(side_stream(c->xstream));
+    HIP_TRY(c->observe.begin());
+    const hipStream_t xs = c->xstream.get();
+    const hipError_t e = launch_observe(src, width, height, n_frames, *desc, dst, strides, xs, c->observe.t0.get(), c->observe.t1.get());
+    if ((rc = finish(xs, e, "dg_observe_device"))) return rc;
+    c->observe.end();
+    return DG_OK;
+}
+
+int dg_ctx_observe_kernel_ms(dg_ctx *c, float *ms) {
+    if (!c || !ms) return set_err(DG_ERR_INVALID, "null argument");
+    if (!c->observe.measured) return set_err(DG_ERR_INVALID, "no dg_observe_device call has launched yet");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(c->observe.elapsed(ms));
     return DG_OK;
 }
 

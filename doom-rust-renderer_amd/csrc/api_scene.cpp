@@ -1,7 +1,7 @@
 // api_scene.cpp — the entry points of the C-ABI (include/doomgpu.h) that need no GPU: the error string and the version, the scene
 // (dg_scene_*), one frame's lists and map lines on the host, the recorded walks, the box downscale on the host (dg_reduced_size,
-// dg_reduce_host) and the reduced depth and label planes (dg_plane_reduced_size, dg_reduce_planes_host), the depth planes, the label
-// planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host, dg_label_lists_host,
+// dg_reduce_host), the reduced depth and label planes (dg_plane_reduced_size, dg_reduce_planes_host), the observation tensors
+// (dg_observed_size, dg_observe_host), the depth planes, the label planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host, dg_label_lists_host,
 // dg_bundle_lists_host: one rule, plane_lists_host), a bundle's slab layout (dg_bundle_layout), and the explored-map frames' host rules
 // (dg_seen_words, dg_seen_lines_host, dg_seen_accumulate_host, dg_explored_map_host) and the player-centred map frames' (dg_ego_map_lines,
 // dg_ego_map_host).  Everything that takes a dg_ctx: context.cpp (a slot's submissions), api_readback.cpp (what reads a slot) and
@@ -16,6 +16,7 @@
 #include "ego_host.hpp"
 #include "explored_cover.hpp"
 #include "frontend.hpp"
+#include "observe_core.h"
 #include "plane_core.h"
 #include "plane_reduce_core.h"
 #include "reduce_core.h"
@@ -410,6 +411,45 @@ int dg_reduce_planes_host(int width, int height, int n_frames, const dg_plane_re
                 if (o_cls) o_cls[o] = cls[s];
             }
         }
+    }
+    return DG_OK;
+}
+
+int dg_observed_size(int width, int height, const dg_obs_desc *desc, int *channels, int *out_h, int *out_w, int *element_bytes) {
+    const int rc = check_observe(width, height, desc);
+    if (rc) return rc;
+    if (channels) *channels = (int)obs_channels(desc->source);
+    if (out_h) *out_h = (int)reduce_out_dim((uint32_t)height, desc->fy);
+    if (out_w) *out_w = (int)reduce_out_dim((uint32_t)width, desc->fx);
+    if (element_bytes) *element_bytes = (int)obs_element_bytes(desc->dtype);
+    return DG_OK;
+}
+
+// The integer values are dg_reduce_host's / dg_reduce_planes_host's own, frame by frame; what is added is observe_core.h's.
+int dg_observe_host(const void *src, int width, int height, int n_frames, const dg_obs_desc *desc, void *dst, const int64_t strides[4]) {
+    int rc = check_observe_call(src, width, height, n_frames, desc, dst, strides);
+    if (rc) return rc;
+    const uint32_t C = obs_channels(desc->source), oW = reduce_out_dim((uint32_t)width, desc->fx), oH = reduce_out_dim((uint32_t)height, desc->fy);
+    const size_t px = (size_t)width * (size_t)height, opx = (size_t)oW * oH;
+    std::vector<uint8_t> bytes;
+    std::vector<int16_t> dist;
+    const dg_reduce_desc rd{desc->fx, desc->fy, desc->source == DG_OBS_GRAY ? (uint32_t)DG_REDUCE_GRAY8 : (uint32_t)DG_REDUCE_RGB24, 0u};
+    const dg_plane_reduce_desc pd{desc->fx, desc->fy, desc->rule, 0u};
+    if (desc->source == DG_OBS_DISTANCE) dist.resize(opx);
+    else bytes.resize(opx * C);
+    for (int f = 0; f < n_frames; f++) {
+        if (desc->source == DG_OBS_DISTANCE)
+            rc = dg_reduce_planes_host(width, height, 1, &pd, static_cast<const int16_t *>(src) + (size_t)f * px, nullptr, nullptr, nullptr, dist.data(), nullptr, nullptr, nullptr);
+        else
+            rc = dg_reduce_host(static_cast<const uint8_t *>(src) + (size_t)f * px * 3u, width, height, 1, &rd, bytes.data());
+        if (rc) return rc;
+        for (uint32_t oy = 0; oy < oH; oy++)
+            for (uint32_t ox = 0; ox < oW; ox++)
+                for (uint32_t c = 0; c < C; c++) {
+                    const size_t i = (size_t)oy * oW + ox;
+                    const int32_t v = desc->source == DG_OBS_DISTANCE ? (int32_t)dist[i] : (int32_t)bytes[i * C + c];
+                    obs_put(*desc, dst, (int64_t)f * strides[0] + (int64_t)c * strides[1] + (int64_t)oy * strides[2] + (int64_t)ox * strides[3], v);
+                }
     }
     return DG_OK;
 }

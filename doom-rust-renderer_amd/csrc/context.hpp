@@ -343,6 +343,7 @@ struct dg_ctx {
     Stream xstream;
     TimedInterval reduce;
     TimedInterval plane_reduce;         // dg_reduce_planes_device: the same stream, events of its own
+    TimedInterval observe;              // dg_observe_device: likewise
     TimedInterval seen, seen_acc;       // dg_seen_lines_device / dg_slot_seen_lines: the events of the last call's kernels, on xstream
 
     // The members' owners free the memory, the streams and the events: with the ctx's device current, and only after every stream that

@@ -3,7 +3,7 @@
 //
 // dg_plane_nearest (DG_PLANE_NEAREST) is a streaming arg-min over the distance plane and a gather from the others.  One workgroup = one
 // band of fy source rows of one frame x a run of whole output pixels (plane_reduce_px_per_wg), the shape of dg_reduce:
-//   1. every lane keeps, per source column it reads, the minimum over the band's rows of plane_col_key (distance, row) in registers and
+//   1. (reduce_band.h) every lane keeps, per source column it reads, the minimum over the band's rows of plane_col_key (distance, row) in registers and
 //      puts it in LDS; dg_plane_nearest<true>: one 16-byte piece of 8 distances per lane and row, the pieces of a row consecutive and
 //      16-byte aligned (2 W % 16 == 0, aligned base), so the run starts up to 7 columns in front of its first pixel;
 //      dg_plane_nearest<false> (any width, any 2-byte aligned base): the lanes of a wave read 64 consecutive distances per load, 8 loads
@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "plane_reduce_kernels.hpp"
+#include "reduce_band.h"
 
 namespace dg {
 
@@ -51,51 +52,8 @@ __global__ __launch_bounds__(PLANE_REDUCE_LANES) void dg_plane_nearest(PlaneRedu
     const uint32_t np = min(P.px_per_wg, P.oW - ox0);                          // output pixels of this run
     const uint32_t c0 = P.fx * ox0;                                            // its source columns: [c0, c1)
     const uint32_t c1 = min(P.W, c0 + P.fx * np);
-    const uint32_t a = PIECES ? c0 & ~7u : c0;
-    const uint32_t off0 = c0 - a;                                              // cols[off0] is column c0
-    const uint32_t pos = a + 8u * tid;                                         // PIECES: pos + 8 <= W, both are multiples of 8
     const int16_t *const rows = P.src.distance + (size_t)f * P.src_px + (size_t)y0 * P.W;
-    uint32_t k[8];
-#pragma unroll
-    for (uint32_t i = 0; i < 8u; i++) k[i] = PLANE_KEY_NONE;
-    if (PIECES) {
-        if (pos < c1) {
-            for (uint32_t r = 0; r < ny; r += 4u) {
-                uint4 v[4];
-#pragma unroll
-                for (uint32_t i = 0; i < 4u; i++) {
-                    v[i] = make_uint4(0u, 0u, 0u, 0u);
-                    if (r + i < ny) v[i] = *reinterpret_cast<const uint4 *>(rows + (size_t)(r + i) * P.W + pos);
-                }
-#pragma unroll
-                for (uint32_t i = 0; i < 4u; i++) {
-                    if (r + i < ny) {
-                        const uint32_t ry = r + i;
-                        k[0] = min(k[0], plane_col_key(v[i].x, ry)); k[1] = min(k[1], plane_col_key(v[i].x >> 16, ry));
-                        k[2] = min(k[2], plane_col_key(v[i].y, ry)); k[3] = min(k[3], plane_col_key(v[i].y >> 16, ry));
-                        k[4] = min(k[4], plane_col_key(v[i].z, ry)); k[5] = min(k[5], plane_col_key(v[i].z >> 16, ry));
-                        k[6] = min(k[6], plane_col_key(v[i].w, ry)); k[7] = min(k[7], plane_col_key(v[i].w >> 16, ry));
-                    }
-                }
-            }
-            uint4 *const o = reinterpret_cast<uint4 *>(cols + 8u * tid);
-            o[0] = make_uint4(k[0], k[1], k[2], k[3]);
-            o[1] = make_uint4(k[4], k[5], k[6], k[7]);
-        }
-    } else {
-        const uint16_t *const urows = reinterpret_cast<const uint16_t *>(rows);
-        for (uint32_t r = 0; r < ny; r++) {
-            const uint16_t *const row = urows + (size_t)r * P.W;
-#pragma unroll
-            for (uint32_t i = 0; i < 8u; i++) {
-                const uint32_t col = c0 + tid + PLANE_REDUCE_LANES * i;
-                if (col < c1) k[i] = min(k[i], plane_col_key(row[col], r));
-            }
-        }
-#pragma unroll
-        for (uint32_t i = 0; i < 8u; i++)
-            if (c0 + tid + PLANE_REDUCE_LANES * i < c1) cols[tid + PLANE_REDUCE_LANES * i] = k[i];
-    }
+    const uint32_t off0 = plane_band_keys<PIECES>(cols, rows, P.W, ny, c0, c1, tid);
     __syncthreads();
     for (uint32_t p = tid; p < np; p += PLANE_REDUCE_LANES) {
         uint32_t x0;

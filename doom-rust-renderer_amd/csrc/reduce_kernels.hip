@@ -2,7 +2,7 @@
 // its own beside the render path.  It reads 3*W*H bytes per frame once and writes fx*fy times fewer (3x fewer again as gray).
 //
 // One workgroup = one band of fy source rows of one frame x a run of whole output pixels (reduce_px_per_wg).
-//   1. every lane adds its bytes of the band's rows in registers, as 16-bit sums per byte position (<= 16 x 255), and puts them in LDS;
+//   1. (reduce_band.h) every lane adds its bytes of the band's rows in registers, as 16-bit sums per byte position (<= 16 x 255), and puts them in LDS;
 //      dg_reduce<true>: one 16-byte piece per lane and row, the pieces of a row consecutive and 16-byte aligned (3 W % 16 == 0, aligned
 //      base), so the run starts up to 15 bytes in front of its first pixel; dg_reduce<false> (any width, any base): the lanes of a wave
 //      read 64 consecutive bytes per load, 16 loads per row;
@@ -15,6 +15,7 @@
 
 #include <algorithm>
 
+#include "reduce_band.h"
 #include "reduce_kernels.hpp"
 
 namespace dg {
@@ -43,55 +44,7 @@ __global__ __launch_bounds__(REDUCE_LANES) void dg_reduce(ReduceParams P) {
     const uint32_t b0 = 3u * P.fx * ox0;                                       // its source bytes within a row: [b0, b1)
     const uint32_t b1 = min(P.row_bytes, b0 + 3u * P.fx * np);
     const uint8_t *const rows = P.src + (size_t)blockIdx.z * P.src_frame + (size_t)y0 * P.row_bytes;
-    uint32_t off0 = 0;                                                         // sums[off0] is byte b0
-    if (PIECES) {
-        const uint32_t a = b0 & ~15u;
-        off0 = b0 - a;
-        const uint32_t pos = a + 16u * tid;                                    // pos + 16 <= row_bytes: both are multiples of 16
-        if (pos < b1) {
-            // bytes 0 and 2 of each dword in ev, 1 and 3 in od: two 16-bit sums per register
-            uint32_t ev[4] = {0u, 0u, 0u, 0u}, od[4] = {0u, 0u, 0u, 0u};
-            for (uint32_t r = 0; r < ny; r += 4u) {
-                uint4 v[4];
-#pragma unroll
-                for (uint32_t i = 0; i < 4u; i++) {
-                    v[i] = make_uint4(0u, 0u, 0u, 0u);
-                    if (r + i < ny) v[i] = *reinterpret_cast<const uint4 *>(rows + (size_t)(r + i) * P.row_bytes + pos);
-                }
-#pragma unroll
-                for (uint32_t i = 0; i < 4u; i++) {
-                    ev[0] += v[i].x & 0x00FF00FFu; od[0] += (v[i].x >> 8) & 0x00FF00FFu;
-                    ev[1] += v[i].y & 0x00FF00FFu; od[1] += (v[i].y >> 8) & 0x00FF00FFu;
-                    ev[2] += v[i].z & 0x00FF00FFu; od[2] += (v[i].z >> 8) & 0x00FF00FFu;
-                    ev[3] += v[i].w & 0x00FF00FFu; od[3] += (v[i].w >> 8) & 0x00FF00FFu;
-                }
-            }
-            uint32_t w[8];
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; k++) {
-                w[2 * k] = (ev[k] & 0xFFFFu) | (od[k] << 16);
-                w[2 * k + 1] = (ev[k] >> 16) | (od[k] & 0xFFFF0000u);
-            }
-            uint4 *const o = reinterpret_cast<uint4 *>(sums + 16u * tid);
-            o[0] = make_uint4(w[0], w[1], w[2], w[3]);
-            o[1] = make_uint4(w[4], w[5], w[6], w[7]);
-        }
-    } else {
-        uint32_t acc[16];
-#pragma unroll
-        for (uint32_t i = 0; i < 16u; i++) acc[i] = 0u;
-        for (uint32_t r = 0; r < ny; r++) {
-            const uint8_t *const row = rows + (size_t)r * P.row_bytes;
-#pragma unroll
-            for (uint32_t i = 0; i < 16u; i++) {
-                const uint32_t pos = b0 + tid + REDUCE_LANES * i;
-                if (pos < b1) acc[i] += row[pos];
-            }
-        }
-#pragma unroll
-        for (uint32_t i = 0; i < 16u; i++)
-            if (b0 + tid + REDUCE_LANES * i < b1) sums[tid + REDUCE_LANES * i] = (uint16_t)acc[i];
-    }
+    const uint32_t off0 = reduce_band_sums<PIECES>(sums, rows, P.row_bytes, ny, b0, b1, tid);
     __syncthreads();
     const uint32_t rcp_full = P.rcp[ny < P.fy ? 2 : 0], rcp_short = P.rcp[ny < P.fy ? 3 : 1];
     uint8_t *const out = P.dst + (size_t)blockIdx.z * P.dst_frame + ((size_t)oy * P.oW + ox0) * (P.gray ? 1u : 3u);

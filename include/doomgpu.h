@@ -529,6 +529,55 @@ int dg_readback_planes_reduced(dg_ctx *ctx, int slot, int first, int count, cons
 int dg_readback_planes_reduced_async(dg_ctx *ctx, int slot, int first, int count, const dg_plane_reduce_desc *desc,
                                      int16_t *distance, uint8_t *kind, uint16_t *id, uint8_t *cls, dg_label_box *boxes);
 
+/* ---- observation tensors ------------------------------------------------------------------------------------------------------------ */
+/* The link between the frames and planes the library leaves in device memory and a network on the same GPU: the box downscale of
+ * dg_reduce_desc or the representative distance of dg_plane_reduce_desc, a clamp, an affine map and a narrowing, written as uint8,
+ * float16, bfloat16 or float32 into a strided (N, C, H, W) destination in ONE pass: contiguous NCHW, channels-last, padded rows, a channel
+ * slice of a wider tensor (channel 3 of an RGB-D tensor), a frame stride larger than one observation (slot t mod k of a frame stack).
+ * Per output element (frame n, channel c, row oy, column ox), in this order:
+ *   1. the integer value v.  DG_OBS_RGB: the byte dg_reduce_host gives for that pixel and channel under (fx, fy, DG_REDUCE_RGB24);
+ *      DG_OBS_GRAY: the byte it gives under DG_REDUCE_GRAY8; DG_OBS_DISTANCE: the distance dg_reduce_planes_host gives under
+ *      (fx, fy, rule), as the signed int16 it is.  Those functions define v.
+ *   2. the clamp: v = min(max(v, lo), hi).
+ *   3. the conversion.  DG_OBS_U8: the element is v (needs scale == 1.0f, bias == 0.0f, 0 <= lo, hi <= 255).  Otherwise
+ *      o = fl32(fl32((float)v * scale) + bias): two IEEE-754 binary32 roundings, never a fused multiply-add; subnormals are kept, overflow
+ *      goes to infinity, the sign of zero follows IEEE (0 * -1 + 0 = +0).  DG_OBS_F32 stores o; DG_OBS_F16 stores o rounded to binary16,
+ *      round-to-nearest-even, subnormals kept, overflow to infinity; DG_OBS_BF16 stores o rounded to bfloat16, round-to-nearest-even.
+ *      With finite scale and bias no NaN can arise.
+ *   4. the store: to dst + (n*strides[0] + c*strides[1] + oy*strides[2] + ox*strides[3]) * element_bytes.  Strides are in ELEMENTS: what a
+ *      tensor's .stride() says for its (N, C, H, W) view.
+ * Strides: every stride is >= 1; over the dimensions whose extent (n_frames, channels, out_h, out_w) is greater than 1, sorted by stride,
+ * each stride must be >= the previous stride times the previous extent (and the largest stride times its extent < 2^62): no two
+ * elements share an address.  Only the addressed elements are written; gaps are left as they were.
+ * DG_ERR_INVALID: a NULL argument, a factor outside 1..16, an unknown source, rule or dtype, a rule other than 0 for a colour source,
+ * reserved != 0, lo > hi or a clamp bound outside int16, a non-finite scale or bias, the DG_OBS_U8 conditions not met, width or height
+ * outside [1, 16384], n_frames < 0, strides the rule refuses, a DG_OBS_DISTANCE source that is not 2-byte aligned, a dst not aligned to
+ * its element size.  n_frames == 0 does nothing.  The source may otherwise sit at any alignment, as for dg_reduce_device.
+ * Out of scope: kind, id and cls planes (categorical: dg_reduce_planes_device serves them), an asynchronous form on a caller's stream,
+ * a readback form, frame stacking inside a batch (a view over the frame axis costs nothing). */
+enum { DG_OBS_RGB = 0, DG_OBS_GRAY = 1, DG_OBS_DISTANCE = 2 };       /* source: 3, 1, 1 channels */
+enum { DG_OBS_U8 = 0, DG_OBS_F16 = 1, DG_OBS_BF16 = 2, DG_OBS_F32 = 3 };
+typedef struct dg_obs_desc {
+    uint32_t fx, fy;      /* box, each 1..16: the geometry of dg_reduce_desc */
+    uint32_t source;      /* DG_OBS_RGB / DG_OBS_GRAY: src is RGB24 frames; DG_OBS_DISTANCE: src is int16 distance planes */
+    uint32_t rule;        /* DG_OBS_DISTANCE: DG_PLANE_POINT or DG_PLANE_NEAREST; otherwise must be 0 */
+    uint32_t dtype;       /* DG_OBS_* */
+    int32_t  lo, hi;      /* clamp of the integer value, lo <= hi, both in [-32768, 32767] */
+    float    scale, bias; /* finite */
+    uint32_t reserved;    /* must be 0 */
+} dg_obs_desc;
+/* Shape of the observation of a width x height source under desc (each pointer may be NULL).  Pure: no ctx, no GPU. */
+int dg_observed_size(int width, int height, const dg_obs_desc *desc, int *channels, int *out_h, int *out_w, int *element_bytes);
+/* The rule on the CPU: n_frames sources at src (host memory) into dst.  Needs no ctx and no GPU, and is what the GPU path is tested
+ * against, bit for bit. */
+int dg_observe_host(const void *src, int width, int height, int n_frames, const dg_obs_desc *desc, void *dst, const int64_t strides[4]);
+/* Device to device, synchronous, on the ctx's stream that belongs to no slot (dg_reduce_device's); touches no slot.  Sources:
+ * dg_slot_framebuffer of a finished slot (the distance plane at dg_bundle_layout(...).distance) or any device buffer. */
+int dg_observe_device(dg_ctx *ctx, const void *src_device, int width, int height, int n_frames, const dg_obs_desc *desc, void *dst_device, const int64_t strides[4]);
+/* GPU time of the last dg_observe_device call's kernel in milliseconds, from events attached to the dispatch itself.
+ * DG_ERR_INVALID: a NULL argument, no dg_observe_device call that launched yet. */
+int dg_ctx_observe_kernel_ms(dg_ctx *ctx, float *ms);
+
 /* ---- 2-D map view (reference: Game::render with viewing_map, src/game.rs:491-499, 229-309) --------------------------------- */
 /* What the window holds after render() in map mode, RGB24 like every frame: black; every linedef without DONTDRAW (flags & 128) in
  * LINEDEFS order, yellow (255, 255, 0) when TWOSIDED (flags & 4) else red (255, 0, 0); then the player arrow in yellow: P->E, R->E, L->E.
@@ -795,7 +844,7 @@ const char *dg_last_error(void); /* thread-local message of the last failing cal
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
