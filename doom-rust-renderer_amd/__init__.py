@@ -98,6 +98,22 @@ class DgViewSectors(ctypes.Structure):
     _fields_ = [("heights", ctypes.POINTER(DgSectorHeights)), ("n", ctypes.c_uint32)]
 
 
+TEX_NONE = -1   # DG_TEX_NONE: "-"
+
+
+class DgSideSurface(ctypes.Structure):
+    _fields_ = [("sidedef", ctypes.c_int32), ("tex_mid", ctypes.c_int32), ("tex_low", ctypes.c_int32), ("tex_up", ctypes.c_int32),
+                ("x_offset", ctypes.c_int32), ("y_offset", ctypes.c_int32)]
+
+
+class DgSectorFlats(ctypes.Structure):
+    _fields_ = [("sector", ctypes.c_int32), ("floor_flat", ctypes.c_int32), ("ceil_flat", ctypes.c_int32)]
+
+
+class DgViewSurfaces(ctypes.Structure):
+    _fields_ = [("sides", ctypes.POINTER(DgSideSurface)), ("n_sides", ctypes.c_uint32), ("flats", ctypes.POINTER(DgSectorFlats)), ("n_flats", ctypes.c_uint32)]
+
+
 # a row of dg_mobj_placed as numpy sees it (dg_scene_mobj_poses, dg_slot_mobj_poses)
 MOBJ_PLACED_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("angle", "<f4"), ("sector", "<i4")])
 
@@ -260,6 +276,17 @@ _SIGNATURES = {
     "dg_submit_bundle_views_sectors": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.c_int, ctypes.c_uint32]),
     "dg_slot_sector_heights": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "dg_slot_sector_height_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
+    "dg_scene_use_texture": (ctypes.c_int, [_P, ctypes.c_char_p]),
+    "dg_scene_use_flat": (ctypes.c_int, [_P, ctypes.c_char_p]),
+    "dg_scene_sidedef_count": (ctypes.c_int, [_P]),
+    "dg_scene_sidedef_surfaces": (ctypes.c_int, [_P, ctypes.POINTER(DgSideSurface), ctypes.c_int]),
+    "dg_scene_sector_flats": (ctypes.c_int, [_P, ctypes.POINTER(DgSectorFlats), ctypes.c_int]),
+    "dg_build_lists_surfaces": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.POINTER(DgViewSurfaces), ctypes.POINTER(DgFrameLists), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32))]),
+    "dg_submit_views_surfaces": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.POINTER(DgViewSurfaces), ctypes.c_int]),
+    "dg_render_views_surfaces": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.POINTER(DgViewSurfaces), ctypes.c_int, _P]),
+    "dg_submit_bundle_views_surfaces": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.POINTER(DgViewSurfaces), ctypes.c_int, ctypes.c_uint32]),
+    "dg_slot_sector_flats": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
+    "dg_slot_surface_timing": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]),
     "dg_build_lists_owners": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgFrameLists), ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32))]),
     "dg_submit_label_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int]),
     "dg_render_label_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewState), ctypes.c_int, _P, _P, _P]),
@@ -604,6 +631,20 @@ def make_view_sectors(sectors):
     return arr, keep
 
 
+def make_view_surfaces(surfaces):
+    """surfaces: one (sides, flats) pair per view — sides a list of (sidedef, tex_mid, tex_low, tex_up, x_offset, y_offset) entries
+    (dg_side_surface), flats a list of (sector, floor_flat, ceil_flat) entries (dg_sector_flats).
+    Returns (ctypes array of dg_view_surfaces, keep-alive list)."""
+    arr = (DgViewSurfaces * max(1, len(surfaces)))()
+    keep = []
+    for i, (sides, flats) in enumerate(surfaces):
+        sa = (DgSideSurface * max(1, len(sides)))(*[DgSideSurface(*[int(v) for v in e]) for e in sides])
+        fa = (DgSectorFlats * max(1, len(flats)))(*[DgSectorFlats(*[int(v) for v in e]) for e in flats])
+        keep += [sa, fa]
+        arr[i] = DgViewSurfaces(sa, len(sides), fa, len(flats))
+    return arr, keep
+
+
 def make_views(records, timestamp: float = 0.0):
     """camera_path records (n, 8) f32 [x, y, angle, cos, sin, cos(-a), sin(-a), floor] -> ctypes array of dg_view."""
     recs = np.asarray(records, dtype=np.float32).reshape(-1, 8)
@@ -719,6 +760,44 @@ class Scene:
         own = ctypes.POINTER(ctypes.c_uint32)()
         _check(lib().dg_build_lists_sectors(self._h, W, H, ctypes.byref(view), vp, vs, ctypes.byref(fl), ctypes.byref(own) if owners else None))
         return (fl, np.array(own[:fl.n_renders], dtype=np.uint32)) if owners else fl
+
+    def build_lists_surfaces(self, W: int, H: int, view: DgView, surfaces=None, sectors=None, poses=None, owners: bool = False):
+        """dg_build_lists_surfaces: build_lists_sectors for a view whose sidedefs and flats are what `surfaces` says
+        ((sides, flats) as make_view_surfaces takes them, or None)."""
+        fl = DgFrameLists()
+        vp, _keep = make_view_poses([poses]) if poses is not None else (None, None)
+        vs, _keep2 = make_view_sectors([sectors]) if sectors is not None else (None, None)
+        vf, _keep3 = make_view_surfaces([surfaces]) if surfaces is not None else (None, None)
+        own = ctypes.POINTER(ctypes.c_uint32)()
+        _check(lib().dg_build_lists_surfaces(self._h, W, H, ctypes.byref(view), vp, vs, vf, ctypes.byref(fl), ctypes.byref(own) if owners else None))
+        return (fl, np.array(own[:fl.n_renders], dtype=np.uint32)) if owners else fl
+
+    def use_texture(self, name: str) -> int:
+        """dg_scene_use_texture: the bitmap id of the wall texture `name` (TEX_NONE for "-"), decoded now if the map did not use it.
+        Call before Context.upload_scene."""
+        return _check(lib().dg_scene_use_texture(self._h, name.encode())) if name != "-" else TEX_NONE
+
+    def use_flat(self, name: str) -> int:
+        """dg_scene_use_flat: a flat handle for `name`, its lump (or its whole animated list) loaded now if the map did not use it.
+        Call before Context.upload_scene."""
+        return _check(lib().dg_scene_use_flat(self._h, name.encode()))
+
+    def sidedef_count(self) -> int:
+        return _check(lib().dg_scene_sidedef_count(self._h))
+
+    def sidedef_surfaces(self) -> np.ndarray:
+        """dg_scene_sidedef_surfaces: every sidedef as loaded, an (n, 6) int32 array [sidedef, tex_mid, tex_low, tex_up, x_offset, y_offset]."""
+        n = self.sidedef_count()
+        out = np.zeros((max(n, 0), 6), dtype=np.int32)
+        _check(lib().dg_scene_sidedef_surfaces(self._h, out.ctypes.data_as(ctypes.POINTER(DgSideSurface)), n))
+        return out
+
+    def sector_flats(self) -> np.ndarray:
+        """dg_scene_sector_flats: every sector's flat handles as loaded, an (n, 3) int32 array [sector, floor_flat, ceil_flat]."""
+        n = lib().dg_scene_sector_count(self._h)
+        out = np.zeros((max(n, 0), 3), dtype=np.int32)
+        _check(lib().dg_scene_sector_flats(self._h, out.ctypes.data_as(ctypes.POINTER(DgSectorFlats)), n))
+        return out
 
     def sector_heights(self) -> np.ndarray:
         """dg_scene_sector_heights: every sector's (floor, ceiling) as loaded, an (n, 2) int16 array."""
@@ -892,6 +971,34 @@ class Context:
         """dg_slot_sector_height_timing: GPU time (ms) of the row kernels of the slot's last submission (0: none ran)."""
         t = ctypes.c_float()
         _check(lib().dg_slot_sector_height_timing(self._h, slot, ctypes.byref(t)))
+        return t.value
+
+    def submit_surfaces(self, slot: int, views, surfaces, n=None, states=None, poses=None, sectors=None):
+        """dg_submit_views_surfaces: submit_sectors() with a dg_view_surfaces per view (make_view_surfaces; None: none)."""
+        _check(lib().dg_submit_views_surfaces(self._h, slot, views, states, poses, sectors, surfaces, len(views) if n is None else n))
+
+    def render_surfaces(self, views, surfaces, states=None, poses=None, sectors=None) -> np.ndarray:
+        """dg_render_views_surfaces: synchronous, slot 0; returns (n, H, W, 3) uint8."""
+        n = len(views)
+        out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
+        _check(lib().dg_render_views_surfaces(self._h, views, states, poses, sectors, surfaces, n, out.ctypes.data_as(_P)))
+        return out
+
+    def submit_bundle_surfaces(self, slot: int, views, what: int, surfaces, n=None, states=None, poses=None, sectors=None):
+        """dg_submit_bundle_views_surfaces: submit_bundle_sectors() with a dg_view_surfaces per view."""
+        _check(lib().dg_submit_bundle_views_surfaces(self._h, slot, views, states, poses, sectors, surfaces, len(views) if n is None else n, what))
+
+    def slot_sector_flats(self, slot: int, first: int, count: int) -> np.ndarray:
+        """dg_slot_sector_flats: the (count, sectors, 2) int32 flat handles (floor, ceiling) the slot's frames were drawn with."""
+        n = lib().dg_scene_sector_count(self._scene._h) if self._scene is not None else 0
+        out = np.zeros((max(count, 0), max(n, 0), 2), dtype=np.int32)
+        _check(lib().dg_slot_sector_flats(self._h, slot, first, count, out.ctypes.data_as(_P)))
+        return out
+
+    def surface_timing(self, slot: int) -> float:
+        """dg_slot_surface_timing: GPU time (ms) of the flat row kernels of the slot's last submission (0: none ran)."""
+        t = ctypes.c_float()
+        _check(lib().dg_slot_surface_timing(self._h, slot, ctypes.byref(t)))
         return t.value
 
     def submit_map(self, slot: int, views, n=None):

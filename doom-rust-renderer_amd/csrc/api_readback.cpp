@@ -399,6 +399,46 @@ int dg_slot_sector_height_timing(dg_ctx *c, int slot, float *ms) {
     return DG_OK;
 }
 
+int dg_slot_sector_flats(dg_ctx *c, int slot, int first, int count, int32_t *out) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (s.phase == Slot::Phase::Empty || !s.from_views || !c->scene) return set_err(DG_ERR_STATE, "dg_slot_sector_flats: the slot holds no view submission");
+    if ((rc = check_range(s, first, count, out != nullptr, "bad frame range"))) return rc;
+    if (count == 0) return DG_OK;
+    if ((rc = settle(c, s, Copy::Leave))) return rc;       // (a seg-walk batch redone as a whole is a host-list batch from here on)
+    const Scene &sc = *c->scene;
+    const size_t n_sectors = sc.sectors.size();
+    if (n_sectors == 0) return DG_OK;
+    if (s.seg_walk() && s.SR.n_frames > 0) {               // the rows the row kernels wrote
+        HIP_TRY(hipMemcpyAsync(out, s.SR.rows + (size_t)first * n_sectors, (size_t)count * n_sectors * sizeof(FsFlats), hipMemcpyDeviceToHost, s.stream.get()));
+        HIP_TRY(slot_sync(s));
+        return DG_OK;
+    }
+    FrameArena &A = *c->arenas[0];                         // the host walker's rule over the kept entries
+    for (int i = 0; i < count; i++) {
+        FsFlats *row = reinterpret_cast<FsFlats *>(out) + (size_t)i * n_sectors;
+        std::memcpy(row, sc.fs_flats.data(), n_sectors * sizeof(FsFlats));
+        const dg_view_surfaces *vs = s.surfaces_of(first + i);
+        if (!vs) continue;
+        (void)resolve_view_surfaces(sc, nullptr, *vs, first + i, A.side_of, A.sides, A.flat_of, A.flats);
+        for (const FlatEntry &e : A.flats) flat_row_place(row, e.sector, e.flats);
+    }
+    return DG_OK;
+}
+
+int dg_slot_surface_timing(dg_ctx *c, int slot, float *ms) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!ms) return set_err(DG_ERR_INVALID, "null argument");
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
+    if ((rc = settle(c, s, Copy::Leave))) return rc;
+    *ms = 0.0f;
+    if (s.seg_walk() && s.SR.n_frames > 0) HIP_TRY(hipEventElapsedTime(ms, s.ev_srow0.get(), s.ev_srow.get()));
+    return DG_OK;
+}
+
 int dg_slot_framebuffer(dg_ctx *c, int slot, void **p) {
     int rc = check_slot(c, slot);
     if (rc) return rc;

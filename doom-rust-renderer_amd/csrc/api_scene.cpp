@@ -260,15 +260,56 @@ int dg_scene_sector_heights(const dg_scene *s, int16_t *floor, int16_t *ceiling,
 
 int dg_build_lists_sectors(const dg_scene *s, int width, int height, const dg_view *view, const dg_view_poses *poses, const dg_view_sectors *sectors, dg_frame_lists *out,
                            const uint32_t **owners) {
+    return dg_build_lists_surfaces(s, width, height, view, poses, sectors, nullptr, out, owners);
+}
+
+int dg_scene_use_texture(dg_scene *s, const char *name) {
+    if (!s || !name) return set_err(DG_ERR_INVALID, "null argument");
+    std::string err;
+    const int id = s->sc->use_texture(name, err);
+    return id == TEX_UNKNOWN ? set_err(DG_ERR_WAD, err) : id;
+}
+
+int dg_scene_use_flat(dg_scene *s, const char *name) {
+    if (!s || !name) return set_err(DG_ERR_INVALID, "null argument");
+    std::string err;
+    const int h = s->sc->use_flat(name, err);
+    return h < 0 ? set_err(DG_ERR_WAD, err) : h;
+}
+
+int dg_scene_sidedef_count(const dg_scene *s) { return s ? (int)s->sc->sidedefs.size() : set_err(DG_ERR_INVALID, "null scene"); }
+
+int dg_scene_sidedef_surfaces(const dg_scene *s, dg_side_surface *out, int n) {
+    if (!s || !out) return set_err(DG_ERR_INVALID, "null argument");
+    const Scene &sc = *s->sc;
+    if (n < 0 || (size_t)n != sc.sidedefs.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_sidedef_count");
+    for (size_t i = 0; i < sc.sidedefs.size(); i++) {
+        const SidedefRec &r = sc.sidedefs[i];
+        out[i] = dg_side_surface{(int32_t)i, r.middle, r.lower, r.upper, (int32_t)r.xoff, (int32_t)r.yoff};
+    }
+    return DG_OK;
+}
+
+int dg_scene_sector_flats(const dg_scene *s, dg_sector_flats *out, int n) {
+    if (!s || !out) return set_err(DG_ERR_INVALID, "null argument");
+    const Scene &sc = *s->sc;
+    if (n < 0 || (size_t)n != sc.sectors.size()) return set_err(DG_ERR_INVALID, "n must equal dg_scene_sector_count");
+    for (size_t i = 0; i < sc.sectors.size(); i++) out[i] = dg_sector_flats{(int32_t)i, sc.fs_flats[i].floor, sc.fs_flats[i].ceil};
+    return DG_OK;
+}
+
+int dg_build_lists_surfaces(const dg_scene *s, int width, int height, const dg_view *view, const dg_view_poses *poses, const dg_view_sectors *sectors,
+                            const dg_view_surfaces *surfaces, dg_frame_lists *out, const uint32_t **owners) {
     if (!s || !view || !out) return set_err(DG_ERR_INVALID, "null argument");
     if (poses && poses->n && !poses->poses) return set_err(DG_ERR_INVALID, "view poses with a null array");
     if (sectors && sectors->n && !sectors->heights) return set_err(DG_ERR_INVALID, "view sectors with a null array");
+    if (surfaces && ((surfaces->n_sides && !surfaces->sides) || (surfaces->n_flats && !surfaces->flats))) return set_err(DG_ERR_INVALID, "view surfaces with a null array");
     std::string err;
     int rc = owners ? check_label_scene(*s->sc, err) : DG_OK;
     if (rc) return set_err(rc, err);
     dg_view v = *view;
     fill_view_trig(v);
-    rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, nullptr, &s->sc->fx, poses, sectors);
+    rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, nullptr, &s->sc->fx, poses, sectors, surfaces);
     if (rc) return set_err(rc, err);
     if (owners) *owners = lists_arena().owners.data();
     return DG_OK;

@@ -79,6 +79,7 @@ int check_batch(const dg_ctx *c, int n) {
     if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
     if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
     if (c->scene->texel_idx.size() != c->uploaded_texels) return set_err(DG_ERR_INVALID, "the scene decoded new bitmaps since dg_upload_scene: upload it again");
+    if (c->scene->flat_pool.size() != c->uploaded_flats || c->scene->anim.size() != c->uploaded_anims) return set_err(DG_ERR_INVALID, "the scene loaded new flats since dg_upload_scene: upload it again");
     return DG_OK;
 }
 
@@ -145,7 +146,7 @@ void fill_walk_params(dg_ctx *c, Slot &s, int n) {
 // as well (the caller has allocated it), from given_owners[i] for the caller's lists.
 int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, int32_t fe = DG_FE_HOST,
                      const uint32_t *const *given_owners = nullptr, bool want_owners = false, const dg_view_poses *poses = nullptr,
-                     const dg_view_sectors *sectors = nullptr) {
+                     const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -165,7 +166,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
             dg_view v = views[i];
             fill_view_trig(v);
             dg_frame_lists fl;
-            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr, sectors ? &sectors[i] : nullptr);
+            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr, sectors ? &sectors[i] : nullptr, surfaces ? &surfaces[i] : nullptr);
             if (!rc[(size_t)i]) rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
             if (labels && !rc[(size_t)i]) rc[(size_t)i] = wall_owners(sc, fl, c->arenas[(size_t)wid]->owners.data(), c->label_tags[(size_t)i], errs[(size_t)i]);
         }
@@ -203,7 +204,8 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
 
 // DG_FE_DEVICE: build the per-seg / per-sprite records of n views in parallel, pack them into the slot's record slab,
 // fill slot.FP / slot.P.  Returns kPartsUnsupported when the batch has to go through build_batch_host instead.
-int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors) {
+int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors,
+                   const dg_view_surfaces *surfaces) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -215,7 +217,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         FeFrameOut &o = c->fe_out[(size_t)i];
         dg_view v = views[i];
         fill_view_trig(v);
-        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr, sectors ? &sectors[i] : nullptr);
+        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr, sectors ? &sectors[i] : nullptr, surfaces ? &surfaces[i] : nullptr);
         if (rc[(size_t)i]) return;
         o.parts.swap(A.parts); o.sprites.swap(A.sprites); o.behind.swap(A.behind); o.sky_parts.swap(A.sky_parts);
         o.bin_off.swap(A.bin_off); o.bin_parts.swap(A.bin_parts); o.sbin_off.swap(A.sbin_off); o.sbin_sprites.swap(A.sbin_sprites);
@@ -289,7 +291,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     s.keep_states(states, n);
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (n >= 64 && !states && !poses && !sectors) c->fe_auto.host_batch((double)s.host_ms, n);      // DG_FE_AUTO's measurement of the host side
+    if (n >= 64 && !states && !poses && !sectors && !surfaces) c->fe_auto.host_batch((double)s.host_ms, n);      // DG_FE_AUTO's measurement of the host side
     HIP_TRY(hipMemcpyAsync(s.d_fe.get(), s.h_fe.get(), L.total, hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
@@ -338,6 +340,7 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
     const size_t anims = t.add(sc.fs_anims), bitmaps = t.add(sc.fs_bitmaps), sky = t.add(sc.flat_sky), mobjs = t.add(sc.fs_mobjs);
     const size_t sframes = t.add(sc.sprite_frames), aoff = t.add(sc.fs_anc_off), anc = t.add(sc.fs_anc);
     const size_t wnodes = t.add(sc.walk_nodes), wleaf = t.add(sc.walk_leaf_sector);       // the pose kernels' descent (mobj_pose_core.h)
+    const size_t flats = t.add(sc.fs_flats), seg_side = t.add(sc.fs_seg_side);             // what the flat rows start as; what the sidedef entries are searched by (§8p)
     const size_t heights = t.add(sc.fs_heights);                                         // what the sector height rows start as (sector_rows_core.h)
     HIP_TRY(t.upload(c->d_fs_scene));
     FsParams &P = c->fs_proto;
@@ -392,6 +395,20 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
             }
         }
     }
+    // per-view surfaces, by the same rule: every slot's flat rows, flat entry staging and sidedef table (slab_layout.h SurfaceLayout)
+    c->d_scene_flats = sc.sectors.empty() ? nullptr : t.at<FsFlats>(flats);
+    c->d_seg_side = t.at<int32_t>(seg_side);
+    if (c->d_scene_flats) {
+        const SurfaceLayout U = surface_layout((size_t)c->cfg.max_batch, sc.sectors.size());
+        for (Slot &s : c->slots) {
+            Slot::PerScene &b = s.per_scene;
+            if (hip_alloc(b.d_flat_rows, U.rows) != hipSuccess || hip_alloc(b.h_flat_entries, U.entries) != hipSuccess || hip_alloc(b.d_flat_entries, U.entries) != hipSuccess ||
+                hip_alloc(b.h_side_table, U.table) != hipSuccess || hip_alloc(b.d_side_table, U.table) != hipSuccess) {
+                b.d_flat_rows.reset(); b.h_flat_entries.reset(); b.d_flat_entries.reset(); b.h_side_table.reset(); b.d_side_table.reset();
+                (void)hipGetLastError();
+            }
+        }
+    }
     c->fs_scene_ok = true;
     return DG_OK;
 }
@@ -442,7 +459,8 @@ void wire_rows(Rows &R, const Rows &proto, const dg_view *views, int n_frames, c
 // DG_FE_DEVICE_SEGS: nothing of the front end runs on the host.  Per frame it ships the view (trig filled) and the DevFrame header,
 // per batch the scene's current light levels and map-object states; dg_fs_* then write the same record arrays build_batch_fe packs,
 // with fixed per-frame strides (fs_frame.h), into the slot's record slab.
-int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors) {
+int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors,
+                   const dg_view_surfaces *surfaces) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -481,6 +499,7 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     }
     // per-view sector heights, likewise: the entries that stand into the slot's staging; the row kernels write the rows from them
     uint32_t n_height_entries = 0;
+    if (surfaces && (!s.per_scene.d_height_rows || !c->d_scene_heights)) { c->fallbacks_fe++; return kPartsUnsupported; }   // (surfaces read heights through rows)
     if (sectors) {
         if (!s.per_scene.d_height_rows || !c->d_scene_heights || (uint64_t)n * sc.sectors.size() >= (1ull << 31)) { c->fallbacks_fe++; return kPartsUnsupported; }
         FrameArena &A = *c->arenas[0];
@@ -491,6 +510,26 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
             release_view_sectors(A.height_of, A.heights);
             if (bad) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": " + view_sectors_error(bad));
         }
+    }
+    // per-view surfaces, likewise: the flat entries that stand into the slot's staging, and the sidedef entries frame after frame,
+    // sorted, behind their offsets first[frame].  More sidedef entries than the table holds: the host walker, counted.
+    uint32_t n_flat_entries = 0, n_side_entries = 0;
+    const SurfaceLayout U = surface_layout((size_t)c->cfg.max_batch, sc.sectors.size());
+    if (surfaces) {
+        if (!s.per_scene.d_flat_rows || !c->d_scene_flats || !c->d_seg_side || (uint64_t)n * sc.sectors.size() >= (1ull << 31)) { c->fallbacks_fe++; return kPartsUnsupported; }
+        FrameArena &A = *c->arenas[0];
+        FlatEntry *const fe = s.per_scene.h_flat_entries.get();
+        uint32_t *const first = reinterpret_cast<uint32_t *>(s.per_scene.h_side_table.get());
+        FsSideEntry *const se = reinterpret_cast<FsSideEntry *>(s.per_scene.h_side_table.get() + U.first_bytes);
+        for (int i = 0; i < n; i++) {
+            const unsigned bad = resolve_view_surfaces(sc, c->fx.wall.on() ? &c->fx.wall : nullptr, surfaces[i], i, A.side_of, A.sides, A.flat_of, A.flats);
+            if (bad) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": " + view_surfaces_error(bad));
+            if ((size_t)n_side_entries + A.sides.size() > U.side_cap) { c->fallbacks_fe++; return kPartsUnsupported; }
+            first[i] = n_side_entries;
+            for (const FsSideEntry &e : A.sides) se[n_side_entries++] = e;
+            for (const FlatEntry &e : A.flats) fe[n_flat_entries++] = e;                                  // (at most one per sector and frame: the staging holds them)
+        }
+        first[n] = n_side_entries;
     }
     uint8_t *const h = s.h_fe.get(), *const d = s.d_fe.get();
     s.views.assign(views, views + n);
@@ -541,9 +580,15 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         Q.mobjs = s.PP.rows; Q.mobj_stride = s.PP.n_mobjs;
     }
     s.HR = SectorRowParams{};
-    if (sectors) {                                         // the row-reading seg walk reads the rows dg_sector_row_fill / _scatter write
+    if (sectors || surfaces) {                                         // the row-reading seg walk reads the rows dg_sector_row_fill / _scatter write
         s.HR = SectorRowParams{c->d_scene_heights, s.per_scene.d_height_entries.get(), s.per_scene.d_height_rows.get(), (uint32_t)sc.sectors.size(), (uint32_t)n,
                                n_height_entries};
+    }
+    s.SR = FlatRowParams{}; s.SF = FsSurf{};
+    if (surfaces) {                                        // the dg_sfc_* pair reads both kinds of rows and the sidedef table
+        s.SR = FlatRowParams{c->d_scene_flats, s.per_scene.d_flat_entries.get(), s.per_scene.d_flat_rows.get(), (uint32_t)sc.sectors.size(), (uint32_t)n, n_flat_entries};
+        const uint8_t *const dt = s.per_scene.d_side_table.get();
+        s.SF = FsSurf{s.HR.rows, s.SR.rows, s.SR.n_sectors, reinterpret_cast<const FsSideEntry *>(dt + U.first_bytes), reinterpret_cast<const uint32_t *>(dt), c->d_seg_side};
     }
     s.LR = LfxRows{};
     if (lfx) wire_rows(s.LR, c->lfx_proto, Q.views, n, states ? reinterpret_cast<const uint32_t *>(d + L.lmask) : nullptr,
@@ -569,20 +614,22 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     HIP_TRY(hipMemcpyAsync(d, h, L.upload, hipMemcpyHostToDevice, s.stream.get()));
     if (n_pose_entries) HIP_TRY(hipMemcpyAsync(s.per_scene.d_pose_entries.get(), s.per_scene.h_pose_entries.get(), (size_t)n_pose_entries * sizeof(PoseEntry), hipMemcpyHostToDevice, s.stream.get()));
     if (n_height_entries) HIP_TRY(hipMemcpyAsync(s.per_scene.d_height_entries.get(), s.per_scene.h_height_entries.get(), (size_t)n_height_entries * sizeof(SectorEntry), hipMemcpyHostToDevice, s.stream.get()));
+    if (n_flat_entries) HIP_TRY(hipMemcpyAsync(s.per_scene.d_flat_entries.get(), s.per_scene.h_flat_entries.get(), (size_t)n_flat_entries * sizeof(FlatEntry), hipMemcpyHostToDevice, s.stream.get()));
+    if (surfaces) HIP_TRY(hipMemcpyAsync(s.per_scene.d_side_table.get(), s.per_scene.h_side_table.get(), U.first_bytes + (size_t)n_side_entries * sizeof(FsSideEntry), hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
 
 int build_batch(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, const dg_view_poses *poses = nullptr,
-                const dg_view_sectors *sectors = nullptr) {
+                const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr) {
     if (!given && c->fs_enabled && c->fs_scene_ok && choose_fs(c, views, n)) {
-        const int rc = build_batch_fs(c, s, views, n, states, poses, sectors);
+        const int rc = build_batch_fs(c, s, views, n, states, poses, sectors, surfaces);
         if (rc != kPartsUnsupported) return rc;
     }
     if (!given && c->fe_enabled && c->fe_scene_ok) {
-        const int rc = build_batch_fe(c, s, views, n, states, poses, sectors);
+        const int rc = build_batch_fe(c, s, views, n, states, poses, sectors, surfaces);
         if (rc != kPartsUnsupported) return rc;
     }
-    return build_batch_host(c, s, views, given, n, states, DG_FE_HOST, nullptr, false, poses, sectors);
+    return build_batch_host(c, s, views, given, n, states, DG_FE_HOST, nullptr, false, poses, sectors, surfaces);
 }
 
 // The 2-D map view's linedef layer of the uploaded scene, on the kernel stream (timed by the slot's ev_start / ev_setup).  The line records
@@ -763,7 +810,12 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
                 s.hrow_from_start = fs_start != nullptr;
                 HIP_TRY(launch_sector_rows(s.HR, ks, fs_start ? fs_start : s.ev_hrow0.get(), s.ev_hrow.get()));
                 const FsRows R{s.HR.rows, s.HR.n_sectors};
-                HIP_TRY(c->fx.wall.on() ? launch_fs_rows_fx(s.FSP, FsRowsFx{c->fs_fx, R.rows, R.stride}, ks) : launch_fs_rows(s.FSP, R, ks));
+                if (s.SR.n_frames > 0) {                                                                // ... the flat rows too, then the pair that reads both and the sidedef table
+                    HIP_TRY(launch_flat_rows(s.SR, ks, s.ev_srow0.get(), s.ev_srow.get()));
+                    HIP_TRY(c->fx.wall.on() ? launch_fs_surf_fx(s.FSP, FsSurfFx{c->fs_fx, s.SF}, ks) : launch_fs_surf(s.FSP, s.SF, ks));
+                } else {
+                    HIP_TRY(c->fx.wall.on() ? launch_fs_rows_fx(s.FSP, FsRowsFx{c->fs_fx, R.rows, R.stride}, ks) : launch_fs_rows(s.FSP, R, ks));
+                }
             } else {
                 HIP_TRY(c->fx.wall.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
             }
@@ -797,7 +849,7 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     fill_view_trig(v);
     dg_frame_lists fl;
     Slot::RedoState redo_state;
-    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->fx), &c->fx, s.poses_of(i), s.sectors_of(i));
+    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->fx), &c->fx, s.poses_of(i), s.sectors_of(i), s.surfaces_of(i));
     if (!rc) rc = bin_frame(sc, c->fk, fl, bf, err);
     if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
@@ -855,7 +907,7 @@ int redo_overflowed(dg_ctx *c, Slot &s) {
         any_state |= st != nullptr;
         sts.push_back(st ? *st : dg_view_state{nullptr, 0, nullptr, 0});
     }
-    int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), any_state ? sts.data() : nullptr, DG_FE_HOST, nullptr, false, s.poses_of(0), s.sectors_of(0));
+    int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), any_state ? sts.data() : nullptr, DG_FE_HOST, nullptr, false, s.poses_of(0), s.sectors_of(0), s.surfaces_of(0));
     if (rc) return rc;
     rc = enqueue_kernels(c, s);
     if (rc) return rc;
@@ -917,22 +969,23 @@ int take_slot(dg_ctx *c, Slot &s) {
 
 // What a submission built for the slot leaves for later: whether it came from views, and then a copy of their poses (the caller's
 // arrays need not outlive the call).
-void built_from(Slot &s, const dg_view *views, const dg_view_poses *poses, int n, const dg_view_sectors *sectors = nullptr) {
+void built_from(Slot &s, const dg_view *views, const dg_view_poses *poses, int n, const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr) {
     s.from_views = views != nullptr;
     s.keep_poses(views ? poses : nullptr, n);
     s.keep_sectors(views ? sectors : nullptr, n);
+    s.keep_surfaces(views ? surfaces : nullptr, n);
 }
 
 // Slot `slot` for a new submission of n views (or of the caller's lists), and its kernels enqueued.
 int submit(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states, const dg_view_poses *poses = nullptr,
-           const dg_view_sectors *sectors = nullptr) {
+           const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     int rc = take_slot(c, s);
     if (rc) return rc;
-    rc = build_batch(c, s, views, given, n, states, poses, sectors);
+    rc = build_batch(c, s, views, given, n, states, poses, sectors, surfaces);
     if (rc) return rc;
-    built_from(s, views, poses, n, sectors);
+    built_from(s, views, poses, n, sectors, surfaces);
     return enqueue_kernels(c, s);
 }
 
@@ -1045,7 +1098,8 @@ int enqueue_bundle(dg_ctx *c, Slot &s) {
 // Slot `slot` for a bundle of n views (or of the caller's lists, with their owner tags when labels are asked for): the host list path
 // whatever front end the ctx has, one list build and one upload for every part.
 int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, const uint32_t *const *owners, int n, const dg_view_state *states,
-                  uint32_t what, const dg_view_poses *poses = nullptr, const dg_view_sectors *sectors = nullptr) {
+                  uint32_t what, const dg_view_poses *poses = nullptr, const dg_view_sectors *sectors = nullptr,
+                  const dg_view_surfaces *surfaces = nullptr) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     if (const int bad = check_batch(c, n)) return bad;
@@ -1056,12 +1110,12 @@ int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     if (labels && (rc = check_label_scene(*c->scene, err))) return set_err(rc, err);
     if ((rc = take_slot(c, s))) return rc;
     if (labels && (rc = ensure_label_buffers(c, s))) return rc;
-    rc = build_batch_host(c, s, views, given, n, states, DG_FE_BUNDLE, owners, labels, poses, sectors);
+    rc = build_batch_host(c, s, views, given, n, states, DG_FE_BUNDLE, owners, labels, poses, sectors, surfaces);
     if (rc) {
         if (s.phase == Slot::Phase::Prepared && s.front_end == DG_FE_BUNDLE) s.reset();   // (described, then an upload failed: nothing says yet which parts it has)
         return rc;
     }
-    built_from(s, views, poses, n, sectors);
+    built_from(s, views, poses, n, sectors, surfaces);
     s.bundle_what = what;
     return enqueue_bundle(c, s);
 }
@@ -1077,6 +1131,13 @@ int check_view_sectors(const dg_view_sectors *sectors, int n) {
     if (sectors)
         for (int i = 0; i < n; i++)
             if (sectors[i].n && !sectors[i].heights) return set_err(DG_ERR_INVALID, "view sectors with a null array");
+    return DG_OK;
+}
+
+int check_view_surfaces(const dg_view_surfaces *surfaces, int n) {
+    if (surfaces)
+        for (int i = 0; i < n; i++)
+            if ((surfaces[i].n_sides && !surfaces[i].sides) || (surfaces[i].n_flats && !surfaces[i].flats)) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": view surfaces with a null array");
     return DG_OK;
 }
 
@@ -1227,7 +1288,7 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
     }
     for (Slot &s : c->slots) {
         HIP_TRY(stream_create(s.stream));
-        for (Event *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles, &s.ev_pose, &s.ev_hrow0, &s.ev_hrow}) HIP_TRY(event_create(*ev));
+        for (Event *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles, &s.ev_pose, &s.ev_hrow0, &s.ev_hrow, &s.ev_srow0, &s.ev_srow}) HIP_TRY(event_create(*ev));
         HIP_TRY(event_create(s.ev_h2d, false));            // (it only orders streams)
         HIP_TRY(stream_create(s.copy_stream));
         HIP_TRY(hip_alloc(s.h_lists, lists_cap));
@@ -1305,6 +1366,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     c->fx = sc.fx;                                      // the effects' setters (and dg_scene_mobj_event) take effect here
     c->fe_scene_ok = sky.w >= 256 && sky.h >= 128;    // a smaller sky bitmap is an index panic only when a sky visplane is drawn: host path
     c->uploaded_texels = sc.texel_idx.size();
+    c->uploaded_flats = sc.flat_pool.size(); c->uploaded_anims = sc.anim.size();
     c->fs_scene_ok = false;
     if (c->fs_enabled && c->fe_scene_ok && sc.fs_ok && c->cfg.width <= FS_MAX_W) {
         const int rc = upload_fs_scene(c, sc);
@@ -1335,14 +1397,25 @@ int dg_submit_views_poses(dg_ctx *c, int slot, const dg_view *views, const dg_vi
 }
 
 int dg_submit_views_sectors(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, int n) {
+    return dg_submit_views_surfaces(c, slot, views, states, poses, sectors, nullptr, n);
+}
+
+int dg_submit_views_surfaces(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors,
+                             const dg_view_surfaces *surfaces, int n) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
     rc = check_view_states(states, n);
     if (!rc) rc = check_view_poses(poses, n);
     if (!rc) rc = check_view_sectors(sectors, n);
+    if (!rc) rc = check_view_surfaces(surfaces, n);
     if (rc) return rc;
-    return submit(c, slot, views, nullptr, n, states, poses, sectors);
+    return submit(c, slot, views, nullptr, n, states, poses, sectors, surfaces);
+}
+
+int dg_render_views_surfaces(dg_ctx *c, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors,
+                             const dg_view_surfaces *surfaces, int n, uint8_t *out) {
+    return read_or_wait(c, 0, dg_submit_views_surfaces(c, 0, views, states, poses, sectors, surfaces, n), n, out);
 }
 
 int dg_render_views_sectors(dg_ctx *c, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, int n, uint8_t *out) {
@@ -1483,6 +1556,11 @@ int dg_submit_bundle_views_poses(dg_ctx *c, int slot, const dg_view *views, cons
 
 int dg_submit_bundle_views_sectors(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, int n,
                                    uint32_t what) {
+    return dg_submit_bundle_views_surfaces(c, slot, views, states, poses, sectors, nullptr, n, what);
+}
+
+int dg_submit_bundle_views_surfaces(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors,
+                                    const dg_view_surfaces *surfaces, int n, uint32_t what) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
@@ -1490,8 +1568,9 @@ int dg_submit_bundle_views_sectors(dg_ctx *c, int slot, const dg_view *views, co
     rc = check_view_states(states, n);
     if (!rc) rc = check_view_poses(poses, n);
     if (!rc) rc = check_view_sectors(sectors, n);
+    if (!rc) rc = check_view_surfaces(surfaces, n);
     if (rc) return rc;
-    return submit_bundle(c, slot, views, nullptr, nullptr, n, states, what, poses, sectors);
+    return submit_bundle(c, slot, views, nullptr, nullptr, n, states, what, poses, sectors, surfaces);
 }
 
 int dg_bundle_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uint32_t *const *owners, int n, uint32_t what) {

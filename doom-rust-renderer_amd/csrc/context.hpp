@@ -23,6 +23,7 @@
 #include "mobj_fx_kernels.hpp"
 #include "mobj_pose_kernels.hpp"
 #include "sector_rows_kernels.hpp"
+#include "surface_rows_kernels.hpp"
 #include "plane_kernels.hpp"
 #include "pool.hpp"
 #include "reduce_core.h"
@@ -48,6 +49,7 @@ struct Slot {
     Event ev_cend, ev_tiles;
     bool hrow_from_start = false; // their start is ev_start (they were the batch's first kernels), not ev_hrow0
     Event ev_hrow0, ev_hrow;      // start and end of the sector height row kernels of a seg-walk batch with sector entries
+    Event ev_srow0, ev_srow;      // start and end of the flat row kernels of a seg-walk batch with surfaces (they follow the height row kernels)
     Event ev_pose;                // the end of the pose kernels, which are the first of a seg-walk batch with poses (ev_start is their start)
     // ev_raster has been recorded at least once: slot_sync waits only on an event that has.  Not part of the phase below, because it is
     // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
@@ -101,6 +103,12 @@ struct Slot {
         DevPtr<FsHeights> d_height_rows;
         PinnedPtr<SectorEntry> h_height_entries;
         DevPtr<SectorEntry> d_height_entries;
+        // per-view surfaces through the seg walk: slab_layout.h's SurfaceLayout
+        DevPtr<FsFlats> d_flat_rows;
+        PinnedPtr<FlatEntry> h_flat_entries;
+        DevPtr<FlatEntry> d_flat_entries;
+        PinnedPtr<uint8_t> h_side_table;
+        DevPtr<uint8_t> d_side_table;
         void drop() { *this = PerScene{}; }
     } per_scene;
     // What a map submission (front_end DG_FE_MAP*) leaves for its kernels and for dg_replay_slot besides d_lists (the arrow lines, then a
@@ -142,6 +150,8 @@ struct Slot {
     LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
     MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
     SectorRowParams HR{};         // ... and, for a batch with sector entries, dg_sector_row_fill / _scatter; the seg walk is then the row-reading pair (HR.n_frames 0: neither)
+    FlatRowParams SR{};           // ... and, for a batch with surfaces, dg_flat_row_fill / _scatter behind them; the seg walk is then the dg_sfc_* pair, given SF (SR.n_frames 0: neither)
+    FsSurf SF{};
     PoseParams PP{};              // ... and, for a batch with poses, dg_mobj_pose_fill / _place in front of them all (PP.n_frames 0: not launched)
     // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
     // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP / DG_FE_MAP_EXPLORED / DG_FE_MAP_EGO (2-D map frames: arrow lines at the start of d_lists) or
@@ -199,6 +209,24 @@ struct Slot {
         for (int i = 0; i < n; i++) sector_entries.insert(sector_entries.end(), vs[i].heights, vs[i].heights + vs[i].n);
         size_t o = 0;
         for (int i = 0; i < n; i++) { sectors.push_back(dg_view_sectors{sector_entries.data() + o, vs[i].n}); o += vs[i].n; }
+    }
+    // ... and of their surfaces, kept likewise: redone frames, whole-batch fallbacks and dg_slot_sector_flats read them
+    std::vector<dg_view_surfaces> surfaces;
+    std::vector<dg_side_surface> side_entries;
+    std::vector<dg_sector_flats> flat_entries;
+    const dg_view_surfaces *surfaces_of(int i) const { return surfaces.empty() ? nullptr : &surfaces[(size_t)i]; }
+    void keep_surfaces(const dg_view_surfaces *vs, int n) {
+        surfaces.clear(); side_entries.clear(); flat_entries.clear();
+        if (!vs) return;
+        for (int i = 0; i < n; i++) {
+            if (vs[i].sides) side_entries.insert(side_entries.end(), vs[i].sides, vs[i].sides + vs[i].n_sides);
+            if (vs[i].flats) flat_entries.insert(flat_entries.end(), vs[i].flats, vs[i].flats + vs[i].n_flats);
+        }
+        size_t so = 0, fo = 0;
+        for (int i = 0; i < n; i++) {
+            surfaces.push_back(dg_view_surfaces{side_entries.data() + so, vs[i].n_sides, flat_entries.data() + fo, vs[i].n_flats});
+            so += vs[i].n_sides; fo += vs[i].n_flats;
+        }
     }
     void keep_poses(const dg_view_poses *ps, int n) {
         poses.clear(); pose_entries.clear();
@@ -272,6 +300,7 @@ struct dg_ctx {
     FrameConsts fk{};
     DevConsts dk{};
     const Scene *scene = nullptr;
+    size_t uploaded_flats = 0, uploaded_anims = 0;   // flat pool size and animation lists at dg_upload_scene time (dg_scene_use_flat adds to both)
     size_t uploaded_texels = 0;         // texel pool size at dg_upload_scene time (grows when new sprite bitmaps are decoded)
     // device scene
     DevPtr<uint32_t> d_palette;         // 256 x u32 RGBX, followed by 256 x (r, g, b, 0) f32
@@ -312,6 +341,8 @@ struct dg_ctx {
     DevPtr<uint8_t> d_fs_scratch;       // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
     size_t fs_zero_bytes = 0;
     FsParams fs_proto{};                // scene pointers and counts, filled at upload
+    const FsFlats *d_scene_flats = nullptr;       // the scene's flats as loaded, in d_fs_scene: what the flat rows start as
+    const int32_t *d_seg_side = nullptr;          // every seg's front sidedef, in d_fs_scene: what a frame's sidedef entries are searched by
     const FsHeights *d_scene_heights = nullptr;   // the scene's heights as loaded, in d_fs_scene: what the height rows start as
     PoseParams pose_proto{};            // the pose kernels' scene pointers (the scene's rows, the BSP, the leaves' sectors), filled at upload
     uint64_t fallbacks_fe = 0;          // batches in which frames were redone because a device-side capacity was exceeded (dg_ctx_fallbacks)

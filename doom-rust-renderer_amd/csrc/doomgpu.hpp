@@ -26,7 +26,7 @@ struct Error : std::runtime_error {
     int code;
     Error(int c, const char *m) : std::runtime_error(m), code(c) {}
 };
-inline void check(int rc) { if (rc < 0) throw Error(rc, dg_last_error()); }
+inline int check(int rc) { if (rc < 0) throw Error(rc, dg_last_error()); return rc; }
 
 struct Color { uint8_t r, g, b, a; };            // sdl2::pixels::Color as the reference uses it
 struct Vertex { float x, y; };                   // src/map/vertexes.rs:9-13
@@ -126,11 +126,46 @@ public:
             if (f != fl[i] || c != ce[i]) moved_.push_back(dg_sector_heights{(int32_t)i, f, c});
         }
     }
+    // Game::new, BEFORE Device::upload: the bitmap id of a wall texture / the handle of a flat a later tick may put on a sidedef or a
+    // sector (Textures::get / Flats::get_animated by name; decoded now if the map did not use it).  DG_TEX_NONE for "-".
+    int use_texture(const char *name) { return std::string(name) == "-" ? DG_TEX_NONE : check(dg_scene_use_texture(h_, name)); }
+    int use_flat(const char *name) { return check(dg_scene_use_flat(h_, name)); }
+    // map.sidedefs' textures and offsets and map.sectors' flats as loaded (the start of a caller's own copy).
+    std::vector<dg_side_surface> sidedefs() const {
+        std::vector<dg_side_surface> out((size_t)dg_scene_sidedef_count(h_));
+        if (!out.empty()) check(dg_scene_sidedef_surfaces(h_, out.data(), (int)out.size()));
+        return out;
+    }
+    std::vector<dg_sector_flats> sector_flats() const {
+        std::vector<dg_sector_flats> out((size_t)dg_scene_sector_count(h_));
+        if (!out.empty()) check(dg_scene_sector_flats(h_, out.data(), (int)out.size()));
+        return out;
+    }
+    // The sidedefs and sectors whose surfaces sync_surfaces last found changed: what Renderer::render passes as the view's entries
+    // (DESIGN.md section 8p).
+    const std::vector<dg_side_surface> &changed_sidedefs() const { return changed_sides_; }
+    const std::vector<dg_sector_flats> &changed_flats() const { return changed_flats_; }
+    void set_changed_surfaces(const std::vector<dg_side_surface> &sides, const std::vector<dg_sector_flats> &flats) {
+        if (!loaded_known_) { loaded_sides_ = sidedefs(); loaded_flats_ = sector_flats(); loaded_known_ = true; }   // (asked once: what loaded does not change)
+        const std::vector<dg_side_surface> &s0 = loaded_sides_;
+        const std::vector<dg_sector_flats> &f0 = loaded_flats_;
+        changed_sides_.clear(); changed_flats_.clear();
+        for (size_t i = 0; i < sides.size() && i < s0.size(); i++) {
+            const dg_side_surface &a = sides[i], &b = s0[i];
+            if (a.tex_mid != b.tex_mid || a.tex_low != b.tex_low || a.tex_up != b.tex_up || a.x_offset != b.x_offset || a.y_offset != b.y_offset)
+                changed_sides_.push_back(dg_side_surface{(int32_t)i, a.tex_mid, a.tex_low, a.tex_up, a.x_offset, a.y_offset});
+        }
+        for (size_t i = 0; i < flats.size() && i < f0.size(); i++)
+            if (flats[i].floor_flat != f0[i].floor_flat || flats[i].ceil_flat != f0[i].ceil_flat) changed_flats_.push_back(dg_sector_flats{(int32_t)i, flats[i].floor_flat, flats[i].ceil_flat});
+    }
     bool sector_floor_height(const Vertex &v, float &out) const { return dg_scene_floor_height_at(h_, v.x, v.y, &out) == 0; }  // bsp.rs:9-44
     dg_scene *handle() const { return h_; }
 private:
     dg_scene *h_ = nullptr;
     std::vector<dg_sector_heights> moved_;
+    std::vector<dg_side_surface> changed_sides_, loaded_sides_;
+    std::vector<dg_sector_flats> changed_flats_, loaded_flats_;
+    bool loaded_known_ = false;
 };
 
 // Game::render, before Renderer(..).render(): the light levels and map-object states of this tick (rust/src/gpu.rs sync_state).
@@ -144,6 +179,11 @@ inline void sync_state(World &world, const std::vector<Sector> &sectors, const s
         check(dg_scene_set_mobj_state(world.handle(), (int)i, st.is_null ? nullptr : st.sprite, st.frame, st.full_bright ? 1 : 0));
     }
 }
+
+// Game::render, likewise: the sidedefs' textures and offsets and the sectors' flats of this tick, index = position in `map.sidedefs` /
+// `map.sectors`, each the caller's copy of World::sidedefs() / World::sector_flats() with what switches, scrollers and "change texture"
+// specials did to it.  What differs from the loaded values is kept in the World for the next Renderer.
+inline void sync_surfaces(World &world, const std::vector<dg_side_surface> &sides, const std::vector<dg_sector_flats> &flats) { world.set_changed_surfaces(sides, flats); }
 
 // One GPU.  Not in the reference (it has no device); plays the role of the borrowed `&mut Pixels` target's backing store.
 class Device {
@@ -213,7 +253,10 @@ public:
     void render() {
         const std::vector<dg_sector_heights> &moved = world_.moved_sectors();
         const dg_view_sectors vs{moved.data(), (uint32_t)moved.size()};
-        check(dg_render_views_sectors(dev_.handle(), &view_, nullptr, nullptr, moved.empty() ? nullptr : &vs, 1, pixels_.pixels.data()));
+        const std::vector<dg_side_surface> &sides = world_.changed_sidedefs();
+        const std::vector<dg_sector_flats> &flats = world_.changed_flats();
+        const dg_view_surfaces vf{sides.data(), (uint32_t)sides.size(), flats.data(), (uint32_t)flats.size()};
+        check(dg_render_views_surfaces(dev_.handle(), &view_, nullptr, nullptr, moved.empty() ? nullptr : &vs, sides.empty() && flats.empty() ? nullptr : &vf, 1, pixels_.pixels.data()));
     }
     // The viewing_map branch of Game::render (src/game.rs:491-499): canvas.clear() to black, draw_map_linedefs, draw_map_player, into
     // the same Pixels.  Reads the player's position and angle only.

@@ -122,6 +122,8 @@ struct Walker {
     const MobjFx *mfx = nullptr;            // the map-object thinkers to draw with (nullptr: none)
     const dg_view_poses *poses = nullptr;   // where this view's map objects are (nullptr: where the scene has them)
     const FsHeights *hrow = nullptr;        // this view's sector heights, [sector] (nullptr: the scene's, as loaded)
+    bool has_sf = false;                    // this view brings surfaces: sf answers for its sidedefs and flats (and hrow is set)
+    FsViewSurfaces sf{};
     uint32_t cur_owner = 0;                 // owner tag of the seg / map object being processed (host-list mode)
     static constexpr int32_t kNoOverride = INT32_MIN;
 
@@ -130,7 +132,7 @@ struct Walker {
     //  or the map-object thinker's state (§8d), else the scene's value.  The arena's two rows hold what overrides the
     // scene: the effects' values, every effect sector and driven object once per frame, then the view's entries on top.
     Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const SceneFx *f, const dg_view_poses *ps,
-           const dg_view_sectors *vs)
+           const dg_view_sectors *vs, const dg_view_surfaces *vf)
         : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e), state(st), fx(f && f->wall.on() ? &f->wall : nullptr),
           lfx(f && f->light.fits(s) ? &f->light : nullptr), mfx(f && f->mobj.fits(s) ? &f->mobj : nullptr), poses(ps) {
         ppos = V2{v.x, v.y};
@@ -149,6 +151,15 @@ struct Walker {
             release_view_sectors(A.height_of, A.heights);
             hrow = A.height_row.data();
             if (bad) { status = DG_ERR_INVALID; err = view_sectors_error(bad); }
+        }
+        if (vf) {                                                    // likewise the flats, and the sorted sidedef entries fs_seg searches
+            const unsigned bad = resolve_view_surfaces(sc, fx, *vf, 0, A.side_of, A.sides, A.flat_of, A.flats);
+            A.flat_row.assign(sc.fs_flats.begin(), sc.fs_flats.end());
+            for (const FlatEntry &e : A.flats) flat_row_place(A.flat_row.data(), e.sector, e.flats);
+            if (!hrow) { A.height_row.assign(sc.fs_heights.begin(), sc.fs_heights.end()); hrow = A.height_row.data(); }   // (surfaces read heights through the row, as on the device)
+            sf = FsViewSurfaces{A.flat_row.data(), A.sides.data(), (uint32_t)A.sides.size(), sc.fs_seg_side.data()};
+            has_sf = true;
+            if (bad) { status = DG_ERR_INVALID; err = view_surfaces_error(bad); }
         }
         if (!state) return;
         const unsigned bad = apply_view_state(sc, *state, [&](size_t i, int32_t level) { A.light_row[i] = level; }, [&](size_t i, int32_t val) { A.mobj_row[i] = val; });
@@ -357,10 +368,13 @@ struct Walker {
     void process_seg(size_t seg_index) {
         FsSeg sg = sc.fs_segs[seg_index];
         cur_owner = ((uint32_t)DG_LABEL_WALL << 16) | (uint32_t)(seg_index & 0xffffu);
-        if (fx) fs_seg_fx(sg, fx->seg[seg_index], fx->lists.data(), view.timestamp);
         FsSegOut so;
         const int16_t light = sg.front_sector >= 0 ? sector_light(sg.front_sector) : (int16_t)0;
-        const int32_t st = hrow ? fs_seg(k, sg, sc.fs_sectors.data(), sc.fs_anims.data(), ppos, view.cos_na, view.sin_na, player_height, view.timestamp, light, so, FsNoFx(), 0, FsRowHeights{hrow})
+        if (fx && !has_sf) fs_seg_fx(sg, fx->seg[seg_index], fx->lists.data(), view.timestamp);
+        const auto with_sf = [&](const auto &wfx) {                   // the device's composition: the policy first, the effects on what it answers
+            return fs_seg(k, sg, sc.fs_sectors.data(), sc.fs_anims.data(), ppos, view.cos_na, view.sin_na, player_height, view.timestamp, light, so, wfx, (uint32_t)seg_index, FsRowHeights{hrow}, sf);
+        };
+        const int32_t st = has_sf ? (fx ? with_sf(FsFx{fx->seg.data(), fx->lists.data()}) : with_sf(FsNoFx())) : hrow ? fs_seg(k, sg, sc.fs_sectors.data(), sc.fs_anims.data(), ppos, view.cos_na, view.sin_na, player_height, view.timestamp, light, so, FsNoFx(), 0, FsRowHeights{hrow})
                                 : fs_seg(k, sg, sc.fs_sectors.data(), sc.fs_anims.data(), ppos, view.cos_na, view.sin_na, player_height, view.timestamp, light, so);
         if (st == FS_SKIP) return;
         if (st != FS_OK) { fail_fs(st); return; }
@@ -549,7 +563,7 @@ struct Walker {
 }  // namespace
 
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const SceneFx *fx,
-                      const dg_view_poses *poses, const dg_view_sectors *sectors) {
+                      const dg_view_poses *poses, const dg_view_sectors *sectors, const dg_view_surfaces *surfaces) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.renders.clear(); A.owners.clear(); A.columns.clear(); A.visplanes.clear(); A.plane_tb.clear(); A.order.clear();
     A.recs->clear(); A.floor_tb.clear(); A.ceil_tb.clear();
@@ -559,7 +573,7 @@ int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameA
     A.top_clip.resize((size_t)W);
     A.bottom_clip.resize((size_t)W);
 
-    Walker wk(sc, W, H, view, A, err, state, fx, poses, sectors);
+    Walker wk(sc, W, H, view, A, err, state, fx, poses, sectors, surfaces);
     if (wk.status) return wk.status;
     wk.walk_bsp();
     if (wk.status) return wk.status;
@@ -608,11 +622,11 @@ void bin_by_columns(const std::vector<T> &recs, int W, Range range, std::vector<
 }  // namespace
 
 int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state, const SceneFx *fx,
-                      const dg_view_poses *poses, const dg_view_sectors *sectors) {
+                      const dg_view_poses *poses, const dg_view_sectors *sectors, const dg_view_surfaces *surfaces) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.parts.clear(); A.sprites.clear(); A.behind.clear(); A.sky_parts.clear(); A.behind_words = 0; A.n_sky_slots = 0;
     A.recs->clear();
-    Walker wk(sc, W, H, view, A, err, state, fx, poses, sectors);
+    Walker wk(sc, W, H, view, A, err, state, fx, poses, sectors, surfaces);
     if (wk.status) return wk.status;
     wk.parts_mode = true;
     wk.walk_bsp();

@@ -12,10 +12,13 @@
 #include <string>
 #include <vector>
 
+#include <algorithm>
+
 #include "../../include/doomgpu.h"
 #include "fe_dev.h"
 #include "scene.hpp"
 #include "sector_rows_core.h"
+#include "surface_rows_core.h"
 
 namespace dg {
 
@@ -58,6 +61,12 @@ struct FrameArena {
     std::vector<int32_t> height_of;
     std::vector<dg_sector_heights> heights;
     std::vector<FsHeights> height_row;
+    // per sidedef / per sector: its entry in `sides` / `flats`, the view's surface entries as they stand (resolve_view_surfaces), or -1,
+    // likewise; flat_row: the flats one view is drawn with, [sector], written whole by every Walker that has surfaces
+    std::vector<int32_t> side_of, flat_of;
+    std::vector<FsSideEntry> sides;
+    std::vector<FlatEntry> flats;
+    std::vector<FsFlats> flat_row;
     FrameArena();
     ~FrameArena();
     FrameArena(const FrameArena &) = delete;
@@ -70,9 +79,10 @@ struct FrameArena {
 // `fx` (optional): the effects to draw with (Scene::fx, or the copy a dg_ctx uploaded); nullptr: none.
 // `poses` (optional): where the view's map objects are (include/doomgpu.h dg_view_poses); nullptr: where the scene has them.
 // `sectors` (optional): the view's sector floor / ceiling heights (dg_view_sectors); nullptr: as loaded.
+// `surfaces` (optional): the view's sidedef textures and offsets and sector flats (dg_view_surfaces); nullptr: as loaded.
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, dg_frame_lists &out, std::string &err,
                       const dg_view_state *state = nullptr, const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr,
-                      const dg_view_sectors *sectors = nullptr);
+                      const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr);
 
 // Checks a view's snapshot against the scene's ranges and hands every valid entry, in order (later entries win), to light(sector, level)
 // or mobj(map object, mfx_encode'd state).  Returns 0, or bit 0: a sector index was out of range, bit 1: a map object or sprite frame
@@ -139,6 +149,59 @@ inline const char *view_sectors_error(unsigned bad) {
     return bad & 1u ? "view sectors: sector index out of range" : "view sectors: height outside int16";
 }
 
+// A view's surfaces as they stand, by the same rules: of two entries for one sidedef or one sector the later wins.  sides holds one
+// FsSideEntry per sidedef, sorted by sidedef — the span fs_side_find searches — each texture with the live wall animation list it
+// belongs to (wall: the effects drawn with, or nullptr); flats one FlatEntry per sector, sorted by sector, tagged with `frame`.
+// side_of / flat_of are the scratch of the de-duplication ([sidedef] / [sector], all -1 or empty before and after).  Returns 0, or
+// bit 0: a sidedef index out of range, bit 1: a texture id that is neither DG_TEX_NONE nor a wall texture of the scene, bit 2: an offset
+// outside int16, bit 3: a sector index out of range, bit 4: a flat handle not of this scene, bit 5: a null array with n > 0 (the other
+// entries still stand).  The host walker, build_batch_fs (context.cpp) and dg_slot_sector_flats all go through it.
+inline unsigned resolve_view_surfaces(const Scene &sc, const WallFx *wall, const dg_view_surfaces &vs, int32_t frame, std::vector<int32_t> &side_of,
+                                      std::vector<FsSideEntry> &sides, std::vector<int32_t> &flat_of, std::vector<FlatEntry> &flats) {
+    sides.clear(); flats.clear();
+    if (side_of.size() != sc.sidedefs.size()) side_of.assign(sc.sidedefs.size(), -1);
+    if (flat_of.size() != sc.sectors.size()) flat_of.assign(sc.sectors.size(), -1);
+    unsigned bad = 0;
+    if ((vs.n_sides && !vs.sides) || (vs.n_flats && !vs.flats)) return 32u;
+    const auto list_of = [&](int32_t tex) -> int8_t {
+        if (wall && tex >= 0)
+            for (size_t l = 0; l < wall->lists.size(); l++)
+                for (int k = 0; k < wall->lists[l].n; k++)
+                    if (wall->lists[l].flat[k] == tex) return (int8_t)l;
+        return (int8_t)-1;
+    };
+    for (uint32_t i = 0; i < vs.n_sides; i++) {
+        const dg_side_surface &e = vs.sides[i];
+        if (e.sidedef < 0 || (size_t)e.sidedef >= sc.sidedefs.size()) { bad |= 1u; continue; }
+        bool tex_ok = true;
+        for (int32_t t : {e.tex_mid, e.tex_low, e.tex_up}) tex_ok &= t == DG_TEX_NONE || sc.is_wall_texture(t);
+        if (!tex_ok) { bad |= 2u; continue; }
+        if (e.x_offset < -32768 || e.x_offset > 32767 || e.y_offset < -32768 || e.y_offset > 32767) { bad |= 4u; continue; }
+        const FsSideEntry en{e.sidedef, e.tex_mid, e.tex_low, e.tex_up, list_of(e.tex_mid), list_of(e.tex_low), list_of(e.tex_up), 0, (int16_t)e.x_offset, (int16_t)e.y_offset};
+        int32_t &at = side_of[(size_t)e.sidedef];
+        if (at < 0) { at = (int32_t)sides.size(); sides.push_back(en); }
+        else sides[(size_t)at] = en;
+    }
+    for (uint32_t i = 0; i < vs.n_flats; i++) {
+        const dg_sector_flats &e = vs.flats[i];
+        if (e.sector < 0 || (size_t)e.sector >= sc.sectors.size()) { bad |= 8u; continue; }
+        if (!sc.is_flat_handle(e.floor_flat) || !sc.is_flat_handle(e.ceil_flat)) { bad |= 16u; continue; }
+        const FlatEntry en{frame, e.sector, FsFlats{e.floor_flat, e.ceil_flat}};
+        int32_t &at = flat_of[(size_t)e.sector];
+        if (at < 0) { at = (int32_t)flats.size(); flats.push_back(en); }
+        else flats[(size_t)at] = en;
+    }
+    for (const FsSideEntry &e : sides) side_of[(size_t)e.sidedef] = -1;
+    for (const FlatEntry &e : flats) flat_of[(size_t)e.sector] = -1;
+    std::sort(sides.begin(), sides.end(), [](const FsSideEntry &a, const FsSideEntry &b) { return a.sidedef < b.sidedef; });
+    std::sort(flats.begin(), flats.end(), [](const FlatEntry &a, const FlatEntry &b) { return a.sector < b.sector; });
+    return bad;
+}
+inline const char *view_surfaces_error(unsigned bad) {
+    return bad & 32u ? "view surfaces with a null array" : bad & 1u ? "view surfaces: sidedef index out of range" : bad & 2u ? "view surfaces: not a wall texture id of this scene"
+         : bad & 4u ? "view surfaces: offset outside int16" : bad & 8u ? "view surfaces: sector index out of range" : "view surfaces: not a flat handle of this scene";
+}
+
 void fill_view_trig(dg_view &v);
 
 // Parts mode: the per-seg and per-sprite half only (BSP order, transform, clip, projection, pegging, sprite sorting and the
@@ -147,7 +210,8 @@ void fill_view_trig(dg_view &v);
 // host list path can judge: the caller redoes the frame with build_frame_lists).
 constexpr int kPartsUnsupported = 1000;
 int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, std::string &err, const dg_view_state *state = nullptr,
-                      const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr, const dg_view_sectors *sectors = nullptr);
+                      const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr, const dg_view_sectors *sectors = nullptr,
+                      const dg_view_surfaces *surfaces = nullptr);
 
 // Per-record constants of render_vertical_bitmap_line (bitmap_render.rs:233-251), shared by the binner and the parts builder.
 DevWallRec make_wall_rec(const BitmapInfo &bi, float lsx, float lsy, float lex, float ley, float start_offset, int32_t start_x, int32_t end_x,

@@ -212,6 +212,76 @@ template <typename Fx> struct FsWithRows : Fx { FsRowHeights ht; };
 template <typename Fx> DG_HD FsOwnHeights fs_heights_of(const Fx &) { return FsOwnHeights(); }
 template <typename Fx> DG_HD FsRowHeights fs_heights_of(const FsWithRows<Fx> &x) { return x.ht; }
 
+// ---- per-view surfaces (dg_view_surfaces) ------------------------------------------------------------------------------
+// A sector's two flats as one view has them, 8 bytes: each word is a flat handle — the flat id, or FS_FLAT_ANIM | the animation list
+// (Flats::get_animated goes by the name's list, whichever member the name is), FS_FLAT_MISSING when the lump does not exist, and
+// FS_FLAT_SKY when the name contains "SKY" (what the sky hack asks of the ceiling's, segs.rs:463-469).  Never negative.
+enum : int32_t { FS_FLAT_INDEX = 0x0fffffff, FS_FLAT_MISSING = 1 << 28, FS_FLAT_SKY = 1 << 29, FS_FLAT_ANIM = 1 << 30 };
+struct alignas(8) FsFlats { int32_t floor, ceil; };
+static_assert(sizeof(FsFlats) == 8, "FsFlats layout");
+DG_HD int32_t fs_flat_handle(int32_t flat, int32_t anim, bool sky) {
+    return (anim >= 0 ? FS_FLAT_ANIM | anim : flat >= 0 ? flat : FS_FLAT_MISSING) | (sky ? FS_FLAT_SKY : 0);
+}
+DG_HD int32_t fs_handle_flat(int32_t h) { return h & (FS_FLAT_ANIM | FS_FLAT_MISSING) ? (h & FS_FLAT_MISSING ? -2 : 0) : h & FS_FLAT_INDEX; }   // (-2: FLAT_MISSING)
+DG_HD int32_t fs_handle_anim(int32_t h) { return h & FS_FLAT_ANIM ? h & FS_FLAT_INDEX : -1; }
+
+// One sidedef as one view has it, 24 bytes: the three bitmap ids (TEX_NONE for "-"), the live wall animation list of each (-1: none, and
+// always -1 without DG_WALL_ANIMATE) and the two offsets.  A frame's entries are sorted by sidedef and unique (resolve_view_surfaces).
+struct FsSideEntry { int32_t sidedef; int32_t tex_mid, tex_low, tex_up; int8_t anim_mid, anim_low, anim_up, pad; int16_t x_offset, y_offset; };
+static_assert(sizeof(FsSideEntry) == 24, "FsSideEntry layout");
+// The entry of `sidedef` among the n sorted entries at e, or -1: a binary search, at most ceil(log2(n + 1)) probes of 4 bytes.
+DG_HD int32_t fs_side_find(const FsSideEntry *e, uint32_t n, int32_t sidedef) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (e[mid].sidedef < sidedef) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && e[lo].sidedef == sidedef ? (int32_t)lo : -1;
+}
+// The seg with an entry's sidedef in place of its own, and what the wall effects then make of it: the scroll count stays the sidedef's
+// (special 48 belongs to the linedef), the animation lists are those of the entry's textures.
+DG_HD void fs_side_fx(const FsNoFx &, FsSeg &, uint32_t, const FsSideEntry &, float) {}
+DG_HD void fs_side_fx(const FsFx &fx, FsSeg &o, uint32_t si, const FsSideEntry &en, float timestamp) {
+    fs_seg_fx(o, FsSegFx{fx.fx[si].scroll_k, en.anim_mid, en.anim_low, en.anim_up, 0}, fx.lists, timestamp);
+}
+// Where fs_seg reads a sidedef's textures and offsets and a sector's flats (game state in the reference: segs.rs:121-200,450-469,
+// 493-588), asked per field.  FsOwnSurfaces: the seg's and the scene table's own fields, as loaded — the default, and the loads every
+// caller without per-view surfaces made before there was a policy.  FsViewSurfaces: the view's row [sector] of flats and its sorted
+// span of sidedef entries, searched by the seg's front sidedef (seg_side[seg]).
+struct FsOwnSurfaces {
+    template <typename Fx> DG_HD decltype(auto) seg(const Fx &fx, const FsSeg &sg, uint32_t si, float timestamp) const { return fx.seg(sg, si, timestamp); }
+    DG_HD int32_t floor_flat(const FsSector &s, int32_t) const { return s.floor_flat; }
+    DG_HD int32_t floor_anim(const FsSector &s, int32_t) const { return s.floor_anim; }
+    DG_HD int32_t ceil_flat(const FsSector &s, int32_t) const { return s.ceil_flat; }
+    DG_HD int32_t ceil_anim(const FsSector &s, int32_t) const { return s.ceil_anim; }
+    DG_HD bool ceil_sky(const FsSector &s, int32_t) const { return s.ceil_tex_sky != 0; }
+};
+struct FsViewSurfaces {
+    const FsFlats *row;                          // [n_sectors] of the frame
+    const FsSideEntry *sides; uint32_t n_sides;  // the frame's span
+    const int32_t *seg_side;                     // [n_segs] front sidedef of every seg (-1: none)
+    template <typename Fx> DG_HD FsSeg seg(const Fx &fx, const FsSeg &sg, uint32_t si, float timestamp) const {
+        const int32_t at = n_sides ? fs_side_find(sides, n_sides, seg_side[si]) : -1;
+        if (at < 0) return fx.seg(sg, si, timestamp);
+        const FsSideEntry en = sides[at];
+        FsSeg o = sg;
+        o.tex_mid = en.tex_mid; o.tex_low = en.tex_low; o.tex_up = en.tex_up;
+        o.sd_xoff = (float)en.x_offset; o.sd_yoff = (float)en.y_offset;
+        fs_side_fx(fx, o, si, en, timestamp);
+        return o;
+    }
+    DG_HD int32_t floor_flat(const FsSector &, int32_t i) const { return fs_handle_flat(row[i].floor); }
+    DG_HD int32_t floor_anim(const FsSector &, int32_t i) const { return fs_handle_anim(row[i].floor); }
+    DG_HD int32_t ceil_flat(const FsSector &, int32_t i) const { return fs_handle_flat(row[i].ceil); }
+    DG_HD int32_t ceil_anim(const FsSector &, int32_t i) const { return fs_handle_anim(row[i].ceil); }
+    DG_HD bool ceil_sky(const FsSector &, int32_t i) const { return (row[i].ceil & FS_FLAT_SKY) != 0; }
+};
+// The surfaces policy an effects policy carries: none (FsOwnSurfaces) unless it is an FsWithSurfaces, which has height rows too.
+template <typename Fx> struct FsWithSurfaces : FsWithRows<Fx> { FsViewSurfaces sf; };
+template <typename Fx> DG_HD FsOwnSurfaces fs_surfaces_of(const Fx &) { return FsOwnSurfaces(); }
+template <typename Fx> DG_HD FsViewSurfaces fs_surfaces_of(const FsWithSurfaces<Fx> &x) { return x.sf; }
+template <typename Fx> DG_HD FsRowHeights fs_heights_of(const FsWithSurfaces<Fx> &x) { return x.ht; }
+
 enum : int32_t {                             // outcome of fs_seg / fs_part
     FS_OK = 0,
     FS_SKIP = 1,                             // nothing to record (not an error)
@@ -242,10 +312,10 @@ DG_HD FsCall fs_call(const FsSegOut &o, uint32_t i) { return i == 0u ? o.call[0]
 
 // Segs::process_seg, segs.rs:353-590, for a viewer at ppos looking along (cos_na, sin_na) = (cos, sin)(-angle).  light: the front
 // sector's CURRENT light level.  Returns FS_OK with 1 .. 5 calls, FS_SKIP, or a failure.  fx / si: the wall effects and the seg's index
-// (applied past the clip and back-face tests, so that the segs turned away there never look at them).
-template <typename K, typename Fx = FsNoFx, typename Ht = FsOwnHeights>
+// (applied past the clip and back-face tests, so that the segs turned away there never look at them); sf: the surfaces policy, asked there too.
+template <typename K, typename Fx = FsNoFx, typename Ht = FsOwnHeights, typename Sf = FsOwnSurfaces>
 DG_HD int32_t fs_seg(const K &k, const FsSeg &sg, const FsSector *sectors, const FsAnim *anims, V2 ppos, float cos_na, float sin_na, float player_height,
-                     float timestamp, int16_t light, FsSegOut &o, const Fx &fx = Fx(), uint32_t si = 0, const Ht &ht = Ht()) {
+                     float timestamp, int16_t light, FsSegOut &o, const Fx &fx = Fx(), uint32_t si = 0, const Ht &ht = Ht(), const Sf &sf = Sf()) {
     if (sg.front_sector < 0) return FS_SKIP;
     // (the clip comes first here: it needs the seg's two vertices only and turns away most segs of a map; the sector heights the
     // reference reads before it — segs.rs:364-402 — have no side effects and are read below, by the segs that are left)
@@ -268,20 +338,20 @@ DG_HD int32_t fs_seg(const K &k, const FsSeg &sg, const FsSector *sectors, const
 
     ScreenLine fl = project(k, o.cl.line, floor_height - player_height);
     if (fl.sx > fl.ex) return FS_SKIP;                            // back face
-    const auto &sw = fx.seg(sg, si, timestamp);                   // the sidedef's textures and x offset as drawn at this timestamp
+    const auto &sw = sf.seg(fx, sg, si, timestamp);               // the sidedef's textures and offsets as drawn at this timestamp
 
-    o.floor_flat = fs_resolve_flat(fs.floor_flat, fs.floor_anim, anims, timestamp);
-    o.ceil_flat = fs_resolve_flat(fs.ceil_flat, fs.ceil_anim, anims, timestamp);
+    o.floor_flat = fs_resolve_flat(sf.floor_flat(fs, sg.front_sector), sf.floor_anim(fs, sg.front_sector), anims, timestamp);
+    o.ceil_flat = fs_resolve_flat(sf.ceil_flat(fs, sg.front_sector), sf.ceil_anim(fs, sg.front_sector), anims, timestamp);
     if (o.floor_flat < 0 || o.ceil_flat < 0) return FS_FAIL_FLAT;
 
     bool draw_ceiling = true;
-    if (bs && fs.ceil_tex_sky && bs->ceil_tex_sky) {              // sky hack, segs.rs:463-477
+    if (bs && sf.ceil_sky(fs, sg.front_sector) && sf.ceil_sky(*bs, sg.back_sector)) {              // sky hack, segs.rs:463-477
         has_pt = false;
         ceiling_height = fs_fmin((float)ht.ceil(*bs, sg.back_sector), ceiling_height);
         draw_ceiling = false;
     }
     o.seg_offset = sg.seg_offset; o.floor_h = fs_floor_h; o.ceil_h = fs_ceil_h; o.light = light;
-    o.sd_xoff = sw.sd_xoff; o.sd_yoff = sg.sd_yoff;
+    o.sd_xoff = sw.sd_xoff; o.sd_yoff = sw.sd_yoff;
     const uint32_t dc = draw_ceiling ? FEP_DRAW_CEILING : 0u;
     if (!two_sided) {
         const int32_t oy = bottom_unpegged ? f32_as_i32(floor_height - ceiling_height) : 0;

@@ -189,7 +189,7 @@ template <typename Fx = FsNoFx> DG_HD void fs_seg_lane(const FsParams &P, int f,
     const FsSeg sg = fs_load_seg(P.segs + si);
     FsSegOut so;
     // (the sector's light level is not read here: nothing below looks at it, fs_ph_emit fetches it for the parts that are kept)
-    const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, (int16_t)0, so, fx, si, fs_heights_of(fx));
+    const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, (int16_t)0, so, fx, si, fs_heights_of(fx), fs_surfaces_of(fx));
     if (st == FS_SKIP || leaf == 0xffffu) return;                             // (a seg of no reachable leaf is never visited; asked here, after the
                                                                               // clip, so that the seg's record is not fetched behind its leaf's)
     if (st != FS_OK) { fs_flag(P, f, FE_OVF_SEGS); return; }
@@ -406,7 +406,7 @@ template <typename Fx = FsNoFx> DG_HD void fs_ph_emit(const FsParams &P, FsShare
         FsSegOut so;
         FePart p;
         const int32_t st = fs_seg(P.k, sg, P.sectors, P.anims, V2{v.x, v.y}, v.cos_na, v.sin_na, v.floor_height + 41.0f, v.timestamp, P.sector_light[(size_t)f * P.light_stride + (size_t)sg.front_sector], so,
-                                  fx, src >> 3, fs_heights_of(fx));
+                                  fx, src >> 3, fs_heights_of(fx), fs_surfaces_of(fx));
         if (st != FS_OK || fs_part(P.k, so, fs_call(so, src & 7u), P.bitmaps, P.flat_sky, v.floor_height, p) != FS_OK) { fs_or_u32(&S.fail, 1u); continue; }   // (cannot happen: dg_fs_segs passed it)
         p.sky_slot = S.kept_sky[o];
         P.parts[(size_t)f * FS_PART_CAP + o] = p;

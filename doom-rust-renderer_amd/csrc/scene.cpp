@@ -7,9 +7,11 @@
 #include "scene.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cctype>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <stdexcept>
 #include <unordered_map>
 
@@ -104,6 +106,7 @@ struct Builder {
     static Builder resume(Scene &s) {
         Builder b(s);
         for (size_t i = 0; i < s.bitmap_names.size(); i++) b.bitmap_by_key[s.bitmap_names[i]] = (int)i;
+        for (size_t i = 0; i < s.flat_names.size(); i++) b.flat_by_name[s.flat_names[i]] = (int)i;
         b.first_sprite = b.wad.find("S_START");
         b.last_sprite = b.wad.find("S_END");
         return b;
@@ -466,6 +469,57 @@ int Scene::find_or_add_sprite_frame(const std::string &sprite, uint8_t frame, st
     }
 }
 
+// dg_scene_use_texture: Textures::get by the loader's rule (Builder::sidedef_texture); a new bitmap is appended, so no id moves.
+int Scene::use_texture(const std::string &name, std::string &err) {
+    if (name == "-") return TEX_NONE;
+    try {
+        Builder b = Builder::resume(*this);
+        b.load_texture_defs();
+        const size_t before = bitmaps.size();
+        const int id = b.texture_bitmap(name);
+        if (id < 0) { err = "Unknown texture " + name + " (Textures::get panics, textures.rs:158)"; return TEX_UNKNOWN; }
+        if (bitmaps.size() != before) { revision++; rebuild_fs_tables(); }
+        return id;
+    } catch (const std::exception &ex) {
+        err = ex.what();
+        rebuild_fs_tables();
+        return TEX_UNKNOWN;
+    }
+}
+
+// dg_scene_use_flat: Flats::get_animated by the loader's rule (the SECTORS loop of load_scene_from_wad): a member of an animated list
+// is that list, every member loaded; any other name is its lump.  A list whose members are already one of Scene::anim is that one.
+int Scene::use_flat(const std::string &name, std::string &err) {
+    try {
+        Builder b = Builder::resume(*this);
+        const size_t before = flat_names.size();
+        const bool sky = name.find("SKY") != std::string::npos;
+        const int al = anim_list_of(name);
+        int32_t h = -1;
+        if (al >= 0) {
+            AnimList a{};
+            bool ok = true;
+            while (kAnim[al][a.n]) { a.flat[a.n] = b.flat(kAnim[al][a.n]); ok &= a.flat[a.n] >= 0; a.n++; }
+            if (ok) {
+                size_t at = 0;
+                while (at < anim.size() && !(anim[at].n == a.n && std::equal(a.flat, a.flat + a.n, anim[at].flat))) at++;
+                if (at == anim.size()) anim.push_back(a);
+                h = fs_flat_handle(-1, (int32_t)at, sky);
+            }
+        } else {
+            const int id = b.flat(name);
+            if (id >= 0) h = fs_flat_handle(id, -1, sky);
+        }
+        if (flat_names.size() != before || fs_anims.size() != anim.size()) { revision++; rebuild_fs_tables(); }
+        if (h < 0) err = "Could not find flat lump " + name + " (Flat::new unwrap, flats.rs:117)";
+        return h;
+    } catch (const std::exception &ex) {
+        err = ex.what();
+        rebuild_fs_tables();
+        return -1;
+    }
+}
+
 // dg_scene_set_wall_effects: the live lists (members decoded through Textures::get, new bitmaps appended), then the per-seg table.
 int Scene::set_wall_effects(uint32_t flags, std::string &err) {
     if (flags & ~(uint32_t)(DG_WALL_ANIMATE | DG_WALL_SCROLL)) { err = "unknown wall effect bits"; return DG_ERR_INVALID; }
@@ -704,6 +758,23 @@ void Scene::rebuild_fs_tables() {
     }
     fs_heights.resize(sectors.size());
     for (size_t i = 0; i < sectors.size(); i++) fs_heights[i] = FsHeights{sectors[i].floor_h, sectors[i].ceil_h};
+    fs_flats.resize(sectors.size());
+    // (the loader gives every animated sector a list of its own: a handle names the first of equal lists, as use_flat does)
+    std::vector<int32_t> first_of(anim.size());
+    {
+        std::map<std::array<int32_t, 5>, int32_t> seen;
+        for (size_t a = 0; a < anim.size(); a++) {
+            std::array<int32_t, 5> key{anim[a].n, -1, -1, -1, -1};
+            for (int k = 0; k < anim[a].n; k++) key[(size_t)k + 1] = anim[a].flat[k];
+            first_of[a] = seen.emplace(key, (int32_t)a).first->second;
+        }
+    }
+    const auto first_equal = [&](int32_t a) { return first_of[(size_t)a]; };
+    for (size_t i = 0; i < sectors.size(); i++) {
+        const SectorRec &s = sectors[i];
+        fs_flats[i] = FsFlats{fs_flat_handle(s.floor_flat, s.floor_anim < 0 ? -1 : first_equal(s.floor_anim), s.floor_sky != 0),
+                              fs_flat_handle(s.ceil_flat, s.ceil_anim < 0 ? -1 : first_equal(s.ceil_anim), s.ceil_tex_sky != 0)};
+    }
     fs_anims.resize(anim.size());
     for (size_t i = 0; i < anim.size(); i++) {
         fs_anims[i].n = anim[i].n;
@@ -713,6 +784,7 @@ void Scene::rebuild_fs_tables() {
     for (size_t i = 0; i < bitmaps.size(); i++)
         fs_bitmaps[i] = FsBitmap{bitmaps[i].texel_off, (int16_t)bitmaps[i].w, (int16_t)bitmaps[i].h, bitmaps[i].top_offset, (uint16_t)bitmaps[i].has_holes};
     fs_segs.resize(segs.size());
+    fs_seg_side.assign(segs.size(), -1);
     for (size_t i = 0; i < segs.size(); i++) {
         const SegRec &sg = segs[i];
         const LinedefRec &ld = linedefs[(size_t)sg.linedef];
@@ -725,6 +797,7 @@ void Scene::rebuild_fs_tables() {
         if (fsd >= 0) {
             const SidedefRec &sd = sidedefs[(size_t)fsd];
             f.front_sector = sd.sector;
+            fs_seg_side[i] = fsd;
             f.sd_xoff = sd.xoff; f.sd_yoff = sd.yoff;
             f.tex_mid = sd.middle; f.tex_low = sd.lower; f.tex_up = sd.upper;
             if (bsd >= 0) f.back_sector = sidedefs[(size_t)bsd].sector;

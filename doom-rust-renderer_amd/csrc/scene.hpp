@@ -151,6 +151,8 @@ struct Scene {
     std::vector<uint16_t> fs_seg_leaf;              // subsector of every seg
     std::vector<FsSector> fs_sectors;
     std::vector<FsHeights> fs_heights;               // the sectors' heights as loaded, compact: what a view's height row starts as (sector_rows_core.h)
+    std::vector<FsFlats> fs_flats;                  // the sectors' flats as loaded, as handles: what a view's flat row starts as (surface_rows_core.h)
+    std::vector<int32_t> fs_seg_side;               // front sidedef of every seg (-1: none): what a view's sidedef entries are searched by
     std::vector<FsAnim> fs_anims;
     std::vector<FsBitmap> fs_bitmaps;
     std::vector<FsMobj> fs_mobjs;
@@ -176,6 +178,17 @@ struct Scene {
     int sprite_bitmap_id(const std::string &sprite, uint8_t frame, uint8_t rotation) const;
     int sector_from_vertex(float x, float y) const;                              // renderer/bsp.rs:9-44
     int find_or_add_sprite_frame(const std::string &sprite, uint8_t frame, std::string &err);
+    // dg_scene_use_texture / dg_scene_use_flat: the bitmap id of Textures::get(name), decoded and appended when new
+    // (TEX_NONE for "-", TEX_UNKNOWN with err for an unknown name); the flat handle (fs_core.h) of Flats::get_animated(name), its lump —
+    // or every member of its animation list — loaded when new (-1 with err when a lump is missing).
+    int use_texture(const std::string &name, std::string &err);
+    int use_flat(const std::string &name, std::string &err);
+    bool is_wall_texture(int32_t id) const { return id >= 0 && (size_t)id < bitmap_names.size() && bitmap_names[(size_t)id].compare(0, 2, "T:") == 0; }
+    bool is_flat_handle(int32_t h) const {
+        if (h < 0 || (h & FS_FLAT_MISSING)) return false;
+        const size_t i = (size_t)(h & FS_FLAT_INDEX);
+        return h & FS_FLAT_ANIM ? i < anim.size() : i < flat_names.size() && ((h & FS_FLAT_SKY) != 0) == (flat_sky[i] != 0);
+    }
     int set_wall_effects(uint32_t flags, std::string &err);                    // DG_OK, or DG_ERR_INVALID / DG_ERR_WAD with err
     int wall_texture_id(const std::string &name, float timestamp) const;       // texture_id after animation (DG_WALL_ANIMATE)
     int set_light_effects(uint32_t flags, uint64_t seed, std::string &err);    // DG_OK, or DG_ERR_INVALID with err

@@ -10,6 +10,7 @@
 
 #include "fs_frame.h"
 #include "sector_rows_core.h"
+#include "surface_rows_core.h"
 #include "walk_core.h"
 
 namespace dg {
@@ -169,6 +170,24 @@ inline SectorRowLayout sector_row_layout(size_t max_batch, size_t n_sectors) {
     L.cells = max_batch * n_sectors;
     L.rows = L.cells * sizeof(FsHeights);
     L.entries = L.cells * sizeof(SectorEntry);
+    return L;
+}
+
+// Per-slot buffers of the per-view surfaces through the seg walk (surface_rows_core.h, fs_core.h FsSideEntry), sized by the scene at
+// dg_upload_scene.  Flats: the rows [max_batch][n_sectors] in HBM only, and the de-duplicated entries — at the most one per cell — as
+// pinned staging and as their HBM copy, like SectorRowLayout.  Sidedefs: one table of `table` bytes, pinned and in HBM (one H2D copy of
+// what a batch has) — [0, first_bytes) the frames' offsets first[frame], max_batch + 1 of them, then the frames' sorted entries one
+// after the other, side_cap = kSideEntriesPerFrame x max_batch at the most: it does not grow with the map's sidedef count.
+constexpr size_t kSideEntriesPerFrame = 64;
+struct SurfaceLayout { size_t cells, rows, entries, side_cap, first_bytes, table; };
+inline SurfaceLayout surface_layout(size_t max_batch, size_t n_sectors) {
+    SurfaceLayout L;
+    L.cells = max_batch * n_sectors;
+    L.rows = L.cells * sizeof(FsFlats);
+    L.entries = L.cells * sizeof(FlatEntry);
+    L.side_cap = kSideEntriesPerFrame * max_batch;
+    L.first_bytes = align_up((max_batch + 1) * sizeof(uint32_t), 16);
+    L.table = L.first_bytes + L.side_cap * sizeof(FsSideEntry);
     return L;
 }
 

@@ -176,7 +176,8 @@ typedef struct dg_config {
  *   DG_FE_DEVICE_SEGS  the per-seg half runs on the GPU too (one lane per seg / map object, one wavefront per frame for what depends on
  *                      the BSP order): the host ships 88 bytes per view and nothing else (with per-view game state,
  *                      dg_submit_views_state: plus one copy of the sector lights and map-object states per view; with per-view poses,
- *                      dg_submit_views_poses: plus 20 bytes per moved object).  Frames it cannot
+ *                      dg_submit_views_poses: plus 20 bytes per moved object; with per-view surfaces, dg_submit_views_surfaces: plus
+ *                      24 bytes per sidedef entry and 16 bytes per sector entry).  Frames it cannot
  *                      judge (a reference panic, a per-frame capacity: 256 parts after culling, 512 map objects in view, 2 560 columns)
  *                      and maps in which a texture / flat lookup would panic fall back to DG_FE_DEVICE / DG_FE_HOST transparently.
  *                      Costs device memory per ctx: max_batch x segs x 41 B of candidate rows + occupancy bits, plus max_batch x segs x 21 B for maps with
@@ -839,12 +840,66 @@ int dg_slot_sector_heights(dg_ctx *ctx, int slot, int first, int count, int16_t 
  * their dispatches; 0 when that submission launched neither (no sector entries, or not the seg walk). */
 int dg_slot_sector_height_timing(dg_ctx *ctx, int slot, float *ms);
 
+/* ---- per-view surfaces (reference: SideDef textures and offsets, Sector floor_texture / ceiling_texture) ------ */
+/* The reference reads a sidedef's three texture names and two offsets, and a sector's two flat names, again on every frame
+ * (src/renderer/segs.rs:121-200,450-469,493-588): a caller who flips a switch, changes a floor's flat or scrolls a wall sees it.  A
+ * dg_view_surfaces says what the surfaces of ONE view are, on top of what the SIDEDEFS and SECTORS lumps loaded:
+ *   a dg_side_surface overrides all five fields of one sidedef, a dg_sector_flats both flats of one sector, for that view only (a caller
+ *     who changes one field copies the others from dg_scene_sidedef_surfaces / dg_scene_sector_flats);
+ *   textures are bitmap ids from dg_scene_use_texture (DG_TEX_NONE: "-"), flats are handles from dg_scene_use_flat;
+ *   what follows is derived again by the reference's rule: the texture's own width and height in the mapper, holes where a masked
+ *     middle appears or disappears, the sky flag of the ceiling flat (the sky hack switches on and off), a floor that becomes sky, an
+ *     animated flat by timestamp (by the name's list, as Flats::get_animated, not by the name's position in it);
+ *   with dg_scene_set_wall_effects, an overriding texture that is a member of a live animation list animates, and the special-48
+ *     scroll is added to the overriding x_offset;
+ *   of two entries for one sidedef or one sector in one view the later wins;
+ *   an index out of range, a texture id that is neither DG_TEX_NONE nor a wall-texture id of this scene, a flat handle not of this
+ *     scene, an offset outside int16, or a NULL array with n > 0 is DG_ERR_INVALID, the frame named in the message;
+ *   states, poses, sector heights and the three effects compose unchanged.
+ * The 2-D map submissions take none.  Every front end gives the same pixels; with DG_FE_DEVICE_SEGS (and DG_FE_AUTO when it picks the
+ * seg walk) the host ships only entries: 16 bytes per sector entry, from which two kernels write the batch's rows [frame][sector] of
+ * 8 bytes, and 24 bytes per sidedef entry, sorted per frame, which the seg walk searches by a seg's front sidedef (per slot, taken at
+ * dg_upload_scene: device memory max_batch x sectors x 24 B of rows and entries and 64 x max_batch x 24 B of sidedef entries, pinned
+ * memory max_batch x sectors x 16 B and the same sidedef table; it does not grow with the sidedef count; when that allocation fails, or a batch holds more than 64 x max_batch sidedef entries, the batch takes the host walker — same pixels,
+ * counted by dg_ctx_fallbacks).  A batch without surfaces launches exactly the kernels it launched before. */
+#define DG_TEX_NONE (-1)                      /* "-" */
+typedef struct dg_side_surface { int32_t sidedef; int32_t tex_mid, tex_low, tex_up; int32_t x_offset, y_offset; } dg_side_surface;
+typedef struct dg_sector_flats { int32_t sector; int32_t floor_flat, ceil_flat; } dg_sector_flats;
+typedef struct dg_view_surfaces { const dg_side_surface *sides; uint32_t n_sides; const dg_sector_flats *flats; uint32_t n_flats; } dg_view_surfaces;
+/* The bitmap id of Textures::get(name), by the loader's case rules: the texture is decoded and appended if the map did not use it (no
+ * id moves); "-" gives DG_TEX_NONE (the value of DG_ERR_INVALID, which a NULL argument gives: "-" is the only name that returns it);
+ * an unknown name is DG_ERR_WAD.  Call before dg_upload_scene, like dg_scene_sprite_frame: a context refuses batches of a scene that
+ * has decoded bitmaps or loaded flats since its upload. */
+int dg_scene_use_texture(dg_scene *s, const char *name);
+/* A flat handle for the name (>= 0): its lump is loaded if the map did not use it; the name of a member of an animated-flat list stands
+ * for that list, and every member is loaded.  A missing lump is DG_ERR_WAD.  Call before dg_upload_scene. */
+int dg_scene_use_flat(dg_scene *s, const char *name);
+/* The surfaces as loaded: one entry per sidedef / per sector, in index order.  n must equal dg_scene_sidedef_count /
+ * dg_scene_sector_count.  (A sidedef whose texture name is unknown to the WAD reports -2 there, and a sector whose flat lump is missing a
+ * handle with bit 28 set: neither is valid to submit — the reference panics when it draws them — so an entry for such a sidedef or
+ * sector has to name something else in that field.) */
+int dg_scene_sidedef_count(const dg_scene *s);
+int dg_scene_sidedef_surfaces(const dg_scene *s, dg_side_surface *out, int n);
+int dg_scene_sector_flats(const dg_scene *s, dg_sector_flats *out, int n);
+/* The _sectors calls with surfaces[i] for views[i]; surfaces == NULL is exactly the _sectors call. */
+int dg_submit_views_surfaces(dg_ctx *ctx, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, const dg_view_surfaces *surfaces, int n);
+int dg_render_views_surfaces(dg_ctx *ctx, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, const dg_view_surfaces *surfaces, int n, uint8_t *rgb24_out);
+int dg_submit_bundle_views_surfaces(dg_ctx *ctx, int slot, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors, const dg_view_surfaces *surfaces, int n, uint32_t what);
+int dg_build_lists_surfaces(const dg_scene *s, int width, int height, const dg_view *view, const dg_view_poses *poses, const dg_view_sectors *sectors, const dg_view_surfaces *surfaces, dg_frame_lists *out, const uint32_t **owners);
+/* The flat handles the frames [first, first + count) of the slot's last submission were drawn with: out[count][dg_scene_sector_count][2]
+ * (floor, ceiling) — after a seg-walk batch with surfaces the rows its two kernels wrote in device memory, otherwise the rows the host
+ * walker derives from the kept entries.  Waits and fails like dg_slot_sector_heights. */
+int dg_slot_sector_flats(dg_ctx *ctx, int slot, int first, int count, int32_t *out);
+/* GPU time of the row kernels (dg_flat_row_fill, dg_flat_row_scatter) of the slot's last submission, from the events attached to their
+ * dispatches; 0 when that submission launched neither (no surfaces, or not the seg walk). */
+int dg_slot_surface_timing(dg_ctx *ctx, int slot, float *ms);
+
 /* ---- misc ----------------------------------------------------------------------------------------------------- */
 const char *dg_last_error(void); /* thread-local message of the last failing call */
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors, the surfaces) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's

@@ -1,0 +1,297 @@
+"""Per-view surfaces on the CPU (include/doomgpu.h: dg_view_surfaces): the host walker with sidedef and flat
+entries and the host-only calls.  Everything is byte-exact.
+
+  oracle          dg_build_lists_surfaces of the UNPATCHED scene -> the emulator's list rasteriser equals the oracle's frame of the WAD
+                  whose SIDEDEFS / SECTORS records were patched to the same names (tests/surface_cases.py): the named cases on
+                  sidedefs and sectors the view sees, and 60 dense random views, on three maps
+  planes          the same cases through dg_depth_lists_host / dg_label_lists_host / dg_bundle_lists_host against lists built from the
+                  product's own scene of the patched WAD
+  wall effects    an override into a live animation list, and onto a scrolling sidedef, with dg_scene_set_wall_effects on
+  errors          every error return of the new host calls; NULL and empty surfaces give the bytes of the _sectors calls
+  getters         dg_scene_sidedef_surfaces / dg_scene_sector_flats / dg_scene_sidedef_count against the lumps
+  stand-alone     tests/surfaces/surfaces_host_main.cpp under AddressSanitizer + UBSan, as a program
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import emul_bind
+import mobj_pose_cases as mp
+import surface_cases as sc
+import wall_fx
+from conftest import ROOT, load_path
+
+W, H = sc.W, sc.H
+MAPS = [1993, 1994, 1995]
+
+
+def _lists_bytes(dg, fl):
+    return (ctypes.string_at(fl.renders, fl.n_renders * ctypes.sizeof(dg.DgBitmapRender)), ctypes.string_at(fl.columns, fl.n_columns * ctypes.sizeof(dg.DgBitmapColumn)),
+            ctypes.string_at(fl.visplanes, fl.n_visplanes * ctypes.sizeof(dg.DgVisplane)), ctypes.string_at(fl.plane_tb, fl.n_plane_tb * 2),
+            ctypes.string_at(fl.order, fl.n_order * ctypes.sizeof(dg.DgDrawCmd)))
+
+
+@pytest.fixture(scope="module", params=MAPS, ids=lambda p: f"seed{p}")
+def world(request, dg, synth, oracle, wad1993, wad1994, wad1995):
+    seed = request.param
+    first = sc.with_extras({1993: wad1993, 1994: wad1994, 1995: wad1995}[seed])      # (a texture and a flat the map does not use)
+    wad = sc.full_wad(first)                                 # (the map of `first`, every texture and flat decoded: surface_cases.full_wad)
+    scene = dg.Scene(wad, "e1m1")
+    path = load_path(seed)
+    side_pairs, flat_pairs = sc.visible_pairs(oracle, wad, path)      # (the bisecting search of 26 frames: the fixture's cost)
+    return {"seed": seed, "wad": wad, "first": first, "scene": scene, "path": path, "names": sc.Names(scene), "emul": emul_bind.EmulScene(wad), "side_pairs": side_pairs,
+            "flat_pairs": flat_pairs, "cases": sc.named_cases(scene, oracle, wad, path, side_pairs, flat_pairs, sc.unused_texture(first), sc.unused_flat(first))}
+
+
+def _view(dg, case, path):
+    return dg.make_views(case.record(path)[None, :8], timestamp=case.timestamp)[0]
+
+
+def _build(dg, world, case, scene=None, owners=False):
+    scene = scene or world["scene"]
+    names = world["names"] if scene is world["scene"] else sc.Names(scene)
+    return scene.build_lists_surfaces(W, H, _view(dg, case, world["path"]), case.surfaces(names), [tuple(e) for e in case.heights] if case.heights else None,
+                                      mp.entries_as_poses(case.poses) if case.poses else None, owners=owners)
+
+
+def _assert_same(got, want, what):
+    bad = np.argwhere(np.any(got != want, axis=2))
+    assert len(bad) == 0, f"{what}: {len(bad)} pixels differ from the oracle, first at (x={bad[0][1]}, y={bad[0][0]})"
+
+
+def test_getters_equal_the_lumps(dg, world):
+    scene, wad = world["scene"], world["wad"]
+    sides, flats = sc.loaded_sides(wad), sc.loaded_flats(wad)
+    names = sc.Names(dg.Scene(wad, "e1m1"))
+    got = names.scene.sidedef_surfaces()
+    assert got.dtype == np.int32 and got.shape == (len(sides), 6) and names.scene.sidedef_count() == len(sides) == scene.sidedef_count()
+    want = np.array([(i, names.texture(m), names.texture(l), names.texture(u), x, y) for i, (m, l, u, x, y) in enumerate(sides)], dtype=np.int32)
+    assert np.array_equal(got, want)
+    gf = names.scene.sector_flats()
+    assert gf.shape == (len(flats), 3) and np.array_equal(gf, np.array([(s, names.flat_handle(f), names.flat_handle(c)) for s, (f, c) in enumerate(flats)], dtype=np.int32))
+    assert names.texture("-") == dg.TEX_NONE == -1
+    assert names.flat_handle("NUKAGE1") == names.flat_handle("NUKAGE3")          # a member of an animated list stands for the list
+    names.scene.close()
+
+
+def test_named_cases_equal_the_oracle_of_the_patched_wad(dg, oracle, world):
+    """The lists of the unpatched scene with entries are, byte for byte, the lists of the product's scene of the patched WAD in every
+    field that names no bitmap or flat id, and draw to the oracle's frame."""
+    wad, path = world["wad"], world["path"]
+    assert [c.name for c in world["cases"]] == sc.NAMES
+    assert len(world["side_pairs"]) >= 20 and len(world["flat_pairs"]) >= 20
+    assert all(c.changes is not None for c in world["cases"]) and [c.name for c in world["cases"] if not c.changes] == ["same"]
+    for c in world["cases"]:
+        want = sc.oracle_frame(oracle, c.patched(wad), c.record(path), W, H)
+        _assert_same(_draw(dg, world, c), want, c)
+        if c.changes is not None:
+            plain = sc.oracle_frame(oracle, c.patched(wad, with_surfaces=False), c.record(path), W, H)
+            assert np.array_equal(want, plain) != c.changes, c
+
+
+def _draw(dg, world, case, scene=None, emul=None):
+    """The case's lists of the unpatched scene, drawn by the emulator's list rasteriser (its scene is of the same WAD, a full_wad: every
+    bitmap and flat id the lists name is the emulator's too)."""
+    fl = _build(dg, world, case, scene)
+    return np.frombuffer((emul or world["emul"]).draw_lists(W, H, fl)[0], dtype=np.uint8).reshape(H, W, 3)
+
+
+def test_sixty_dense_random_views_equal_the_oracle(dg, oracle, world):
+    wad, path = world["wad"], world["path"]
+    changed = 0
+    for c in sc.random_cases(wad, 60, seed=world["seed"]):
+        want = sc.oracle_frame(oracle, c.patched(wad), c.record(path), W, H)
+        _assert_same(_draw(dg, world, c), want, c)
+        changed += not np.array_equal(want, sc.oracle_frame(oracle, wad, c.record(path), W, H))
+    assert changed >= 55                                          # (every sector's flats are redrawn: nearly every view shows it)
+
+
+def test_planes_equal_those_of_the_scene_of_the_patched_wad(dg, world):
+    """Depth, label and bundle planes of lists built with entries on the unpatched scene equal those of the product's own scene of the
+    patched WAD; so do the owner tags and every list field that carries no bitmap or flat id (the two scenes number those apart)."""
+    wad, scene, path = world["wad"], world["scene"], world["path"]
+    for c in world["cases"] + sc.random_cases(wad, 6, seed=7 + world["seed"]):
+        view = _view(dg, c, path)
+        fl, own = _build(dg, world, c, owners=True)
+        frames = (dg.DgFrameLists * 1)(fl)
+        got = (dg.depth_lists_host(scene, W, H, frames), dg.label_lists_host(scene, W, H, frames, [own]), dg.bundle_lists_host(scene, W, H, frames, [own]))
+        shape = (fl.n_renders, fl.n_columns, fl.n_visplanes, fl.n_plane_tb, fl.n_order)
+        tb, order = ctypes.string_at(fl.plane_tb, fl.n_plane_tb * 2), ctypes.string_at(fl.order, fl.n_order * ctypes.sizeof(dg.DgDrawCmd))
+        patched = dg.Scene(c.patched(wad), "e1m1")
+        fl2, own2 = patched.build_lists_owners(W, H, view)
+        assert shape == (fl2.n_renders, fl2.n_columns, fl2.n_visplanes, fl2.n_plane_tb, fl2.n_order) and np.array_equal(own, own2), c
+        assert tb == ctypes.string_at(fl2.plane_tb, fl2.n_plane_tb * 2) and order == ctypes.string_at(fl2.order, fl2.n_order * ctypes.sizeof(dg.DgDrawCmd)), c
+        frames2 = (dg.DgFrameLists * 1)(fl2)
+        want = (dg.depth_lists_host(patched, W, H, frames2), dg.label_lists_host(patched, W, H, frames2, [own2]), dg.bundle_lists_host(patched, W, H, frames2, [own2]))
+        for g, w in zip(got, want):
+            for a, b in zip(g, w):
+                assert np.array_equal(a, b), c
+        patched.close()
+
+
+def test_null_and_empty_surfaces_give_the_bytes_of_the_sectors_calls(dg, world):
+    scene, names, wad = world["scene"], world["names"], world["wad"]
+    for f in (217, 640):
+        view = dg.make_views(world["path"][[f]])[0]
+        plain = _lists_bytes(dg, scene.build_lists_sectors(W, H, view, None))
+        assert plain == _lists_bytes(dg, scene.build_lists(W, H, view)) and len(plain[0]) > 0
+        assert _lists_bytes(dg, scene.build_lists_surfaces(W, H, view, None)) == plain
+        assert _lists_bytes(dg, scene.build_lists_surfaces(W, H, view, ([], []))) == plain
+        same = next(c for c in world["cases"] if c.name == "same")
+        assert _lists_bytes(dg, scene.build_lists_surfaces(W, H, view, same.surfaces(names))) == plain
+        hs = [(3, -8, 200)]
+        assert _lists_bytes(dg, scene.build_lists_surfaces(W, H, view, ([], []), hs)) == _lists_bytes(dg, scene.build_lists_sectors(W, H, view, hs))
+
+
+def test_wall_effects_on_top_of_an_override(dg):
+    """With dg_scene_set_wall_effects on: an overriding texture that is a member of a live animation list animates, a texture that is not
+    stands still, and the special-48 scroll is added to the overriding x offset — the lists are those of the product's scene of the
+    patched WAD with the same effects, at timestamps that select different frames and scroll amounts."""
+    wad = sc.full_wad(wall_fx.fx_wad())                          # (every texture decoded at load, in one order for the product and the emulator)
+    path = load_path(1993)
+    sides = sc.loaded_sides(wad)
+    k = wall_fx.scroll_counts(wad)
+    scrolling = [i for i in range(len(sides)) if k[i]]
+    assert scrolling and wall_fx.live_lists(wad)
+    plain = dg.Scene(wad, "e1m1")
+    names = sc.Names(plain)
+    entries = []
+    for j, i in enumerate(range(0, len(sides), 3)):
+        tex = ("BFALL2", "SLADRIP3", "FIREWALB", "BRICK1", "BLODGR2")[j % 5]          # (BLODGR: a list that is not live)
+        entries.append((i,) + tuple(n if n == "-" else tex for n in sides[i][:3]) + (sides[i][3] + 5, sides[i][4] - 3))
+    for i in scrolling:
+        entries.append((i,) + tuple(n if n == "-" else "BFALL4" for n in sides[i][:3]) + (32760, 1))
+    case = sc.Case("fx", 0, entries)
+    baked = dg.Scene(case.patched(wad), "e1m1")
+    emul_plain, emul_baked = emul_bind.EmulScene(wad), emul_bind.EmulScene(case.patched(wad))
+
+    def draw(emul, fl):
+        return np.frombuffer(emul.draw_lists(W, H, fl)[0], dtype=np.uint8).reshape(H, W, 3).copy()
+    differs = 0
+    for flags in (dg.DG_WALL_ANIMATE | dg.DG_WALL_SCROLL, dg.DG_WALL_ANIMATE, dg.DG_WALL_SCROLL):
+        plain.set_wall_effects(flags)
+        baked.set_wall_effects(flags)
+        emul_plain.set_wall_effects(flags)
+        emul_baked.set_wall_effects(flags)
+        surf = case.surfaces(names)
+        for f, t in ((40, 0.0), (217, 0.4), (323, 1.7), (640, 1900.3)):
+            view = dg.make_views(path[[f]], timestamp=t)[0]
+            got = plain.build_lists_surfaces(W, H, view, surf)
+            shape = (got.n_renders, got.n_columns, got.n_visplanes, got.n_order)
+            frame = draw(emul_plain, got)
+            want = baked.build_lists(W, H, view)
+            assert shape == (want.n_renders, want.n_columns, want.n_visplanes, want.n_order), (flags, f, t)
+            assert np.array_equal(frame, draw(emul_baked, want)), (flags, f, t)
+            differs += not np.array_equal(frame, draw(emul_plain, plain.build_lists(W, H, view)))
+    assert differs >= 8
+    plain.close(); baked.close()
+
+
+def test_argument_errors(dg, world):
+    L, scene, names = dg.lib(), world["scene"], world["names"]
+    n_sd, n_sec = scene.sidedef_count(), scene.sector_count()
+    view = dg.make_views(world["path"][[0]])[0]
+    fl = dg.DgFrameLists()
+    t, f = names.texture("BRICK1"), names.flat_handle("FLOOR0")
+    sprite_bitmap = next(i for i in range(4096) if i not in set(scene.sidedef_surfaces()[:, 1:4].ravel()) and not _is_wall_texture(dg, scene, i))
+
+    def invalid(surfaces, text):
+        with pytest.raises(dg.DoomGpuError) as e:
+            scene.build_lists_surfaces(W, H, view, surfaces)
+        assert e.value.code == dg.DG_ERR_INVALID and text in str(e.value), (surfaces, str(e.value))
+    for bad in (n_sd, n_sd + 7, -1, 1 << 20):
+        invalid(([(0, t, t, t, 0, 0), (bad, t, t, t, 0, 0)], []), "sidedef index out of range")
+    for bad in (n_sec, -1, 1 << 20):
+        invalid(([], [(bad, f, f)]), "sector index out of range")
+    for bad in (-2, -7, 1 << 24, sprite_bitmap):
+        for slot in range(3):
+            tex = [t, t, t]
+            tex[slot] = bad
+            invalid(([(0, tex[0], tex[1], tex[2], 0, 0)], []), "not a wall texture id")
+    for x, y in ((-32769, 0), (32768, 0), (0, -32769), (0, 32768)):
+        invalid(([(0, t, t, t, x, y)], []), "offset outside int16")
+    for bad in (-1, -2, 1 << 28, (1 << 30) | 4000, 5000, f | (1 << 29)):
+        invalid(([], [(0, bad, f)]), "not a flat handle")
+        invalid(([], [(0, f, bad)]), "not a flat handle")
+    scene.build_lists_surfaces(W, H, view, ([(0, -1, -1, -1, -32768, 32767), (n_sd - 1, t, -1, t, 32767, -32768)], [(0, f, f), (n_sec - 1, f, f)]))
+    for vs in (dg.DgViewSurfaces(None, 3, None, 0), dg.DgViewSurfaces(None, 0, None, 2)):
+        assert L.dg_build_lists_surfaces(scene._h, W, H, ctypes.byref(view), None, None, ctypes.byref(vs), ctypes.byref(fl), None) == dg.DG_ERR_INVALID
+        assert b"null array" in L.dg_last_error()
+    assert L.dg_build_lists_surfaces(None, W, H, ctypes.byref(view), None, None, None, ctypes.byref(fl), None) == dg.DG_ERR_INVALID
+    assert L.dg_build_lists_surfaces(scene._h, W, H, None, None, None, None, ctypes.byref(fl), None) == dg.DG_ERR_INVALID
+    assert L.dg_build_lists_surfaces(scene._h, W, H, ctypes.byref(view), None, None, None, None, None) == dg.DG_ERR_INVALID
+    assert L.dg_build_lists_surfaces(scene._h, W, H, ctypes.byref(view), None, None, None, ctypes.byref(fl), None) == dg.DG_OK
+    vs0 = dg.DgViewSurfaces(None, 0, None, 0)
+    assert L.dg_build_lists_surfaces(scene._h, W, H, ctypes.byref(view), None, None, ctypes.byref(vs0), ctypes.byref(fl), None) == dg.DG_OK
+    sides = (dg.DgSideSurface * (n_sd + 1))()
+    flats = (dg.DgSectorFlats * (n_sec + 1))()
+    for bad_n in (n_sd - 1, n_sd + 1, 0, -1):
+        assert L.dg_scene_sidedef_surfaces(scene._h, sides, bad_n) == dg.DG_ERR_INVALID
+    for bad_n in (n_sec - 1, n_sec + 1, 0, -1):
+        assert L.dg_scene_sector_flats(scene._h, flats, bad_n) == dg.DG_ERR_INVALID
+    assert L.dg_scene_sidedef_surfaces(None, sides, n_sd) == dg.DG_ERR_INVALID and L.dg_scene_sidedef_surfaces(scene._h, None, n_sd) == dg.DG_ERR_INVALID
+    assert L.dg_scene_sector_flats(None, flats, n_sec) == dg.DG_ERR_INVALID and L.dg_scene_sector_flats(scene._h, None, n_sec) == dg.DG_ERR_INVALID
+    assert L.dg_scene_sidedef_count(None) == dg.DG_ERR_INVALID
+    assert L.dg_scene_use_texture(None, b"BRICK1") == dg.DG_ERR_INVALID and L.dg_scene_use_texture(scene._h, None) == dg.DG_ERR_INVALID
+    assert L.dg_scene_use_flat(None, b"FLOOR0") == dg.DG_ERR_INVALID and L.dg_scene_use_flat(scene._h, None) == dg.DG_ERR_INVALID
+    assert L.dg_scene_use_texture(scene._h, b"NOSUCHTX") == dg.DG_ERR_WAD and L.dg_scene_use_flat(scene._h, b"NOSUCHFL") == dg.DG_ERR_WAD
+    assert L.dg_scene_use_texture(scene._h, b"-") == dg.TEX_NONE
+    assert L.dg_scene_use_texture(scene._h, b"brick1") == t                      # the loader's case rule: Textures::get upper-cases
+
+
+def _is_wall_texture(dg, scene, i):
+    fl = dg.DgFrameLists()
+    view = dg.make_views(np.zeros((1, 8), dtype=np.float32))[0]
+    vs, _keep = dg.make_view_surfaces([([(0, i, -1, -1, 0, 0)], [])])
+    return dg.lib().dg_build_lists_surfaces(scene._h, W, H, ctypes.byref(view), None, None, vs, ctypes.byref(fl), None) != dg.DG_ERR_INVALID or \
+        b"not a wall texture" not in dg.lib().dg_last_error()
+
+
+def test_use_texture_and_use_flat_append_and_move_no_id(dg, wad1993):
+    wad1993 = sc.with_extras(wad1993)
+    scene = dg.Scene(wad1993, "e1m1")
+    before_sides, before_flats = scene.sidedef_surfaces(), scene.sector_flats()
+    new_t, new_f = sc.unused_texture(wad1993), sc.unused_flat(wad1993)
+    t = scene.use_texture(new_t)
+    assert t >= 0 and t not in set(before_sides[:, 1:4].ravel()) and scene.use_texture(new_t) == t == scene.use_texture(new_t.lower())
+    f = scene.use_flat(new_f)
+    assert f >= 0 and f not in set(before_flats[:, 1:].ravel()) and scene.use_flat(new_f) == f
+    assert np.array_equal(scene.sidedef_surfaces(), before_sides) and np.array_equal(scene.sector_flats(), before_flats)
+    sky = scene.use_flat("F_SKY1")
+    assert sky & (1 << 29) and not f & (1 << 29)
+    scene.close()
+
+
+def test_the_binding_and_the_header_carry_the_surface_entry_points(dg):
+    declared = dg.declared_symbols()
+    out = subprocess.run(["nm", "-D", "--defined-only", dg.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    for n in ("dg_scene_use_texture", "dg_scene_use_flat", "dg_scene_sidedef_count", "dg_scene_sidedef_surfaces", "dg_scene_sector_flats", "dg_submit_views_surfaces",
+              "dg_render_views_surfaces", "dg_submit_bundle_views_surfaces", "dg_build_lists_surfaces", "dg_slot_sector_flats", "dg_slot_surface_timing"):
+        assert n in declared and n in exported and n in dg._SIGNATURES and hasattr(dg.lib(), n), n
+    for n in ("submit_surfaces", "render_surfaces", "submit_bundle_surfaces", "slot_sector_flats", "surface_timing"):
+        assert callable(getattr(dg.Context, n)), n
+    for n in ("use_texture", "use_flat", "sidedef_count", "sidedef_surfaces", "sector_flats", "build_lists_surfaces"):
+        assert callable(getattr(dg.Scene, n)), n
+    assert callable(dg.make_view_surfaces)
+    assert (ctypes.sizeof(dg.DgSideSurface), ctypes.sizeof(dg.DgSectorFlats), ctypes.sizeof(dg.DgViewSurfaces)) == (24, 12, 32) and b"ABI 4" in dg.lib().dg_version()
+
+
+def test_the_shared_bodies_as_a_stand_alone_program_under_sanitizers(tmp_path, wad1993):
+    """tests/surfaces/surfaces_host_main.cpp (its own main) with the host sources of the library, built with
+    -fsanitize=address,undefined and run as a program: resolve_view_surfaces, surface_rows_core.h's fill and scatter bodies lane after
+    lane at the kernels' boundary counts, fs_side_find with 0, 1, 2 and 257 entries, then build_frame_lists with entries.  It checks its
+    own results; any sanitizer report fails it."""
+    csrc = os.path.join(ROOT, "doom-rust-renderer_amd", "csrc")
+    exe = tmp_path / "surfaces_host_main"
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-fno-omit-frame-pointer", "-o", str(exe), os.path.join(ROOT, "tests", "surfaces", "surfaces_host_main.cpp")] +
+                          [os.path.join(csrc, f) for f in ("api_scene.cpp", "scene.cpp", "frontend.cpp", "binner.cpp", "walk.cpp")])
+    wad = tmp_path / "light.wad"
+    wad.write_bytes(wad1993)
+    r = subprocess.run([str(exe), str(wad), os.path.join(ROOT, "tests", "golden", "campath_seed1993.f32"), "e1m1"],
+                       capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), timeout=600)
+    assert r.returncode == 0 and "surfaces_host_main: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
