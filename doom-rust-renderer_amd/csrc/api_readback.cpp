@@ -240,6 +240,56 @@ void dg::finish_readback(const dg_ctx *c, const Slot &s, const Slot::Readback &r
     }
 }
 
+namespace {
+
+// One kind of per-view rows (view_rows_core.h) of the slot's view submission, frames [first, first + count): what the kind's kernels
+// wrote when the batch went through the seg walk with them, else the scene's row with the frame's kept entries on top — `host` puts
+// one frame's there, by the host walker's rule.
+template <class K, class Host>
+int slot_rows(dg_ctx *c, int slot, int first, int count, typename K::Elem *out, const char *call, const RowRun<K> Slot::*run,
+              const std::vector<typename K::Elem> Scene::*scene_rows, Host host) {
+    using Elem = typename K::Elem;
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    Slot &s = c->slots[(size_t)slot];
+    if (s.phase == Slot::Phase::Empty || !s.from_views || !c->scene) return set_err(DG_ERR_STATE, std::string(call) + ": the slot holds no view submission");
+    if ((rc = check_range(s, first, count, out != nullptr, "bad frame range"))) return rc;
+    if (count == 0) return DG_OK;
+    if ((rc = settle(c, s, Copy::Leave))) return rc;       // (a seg-walk batch redone as a whole is a host-list batch from here on)
+    const Scene &sc = *c->scene;
+    const std::vector<Elem> &loaded = sc.*scene_rows;
+    const size_t n_items = loaded.size();
+    if (n_items == 0) return DG_OK;
+    if (s.seg_walk() && (s.*run).on()) {                   // the rows the kind's kernels wrote
+        HIP_TRY(hipMemcpyAsync(out, (s.*run).P.rows + (size_t)first * n_items, (size_t)count * n_items * sizeof(Elem), hipMemcpyDeviceToHost, s.stream.get()));
+        HIP_TRY(slot_sync(s));
+        return DG_OK;
+    }
+    FrameArena &A = *c->arenas[0];
+    for (int i = 0; i < count; i++) {
+        Elem *row = out + (size_t)i * n_items;
+        std::memcpy(row, loaded.data(), n_items * sizeof(Elem));
+        host(sc, s, A, first + i, row);
+    }
+    return DG_OK;
+}
+
+// The time of the kind's kernels in the slot's last submission; 0 when it had none.
+template <class K> int slot_rows_timing(dg_ctx *c, int slot, float *ms, const RowRun<K> Slot::*run) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!ms) return set_err(DG_ERR_INVALID, "null argument");
+    Slot &s = c->slots[(size_t)slot];
+    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
+    if ((rc = settle(c, s, Copy::Leave))) return rc;
+    *ms = 0.0f;
+    const RowRun<K> &r = s.*run;
+    if (s.seg_walk() && r.on()) HIP_TRY(hipEventElapsedTime(ms, (r.from_start ? s.ev_start : r.t0).get(), r.t1.get()));
+    return DG_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int dg_readback(dg_ctx *c, int slot, int first, int count, uint8_t *out) {
@@ -330,114 +380,40 @@ int dg_frame_checksums(dg_ctx *c, int slot, int first, int count, uint64_t *out)
 
 int dg_slot_mobj_poses(dg_ctx *c, int slot, int first, int count, dg_mobj_placed *out) {
     static_assert(sizeof(dg_mobj_placed) == sizeof(FsMobj) && offsetof(dg_mobj_placed, sector) == offsetof(FsMobj, sector), "dg_mobj_placed / FsMobj");
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (s.phase == Slot::Phase::Empty || !s.from_views || !c->scene) return set_err(DG_ERR_STATE, "dg_slot_mobj_poses: the slot holds no view submission");
-    if ((rc = check_range(s, first, count, out != nullptr, "bad frame range"))) return rc;
-    if (count == 0) return DG_OK;
-    if ((rc = settle(c, s, Copy::Leave))) return rc;       // (a seg-walk batch redone as a whole is a host-list batch from here on)
-    const Scene &sc = *c->scene;
-    const size_t n_mobjs = sc.mobjs.size();
-    if (n_mobjs == 0) return DG_OK;
-    if (s.seg_walk() && s.PP.n_frames > 0) {               // the rows the pose kernels wrote
-        HIP_TRY(hipMemcpyAsync(out, s.PP.rows + (size_t)first * n_mobjs, (size_t)count * n_mobjs * sizeof(FsMobj), hipMemcpyDeviceToHost, s.stream.get()));
-        HIP_TRY(slot_sync(s));
-        return DG_OK;
-    }
-    FrameArena &A = *c->arenas[0];                         // the host walker's rule (Walker::mobj_placed) over the kept entries
-    for (int i = 0; i < count; i++) {
-        dg_mobj_placed *row = out + (size_t)i * n_mobjs;
-        std::memcpy(row, sc.fs_mobjs.data(), n_mobjs * sizeof(FsMobj));
-        const dg_view_poses *vp = s.poses_of(first + i);
-        if (!vp) continue;
-        (void)resolve_view_poses(sc, *vp, A.pose_of, A.poses);
-        for (const dg_mobj_pose &p : A.poses) row[p.mobj] = dg_mobj_placed{p.x, p.y, p.angle, sc.sector_from_vertex(p.x, p.y)};
-        release_view_poses(A.pose_of, A.poses);
-    }
-    return DG_OK;
+    return slot_rows<PoseRows>(c, slot, first, count, reinterpret_cast<FsMobj *>(out), "dg_slot_mobj_poses", &Slot::pose_run, &Scene::fs_mobjs,
+                               [](const Scene &sc, const Slot &s, FrameArena &A, int frame, FsMobj *row) {      // (Walker::mobj_placed)
+                                   const dg_view_poses *vp = s.poses_of(frame);
+                                   if (!vp) return;
+                                   (void)resolve_view_poses(sc, *vp, A.poses);
+                                   for (const dg_mobj_pose &p : A.poses.out) row[p.mobj] = FsMobj{p.x, p.y, p.angle, sc.sector_from_vertex(p.x, p.y)};
+                                   A.poses.release();
+                               });
 }
 
 int dg_slot_sector_heights(dg_ctx *c, int slot, int first, int count, int16_t *out) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (s.phase == Slot::Phase::Empty || !s.from_views || !c->scene) return set_err(DG_ERR_STATE, "dg_slot_sector_heights: the slot holds no view submission");
-    if ((rc = check_range(s, first, count, out != nullptr, "bad frame range"))) return rc;
-    if (count == 0) return DG_OK;
-    if ((rc = settle(c, s, Copy::Leave))) return rc;       // (a seg-walk batch redone as a whole is a host-list batch from here on)
-    const Scene &sc = *c->scene;
-    const size_t n_sectors = sc.sectors.size();
-    if (n_sectors == 0) return DG_OK;
-    if (s.seg_walk() && s.HR.n_frames > 0) {               // the rows the row kernels wrote
-        HIP_TRY(hipMemcpyAsync(out, s.HR.rows + (size_t)first * n_sectors, (size_t)count * n_sectors * sizeof(FsHeights), hipMemcpyDeviceToHost, s.stream.get()));
-        HIP_TRY(slot_sync(s));
-        return DG_OK;
-    }
-    FrameArena &A = *c->arenas[0];                         // the host walker's rule over the kept entries
-    for (int i = 0; i < count; i++) {
-        FsHeights *row = reinterpret_cast<FsHeights *>(out) + (size_t)i * n_sectors;
-        std::memcpy(row, sc.fs_heights.data(), n_sectors * sizeof(FsHeights));
-        const dg_view_sectors *vs = s.sectors_of(first + i);
-        if (!vs) continue;
-        (void)resolve_view_sectors(sc, *vs, A.height_of, A.heights);
-        for (const dg_sector_heights &h : A.heights) sector_row_place(row, h.sector, h.floor_height, h.ceiling_height);
-        release_view_sectors(A.height_of, A.heights);
-    }
-    return DG_OK;
+    return slot_rows<HeightRows>(c, slot, first, count, reinterpret_cast<FsHeights *>(out), "dg_slot_sector_heights", &Slot::height_run, &Scene::fs_heights,
+                                 [](const Scene &sc, const Slot &s, FrameArena &A, int frame, FsHeights *row) {
+                                     const dg_view_sectors *vs = s.sectors_of(frame);
+                                     if (!vs) return;
+                                     (void)resolve_view_sectors(sc, *vs, A.heights);
+                                     for (const dg_sector_heights &h : A.heights.out) sector_row_place(row, h.sector, h.floor_height, h.ceiling_height);
+                                     A.heights.release();
+                                 });
 }
 
-int dg_slot_sector_height_timing(dg_ctx *c, int slot, float *ms) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    if (!ms) return set_err(DG_ERR_INVALID, "null argument");
-    Slot &s = c->slots[(size_t)slot];
-    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
-    if ((rc = settle(c, s, Copy::Leave))) return rc;
-    *ms = 0.0f;
-    if (s.seg_walk() && s.HR.n_frames > 0) HIP_TRY(hipEventElapsedTime(ms, (s.hrow_from_start ? s.ev_start : s.ev_hrow0).get(), s.ev_hrow.get()));
-    return DG_OK;
-}
+int dg_slot_sector_height_timing(dg_ctx *c, int slot, float *ms) { return slot_rows_timing(c, slot, ms, &Slot::height_run); }
 
 int dg_slot_sector_flats(dg_ctx *c, int slot, int first, int count, int32_t *out) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    Slot &s = c->slots[(size_t)slot];
-    if (s.phase == Slot::Phase::Empty || !s.from_views || !c->scene) return set_err(DG_ERR_STATE, "dg_slot_sector_flats: the slot holds no view submission");
-    if ((rc = check_range(s, first, count, out != nullptr, "bad frame range"))) return rc;
-    if (count == 0) return DG_OK;
-    if ((rc = settle(c, s, Copy::Leave))) return rc;       // (a seg-walk batch redone as a whole is a host-list batch from here on)
-    const Scene &sc = *c->scene;
-    const size_t n_sectors = sc.sectors.size();
-    if (n_sectors == 0) return DG_OK;
-    if (s.seg_walk() && s.SR.n_frames > 0) {               // the rows the row kernels wrote
-        HIP_TRY(hipMemcpyAsync(out, s.SR.rows + (size_t)first * n_sectors, (size_t)count * n_sectors * sizeof(FsFlats), hipMemcpyDeviceToHost, s.stream.get()));
-        HIP_TRY(slot_sync(s));
-        return DG_OK;
-    }
-    FrameArena &A = *c->arenas[0];                         // the host walker's rule over the kept entries
-    for (int i = 0; i < count; i++) {
-        FsFlats *row = reinterpret_cast<FsFlats *>(out) + (size_t)i * n_sectors;
-        std::memcpy(row, sc.fs_flats.data(), n_sectors * sizeof(FsFlats));
-        const dg_view_surfaces *vs = s.surfaces_of(first + i);
-        if (!vs) continue;
-        (void)resolve_view_surfaces(sc, nullptr, *vs, first + i, A.side_of, A.sides, A.flat_of, A.flats);
-        for (const FlatEntry &e : A.flats) flat_row_place(row, e.sector, e.flats);
-    }
-    return DG_OK;
+    return slot_rows<FlatRows>(c, slot, first, count, reinterpret_cast<FsFlats *>(out), "dg_slot_sector_flats", &Slot::flat_run, &Scene::fs_flats,
+                               [](const Scene &sc, const Slot &s, FrameArena &A, int frame, FsFlats *row) {
+                                   const dg_view_surfaces *vs = s.surfaces_of(frame);
+                                   if (!vs) return;
+                                   (void)resolve_view_surfaces(sc, nullptr, *vs, frame, A.sides, A.flats);
+                                   for (const FlatEntry &e : A.flats.out) flat_row_place(row, e.sector, e.flats);
+                               });
 }
 
-int dg_slot_surface_timing(dg_ctx *c, int slot, float *ms) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    if (!ms) return set_err(DG_ERR_INVALID, "null argument");
-    Slot &s = c->slots[(size_t)slot];
-    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
-    if ((rc = settle(c, s, Copy::Leave))) return rc;
-    *ms = 0.0f;
-    if (s.seg_walk() && s.SR.n_frames > 0) HIP_TRY(hipEventElapsedTime(ms, s.ev_srow0.get(), s.ev_srow.get()));
-    return DG_OK;
-}
+int dg_slot_surface_timing(dg_ctx *c, int slot, float *ms) { return slot_rows_timing(c, slot, ms, &Slot::flat_run); }
 
 int dg_slot_framebuffer(dg_ctx *c, int slot, void **p) {
     int rc = check_slot(c, slot);
@@ -447,17 +423,7 @@ int dg_slot_framebuffer(dg_ctx *c, int slot, void **p) {
     return DG_OK;
 }
 
-int dg_slot_mobj_pose_timing(dg_ctx *c, int slot, float *ms) {
-    int rc = check_slot(c, slot);
-    if (rc) return rc;
-    if (!ms) return set_err(DG_ERR_INVALID, "null argument");
-    Slot &s = c->slots[(size_t)slot];
-    if (!s.has_run()) return set_err(DG_ERR_INVALID, "slot has not run yet");
-    if ((rc = settle(c, s, Copy::Leave))) return rc;
-    *ms = 0.0f;
-    if (s.seg_walk() && s.PP.n_frames > 0) HIP_TRY(hipEventElapsedTime(ms, s.ev_start.get(), s.ev_pose.get()));
-    return DG_OK;
-}
+int dg_slot_mobj_pose_timing(dg_ctx *c, int slot, float *ms) { return slot_rows_timing(c, slot, ms, &Slot::pose_run); }
 
 int dg_slot_label_timing(dg_ctx *c, int slot, float *tiles_ms, float *boxes_ms) {
     int rc = check_slot(c, slot);

@@ -299,6 +299,19 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
 // DG_FE_DEVICE_SEGS: the scene's per-seg / per-sprite tables and BSP tables (Scene::rebuild_fs_tables) in one device allocation, the
 // tables of the effects that are on in one each, and the per-batch scratch of the seg walk, whose size follows the scene (segs, leaves).
 void drop_fs_scene(dg_ctx *c) { c->d_fs_scene.reset(); c->d_fs_scratch.reset(); c->d_wall_fx.reset(); c->d_light_fx.reset(); c->d_mobj_fx.reset(); }
+// One kind of per-view rows at dg_upload_scene: `proto` becomes the scene side of its kernels' arguments, and every slot gets the
+// kind's buffers.  scene_rows null: the scene has no such rows — no proto, no buffers.  A slot whose buffers cannot be had stays
+// without, and sends its batches that carry the kind through the host walker (build_batch_fs).
+template <class K>
+void upload_view_rows(dg_ctx *c, ViewRowParams<K> &proto, RowBuffers<K> Slot::PerScene::*buffers, const typename K::Elem *scene_rows, size_t n_items,
+                      const typename K::Ctx &ctx = {}) {
+    proto = ViewRowParams<K>{};
+    for (Slot &s : c->slots) s.per_scene.*buffers = {};
+    if (!scene_rows) return;
+    proto.scene_rows = scene_rows; proto.n_items = (uint32_t)n_items; proto.ctx = ctx;
+    const ViewRowLayout L = view_row_layout<K>((size_t)c->cfg.max_batch, n_items);
+    for (Slot &s : c->slots) (s.per_scene.*buffers).alloc(L);
+}
 int upload_fs_scene(dg_ctx *c, const Scene &sc) {
     drop_fs_scene(c);
     c->fs_fx = FsFx{};
@@ -341,7 +354,7 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
     const size_t sframes = t.add(sc.sprite_frames), aoff = t.add(sc.fs_anc_off), anc = t.add(sc.fs_anc);
     const size_t wnodes = t.add(sc.walk_nodes), wleaf = t.add(sc.walk_leaf_sector);       // the pose kernels' descent (mobj_pose_core.h)
     const size_t flats = t.add(sc.fs_flats), seg_side = t.add(sc.fs_seg_side);             // what the flat rows start as; what the sidedef entries are searched by (§8p)
-    const size_t heights = t.add(sc.fs_heights);                                         // what the sector height rows start as (sector_rows_core.h)
+    const size_t heights = t.add(sc.fs_heights);                                         // what the sector height rows start as (view_rows_core.h)
     HIP_TRY(t.upload(c->d_fs_scene));
     FsParams &P = c->fs_proto;
     P = FsParams{};
@@ -364,49 +377,22 @@ int upload_fs_scene(dg_ctx *c, const Scene &sc) {
     P.cl_rows = reinterpret_cast<uint32_t *>(d + L.cl_rows);
     P.keep_rows = reinterpret_cast<uint32_t *>(d + L.keep_rows);
     P.cl_row_cap = L.cl_row_cap;
-    // per-view poses: the scene's pointers of the pose kernels, and every slot's rows and entry staging, sized by the scene like the
-    // scratch above.  A slot whose buffers cannot be had sends its batches with poses through the host walker (build_batch_fs).
-    c->pose_proto = PoseParams{};
-    if (P.n_mobjs && !sc.walk_nodes.empty()) {
-        PoseParams &Z = c->pose_proto;
-        Z.scene_rows = P.mobjs; Z.nodes = t.at<WalkNode>(wnodes); Z.leaf_sector = t.at<int32_t>(wleaf);
-        Z.root = (int32_t)sc.walk_nodes.size() - 1;
-        Z.n_mobjs = P.n_mobjs;
-        const size_t cells = (size_t)c->cfg.max_batch * P.n_mobjs;
-        for (Slot &s : c->slots) {
-            Slot::PerScene &b = s.per_scene;
-            if (hip_alloc(b.d_pose_rows, cells * sizeof(FsMobj)) != hipSuccess || hip_alloc(b.h_pose_entries, cells * sizeof(PoseEntry)) != hipSuccess ||
-                hip_alloc(b.d_pose_entries, cells * sizeof(PoseEntry)) != hipSuccess) {
-                b.d_pose_rows.reset(); b.h_pose_entries.reset(); b.d_pose_entries.reset();
-                (void)hipGetLastError();
-            }
-        }
-    }
-    // per-view sector heights, by the same rule: every slot's rows and entry staging (slab_layout.h SectorRowLayout)
-    c->d_scene_heights = sc.sectors.empty() ? nullptr : t.at<FsHeights>(heights);
-    if (c->d_scene_heights) {
-        const SectorRowLayout H = sector_row_layout((size_t)c->cfg.max_batch, sc.sectors.size());
-        for (Slot &s : c->slots) {
-            Slot::PerScene &b = s.per_scene;
-            if (hip_alloc(b.d_height_rows, H.rows) != hipSuccess || hip_alloc(b.h_height_entries, H.entries) != hipSuccess ||
-                hip_alloc(b.d_height_entries, H.entries) != hipSuccess) {
-                b.d_height_rows.reset(); b.h_height_entries.reset(); b.d_height_entries.reset();
-                (void)hipGetLastError();
-            }
-        }
-    }
-    // per-view surfaces, by the same rule: every slot's flat rows, flat entry staging and sidedef table (slab_layout.h SurfaceLayout)
-    c->d_scene_flats = sc.sectors.empty() ? nullptr : t.at<FsFlats>(flats);
+    // the three kinds of per-view rows: the scene side of their kernels' arguments, and every slot's rows and entry staging, sized by
+    // the scene like the scratch above (upload_view_rows).  The poses need map objects and a BSP, the other two sectors; the surfaces
+    // bring their sidedef table, which stands or falls with the flats' buffers.
+    const size_t n_sectors = sc.sectors.size();
+    const bool pose_rows = P.n_mobjs && !sc.walk_nodes.empty();
+    upload_view_rows(c, c->pose_proto, &Slot::PerScene::poses, pose_rows ? P.mobjs : nullptr, P.n_mobjs,
+                     PoseCtx{t.at<WalkNode>(wnodes), t.at<int32_t>(wleaf), (int32_t)sc.walk_nodes.size() - 1});
+    upload_view_rows(c, c->height_proto, &Slot::PerScene::heights, n_sectors ? t.at<FsHeights>(heights) : nullptr, n_sectors);
+    upload_view_rows(c, c->flat_proto, &Slot::PerScene::flats, n_sectors ? t.at<FsFlats>(flats) : nullptr, n_sectors);
     c->d_seg_side = t.at<int32_t>(seg_side);
-    if (c->d_scene_flats) {
-        const SurfaceLayout U = surface_layout((size_t)c->cfg.max_batch, sc.sectors.size());
-        for (Slot &s : c->slots) {
-            Slot::PerScene &b = s.per_scene;
-            if (hip_alloc(b.d_flat_rows, U.rows) != hipSuccess || hip_alloc(b.h_flat_entries, U.entries) != hipSuccess || hip_alloc(b.d_flat_entries, U.entries) != hipSuccess ||
-                hip_alloc(b.h_side_table, U.table) != hipSuccess || hip_alloc(b.d_side_table, U.table) != hipSuccess) {
-                b.d_flat_rows.reset(); b.h_flat_entries.reset(); b.d_flat_entries.reset(); b.h_side_table.reset(); b.d_side_table.reset();
-                (void)hipGetLastError();
-            }
+    const SurfaceLayout U = surface_layout((size_t)c->cfg.max_batch, n_sectors);
+    for (Slot &s : c->slots) {
+        Slot::PerScene &b = s.per_scene;
+        if (!b.flats || hip_alloc(b.h_side_table, U.table) != hipSuccess || hip_alloc(b.d_side_table, U.table) != hipSuccess) {
+            b.flats = {}; b.h_side_table.reset(); b.d_side_table.reset();
+            (void)hipGetLastError();
         }
     }
     c->fs_scene_ok = true;
@@ -456,6 +442,26 @@ void wire_rows(Rows &R, const Rows &proto, const dg_view *views, int n_frames, c
     stride = (uint32_t)n;
 }
 
+// One kind of per-view rows (view_rows_core.h) in a seg-walk batch.  Can the slot carry it for n frames — the scene has such rows, the
+// slot got its buffers at dg_upload_scene, and the cells stay below the kernels' 2^31?  If not the batch takes the host walker, and
+// is counted.
+template <class K> bool carries_rows(dg_ctx *c, const RowBuffers<K> &b, const ViewRowParams<K> &proto, int n) {
+    if (b && proto.scene_rows && K::ctx_ok(proto.ctx) && (uint64_t)n * proto.n_items < (1ull << 31)) return true;
+    c->fallbacks_fe++;
+    return false;
+}
+// This batch's arguments of the kind's kernels: n frames, the first n_entries of the slot's staging.
+template <class K> void wire_view_rows(RowRun<K> &run, const ViewRowParams<K> &proto, const RowBuffers<K> &b, int n, uint32_t n_entries) {
+    run.P = proto;
+    run.P.entries = b.d_entries.get(); run.P.rows = b.rows.get();
+    run.P.n_frames = (uint32_t)n; run.P.n_entries = n_entries;
+}
+// ... and their way to the device, on the slot's stream.
+template <class K> hipError_t copy_row_entries(const RowBuffers<K> &b, uint32_t n_entries, hipStream_t stream) {
+    if (!n_entries) return hipSuccess;
+    return hipMemcpyAsync(b.d_entries.get(), b.h_entries.get(), (size_t)n_entries * sizeof(typename K::Entry), hipMemcpyHostToDevice, stream);
+}
+
 // DG_FE_DEVICE_SEGS: nothing of the front end runs on the host.  Per frame it ships the view (trig filled) and the DevFrame header,
 // per batch the scene's current light levels and map-object states; dg_fs_* then write the same record arrays build_batch_fe packs,
 // with fixed per-frame strides (fs_frame.h), into the slot's record slab.
@@ -486,28 +492,28 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     if (poses && sc.mobjs.empty())                                    // (no entry can be valid)
         for (int i = 0; i < n; i++)
             if (poses[i].n) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": view poses: map object index out of range");
+    Slot::PerScene &B = s.per_scene;
+    FrameArena &A = *c->arenas[0];
     if (pose_rows) {
-        if (!s.per_scene.d_pose_rows || !c->pose_proto.nodes || (uint64_t)n * sc.mobjs.size() >= (1ull << 31)) { c->fallbacks_fe++; return kPartsUnsupported; }
-        FrameArena &A = *c->arenas[0];
-        PoseEntry *const he = s.per_scene.h_pose_entries.get();
+        if (!carries_rows(c, B.poses, c->pose_proto, n)) return kPartsUnsupported;
+        PoseEntry *const he = B.poses.h_entries.get();
         for (int i = 0; i < n; i++) {
-            const bool ok = resolve_view_poses(sc, poses[i], A.pose_of, A.poses);
-            for (const dg_mobj_pose &p : A.poses) he[n_pose_entries++] = PoseEntry{i, p.mobj, p.x, p.y, p.angle};     // (at most one per object and frame: the staging holds them)
-            release_view_poses(A.pose_of, A.poses);
+            const bool ok = resolve_view_poses(sc, poses[i], A.poses);
+            for (const dg_mobj_pose &p : A.poses.out) he[n_pose_entries++] = PoseEntry{i, p.mobj, p.x, p.y, p.angle};     // (at most one per object and frame: the staging holds them)
+            A.poses.release();
             if (!ok) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": view poses: map object index out of range");
         }
     }
     // per-view sector heights, likewise: the entries that stand into the slot's staging; the row kernels write the rows from them
+    // (surfaces read heights through rows, with or without sector entries)
     uint32_t n_height_entries = 0;
-    if (surfaces && (!s.per_scene.d_height_rows || !c->d_scene_heights)) { c->fallbacks_fe++; return kPartsUnsupported; }   // (surfaces read heights through rows)
+    if ((sectors || surfaces) && !carries_rows(c, B.heights, c->height_proto, n)) return kPartsUnsupported;
     if (sectors) {
-        if (!s.per_scene.d_height_rows || !c->d_scene_heights || (uint64_t)n * sc.sectors.size() >= (1ull << 31)) { c->fallbacks_fe++; return kPartsUnsupported; }
-        FrameArena &A = *c->arenas[0];
-        SectorEntry *const he = s.per_scene.h_height_entries.get();
+        SectorEntry *const he = B.heights.h_entries.get();
         for (int i = 0; i < n; i++) {
-            const unsigned bad = resolve_view_sectors(sc, sectors[i], A.height_of, A.heights);
-            for (const dg_sector_heights &e : A.heights) he[n_height_entries++] = SectorEntry{i, e.sector, (int16_t)e.floor_height, (int16_t)e.ceiling_height};   // (at most one per sector and frame: the staging holds them)
-            release_view_sectors(A.height_of, A.heights);
+            const unsigned bad = resolve_view_sectors(sc, sectors[i], A.heights);
+            for (const dg_sector_heights &e : A.heights.out) he[n_height_entries++] = SectorEntry{i, e.sector, (int16_t)e.floor_height, (int16_t)e.ceiling_height};   // (at most one per sector and frame: the staging holds them)
+            A.heights.release();
             if (bad) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": " + view_sectors_error(bad));
         }
     }
@@ -516,18 +522,17 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     uint32_t n_flat_entries = 0, n_side_entries = 0;
     const SurfaceLayout U = surface_layout((size_t)c->cfg.max_batch, sc.sectors.size());
     if (surfaces) {
-        if (!s.per_scene.d_flat_rows || !c->d_scene_flats || !c->d_seg_side || (uint64_t)n * sc.sectors.size() >= (1ull << 31)) { c->fallbacks_fe++; return kPartsUnsupported; }
-        FrameArena &A = *c->arenas[0];
-        FlatEntry *const fe = s.per_scene.h_flat_entries.get();
-        uint32_t *const first = reinterpret_cast<uint32_t *>(s.per_scene.h_side_table.get());
-        FsSideEntry *const se = reinterpret_cast<FsSideEntry *>(s.per_scene.h_side_table.get() + U.first_bytes);
+        if (!carries_rows(c, B.flats, c->flat_proto, n)) return kPartsUnsupported;
+        FlatEntry *const fe = B.flats.h_entries.get();
+        uint32_t *const first = reinterpret_cast<uint32_t *>(B.h_side_table.get());
+        FsSideEntry *const se = reinterpret_cast<FsSideEntry *>(B.h_side_table.get() + U.first_bytes);
         for (int i = 0; i < n; i++) {
-            const unsigned bad = resolve_view_surfaces(sc, c->fx.wall.on() ? &c->fx.wall : nullptr, surfaces[i], i, A.side_of, A.sides, A.flat_of, A.flats);
+            const unsigned bad = resolve_view_surfaces(sc, c->fx.wall.on() ? &c->fx.wall : nullptr, surfaces[i], i, A.sides, A.flats);
             if (bad) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": " + view_surfaces_error(bad));
-            if ((size_t)n_side_entries + A.sides.size() > U.side_cap) { c->fallbacks_fe++; return kPartsUnsupported; }
+            if ((size_t)n_side_entries + A.sides.out.size() > U.side_cap) { c->fallbacks_fe++; return kPartsUnsupported; }
             first[i] = n_side_entries;
-            for (const FsSideEntry &e : A.sides) se[n_side_entries++] = e;
-            for (const FlatEntry &e : A.flats) fe[n_flat_entries++] = e;                                  // (at most one per sector and frame: the staging holds them)
+            for (const FsSideEntry &e : A.sides.out) se[n_side_entries++] = e;
+            for (const FlatEntry &e : A.flats.out) fe[n_flat_entries++] = e;                               // (at most one per sector and frame: the staging holds them)
         }
         first[n] = n_side_entries;
     }
@@ -572,23 +577,16 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     Q.mstate_stride = states ? (uint32_t)sc.mobjs.size() : 0u;
     Q.views = reinterpret_cast<const dg_view *>(d + L.views);
     Q.n_frames = n;
-    s.PP = PoseParams{};
+    s.pose_run.P = {}; s.height_run.P = {}; s.flat_run.P = {}; s.SF = FsSurf{};
     if (pose_rows) {                                       // the seg walk reads the rows dg_mobj_pose_fill / _place write
-        s.PP = c->pose_proto;
-        s.PP.entries = s.per_scene.d_pose_entries.get(); s.PP.rows = s.per_scene.d_pose_rows.get();
-        s.PP.n_frames = (uint32_t)n; s.PP.n_entries = n_pose_entries;
-        Q.mobjs = s.PP.rows; Q.mobj_stride = s.PP.n_mobjs;
+        wire_view_rows(s.pose_run, c->pose_proto, B.poses, n, n_pose_entries);
+        Q.mobjs = s.pose_run.P.rows; Q.mobj_stride = s.pose_run.P.n_items;
     }
-    s.HR = SectorRowParams{};
-    if (sectors || surfaces) {                                         // the row-reading seg walk reads the rows dg_sector_row_fill / _scatter write
-        s.HR = SectorRowParams{c->d_scene_heights, s.per_scene.d_height_entries.get(), s.per_scene.d_height_rows.get(), (uint32_t)sc.sectors.size(), (uint32_t)n,
-                               n_height_entries};
-    }
-    s.SR = FlatRowParams{}; s.SF = FsSurf{};
+    if (sectors || surfaces) wire_view_rows(s.height_run, c->height_proto, B.heights, n, n_height_entries);   // the row-reading seg walk reads the rows dg_sector_row_fill / _scatter write
     if (surfaces) {                                        // the dg_sfc_* pair reads both kinds of rows and the sidedef table
-        s.SR = FlatRowParams{c->d_scene_flats, s.per_scene.d_flat_entries.get(), s.per_scene.d_flat_rows.get(), (uint32_t)sc.sectors.size(), (uint32_t)n, n_flat_entries};
-        const uint8_t *const dt = s.per_scene.d_side_table.get();
-        s.SF = FsSurf{s.HR.rows, s.SR.rows, s.SR.n_sectors, reinterpret_cast<const FsSideEntry *>(dt + U.first_bytes), reinterpret_cast<const uint32_t *>(dt), c->d_seg_side};
+        wire_view_rows(s.flat_run, c->flat_proto, B.flats, n, n_flat_entries);
+        const uint8_t *const dt = B.d_side_table.get();
+        s.SF = FsSurf{s.height_run.P.rows, s.flat_run.P.rows, s.flat_run.P.n_items, reinterpret_cast<const FsSideEntry *>(dt + U.first_bytes), reinterpret_cast<const uint32_t *>(dt), c->d_seg_side};
     }
     s.LR = LfxRows{};
     if (lfx) wire_rows(s.LR, c->lfx_proto, Q.views, n, states ? reinterpret_cast<const uint32_t *>(d + L.lmask) : nullptr,
@@ -612,10 +610,10 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(d, h, L.upload, hipMemcpyHostToDevice, s.stream.get()));
-    if (n_pose_entries) HIP_TRY(hipMemcpyAsync(s.per_scene.d_pose_entries.get(), s.per_scene.h_pose_entries.get(), (size_t)n_pose_entries * sizeof(PoseEntry), hipMemcpyHostToDevice, s.stream.get()));
-    if (n_height_entries) HIP_TRY(hipMemcpyAsync(s.per_scene.d_height_entries.get(), s.per_scene.h_height_entries.get(), (size_t)n_height_entries * sizeof(SectorEntry), hipMemcpyHostToDevice, s.stream.get()));
-    if (n_flat_entries) HIP_TRY(hipMemcpyAsync(s.per_scene.d_flat_entries.get(), s.per_scene.h_flat_entries.get(), (size_t)n_flat_entries * sizeof(FlatEntry), hipMemcpyHostToDevice, s.stream.get()));
-    if (surfaces) HIP_TRY(hipMemcpyAsync(s.per_scene.d_side_table.get(), s.per_scene.h_side_table.get(), U.first_bytes + (size_t)n_side_entries * sizeof(FsSideEntry), hipMemcpyHostToDevice, s.stream.get()));
+    HIP_TRY(copy_row_entries(B.poses, n_pose_entries, s.stream.get()));
+    HIP_TRY(copy_row_entries(B.heights, n_height_entries, s.stream.get()));
+    HIP_TRY(copy_row_entries(B.flats, n_flat_entries, s.stream.get()));
+    if (surfaces) HIP_TRY(hipMemcpyAsync(B.d_side_table.get(), B.h_side_table.get(), U.first_bytes + (size_t)n_side_entries * sizeof(FsSideEntry), hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
 
@@ -802,22 +800,27 @@ int enqueue_kernels(dg_ctx *c, Slot &s) {
         if (s.seg_walk()) {                                                                             // the seg walk writes what the column walk reads
             if (c->fs_rows_dirty) HIP_TRY(hipMemsetAsync(c->d_fs_scratch.get(), 0, c->fs_zero_bytes, ks));    // (dg_fs_frame leaves its rows clean)
             c->fs_rows_dirty = true;
-            hipEvent_t fs_start = s.ev_start.get();
-            if (s.PP.n_frames > 0) { HIP_TRY(launch_mobj_poses(s.PP, ks, fs_start, s.ev_pose.get())); fs_start = nullptr; }   // the rows dg_fs_frame's map-object phase reads
-            if (s.LR.n_frames > 0) { HIP_TRY(launch_light_rows(s.LR, ks, fs_start)); fs_start = nullptr; }     // the rows dg_fs_* read
-            if (s.MR.n_frames > 0) { HIP_TRY(launch_mobj_rows(s.MR, ks, fs_start)); fs_start = nullptr; }
-            if (s.HR.n_frames > 0) {                                                                    // the height rows, then the pair that reads them
-                s.hrow_from_start = fs_start != nullptr;
-                HIP_TRY(launch_sector_rows(s.HR, ks, fs_start ? fs_start : s.ev_hrow0.get(), s.ev_hrow.get()));
-                const FsRows R{s.HR.rows, s.HR.n_sectors};
-                if (s.SR.n_frames > 0) {                                                                // ... the flat rows too, then the pair that reads both and the sidedef table
-                    HIP_TRY(launch_flat_rows(s.SR, ks, s.ev_srow0.get(), s.ev_srow.get()));
-                    HIP_TRY(c->fx.wall.on() ? launch_fs_surf_fx(s.FSP, FsSurfFx{c->fs_fx, s.SF}, ks) : launch_fs_surf(s.FSP, s.SF, ks));
-                } else {
-                    HIP_TRY(c->fx.wall.on() ? launch_fs_rows_fx(s.FSP, FsRowsFx{c->fs_fx, R.rows, R.stride}, ks) : launch_fs_rows(s.FSP, R, ks));
-                }
+            // The batch's start event goes to whichever launch comes first; every later one takes its own, if it has one.
+            hipEvent_t first = s.ev_start.get();
+            const auto start = [&first](hipEvent_t own) { const hipEvent_t e = first ? first : own; first = nullptr; return e; };
+            const auto rows = [&](auto &run) {                                 // one kind of per-view rows, when the batch carries it
+                if (!run.on()) return hipSuccess;
+                run.from_start = first != nullptr;
+                return launch_view_rows(run.P, ks, start(run.t0.get()), run.t1.get());
+            };
+            HIP_TRY(rows(s.pose_run));                                                                    // the rows dg_fs_frame's map-object phase reads
+            if (s.LR.n_frames > 0) HIP_TRY(launch_light_rows(s.LR, ks, start(nullptr)));                   // the rows dg_fs_* read
+            if (s.MR.n_frames > 0) HIP_TRY(launch_mobj_rows(s.MR, ks, start(nullptr)));
+            HIP_TRY(rows(s.height_run));
+            HIP_TRY(rows(s.flat_run));
+            const bool wfx = c->fx.wall.on();
+            const FsRows R{s.height_run.P.rows, s.height_run.P.n_items};
+            if (s.flat_run.on()) {                          // the pair that reads the height rows, the flat rows and the sidedef table
+                HIP_TRY(wfx ? launch_fs_surf_fx(s.FSP, FsSurfFx{c->fs_fx, s.SF}, ks, start(nullptr)) : launch_fs_surf(s.FSP, s.SF, ks, start(nullptr)));
+            } else if (s.height_run.on()) {                 // the pair that reads the height rows
+                HIP_TRY(wfx ? launch_fs_rows_fx(s.FSP, FsRowsFx{c->fs_fx, R.rows, R.stride}, ks, start(nullptr)) : launch_fs_rows(s.FSP, R, ks, start(nullptr)));
             } else {
-                HIP_TRY(c->fx.wall.on() ? launch_fs_fx(s.FSP, c->fs_fx, ks, fs_start) : launch_fs(s.FSP, ks, fs_start));
+                HIP_TRY(wfx ? launch_fs_fx(s.FSP, c->fs_fx, ks, start(nullptr)) : launch_fs(s.FSP, ks, start(nullptr)));
             }
             c->fs_rows_dirty = false;
         }
@@ -1288,7 +1291,7 @@ int dg_create(const dg_config *cfg, dg_ctx **out) {
     }
     for (Slot &s : c->slots) {
         HIP_TRY(stream_create(s.stream));
-        for (Event *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles, &s.ev_pose, &s.ev_hrow0, &s.ev_hrow, &s.ev_srow0, &s.ev_srow}) HIP_TRY(event_create(*ev));
+        for (Event *ev : {&s.ev_start, &s.ev_setup, &s.ev_raster, &s.ev_rstart, &s.ev_cend, &s.ev_tiles, &s.pose_run.t0, &s.pose_run.t1, &s.height_run.t0, &s.height_run.t1, &s.flat_run.t0, &s.flat_run.t1}) HIP_TRY(event_create(*ev));
         HIP_TRY(event_create(s.ev_h2d, false));            // (it only orders streams)
         HIP_TRY(stream_create(s.copy_stream));
         HIP_TRY(hip_alloc(s.h_lists, lists_cap));

@@ -21,14 +21,12 @@
 #include "kernels.hpp"
 #include "light_fx_kernels.hpp"
 #include "mobj_fx_kernels.hpp"
-#include "mobj_pose_kernels.hpp"
-#include "sector_rows_kernels.hpp"
-#include "surface_rows_kernels.hpp"
 #include "plane_kernels.hpp"
 #include "pool.hpp"
 #include "reduce_core.h"
 #include "scene.hpp"
 #include "slab_layout.h"
+#include "view_rows_kernels.hpp"
 #include "walk_core.h"
 
 #define HIP_TRY(expr)                                                                                   \
@@ -39,6 +37,29 @@
 
 namespace dg {
 
+// One kind of per-view rows through the seg walk (view_rows_core.h).  A slot's buffers of it, as view_row_layout<K>
+// sizes them: the rows the kind's kernels write, and the de-duplicated entries' staging + HBM.  All three or none: a slot without
+// them sends its batches that carry the kind through the host walker (build_batch_fs).
+template <class K> struct RowBuffers {
+    DevPtr<typename K::Elem> rows;
+    PinnedPtr<typename K::Entry> h_entries;
+    DevPtr<typename K::Entry> d_entries;
+    explicit operator bool() const { return rows != nullptr; }
+    void alloc(const ViewRowLayout &L) {
+        if (hip_alloc(rows, L.rows) == hipSuccess && hip_alloc(h_entries, L.entries) == hipSuccess && hip_alloc(d_entries, L.entries) == hipSuccess) return;
+        *this = RowBuffers{};
+        (void)hipGetLastError();    // (not an error of the upload: the host walker stands in)
+    }
+};
+// ... and what a slot's last submission has of the kind: the kernels' arguments (n_frames 0: not launched), and the events on their
+// first and last dispatch — t0 only when the batch's start event did not go to them (enqueue_kernels).
+template <class K> struct RowRun {
+    ViewRowParams<K> P{};
+    Event t0, t1;
+    bool from_start = false;      // they were the batch's first kernels: their start is the slot's ev_start, not t0
+    bool on() const { return P.n_frames > 0; }
+};
+
 struct Slot {
     Stream stream;
     // timing events, attached to the dispatches themselves (kernels.hpp): first / last front-end kernel, raster launch; ev_raster is also
@@ -47,10 +68,6 @@ struct Slot {
     // bundles: the end of the colour raster launch when dg_bundle_tiles follows it (ev_raster is then that kernel's end: always the end of
     // the submission's LAST kernel), and dg_bundle_tiles' start
     Event ev_cend, ev_tiles;
-    bool hrow_from_start = false; // their start is ev_start (they were the batch's first kernels), not ev_hrow0
-    Event ev_hrow0, ev_hrow;      // start and end of the sector height row kernels of a seg-walk batch with sector entries
-    Event ev_srow0, ev_srow;      // start and end of the flat row kernels of a seg-walk batch with surfaces (they follow the height row kernels)
-    Event ev_pose;                // the end of the pose kernels, which are the first of a seg-walk batch with poses (ev_start is their start)
     // ev_raster has been recorded at least once: slot_sync waits only on an event that has.  Not part of the phase below, because it is
     // a fact about the event, not about the submission: it stays true when the slot goes back to empty.
     bool raster_recorded = false;
@@ -93,20 +110,12 @@ struct Slot {
         PinnedPtr<uint32_t> h_masks;     // map frames: the mask rows of the last submission that had any (staging + HBM, max_batch x
         DevPtr<uint32_t> d_masks;        // mask_words), kept for dg_replay_slot
         size_t mask_words = 0;
-        // per-view map-object poses through the seg walk: the rows max_batch x map objects the pose kernels write, and
-        // the de-duplicated entries' staging + HBM (as many at the most).  Unlike the others these are taken at dg_upload_scene
-        // (upload_fs_scene), so that nothing is allocated on the submit path; empty: batches with poses take the host walker.
-        DevPtr<FsMobj> d_pose_rows;
-        PinnedPtr<PoseEntry> h_pose_entries;
-        DevPtr<PoseEntry> d_pose_entries;
-        // per-view sector heights through the seg walk, by the same rule: slab_layout.h's SectorRowLayout
-        DevPtr<FsHeights> d_height_rows;
-        PinnedPtr<SectorEntry> h_height_entries;
-        DevPtr<SectorEntry> d_height_entries;
-        // per-view surfaces through the seg walk: slab_layout.h's SurfaceLayout
-        DevPtr<FsFlats> d_flat_rows;
-        PinnedPtr<FlatEntry> h_flat_entries;
-        DevPtr<FlatEntry> d_flat_entries;
+        // per-view map-object poses, sector heights (§8n) and sector flats (§8p) through the seg walk.  Unlike the others
+        // these are taken at dg_upload_scene (upload_fs_scene), so that nothing is allocated on the submit path.
+        RowBuffers<PoseRows> poses;
+        RowBuffers<HeightRows> heights;
+        RowBuffers<FlatRows> flats;
+        // ... and the surfaces' sidedef table (slab_layout.h's SurfaceLayout), there exactly when `flats` is
         PinnedPtr<uint8_t> h_side_table;
         DevPtr<uint8_t> d_side_table;
         void drop() { *this = PerScene{}; }
@@ -149,10 +158,10 @@ struct Slot {
     FsParams FSP{};               // DG_FE_DEVICE_SEGS: the device seg walk in front of the column walk
     LfxRows LR{};                 // ... and, with the light effects on, dg_light_rows in front of it (LR.n_frames 0: not launched)
     MfxRows MR{};                 // ... and, with the map-object thinkers on, dg_mobj_rows (MR.n_frames 0: not launched)
-    SectorRowParams HR{};         // ... and, for a batch with sector entries, dg_sector_row_fill / _scatter; the seg walk is then the row-reading pair (HR.n_frames 0: neither)
-    FlatRowParams SR{};           // ... and, for a batch with surfaces, dg_flat_row_fill / _scatter behind them; the seg walk is then the dg_sfc_* pair, given SF (SR.n_frames 0: neither)
+    RowRun<PoseRows> pose_run;    // ... and, for a batch with poses, dg_mobj_pose_fill / _place in front of them all
+    RowRun<HeightRows> height_run;   // ... and, for a batch with sector entries or surfaces, dg_sector_row_fill / _scatter; the seg walk is then the row-reading pair
+    RowRun<FlatRows> flat_run;    // ... and, for a batch with surfaces, dg_flat_row_fill / _scatter behind them; the seg walk is then the dg_sfc_* pair, given SF
     FsSurf SF{};
-    PoseParams PP{};              // ... and, for a batch with poses, dg_mobj_pose_fill / _place in front of them all (PP.n_frames 0: not launched)
     // What the last submission went through, as dg_timing.front_end reports it: DG_FE_HOST, DG_FE_DEVICE (the device column walk),
     // DG_FE_DEVICE_SEGS (... with the per-seg half on the GPU too), DG_FE_MAP / DG_FE_MAP_EXPLORED / DG_FE_MAP_EGO (2-D map frames: arrow lines at the start of d_lists) or
     // DG_FE_DEPTH (host lists walked by dg_depth_tiles: the framebuffer slab holds the two planes, not RGB24) or DG_FE_LABELS (host lists
@@ -341,10 +350,12 @@ struct dg_ctx {
     DevPtr<uint8_t> d_fs_scratch;       // occupancy rows (zero between batches) | candidate rows F x n_segs x 5 x 8 B | candidate lists + keep bits of frames beyond FS_CL_CAP
     size_t fs_zero_bytes = 0;
     FsParams fs_proto{};                // scene pointers and counts, filled at upload
-    const FsFlats *d_scene_flats = nullptr;       // the scene's flats as loaded, in d_fs_scene: what the flat rows start as
     const int32_t *d_seg_side = nullptr;          // every seg's front sidedef, in d_fs_scene: what a frame's sidedef entries are searched by
-    const FsHeights *d_scene_heights = nullptr;   // the scene's heights as loaded, in d_fs_scene: what the height rows start as
-    PoseParams pose_proto{};            // the pose kernels' scene pointers (the scene's rows, the BSP, the leaves' sectors), filled at upload
+    // the row kernels' scene side, in d_fs_scene, filled at upload: the table as loaded that the rows start as, its length, and the pose
+    // kernels' BSP and leaf sectors (scene_rows null: the scene has no such rows)
+    PoseParams pose_proto{};
+    SectorRowParams height_proto{};
+    FlatRowParams flat_proto{};
     uint64_t fallbacks_fe = 0;          // batches in which frames were redone because a device-side capacity was exceeded (dg_ctx_fallbacks)
     uint64_t redone_frames = 0;         // frames redone through the host list path, one at a time (dg_ctx_redone_frames)
     DevPtr<DevRSpan> d_redo_rspans;     // resolved spans of ONE frame being redone (allocated on first use)

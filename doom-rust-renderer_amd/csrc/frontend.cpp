@@ -143,21 +143,21 @@ struct Walker {
             for (size_t r = 0; r < lfx->recs.size(); r++) A.light_row[lfx->recs[r].sector] = lfx->level(r, v.timestamp);
         if (mfx)
             for (uint32_t i : mfx->driven) A.mobj_row[i] = mfx->value(i, v.timestamp);
-        if (poses && !resolve_view_poses(sc, *poses, A.pose_of, A.poses)) { status = DG_ERR_INVALID; err = "view poses: map object index out of range"; }
+        if (poses && !resolve_view_poses(sc, *poses, A.poses)) { status = DG_ERR_INVALID; err = "view poses: map object index out of range"; }
         if (vs) {                                                    // the scene's heights with the view's entries on top, a row of this frame alone
-            const unsigned bad = resolve_view_sectors(sc, *vs, A.height_of, A.heights);
+            const unsigned bad = resolve_view_sectors(sc, *vs, A.heights);
             A.height_row.assign(sc.fs_heights.begin(), sc.fs_heights.end());
-            for (const dg_sector_heights &h : A.heights) sector_row_place(A.height_row.data(), h.sector, h.floor_height, h.ceiling_height);
-            release_view_sectors(A.height_of, A.heights);
+            for (const dg_sector_heights &h : A.heights.out) sector_row_place(A.height_row.data(), h.sector, h.floor_height, h.ceiling_height);
+            A.heights.release();
             hrow = A.height_row.data();
             if (bad) { status = DG_ERR_INVALID; err = view_sectors_error(bad); }
         }
         if (vf) {                                                    // likewise the flats, and the sorted sidedef entries fs_seg searches
-            const unsigned bad = resolve_view_surfaces(sc, fx, *vf, 0, A.side_of, A.sides, A.flat_of, A.flats);
+            const unsigned bad = resolve_view_surfaces(sc, fx, *vf, 0, A.sides, A.flats);
             A.flat_row.assign(sc.fs_flats.begin(), sc.fs_flats.end());
-            for (const FlatEntry &e : A.flats) flat_row_place(A.flat_row.data(), e.sector, e.flats);
+            for (const FlatEntry &e : A.flats.out) flat_row_place(A.flat_row.data(), e.sector, e.flats);
             if (!hrow) { A.height_row.assign(sc.fs_heights.begin(), sc.fs_heights.end()); hrow = A.height_row.data(); }   // (surfaces read heights through the row, as on the device)
-            sf = FsViewSurfaces{A.flat_row.data(), A.sides.data(), (uint32_t)A.sides.size(), sc.fs_seg_side.data()};
+            sf = FsViewSurfaces{A.flat_row.data(), A.sides.out.data(), (uint32_t)A.sides.out.size(), sc.fs_seg_side.data()};
             has_sf = true;
             if (bad) { status = DG_ERR_INVALID; err = view_surfaces_error(bad); }
         }
@@ -171,14 +171,14 @@ struct Walker {
         if (mfx)
             for (uint32_t i : mfx->driven) A.mobj_row[i] = kNoOverride;
         if (state) apply_view_state(sc, *state, [&](size_t i, int32_t) { A.light_row[i] = kNoOverride; }, [&](size_t i, int32_t) { A.mobj_row[i] = kNoOverride; });
-        if (poses) release_view_poses(A.pose_of, A.poses);
+        if (poses) A.poses.release();
     }
     // MapObject.position / .angle and get_sector_from_vertex(position) as draw_map_objects reads them for this frame
     // (renderer/map_objects.rs:55,74,99-116): the view's pose if it has one for the object, else the scene's row.
     FsMobj mobj_placed(size_t i) const {
-        const int32_t at = poses ? A.pose_of[i] : -1;
+        const int32_t at = poses ? A.poses.of[i] : -1;
         if (at < 0) return sc.fs_mobjs[i];
-        const dg_mobj_pose &p = A.poses[(size_t)at];
+        const dg_mobj_pose &p = A.poses.out[(size_t)at];
         return FsMobj{p.x, p.y, p.angle, sc.sector_from_vertex(p.x, p.y)};
     }
     int16_t sector_light(int sector) const {

@@ -17,10 +17,34 @@
 #include "../../include/doomgpu.h"
 #include "fe_dev.h"
 #include "scene.hpp"
-#include "sector_rows_core.h"
-#include "surface_rows_core.h"
+#include "view_rows_core.h"
 
 namespace dg {
+
+// A view's entries for the items of one scene table as they stand: of two entries for one index the later wins, at the place of the
+// first.  Index: the entry's member that names its item.  begin(n) starts a view over n items (the one before has been released),
+// put(value) takes an entry whose index has been checked, release() hands the index row back all -1 and leaves out as it is, in any
+// order — O(entries), so that an arena's row is never cleared whole.
+template <class T, int32_t T::*Index> struct LatestPerIndex {
+    std::vector<int32_t> of;        // per item: its entry in out, or -1
+    std::vector<T> out;             // one entry per item that has any, in the order of the items' first entries
+    void begin(size_t n_items) {
+        out.clear();
+        if (of.size() != n_items) of.assign(n_items, -1);
+    }
+    __attribute__((always_inline)) void put(const T &value) {        // (once per entry of a batch — millions: never a call of its own)
+        int32_t &at = of[(size_t)(value.*Index)];
+        if (at < 0) { at = (int32_t)out.size(); out.push_back(value); }
+        else out[(size_t)at] = value;
+    }
+    void release() {
+        for (const T &value : out) of[(size_t)(value.*Index)] = -1;
+    }
+};
+using LatestPoses = LatestPerIndex<dg_mobj_pose, &dg_mobj_pose::mobj>;
+using LatestHeights = LatestPerIndex<dg_sector_heights, &dg_sector_heights::sector>;
+using LatestSides = LatestPerIndex<FsSideEntry, &FsSideEntry::sidedef>;
+using LatestFlats = LatestPerIndex<FlatEntry, &FlatEntry::sector>;
 
 struct FrameConsts {   // src/renderer/constants.rs:3-17, evaluated in f32 exactly like the const items
     float ARC, GSW, GCFX, CFX, CFY;
@@ -53,19 +77,14 @@ struct FrameArena {
     // per sector / per map object: the value this view draws with (its snapshot entry, else the effect's value at its tics) or "no
     // override"; the Walker writes the entries of one frame and takes them back
     std::vector<int32_t> light_row, mobj_row;
-    // per map object: its entry in `poses`, the view's poses as they stand (resolve_view_poses), or -1; written and taken back likewise
-    std::vector<int32_t> pose_of;
-    std::vector<dg_mobj_pose> poses;
-    // per sector: its entry in `heights`, the view's sector entries as they stand (resolve_view_sectors), or -1, likewise; height_row:
-    // the heights one view is drawn with, [sector] — the scene's with those entries on top, written whole by every Walker that has entries
-    std::vector<int32_t> height_of;
-    std::vector<dg_sector_heights> heights;
+    // the view's poses (per map object), sector entries (per sector) and surface entries (per sidedef / per sector) as they stand
+    // (resolve_view_*); written and taken back likewise
+    LatestPoses poses;
+    LatestHeights heights;
+    LatestSides sides;
+    LatestFlats flats;
+    // the heights / flats one view is drawn with, [sector] — the scene's with those entries on top, written whole by every Walker that has entries
     std::vector<FsHeights> height_row;
-    // per sidedef / per sector: its entry in `sides` / `flats`, the view's surface entries as they stand (resolve_view_surfaces), or -1,
-    // likewise; flat_row: the flats one view is drawn with, [sector], written whole by every Walker that has surfaces
-    std::vector<int32_t> side_of, flat_of;
-    std::vector<FsSideEntry> sides;
-    std::vector<FlatEntry> flats;
     std::vector<FsFlats> flat_row;
     FrameArena();
     ~FrameArena();
@@ -104,46 +123,34 @@ unsigned apply_view_state(const Scene &sc, const dg_view_state &st, LightFn ligh
 }
 
 // A view's poses as they stand: every entry is checked against the scene's range, and of two entries for one object the later wins.
-// out: one entry per moved object, in the order of the objects' first entries; pose_of[object]: its place in out, else -1.  pose_of
-// must come in all -1 (or empty) and is handed back so by release_view_poses.  Returns false when an object index was out of range
-// (the entries that are in range still stand).  The host walker, build_batch_fs (context.cpp) and dg_slot_mobj_poses all go through it.
-inline bool resolve_view_poses(const Scene &sc, const dg_view_poses &vp, std::vector<int32_t> &pose_of, std::vector<dg_mobj_pose> &out) {
-    out.clear();
-    if (pose_of.size() != sc.mobjs.size()) pose_of.assign(sc.mobjs.size(), -1);
+// poses.out: one entry per moved object, in the order of the objects' first entries; poses.of[object]: its place there, else -1,
+// until the caller's poses.release().  Returns false when an object index was out of range (the entries that are in range still
+// stand).  The host walker, build_batch_fs (context.cpp) and dg_slot_mobj_poses all go through it.
+inline bool resolve_view_poses(const Scene &sc, const dg_view_poses &vp, LatestPoses &poses) {
+    poses.begin(sc.mobjs.size());
     bool ok = true;
     for (uint32_t i = 0; i < vp.n; i++) {
         const dg_mobj_pose &p = vp.poses[i];
         if (p.mobj < 0 || (size_t)p.mobj >= sc.mobjs.size()) { ok = false; continue; }
-        int32_t &at = pose_of[(size_t)p.mobj];
-        if (at < 0) { at = (int32_t)out.size(); out.push_back(p); }
-        else out[(size_t)at] = p;
+        poses.put(p);
     }
     return ok;
 }
-inline void release_view_poses(std::vector<int32_t> &pose_of, const std::vector<dg_mobj_pose> &out) {
-    for (const dg_mobj_pose &p : out) pose_of[(size_t)p.mobj] = -1;
-}
 
-// A view's sector heights as they stand, by the same rules: of two entries for one sector the later wins; out holds one entry per
-// sector in the order of the sectors' first entries, height_of[sector] its place in out, else -1 (in all -1 or empty, handed back so by
-// release_view_sectors).  Returns 0, or bit 0: a sector index out of range, bit 1: a height outside int16 (the other entries still
+// A view's sector heights as they stand, by the same rules: of two entries for one sector the later wins; heights.out holds one entry
+// per sector in the order of the sectors' first entries, heights.of[sector] its place there, else -1, until the caller's
+// heights.release().  Returns 0, or bit 0: a sector index out of range, bit 1: a height outside int16 (the other entries still
 // stand).  The host walker, build_batch_fs (context.cpp) and dg_slot_sector_heights all go through it.
-inline unsigned resolve_view_sectors(const Scene &sc, const dg_view_sectors &vs, std::vector<int32_t> &height_of, std::vector<dg_sector_heights> &out) {
-    out.clear();
-    if (height_of.size() != sc.sectors.size()) height_of.assign(sc.sectors.size(), -1);
+inline unsigned resolve_view_sectors(const Scene &sc, const dg_view_sectors &vs, LatestHeights &heights) {
+    heights.begin(sc.sectors.size());
     unsigned bad = 0;
     for (uint32_t i = 0; i < vs.n; i++) {
         const dg_sector_heights &h = vs.heights[i];
         if (h.sector < 0 || (size_t)h.sector >= sc.sectors.size()) { bad |= 1u; continue; }
         if (h.floor_height < -32768 || h.floor_height > 32767 || h.ceiling_height < -32768 || h.ceiling_height > 32767) { bad |= 2u; continue; }
-        int32_t &at = height_of[(size_t)h.sector];
-        if (at < 0) { at = (int32_t)out.size(); out.push_back(h); }
-        else out[(size_t)at] = h;
+        heights.put(h);
     }
     return bad;
-}
-inline void release_view_sectors(std::vector<int32_t> &height_of, const std::vector<dg_sector_heights> &out) {
-    for (const dg_sector_heights &h : out) height_of[(size_t)h.sector] = -1;
 }
 inline const char *view_sectors_error(unsigned bad) {
     return bad & 1u ? "view sectors: sector index out of range" : "view sectors: height outside int16";
@@ -152,15 +159,14 @@ inline const char *view_sectors_error(unsigned bad) {
 // A view's surfaces as they stand, by the same rules: of two entries for one sidedef or one sector the later wins.  sides holds one
 // FsSideEntry per sidedef, sorted by sidedef — the span fs_side_find searches — each texture with the live wall animation list it
 // belongs to (wall: the effects drawn with, or nullptr); flats one FlatEntry per sector, sorted by sector, tagged with `frame`.
-// side_of / flat_of are the scratch of the de-duplication ([sidedef] / [sector], all -1 or empty before and after).  Returns 0, or
+// Both are released here (sides.of / flats.of all -1 before and after): the callers read sides.out and flats.out alone.  Returns 0, or
 // bit 0: a sidedef index out of range, bit 1: a texture id that is neither DG_TEX_NONE nor a wall texture of the scene, bit 2: an offset
 // outside int16, bit 3: a sector index out of range, bit 4: a flat handle not of this scene, bit 5: a null array with n > 0 (the other
 // entries still stand).  The host walker, build_batch_fs (context.cpp) and dg_slot_sector_flats all go through it.
-inline unsigned resolve_view_surfaces(const Scene &sc, const WallFx *wall, const dg_view_surfaces &vs, int32_t frame, std::vector<int32_t> &side_of,
-                                      std::vector<FsSideEntry> &sides, std::vector<int32_t> &flat_of, std::vector<FlatEntry> &flats) {
-    sides.clear(); flats.clear();
-    if (side_of.size() != sc.sidedefs.size()) side_of.assign(sc.sidedefs.size(), -1);
-    if (flat_of.size() != sc.sectors.size()) flat_of.assign(sc.sectors.size(), -1);
+inline unsigned resolve_view_surfaces(const Scene &sc, const WallFx *wall, const dg_view_surfaces &vs, int32_t frame, LatestSides &sides,
+                                      LatestFlats &flats) {
+    sides.begin(sc.sidedefs.size());
+    flats.begin(sc.sectors.size());
     unsigned bad = 0;
     if ((vs.n_sides && !vs.sides) || (vs.n_flats && !vs.flats)) return 32u;
     const auto list_of = [&](int32_t tex) -> int8_t {
@@ -178,23 +184,18 @@ inline unsigned resolve_view_surfaces(const Scene &sc, const WallFx *wall, const
         if (!tex_ok) { bad |= 2u; continue; }
         if (e.x_offset < -32768 || e.x_offset > 32767 || e.y_offset < -32768 || e.y_offset > 32767) { bad |= 4u; continue; }
         const FsSideEntry en{e.sidedef, e.tex_mid, e.tex_low, e.tex_up, list_of(e.tex_mid), list_of(e.tex_low), list_of(e.tex_up), 0, (int16_t)e.x_offset, (int16_t)e.y_offset};
-        int32_t &at = side_of[(size_t)e.sidedef];
-        if (at < 0) { at = (int32_t)sides.size(); sides.push_back(en); }
-        else sides[(size_t)at] = en;
+        sides.put(en);
     }
     for (uint32_t i = 0; i < vs.n_flats; i++) {
         const dg_sector_flats &e = vs.flats[i];
         if (e.sector < 0 || (size_t)e.sector >= sc.sectors.size()) { bad |= 8u; continue; }
         if (!sc.is_flat_handle(e.floor_flat) || !sc.is_flat_handle(e.ceil_flat)) { bad |= 16u; continue; }
-        const FlatEntry en{frame, e.sector, FsFlats{e.floor_flat, e.ceil_flat}};
-        int32_t &at = flat_of[(size_t)e.sector];
-        if (at < 0) { at = (int32_t)flats.size(); flats.push_back(en); }
-        else flats[(size_t)at] = en;
+        flats.put(FlatEntry{frame, e.sector, FsFlats{e.floor_flat, e.ceil_flat}});
     }
-    for (const FsSideEntry &e : sides) side_of[(size_t)e.sidedef] = -1;
-    for (const FlatEntry &e : flats) flat_of[(size_t)e.sector] = -1;
-    std::sort(sides.begin(), sides.end(), [](const FsSideEntry &a, const FsSideEntry &b) { return a.sidedef < b.sidedef; });
-    std::sort(flats.begin(), flats.end(), [](const FlatEntry &a, const FlatEntry &b) { return a.sector < b.sector; });
+    sides.release();
+    flats.release();
+    std::sort(sides.out.begin(), sides.out.end(), [](const FsSideEntry &a, const FsSideEntry &b) { return a.sidedef < b.sidedef; });
+    std::sort(flats.out.begin(), flats.out.end(), [](const FlatEntry &a, const FlatEntry &b) { return a.sector < b.sector; });
     return bad;
 }
 inline const char *view_surfaces_error(unsigned bad) {

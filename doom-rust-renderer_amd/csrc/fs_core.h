@@ -193,7 +193,7 @@ struct FsFx {
 
 // Where fs_seg / fs_mobj read a sector's floor and ceiling heights (Sector.floor_height / .ceiling_height, game state in the reference:
 // segs.rs:376-402,463-484, map_objects.rs:115).  FsOwnHeights: the scene table's own fields, the heights as loaded — the default, and what
-// every caller without per-view heights compiles to.  FsRowHeights: the view's row [sector] (dg_view_sectors, sector_rows_core.h).
+// every caller without per-view heights compiles to.  FsRowHeights: the view's row [sector] (dg_view_sectors, view_rows_core.h).
 // Both take the sector's record and its index, and hand back one height: stated so, the default reads exactly the field the caller
 // read before there was a policy.
 struct alignas(4) FsHeights { int16_t floor_h, ceil_h; };

@@ -1,4 +1,5 @@
-// fs_kernels.hpp — launch interface of the device seg walk (fs_kernels.hip, fs_fx_kernels.hip), and what the two files share.
+// fs_kernels.hpp — launch interface of the device seg walk (fs_kernels.hip, fs_fx_kernels.hip, and the pairs that read per-view rows:
+// fs_rows_kernels.hip, fs_surf_kernels.hip), and what the files share.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -12,6 +13,22 @@ namespace dg {
 hipError_t launch_fs(const FsParams &P, hipStream_t stream, hipEvent_t start = nullptr);
 // The same with the scene's wall effects (fs_fx_kernels.hip: dg_wfx_segs, dg_wfx_frame); X.fx has one entry per seg.
 hipError_t launch_fs_fx(const FsParams &P, const FsFx &X, hipStream_t stream, hipEvent_t start = nullptr);
+
+// The seg walk's second kernel argument when the batch has height rows: the rows [frame][stride], and with the wall effects their tables.
+struct FsRows { const FsHeights *rows; uint32_t stride; };
+struct FsRowsFx { FsFx fx; const FsHeights *rows; uint32_t stride; };
+// launch_fs / launch_fs_fx with the heights read from R.rows: dg_hts_segs, dg_hts_frame / dg_hts_wfx_segs, dg_hts_wfx_frame.
+hipError_t launch_fs_rows(const FsParams &P, const FsRows &R, hipStream_t stream, hipEvent_t start = nullptr);
+hipError_t launch_fs_rows_fx(const FsParams &P, const FsRowsFx &R, hipStream_t stream, hipEvent_t start = nullptr);
+
+// The seg walk's second kernel argument when the batch has surfaces: the height rows and the flat rows [frame][stride], the frames'
+// sidedef entries — frame f's are sides[first[f]] .. sides[first[f + 1]], sorted by sidedef — and the segs' front sidedefs; with the
+// wall effects their tables.
+struct FsSurf { const FsHeights *heights; const FsFlats *flats; uint32_t stride; const FsSideEntry *sides; const uint32_t *first; const int32_t *seg_side; };
+struct FsSurfFx { FsFx fx; FsSurf s; };
+// launch_fs / launch_fs_fx with heights, flats and sidedefs read through R: dg_sfc_segs, dg_sfc_frame / dg_sfc_wfx_segs, dg_sfc_wfx_frame.
+hipError_t launch_fs_surf(const FsParams &P, const FsSurf &R, hipStream_t stream, hipEvent_t start = nullptr);
+hipError_t launch_fs_surf_fx(const FsParams &P, const FsSurfFx &R, hipStream_t stream, hipEvent_t start = nullptr);
 
 }  // namespace dg
 

@@ -4,7 +4,6 @@
 // The phases and their order are fs_frame.h's, the launch fs_kernels.hpp's.  A translation unit of its own, and the rows in a second
 // kernel argument rather than in FsParams, so that a batch without sector entries runs kernels that never see them.
 #include "fs_kernels.hpp"
-#include "sector_rows_kernels.hpp"
 
 namespace dg {
 

@@ -6,7 +6,6 @@
 // fs_frame.h's, the launch fs_kernels.hpp's.  A translation unit of its own, and the tables in a second kernel argument rather than in
 // FsParams, so that a batch without surfaces runs kernels that never see them.
 #include "fs_kernels.hpp"
-#include "surface_rows_kernels.hpp"
 
 namespace dg {
 

@@ -150,8 +150,8 @@ struct Scene {
     std::vector<FsSeg> fs_segs;                     // one per seg
     std::vector<uint16_t> fs_seg_leaf;              // subsector of every seg
     std::vector<FsSector> fs_sectors;
-    std::vector<FsHeights> fs_heights;               // the sectors' heights as loaded, compact: what a view's height row starts as (sector_rows_core.h)
-    std::vector<FsFlats> fs_flats;                  // the sectors' flats as loaded, as handles: what a view's flat row starts as (surface_rows_core.h)
+    std::vector<FsHeights> fs_heights;               // the sectors' heights as loaded, compact: what a view's height row starts as (view_rows_core.h)
+    std::vector<FsFlats> fs_flats;                  // the sectors' flats as loaded, as handles: what a view's flat row starts as (view_rows_core.h)
     std::vector<int32_t> fs_seg_side;               // front sidedef of every seg (-1: none): what a view's sidedef entries are searched by
     std::vector<FsAnim> fs_anims;
     std::vector<FsBitmap> fs_bitmaps;

@@ -9,8 +9,7 @@
 #include <algorithm>
 
 #include "fs_frame.h"
-#include "sector_rows_core.h"
-#include "surface_rows_core.h"
+#include "view_rows_core.h"
 #include "walk_core.h"
 
 namespace dg {
@@ -160,31 +159,30 @@ inline FsScratchLayout fs_scratch_layout(size_t max_batch, uint32_t n_segs) {
     return L;
 }
 
-// Per-slot buffers of the per-view sector heights through the seg walk (sector_rows_core.h), sized by the scene at dg_upload_scene:
-// the rows [max_batch][n_sectors] the row kernels write and the seg walk reads, in HBM only, and the de-duplicated entries — at the
-// most one per cell — as pinned staging and as their HBM copy (two allocations of `entries` bytes: one H2D copy of what a batch has).
+// Per-slot buffers of one kind of per-view rows through the seg walk (view_rows_core.h), sized by the scene at dg_upload_scene: the
+// rows [max_batch][n_items] the row kernels write and the seg walk reads, in HBM only, and the de-duplicated entries — at the most
+// one per cell — as pinned staging and as their HBM copy (two allocations of `entries` bytes: one H2D copy of what a batch has).
 // cells is the capacity that follows: entries a batch can stage, and elements its rows hold.
-struct SectorRowLayout { size_t cells, rows, entries; };
-inline SectorRowLayout sector_row_layout(size_t max_batch, size_t n_sectors) {
-    SectorRowLayout L;
-    L.cells = max_batch * n_sectors;
-    L.rows = L.cells * sizeof(FsHeights);
-    L.entries = L.cells * sizeof(SectorEntry);
+struct ViewRowLayout { size_t cells, rows, entries; };
+template <class K> ViewRowLayout view_row_layout(size_t max_batch, size_t n_items) {
+    ViewRowLayout L;
+    L.cells = max_batch * n_items;
+    L.rows = L.cells * sizeof(typename K::Elem);
+    L.entries = L.cells * sizeof(typename K::Entry);
     return L;
 }
+using SectorRowLayout = ViewRowLayout;
+inline SectorRowLayout sector_row_layout(size_t max_batch, size_t n_sectors) { return view_row_layout<HeightRows>(max_batch, n_sectors); }
 
-// Per-slot buffers of the per-view surfaces through the seg walk (surface_rows_core.h, fs_core.h FsSideEntry), sized by the scene at
-// dg_upload_scene.  Flats: the rows [max_batch][n_sectors] in HBM only, and the de-duplicated entries — at the most one per cell — as
-// pinned staging and as their HBM copy, like SectorRowLayout.  Sidedefs: one table of `table` bytes, pinned and in HBM (one H2D copy of
-// what a batch has) — [0, first_bytes) the frames' offsets first[frame], max_batch + 1 of them, then the frames' sorted entries one
-// after the other, side_cap = kSideEntriesPerFrame x max_batch at the most: it does not grow with the map's sidedef count.
+// What the per-view surfaces add to their flat rows (view_row_layout<FlatRows>, whose three fields lead here), sized likewise.
+// Sidedefs (fs_core.h FsSideEntry): one table of `table` bytes, pinned and in HBM (one H2D copy of what a batch has) — [0, first_bytes)
+// the frames' offsets first[frame], max_batch + 1 of them, then the frames' sorted entries one after the other, side_cap =
+// kSideEntriesPerFrame x max_batch at the most: it does not grow with the map's sidedef count.
 constexpr size_t kSideEntriesPerFrame = 64;
-struct SurfaceLayout { size_t cells, rows, entries, side_cap, first_bytes, table; };
+struct SurfaceLayout : ViewRowLayout { size_t side_cap, first_bytes, table; };
 inline SurfaceLayout surface_layout(size_t max_batch, size_t n_sectors) {
     SurfaceLayout L;
-    L.cells = max_batch * n_sectors;
-    L.rows = L.cells * sizeof(FsFlats);
-    L.entries = L.cells * sizeof(FlatEntry);
+    static_cast<ViewRowLayout &>(L) = view_row_layout<FlatRows>(max_batch, n_sectors);
     L.side_cap = kSideEntriesPerFrame * max_batch;
     L.first_bytes = align_up((max_batch + 1) * sizeof(uint32_t), 16);
     L.table = L.first_bytes + L.side_cap * sizeof(FsSideEntry);

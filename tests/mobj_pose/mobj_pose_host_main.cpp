@@ -1,7 +1,7 @@
 // tests/mobj_pose/mobj_pose_host_main.cpp — the per-view map-object poses' host side as a stand-alone program, for a sanitizer build
 // (tests/test_mobj_pose_host.py builds it with -fsanitize=address,undefined together with the library's host sources and runs it).
 //   usage: mobj_pose_host_main <wad file> <camera path .f32> <map name>
-// mobj_pose_core.h's fill and place bodies run lane after lane, as the two kernels index them (256-lane groups, the last one partial),
+// view_rows_core.h's fill and scatter bodies run lane after lane for the pose kind (mobj_pose_core.h), as the two kernels index them (256-lane groups, the last one partial),
 // over batches and entry counts at the kernels' boundaries; every row is compared with Scene::sector_from_vertex.  Then the host walker
 // with poses through the C-ABI: the lists of dg_build_lists_poses against the rows.  It checks what it gets.
 #include <cmath>
@@ -103,21 +103,21 @@ int main(int argc, char **argv) {
             }
             std::vector<FsMobj> rows(cells, FsMobj{-1.0f, -1.0f, -1.0f, -7});
             PoseParams P{};
-            P.scene_rows = sc.fs_mobjs.data(); P.nodes = sc.walk_nodes.data(); P.leaf_sector = sc.walk_leaf_sector.data();
+            P.scene_rows = sc.fs_mobjs.data(); P.ctx.nodes = sc.walk_nodes.data(); P.ctx.leaf_sector = sc.walk_leaf_sector.data();
             P.entries = entries.data(); P.rows = rows.data();
-            P.root = (int32_t)sc.walk_nodes.size() - 1;
-            P.n_mobjs = n_mobjs; P.n_frames = n_frames; P.n_entries = n_entries;
+            P.ctx.root = (int32_t)sc.walk_nodes.size() - 1;
+            P.n_items = n_mobjs; P.n_frames = n_frames; P.n_entries = n_entries;
             for (uint32_t g = 0; g < (cells + 255u) / 256u; g++)              // dg_mobj_pose_fill
                 for (uint32_t t = 0; t < 256u; t++) {
                     const uint32_t idx = g * 256u + t;
-                    if (idx >= P.n_frames * P.n_mobjs) continue;
-                    pose_fill(P, idx);
+                    if (idx >= P.n_frames * P.n_items) continue;
+                    view_row_fill(P, idx);
                 }
             for (uint32_t g = 0; g < (n_entries + 255u) / 256u; g++)          // dg_mobj_pose_place
                 for (uint32_t t = 0; t < 256u; t++) {
                     const uint32_t e = g * 256u + t;
                     if (e >= P.n_entries) continue;
-                    pose_place(P, e);
+                    view_row_scatter(P, e);
                 }
             std::vector<int32_t> entry_of(cells, -1);
             for (uint32_t e = 0; e < n_entries; e++) {

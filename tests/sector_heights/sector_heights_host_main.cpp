@@ -2,7 +2,7 @@
 // build (tests/test_sector_heights_host.py builds it with -fsanitize=address,undefined together with the library's host sources and
 // runs it).
 //   usage: sector_heights_host_main <wad file> <camera path .f32> <map name>
-// resolve_view_sectors over duplicate, out-of-range and out-of-int16 entries; sector_rows_core.h's fill and scatter bodies lane after
+// resolve_view_sectors over duplicate, out-of-range and out-of-int16 entries; view_rows_core.h's fill and scatter bodies lane after
 // lane, as the two kernels index them (256-lane groups, the last one partial), over batches and entry counts at the kernels'
 // boundaries, every row compared with the entries applied in order; then the host walker with entries through the C-ABI.  It checks
 // what it gets.
@@ -15,8 +15,8 @@
 
 #include "../../doom-rust-renderer_amd/csrc/api_common.hpp"
 #include "../../doom-rust-renderer_amd/csrc/frontend.hpp"
-#include "../../doom-rust-renderer_amd/csrc/sector_rows_core.h"
 #include "../../doom-rust-renderer_amd/csrc/slab_layout.h"
+#include "../../doom-rust-renderer_amd/csrc/view_rows_core.h"
 
 using namespace dg;
 
@@ -51,18 +51,54 @@ int main(int argc, char **argv) {
     }
 
     // resolve_view_sectors: the later of two wins, bad entries are reported and left out, the index row is handed back clean
-    std::vector<int32_t> height_of;
-    std::vector<dg_sector_heights> stand;
+    LatestHeights latest;
+    std::vector<int32_t> &height_of = latest.of;
+    std::vector<dg_sector_heights> &stand = latest.out;
     {
         const dg_sector_heights in[] = {{3, 500, -300}, {0, 1, 2}, {3, 8, 8}, {(int32_t)n_sectors, 0, 0}, {-1, 0, 0}, {1, 32768, 0}, {1, 0, -32769}, {2, -32768, 32767}};
         const dg_view_sectors vs{in, 8};
-        CHECK(resolve_view_sectors(sc, vs, height_of, stand) == 3u);
+        CHECK(resolve_view_sectors(sc, vs, latest) == 3u);
         CHECK(stand.size() == 3 && stand[0].sector == 3 && stand[0].floor_height == 8 && stand[0].ceiling_height == 8 && stand[1].sector == 0 && stand[2].sector == 2);
         CHECK(height_of[3] == 0 && height_of[0] == 1 && height_of[2] == 2 && height_of[1] == -1);
-        release_view_sectors(height_of, stand);
+        latest.release();
         for (int32_t v : height_of) CHECK(v == -1);
         const dg_view_sectors none{nullptr, 0};
-        CHECK(resolve_view_sectors(sc, none, height_of, stand) == 0u && stand.empty());
+        CHECK(resolve_view_sectors(sc, none, latest) == 0u && stand.empty());
+    }
+
+    // LatestPerIndex, what the three resolve_view_* de-duplicate with: a repeated index keeps the place of its first entry and the
+    // value of its last, release() hands the index row back all -1 and leaves out alone, begin() with another item count re-sizes
+    {
+        struct Item { int32_t index; int value; };
+        LatestPerIndex<Item, &Item::index> l;
+        l.begin(5);
+        CHECK(l.of.size() == 5 && l.out.empty());
+        for (int32_t v : l.of) CHECK(v == -1);
+        for (const Item &it : {Item{4, 40}, Item{1, 10}, Item{4, 41}, Item{0, 7}, Item{1, 11}, Item{4, 42}}) l.put(it);
+        CHECK(l.out.size() == 3 && l.out[0].index == 4 && l.out[0].value == 42 && l.out[1].index == 1 && l.out[1].value == 11 && l.out[2].index == 0 && l.out[2].value == 7);
+        CHECK(l.of[4] == 0 && l.of[1] == 1 && l.of[0] == 2 && l.of[2] == -1 && l.of[3] == -1);
+        l.release();
+        for (int32_t v : l.of) CHECK(v == -1);
+        CHECK(l.of.size() == 5 && l.out.size() == 3 && l.out[0].value == 42);
+        l.release();                                                    // (a second one changes nothing)
+        for (int32_t v : l.of) CHECK(v == -1);
+        l.begin(5);
+        CHECK(l.out.empty() && l.of.size() == 5);
+        l.put(Item{4, 1});
+        CHECK(l.of[4] == 0 && l.out.size() == 1);                       // (the first place again, not the earlier view's)
+        l.release();
+        l.begin(9);
+        CHECK(l.of.size() == 9 && l.out.empty());
+        for (int32_t v : l.of) CHECK(v == -1);
+        l.put(Item{8, 80}); l.put(Item{8, 81}); l.put(Item{0, 1});
+        CHECK(l.of[8] == 0 && l.of[0] == 1 && l.out.size() == 2 && l.out[0].value == 81);
+        l.release();
+        for (int32_t v : l.of) CHECK(v == -1);
+        l.begin(2);
+        CHECK(l.of.size() == 2 && l.out.empty());
+        for (int32_t v : l.of) CHECK(v == -1);
+        l.begin(0);
+        CHECK(l.of.empty() && l.out.empty());
     }
 
     // the row bodies at the kernels' boundary counts
@@ -92,19 +128,19 @@ int main(int argc, char **argv) {
                 for (uint32_t s = 0; s < n_sectors; s++) want[fr * n_sectors + s] = sc.fs_heights[s];
                 for (const dg_sector_heights &g : given[fr]) want[fr * n_sectors + (uint32_t)g.sector] = FsHeights{(int16_t)g.floor_height, (int16_t)g.ceiling_height};
                 const dg_view_sectors vs{given[fr].data(), (uint32_t)given[fr].size()};
-                CHECK(resolve_view_sectors(sc, vs, height_of, stand) == 0u);
+                CHECK(resolve_view_sectors(sc, vs, latest) == 0u);
                 for (const dg_sector_heights &g : stand) { CHECK(n_staged < L.cells); staged[n_staged++] = SectorEntry{(int32_t)fr, g.sector, (int16_t)g.floor_height, (int16_t)g.ceiling_height}; }
-                release_view_sectors(height_of, stand);
+                latest.release();
             }
             CHECK(n_staged == n_entries);
             std::vector<FsHeights> rows(total, FsHeights{-1, -1});
             const SectorRowParams P{sc.fs_heights.data(), staged.data(), rows.data(), n_sectors, n_frames, n_staged};
             for (uint32_t b = 0; b < (total + 255u) / 256u; b++)
                 for (uint32_t t = 0; t < 256; t++)
-                    if (b * 256u + t < P.n_frames * P.n_sectors) sector_row_fill(P, b * 256u + t);
+                    if (b * 256u + t < P.n_frames * P.n_items) view_row_fill(P, b * 256u + t);
             for (uint32_t b = 0; b < (n_staged + 255u) / 256u; b++)
                 for (uint32_t t = 0; t < 256; t++)
-                    if (b * 256u + t < P.n_entries) sector_row_scatter(P, b * 256u + t);
+                    if (b * 256u + t < P.n_entries) view_row_scatter(P, b * 256u + t);
             CHECK(std::memcmp(rows.data(), want.data(), (size_t)total * sizeof(FsHeights)) == 0);
             cells_checked += total;
         }
@@ -113,7 +149,7 @@ int main(int argc, char **argv) {
         std::vector<FsHeights> rows(2 * n_sectors, FsHeights{7, 7});
         const SectorEntry bad[] = {{2, 0, 1, 1}, {-1, 0, 1, 1}, {0, (int32_t)n_sectors, 1, 1}, {0, -1, 1, 1}, {1, (int32_t)n_sectors - 1, 5, 6}};
         const SectorRowParams P{sc.fs_heights.data(), bad, rows.data(), n_sectors, 2, 5};
-        for (uint32_t e = 0; e < 5; e++) sector_row_scatter(P, e);
+        for (uint32_t e = 0; e < 5; e++) view_row_scatter(P, e);
         for (uint32_t i = 0; i + 1 < 2 * n_sectors; i++) CHECK(rows[i].floor_h == 7 && rows[i].ceil_h == 7);
         CHECK(rows[2 * n_sectors - 1].floor_h == 5 && rows[2 * n_sectors - 1].ceil_h == 6);
     }

@@ -1,7 +1,7 @@
 // tests/surfaces/surfaces_host_main.cpp — the per-view surfaces' host side as a stand-alone program, for a sanitizer build
 // (tests/test_surfaces_host.py builds it with -fsanitize=address,undefined together with the library's host sources and runs it).
 //   usage: surfaces_host_main <wad file> <camera path .f32> <map name>
-// resolve_view_surfaces over duplicate and invalid entries; surface_rows_core.h's fill and scatter bodies lane after lane, as the two
+// resolve_view_surfaces over duplicate and invalid entries; view_rows_core.h's fill and scatter bodies lane after lane, as the two
 // kernels index them (256-lane groups, the last one partial), over batches and entry counts at the kernels' boundaries; fs_side_find
 // over 0, 1, 2 and 257 entries with hits at both ends and misses below, between and above; the side table laid out as build_batch_fs
 // stages it; then the host walker with entries through the C-ABI.  It checks what it gets.
@@ -15,7 +15,7 @@
 #include "../../doom-rust-renderer_amd/csrc/api_common.hpp"
 #include "../../doom-rust-renderer_amd/csrc/frontend.hpp"
 #include "../../doom-rust-renderer_amd/csrc/slab_layout.h"
-#include "../../doom-rust-renderer_amd/csrc/surface_rows_core.h"
+#include "../../doom-rust-renderer_amd/csrc/view_rows_core.h"
 
 using namespace dg;
 
@@ -54,24 +54,26 @@ int main(int argc, char **argv) {
     }
 
     // resolve_view_surfaces: the later of two wins, bad entries are reported and left out, the output is sorted, the scratch handed back clean
-    std::vector<int32_t> side_of, flat_of;
-    std::vector<FsSideEntry> sides;
-    std::vector<FlatEntry> flats;
+    LatestSides latest_sides;
+    LatestFlats latest_flats;
+    std::vector<int32_t> &side_of = latest_sides.of, &flat_of = latest_flats.of;
+    std::vector<FsSideEntry> &sides = latest_sides.out;
+    std::vector<FlatEntry> &flats = latest_flats.out;
     {
         const dg_side_surface in[] = {{5, t_wide, t_wide, t_wide, 99, -99}, {2, t_brick, -1, t_grate, 1, 2}, {5, t_brick, t_brick, -1, -32768, 32767}, {(int32_t)n_sides, -1, -1, -1, 0, 0},
                                       {-1, -1, -1, -1, 0, 0}, {1, -2, -1, -1, 0, 0}, {1, -1, 1 << 24, -1, 0, 0}, {1, -1, -1, -1, 32768, 0}, {1, -1, -1, -1, 0, -32769}, {0, -1, -1, -1, 0, 0}};
         const dg_sector_flats fin[] = {{3, f_sky, f_sky}, {0, f_floor, f_nuk}, {3, f_nuk, f_floor}, {(int32_t)n_sectors, f_floor, f_floor}, {-1, f_floor, f_floor}, {1, -1, f_floor},
                                        {1, f_floor, FS_FLAT_MISSING}, {1, f_floor | FS_FLAT_SKY, f_floor}, {1, FS_FLAT_ANIM | 100000, f_floor}};
         const dg_view_surfaces vs{in, 10, fin, 9};
-        CHECK(resolve_view_surfaces(sc, nullptr, vs, 7, side_of, sides, flat_of, flats) == (1u | 2u | 4u | 8u | 16u));
+        CHECK(resolve_view_surfaces(sc, nullptr, vs, 7, latest_sides, latest_flats) == (1u | 2u | 4u | 8u | 16u));
         CHECK(sides.size() == 3 && sides[0].sidedef == 0 && sides[1].sidedef == 2 && sides[2].sidedef == 5 && sides[2].tex_mid == t_brick && sides[2].tex_up == -1 &&
               sides[2].x_offset == -32768 && sides[2].y_offset == 32767 && sides[1].anim_mid == -1);
         CHECK(flats.size() == 2 && flats[0].sector == 0 && flats[1].sector == 3 && flats[1].flats.floor == f_nuk && flats[1].flats.ceil == f_floor && flats[0].frame == 7);
         for (int32_t v : side_of) CHECK(v == -1);
         for (int32_t v : flat_of) CHECK(v == -1);
         const dg_view_surfaces none{nullptr, 0, nullptr, 0}, null_sides{nullptr, 2, nullptr, 0}, null_flats{nullptr, 0, nullptr, 1};
-        CHECK(resolve_view_surfaces(sc, nullptr, none, 0, side_of, sides, flat_of, flats) == 0u && sides.empty() && flats.empty());
-        CHECK(resolve_view_surfaces(sc, nullptr, null_sides, 0, side_of, sides, flat_of, flats) == 32u && resolve_view_surfaces(sc, nullptr, null_flats, 0, side_of, sides, flat_of, flats) == 32u);
+        CHECK(resolve_view_surfaces(sc, nullptr, none, 0, latest_sides, latest_flats) == 0u && sides.empty() && flats.empty());
+        CHECK(resolve_view_surfaces(sc, nullptr, null_sides, 0, latest_sides, latest_flats) == 32u && resolve_view_surfaces(sc, nullptr, null_flats, 0, latest_sides, latest_flats) == 32u);
     }
 
     // the search: 0, 1, 2 and 257 entries; hits at both ends, misses below, between and above
@@ -107,7 +109,7 @@ int main(int argc, char **argv) {
                 given[fr].push_back(dg_side_surface{sd, t_wide, t_brick, t_grate, (int32_t)(fr * 100 + k), -(int32_t)k});
             }
             const dg_view_surfaces vs{given[fr].data(), (uint32_t)given[fr].size(), nullptr, 0};
-            CHECK(resolve_view_surfaces(sc, nullptr, vs, (int32_t)fr, side_of, sides, flat_of, flats) == 0u);
+            CHECK(resolve_view_surfaces(sc, nullptr, vs, (int32_t)fr, latest_sides, latest_flats) == 0u);
             CHECK(staged + sides.size() <= L.side_cap);
             first[fr] = staged;
             for (const FsSideEntry &e : sides) se[staged++] = e;
@@ -163,7 +165,7 @@ int main(int argc, char **argv) {
                 for (uint32_t s = 0; s < n_sectors; s++) want[fr * n_sectors + s] = sc.fs_flats[s];
                 for (const dg_sector_flats &g : given[fr]) want[fr * n_sectors + (uint32_t)g.sector] = FsFlats{g.floor_flat, g.ceil_flat};
                 const dg_view_surfaces vs{nullptr, 0, given[fr].data(), (uint32_t)given[fr].size()};
-                CHECK(resolve_view_surfaces(sc, nullptr, vs, (int32_t)fr, side_of, sides, flat_of, flats) == 0u);
+                CHECK(resolve_view_surfaces(sc, nullptr, vs, (int32_t)fr, latest_sides, latest_flats) == 0u);
                 for (const FlatEntry &g : flats) { CHECK(n_staged < L.cells); staged[n_staged++] = g; }
             }
             CHECK(n_staged == n_entries);
@@ -171,10 +173,10 @@ int main(int argc, char **argv) {
             const FlatRowParams P{sc.fs_flats.data(), staged.data(), rows.data(), n_sectors, n_frames, n_staged};
             for (uint32_t b = 0; b < (total + 255u) / 256u; b++)
                 for (uint32_t t = 0; t < 256; t++)
-                    if (b * 256u + t < P.n_frames * P.n_sectors) flat_row_fill(P, b * 256u + t);
+                    if (b * 256u + t < P.n_frames * P.n_items) view_row_fill(P, b * 256u + t);
             for (uint32_t b = 0; b < (n_staged + 255u) / 256u; b++)
                 for (uint32_t t = 0; t < 256; t++)
-                    if (b * 256u + t < P.n_entries) flat_row_scatter(P, b * 256u + t);
+                    if (b * 256u + t < P.n_entries) view_row_scatter(P, b * 256u + t);
             CHECK(std::memcmp(rows.data(), want.data(), (size_t)total * sizeof(FsFlats)) == 0);
             cells_checked += total;
         }
@@ -183,7 +185,7 @@ int main(int argc, char **argv) {
         std::vector<FsFlats> rows(2 * n_sectors, FsFlats{7, 7});
         const FlatEntry bad[] = {{2, 0, {1, 1}}, {-1, 0, {1, 1}}, {0, (int32_t)n_sectors, {1, 1}}, {0, -1, {1, 1}}, {1, (int32_t)n_sectors - 1, {5, 6}}};
         const FlatRowParams P{sc.fs_flats.data(), bad, rows.data(), n_sectors, 2, 5};
-        for (uint32_t e = 0; e < 5; e++) flat_row_scatter(P, e);
+        for (uint32_t e = 0; e < 5; e++) view_row_scatter(P, e);
         for (uint32_t i = 0; i + 1 < 2 * n_sectors; i++) CHECK(rows[i].floor == 7 && rows[i].ceil == 7);
         CHECK(rows[2 * n_sectors - 1].floor == 5 && rows[2 * n_sectors - 1].ceil == 6);
     }

@@ -1,5 +1,5 @@
 """Per-view map-object poses on the CPU (include/doomgpu.h: dg_view_poses): the host walker with poses, the host-only
-calls, and the shared fill / place bodies of mobj_pose_core.h.  Everything is byte-exact.
+calls, and the shared fill / scatter bodies of view_rows_core.h for the pose kind (mobj_pose_core.h).  Everything is byte-exact.
 
   oracle          dg_build_lists_poses -> the emulator's list rasteriser equals the oracle's frame of the WAD whose THINGS records were
                   patched to the same poses (tests/mobj_pose_cases.py): one object, all objects, across a floor step, into another light,
@@ -217,7 +217,7 @@ def test_argument_errors(dg, world):
 
 def test_the_pose_bodies_as_a_stand_alone_program_under_sanitizers(tmp_path, wad1993):
     """tests/mobj_pose/mobj_pose_host_main.cpp (its own main) with the host sources of the library, built with
-    -fsanitize=address,undefined and run as a program: mobj_pose_core.h's fill and place bodies lane after lane at the kernels' boundary
+    -fsanitize=address,undefined and run as a program: view_rows_core.h's fill and scatter bodies for the pose kind lane after lane at the kernels' boundary
     counts against Scene::sector_from_vertex, then the host walker with poses.  It checks its own results; any sanitizer report fails it."""
     csrc = os.path.join(ROOT, "doom-rust-renderer_amd", "csrc")
     exe = tmp_path / "mobj_pose_host_main"

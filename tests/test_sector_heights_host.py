@@ -210,7 +210,7 @@ def test_the_binding_and_the_header_carry_the_sector_height_entry_points(dg):
 
 def test_the_row_bodies_as_a_stand_alone_program_under_sanitizers(tmp_path, wad1993):
     """tests/sector_heights/sector_heights_host_main.cpp (its own main) with the host sources of the library, built with
-    -fsanitize=address,undefined and run as a program: resolve_view_sectors, sector_rows_core.h's fill and scatter bodies lane after lane
+    -fsanitize=address,undefined and run as a program: resolve_view_sectors, LatestPerIndex, view_rows_core.h's fill and scatter bodies lane after lane
     at the kernels' boundary counts, then build_frame_lists with entries.  It checks its own results; any sanitizer report fails it."""
     csrc = os.path.join(ROOT, "doom-rust-renderer_amd", "csrc")
     exe = tmp_path / "sector_heights_host_main"

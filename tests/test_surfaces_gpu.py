@@ -130,6 +130,78 @@ def test_the_rows_the_flat_row_kernels_write(dg, scene, names, path1993, n_frame
     ctx.close()
 
 
+@pytest.mark.parametrize("n_frames", [1, 65])
+def test_all_three_row_kinds_in_one_batch(dg, scene, names, wad, path1993, n_frames):
+    """Poses, sector entries and surfaces in ONE seg-walk batch: the three kinds of per-view rows share one launch
+    sequence and one start-event rule.  Each kind's rows equal its own expected-row builder byte for byte, each kind's kernels have a
+    time, and the frames are the host walker's of the same batch; a batch without per-view inputs on the same slot then runs none of
+    them, reads the scene's rows and is the host walker's again."""
+    W, H = 131, 67
+    n_mobjs = scene.mobj_count()
+    rng = np.random.default_rng(8 + n_frames)
+    poses_of = mp.batch_cases(scene, wad, path1993, n_frames)
+    dense = sc.random_cases(wad, n_frames, seed=77 + n_frames)
+    cases = []
+    for k in range(n_frames):
+        f = poses_of[k].frame
+        sides = dense[k].sides
+        sides = [sides[(j * len(sides)) // 64] for j in range(64)] if len(sides) > 64 else sides       # (the side table holds 64 per frame)
+        cases.append(sc.Case(f"all{k}", f, sides, dense[k].flats, heights=sh.random_row(wad, rng, "jitter"), poses=poses_of[k].entries,
+                             timestamp=float(np.float32(0.25 * (k % 5)))))
+    vf, keep0 = dg.make_view_surfaces([c.surfaces(names) for c in cases])
+    vs, keep1 = dg.make_view_sectors([c.heights for c in cases])
+    vp, keep2 = dg.make_view_poses([mp.entries_as_poses(c.poses) for c in cases])
+    views = dg.make_views(np.stack([c.record(path1993)[:8] for c in cases]))
+    for i, c in enumerate(cases):
+        views[i].timestamp = c.timestamp
+    base_poses = scene.mobj_poses()
+    want_poses = np.tile(base_poses, (n_frames, 1))
+    for k, c in enumerate(cases):
+        for m, (x, y, deg) in mp.resolved(c.poses).items():
+            px, py, ang = mp.pose(x, y, deg)
+            want_poses[k, m] = (px, py, ang, int(scene.sectors_at([px], [py])[0]))
+    want_heights = sh.expected_rows(wad, [sh.Case("", 0, c.heights) for c in cases])
+    want_flats = sc.expected_flat_rows(scene, names, cases)
+    base_heights, base_flats = sh.loaded_heights(wad), scene.sector_flats()[:, 1:]
+
+    def bits(rows):
+        return np.ascontiguousarray(rows).view(np.uint8)
+    host = dg.Context(W, H, max_batch=65, slots=1, front_end=dg_fe(dg, 1))
+    host.upload_scene(scene)
+    host.submit_surfaces(0, views, vf, poses=vp, sectors=vs)
+    host_sums = host.frame_checksums(0, 0, n_frames)
+    host.submit_surfaces(0, views, None)
+    host_plain = host.frame_checksums(0, 0, n_frames)
+    host.close()
+    assert not np.array_equal(host_sums, host_plain)
+
+    ctx = dg.Context(W, H, max_batch=65, slots=1, front_end=dg_fe(dg, 3))
+    ctx.upload_scene(scene)
+    before = ctx.fallbacks()
+    ctx.submit_surfaces(0, views, vf, poses=vp, sectors=vs)
+    got_poses = ctx.slot_mobj_poses(0, 0, n_frames)
+    assert got_poses.shape == (n_frames, n_mobjs) and np.array_equal(bits(got_poses), bits(want_poses))
+    assert np.array_equal(bits(ctx.slot_sector_heights(0, 0, n_frames)), bits(want_heights))
+    assert np.array_equal(bits(ctx.slot_sector_flats(0, 0, n_frames)), bits(want_flats))
+    assert not np.array_equal(bits(want_poses), bits(np.tile(base_poses, (n_frames, 1)))) and not np.array_equal(want_heights[0], base_heights)
+    assert not np.array_equal(want_flats[0], base_flats)
+    assert ctx.timing(0)["front_end"] == dg.DG_FE_DEVICE_SEGS and ctx.fallbacks() == before
+    times = (ctx.mobj_pose_timing(0), ctx.sector_height_timing(0), ctx.surface_timing(0))
+    print("all three kinds:", n_frames, "pose / height / flat kernels ms", times)
+    assert all(np.isfinite(t) and t >= 0.0 for t in times), times
+    assert np.array_equal(ctx.frame_checksums(0, 0, n_frames), host_sums)
+    # the same slot without per-view inputs: none of the six kernels, the scene's rows, the plain frames
+    ctx.submit_surfaces(0, views, None)
+    assert (ctx.mobj_pose_timing(0), ctx.sector_height_timing(0), ctx.surface_timing(0)) == (0.0, 0.0, 0.0)
+    assert np.array_equal(bits(ctx.slot_mobj_poses(0, 0, n_frames)), bits(np.tile(base_poses, (n_frames, 1))))
+    assert np.array_equal(ctx.slot_sector_heights(0, 0, n_frames), np.repeat(base_heights[None], n_frames, axis=0))
+    assert np.array_equal(ctx.slot_sector_flats(0, 0, n_frames), np.repeat(base_flats[None], n_frames, axis=0))
+    assert ctx.timing(0)["front_end"] == dg.DG_FE_DEVICE_SEGS and ctx.fallbacks() == before
+    assert np.array_equal(ctx.frame_checksums(0, 0, n_frames), host_plain)
+    ctx.close()
+    del keep0, keep1, keep2
+
+
 def test_the_side_table_at_its_shapes_and_its_capacity(dg, scene, names, wad, path1993, pixel_batch):
     """The reference is the host front end of the same scene and entries (equal to the oracle on the CPU tier and in the pixel tests)."""
     W, H = 131, 67

@@ -282,7 +282,7 @@ def test_the_binding_and_the_header_carry_the_surface_entry_points(dg):
 
 def test_the_shared_bodies_as_a_stand_alone_program_under_sanitizers(tmp_path, wad1993):
     """tests/surfaces/surfaces_host_main.cpp (its own main) with the host sources of the library, built with
-    -fsanitize=address,undefined and run as a program: resolve_view_surfaces, surface_rows_core.h's fill and scatter bodies lane after
+    -fsanitize=address,undefined and run as a program: resolve_view_surfaces, view_rows_core.h's fill and scatter bodies lane after
     lane at the kernels' boundary counts, fs_side_find with 0, 1, 2 and 257 entries, then build_frame_lists with entries.  It checks its
     own results; any sanitizer report fails it."""
     csrc = os.path.join(ROOT, "doom-rust-renderer_amd", "csrc")

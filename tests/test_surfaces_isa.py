@@ -1,12 +1,13 @@
 """CPU tier ISA checks of the per-view surfaces: the surface-reading variants of the device seg walk
 (fs_surf_kernels.hip) keep the budgets test_isa_checks.py / test_wall_fx_isa.py hold the existing pairs to (segs: no LDS, <= 16 B
 scratch; frame: <= 40.5 KB LDS for four workgroups per CU, <= 160 B scratch; both <= 128 VGPRs), the two flat row kernels
-(surface_rows_kernels.hip) use no LDS and no scratch, the new frame kernels run fs_frame.h's one phase sequence, and the files that
+(view_rows_kernels.hip) use no LDS and no scratch, the new frame kernels run fs_frame.h's one phase sequence, and the files that
 existed before are not touched by the new policy."""
 import os
 import re
 
 from test_isa_checks import CSRC
+from test_sector_heights_isa import VIEW_ROW_KERNELS, view_row_kernels
 from test_wall_fx_isa import _body, _calls, _kernels
 
 
@@ -23,13 +24,10 @@ def test_surface_reading_pairs_keep_the_seg_walk_budgets():
 
 
 def test_flat_row_kernels_use_no_lds_and_no_scratch():
-    ks = _kernels("surface_rows_kernels.hip")
-    assert len(ks) == 2, list(ks)
+    ks = view_row_kernels()
     for kernel in ("dg_flat_row_fill", "dg_flat_row_scatter"):
-        hits = [(n, v) for n, v in ks.items() if kernel in n]
-        assert len(hits) == 1, (kernel, list(ks))
-        name, (lds, scratch, vgpr) = hits[0]
-        assert lds == 0 and scratch == 0 and vgpr <= 32, (name, lds, scratch, vgpr)
+        lds, scratch, vgpr = ks[kernel]
+        assert lds == 0 and scratch == 0 and vgpr <= VIEW_ROW_KERNELS[kernel], (kernel, lds, scratch, vgpr)
 
 
 def test_surface_reading_frame_kernels_run_the_one_phase_sequence():
@@ -48,8 +46,8 @@ def test_the_default_surfaces_policy_reads_the_scene_tables():
     files are untouched by it, and the kernel counts of the files that hold the row-reading pairs and the height row kernels stand."""
     for name in ("fs_kernels.hip", "fs_fx_kernels.hip", "fs_rows_kernels.hip"):
         txt = open(os.path.join(CSRC, name)).read()
-        assert "Surfaces" not in txt and "FsSurf" not in txt and "surface_rows" not in txt, name
-    assert len(_kernels("fs_rows_kernels.hip")) == 4 and len(_kernels("sector_rows_kernels.hip")) == 2
+        assert "Surfaces" not in txt and "FsSurf" not in txt and "surface_rows" not in txt and "view_rows" not in txt, name
+    assert len(_kernels("fs_rows_kernels.hip")) == 4 and len(view_row_kernels()) == 6
     core = open(os.path.join(CSRC, "fs_core.h")).read()
     assert "typename Ht = FsOwnHeights" in core and "const Ht &ht = Ht()" in core
     assert "typename Sf = FsOwnSurfaces" in core and "const Sf &sf = Sf()" in core
