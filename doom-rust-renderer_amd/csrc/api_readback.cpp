@@ -382,7 +382,7 @@ int dg_slot_mobj_poses(dg_ctx *c, int slot, int first, int count, dg_mobj_placed
     static_assert(sizeof(dg_mobj_placed) == sizeof(FsMobj) && offsetof(dg_mobj_placed, sector) == offsetof(FsMobj, sector), "dg_mobj_placed / FsMobj");
     return slot_rows<PoseRows>(c, slot, first, count, reinterpret_cast<FsMobj *>(out), "dg_slot_mobj_poses", &Slot::pose_run, &Scene::fs_mobjs,
                                [](const Scene &sc, const Slot &s, FrameArena &A, int frame, FsMobj *row) {      // (Walker::mobj_placed)
-                                   const dg_view_poses *vp = s.poses_of(frame);
+                                   const dg_view_poses *vp = s.kept.at(frame).poses;
                                    if (!vp) return;
                                    (void)resolve_view_poses(sc, *vp, A.poses);
                                    for (const dg_mobj_pose &p : A.poses.out) row[p.mobj] = FsMobj{p.x, p.y, p.angle, sc.sector_from_vertex(p.x, p.y)};
@@ -393,7 +393,7 @@ int dg_slot_mobj_poses(dg_ctx *c, int slot, int first, int count, dg_mobj_placed
 int dg_slot_sector_heights(dg_ctx *c, int slot, int first, int count, int16_t *out) {
     return slot_rows<HeightRows>(c, slot, first, count, reinterpret_cast<FsHeights *>(out), "dg_slot_sector_heights", &Slot::height_run, &Scene::fs_heights,
                                  [](const Scene &sc, const Slot &s, FrameArena &A, int frame, FsHeights *row) {
-                                     const dg_view_sectors *vs = s.sectors_of(frame);
+                                     const dg_view_sectors *vs = s.kept.at(frame).sectors;
                                      if (!vs) return;
                                      (void)resolve_view_sectors(sc, *vs, A.heights);
                                      for (const dg_sector_heights &h : A.heights.out) sector_row_place(row, h.sector, h.floor_height, h.ceiling_height);
@@ -406,7 +406,7 @@ int dg_slot_sector_height_timing(dg_ctx *c, int slot, float *ms) { return slot_r
 int dg_slot_sector_flats(dg_ctx *c, int slot, int first, int count, int32_t *out) {
     return slot_rows<FlatRows>(c, slot, first, count, reinterpret_cast<FsFlats *>(out), "dg_slot_sector_flats", &Slot::flat_run, &Scene::fs_flats,
                                [](const Scene &sc, const Slot &s, FrameArena &A, int frame, FsFlats *row) {
-                                   const dg_view_surfaces *vs = s.surfaces_of(frame);
+                                   const dg_view_surfaces *vs = s.kept.at(frame).surfaces;
                                    if (!vs) return;
                                    (void)resolve_view_surfaces(sc, nullptr, *vs, frame, A.sides, A.flats);
                                    for (const FlatEntry &e : A.flats.out) flat_row_place(row, e.sector, e.flats);

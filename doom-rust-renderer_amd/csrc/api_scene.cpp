@@ -231,7 +231,7 @@ int dg_build_lists(const dg_scene *s, int width, int height, const dg_view *view
     dg_view v = *view;
     fill_view_trig(v);
     std::string err;
-    int rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, nullptr, &s->sc->fx);
+    int rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, {}, &s->sc->fx);
     return rc ? set_err(rc, err) : DG_OK;
 }
 
@@ -301,15 +301,14 @@ int dg_scene_sector_flats(const dg_scene *s, dg_sector_flats *out, int n) {
 int dg_build_lists_surfaces(const dg_scene *s, int width, int height, const dg_view *view, const dg_view_poses *poses, const dg_view_sectors *sectors,
                             const dg_view_surfaces *surfaces, dg_frame_lists *out, const uint32_t **owners) {
     if (!s || !view || !out) return set_err(DG_ERR_INVALID, "null argument");
-    if (poses && poses->n && !poses->poses) return set_err(DG_ERR_INVALID, "view poses with a null array");
-    if (sectors && sectors->n && !sectors->heights) return set_err(DG_ERR_INVALID, "view sectors with a null array");
-    if (surfaces && ((surfaces->n_sides && !surfaces->sides) || (surfaces->n_flats && !surfaces->flats))) return set_err(DG_ERR_INVALID, "view surfaces with a null array");
+    const ViewInputs in{nullptr, poses, sectors, surfaces};
     std::string err;
+    if (!check_view_inputs(in, err)) return set_err(DG_ERR_INVALID, err);
     int rc = owners ? check_label_scene(*s->sc, err) : DG_OK;
     if (rc) return set_err(rc, err);
     dg_view v = *view;
     fill_view_trig(v);
-    rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, nullptr, &s->sc->fx, poses, sectors, surfaces);
+    rc = build_frame_lists(*s->sc, width, height, v, lists_arena(), *out, err, in, &s->sc->fx);
     if (rc) return set_err(rc, err);
     if (owners) *owners = lists_arena().owners.data();
     return DG_OK;

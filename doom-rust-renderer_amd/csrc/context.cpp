@@ -144,9 +144,8 @@ void fill_walk_params(dg_ctx *c, Slot &s, int n) {
 // as — DG_FE_HOST, DG_FE_DEPTH when dg_depth_tiles will walk the lists, DG_FE_LABELS when dg_label_tiles will, or DG_FE_BUNDLE.  A label
 // submission, and a bundle that says so (want_owners), needs owner tags: the tags of the wall records then go into the slot's owner array
 // as well (the caller has allocated it), from given_owners[i] for the caller's lists.
-int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, int32_t fe = DG_FE_HOST,
-                     const uint32_t *const *given_owners = nullptr, bool want_owners = false, const dg_view_poses *poses = nullptr,
-                     const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr) {
+int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const BatchInputs &in, int32_t fe = DG_FE_HOST,
+                     const uint32_t *const *given_owners = nullptr, bool want_owners = false) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -166,7 +165,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
             dg_view v = views[i];
             fill_view_trig(v);
             dg_frame_lists fl;
-            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr, sectors ? &sectors[i] : nullptr, surfaces ? &surfaces[i] : nullptr);
+            rc[(size_t)i] = build_frame_lists(sc, W, H, v, *c->arenas[(size_t)wid], fl, errs[(size_t)i], in.at(i), &c->fx);
             if (!rc[(size_t)i]) rc[(size_t)i] = bin_frame(sc, c->fk, fl, bf, errs[(size_t)i]);
             if (labels && !rc[(size_t)i]) rc[(size_t)i] = wall_owners(sc, fl, c->arenas[(size_t)wid]->owners.data(), c->label_tags[(size_t)i], errs[(size_t)i]);
         }
@@ -204,8 +203,7 @@ int build_batch_host(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_li
 
 // DG_FE_DEVICE: build the per-seg / per-sprite records of n views in parallel, pack them into the slot's record slab,
 // fill slot.FP / slot.P.  Returns kPartsUnsupported when the batch has to go through build_batch_host instead.
-int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors,
-                   const dg_view_surfaces *surfaces) {
+int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const BatchInputs &in) {
     const auto t0 = std::chrono::steady_clock::now();
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
@@ -217,7 +215,7 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
         FeFrameOut &o = c->fe_out[(size_t)i];
         dg_view v = views[i];
         fill_view_trig(v);
-        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], states ? &states[i] : nullptr, &c->fx, poses ? &poses[i] : nullptr, sectors ? &sectors[i] : nullptr, surfaces ? &surfaces[i] : nullptr);
+        rc[(size_t)i] = build_frame_parts(sc, W, H, v, A, errs[(size_t)i], in.at(i), &c->fx);
         if (rc[(size_t)i]) return;
         o.parts.swap(A.parts); o.sprites.swap(A.sprites); o.behind.swap(A.behind); o.sky_parts.swap(A.sky_parts);
         o.bin_off.swap(A.bin_off); o.bin_parts.swap(A.bin_parts); o.sbin_off.swap(A.sbin_off); o.sbin_sprites.swap(A.sbin_sprites);
@@ -288,10 +286,9 @@ int build_batch_fe(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     fill_walk_params(c, s, n);
     s.describe(DG_FE_DEVICE, n, L.total, parts, sprites);
     s.views.assign(views, views + n);
-    s.keep_states(states, n);
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (n >= 64 && !states && !poses && !sectors && !surfaces) c->fe_auto.host_batch((double)s.host_ms, n);      // DG_FE_AUTO's measurement of the host side
+    if (n >= 64 && !in.any()) c->fe_auto.host_batch((double)s.host_ms, n);      // DG_FE_AUTO's measurement of the host side
     HIP_TRY(hipMemcpyAsync(s.d_fe.get(), s.h_fe.get(), L.total, hipMemcpyHostToDevice, s.stream.get()));
     return DG_OK;
 }
@@ -410,9 +407,9 @@ void calibrate_host(dg_ctx *c, const dg_view *views, int n) {
     FrameArena &A = *c->arenas[0];
     std::string err;
     const int warm = std::min(4, n), timed = std::min(8, n);
-    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx); }
+    for (int i = 0; i < warm; i++) { dg_view v = views[i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, {}, &c->fx); }
     const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, nullptr, &c->fx); }
+    for (int i = 0; i < timed; i++) { dg_view v = views[n - 1 - i]; fill_view_trig(v); (void)build_frame_parts(sc, c->cfg.width, c->cfg.height, v, A, err, {}, &c->fx); }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->fe_auto.calibrated(ms, timed, c->n_threads);
 }
@@ -465,9 +462,12 @@ template <class K> hipError_t copy_row_entries(const RowBuffers<K> &b, uint32_t 
 // DG_FE_DEVICE_SEGS: nothing of the front end runs on the host.  Per frame it ships the view (trig filled) and the DevFrame header,
 // per batch the scene's current light levels and map-object states; dg_fs_* then write the same record arrays build_batch_fe packs,
 // with fixed per-frame strides (fs_frame.h), into the slot's record slab.
-int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors,
-                   const dg_view_surfaces *surfaces) {
+int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const BatchInputs &in) {
     const auto t0 = std::chrono::steady_clock::now();
+    const dg_view_state *const states = in.states;
+    const dg_view_poses *const poses = in.poses;
+    const dg_view_sectors *const sectors = in.sectors;
+    const dg_view_surfaces *const surfaces = in.surfaces;
     if (const int bad = check_batch(c, n)) return bad;
     const Scene &sc = *c->scene;
     const int W = c->cfg.width;
@@ -606,7 +606,6 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     F.order = Q.order_list; F.order_cnt = Q.order_cnt;
     fill_walk_params(c, s, n);
     s.describe(DG_FE_DEVICE_SEGS, n, L.upload, 0, 0);
-    s.keep_states(states, n);
     s.snapshot_scene(sc);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(d, h, L.upload, hipMemcpyHostToDevice, s.stream.get()));
@@ -617,17 +616,16 @@ int build_batch_fs(dg_ctx *c, Slot &s, const dg_view *views, int n, const dg_vie
     return DG_OK;
 }
 
-int build_batch(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states = nullptr, const dg_view_poses *poses = nullptr,
-                const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr) {
+int build_batch(dg_ctx *c, Slot &s, const dg_view *views, const dg_frame_lists *given, int n, const BatchInputs &in) {
     if (!given && c->fs_enabled && c->fs_scene_ok && choose_fs(c, views, n)) {
-        const int rc = build_batch_fs(c, s, views, n, states, poses, sectors, surfaces);
+        const int rc = build_batch_fs(c, s, views, n, in);
         if (rc != kPartsUnsupported) return rc;
     }
     if (!given && c->fe_enabled && c->fe_scene_ok) {
-        const int rc = build_batch_fe(c, s, views, n, states, poses, sectors, surfaces);
+        const int rc = build_batch_fe(c, s, views, n, in);
         if (rc != kPartsUnsupported) return rc;
     }
-    return build_batch_host(c, s, views, given, n, states, DG_FE_HOST, nullptr, false, poses, sectors, surfaces);
+    return build_batch_host(c, s, views, given, n, in);
 }
 
 // The 2-D map view's linedef layer of the uploaded scene, on the kernel stream (timed by the slot's ev_start / ev_setup).  The line records
@@ -852,7 +850,9 @@ int redo_frame_host(dg_ctx *c, Slot &s, int i) {
     fill_view_trig(v);
     dg_frame_lists fl;
     Slot::RedoState redo_state;
-    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, s.state_for_redo(sc, i, redo_state, c->fx), &c->fx, s.poses_of(i), s.sectors_of(i), s.surfaces_of(i));
+    ViewInputs in = s.kept.at(i);
+    in.state = s.state_for_redo(sc, i, redo_state, c->fx);
+    int rc = build_frame_lists(sc, W, H, v, *c->arenas[0], fl, err, in, &c->fx);
     if (!rc) rc = bin_frame(sc, c->fk, fl, bf, err);
     if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     bf.hdr.span_base = 0; bf.hdr.wall_base = 0; bf.hdr.plane_base = 0;
@@ -900,7 +900,8 @@ int redo_overflowed(dg_ctx *c, Slot &s) {
         else c->redone_frames++;
     }
     if (!whole_batch) return DG_OK;
-    // (the whole batch again, with every frame's submit-time state: build_batch_host reads the states while it runs and keeps nothing of them)
+    // (the whole batch again, with every frame's submit-time state and the slot's own kept inputs: build_batch_host reads them while it
+    // runs and, like every builder, writes nothing to s.kept — built_from, which does, is not called here)
     const std::vector<dg_view> views = s.views;
     std::vector<Slot::RedoState> redo_states(views.size());
     std::vector<dg_view_state> sts;
@@ -910,7 +911,9 @@ int redo_overflowed(dg_ctx *c, Slot &s) {
         any_state |= st != nullptr;
         sts.push_back(st ? *st : dg_view_state{nullptr, 0, nullptr, 0});
     }
-    int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), any_state ? sts.data() : nullptr, DG_FE_HOST, nullptr, false, s.poses_of(0), s.sectors_of(0), s.surfaces_of(0));
+    BatchInputs in = s.kept.inputs();
+    in.states = any_state ? sts.data() : nullptr;
+    int rc = build_batch_host(c, s, views.data(), nullptr, (int)views.size(), in);
     if (rc) return rc;
     rc = enqueue_kernels(c, s);
     if (rc) return rc;
@@ -970,25 +973,22 @@ int take_slot(dg_ctx *c, Slot &s) {
     return s.phase == Slot::Phase::Queued || s.copy_pending ? make_final(c, s, Copy::Complete) : DG_OK;
 }
 
-// What a submission built for the slot leaves for later: whether it came from views, and then a copy of their poses (the caller's
-// arrays need not outlive the call).
-void built_from(Slot &s, const dg_view *views, const dg_view_poses *poses, int n, const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr) {
+// What a submission built for the slot leaves for later: whether it came from views, and then a copy of what they brought (the
+// caller's arrays need not outlive the call).  The one place that writes the slot's kept copy.
+void built_from(Slot &s, const dg_view *views, const BatchInputs &in, int n) {
     s.from_views = views != nullptr;
-    s.keep_poses(views ? poses : nullptr, n);
-    s.keep_sectors(views ? sectors : nullptr, n);
-    s.keep_surfaces(views ? surfaces : nullptr, n);
+    s.kept.keep(views ? in : BatchInputs{}, n);
 }
 
 // Slot `slot` for a new submission of n views (or of the caller's lists), and its kernels enqueued.
-int submit(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states, const dg_view_poses *poses = nullptr,
-           const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr) {
+int submit(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const BatchInputs &in) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     int rc = take_slot(c, s);
     if (rc) return rc;
-    rc = build_batch(c, s, views, given, n, states, poses, sectors, surfaces);
+    rc = build_batch(c, s, views, given, n, in);
     if (rc) return rc;
-    built_from(s, views, poses, n, sectors, surfaces);
+    built_from(s, views, in, n);
     return enqueue_kernels(c, s);
 }
 
@@ -1039,14 +1039,14 @@ int launched(Slot &s, hipError_t e, const char *what) {
 
 // Slot `slot` for a depth submission of n views (or of the caller's lists): always the host list path, whatever front end the ctx has;
 // dg_depth_tiles on the slot's own stream, behind the upload.
-int submit_depth(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const dg_view_state *states) {
+int submit_depth(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, int n, const BatchInputs &in) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     int rc = take_slot(c, s);
     if (rc) return rc;
-    rc = build_batch_host(c, s, views, given, n, states, DG_FE_DEPTH);
+    rc = build_batch_host(c, s, views, given, n, in, DG_FE_DEPTH);
     if (rc) return rc;
-    built_from(s, views, nullptr, n);
+    built_from(s, views, in, n);
     const BundlePlanes out = planes_of(c, s);
     return launched(s, launch_depth(s.P, out.dist, out.kind, s.stream.get(), s.ev_rstart.get(), s.ev_raster.get()), "launch_depth");
 }
@@ -1054,7 +1054,7 @@ int submit_depth(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists
 // Slot `slot` for a label submission of n views (or of the caller's lists with their owner tags): the host list path like depth;
 // dg_label_tiles and dg_label_boxes on the slot's own stream, behind the uploads.  ev_setup, which a label submission has no front-end
 // half to time with, marks the end of dg_label_tiles.
-int submit_labels(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, const uint32_t *const *owners, int n, const dg_view_state *states) {
+int submit_labels(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, const uint32_t *const *owners, int n, const BatchInputs &in) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     int rc = take_slot(c, s);
@@ -1063,9 +1063,9 @@ int submit_labels(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     std::string err;
     if ((rc = check_label_scene(*c->scene, err))) return set_err(rc, err);
     if ((rc = ensure_label_buffers(c, s))) return rc;
-    rc = build_batch_host(c, s, views, given, n, states, DG_FE_LABELS, owners);
+    rc = build_batch_host(c, s, views, given, n, in, DG_FE_LABELS, owners);
     if (rc) return rc;
-    built_from(s, views, nullptr, n);
+    built_from(s, views, in, n);
     const BundlePlanes out = planes_of(c, s);
     return launched(s, launch_labels(s.P, s.d_owners.get(), out.id, out.cls, out.boxes, out.n_mobjs, s.stream.get(), s.ev_rstart.get(), s.ev_setup.get(), s.ev_raster.get()), "launch_labels");
 }
@@ -1100,9 +1100,8 @@ int enqueue_bundle(dg_ctx *c, Slot &s) {
 
 // Slot `slot` for a bundle of n views (or of the caller's lists, with their owner tags when labels are asked for): the host list path
 // whatever front end the ctx has, one list build and one upload for every part.
-int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, const uint32_t *const *owners, int n, const dg_view_state *states,
-                  uint32_t what, const dg_view_poses *poses = nullptr, const dg_view_sectors *sectors = nullptr,
-                  const dg_view_surfaces *surfaces = nullptr) {
+int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_lists *given, const uint32_t *const *owners, int n, const BatchInputs &in,
+                  uint32_t what) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     Slot &s = c->slots[(size_t)slot];
     if (const int bad = check_batch(c, n)) return bad;
@@ -1113,41 +1112,21 @@ int submit_bundle(dg_ctx *c, int slot, const dg_view *views, const dg_frame_list
     if (labels && (rc = check_label_scene(*c->scene, err))) return set_err(rc, err);
     if ((rc = take_slot(c, s))) return rc;
     if (labels && (rc = ensure_label_buffers(c, s))) return rc;
-    rc = build_batch_host(c, s, views, given, n, states, DG_FE_BUNDLE, owners, labels, poses, sectors, surfaces);
+    rc = build_batch_host(c, s, views, given, n, in, DG_FE_BUNDLE, owners, labels);
     if (rc) {
         if (s.phase == Slot::Phase::Prepared && s.front_end == DG_FE_BUNDLE) s.reset();   // (described, then an upload failed: nothing says yet which parts it has)
         return rc;
     }
-    built_from(s, views, poses, n, sectors, surfaces);
+    built_from(s, views, in, n);
     s.bundle_what = what;
     return enqueue_bundle(c, s);
 }
 
-int check_view_poses(const dg_view_poses *poses, int n) {
-    if (poses)
-        for (int i = 0; i < n; i++)
-            if (poses[i].n && !poses[i].poses) return set_err(DG_ERR_INVALID, "view poses with a null array");
-    return DG_OK;
-}
-
-int check_view_sectors(const dg_view_sectors *sectors, int n) {
-    if (sectors)
-        for (int i = 0; i < n; i++)
-            if (sectors[i].n && !sectors[i].heights) return set_err(DG_ERR_INVALID, "view sectors with a null array");
-    return DG_OK;
-}
-
-int check_view_surfaces(const dg_view_surfaces *surfaces, int n) {
-    if (surfaces)
-        for (int i = 0; i < n; i++)
-            if ((surfaces[i].n_sides && !surfaces[i].sides) || (surfaces[i].n_flats && !surfaces[i].flats)) return set_err(DG_ERR_INVALID, "frame " + std::to_string(i) + ": view surfaces with a null array");
-    return DG_OK;
-}
-
-int check_view_states(const dg_view_state *states, int n) {
-    if (states)
-        for (int i = 0; i < n; i++)
-            if ((states[i].n_lights && !states[i].lights) || (states[i].n_mobjs && !states[i].mobjs)) return set_err(DG_ERR_INVALID, "view state with a null array");
+// check_view_inputs for every view of a batch.  (Only the surfaces' message names the frame.)
+int check_batch_inputs(const BatchInputs &in, int n) {
+    std::string why;
+    for (int i = 0; in.any() && i < n; i++)
+        if (!check_view_inputs(in.at(i), why)) return set_err(DG_ERR_INVALID, (why == view_surfaces_error(32u) ? "frame " + std::to_string(i) + ": " : "") + why);
     return DG_OK;
 }
 
@@ -1193,7 +1172,7 @@ int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int
     if (mask) std::memcpy(s.per_scene.h_masks.get(), mask, mask_bytes);
     s.map = Slot::MapState{ego ? *ego : dg_ego_map{}, mask != nullptr, false};
     s.describe(fe, n, bytes + mask_bytes, 0, 0);
-    built_from(s, nullptr, nullptr, n);
+    built_from(s, nullptr, BatchInputs{}, n);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream.get()));
     if (mask) HIP_TRY(hipMemcpyAsync(s.per_scene.d_masks.get(), s.per_scene.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream.get()));
@@ -1408,12 +1387,9 @@ int dg_submit_views_surfaces(dg_ctx *c, int slot, const dg_view *views, const dg
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
-    rc = check_view_states(states, n);
-    if (!rc) rc = check_view_poses(poses, n);
-    if (!rc) rc = check_view_sectors(sectors, n);
-    if (!rc) rc = check_view_surfaces(surfaces, n);
-    if (rc) return rc;
-    return submit(c, slot, views, nullptr, n, states, poses, sectors, surfaces);
+    const BatchInputs in{states, poses, sectors, surfaces};
+    if ((rc = check_batch_inputs(in, n))) return rc;
+    return submit(c, slot, views, nullptr, n, in);
 }
 
 int dg_render_views_surfaces(dg_ctx *c, const dg_view *views, const dg_view_state *states, const dg_view_poses *poses, const dg_view_sectors *sectors,
@@ -1468,10 +1444,10 @@ int dg_prepare_views(dg_ctx *c, int slot, const dg_view *views, int n) {
     rc = take_slot(c, s);
     if (rc) return rc;
     c->preparing = true;
-    rc = build_batch(c, s, views, nullptr, n);
+    rc = build_batch(c, s, views, nullptr, n, BatchInputs{});
     c->preparing = false;
     if (rc) return rc;
-    built_from(s, views, nullptr, n);
+    built_from(s, views, BatchInputs{}, n);
     if (s.column_walk()) {        // run the column walk once so that a batch that has to go through the host list path as a whole
         rc = enqueue_kernels(c, s);   // is re-prepared that way now, not on a replay
         if (rc) return rc;
@@ -1500,16 +1476,16 @@ int dg_draw_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, int n, uint
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!frames) return set_err(DG_ERR_INVALID, "null frames");
-    return read_or_wait(c, slot, submit(c, slot, nullptr, frames, n, nullptr), n, out);
+    return read_or_wait(c, slot, submit(c, slot, nullptr, frames, n, BatchInputs{}), n, out);
 }
 
 int dg_submit_depth_views(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, int n) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
-    rc = check_view_states(states, n);
-    if (rc) return rc;
-    return submit_depth(c, slot, views, nullptr, n, states);
+    const BatchInputs in{states};
+    if ((rc = check_batch_inputs(in, n))) return rc;
+    return submit_depth(c, slot, views, nullptr, n, in);
 }
 
 int dg_render_depth_views(dg_ctx *c, const dg_view *views, const dg_view_state *states, int n, int16_t *distance, uint8_t *kind) {
@@ -1520,16 +1496,16 @@ int dg_depth_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, int n, int
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!frames) return set_err(DG_ERR_INVALID, "null frames");
-    return read_or_wait(c, slot, submit_depth(c, slot, nullptr, frames, n, nullptr), distance || kind, [&] { return dg_readback_depth(c, slot, 0, n, distance, kind); });
+    return read_or_wait(c, slot, submit_depth(c, slot, nullptr, frames, n, BatchInputs{}), distance || kind, [&] { return dg_readback_depth(c, slot, 0, n, distance, kind); });
 }
 
 int dg_submit_label_views(dg_ctx *c, int slot, const dg_view *views, const dg_view_state *states, int n) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
-    rc = check_view_states(states, n);
-    if (rc) return rc;
-    return submit_labels(c, slot, views, nullptr, nullptr, n, states);
+    const BatchInputs in{states};
+    if ((rc = check_batch_inputs(in, n))) return rc;
+    return submit_labels(c, slot, views, nullptr, nullptr, n, in);
 }
 
 int dg_render_label_views(dg_ctx *c, const dg_view *views, const dg_view_state *states, int n, uint16_t *id, uint8_t *cls, dg_label_box *boxes) {
@@ -1540,7 +1516,7 @@ int dg_label_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uint
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!frames || !owners) return set_err(DG_ERR_INVALID, "null frames or owners");
-    return read_or_wait(c, slot, submit_labels(c, slot, nullptr, frames, owners, n, nullptr), id || cls || boxes, [&] { return dg_readback_labels(c, slot, 0, n, id, cls, boxes); });
+    return read_or_wait(c, slot, submit_labels(c, slot, nullptr, frames, owners, n, BatchInputs{}), id || cls || boxes, [&] { return dg_readback_labels(c, slot, 0, n, id, cls, boxes); });
 }
 
 int dg_bundle_capacity(const dg_ctx *c, uint32_t what) {
@@ -1568,12 +1544,9 @@ int dg_submit_bundle_views_surfaces(dg_ctx *c, int slot, const dg_view *views, c
     if (rc) return rc;
     if (!views) return set_err(DG_ERR_INVALID, "null views");
     if ((rc = check_bundle_what(what))) return rc;
-    rc = check_view_states(states, n);
-    if (!rc) rc = check_view_poses(poses, n);
-    if (!rc) rc = check_view_sectors(sectors, n);
-    if (!rc) rc = check_view_surfaces(surfaces, n);
-    if (rc) return rc;
-    return submit_bundle(c, slot, views, nullptr, nullptr, n, states, what, poses, sectors, surfaces);
+    const BatchInputs in{states, poses, sectors, surfaces};
+    if ((rc = check_batch_inputs(in, n))) return rc;
+    return submit_bundle(c, slot, views, nullptr, nullptr, n, in, what);
 }
 
 int dg_bundle_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uint32_t *const *owners, int n, uint32_t what) {
@@ -1582,7 +1555,7 @@ int dg_bundle_lists(dg_ctx *c, int slot, const dg_frame_lists *frames, const uin
     if (!frames) return set_err(DG_ERR_INVALID, "null frames");
     if ((rc = check_bundle_what(what))) return rc;
     if ((what & BUNDLE_LABELS) && !owners) return set_err(DG_ERR_INVALID, "null owners: DG_BUNDLE_LABELS needs the owner tags");
-    rc = submit_bundle(c, slot, nullptr, frames, owners, n, nullptr, what);
+    rc = submit_bundle(c, slot, nullptr, frames, owners, n, BatchInputs{}, what);
     return rc ? rc : dg_wait(c, slot);                    // (no output of its own: the parts are the readbacks' to fetch)
 }
 

@@ -197,53 +197,12 @@ struct Slot {
     }
     bool harvested = true;        // DG_FE_AUTO has read this submission's GPU time
     std::vector<dg_view> views;   // the views of that submission (to redo it on the host if a capacity overflowed)
-    // ... and a private copy of their game-state snapshots (the caller's arrays need not outlive the call)
-    std::vector<dg_view_state> states;
-    std::vector<dg_sector_light> state_lights;
-    std::vector<dg_mobj_state> state_mobjs;
-    // ... and of their poses, kept by every view submission whatever its front end: a frame redone on the host is drawn with them,
-    // and dg_slot_mobj_poses derives the rows of a host-walker submission from them.  from_views: the slot's submission was built from
-    // views (not from the caller's lists, not a 2-D map submission) — the submit functions say so once it is built.
-    std::vector<dg_view_poses> poses;
-    std::vector<dg_mobj_pose> pose_entries;
+    // ... and a private copy of what they brought (KeptInputs), taken by built_from and by nothing else — no builder
+    // writes it, because redo_overflowed hands it to one.  A frame redone on the host is drawn with it, and dg_slot_mobj_poses /
+    // _sector_heights / _sector_flats derive the rows of a host-walker submission from it.  from_views: the slot's submission was built
+    // from views (not from the caller's lists, not a 2-D map submission) — the submit functions say so once it is built.
+    KeptInputs kept;
     bool from_views = false;
-    const dg_view_poses *poses_of(int i) const { return poses.empty() ? nullptr : &poses[(size_t)i]; }
-    // ... and of their sector heights, kept likewise (dg_slot_sector_heights derives a host-walker submission's rows from them)
-    std::vector<dg_view_sectors> sectors;
-    std::vector<dg_sector_heights> sector_entries;
-    const dg_view_sectors *sectors_of(int i) const { return sectors.empty() ? nullptr : &sectors[(size_t)i]; }
-    void keep_sectors(const dg_view_sectors *vs, int n) {
-        sectors.clear(); sector_entries.clear();
-        if (!vs) return;
-        for (int i = 0; i < n; i++) sector_entries.insert(sector_entries.end(), vs[i].heights, vs[i].heights + vs[i].n);
-        size_t o = 0;
-        for (int i = 0; i < n; i++) { sectors.push_back(dg_view_sectors{sector_entries.data() + o, vs[i].n}); o += vs[i].n; }
-    }
-    // ... and of their surfaces, kept likewise: redone frames, whole-batch fallbacks and dg_slot_sector_flats read them
-    std::vector<dg_view_surfaces> surfaces;
-    std::vector<dg_side_surface> side_entries;
-    std::vector<dg_sector_flats> flat_entries;
-    const dg_view_surfaces *surfaces_of(int i) const { return surfaces.empty() ? nullptr : &surfaces[(size_t)i]; }
-    void keep_surfaces(const dg_view_surfaces *vs, int n) {
-        surfaces.clear(); side_entries.clear(); flat_entries.clear();
-        if (!vs) return;
-        for (int i = 0; i < n; i++) {
-            if (vs[i].sides) side_entries.insert(side_entries.end(), vs[i].sides, vs[i].sides + vs[i].n_sides);
-            if (vs[i].flats) flat_entries.insert(flat_entries.end(), vs[i].flats, vs[i].flats + vs[i].n_flats);
-        }
-        size_t so = 0, fo = 0;
-        for (int i = 0; i < n; i++) {
-            surfaces.push_back(dg_view_surfaces{side_entries.data() + so, vs[i].n_sides, flat_entries.data() + fo, vs[i].n_flats});
-            so += vs[i].n_sides; fo += vs[i].n_flats;
-        }
-    }
-    void keep_poses(const dg_view_poses *ps, int n) {
-        poses.clear(); pose_entries.clear();
-        if (!ps) return;
-        for (int i = 0; i < n; i++) pose_entries.insert(pose_entries.end(), ps[i].poses, ps[i].poses + ps[i].n);
-        size_t o = 0;
-        for (int i = 0; i < n; i++) { poses.push_back(dg_view_poses{pose_entries.data() + o, ps[i].n}); o += ps[i].n; }
-    }
     // The scene's own light levels and map-object states as they were when the batch was submitted: a frame that overflows a capacity is
     // redone at dg_wait time from the host walker, and dg_scene_set_sector_light / _mobj_state may have moved the scene on by then
     // (lights.rs:47-259 and map_objects.rs:63-121 run between two submissions of a pipelined caller).
@@ -264,7 +223,7 @@ struct Slot {
     // fx: the effects the frame was drawn with — the light effects' sectors keep the effect's level and the objects the thinkers drive
     // their state, so the snapshot does not list them.
     const dg_view_state *state_for_redo(const Scene &sc, int i, RedoState &tmp, const SceneFx &fx) const {
-        const dg_view_state *own = states.empty() ? nullptr : &states[(size_t)i];
+        const dg_view_state *own = kept.at(i).state;
         if (snap_scene != &sc || snap_rev == sc.revision) return own;
         tmp.lights.clear();
         const bool lfx = fx.light.fits(sc), mfx = fx.mobj.fits(sc);      // (the snapshot has the scene's sizes: snapshot_scene)
@@ -276,16 +235,6 @@ struct Slot {
         if (own) { tmp.lights.insert(tmp.lights.end(), own->lights, own->lights + own->n_lights); tmp.mobjs.insert(tmp.mobjs.end(), own->mobjs, own->mobjs + own->n_mobjs); }
         tmp.st = dg_view_state{tmp.lights.data(), (uint32_t)tmp.lights.size(), tmp.mobjs.data(), (uint32_t)tmp.mobjs.size()};
         return &tmp.st;
-    }
-    void keep_states(const dg_view_state *st, int n) {
-        states.clear(); state_lights.clear(); state_mobjs.clear();
-        if (!st) return;
-        for (int i = 0; i < n; i++) { state_lights.insert(state_lights.end(), st[i].lights, st[i].lights + st[i].n_lights); state_mobjs.insert(state_mobjs.end(), st[i].mobjs, st[i].mobjs + st[i].n_mobjs); }
-        size_t lo = 0, mo = 0;
-        for (int i = 0; i < n; i++) {
-            states.push_back(dg_view_state{state_lights.data() + lo, st[i].n_lights, state_mobjs.data() + mo, st[i].n_mobjs});
-            lo += st[i].n_lights; mo += st[i].n_mobjs;
-        }
     }
 };
 

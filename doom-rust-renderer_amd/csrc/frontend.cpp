@@ -131,10 +131,11 @@ struct Walker {
     // (src/lights.rs:47-259, src/map_objects.rs:63-121): the view's snapshot entry if there is one, else the light effect's level
     //  or the map-object thinker's state (§8d), else the scene's value.  The arena's two rows hold what overrides the
     // scene: the effects' values, every effect sector and driven object once per frame, then the view's entries on top.
-    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const dg_view_state *st, const SceneFx *f, const dg_view_poses *ps,
-           const dg_view_sectors *vs, const dg_view_surfaces *vf)
-        : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e), state(st), fx(f && f->wall.on() ? &f->wall : nullptr),
-          lfx(f && f->light.fits(s) ? &f->light : nullptr), mfx(f && f->mobj.fits(s) ? &f->mobj : nullptr), poses(ps) {
+    Walker(const Scene &s, int W, int H, const dg_view &v, FrameArena &a, std::string &e, const ViewInputs &in, const SceneFx *f)
+        : sc(s), k(make_consts(W, H)), view(v), A(a), recs(*a.recs), err(e), state(in.state), fx(f && f->wall.on() ? &f->wall : nullptr),
+          lfx(f && f->light.fits(s) ? &f->light : nullptr), mfx(f && f->mobj.fits(s) ? &f->mobj : nullptr), poses(in.poses) {
+        const dg_view_sectors *const vs = in.sectors;
+        const dg_view_surfaces *const vf = in.surfaces;
         ppos = V2{v.x, v.y};
         player_height = v.floor_height + kEye;
         if (A.light_row.size() != sc.sectors.size()) A.light_row.assign(sc.sectors.size(), kNoOverride);
@@ -562,8 +563,7 @@ struct Walker {
 
 }  // namespace
 
-int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const dg_view_state *state, const SceneFx *fx,
-                      const dg_view_poses *poses, const dg_view_sectors *sectors, const dg_view_surfaces *surfaces) {
+int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, dg_frame_lists &out, std::string &err, const ViewInputs &in, const SceneFx *fx) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.renders.clear(); A.owners.clear(); A.columns.clear(); A.visplanes.clear(); A.plane_tb.clear(); A.order.clear();
     A.recs->clear(); A.floor_tb.clear(); A.ceil_tb.clear();
@@ -573,7 +573,7 @@ int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameA
     A.top_clip.resize((size_t)W);
     A.bottom_clip.resize((size_t)W);
 
-    Walker wk(sc, W, H, view, A, err, state, fx, poses, sectors, surfaces);
+    Walker wk(sc, W, H, view, A, err, in, fx);
     if (wk.status) return wk.status;
     wk.walk_bsp();
     if (wk.status) return wk.status;
@@ -621,12 +621,11 @@ void bin_by_columns(const std::vector<T> &recs, int W, Range range, std::vector<
 }
 }  // namespace
 
-int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const dg_view_state *state, const SceneFx *fx,
-                      const dg_view_poses *poses, const dg_view_sectors *sectors, const dg_view_surfaces *surfaces) {
+int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &A, std::string &err, const ViewInputs &in, const SceneFx *fx) {
     if (W <= 0 || H <= 0 || W > 16384 || H > 16384) { err = "bad frame size"; return DG_ERR_INVALID; }
     A.parts.clear(); A.sprites.clear(); A.behind.clear(); A.sky_parts.clear(); A.behind_words = 0; A.n_sky_slots = 0;
     A.recs->clear();
-    Walker wk(sc, W, H, view, A, err, state, fx, poses, sectors, surfaces);
+    Walker wk(sc, W, H, view, A, err, in, fx);
     if (wk.status) return wk.status;
     wk.parts_mode = true;
     wk.walk_bsp();

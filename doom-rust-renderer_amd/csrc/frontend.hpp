@@ -92,16 +92,83 @@ struct FrameArena {
     FrameArena &operator=(const FrameArena &) = delete;
 };
 
+// What one view may bring besides the view itself (include/doomgpu.h); each is optional.  A further per-view input is one member
+// here, in BatchInputs and in KeptInputs, one line in check_view_inputs, and its consumer.
+struct ViewInputs {
+    const dg_view_state *state = nullptr;         // the view's game-state snapshot (dg_view_state); nullptr: the scene's state
+    const dg_view_poses *poses = nullptr;         // where the view's map objects are (dg_view_poses); nullptr: where the scene has them
+    const dg_view_sectors *sectors = nullptr;     // the view's sector floor / ceiling heights (dg_view_sectors); nullptr: as loaded
+    const dg_view_surfaces *surfaces = nullptr;   // the view's sidedef textures and offsets and sector flats (dg_view_surfaces); nullptr: as loaded
+    ViewInputs() = default;
+    // (not explicit: a caller with a state alone, or none — nullptr — passes it as before)
+    ViewInputs(const dg_view_state *st, const dg_view_poses *ps = nullptr, const dg_view_sectors *vs = nullptr, const dg_view_surfaces *vf = nullptr)
+        : state(st), poses(ps), sectors(vs), surfaces(vf) {}
+    bool any() const { return state || poses || sectors || surfaces; }
+};
+// ... and a batch's: each null, or one element per view.
+struct BatchInputs {
+    const dg_view_state *states = nullptr;
+    const dg_view_poses *poses = nullptr;
+    const dg_view_sectors *sectors = nullptr;
+    const dg_view_surfaces *surfaces = nullptr;
+    bool any() const { return states || poses || sectors || surfaces; }
+    __attribute__((always_inline)) ViewInputs at(int i) const {     // (once per frame, inside the builders' per-frame lambdas)
+        return ViewInputs{states ? states + i : nullptr, poses ? poses + i : nullptr, sectors ? sectors + i : nullptr, surfaces ? surfaces + i : nullptr};
+    }
+};
+
+// A private copy of a batch's inputs, entries included: the caller's arrays need not outlive the call that handed them over.  Every
+// view's entries of one kind lie in one flat vector, and the per-view structs point into it.
+class KeptInputs {
+    std::vector<dg_view_state> states;
+    std::vector<dg_sector_light> lights;
+    std::vector<dg_mobj_state> mobjs;
+    std::vector<dg_view_poses> poses;
+    std::vector<dg_mobj_pose> pose_entries;
+    std::vector<dg_view_sectors> sectors;
+    std::vector<dg_sector_heights> height_entries;
+    std::vector<dg_view_surfaces> surfaces;
+    std::vector<dg_side_surface> side_entries;
+    std::vector<dg_sector_flats> flat_entries;
+    // views: the caller's structs of one kind, copied as they are; the arrays they name through (ptr, count) go into `flat` one after
+    // the other, and only then — the vector has stopped growing — are the copies pointed at their part of it.  An array may be null
+    // when its count is 0.
+    template <class V, class E> static void flatten(std::vector<V> &views, std::vector<E> &flat, const E *V::*ptr, uint32_t V::*count) {
+        flat.clear();
+        for (const V &v : views)
+            if (v.*count) flat.insert(flat.end(), v.*ptr, v.*ptr + v.*count);
+        size_t at = 0;
+        for (V &v : views) { v.*ptr = flat.data() + at; at += v.*count; }
+    }
+    template <class V> static void copy_views(std::vector<V> &views, const V *from, int n) {
+        if (from) views.assign(from, from + n);
+        else views.clear();
+    }
+
+public:
+    // A deep copy of n views' inputs (checked: check_view_inputs) in place of what was kept; an empty `in` keeps nothing.
+    void keep(const BatchInputs &in, int n) {
+        copy_views(states, in.states, n); copy_views(poses, in.poses, n); copy_views(sectors, in.sectors, n); copy_views(surfaces, in.surfaces, n);
+        flatten(states, lights, &dg_view_state::lights, &dg_view_state::n_lights);
+        flatten(states, mobjs, &dg_view_state::mobjs, &dg_view_state::n_mobjs);
+        flatten(poses, pose_entries, &dg_view_poses::poses, &dg_view_poses::n);
+        flatten(sectors, height_entries, &dg_view_sectors::heights, &dg_view_sectors::n);
+        flatten(surfaces, side_entries, &dg_view_surfaces::sides, &dg_view_surfaces::n_sides);
+        flatten(surfaces, flat_entries, &dg_view_surfaces::flats, &dg_view_surfaces::n_flats);
+    }
+    // What is kept, pointing into this object until its next keep(): null for every input that was not given.
+    BatchInputs inputs() const {
+        return BatchInputs{states.empty() ? nullptr : states.data(), poses.empty() ? nullptr : poses.data(), sectors.empty() ? nullptr : sectors.data(),
+                           surfaces.empty() ? nullptr : surfaces.data()};
+    }
+    ViewInputs at(int i) const { return inputs().at(i); }
+};
+
 // Fills `arena` and `out` (pointers into arena).  Returns DG_OK or DG_ERR_RENDER with `err` set where the
 // reference would panic.  `view` must have its trig fields filled.
-// `state` (optional): the view's game-state snapshot (include/doomgpu.h dg_view_state).
 // `fx` (optional): the effects to draw with (Scene::fx, or the copy a dg_ctx uploaded); nullptr: none.
-// `poses` (optional): where the view's map objects are (include/doomgpu.h dg_view_poses); nullptr: where the scene has them.
-// `sectors` (optional): the view's sector floor / ceiling heights (dg_view_sectors); nullptr: as loaded.
-// `surfaces` (optional): the view's sidedef textures and offsets and sector flats (dg_view_surfaces); nullptr: as loaded.
 int build_frame_lists(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, dg_frame_lists &out, std::string &err,
-                      const dg_view_state *state = nullptr, const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr,
-                      const dg_view_sectors *sectors = nullptr, const dg_view_surfaces *surfaces = nullptr);
+                      const ViewInputs &in = {}, const SceneFx *fx = nullptr);
 
 // Checks a view's snapshot against the scene's ranges and hands every valid entry, in order (later entries win), to light(sector, level)
 // or mobj(map object, mfx_encode'd state).  Returns 0, or bit 0: a sector index was out of range, bit 1: a map object or sprite frame
@@ -203,6 +270,18 @@ inline const char *view_surfaces_error(unsigned bad) {
          : bad & 4u ? "view surfaces: offset outside int16" : bad & 8u ? "view surfaces: sector index out of range" : "view surfaces: not a flat handle of this scene";
 }
 
+// The one rule every entry point checks before anything reads a view's inputs: no array is null with a count above 0.  False, with
+// `why` set, otherwise.
+inline bool check_view_inputs(const ViewInputs &in, std::string &why) {
+    const char *bad = nullptr;
+    if (in.state && ((in.state->n_lights && !in.state->lights) || (in.state->n_mobjs && !in.state->mobjs))) bad = "view state with a null array";
+    else if (in.poses && in.poses->n && !in.poses->poses) bad = "view poses with a null array";
+    else if (in.sectors && in.sectors->n && !in.sectors->heights) bad = "view sectors with a null array";
+    else if (in.surfaces && ((in.surfaces->n_sides && !in.surfaces->sides) || (in.surfaces->n_flats && !in.surfaces->flats))) bad = view_surfaces_error(32u);
+    if (bad) why = bad;
+    return !bad;
+}
+
 void fill_view_trig(dg_view &v);
 
 // Parts mode: the per-seg and per-sprite half only (BSP order, transform, clip, projection, pegging, sprite sorting and the
@@ -210,9 +289,8 @@ void fill_view_trig(dg_view &v);
 // Returns DG_OK, DG_ERR_RENDER (the reference would panic before any column is walked) or kPartsUnsupported (a case only the
 // host list path can judge: the caller redoes the frame with build_frame_lists).
 constexpr int kPartsUnsupported = 1000;
-int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, std::string &err, const dg_view_state *state = nullptr,
-                      const SceneFx *fx = nullptr, const dg_view_poses *poses = nullptr, const dg_view_sectors *sectors = nullptr,
-                      const dg_view_surfaces *surfaces = nullptr);
+int build_frame_parts(const Scene &sc, int W, int H, const dg_view &view, FrameArena &arena, std::string &err, const ViewInputs &in = {},
+                      const SceneFx *fx = nullptr);
 
 // Per-record constants of render_vertical_bitmap_line (bitmap_render.rs:233-251), shared by the binner and the parts builder.
 DevWallRec make_wall_rec(const BitmapInfo &bi, float lsx, float lsy, float lex, float ley, float start_offset, int32_t start_x, int32_t end_x,

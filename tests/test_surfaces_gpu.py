@@ -11,11 +11,13 @@
   dense       64 views with every sector's flats and a third of the sidedefs redrawn, through the seg walk and DG_FE_AUTO
   bundle      colour, depth and labels from one submission; the label plane's holes follow GRATE1
   redone      frames redone on the host after a column overflow keep their surfaces
+              ... and read only the slot's copy: the caller's entry arrays are overwritten before dg_wait
   replay      dg_replay_slot of a batch with entries reproduces it; a slot reused after a scene with another sidedef count
   mirror      doomgpu.hpp with a sidedef and a sector changed between two render() calls
 The scene is of a WAD with a texture and a flat no map uses (surface_cases.with_extras): dg_scene_use_texture / dg_scene_use_flat
 decode and append them before the upload.
 """
+import ctypes
 import os
 import subprocess
 
@@ -139,14 +141,14 @@ def test_all_three_row_kinds_in_one_batch(dg, scene, names, wad, path1993, n_fra
     W, H = 131, 67
     n_mobjs = scene.mobj_count()
     rng = np.random.default_rng(8 + n_frames)
-    poses_of = mp.batch_cases(scene, wad, path1993, n_frames)
+    pose_cases = mp.batch_cases(scene, wad, path1993, n_frames)
     dense = sc.random_cases(wad, n_frames, seed=77 + n_frames)
     cases = []
     for k in range(n_frames):
-        f = poses_of[k].frame
+        f = pose_cases[k].frame
         sides = dense[k].sides
         sides = [sides[(j * len(sides)) // 64] for j in range(64)] if len(sides) > 64 else sides       # (the side table holds 64 per frame)
-        cases.append(sc.Case(f"all{k}", f, sides, dense[k].flats, heights=sh.random_row(wad, rng, "jitter"), poses=poses_of[k].entries,
+        cases.append(sc.Case(f"all{k}", f, sides, dense[k].flats, heights=sh.random_row(wad, rng, "jitter"), poses=pose_cases[k].entries,
                              timestamp=float(np.float32(0.25 * (k % 5)))))
     vf, keep0 = dg.make_view_surfaces([c.surfaces(names) for c in cases])
     vs, keep1 = dg.make_view_sectors([c.heights for c in cases])
@@ -517,6 +519,31 @@ def test_redone_frames_keep_their_surfaces(dg, scene, names, path1993, pixel_bat
         assert counts["front_end"] > 0 and counts["redone_frames"] > 0
         ctx.close()
     del keep
+
+
+def test_redone_frames_read_only_the_slots_copy_of_the_inputs(dg, scene, names, path1993, pixel_batch, monkeypatch):
+    """The same overflowing batch with all four inputs, and every entry array of the caller's overwritten with 0xFF bytes between the
+    submission and dg_wait: the frames redone on the host at dg_wait are drawn from the slot's kept copy alone, so they are still the
+    oracle's."""
+    W, H = 320, 200
+    n = 8
+    want = pixel_batch["oracle"](W, H)[:n]
+    monkeypatch.setenv("DOOMGPU_FE_COLUMN_SLOTS", "3")
+    for fe in (2, 3):
+        cases, views, vf, vs, poses, states, keep = _batch(dg, path1993, names, pixel_batch, n)
+        ctx = dg.Context(W, H, max_batch=n, slots=1, front_end=dg_fe(dg, fe))
+        ctx.upload_scene(scene)
+        ctx.submit_surfaces(0, views, vf, states=states, poses=poses, sectors=vs)
+        arrays = [a for k in keep for a in k]
+        assert len(arrays) == 6 * n
+        for a in arrays:
+            ctypes.memset(a, 0xFF, ctypes.sizeof(a))
+        ctx.wait(0)
+        _assert_frames(ctx.readback(0, 0, n), want, ("redone from the kept copy", fe))
+        counts = ctx.fallbacks()
+        assert counts["front_end"] > 0 and counts["redone_frames"] > 0
+        ctx.close()
+        del keep
 
 
 def test_replay_and_a_slot_reused_after_another_scene(dg, scene, names, wad1995, path1993, path1995, pixel_batch):
