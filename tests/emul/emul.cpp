@@ -206,7 +206,54 @@ static int draw_frame_lists(const Scene &sc, int W, int H, const dg_frame_lists 
 // The device column walk (fe_core.h bodies, the loops of fe_kernels.hip restated serially) on the CPU, compared span for
 // span with the host list path.  stats[0..3] = spans, parts, sprites, overflow flags; stats[4] = 1 when the column-major
 // DevRSpan list is byte-identical to the host path's; stats[5] = zero-filled sky visplane entries found by fe_gap.
+//
+// `slots` is the ctx's column slot count (DOOMGPU_FE_COLUMN_SLOTS); `span_stride` the frame's share of the span list (context.cpp: 24 x W;
+// 0 = as many as the scratch holds).  `cn` (optional) receives counts taken next to the bodies, not by them: where a frame's records put
+// each of the walk's loops (tests/column_walk_cases.py).  A frame that does not fit its span list draws nothing (dg_fe_scan).
+struct FeWalkCounts {
+    uint32_t *percol;             // [6][W]: spans of the walk, wall records, sky gap entries, sprite spans, sprite columns clipped by a record of
+                                  //         the behind row's last word, 1 where two spans of the column share a key
+    uint32_t *perbin;             // [4][w64]: parts listed, sprites listed, list position (1-based) of the part that closed the bin's last open
+                                  //           column (0: the bin stayed open), sky parts listed behind that part
+    uint64_t *misc;               // [8]: parts, sprites, behind_words, sky slots, flags, spans of the frame, gap entries, gap entries whose
+                                  //      scan for the nearest event leaves the entry's own 64-column word
+};
+static int fe_walk(void *scene, int W, int H, const dg_view *view_in, uint32_t slots, uint32_t span_stride, uint8_t *rgb, uint64_t *stats, const FeWalkCounts *cn);
 int emul_render_fe(void *scene, int W, int H, const dg_view *view_in, uint8_t *rgb, uint64_t *stats) {
+    return fe_walk(scene, W, H, view_in, FE_DEFAULT_COL_SLOTS, 0, rgb, stats, nullptr);
+}
+int emul_render_fe_slots(void *scene, int W, int H, const dg_view *view_in, uint32_t slots, uint8_t *rgb, uint64_t *stats, uint32_t *percol, uint32_t *perbin,
+                         uint64_t *misc) {
+    if (slots < 1 || slots > FE_MAX_COL_SLOTS) { g_err = "slots out of range"; return DG_ERR_INVALID; }
+    const FeWalkCounts cn{percol, perbin, misc};
+    return fe_walk(scene, W, H, view_in, slots, 24u * (uint32_t)W, rgb, stats, percol ? &cn : nullptr);
+}
+// The sprite's clip arrays once more, by hand, with and without the records of the behind row's last word: do those records decide the span?
+static bool last_word_clips(const FeParams &P, const FeFrame &ff, const FeSprite &s, const FeColumn &c, const FeRecStore &st) {
+    const uint32_t *row = P.behind + ff.behind_base + s.behind_off;
+    const size_t at0 = (size_t)c.x, W = (size_t)P.k.W;                        // (frame 0 of one)
+    int32_t tc[2] = {-1, -1}, bc[2] = {P.k.H, P.k.H};
+    for (uint32_t i = 0; i < c.nrec; i++) {
+        uint32_t part; int32_t t, b;
+        if (i < FE_NEAR_RECS) {
+            const uint32_t at = i * (uint32_t)FE_BIN_W + ((uint32_t)c.x & 63u);
+            part = st.near_part[at]; t = (int16_t)(st.near_cand[at] & 0xffffu); b = (int16_t)(st.near_cand[at] >> 16);
+        } else {
+            const FeColRec &r = P.recs[at0 + (size_t)i * W];
+            part = r.part; t = r.top_cand; b = r.bottom_cand;
+        }
+        if ((row[part >> 5] >> (part & 31)) & 1u) continue;
+        for (int k = 0; k < 2; k++) {
+            if (k == 1 && (part >> 5) == ff.behind_words - 1) continue;
+            tc[k] = std::max(tc[k], t); bc[k] = std::min(bc[k], b);
+        }
+    }
+    const int32_t by = f32_as_i16(s.bsy + ((float)c.x - s.bsx) * s.bdelta), ty = f32_as_i16(s.tsy + ((float)c.x - s.tsx) * s.tdelta);
+    int32_t ct[2], cb[2];
+    for (int k = 0; k < 2; k++) { ct[k] = std::max(0, std::max(ty, tc[k])); cb[k] = std::min(P.k.H - 1, std::min(by, bc[k])); }
+    return ct[1] <= cb[1] && (ct[0] != ct[1] || cb[0] != cb[1]);
+}
+static int fe_walk(void *scene, int W, int H, const dg_view *view_in, uint32_t slots, uint32_t span_stride, uint8_t *rgb, uint64_t *stats, const FeWalkCounts *cn) {
     const Scene &sc = *(const Scene *)scene;
     dg_view view = *view_in;
     fill_view_trig(view);
@@ -240,29 +287,35 @@ int emul_render_fe(void *scene, int W, int H, const dg_view *view_in, uint8_t *r
     FeFrame ff{0, (uint32_t)arena.parts.size(), 0, (uint32_t)arena.sprites.size(), 0, arena.behind_words, arena.n_sky_slots, 0, 0, 0, {0, 0}};
     const uint32_t w64 = (uint32_t)((W + 63) / 64);
     std::vector<uint32_t> cnt((size_t)W), col_off((size_t)W + 1), flags(1, 0);
-    std::vector<FeU4> cspans((size_t)FE_DEFAULT_COL_SLOTS * W);
-    std::vector<FeColRec> recs((size_t)FE_DEFAULT_COL_SLOTS * W);
+    std::vector<FeU4> cspans((size_t)slots * W);
+    std::vector<FeColRec> recs((size_t)slots * W);
     const size_t ev_kind = (size_t)arena.n_sky_slots * w64;               // zeroed like the product: no add, flushed
     std::vector<uint64_t> events(3 * ev_kind + 1, 0);
-    std::vector<DevRSpan> rspans((size_t)W * FE_DEFAULT_COL_SLOTS);
+    std::vector<DevRSpan> rspans((size_t)W * slots);
     FeParams P{};
     P.scene = ds; P.k = k; P.frames = &fr; P.fframes = &ff; P.parts = arena.parts.data(); P.sprites = arena.sprites.data();
     P.behind = arena.behind.data(); P.bin_off = arena.bin_off.data(); P.bin_parts = arena.bin_parts.data();
     P.sbin_off = arena.sbin_off.data(); P.sbin_sprites = arena.sbin_sprites.data(); P.cspans = cspans.data(); P.recs = recs.data(); P.cnt = cnt.data();
     P.events = events.data(); P.flags = flags.data(); P.totals = nullptr; P.col_off = col_off.data(); P.rspans = rspans.data();
-    P.n_frames = 1; P.max_sky_slots = arena.n_sky_slots; P.gap_waves = 0; P.span_stride = (uint32_t)rspans.size(); P.w64 = w64; P.col_slots = FE_DEFAULT_COL_SLOTS;
+    P.n_frames = 1; P.max_sky_slots = arena.n_sky_slots; P.gap_waves = 0; P.span_stride = span_stride ? span_stride : (uint32_t)rspans.size(); P.w64 = w64; P.col_slots = slots;
 
     // dg_fe_columns, one "lane" at a time (each bin's near records in their own little arrays, like a wave's LDS)
     std::vector<uint32_t> near_cand((size_t)FE_NEAR_RECS * FE_BIN_W);
     std::vector<uint16_t> near_part((size_t)FE_NEAR_RECS * FE_BIN_W);
     const FeRecStore st{near_cand.data(), near_part.data()};
+    if (cn) {
+        std::fill(cn->percol, cn->percol + 6 * (size_t)W, 0u);
+        std::fill(cn->perbin, cn->perbin + 4 * (size_t)w64, 0u);
+    }
     for (int x = 0; x < W; x++) {
         FeColumn c = fe_column_start(P, 0, x);
         const uint32_t bin = (uint32_t)x / FE_BIN_W;                       // the wave that owns this column walks its bin's lists
+        uint32_t closed_at = 0;
         for (uint32_t bi = arena.bin_off[bin]; bi < arena.bin_off[bin + 1]; bi++) {
             const uint32_t pi = arena.bin_parts[bi];
             const FePart &p = P.parts[pi];
             if (x < p.sx || x > p.ex) continue;
+            closed_at = bi - arena.bin_off[bin] + 1;                   // (the walk of this column ends behind the part that occludes it)
             uint32_t ev = fe_part_column(P, 0, p, pi, c, st);
             if (p.sky_slot >= 0) {
                 const uint64_t bit = 1ull << (x & 63);
@@ -278,13 +331,27 @@ int emul_render_fe(void *scene, int W, int H, const dg_view *view_in, uint8_t *r
             const uint32_t si = arena.sbin_sprites[bi];
             const FeSprite &s = P.sprites[si];
             if (s.behind_off != si * ff.behind_words) { g_err = "behind row of sprite i is not row i"; return DG_ERR_INVALID; }   // dg_fe_columns stages rows by index
-            if (x >= s.x0 && x < s.x1) fe_sprite_column(P, 0, ff, s, si, c, st, fe_behind_row(P, ff, s));
+            if (x >= s.x0 && x < s.x1) {
+                const uint32_t before = c.nsp;
+                fe_sprite_column(P, 0, ff, s, si, c, st, fe_behind_row(P, ff, s));
+                if (cn && c.nsp > before) {
+                    cn->percol[3 * (size_t)W + x]++;
+                    if (last_word_clips(P, ff, s, c, st)) cn->percol[4 * (size_t)W + x]++;
+                }
+            }
+        }
+        if (cn) {
+            cn->percol[x] = c.nsp; cn->percol[(size_t)W + x] = c.nrec;
+            // the bin closes behind the part that occluded its last open column; a column that stays open keeps the bin open to its end
+            uint32_t &cl = cn->perbin[2 * (size_t)w64 + bin];
+            if (!c.hor) cl = 0xffffffffu;
+            else if (cl != 0xffffffffu) cl = std::max(cl, closed_at);
         }
         cnt[(size_t)x] = c.nsp;
         flags[0] |= c.ovf;
     }
     // dg_fe_gaps, dg_fe_scan, dg_fe_scatter
-    uint64_t n_gaps = 0;
+    uint64_t n_gaps = 0, n_gaps_far = 0;
     if (arena.sky_parts.size() != arena.n_sky_slots) { g_err = "sky_parts / n_sky_slots mismatch"; return DG_ERR_INVALID; }
     for (uint32_t si = 0; si < ff.n_sky_slots; si++) {            // dg_fe_gaps: one wave per sky slot
         const uint32_t pi = arena.sky_parts[si];
@@ -296,15 +363,40 @@ int emul_render_fe(void *scene, int W, int H, const dg_view *view_in, uint8_t *r
             for (int x = p.sx; x <= p.ex; x++) {
                 if (!fe_gap(add, open, x, p.sx, p.ex)) continue;
                 n_gaps++;
+                if (cn) {
+                    cn->percol[2 * (size_t)W + x]++;
+                    const uint64_t evw = add[x >> 6] | ~open[x >> 6];
+                    const int b0 = x & 63;
+                    if (!(evw & ((1ull << b0) - 1ull)) || !(evw & (b0 == 63 ? 0ull : ~0ull << (b0 + 1)))) n_gaps_far++;
+                }
                 const uint32_t slot = cnt[(size_t)x]++;
-                if (slot >= FE_DEFAULT_COL_SLOTS) { flags[0] |= FE_OVF_SPANS; continue; }
+                if (slot >= slots) { flags[0] |= FE_OVF_SPANS; continue; }
                 cspans[(size_t)slot * W + (size_t)x] = FeU4{FE_KEY_PLANE | (pi << 2) | (uint32_t)kind, 0u, 0u, (uint32_t)SPAN_SKY << FES_KIND_SHIFT};
             }
         }
     }
+    uint32_t total = 0;
+    for (int x = 0; x < W; x++) total += std::min<uint32_t>(cnt[(size_t)x], slots);
+    if (total > P.span_stride) flags[0] |= FE_OVF_FRAME;                   // dg_fe_scan: every column of the frame gets no spans
+    if (cn) {
+        for (uint32_t b = 0; b < w64; b++) {
+            cn->perbin[b] = arena.bin_off[b + 1] - arena.bin_off[b];
+            cn->perbin[(size_t)w64 + b] = arena.sbin_off[b + 1] - arena.sbin_off[b];
+            uint32_t &cl = cn->perbin[2 * (size_t)w64 + b];
+            if (cl == 0xffffffffu) cl = 0;
+            for (uint32_t bi = arena.bin_off[b] + cl; cl && bi < arena.bin_off[b + 1]; bi++) cn->perbin[3 * (size_t)w64 + b] += P.parts[arena.bin_parts[bi]].sky_slot >= 0;
+        }
+        for (int x = 0; x < W; x++) {
+            const uint32_t n = std::min<uint32_t>(cnt[(size_t)x], slots);
+            for (uint32_t i = 0; i < n; i++)
+                for (uint32_t j = 0; j < i; j++) cn->percol[5 * (size_t)W + x] |= cspans[(size_t)i * W + x].x == cspans[(size_t)j * W + x].x;
+        }
+        const uint64_t m[8] = {ff.n_parts, ff.n_sprites, ff.behind_words, ff.n_sky_slots, flags[0], total, n_gaps, n_gaps_far};
+        std::copy(m, m + 8, cn->misc);
+    }
     uint32_t off = 0;
     for (int x = 0; x < W; x++) {
-        const uint32_t n = std::min<uint32_t>(cnt[(size_t)x], FE_DEFAULT_COL_SLOTS);
+        const uint32_t n = (flags[0] & FE_OVF_FRAME) ? 0u : std::min<uint32_t>(cnt[(size_t)x], slots);
         col_off[(size_t)x] = off;
         for (uint32_t i = 0; i < n; i++) {
             const FeU4 cs = cspans[(size_t)i * W + x];

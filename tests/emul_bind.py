@@ -26,6 +26,8 @@ def lib():
         L.emul_last_error.restype = ctypes.c_char_p
         L.emul_render.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
         L.emul_render_fe.argtypes = L.emul_render.argtypes
+        L.emul_render_fe_slots.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_uint32, ctypes.c_void_p,
+                                           ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.emul_draw_lists.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
         L.emul_render_state.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                         ctypes.c_uint32, ctypes.c_void_p]
@@ -153,3 +155,25 @@ class EmulScene:
         if rc:
             raise RuntimeError(f"emul rc {rc}: {lib().emul_last_error().decode()}")
         return buf.tobytes(), list(st)
+
+    def fe_walk_counts(self, W, H, rec, slots=48, timestamp=0.0):
+        """render_fe with `slots` column slots (DOOMGPU_FE_COLUMN_SLOTS) and the product's span list share (24 x W), plus counts taken
+        next to the walk's bodies: where the frame's records put each of its loops.  -> (frame bytes, stats as render_fe's, counts);
+        a frame that exceeds its span list share is flagged (stats[3] & 4) and not drawn (zeros).  counts: per column `nsp` (spans of the
+        walk), `nrec`, `gaps` (sky gap entries), `sprite_spans`, `last_word` (sprite spans whose extent a wall record of the behind
+        row's last word decides), `equal_keys`; per 64-column bin `parts`, `sprites`, `closed_at` (1-based list position of the part
+        behind which no column of the bin is open; 0: it stayed open), `sky_behind` (sky parts listed behind that); and `n_parts`,
+        `n_sprites`, `behind_words`, `sky_slots`, `flags`, `total`, `n_gaps`, `far_gaps` (gap entries whose scan leaves their word)."""
+        v = DgView(float(rec[0]), float(rec[1]), float(rec[2]), float(rec[7]), float(rec[3]), float(rec[4]), float(rec[5]), float(rec[6]),
+                   float(timestamp), 1)
+        buf = np.zeros(3 * W * H, dtype=np.uint8)
+        st = (ctypes.c_uint64 * 6)()
+        w64 = (W + 63) // 64
+        percol, perbin, misc = np.zeros((6, W), dtype=np.uint32), np.zeros((4, w64), dtype=np.uint32), np.zeros(8, dtype=np.uint64)
+        rc = lib().emul_render_fe_slots(self._h, W, H, ctypes.byref(v), slots, buf.ctypes.data, st, percol.ctypes.data, perbin.ctypes.data, misc.ctypes.data)
+        if rc:
+            raise RuntimeError(f"emul rc {rc}: {lib().emul_last_error().decode()}")
+        counts = dict(zip("nsp nrec gaps sprite_spans last_word equal_keys".split(), percol))
+        counts.update(zip("parts sprites closed_at sky_behind".split(), perbin))
+        counts.update(zip("n_parts n_sprites behind_words sky_slots flags total n_gaps far_gaps".split(), (int(m) for m in misc)))
+        return buf.tobytes(), list(st), counts
