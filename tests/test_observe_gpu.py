@@ -6,7 +6,9 @@ loaded it long ago; the tests here read the child's per-case results.
   grid       np_reduce.SIZES x np_reduce.FACTORS for (RGB, F32, NCHW), 1, 3 and 65 frames (1 and 3 at 320x200)
   combos     every source/rule x dtype x layout at every size of np_reduce.SIZES and four box sizes, the frame counts and maps taking
              turns.  A row of 64, 80 or 320 pixels is a multiple of 16 bytes in both source formats, so these take the 16-byte kernels;
-             131x67, 5x9 and 1x1 take the any-width ones; 16x16 on 5x9 and 1x1 is a box larger than the frame
+             131x67, 5x9 and 1x1 take the any-width ones; 16x16 on 5x9 and 1x1 is a box larger than the frame.  Every row of this
+             file is ONE run of its band kernel (blockIdx.x == 0), every call one launch: rows of several runs, obs_item in a short
+             last run, more than 65535 frames and offsets past 2^32 are tests/test_extents_gpu.py's
   unaligned  64x40 sources one byte (colour) or two bytes (distance) off a 16-byte boundary: the any-width kernels at a 16-byte width
   maps       every map of np_observe.MAPS / U8_MAPS on every source and dtype
   sweep      every int16 once through tensors of the four dtypes, by observe_into; observe_into's refusals

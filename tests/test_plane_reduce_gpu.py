@@ -2,7 +2,8 @@
 (np_plane_reduce).
 1. dg_reduce_planes_device between torch tensors over the grid the CPU tier runs (64x40 and 320x200 take the 16-byte kernel, 80x50 too;
    131x67, 5x9, 1x1 and a 64x40 source one element off take the any-width one; 16x16 on 5x9 is a box larger than the frame), both rules,
-   1, 3 and 65 frames, pairs left out, sentinel elements around every destination.  These cases, the call's errors and the call with
+   1, 3 and 65 frames, pairs left out, sentinel elements around every destination.  Every row here, the 1280-wide slot's included,
+   is ONE run of dg_plane_nearest (plane_reduce_px_per_wg covers about 2040 source columns), in one launch: rows of several runs, more than 65535 frames and buffers past 2^32 are tests/test_extents_gpu.py's.  These cases, the call's errors and the call with
    slots in flight run in ONE child process (tests/plane_reduce/torch_cases.py), because torch has to be imported before libdoomgpu.so
    is loaded and this session loaded it long ago; the tests here read the child's per-case results.
 2. dg_readback_planes_reduced of a bundle, a depth slot and a label slot equals the model applied to dg_readback_depth /

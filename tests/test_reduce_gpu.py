@@ -1,7 +1,9 @@
 """GPU tier of the reduced-size frames, every result byte for byte against the numpy restatement (np_reduce).
-1. dg_reduce_device between torch uint8 tensors over the grid the CPU tier runs (64x40 and 320x200 take the 16-byte kernel, 80x50,
-   131x67, 5x9 and 1x1 the any-width one; 16x16 on 5x9 is a box larger than the frame), 1, 3 and 65 frames, a source and a destination
-   offset by one byte, and sentinel bytes around the destination.  These cases, the slot's framebuffer reduced into a tensor and
+1. dg_reduce_device between torch uint8 tensors over the grid the CPU tier runs (64x40, 80x50 and 320x200 take the 16-byte kernel:
+   their rows are 192, 240 and 960 bytes; 131x67, 5x9 and 1x1 the any-width one; 16x16 on 5x9 is a box larger than the frame), 1, 3
+   and 65 frames, a source and a destination offset by one byte, and sentinel bytes around the destination.  Every row here, the
+   1280-wide slot's included, is ONE run of its kernel (reduce_px_per_wg covers about 1360 source pixels), one launch, and far below
+   2^32 bytes: rows of several runs, more than 65535 frames and buffers past 2^32 are tests/test_extents_gpu.py's.  These cases, the slot's framebuffer reduced into a tensor and
    dg_reduce_device with slots in flight run in ONE child process (tests/reduce/torch_cases.py), because torch has to be imported
    before libdoomgpu.so is loaded and this session loaded it long ago; the tests here read the child's per-case results.
 2. dg_readback_reduced of rendered frames equals the model applied to dg_readback, at 320x200 and 1280x800, sub-ranges included.
