@@ -136,6 +136,12 @@ class DgObsDesc(ctypes.Structure):
                 ("lo", ctypes.c_int32), ("hi", ctypes.c_int32), ("scale", ctypes.c_float), ("bias", ctypes.c_float), ("reserved", ctypes.c_uint32)]
 
 
+DG_PIC_OFFSETS = 1                       # dg_screen_picture.flags: the origin moves by the picture's offsets times the scale
+DG_PIC_MIRROR = 2                        # ... texel column w-1-tx
+# dg_screen_picture, one item of a frame's screen pictures
+SCREEN_PICTURE_DTYPE = np.dtype([("picture", "<i4"), ("x", "<i4"), ("y", "<i4"), ("scale_x", "<u2"), ("scale_y", "<u2"), ("light_level", "<i2"), ("flags", "<u2")])
+
+
 class DgBundleOffsets(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in "colour distance kind id cls total".split()]
 
@@ -308,6 +314,13 @@ _SIGNATURES = {
     "dg_observe_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgObsDesc), _P, ctypes.POINTER(ctypes.c_int64)]),
     "dg_observe_device": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgObsDesc), _P, ctypes.POINTER(ctypes.c_int64)]),
     "dg_ctx_observe_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
+    "dg_scene_use_picture": (ctypes.c_int, [_P, ctypes.c_char_p]),
+    "dg_scene_picture_count": (ctypes.c_int, [_P]),
+    "dg_scene_picture_info": (ctypes.c_int, [_P, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int32)] * 4),
+    "dg_overlay_host": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "dg_overlay_device": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "dg_slot_overlay": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "dg_ctx_overlay_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "dg_readback_planes_reduced": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 5),
     "dg_readback_planes_reduced_async": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgPlaneReduceDesc)] + [_P] * 5),
     "dg_seen_words": (ctypes.c_int, [_P]),
@@ -427,6 +440,36 @@ def observe_host(src, desc: DgObsDesc) -> np.ndarray:
     strides = (ctypes.c_int64 * 4)(c * oh * ow, oh * ow, ow, 1)
     _check(lib().dg_observe_host(src.ctypes.data_as(_P), w, h, n, ctypes.byref(desc), out.ctypes.data_as(_P), strides))
     return out
+
+
+def screen_pictures(items_per_frame):
+    """items[] and first[n + 1] of a batch's screen pictures from a list, one entry per frame, of lists of tuples
+    (picture, x, y[, scale_x[, scale_y[, light_level[, flags]]]]) — scales default to 1, the light to 255, the flags to 0.
+    Returns (items, first): a SCREEN_PICTURE_DTYPE array and a uint32 array."""
+    defaults = (1, 1, 255, 0)
+    rows, first = [], [0]
+    for frame in items_per_frame:
+        for it in frame:
+            it = tuple(it)
+            if not 3 <= len(it) <= 7:
+                raise ValueError("a screen picture is (picture, x, y[, scale_x[, scale_y[, light_level[, flags]]]])")
+            rows.append(it + defaults[len(it) - 3:])
+        first.append(len(rows))
+    items = np.array(rows, dtype=SCREEN_PICTURE_DTYPE) if rows else np.zeros(0, dtype=SCREEN_PICTURE_DTYPE)
+    return items, np.array(first, dtype=np.uint32)
+
+
+def overlay_host(scene, frames, items_per_frame):
+    """dg_overlay_host: the screen pictures items_per_frame (screen_pictures) drawn in place on frames, an (n, H, W, 3) uint8
+    C-contiguous array with one list per frame; returns frames."""
+    if not (isinstance(frames, np.ndarray) and frames.dtype == np.uint8 and frames.ndim == 4 and frames.shape[3] == 3 and frames.flags.c_contiguous and frames.flags.writeable):
+        raise ValueError("frames must be a writeable C-contiguous (n, H, W, 3) uint8 array")
+    n, h, w, _ = frames.shape
+    if len(items_per_frame) != n:
+        raise ValueError("one list of screen pictures per frame")
+    items, first = screen_pictures(items_per_frame)
+    _check(lib().dg_overlay_host(scene._h, frames.ctypes.data_as(_P), w, h, n, items.ctypes.data_as(_P), first.ctypes.data_as(_P)))
+    return frames
 
 
 def reduce_planes_host(desc, distance=None, kind=None, id=None, cls=None) -> dict:
@@ -781,6 +824,20 @@ class Scene:
         """dg_scene_use_flat: a flat handle for `name`, its lump (or its whole animated list) loaded now if the map did not use it.
         Call before Context.upload_scene."""
         return _check(lib().dg_scene_use_flat(self._h, name.encode()))
+
+    def use_picture(self, name: str) -> int:
+        """dg_scene_use_picture: the handle of the picture lump `name` (a sprite lump, a patch, any lump in picture format), decoded now
+        if the scene does not hold it.  Call before Context.upload_scene."""
+        return _check(lib().dg_scene_use_picture(self._h, name.encode()))
+
+    def picture_count(self) -> int:
+        return _check(lib().dg_scene_picture_count(self._h))
+
+    def picture_info(self, picture: int):
+        """dg_scene_picture_info: (w, h, left_offset, top_offset) of a picture handle."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        _check(lib().dg_scene_picture_info(self._h, picture, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def sidedef_count(self) -> int:
         return _check(lib().dg_scene_sidedef_count(self._h))
@@ -1230,6 +1287,24 @@ class Context:
         """dg_ctx_observe_kernel_ms: GPU time of the last observe_device call's kernel."""
         ms = ctypes.c_float()
         _check(lib().dg_ctx_observe_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def overlay_device(self, frames_ptr: int, width: int, height: int, items_per_frame):
+        """dg_overlay_device: the screen pictures items_per_frame (screen_pictures: one list per frame) drawn on the RGB24 frames at
+        device address frames_ptr (synchronous; touches no slot)."""
+        items, first = screen_pictures(items_per_frame)
+        _check(lib().dg_overlay_device(self._h, _P(frames_ptr), width, height, len(items_per_frame), items.ctypes.data_as(_P), first.ctypes.data_as(_P)))
+
+    def slot_overlay(self, slot: int, first_frame: int, items_per_frame):
+        """dg_slot_overlay: the screen pictures items_per_frame drawn on the colour frames first_frame .. of the slot's last submission,
+        one list per frame, once the submission is final."""
+        items, first = screen_pictures(items_per_frame)
+        _check(lib().dg_slot_overlay(self._h, slot, first_frame, len(items_per_frame), items.ctypes.data_as(_P), first.ctypes.data_as(_P)))
+
+    def overlay_kernel_ms(self) -> float:
+        """dg_ctx_overlay_kernel_ms: GPU time of the last overlay_device / slot_overlay call's kernel."""
+        ms = ctypes.c_float()
+        _check(lib().dg_ctx_overlay_kernel_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
     def plane_reduce_kernel_ms(self) -> float:

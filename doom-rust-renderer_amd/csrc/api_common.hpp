@@ -5,6 +5,7 @@
 #include "../../include/doomgpu.h"
 #include "binner.hpp"
 #include "observe_core.h"
+#include "overlay_plan.hpp"
 #include "plane_reduce_core.h"
 #include "scene.hpp"
 
@@ -51,6 +52,24 @@ inline int check_observe_call(const void *src, int width, int height, int n_fram
     const uint32_t extent[4] = {(uint32_t)n_frames, dg::obs_channels(desc->source), dg::reduce_out_dim((uint32_t)height, desc->fy), dg::reduce_out_dim((uint32_t)width, desc->fx)};
     if (!dg::obs_strides_ok(strides, extent))
         return set_err(DG_ERR_INVALID, "observe: every stride >= 1 and, sorted, each >= the one before times its extent (no two elements share an address)");
+    return DG_OK;
+}
+
+// The scene's screen pictures as the overlay's items name them (dg_overlay_host: the scene's own; dg_upload_scene: the ctx's copy).
+inline std::vector<dg::OvlPicture> overlay_pictures(const dg::Scene &sc) {
+    std::vector<dg::OvlPicture> out;
+    out.reserve(sc.pictures.size());
+    for (const int32_t id : sc.pictures) {
+        const dg::BitmapInfo &b = sc.bitmaps[(size_t)id];
+        out.push_back(dg::OvlPicture{b.w, b.h, b.left_offset, b.top_offset, b.texel_off});
+    }
+    return out;
+}
+// What dg_overlay_host, dg_overlay_device and dg_slot_overlay check alike, and the plan of a call that passed.
+inline int overlay_checked_plan(const std::vector<dg::OvlPicture> &pictures, int width, int height, int n_frames, const dg_screen_picture *items, const uint32_t *first,
+                                dg::OvlPlan &plan) {
+    if (const char *bad = dg::overlay_check((int32_t)pictures.size(), width, height, n_frames, items, first)) return set_err(DG_ERR_INVALID, bad);
+    dg::overlay_plan(pictures.data(), width, height, n_frames, items, first, plan);
     return DG_OK;
 }
 

@@ -1,7 +1,8 @@
 // api_device.cpp — the entry points of the C-ABI (include/doomgpu.h) that take a dg_ctx and are no part of a slot's lifecycle: each
 // runs on a stream of the ctx's own, created by its first use, and returns when its work is done.  The box downscale of frames in device
 // memory (dg_reduce_device), the reduced depth and label planes (dg_reduce_planes_device), the observation tensors
-// (dg_observe_device), the linedefs seen in label planes (dg_seen_lines_device, dg_slot_seen_lines — the one call here that reads a slot, once its submission is final), the floor heights of
+// (dg_observe_device), the screen pictures over colour frames (dg_overlay_device, dg_slot_overlay — which draws on a slot's frames once
+// they are final), the linedefs seen in label planes (dg_seen_lines_device, dg_slot_seen_lines — the one call here that reads a slot, once its submission is final), the floor heights of
 // recorded walks (dg_ctx_locate_walks), and the getters of their kernels' times.  The readbacks of a slot's frames and planes:
 // api_readback.cpp.  Slot, dg_ctx and the slot helpers: context.hpp.
 #include <hip/hip_runtime_api.h>
@@ -14,6 +15,7 @@
 #include "context.hpp"
 #include "explored_kernels.hpp"
 #include "observe_kernels.hpp"
+#include "overlay_kernels.hpp"
 #include "plane_reduce_kernels.hpp"
 #include "reduce_kernels.hpp"
 #include "walk.hpp"
@@ -108,6 +110,68 @@ int dg_ctx_observe_kernel_ms(dg_ctx *c, float *ms) {
     if (!c->observe.measured) return set_err(DG_ERR_INVALID, "no dg_observe_device call has launched yet");
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(c->observe.elapsed(ms));
+    return DG_OK;
+}
+
+// dg_overlay_device and dg_slot_overlay once they know the frames: the plan's records into the ctx's scratch (items, then the rectangle
+// records on a 256-byte boundary), the kernel, and the wait.  A plan without rectangles launches nothing.
+static int overlay_frames(dg_ctx *c, uint8_t *frames, int width, int height, const OvlPlan &plan, const char *name) {
+    if (plan.rects.empty()) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(side_stream(c->xstream));
+    const size_t item_bytes = plan.items.size() * sizeof(OvlItem), rects_at = (item_bytes + 255) & ~(size_t)255;
+    const size_t rect_bytes = plan.rects.size() * sizeof(OvlRect), total = rects_at + rect_bytes;
+    if (total > c->overlay_cap) {
+        c->overlay_cap = 0;
+        const size_t cap = (total + 65535) & ~(size_t)65535;
+        HIP_TRY(hip_alloc(c->d_overlay, cap));
+        c->overlay_cap = cap;
+    }
+    HIP_TRY(c->overlay.begin());
+    const hipStream_t xs = c->xstream.get();
+    uint8_t *const d = c->d_overlay.get();
+    hipError_t e = hipMemcpyAsync(d, plan.items.data(), item_bytes, hipMemcpyHostToDevice, xs);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + rects_at, plan.rects.data(), rect_bytes, hipMemcpyHostToDevice, xs);
+    if (e == hipSuccess)
+        e = launch_overlay(frames, width, height, reinterpret_cast<const OvlRect *>(d + rects_at), (uint32_t)plan.rects.size(), plan.max_tiles,
+                           reinterpret_cast<const OvlItem *>(d), c->d_palette.get(), c->d_texel_idx.get(), c->d_texel_opq.get(), xs, c->overlay.t0.get(), c->overlay.t1.get());
+    if (const int bad = finish(xs, e, name)) return bad;             // before the plan goes, whatever was queued has run
+    c->overlay.end();
+    return DG_OK;
+}
+
+int dg_overlay_device(dg_ctx *c, void *frames, int width, int height, int n_frames, const dg_screen_picture *items, const uint32_t *first) {
+    if (!c || !frames) return set_err(DG_ERR_INVALID, "null argument");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    OvlPlan plan;
+    if (const int rc = overlay_checked_plan(c->pictures, width, height, n_frames, items, first, plan)) return rc;
+    return overlay_frames(c, static_cast<uint8_t *>(frames), width, height, plan, "dg_overlay_device");
+}
+
+int dg_slot_overlay(dg_ctx *c, int slot, int first_frame, int count, const dg_screen_picture *items, const uint32_t *first) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    Slot &s = c->slots[(size_t)slot];
+    if ((rc = refuse_no_colour(s, "dg_slot_overlay"))) return rc;
+    if (first_frame < 0 || count < 0 || first_frame > s.n_frames || count > s.n_frames - first_frame) return set_err(DG_ERR_INVALID, "bad frame range");
+    if (s.phase == Slot::Phase::Prepared) return set_err(DG_ERR_INVALID, "dg_slot_overlay: the slot's views are prepared and have not run (dg_replay_slot)");
+    if (s.copy_pending) return set_err(DG_ERR_INVALID, "dg_slot_overlay: an asynchronous readback of the slot is pending (dg_wait completes it)");
+    OvlPlan plan;
+    if ((rc = overlay_checked_plan(c->pictures, c->cfg.width, c->cfg.height, count, items, first, plan))) return rc;
+    if (plan.rects.empty()) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if ((rc = make_final(c, s, Copy::Leave))) return rc;
+    const size_t W = (size_t)c->cfg.width, H = (size_t)c->cfg.height;
+    uint8_t *const frames = s.d_fb.get() + s.layout(W, H).colour + (size_t)first_frame * 3u * W * H;
+    return overlay_frames(c, frames, c->cfg.width, c->cfg.height, plan, "dg_slot_overlay");
+}
+
+int dg_ctx_overlay_kernel_ms(dg_ctx *c, float *ms) {
+    if (!c || !ms) return set_err(DG_ERR_INVALID, "null argument");
+    if (!c->overlay.measured) return set_err(DG_ERR_INVALID, "no dg_overlay_device or dg_slot_overlay call has launched yet");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(c->overlay.elapsed(ms));
     return DG_OK;
 }
 

@@ -1,7 +1,7 @@
 // api_scene.cpp — the entry points of the C-ABI (include/doomgpu.h) that need no GPU: the error string and the version, the scene
 // (dg_scene_*), one frame's lists and map lines on the host, the recorded walks, the box downscale on the host (dg_reduced_size,
 // dg_reduce_host), the reduced depth and label planes (dg_plane_reduced_size, dg_reduce_planes_host), the observation tensors
-// (dg_observed_size, dg_observe_host), the depth planes, the label planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host, dg_label_lists_host,
+// (dg_observed_size, dg_observe_host), the screen pictures (dg_scene_use_picture, dg_overlay_host), the depth planes, the label planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host, dg_label_lists_host,
 // dg_bundle_lists_host: one rule, plane_lists_host), a bundle's slab layout (dg_bundle_layout), and the explored-map frames' host rules
 // (dg_seen_words, dg_seen_lines_host, dg_seen_accumulate_host, dg_explored_map_host) and the player-centred map frames' (dg_ego_map_lines,
 // dg_ego_map_host).  Everything that takes a dg_ctx: context.cpp (a slot's submissions), api_readback.cpp (what reads a slot) and
@@ -275,6 +275,53 @@ int dg_scene_use_flat(dg_scene *s, const char *name) {
     std::string err;
     const int h = s->sc->use_flat(name, err);
     return h < 0 ? set_err(DG_ERR_WAD, err) : h;
+}
+
+int dg_scene_use_picture(dg_scene *s, const char *name) {
+    if (!s || !name) return set_err(DG_ERR_INVALID, "null argument");
+    std::string err;
+    const int h = s->sc->use_picture(name, err);
+    return h < 0 ? set_err(DG_ERR_WAD, err) : h;
+}
+
+int dg_scene_picture_count(const dg_scene *s) { return s ? (int)s->sc->pictures.size() : set_err(DG_ERR_INVALID, "null scene"); }
+
+int dg_scene_picture_info(const dg_scene *s, int picture, int32_t *w, int32_t *h, int32_t *left, int32_t *top) {
+    if (!s || picture < 0 || (size_t)picture >= s->sc->pictures.size()) return set_err(DG_ERR_INVALID, "not a picture handle of the scene");
+    const BitmapInfo &b = s->sc->bitmaps[(size_t)s->sc->pictures[(size_t)picture]];
+    if (w) *w = b.w;
+    if (h) *h = b.h;
+    if (left) *left = b.left_offset;
+    if (top) *top = b.top_offset;
+    return DG_OK;
+}
+
+// The walk of dg_overlay_tiles (overlay_kernels.hip) on the host: the plan's rectangle records tile by tile, and per pixel the items from
+// the last to the first until one has a Some texel there.
+int dg_overlay_host(const dg_scene *s, uint8_t *frames, int width, int height, int n_frames, const dg_screen_picture *items, const uint32_t *first) {
+    if (!s || !frames) return set_err(DG_ERR_INVALID, "null argument");
+    const Scene &sc = *s->sc;
+    OvlPlan plan;
+    if (const int rc = overlay_checked_plan(overlay_pictures(sc), width, height, n_frames, items, first, plan)) return rc;
+    const size_t W = (size_t)width, frame_bytes = 3u * W * (size_t)height;
+    for (const OvlRect &r : plan.rects)
+        for (uint32_t t = r.tile0; t < r.tile0 + r.tiles; t++) {
+            const int32_t tx0 = (int32_t)(r.x0 + (t % r.tiles_x) * OVL_TILE_W), ty0 = (int32_t)(r.y0 + (t / r.tiles_x) * OVL_TILE_H);
+            for (int32_t py = ty0; py < ty0 + (int32_t)OVL_TILE_H && py < (int32_t)r.y1; py++)
+                for (int32_t px = tx0; px < tx0 + (int32_t)OVL_TILE_W && px < (int32_t)r.x1; px++)
+                    for (uint32_t k = r.item1; k > r.item0; k--) {
+                        const OvlItem &it = plan.items[k - 1u];
+                        if (!ovl_covers(it, px, py)) continue;
+                        const uint32_t o = ovl_texel(it, px, py);
+                        if (!sc.texel_opq[o]) continue;
+                        const uint8_t *const pal = sc.palette + 3u * sc.texel_idx[o];
+                        const uint32_t rgb = ovl_colour(it, (uint32_t)pal[0] | ((uint32_t)pal[1] << 8) | ((uint32_t)pal[2] << 16));
+                        uint8_t *const p = frames + (size_t)r.frame * frame_bytes + ((size_t)py * W + (size_t)px) * 3u;
+                        p[0] = (uint8_t)rgb; p[1] = (uint8_t)(rgb >> 8); p[2] = (uint8_t)(rgb >> 16);
+                        break;
+                    }
+        }
+    return DG_OK;
 }
 
 int dg_scene_sidedef_count(const dg_scene *s) { return s ? (int)s->sc->sidedefs.size() : set_err(DG_ERR_INVALID, "null scene"); }

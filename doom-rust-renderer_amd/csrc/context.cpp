@@ -1315,6 +1315,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     const Scene &sc = *scene->sc;
     c->d_palette.reset(); c->d_texel_idx.reset(); c->d_texel_opq.reset();
     c->d_flats = nullptr;               // inside d_texel_idx's allocation
+    c->pictures.clear();                // (their texels went with the planes)
     // the slots' prepared records point into the device scene that was just freed: nothing may be replayed from them
     for (Slot &s : c->slots) { s.reset(); s.per_scene.drop(); }                   // (the box table is sized by the scene's map objects, a mask row by its linedefs)
     // ... and what was derived from the old scene goes (a new scene may reuse the old one's address and revision).  The slots are drained;
@@ -1348,6 +1349,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     c->fx = sc.fx;                                      // the effects' setters (and dg_scene_mobj_event) take effect here
     c->fe_scene_ok = sky.w >= 256 && sky.h >= 128;    // a smaller sky bitmap is an index panic only when a sky visplane is drawn: host path
     c->uploaded_texels = sc.texel_idx.size();
+    c->pictures = overlay_pictures(sc);
     c->uploaded_flats = sc.flat_pool.size(); c->uploaded_anims = sc.anim.size();
     c->fs_scene_ok = false;
     if (c->fs_enabled && c->fe_scene_ok && sc.fs_ok && c->cfg.width <= FS_MAX_W) {

@@ -336,6 +336,12 @@ struct dg_ctx {
     TimedInterval plane_reduce;         // dg_reduce_planes_device: the same stream, events of its own
     TimedInterval observe;              // dg_observe_device: likewise
     TimedInterval seen, seen_acc;       // dg_seen_lines_device / dg_slot_seen_lines: the events of the last call's kernels, on xstream
+    // dg_overlay_device / dg_slot_overlay: the scene's screen pictures as of dg_upload_scene (a handle beyond them was loaded since), the
+    // device scratch a call stages its item and rectangle records in (grown when a call needs more), and the last call's kernel, on xstream
+    std::vector<OvlPicture> pictures;
+    DevPtr<uint8_t> d_overlay;
+    size_t overlay_cap = 0;
+    TimedInterval overlay;
 
     // The members' owners free the memory, the streams and the events: with the ctx's device current, and only after every stream that
     // may still use them has drained.  (A ctx whose creation failed half way comes here with some of them still empty.)

@@ -487,6 +487,24 @@ int Scene::use_texture(const std::string &name, std::string &err) {
     }
 }
 
+// dg_scene_use_picture: Pictures::get (pictures.rs:38-47) through the loader's picture_bitmap — the bitmap a sprite frame of that lump
+// shares when one was loaded first.  A lump that fails to decode leaves nothing behind: add_bitmap runs after the decode.
+int Scene::use_picture(const std::string &name, std::string &err) {
+    try {
+        Builder b = Builder::resume(*this);
+        const size_t before = bitmaps.size();
+        const int id = b.picture_bitmap(name, false);
+        if (bitmaps.size() != before) { revision++; rebuild_fs_tables(); }
+        const auto at = std::find(pictures.begin(), pictures.end(), id);
+        if (at != pictures.end()) return (int)(at - pictures.begin());
+        pictures.push_back(id);
+        return (int)pictures.size() - 1;
+    } catch (const std::exception &ex) {
+        err = ex.what();
+        return -1;
+    }
+}
+
 // dg_scene_use_flat: Flats::get_animated by the loader's rule (the SECTORS loop of load_scene_from_wad): a member of an animated list
 // is that list, every member loaded; any other name is its lump.  A list whose members are already one of Scene::anim is that one.
 int Scene::use_flat(const std::string &name, std::string &err) {

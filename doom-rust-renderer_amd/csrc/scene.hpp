@@ -140,7 +140,8 @@ struct Scene {
     std::vector<SpriteFrameRec> sprite_frames;
     std::vector<std::string> sprite_frame_keys;     // "SPRT<frame>"
     int32_t sky_bitmap = TEX_UNKNOWN;
-    uint64_t revision = 0;                          // bumped by the mutable-state setters
+    std::vector<int32_t> pictures;                  // screen pictures (dg_scene_use_picture): the handle indexes this, the entry is a bitmap id
+    uint64_t revision = 0;                         // bumped by the mutable-state setters
     std::vector<int16_t> wad_light;                 // per sector its level as the WAD holds it (the light effects' max and surrounding min)
     // as last set by set_wall_effects, set_light_effects and set_mobj_thinkers / mobj_event (dg_build_lists, dg_scene_sector_lights_at and
     // dg_scene_mobj_states_at read it)
@@ -183,6 +184,10 @@ struct Scene {
     // or every member of its animation list — loaded when new (-1 with err when a lump is missing).
     int use_texture(const std::string &name, std::string &err);
     int use_flat(const std::string &name, std::string &err);
+    // dg_scene_use_picture: the handle of Pictures::get(name) — the lump of that name anywhere in the WAD, decoded as the
+    // loader decodes patches and sprites and appended when the scene does not hold it yet (-1 with err when there is no such lump or it
+    // does not decode).  The same name gives the same handle.
+    int use_picture(const std::string &name, std::string &err);
     bool is_wall_texture(int32_t id) const { return id >= 0 && (size_t)id < bitmap_names.size() && bitmap_names[(size_t)id].compare(0, 2, "T:") == 0; }
     bool is_flat_handle(int32_t h) const {
         if (h < 0 || (h & FS_FLAT_MISSING)) return false;

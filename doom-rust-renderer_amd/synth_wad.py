@@ -816,6 +816,26 @@ def _route_from_build(seed, heavy, vanilla=False, grid=None, n_things=None):
     return route[:-1]  # closed loop: last point == first
 
 
+def append_lumps(wad: bytes, lumps) -> bytes:
+    """A copy of the WAD with the (name, bytes) lumps added behind its last lump: the data in front of a new directory at the end."""
+    n, off = struct.unpack_from("<II", wad, 4)
+    data, directory = bytearray(wad), bytearray(wad[off:off + 16 * n])
+    for name, blob in lumps:
+        directory += struct.pack("<II", len(data), len(blob)) + _name8(name)
+        data += blob
+    struct.pack_into("<II", data, 4, n + len(lumps), len(data))
+    return bytes(data + directory)
+
+
+def hud_lumps(seed: int = 1993):
+    """The pictures of a screen that no map lump names: ("STBAR", a 320 x 32 status bar without holes) and ("XHAIR", a 9 x 9 cross,
+    holes everywhere else, offsets at its centre)."""
+    rng = XorShift32(seed ^ 0x48554421)
+    bar = [[96 + ((x // 8 + y // 8) & 7) if rng.below(16) else 4 for x in range(320)] for y in range(32)]
+    cross = [[176 if (x == 4 or y == 4) and abs(x - 4) + abs(y - 4) >= 2 else None for x in range(9)] for y in range(9)]
+    return [("STBAR", _picture_lump(320, 32, bar)), ("XHAIR", _picture_lump(9, 9, cross, 4, 4))]
+
+
 def wad_directory(wad: bytes):
     n, off = struct.unpack_from("<II", wad, 4)
     out = []

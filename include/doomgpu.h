@@ -894,12 +894,63 @@ int dg_slot_sector_flats(dg_ctx *ctx, int slot, int first, int count, int32_t *o
  * dispatches; 0 when that submission launched neither (no surfaces, or not the seg walk). */
 int dg_slot_surface_timing(dg_ctx *ctx, int slot, float *ms);
 
+/* ---- screen pictures: weapon, status bar, crosshair over finished colour frames ----------------------
+ * The screen is not the world: a picture is laid over RGB24 frames that are already rendered, in a pass of its own, and is no input of
+ * a submission.  The reference has the parts — Pictures::get (src/graphics/pictures.rs:38-47), Bitmap::test_flat_draw
+ * (src/graphics/bitmap.rs:28-53), Picture::mirror (pictures.rs:129-147), the weapon states of src/info.rs — and never calls them from
+ * render(); this is test_flat_draw without its debugging background, with a free scale, origin and light.
+ *
+ * dg_scene_use_picture: the handle (>= 0) of the lump `name` anywhere in the WAD — sprite lumps and patches included — by the loader's
+ * case rule (to_ascii_uppercase), decoded by the loader's picture decoder and appended to the scene's bitmaps when new (no id moves;
+ * the scene's revision changes when a bitmap was added).  The same name gives the same handle.  NULL: DG_ERR_INVALID.  No such lump, or one
+ * that does not decode as a picture (a post that runs past the picture's height is an index panic in the reference): DG_ERR_WAD.
+ * Call before dg_upload_scene, like dg_scene_use_texture. */
+int dg_scene_use_picture(dg_scene *s, const char *name);
+int dg_scene_picture_count(const dg_scene *s);
+/* Size and offsets of a picture; any output may be NULL.  DG_ERR_INVALID: a NULL scene, not a handle of the scene. */
+int dg_scene_picture_info(const dg_scene *s, int picture, int32_t *w, int32_t *h, int32_t *left, int32_t *top);
+
+#define DG_PIC_OFFSETS 1u   /* origin moves left/up by the picture's offsets times the scale (vanilla's V_DrawPatch) */
+#define DG_PIC_MIRROR  2u   /* Picture::mirror, pictures.rs:129-147: texel column w-1-tx */
+typedef struct dg_screen_picture { int32_t picture; int32_t x, y; uint16_t scale_x, scale_y; int16_t light_level; uint16_t flags; } dg_screen_picture;
+/* A batch of n frames brings items[] and first[n + 1]: first[0] = 0, first[] non-decreasing, frame f owns items[first[f] .. first[f + 1])
+ * (possibly none).  The rule, all integers but the shade, for picture P of w x h with offsets l, t:
+ *   ox = x - (OFFSETS ? l * scale_x : 0),  oy = y - (OFFSETS ? t * scale_y : 0)
+ *   the item covers ox <= px < ox + w * scale_x, oy <= py < oy + h * scale_y, clipped to the frame
+ *   its texel there is tx = (px - ox) / scale_x (w - 1 - tx under MIRROR), ty = (py - oy) / scale_y
+ *   a None texel leaves the pixel alone; Some(v) sets it to diminish_color(palette[v], light_level, 0) — the palette colour at 255
+ *   the items of a frame act in list order, later over earlier.
+ * With scale 4, flags 0 and light 255 one item is test_flat_draw.  Checked first, for the whole call, and DG_ERR_INVALID with nothing
+ * drawn otherwise: every picture a handle of the scene, scales in 1..16, light_level in 0..255, x and y within +-(1 << 20), no unknown
+ * flag bits, first[] well formed, width and height in [1, 16384], n_frames >= 0, no NULL argument.
+ *
+ * dg_overlay_host draws in place on frames[n_frames][height][width][3] in host memory; needs no GPU. */
+int dg_overlay_host(const dg_scene *s, uint8_t *frames, int width, int height, int n_frames, const dg_screen_picture *items, const uint32_t *first);
+/* The same on frames in device memory on the ctx's device — the caller's, or dg_slot_framebuffer of a finished slot — of any size in
+ * [1, 16384]^2, independent of the ctx's; items and first are host arrays, staged in a scratch of the ctx's that grows as needed.  Runs
+ * on the ctx's stream that belongs to no slot (dg_reduce_device's) and returns when done.  Every covered pixel is stored once, with the
+ * colour of the topmost item that has a Some texel there; a pixel no item sets is neither read nor written.  Needs an uploaded scene;
+ * a picture loaded since dg_upload_scene is DG_ERR_INVALID until the scene is uploaded again.  n_frames = 0, or no items: DG_OK, nothing
+ * launched. */
+int dg_overlay_device(dg_ctx *ctx, void *frames_device, int width, int height, int n_frames, const dg_screen_picture *items, const uint32_t *first);
+/* ... on the colour frames [first_frame, first_frame + count) of the slot's last submission, once that is final (waits like dg_wait;
+ * frames that overflowed a capacity are redone first): views, caller-built lists, 2-D map, explored-map and player-centred map frames,
+ * and the colour part of a bundle at its place in the bundle's layout.  items / first describe `count` frames.  DG_ERR_INVALID: a depth
+ * or label slot, a bundle without DG_BUNDLE_COLOUR, an empty slot, a bad frame range, and — nothing drawn — a slot with a
+ * dg_readback_async (or reduced one) pending: that copy was promised the frames as rendered.  Afterwards dg_readback(_async),
+ * dg_frame_checksums, dg_readback_reduced(_async), dg_reduce_device and dg_observe_device see the overlaid frames.  A new submission or
+ * dg_replay_slot renders over the pictures; calling twice draws twice. */
+int dg_slot_overlay(dg_ctx *ctx, int slot, int first_frame, int count, const dg_screen_picture *items, const uint32_t *first);
+/* GPU time of the last dg_overlay_device / dg_slot_overlay call's kernel in milliseconds, from events attached to the dispatch itself.
+ * DG_ERR_INVALID: a NULL argument, no such call that launched yet. */
+int dg_ctx_overlay_kernel_ms(dg_ctx *ctx, float *ms);
+
 /* ---- misc ----------------------------------------------------------------------------------------------------- */
 const char *dg_last_error(void); /* thread-local message of the last failing call */
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors, the surfaces) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors, the surfaces, the screen pictures) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
