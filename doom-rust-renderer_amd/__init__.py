@@ -33,6 +33,7 @@ DG_BUNDLE_COLOUR, DG_BUNDLE_DEPTH, DG_BUNDLE_LABELS = 1, 2, 4   # the parts of a
 LABEL_BOX_DTYPE = np.dtype([("pixels", "<u4"), ("x0", "<i2"), ("y0", "<i2"), ("x1", "<i2"), ("y1", "<i2")])
 DG_FE_MAP_EXPLORED = 8  # dg_timing.front_end of an explored-map submission
 DG_FE_MAP_EGO = 9  # dg_timing.front_end of a player-centred map submission
+DG_FE_MAP_FLOOR = 10  # dg_timing.front_end of a floor-textured player-centred map submission
 DG_EGO_ROTATE, DG_EGO_ARROW = 1, 2   # dg_ego_map.flags
 DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
@@ -336,6 +337,12 @@ _SIGNATURES = {
     "dg_ego_map_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgEgoMap), _P, _P]),
     "dg_submit_ego_map_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P]),
     "dg_render_ego_map_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, _P]),
+    "dg_floor_map_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
+                                         ctypes.POINTER(DgViewSurfaces), _P]),
+    "dg_submit_floor_map_views": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
+                                                 ctypes.POINTER(DgViewSurfaces)]),
+    "dg_render_floor_map_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
+                                                 ctypes.POINTER(DgViewSurfaces), _P]),
     "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
     "dg_walk_free": (None, [_P]),
     "dg_walk_tics": (ctypes.c_int, [_P]),
@@ -634,6 +641,20 @@ def ego_map_host(scene, width: int, height: int, view, params, mask_row=None) ->
     _keep, mp = _mask_ptr(mask_row)
     out = np.empty((height, width, 3), dtype=np.uint8)
     _check(lib().dg_ego_map_host(scene._h, width, height, ctypes.byref(view), ctypes.byref(p), mp, out.ctypes.data_as(_P)))
+    return out
+
+
+def floor_map_host(scene, width: int, height: int, view, params, mask_row=None, state=None, surfaces=None, out=None) -> np.ndarray:
+    """dg_floor_map_host: one floor-textured player-centred map frame (H, W, 3) uint8 by the literal rule; mask_row None: every line and
+    every sector; state a (lights, mobjs) pair and surfaces a (sides, flats) pair as make_view_states / make_view_surfaces take them, or
+    None.  out: the array to fill (else a new one)."""
+    p = _ego_params(params)
+    _keep, mp = _mask_ptr(mask_row)
+    vs, _keep2 = make_view_states([state]) if state is not None else (None, None)
+    vf, _keep3 = make_view_surfaces([surfaces]) if surfaces is not None else (None, None)
+    if out is None:
+        out = np.empty((height, width, 3), dtype=np.uint8)
+    _check(lib().dg_floor_map_host(scene._h, width, height, ctypes.byref(view), ctypes.byref(p), mp, vs, vf, out.ctypes.data_as(_P)))
     return out
 
 
@@ -1096,6 +1117,26 @@ class Context:
         _keep, mp = _mask_ptr(mask)
         out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
         _check(lib().dg_render_ego_map_views(self._h, views, n, ctypes.byref(p), mp, out.ctypes.data_as(_P)))
+        return out
+
+    def submit_floor_map(self, slot: int, views, params, mask=None, states=None, surfaces=None, n=None):
+        """dg_submit_floor_map_views: floor-textured player-centred map frames (params and mask as submit_ego_map; states / surfaces:
+        one entry per view as make_view_states / make_view_surfaces take them, or None), asynchronously."""
+        p = _ego_params(params)
+        _keep, mp = _mask_ptr(mask)
+        vs, _keep2 = make_view_states(states) if states is not None else (None, None)
+        vf, _keep3 = make_view_surfaces(surfaces) if surfaces is not None else (None, None)
+        _check(lib().dg_submit_floor_map_views(self._h, slot, views, len(views) if n is None else n, ctypes.byref(p), mp, vs, vf))
+
+    def render_floor_map(self, views, params, mask=None, states=None, surfaces=None) -> np.ndarray:
+        """dg_render_floor_map_views: synchronous through slot 0; returns (n, H, W, 3) uint8."""
+        n = len(views)
+        p = _ego_params(params)
+        _keep, mp = _mask_ptr(mask)
+        vs, _keep2 = make_view_states(states) if states is not None else (None, None)
+        vf, _keep3 = make_view_surfaces(surfaces) if surfaces is not None else (None, None)
+        out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
+        _check(lib().dg_render_floor_map_views(self._h, views, n, ctypes.byref(p), mp, vs, vf, out.ctypes.data_as(_P)))
         return out
 
     def seen_lines_device(self, width: int, height: int, n_frames: int, id_ptr: int, cls_ptr: int, seen_ptr: int):

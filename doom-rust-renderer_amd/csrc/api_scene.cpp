@@ -14,6 +14,7 @@
 #include "api_common.hpp"
 #include "binner.hpp"
 #include "ego_host.hpp"
+#include "floor_map_host.hpp"
 #include "explored_cover.hpp"
 #include "frontend.hpp"
 #include "observe_core.h"
@@ -664,6 +665,21 @@ int dg_ego_map_host(const dg_scene *s, int width, int height, const dg_view *vie
     if (rc) return rc;
     map_draw_lines_host(lines.data(), lines.size(), width, height, rgb24_out, [](size_t) { return true; });
     return DG_OK;
+}
+
+// The literal rule of the floor-textured frames (floor_map_host.hpp), with the scene's effects as last set.  Everything is checked
+// before the first byte of rgb24_out is written.
+int dg_floor_map_host(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const uint32_t *mask_row,
+                      const dg_view_state *state, const dg_view_surfaces *surfaces, uint8_t *rgb24_out) {
+    if (!s || !view || !params || !rgb24_out) return set_err(DG_ERR_INVALID, "null argument");
+    std::string err;
+    int rc = floor_check_call(*s->sc, width, height, params, err);
+    if (rc) return set_err(rc, err);
+    dg_view v = *view;
+    fill_view_trig(v);
+    rc = ego_check_view(v, err);
+    if (!rc) rc = floor_frame_host(*s->sc, &s->sc->fx.light, width, height, v, *params, mask_row, state, surfaces, rgb24_out, err);
+    return rc ? set_err(rc, err) : DG_OK;
 }
 
 }  // extern "C"

@@ -40,6 +40,8 @@
 #include "context.hpp"
 #include "ego_host.hpp"
 #include "ego_kernels.hpp"
+#include "floor_map_host.hpp"
+#include "floor_map_kernels.hpp"
 #include "explored_cover.hpp"
 #include "explored_kernels.hpp"
 #include "map_kernels.hpp"
@@ -667,13 +669,15 @@ int build_map_layer(dg_ctx *c, Slot &s) {
 
 // Host tables into device memory on the kernel stream, between the slot's ev_start / ev_setup; done when it returns (the host copies may go).
 struct TableCopy { void *dst; const void *src; size_t bytes; };
-int upload_timed(dg_ctx *c, Slot &s, std::initializer_list<TableCopy> copies) {
+int upload_timed(dg_ctx *c, Slot &s, const TableCopy *copies, size_t n) {
     HIP_TRY(hipEventRecord(s.ev_start.get(), c->kstream.get()));
-    for (const TableCopy &k : copies) HIP_TRY(hipMemcpyAsync(k.dst, k.src, k.bytes, hipMemcpyHostToDevice, c->kstream.get()));
+    for (size_t k = 0; k < n; k++)
+        if (copies[k].bytes) HIP_TRY(hipMemcpyAsync(copies[k].dst, copies[k].src, copies[k].bytes, hipMemcpyHostToDevice, c->kstream.get()));
     HIP_TRY(hipEventRecord(s.ev_setup.get(), c->kstream.get()));
     HIP_TRY(hipStreamSynchronize(c->kstream.get()));
     return DG_OK;
 }
+int upload_timed(dg_ctx *c, Slot &s, std::initializer_list<TableCopy> copies) { return upload_timed(c, s, copies.begin(), copies.size()); }
 
 // The explored-map frames' cover of the uploaded scene at the ctx's frame size, built on the host (explored_cover.hpp).
 int upload_explored_cover(dg_ctx *c, Slot &s) {
@@ -704,6 +708,41 @@ int upload_ego_table(dg_ctx *c, Slot &s) {
     return DG_OK;
 }
 
+// The floor-textured map frames' tables of the uploaded scene (floor_tables) in one allocation — and, in the same timed upload, the
+// player-centred frames' line table when no submission has made it yet: dg_floor_map_tiles reads both.
+int upload_floor_table(dg_ctx *c, Slot &s) {
+    const Scene &sc = *c->scene;
+    FloorHostTables t;
+    floor_tables(sc, t);
+    SlabCursor cur;
+    const size_t at_segs = cur.take(t.segs.size() * sizeof(FloorSeg)), at_nodes = cur.take(sc.walk_nodes.size() * sizeof(WalkNode));
+    const size_t at_leaves = cur.take(t.leaves.size() * sizeof(FloorLeaf)), at_lines = cur.take(t.lines.size() * sizeof(FloorLine));
+    DevPtr<uint8_t> table, ego;
+    HIP_TRY(hip_alloc(table, std::max<size_t>(cur.end(), 16)));
+    uint8_t *const d = table.get();
+    std::vector<TableCopy> copies{{d + at_segs, t.segs.data(), t.segs.size() * sizeof(FloorSeg)}, {d + at_nodes, sc.walk_nodes.data(), sc.walk_nodes.size() * sizeof(WalkNode)},
+                                  {d + at_leaves, t.leaves.data(), t.leaves.size() * sizeof(FloorLeaf)}, {d + at_lines, t.lines.data(), t.lines.size() * sizeof(FloorLine)}};
+    std::vector<EgoLine> lines;
+    std::vector<uint32_t> words;
+    const bool with_ego = !c->per_scene.ego_table;
+    if (with_ego) {
+        ego_line_table(sc, lines, words);
+        const size_t L = lines.size();
+        HIP_TRY(hip_alloc(ego, L * (sizeof(EgoLine) + sizeof(uint32_t))));
+        copies.push_back({ego.get(), lines.data(), L * sizeof(EgoLine)});
+        copies.push_back({ego.get() + L * sizeof(EgoLine), words.data(), L * sizeof(uint32_t)});
+    }
+    if (const int bad = upload_timed(c, s, copies.data(), copies.size())) return bad;
+    dg_ctx::PerScene &p = c->per_scene;
+    if (with_ego) { p.ego_lines = (uint32_t)lines.size(); p.ego_table = std::move(ego); }
+    p.floor_T = FloorTables{reinterpret_cast<const WalkNode *>(d + at_nodes), (uint32_t)sc.walk_nodes.size(), reinterpret_cast<const FloorLeaf *>(d + at_leaves),
+                            (uint32_t)t.leaves.size(), reinterpret_cast<const FloorSeg *>(d + at_segs), (uint32_t)t.segs.size(), c->d_flats,
+                            (uint32_t)(c->uploaded_flats / 4096u), c->d_palette.get(), (uint32_t)sc.sectors.size()};
+    p.floor_lines = reinterpret_cast<const FloorLine *>(d + at_lines);
+    p.floor_table = std::move(table);
+    return DG_OK;
+}
+
 // The per-scene table of the slot's map kind: built by the first such submission after dg_upload_scene, which then has a timed front half.
 int ensure_map_table(dg_ctx *c, Slot &s) {
     s.map.built = false;
@@ -711,6 +750,7 @@ int ensure_map_table(dg_ctx *c, Slot &s) {
     switch (s.front_end) {
     case DG_FE_MAP: if (c->per_scene.map_layer) return DG_OK; rc = build_map_layer(c, s); break;
     case DG_FE_MAP_EXPLORED: if (c->per_scene.cover) return DG_OK; rc = upload_explored_cover(c, s); break;
+    case DG_FE_MAP_FLOOR: if (c->per_scene.floor_table) return DG_OK; rc = upload_floor_table(c, s); break;
     default: if (c->per_scene.ego_table) return DG_OK; rc = upload_ego_table(c, s); break;
     }
     s.map.built = rc == DG_OK;
@@ -758,7 +798,7 @@ int enqueue_map_frames(dg_ctx *c, Slot &s) {
     } else if (s.front_end == DG_FE_MAP_EXPLORED) {       // the cover picked through the frame's mask row + the arrow, per frame
         HIP_TRY(launch_explored_frames(t.cover.get(), t.chains.get(), s.per_scene.d_masks.get(), (uint32_t)s.per_scene.mask_words, arrow, s.n_frames, s.d_fb.get(),
                                        W, H, ks, s.ev_rstart.get(), s.ev_raster.get()));
-    } else {                                              // player-centred: one kernel
+    } else {                                              // player-centred: one kernel; floor-textured: the mask's sector rows, then one kernel
         EgoParams E{};
         E.lines = reinterpret_cast<const EgoLine *>(t.ego_table.get());
         E.words = reinterpret_cast<const uint32_t *>(t.ego_table.get() + (size_t)t.ego_lines * sizeof(EgoLine));
@@ -770,7 +810,13 @@ int enqueue_map_frames(dg_ctx *c, Slot &s) {
         E.scale = s.map.ego.scale; E.rotate = s.map.ego.flags & EGO_ROTATE;
         E.W = W; E.H = H;
         E.fb = s.d_fb.get(); E.n_frames = s.n_frames;
-        HIP_TRY(launch_ego_tiles(E, ks, s.ev_rstart.get(), s.ev_raster.get()));
+        if (s.front_end == DG_FE_MAP_FLOOR) {
+            const Slot::PerScene &b = s.per_scene;
+            const uint32_t seen_words = (uint32_t)floor_seen_words(*c->scene);
+            if (E.masks) HIP_TRY(launch_floor_seen_sectors(t.floor_lines, t.ego_lines, t.floor_T.n_sectors, E.masks, E.mask_words, b.d_floor_seen.get(), seen_words, s.n_frames, ks));
+            const FloorMapParams Q{E, t.floor_T, b.d_floor_cells.get(), E.masks ? b.d_floor_seen.get() : nullptr, seen_words, 1.0f / s.map.ego.scale};
+            HIP_TRY(launch_floor_map_tiles(Q, ks, s.ev_rstart.get(), s.ev_raster.get()));
+        } else HIP_TRY(launch_ego_tiles(E, ks, s.ev_rstart.get(), s.ev_raster.get()));
     }
     guard.armed = false;
     return queued(s);                                     // (never DG_FE_AUTO's measurement)
@@ -1141,12 +1187,26 @@ int ensure_slot_masks(dg_ctx *c, Slot &s, size_t words) {
     return DG_OK;
 }
 
-// What the three map submissions do alike once each has checked its own arguments: slot `slot` for n map frames of kind fe, and their
+// The slot's floor cells and sector rows (max_batch x sectors), there from its first floor-textured submission after dg_upload_scene on.
+int ensure_slot_floor(dg_ctx *c, Slot &s) {
+    Slot::PerScene &b = s.per_scene;
+    if (b.d_floor_cells) return DG_OK;
+    HIP_TRY(slot_sync(s));
+    const size_t cells = (size_t)c->cfg.max_batch * c->scene->sectors.size();
+    HIP_TRY(hip_alloc(b.h_floor_cells, cells * sizeof(FloorCell)));
+    HIP_TRY(hip_alloc(b.d_floor_seen, (size_t)c->cfg.max_batch * floor_seen_words(*c->scene) * sizeof(uint32_t)));
+    HIP_TRY(hip_alloc(b.d_floor_cells, cells * sizeof(FloorCell)));
+    return DG_OK;
+}
+
+// What the map submissions do alike once each has checked its own arguments: slot `slot` for n map frames of kind fe, and their
 // kernels enqueued.  arrow_lines(v, l, err): the kind's per-view checks and the arrow's three lines of view v (trig filled; the host owns
 // the libm trig: dg_view has no field for the head angles) into l, which starts as three empty lines.  ego: a player-centred submission's
-// parameters (else null): its views follow the arrow lines.  mask: n rows of the scene's row length, or null.
+// parameters (else null): its views follow the arrow lines.  mask: n rows of the scene's row length, or null.  cells: a floor-textured
+// submission's n rows of floor cells (else null).
 template <class ArrowLines>
-int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int n, const dg_ego_map *ego, const uint32_t *mask, ArrowLines arrow_lines) {
+int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int n, const dg_ego_map *ego, const uint32_t *mask, ArrowLines arrow_lines,
+                      const FloorCell *cells = nullptr) {
     const int W = c->cfg.width, H = c->cfg.height;
     const size_t words = seen_words((uint32_t)c->scene->linedefs.size());
     const size_t bytes = ego_views_at(n) + (ego ? (size_t)n * sizeof(EgoView) : 0), mask_bytes = mask ? (size_t)n * words * sizeof(uint32_t) : 0;
@@ -1156,6 +1216,8 @@ int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int
     if (rc) return rc;
     if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
     if (mask && (rc = ensure_slot_masks(c, s, words))) return rc;
+    if (cells && (rc = ensure_slot_floor(c, s))) return rc;
+    const size_t cell_bytes = cells ? (size_t)n * c->scene->sectors.size() * sizeof(FloorCell) : 0;
     const auto t0 = std::chrono::steady_clock::now();
     MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
     EgoView *hv = reinterpret_cast<EgoView *>(s.h_lists.get() + ego_views_at(n));
@@ -1170,12 +1232,14 @@ int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int
         if (ego) hv[i] = ego_view(v);
     }
     if (mask) std::memcpy(s.per_scene.h_masks.get(), mask, mask_bytes);
+    if (cells) std::memcpy(s.per_scene.h_floor_cells.get(), cells, cell_bytes);
     s.map = Slot::MapState{ego ? *ego : dg_ego_map{}, mask != nullptr, false};
-    s.describe(fe, n, bytes + mask_bytes, 0, 0);
+    s.describe(fe, n, bytes + mask_bytes + cell_bytes, 0, 0);
     built_from(s, nullptr, BatchInputs{}, n);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream.get()));
     if (mask) HIP_TRY(hipMemcpyAsync(s.per_scene.d_masks.get(), s.per_scene.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream.get()));
+    if (cells) HIP_TRY(hipMemcpyAsync(s.per_scene.d_floor_cells.get(), s.per_scene.h_floor_cells.get(), cell_bytes, hipMemcpyHostToDevice, s.stream.get()));
     return enqueue_kernels(c, s);
 }
 
@@ -1615,6 +1679,44 @@ int dg_submit_ego_map_views(dg_ctx *c, int slot, const dg_view *views, int n, co
 
 int dg_render_ego_map_views(dg_ctx *c, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, uint8_t *out) {
     return read_or_wait(c, 0, dg_submit_ego_map_views(c, 0, views, n, params, mask), n, out);
+}
+
+// Every check of the call and of every view comes before the slot is touched: the cells of all n views are built first.
+int dg_submit_floor_map_views(dg_ctx *c, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,
+                              const dg_view_surfaces *surfaces) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!views || !params) return set_err(DG_ERR_INVALID, "null views or params");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    const Scene &sc = *c->scene;
+    const int W = c->cfg.width, H = c->cfg.height;
+    std::string err;
+    rc = floor_check_call(sc, W, H, params, err);
+    if (rc) return set_err(rc, err);
+    if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
+    if (sc.flat_pool.size() != c->uploaded_flats || sc.anim.size() != c->uploaded_anims) return set_err(DG_ERR_INVALID, "the scene loaded new flats since dg_upload_scene: upload it again");
+    const bool arrow = (params->flags & EGO_ARROW) != 0;
+    const size_t S = sc.sectors.size();
+    static thread_local std::vector<FloorCell> cells;
+    static thread_local FloorRowScratch scratch;
+    cells.resize((size_t)n * S);
+    for (int i = 0; i < n; i++) {
+        dg_view v = views[i];
+        fill_view_trig(v);
+        dg_map_line l[3] = {};
+        rc = ego_check_view(v, err);
+        if (!rc && arrow) rc = ego_arrow_lines(W, H, v, *params, l, err);
+        if (!rc) rc = floor_view_cells(sc, &c->fx.light, v, states ? states + i : nullptr, surfaces ? surfaces + i : nullptr, scratch, cells.data() + (size_t)i * S, err);
+        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
+    }
+    return submit_map_frames(c, slot, DG_FE_MAP_FLOOR, views, n, params, mask, [&](const dg_view &v, dg_map_line *l, std::string &why) {
+        return arrow ? ego_arrow_lines(W, H, v, *params, l, why) : DG_OK;
+    }, cells.data());
+}
+
+int dg_render_floor_map_views(dg_ctx *c, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,
+                              const dg_view_surfaces *surfaces, uint8_t *out) {
+    return read_or_wait(c, 0, dg_submit_floor_map_views(c, 0, views, n, params, mask, states, surfaces), n, out);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include "binner.hpp"
 #include "fe_auto.hpp"
 #include "fe_kernels.hpp"
+#include "floor_map_core.h"
 #include "frontend.hpp"
 #include "fs_kernels.hpp"
 #include "hip_mem.hpp"
@@ -110,6 +111,11 @@ struct Slot {
         PinnedPtr<uint32_t> h_masks;     // map frames: the mask rows of the last submission that had any (staging + HBM, max_batch x
         DevPtr<uint32_t> d_masks;        // mask_words), kept for dg_replay_slot
         size_t mask_words = 0;
+        // floor-textured map frames: the cells [max_batch][sectors] of the last such submission (staging + HBM) and the
+        // sector rows [max_batch][ceil(sectors / 32)] dg_floor_seen_sectors builds from its mask rows
+        PinnedPtr<FloorCell> h_floor_cells;
+        DevPtr<FloorCell> d_floor_cells;
+        DevPtr<uint32_t> d_floor_seen;
         // per-view map-object poses, sector heights (§8n) and sector flats (§8p) through the seg walk.  Unlike the others
         // these are taken at dg_upload_scene (upload_fs_scene), so that nothing is allocated on the submit path.
         RowBuffers<PoseRows> poses;
@@ -123,7 +129,7 @@ struct Slot {
     // What a map submission (front_end DG_FE_MAP*) leaves for its kernels and for dg_replay_slot besides d_lists (the arrow lines, then a
     // player-centred submission's views) and the mask rows above: written as a whole by every such submission.
     struct MapState {
-        dg_ego_map ego{};                // DG_FE_MAP_EGO: scale and flags
+        dg_ego_map ego{};                // DG_FE_MAP_EGO, DG_FE_MAP_FLOOR: scale and flags
         bool masked = false;             // the kernel reads the slot's mask rows (a player-centred submission may come without)
         bool built = false;              // the enqueue built the kind's per-scene table: ev_start .. ev_setup time that
     } map;
@@ -176,7 +182,7 @@ struct Slot {
     }
     bool column_walk() const { return front_end == DG_FE_DEVICE || front_end == DG_FE_DEVICE_SEGS; }
     bool seg_walk() const { return front_end == DG_FE_DEVICE_SEGS; }
-    bool map_frames() const { return front_end == DG_FE_MAP || front_end == DG_FE_MAP_EXPLORED || front_end == DG_FE_MAP_EGO; }   // arrow lines at the start of d_lists
+    bool map_frames() const { return front_end == DG_FE_MAP || front_end == DG_FE_MAP_EXPLORED || front_end == DG_FE_MAP_EGO || front_end == DG_FE_MAP_FLOOR; }   // arrow lines at the start of d_lists
     // This submission has a timed front half (ev_start .. ev_setup): a depth or label submission has none, a map submission only when it
     // built its kind's per-scene table.
     bool timed_front_half() const { return front_end != DG_FE_DEPTH && front_end != DG_FE_LABELS && (!map_frames() || map.built); }
@@ -322,6 +328,9 @@ struct dg_ctx {
         DevPtr<uint32_t> cover, chains;     // explored-map frames: explored_core.h's cover and its chains (upload_explored_cover)
         DevPtr<uint8_t> ego_table;          // player-centred map frames: EgoLine per linedef, then a word per linedef (upload_ego_table)
         uint32_t ego_lines = 0;
+        DevPtr<uint8_t> floor_table;        // floor-textured map frames: segs, nodes, leaves and the linedefs' sectors (upload_floor_table)
+        FloorTables floor_T{};              // ... as dg_floor_map_tiles reads them
+        const FloorLine *floor_lines = nullptr;
         DevPtr<uint32_t> seg_line;          // dg_seen_lines_device / dg_slot_seen_lines: seg -> linedef (ensure_seen)
         DevPtr<uint32_t> seen_scratch;      // dg_slot_seen_lines: its scratch rows, sized by max_batch and the scene's row length
         DevPtr<uint8_t> walk_tables;        // dg_ctx_locate_walks: the node and leaf tables (walk_core.h)

@@ -99,12 +99,15 @@ DG_HD void ego_seg_rows(const MapSeg &s, int32_t &lo, int32_t &hi) {
     lo = s.y0 < y1 ? s.y0 : y1; hi = s.y0 < y1 ? y1 : s.y0;
 }
 
-// Four pixels' tile values as the 12 bytes of RGB24 they become, in three little-endian words.
-DG_HD void ego_pack4(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t &o0, uint32_t &o1, uint32_t &o2) {
-    const uint32_t c0 = ego_value_rgb(v0), c1 = ego_value_rgb(v1), c2 = ego_value_rgb(v2), c3 = ego_value_rgb(v3);
+// Four pixels' colours (r | g << 8 | b << 16) as the 12 bytes of RGB24 they become, in three little-endian words.
+DG_HD void ego_pack4_rgb(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t &o0, uint32_t &o1, uint32_t &o2) {
     o0 = c0 | (c1 << 24);
     o1 = (c1 >> 8) | (c2 << 16);
     o2 = (c2 >> 16) | (c3 << 8);
+}
+// ... from their tile values.
+DG_HD void ego_pack4(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t &o0, uint32_t &o1, uint32_t &o2) {
+    ego_pack4_rgb(ego_value_rgb(v0), ego_value_rgb(v1), ego_value_rgb(v2), ego_value_rgb(v3), o0, o1, o2);
 }
 
 }  // namespace dg

@@ -20,109 +20,28 @@
 #include <algorithm>
 
 #include "ego_kernels.hpp"
+#include "ego_tile_phases.h"
 
 namespace dg {
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kThreads = kEgoThreads;
+constexpr int kMaxY = kEgoMaxY;
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kMaxY = 65535;                              // frames per launch: the grid's y extent
-
+// The phases are ego_tile_phases.h's, shared with dg_floor_map_tiles.
 template <uint32_t TILE, int PX>
 __global__ void __launch_bounds__(kThreads) dg_ego_tiles(EgoParams p) {
     __shared__ __attribute__((aligned(16))) uint32_t tile[TILE];
     __shared__ MapSeg list[EGO_CHUNK];
     __shared__ uint32_t n_list[2];                        // chunk c appends through n_list[c & 1]; the other one is cleared meanwhile
-    const uint32_t tid = threadIdx.x, f = blockIdx.y;
-    const int32_t W = p.W, H = p.H;
-    const uint32_t band_rows = ego_band_rows((uint32_t)W);
-    const int32_t row0 = (int32_t)(blockIdx.x * band_rows);
-    if (row0 >= H) return;                                // (the grid has ego_bands bands: never)
-    const int32_t rows = min((int32_t)band_rows, H - row0);
-    const uint32_t px = (uint32_t)rows * (uint32_t)W;
-    if (px > TILE) return;                                // (the launcher picks TILE so: never)
-    for (uint32_t i = 4u * tid; i < px; i += 4u * kThreads)     // i + 3 < TILE: both are multiples of 4
-        *reinterpret_cast<uint4 *>(&tile[i]) = make_uint4(0u, 0u, 0u, 0u);
-    if (tid < 2u) n_list[tid] = 0u;
+    const uint32_t f = blockIdx.y;
+    EgoBand b;
+    if (!ego_band<TILE>(p.W, p.H, b)) return;
     const EgoView v = p.views[f];
-    const uint32_t *const mask = p.masks ? p.masks + (size_t)f * p.mask_words : nullptr;
-    const bool rotate = p.rotate != 0u;
-    __syncthreads();
-    uint32_t parity = 0u;
-    for (uint32_t base = 0; base < p.n_lines; base += EGO_CHUNK, parity ^= 1u) {
-        const uint32_t l = base + tid;
-        if (l < p.n_lines) {
-            const uint32_t w = p.words[l];
-            if ((w & EGO_DRAWN) && (!mask || ((mask[l >> 5] >> (l & 31u)) & 1u))) {
-                const MapSeg s = ego_band_seg(p.lines[l], w & ~EGO_DRAWN, v, p.scale, rotate, W, H, row0, rows);
-                if (s.count > 0) {
-                    const uint32_t at = atomicAdd(&n_list[parity], 1u);
-                    if (at < EGO_CHUNK) list[at] = s;     // (a chunk has EGO_CHUNK lines: always)
-                }
-            }
-        }
-        __syncthreads();
-        const uint32_t n = min(n_list[parity], EGO_CHUNK);
-        if (tid == 0u) n_list[parity ^ 1u] = 0u;          // the next chunk appends only after the barrier below
-        for (uint32_t e = tid / kWave; e < n; e += kThreads / kWave) {
-            const MapSeg s = list[e];
-            for (int32_t k = (int32_t)(tid % kWave); k < s.count; k += kWave) {
-                int32_t x, y;
-                map_seg_point(s, (int64_t)s.first + k, x, y);
-                if ((uint32_t)x < (uint32_t)W && (uint32_t)y < (uint32_t)rows) atomicMax(&tile[(uint32_t)y * (uint32_t)W + (uint32_t)x], s.rgb);
-            }
-        }
-        __syncthreads();
-    }
-    if (p.arrow) {
-        for (uint32_t a = 0; a < 3u; a++) {
-            const MapSeg s = p.arrow[(size_t)3u * f + a];
-            int32_t lo, hi;
-            ego_seg_rows(s, lo, hi);
-            if (s.count <= 0 || hi < row0 || lo >= row0 + rows) continue;
-            for (int32_t k = (int32_t)tid; k < s.count; k += kThreads) {
-                int32_t x, y;
-                map_seg_point(s, (int64_t)s.first + k, x, y);
-                y -= row0;
-                if ((uint32_t)x < (uint32_t)W && (uint32_t)y < (uint32_t)rows) atomicMax(&tile[(uint32_t)y * (uint32_t)W + (uint32_t)x], EGO_ARROW_VALUE);
-            }
-        }
-        __syncthreads();
-    }
-    uint8_t *const out = p.fb + (size_t)f * 3u * (size_t)W * (size_t)H + (size_t)3u * (size_t)row0 * (size_t)W;
-    const uint32_t n_items = px / PX;                     // PX divides px (the launcher picks PX so)
-    for (uint32_t j = tid; j < n_items; j += kThreads) {
-        if constexpr (PX == 1) {
-            const uint32_t rgb = ego_value_rgb(tile[j]);
-            uint8_t *const o = out + 3u * (size_t)j;
-            o[0] = (uint8_t)rgb; o[1] = (uint8_t)(rgb >> 8); o[2] = (uint8_t)(rgb >> 16);
-        } else if constexpr (PX == 4) {
-            const uint4 t = *reinterpret_cast<const uint4 *>(&tile[4u * j]);
-            uint32_t o0, o1, o2;
-            ego_pack4(t.x, t.y, t.z, t.w, o0, o1, o2);
-            uint32_t *const dst = reinterpret_cast<uint32_t *>(out) + (size_t)j * 3u;
-            __builtin_nontemporal_store(o0, dst);
-            __builtin_nontemporal_store(o1, dst + 1);
-            __builtin_nontemporal_store(o2, dst + 2);
-        } else {
-            uint32_t o[12];
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const uint4 t = *reinterpret_cast<const uint4 *>(&tile[16u * j + 4u * g]);
-                ego_pack4(t.x, t.y, t.z, t.w, o[3 * g], o[3 * g + 1], o[3 * g + 2]);
-            }
-            u32x4 *const dst = reinterpret_cast<u32x4 *>(out) + (size_t)j * 3u;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                u32x4 t;
-                t.x = o[4 * k]; t.y = o[4 * k + 1]; t.z = o[4 * k + 2]; t.w = o[4 * k + 3];
-                __builtin_nontemporal_store(t, dst + k);
-            }
-        }
-    }
+    ego_tile_lines(tile, list, n_list, p.lines, p.words, p.n_lines, p.masks ? p.masks + (size_t)f * p.mask_words : nullptr,
+                   p.arrow ? p.arrow + (size_t)3u * f : nullptr, v, p.scale, p.rotate != 0u, p.W, p.H, b);
+    ego_tile_store<PX>(tile, ego_band_out(p.fb, f, p.W, p.H, b), b.px, [](uint32_t w) { return ego_value_rgb(w); });
 }
 
 template <uint32_t TILE>

@@ -945,12 +945,58 @@ int dg_slot_overlay(dg_ctx *ctx, int slot, int first_frame, int count, const dg_
  * DG_ERR_INVALID: a NULL argument, no such call that launched yet. */
 int dg_ctx_overlay_kernel_ms(dg_ctx *ctx, float *ms);
 
+/* ---- floor-textured player-centred map frames: the sectors' floors under the lines ---------------------------- */
+/* The player-centred map frames above are lines on black.  The map most users of this vocabulary know draws the sectors' floor textures
+ * under the lines (ViZDoom's set_automap_render_textures, ZDoom's am_textured).  A floor-map frame of a view takes the same dg_ego_map:
+ * DG_EGO_ROTATE, DG_EGO_ARROW and the contract (W, H in [16, 16384], scale in [2^-10, 64], |view.x|, |view.y| <= 65536, |cos_a|,
+ * |sin_a| <= 1, at most 65 535 linedefs) mean what they mean there, and a pixel on which dg_ego_map_host draws a line or the arrow has
+ * exactly that colour.  Every other pixel (X, Y), every operation in f32 in this order, no contraction, inv = 1.0f / scale once per call:
+ *   1. the map point          r = ((float)(X - W/2) + 0.5f) * inv,  f = ((float)(H/2 - Y) - 0.5f) * inv     (the pixel's centre)
+ *                             DG_EGO_ROTATE:  dx = r*sin_a + f*cos_a,  dy = f*sin_a - r*cos_a      without it:  dx = r, dy = f
+ *                             mx = view.x + dx,  my = view.y + dy
+ *   2. the leaf               from the BSP's root, left of or on a node's partition (Vertex::is_left_of_line, cross <= 0) to its left
+ *                             child: get_sector_from_vertex (src/renderer/bsp.rs:9-44).  A leaf none of whose segs has a sidedef on its
+ *                             side: background.
+ *   3. inside the subsector   for every seg v1 -> v2 of the leaf in lump order:
+ *                             (mx - v1x) * (v2y - v1y) - (my - v1y) * (v2x - v1x) < 0.0f (strictly behind the seg): background.  The BSP
+ *                             gives every point of the plane a leaf, solid rock and the outside of the level included.
+ *   4. the floor              its flat: a dg_sector_flats entry of the view for the sector, else the scene's; an animated flat by
+ *                             view.timestamp (Flats::get_animated).  A missing flat or a sky floor: background.  Its light: a
+ *                             dg_sector_light entry of the view, else the light effect's level at the timestamp with DG_LIGHT_THINKERS, else
+ *                             the scene's.  Both are what the colour frame of the same view draws the floor with.
+ *   5. texel and shade        tx = f32_as_i32(floorf(mx)) & 63, ty = f32_as_i32(floorf(my)) & 63, the texel flat[ty][tx] (both axes
+ *                             positive, src/renderer/visplanes.rs:119-125); the colour diminish_color(palette[texel], light, 0).
+ * Background is (0, 0, 0).  |mx|, |my| stay below 2^24 whenever scale >= 2^-9 or W, H <= 8192 (|r|, |f| <= 8192.5 / scale, |dx|, |dy| <=
+ * |r| + |f|); the rule is defined beyond that too (the conversion saturates).
+ * With a mask row (the layout of dg_submit_ego_map_views) a linedef is drawn only if its bit is set, and a sector is shown only if at
+ * least one linedef with a sidedef facing it has its bit set; every other sector's pixels are background.  No mask: every line, every sector.
+ * state / surfaces: NULL, or the view's game state and surfaces — only state->lights and surfaces->flats are read (entries validated as
+ * for dg_submit_views_surfaces: an index out of range, a handle not of this scene, a NULL array with n > 0 are DG_ERR_INVALID).
+ * dg_timing.front_end of such a submission; never a dg_config.front_end. */
+enum { DG_FE_MAP_FLOOR = 10 };
+/* One frame (3*W*H bytes) by the literal rule, with the scene's light effects as last set.  Everything is checked before the first byte
+ * is written.  A NULL scene, view, params or rgb24_out: DG_ERR_INVALID. */
+int dg_floor_map_host(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const uint32_t *mask_row,
+                      const dg_view_state *state, const dg_view_surfaces *surfaces, uint8_t *rgb24_out);
+/* Asynchronous, exactly like dg_submit_ego_map_views: n frames at the ctx's size into the slot's framebuffer slab; states / surfaces NULL
+ * or [n].  Every check comes first: a refused call leaves the slot as it was.  It is a colour frame like the other map submissions
+ * (readbacks, checksums, reduced readbacks, dg_observe_device, dg_replay_slot, dg_slot_overlay; dg_slot_seen_lines refuses it);
+ * dg_slot_timing gives front_end = DG_FE_MAP_FLOOR, raster_ms = the per-frame kernel (dg_floor_map_tiles), setup_ms = the upload of the
+ * scene's tables (nodes, leaves, segs, the linedefs' sectors and dg_submit_ego_map_views' line table) when this submission made it, else
+ * 0.  The host ships 8 bytes per (frame, sector) — the flat and the shade factor of each sector as the view has them — and with a mask
+ * dg_floor_seen_sectors builds the sector rows on the GPU.  Errors as dg_submit_ego_map_views; a scene without subsectors: DG_ERR_INVALID. */
+int dg_submit_floor_map_views(dg_ctx *ctx, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask,
+                              const dg_view_state *states, const dg_view_surfaces *surfaces);
+/* Synchronous, slot 0: if rgb24_out != NULL copy n*3*W*H bytes to host memory. */
+int dg_render_floor_map_views(dg_ctx *ctx, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask,
+                              const dg_view_state *states, const dg_view_surfaces *surfaces, uint8_t *rgb24_out);
+
 /* ---- misc ----------------------------------------------------------------------------------------------------- */
 const char *dg_last_error(void); /* thread-local message of the last failing call */
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors, the surfaces, the screen pictures) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors, the surfaces, the screen pictures, the floor-textured map frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
@@ -960,7 +1006,7 @@ typedef struct dg_timing {
     float host_ms;            /* host list generation + binning + packing of that submission (wall clock) */
     uint64_t n_spans, n_frames, covered_pixels;
     uint64_t n_walls, n_planes, list_bytes; /* drawn records / visplanes, bytes of lists copied to HBM */
-    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH, DG_FE_LABELS, DG_FE_BUNDLE, DG_FE_MAP_EXPLORED, DG_FE_MAP_EGO): what that submission actually used; with DG_FE_DEVICE setup_ms is
+    int32_t front_end;        /* DG_FE_HOST, DG_FE_DEVICE or DG_FE_DEVICE_SEGS (DG_FE_MAP, DG_FE_DEPTH, DG_FE_LABELS, DG_FE_BUNDLE, DG_FE_MAP_EXPLORED, DG_FE_MAP_EGO, DG_FE_MAP_FLOOR): what that submission actually used; with DG_FE_DEVICE setup_ms is
                                  the column walk (dg_fe_columns, dg_fe_gaps, dg_fe_scan, dg_fe_scatter), n_walls = wall records,
                                  n_planes = sprites, covered_pixels is not tracked (0) */
 } dg_timing;
