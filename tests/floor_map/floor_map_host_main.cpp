@@ -6,7 +6,10 @@
 //   2. dg_floor_map_tiles' phases as a host loop over ego_core.h's and floor_map_core.h's functions — owner tile, lines and arrow by
 //      max, the floor phase into the words that stayed 0, the resolve in the launcher's store form — on a heap tile of exactly the
 //      band's size and a heap frame of exactly 3 W H bytes, against 1. byte for byte;
-//   3. at 131x67, dg_floor_map_host through the C-ABI against 1., and what it refuses, with the output untouched.
+//   3. at 131x67, dg_floor_map_host through the C-ABI against 1., and what it refuses, with the output untouched;
+//   4. the table sets of floor_map_tables.h (no nodes, a leaf without a sector, a leaf without segs, a chain of 200 partitions, every
+//      index the rule must refuse and its control) through floor_map_core.h's functions over heap tables of exactly the stated counts:
+//      a refused index gives background, and where no index is out of range the frame equals a literal descent written here.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -18,6 +21,7 @@
 
 #include "../../doom-rust-renderer_amd/csrc/api_common.hpp"
 #include "../../doom-rust-renderer_amd/csrc/floor_map_host.hpp"
+#include "floor_map_tables.h"
 
 #define CHECK(cond)                                                              \
     do {                                                                         \
@@ -176,6 +180,64 @@ static int phases_frame(const dg::Scene &sc, const Case &c, const dg_view &v, co
     return 0;
 }
 
+// Part 4: one pixel of a table set by a literal descent that checks no index (for sets all of whose indices are in range).
+static uint32_t literal_table_pixel(const dg::FloorTables &T, const dg::FloorCell *row, const floor_tables_test::TestView &t, int X, int Y) {
+    const float inv = 1.0f / t.scale;
+    const float r = ((float)(X - t.W / 2) + 0.5f) * inv, f = ((float)(t.H / 2 - Y) - 0.5f) * inv;
+    const float dx = t.rotate ? r * t.v.sin_a + f * t.v.cos_a : r, dy = t.rotate ? f * t.v.sin_a - r * t.v.cos_a : f;
+    const float mx = t.v.x + dx, my = t.v.y + dy;
+    int32_t c = (int32_t)T.n_nodes - 1;
+    while (c >= 0) {
+        const dg::WalkNode &n = T.nodes[c];
+        const float v2x = n.x + n.dx, v2y = n.y + n.dy;
+        const float ax = mx - n.x, ay = my - n.y, bx = v2x - n.x, by = v2y - n.y;
+        c = ax * by - ay * bx <= 0.0f ? n.child[1] : n.child[0];
+    }
+    const dg::FloorLeaf &l = T.leaves[~c];
+    if (l.sector < 0) return 0u;
+    for (uint32_t k = 0; k < l.count; k++) {
+        const dg::FloorSeg &g = T.segs[l.first + k];
+        const float ax = mx - g.v1x, ay = my - g.v1y, bx = g.v2x - g.v1x, by = g.v2y - g.v1y;
+        if (ax * by - ay * bx < 0.0f) return 0u;
+    }
+    const dg::FloorCell cell = row[l.sector];
+    if (cell.flat < 0) return 0u;
+    const int tx = (int)std::floor(mx) & 63, ty = (int)std::floor(my) & 63;
+    const uint32_t pal = T.palette[T.flats[(size_t)cell.flat * 4096 + (size_t)ty * 64 + (size_t)tx]];
+    uint32_t rgb = 0;
+    for (int ch = 0; ch < 3; ch++) {
+        const float col = (float)((pal >> (8 * ch)) & 255u) * cell.factor;
+        rgb |= (uint32_t)(col >= 255.0f ? 255 : col <= 0.0f ? 0 : (int)col) << (8 * ch);
+    }
+    return rgb;
+}
+
+static int table_sets(uint64_t &lit_all) {
+    using namespace floor_tables_test;
+    const std::vector<TableSet> sets = all_sets();
+    CHECK(sets.size() == 15);
+    for (const TableSet &s : sets) {
+        Exact e;
+        exact(s, e);
+        const std::vector<dg::FloorCell> row(s.row.begin(), s.row.begin() + s.n_sectors);       // exactly the frame's row
+        uint64_t lit = 0, px = 0;
+        for (const TestView &t : views_of(s)) {
+            std::vector<uint8_t> got((size_t)3 * (size_t)t.W * (size_t)t.H);
+            lit += rule_frame(e.T, row.data(), t, got.data());
+            px += (uint64_t)t.W * (uint64_t)t.H;
+            if (s.expect == TableSet::B_DARK) continue;     // (an index out of range: the literal descent is not defined there)
+            for (int Y = 0; Y < t.H; Y++)
+                for (int X = 0; X < t.W; X++) {
+                    const uint8_t *const q = &got[3 * ((size_t)Y * (size_t)t.W + (size_t)X)];
+                    CHECK(literal_table_pixel(e.T, row.data(), t, X, Y) == ((uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16));
+                }
+        }
+        if (!meets(s, lit, px)) { std::printf("floor_map_host_main: %s: %llu of %llu pixels lit\n", s.name.c_str(), (unsigned long long)lit, (unsigned long long)px); return 1; }
+        lit_all += lit;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 4) { std::printf("usage: floor_map_host_main WAD PATH.f32 MAP\n"); return 2; }
     std::ifstream wf(argv[1], std::ios::binary);
@@ -246,6 +308,10 @@ int main(int argc, char **argv) {
     const dg_view_surfaces sf{nullptr, 0u, &far_flat, 1u};
     CHECK(dg_floor_map_host(s, 64, 40, &v0, &good, nullptr, nullptr, &sf, &one) == DG_ERR_INVALID && one == 7);
     dg_scene_free(s);
-    std::printf("floor_map_host_main: ok (%llu lit pixels, %llu black)\n", (unsigned long long)floor_px, (unsigned long long)black_px);
+    uint64_t table_px = 0;
+    if (table_sets(table_px)) return 1;
+    CHECK(table_px > 50000);
+    std::printf("floor_map_host_main: ok (%llu lit pixels, %llu black, %llu lit on the table sets)\n", (unsigned long long)floor_px, (unsigned long long)black_px,
+                (unsigned long long)table_px);
     return 0;
 }

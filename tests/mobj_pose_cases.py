@@ -11,10 +11,17 @@ such WAD: they go through the second renderer (np_front_end.render_frame takes t
 
 Targets are integer-rounded positions of OTHER frames of the committed camera path: inside the map, spread over sectors of different
 floor heights and light levels, and a few frames ahead of the camera they are in view more often than not.  `oracle_frames` renders
-every case and asserts that more than half of the moving cases change the oracle's frame: no frame is left out of a comparison."""
+every case and asserts that more than half of the moving cases change the oracle's frame: no frame is left out of a comparison.
+
+`line_points` are entries on the hand world's partition line (tests/walk_cases.py: line_starts): points at which the side test is 0.0 and
+a fused one is not, and exact ties.  Importing this module asserts, by the numpy descent alone, that a fused test finds sector 1 where
+the rule finds sector 0 at four and more of them."""
 import struct
 
 import numpy as np
+
+import floor_map_cases as fc
+import walk_cases
 
 F = np.float32
 W, H = 160, 100                                          # the CPU tier's frame size
@@ -222,3 +229,26 @@ def model_sectors(wad: bytes, xs, ys, map_name: str = "E1M1"):
             s = nf.get_sector_from_vertex(m, (F(x), F(y)))
             out[i] = -1 if s is None else index[id(s)]
     return out
+
+
+# ---- entries on the hand world's partition line ---------------------------------------------------------------------------------------
+def line_points():
+    """(xs, ys, n_witnesses) on the hand world (fc.wad_of("hand")): the witnesses of a fused side test first, then the exact ties."""
+    return walk_cases.line_starts()
+
+
+def line_sectors(xs, ys, fused: bool = False):
+    """The numpy descent (np_floor_map.leaf_at) of every point: its sector; fused: with the side test as a contracting compiler evaluates it."""
+    m = fc.fused_model("hand", fc.SIDE) if fused else fc.model_of("hand")
+    return m.leaf_sector[m.leaf_at(np.asarray(xs, F), np.asarray(ys, F))].astype(np.int32)
+
+
+def _line_points_shown():
+    xs, ys, n = line_points()
+    rule, fused = line_sectors(xs, ys), line_sectors(xs, ys, fused=True)
+    assert n >= 4 and (rule[:n] == 0).all() and (fused[:n] == 1).all()
+    assert np.array_equal(rule[n:], fused[n:]) and set(rule[n:].tolist()) == {0, 1}
+    assert np.array_equal(rule, model_sectors(fc.wad_of("hand"), xs, ys))          # (the second renderer's descent agrees with the rule's)
+
+
+_line_points_shown()

@@ -41,7 +41,27 @@ def cycle(timestamp, n: int) -> int:
     return (2 ** 64 - 1 if t >= F(2.0 ** 64) else int(t)) % n
 
 
+ROTATION, SIDE, BEHIND_TEST = "rotation", "side", "behind"      # the places FloorModel.fused switches, each on its own
+
+
+def sum2(a, b, c, d, sign, fused: bool):
+    """a * b + sign * (c * d) over f32 arrays.  The rule's: both products rounded to f32, then their sum.  fused: what a compiler that
+    contracts makes of the same expression, fma(a, b, sign * (c * d)) — the second product rounded to f32, the first one exact (two
+    f32 factors have 48 significant bits: exact in float64), one rounding of the sum.  The sum passes through float64 on its way to f32;
+    its sign and whether it is zero, which is all the two tests read, are those of the exact sum."""
+    a, b, c, d = (np.asarray(v, F) for v in (a, b, c, d))
+    second = c * d
+    assert second.dtype == F
+    if not fused:
+        first = a * b
+        return first + second if sign > 0 else first - second
+    exact = a.astype(np.float64) * b.astype(np.float64)
+    return (exact + second.astype(np.float64) if sign > 0 else exact - second.astype(np.float64)).astype(F)
+
+
 class FloorModel:
+    fused = frozenset()                                   # test code only: of ROTATION, SIDE, BEHIND_TEST, the sums of two products evaluated as sum2's fused form
+
     def __init__(self, wad: bytes, map_name: str = "E1M1"):
         self.wad = wad
         self.ego = ng.EgoModel(wad, map_name)
@@ -103,8 +123,8 @@ class FloorModel:
             r = ((X - W // 2).astype(F) + F(0.5)) * inv
             f = ((H // 2 - Y).astype(F) - F(0.5)) * inv
             if rotate:
-                dx = r * s + f * c
-                dy = f * s - r * c
+                dx = sum2(r, s, f, c, +1, ROTATION in self.fused)
+                dy = sum2(f, s, r, c, -1, ROTATION in self.fused)
             else:
                 dx, dy = r, f
             mx, my = x + dx, y + dy
@@ -127,7 +147,7 @@ class FloorModel:
                 v2x, v2y = n[:, 0] + n[:, 2], n[:, 1] + n[:, 3]
                 ax, ay = mx[i] - n[:, 0], my[i] - n[:, 1]
                 bx, by = v2x - n[:, 0], v2y - n[:, 1]
-                left = (ax * by - ay * bx) <= F(0.0)
+                left = sum2(ax, by, ay, bx, -1, SIDE in self.fused) <= F(0.0)
                 child = self.node_child[cur[i], np.where(left, 1, 0)]
                 sub = (child & 0x8000) != 0
                 leaf[i[sub]] = child[sub] & 0x7FFF
@@ -145,7 +165,7 @@ class FloorModel:
                 for v1, v2, _, _ in self.segs[first:first + count]:
                     ax, ay = mx[at] - self.vx[v1], my[at] - self.vy[v1]
                     bx, by = F(self.vx[v2] - self.vx[v1]), F(self.vy[v2] - self.vy[v1])
-                    out[at] |= (ax * by - ay * bx) < F(0.0)
+                    out[at] |= sum2(ax, by, ay, bx, -1, BEHIND_TEST in self.fused) < F(0.0)
         return out
 
     def shown_sectors(self, mask_row):

@@ -5,6 +5,8 @@ The band decomposition and the store forms are dg_ego_tiles' (tests/test_ego_gpu
    64x40     one band, 16-byte stores              44x41     dword stores, one band
    300x41    dword stores, two bands               131x67    byte stores, two bands
    320x200   eight bands, 16-byte stores           1280x800  6-row bands, the last of 2 rows
+Pixel centres within a rounding of a partition line, exactly on it, on segs and vertices, and the contract's corners (scales 2^-10 and 64,
+|view| 65536, 16384x16) are held against the host and the numpy model (floor_map_cases.WITNESS_CASES, TIE_CASES, CORNER_CASES).
 Every size runs every case of floor_map_cases.py as a submission of three frames (the case's view moved along x, a mask row of its own
 per frame, the case's light and flat entries in the first and the last frame): masks, states, surfaces, the light effects, animated flats and
 a sky floor are among the cases.  Frames narrower or lower than 16 pixels (8200x2, and the 65 537 frames of 4x1 that cross the grid's y
@@ -104,6 +106,58 @@ def test_one_frame_against_the_numpy_model(dg, scenes):
         ctx.close()
 
 
+def _render_cases(dg, ctx, sc, cases):
+    """The cases' own views as one submission: they share scale and flags; a mask row, if any has one, per frame."""
+    c0 = cases[0]
+    assert all((c["scale"], c["flags"], c["world"]) == (c0["scale"], c0["flags"], c0["world"]) and not c["lights"] and not c["flats"] for c in cases)
+    views = (dg.DgView * len(cases))(*[fc.view_of(dg, c) for c in cases])
+    masks = None if c0["mask"] is None else np.stack([fc.mask_row(c) for c in cases])
+    return ctx.render_floor_map(views, (c0["scale"], c0["flags"]), masks)
+
+
+def _check_against_host_and_model(dg, sc, cases, W, H, what):
+    ctx = dg.Context(W, H, max_batch=len(cases), slots=1)
+    ctx.upload_scene(sc)
+    got = _render_cases(dg, ctx, sc, cases)
+    ctx.close()
+    for k, c in enumerate(cases):
+        host = dg.floor_map_host(sc, W, H, fc.view_of(dg, c), (c["scale"], c["flags"]), fc.mask_row(c))
+        want = fc.model_frame(c, W, H)
+        assert want.any()
+        print(f"{what} {c['name']} {W}x{H}: {int((got[k] != host).any(axis=2).sum())} pixels differ from the host's, {int((got[k] != want).any(axis=2).sum())} from the model's")
+        assert np.array_equal(got[k], host) and np.array_equal(got[k], want), (what, c["name"], W, H)
+
+
+@pytest.mark.parametrize("size", fc.SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_witnesses_of_a_fused_side_test(dg, scenes, size):
+    """floor_map_cases.WITNESS_CASES as one batch: pixel centres at which the rule's side test is 0.0 and a fused one is not (the import
+    asserts what a fused model draws there), and the rotated view of which a fused rotation changes 16 pixels and more at 320x200.  A
+    library built with contraction on fails here."""
+    _check_against_host_and_model(dg, scenes["hand"], fc.WITNESS_CASES, *size, "witness")
+    _check_against_host_and_model(dg, scenes["light"], [fc.ROTATION_WITNESS], *size, "witness")
+
+
+@pytest.mark.parametrize("size", fc.SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_pixel_centres_exactly_on_partition_segs_and_vertices(dg, scenes, size):
+    """floor_map_cases.TIE_CASES: the descent's <= and floor_behind's < where the test is exactly 0.0."""
+    for c in fc.TIE_CASES:
+        _check_against_host_and_model(dg, scenes["hand"], [c], *size, "tie")
+
+
+@pytest.mark.parametrize("c", fc.CORNER_CASES, ids=lambda c: c["name"])
+def test_the_corners_of_the_contract(dg, scenes, c):
+    _check_against_host_and_model(dg, scenes[c["world"]], [c], *c["size"], "corner")
+
+
+def test_the_wave_shapes_the_cases_name(dg, scenes):
+    """floor_map_cases asserts at import which waves occur in WAVE_CASES at 131x67, cut as the kernel cuts them: no wanting lane, the
+    first wanting lane in the upper half, only lane 63, a partial last wave, whole waves past the band, parting at the root and at the
+    last node above the leaves."""
+    for name in fc.WAVE_CASES:
+        c = fc.BY_NAME[name]
+        _check_against_host_and_model(dg, scenes[c["world"]], [c], 131, 67, "waves")
+
+
 def test_three_frames_at_1280x800(dg, scenes):
     W, H = 1280, 800
     assert _shape(W, H) == SHAPES[(W, H)] and H % 6 == 2
@@ -132,6 +186,19 @@ def test_the_launcher_past_the_grid_extent_and_on_the_wide_tile(tmp_path):
                            "-o", str(exe), os.path.join(HERE, "floor_map", "floor_map_launch_main.hip"), os.path.join(csrc, "floor_map_kernels.hip")])
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "floor_map_launch_main: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_the_kernel_on_tables_no_map_has_and_on_indices_it_must_refuse(tmp_path):
+    """tests/floor_map/floor_map_tables_main.hip: dg_floor_map_tiles on tables built in the program (floor_map_tables.h) — no nodes, a leaf
+    without a sector, a leaf without segs, a chain of 200 partitions, and a child, leaf, sector, seg range and flat out of range, each on
+    device tables whose slack holds decoys that would light the pixel — against the rule's functions on the host.  It checks its own
+    results."""
+    csrc = os.path.join(ROOT, "doom-rust-renderer_amd", "csrc")
+    exe = tmp_path / "floor_map_tables_main"
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
+                           "-o", str(exe), os.path.join(HERE, "floor_map", "floor_map_tables_main.hip"), os.path.join(csrc, "floor_map_kernels.hip")])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "floor_map_tables_main: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 def test_timing_readbacks_overlay_and_replay(dg, scenes):

@@ -6,6 +6,8 @@ per-pixel rule at 5x3, 131x67, 1x1 and 8200x2 — as a stand-alone program under
            the rule at 1x1 is the stand-alone program's to check, below the C-ABI
   cases    scales 0.05, 0.1, 0.25, 0.5, 1 and 16; rotated and not; with and without mask, arrow, light entries and flat entries; the
            light effects on; an animated flat at three timestamps; a sky floor
+  lines    pixel centres within a rounding of a partition line, exactly on it, on a seg and on a vertex (floor_map_cases.WITNESS_CASES,
+           TIE_CASES), at 131x67 and 320x200; the contract's corners: scales 2^-10 and 64, |view.x| = |view.y| = 65536, 16384x16
   errors   every refusal, with the output untouched after each
 """
 import ctypes
@@ -40,6 +42,25 @@ def test_frames_equal_the_model(dg, scenes, c, size):
     got = _host(dg, scenes[c["world"]], c, W, H)
     want = fc.model_frame(c, W, H)
     assert np.array_equal(got, want), (c["name"], W, H, int((got != want).any(axis=2).sum()))
+
+
+@pytest.mark.parametrize("size", fc.SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("c", fc.WITNESS_CASES + fc.TIE_CASES + [fc.ROTATION_WITNESS], ids=lambda c: c["name"])
+def test_pixel_centres_on_the_lines_equal_the_unfused_model(dg, scenes, c, size):
+    """Views whose pixel centres lie within a rounding of the hand world's partition (a fused side test draws other frames:
+    floor_map_cases._witnesses), exactly on it, on one-sided segs and on vertices, and the rotated view a fused rotation changes."""
+    W, H = size
+    got = _host(dg, scenes[c["world"]], c, W, H)
+    want = fc.model_frame(c, W, H)
+    assert np.array_equal(got, want), (c["name"], W, H, int((got != want).any(axis=2).sum()))
+
+
+@pytest.mark.parametrize("c", fc.CORNER_CASES, ids=lambda c: c["name"])
+def test_the_corners_of_the_contract_equal_the_model(dg, scenes, c):
+    W, H = c["size"]
+    got = _host(dg, scenes[c["world"]], c, W, H)
+    want = fc.model_frame(c, W, H)
+    assert want.any() and np.array_equal(got, want), (c["name"], W, H, int((got != want).any(axis=2).sum()))
 
 
 def test_the_cases_cover_the_parameters_the_tier_names():

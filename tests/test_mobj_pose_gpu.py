@@ -2,7 +2,8 @@
 
   rows        the rows the pose kernels write for the seg walk (dg_slot_mobj_poses) equal the scene's rows with the entries applied and
               dg_scene_sectors_at's sectors: batches of 1, 3, 64 and 65 frames, entry totals at the kernels' boundaries, points on and next
-              to partition lines, on vertices, NaN / infinite, and a map with holes; the seg walk keeps its path and its counters
+              to partition lines, on vertices, NaN / infinite, and a map with holes; the seg walk keeps its path and its counters;
+              on the hand world's oblique partition the points at which a fused side test finds the other sector, and exact ties
   pixels      72 views with a different pose set each, and light and state entries on top, through every front end against the oracle's
               frames of the per-view patched WADs; poses == NULL is dg_submit_views_state
   bundle      colour, depth and labels of posed views from one submission; a moved object's box moves with it
@@ -121,6 +122,32 @@ def test_the_rows_the_pose_kernels_write(dg, scene, holes, wad1993, path1993, n_
     if which == "holes" and n_frames >= 3:
         assert none_seen > 0                                   # rows with sector -1 were among them
     ctx.close()
+
+
+def test_entries_on_the_partition_line_of_the_hand_world(dg):
+    """mobj_pose_cases.line_points as pose entries, four objects to a frame: points at which pose_sector_at's side test is 0.0 and a fused
+    one is not (the import asserts sector 0 by the rule and 1 fused), and exact ties.  The rows' sectors equal the host's and the numpy
+    descent's; a library built with contraction on fails here."""
+    xs, ys, n = mp.line_points()
+    sc = dg.Scene(mp.fc.wad_of("hand"), "e1m1")
+    n_mobjs = sc.mobj_count()
+    n_frames = -(-len(xs) // n_mobjs)
+    entries = [[(i - f * n_mobjs, float(xs[i]), float(ys[i]), float(F(0.01 * i))) for i in range(f * n_mobjs, min(len(xs), (f + 1) * n_mobjs))] for f in range(n_frames)]
+    poses, keep = dg.make_view_poses(entries)
+    views = (dg.DgView * n_frames)(*[dg.DgView(96.0, 180.0, 0.0, 41.0, 1.0, 0.0, 1.0, 0.0, 0.0, 1)] * n_frames)
+    ctx = dg.Context(131, 67, max_batch=n_frames, slots=1, front_end=dg_fe(dg, 3))
+    ctx.upload_scene(sc)
+    ctx.submit_poses(0, views, poses)
+    rows = ctx.slot_mobj_poses(0, 0, n_frames)
+    got = rows["sector"].reshape(-1)[:len(xs)]
+    assert np.array_equal(rows["x"].reshape(-1)[:len(xs)].view(np.uint32), xs.view(np.uint32))
+    host, model = sc.sectors_at(xs, ys), mp.line_sectors(xs, ys)
+    print(f"pose rows whose sector differs from the host's: {int((got != host).sum())}, from the numpy descent's: {int((got != model).sum())} of {len(xs)}")
+    assert np.array_equal(got, host) and np.array_equal(got, model)
+    assert (got[:n] == 0).all() and set(got[n:].tolist()) == {0, 1}
+    ctx.close()
+    sc.close()
+    del keep
 
 
 def dg_fe(dg, fe):

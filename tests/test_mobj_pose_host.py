@@ -7,7 +7,8 @@ calls, and the shared fill / scatter bodies of view_rows_core.h for the pose kin
   patched scene   the lists and owner tags equal those of the product's own scene of the patched WAD: the tags keep their indices
   fractional      fractional positions and arbitrary angles against the second renderer (np_front_end.render_frame)
   sectors         dg_scene_sectors_at against np_front_end.get_sector_from_vertex: random points, points on and within an ulp of partition
-                  lines, vertices, NaN and infinities, and a map with holes, where an object moved into no sector is not drawn
+                  lines, vertices, NaN and infinities, and a map with holes, where an object moved into no sector is not drawn; on the
+                  hand world's oblique partition the points at which a fused side test finds the other sector, and exact ties
   errors          every error return of the new host calls
   stand-alone     tests/mobj_pose/mobj_pose_host_main.cpp under AddressSanitizer + UBSan, as a program
 """
@@ -131,6 +132,16 @@ def test_sectors_at_equals_the_model(world):
     want = mp.model_sectors(world["wad"], xs, ys)
     assert np.array_equal(got, want), f"{int((got != want).sum())} of {len(xs)} points differ, first {np.argwhere(got != want)[0]}"
     assert (want >= 0).sum() > 1000 and len(set(want.tolist())) > 50
+
+
+def test_sectors_at_on_the_partition_line_of_the_hand_world(dg):
+    """mobj_pose_cases.line_points: where the side test is 0.0 and a fused one is not (sector 0 by the rule, 1 fused), and exact ties."""
+    xs, ys, n = mp.line_points()
+    scene = dg.Scene(mp.fc.wad_of("hand"), "e1m1")
+    got = scene.sectors_at(xs, ys)
+    assert np.array_equal(got, mp.line_sectors(xs, ys)), np.flatnonzero(got != mp.line_sectors(xs, ys))
+    assert (got[:n] == 0).all()
+    scene.close()
 
 
 @pytest.fixture(scope="module")

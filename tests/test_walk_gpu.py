@@ -4,7 +4,8 @@
 2. Sixteen views of a walk located on the GPU, through all three front ends, equal the oracle's frames of the model's views.
 3. A call while a slot is in flight leaves that slot's frames and the fallback counters as they are.
 4. A walk of another scene, and a ctx with no scene uploaded: DG_ERR_INVALID.
-5. A second call on located walks changes nothing and raises nothing."""
+5. A second call on located walks changes nothing and raises nothing.
+6. Starts on the hand world's partition line, where a fused side test finds the other room: the host's and the model's floors."""
 import ctypes
 
 import numpy as np
@@ -57,6 +58,30 @@ def _compare(dg, ctx, sc, descs, total):
 def test_gpu_floors_equal_host_floors(dg, ctx, holes, calls, k):
     for total in ([1, 2] if k == 0 else [(1 << k) - 1, 1 << k, (1 << k) + 1]):
         _compare(dg, ctx, holes[0], calls[total], total)
+
+
+def test_starts_on_the_partition_line_of_the_hand_world(dg):
+    """walk_cases.line_walks in one call: starts at which walk_left_of is 0.0 and a fused test is not (the import asserts that a fused
+    model finds the other room's floor there), and exact ties.  The floors equal the host's and the model's; a library built with
+    contraction on fails here."""
+    wad = wc.hand_wad()
+    sc, bsp = dg.Scene(wad, "E1M1"), wm.Bsp(wad)
+    c = dg.Context(W, H, max_batch=1, slots=1)
+    c.upload_scene(sc)
+    descs = wc.line_walks()
+    on_gpu = [dg.Walk(sc, k, start=s, turbo=t) for s, t, k in descs]
+    on_host = [dg.Walk(sc, k, start=s, turbo=t) for s, t, k in descs]
+    c.locate_walks(on_gpu)
+    wrong = 0
+    for (s, t, k), g, h in zip(descs, on_gpu, on_host):
+        a, b, m = g.floors().view(np.uint32), h.floors().view(np.uint32), wm.walk(bsp, s, t, k).floors.view(np.uint32)
+        wrong += not (np.array_equal(a, b) and np.array_equal(a, m))
+    print(f"walks whose floors differ from the host's or the model's: {wrong} of {len(descs)}")
+    assert wrong == 0
+    for w in on_gpu + on_host:
+        w.close()
+    c.close()
+    sc.close()
 
 
 def test_sixteen_views_through_every_front_end_equal_the_oracle(dg, oracle, wad1993):

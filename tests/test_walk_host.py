@@ -74,6 +74,18 @@ def _check(dg, sc, bsp, start, turbo, keys, times=None):
     return r
 
 
+def test_starts_on_the_partition_line_of_the_hand_world(dg):
+    """walk_cases.line_walks: starts at which the side test is 0.0 and a fused one is not (room A's floor 0 against room B's 24), and exact
+    ties on the partition, on segs and on vertices."""
+    wad = wc.hand_wad()
+    sc, bsp = dg.Scene(wad, "E1M1"), wm.Bsp(wad)
+    floors = set()
+    for start, turbo, keys in wc.line_walks():
+        floors |= set(_check(dg, sc, bsp, start, turbo, keys, times=[0.0, 0.03, 1.0]).floors.tolist())
+    assert floors == {0.0, 24.0}
+    sc.close()
+
+
 @pytest.mark.parametrize("name", MAPS)
 def test_all_64_masks_held_for_three_tics(dg, maps, name):
     _, sc, bsp = maps[name]

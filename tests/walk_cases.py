@@ -7,11 +7,16 @@ subsectors of a synthetic map (SSECTORS count 0): every subsector a far ring of 
 every seventh of the others, so that walks inside the map cross between hits and misses all the time.
 
 `gpu_calls` builds, for every total probe count the GPU tier asks for, the walks of one dg_ctx_locate_walks call.  None of their keys
-turn, so tests/walk_model.py can work out their probes by one accumulate and the CPU tier can check the mix (test_walk_host.py)."""
+turn, so tests/walk_model.py can work out their probes by one accumulate and the CPU tier can check the mix (test_walk_host.py).
+
+`line_walks` starts walks on the hand world's partition line: at the points where the side test is 0.0 and a fused one is not, and at
+the exact ties on the partition, on segs and on vertices (tests/floor_map_cases.py finds both kinds).  Importing this module asserts,
+by the model alone, that a fused side test puts four and more of those starts on the other room's floor."""
 import struct
 
 import numpy as np
 
+import floor_map_cases as fc
 import walk_model as wm
 
 L, R, U, D, A, S = wm.LEFT, wm.RIGHT, wm.UP, wm.DOWN, wm.ALT, wm.SHIFT
@@ -103,3 +108,39 @@ def gpu_calls(bsp):
             descs.append((start, turbo, _keys_for(rng, n - 1)))
         calls.append((total, descs))
     return calls
+
+
+def hand_wad() -> bytes:
+    return fc.wad_of("hand")
+
+
+def line_starts():
+    """(xs, ys, n_witnesses): the witness points first, then the exact ties."""
+    wx, wy = fc.side_witness_points()
+    tx, ty = fc.tie_points()
+    return np.concatenate([wx, tx]), np.concatenate([wy, ty]), len(wx)
+
+
+def line_walks():
+    """[(start, turbo, keys), ...] on the hand world: from every point of line_starts a walk of no tics and one of a few tics that
+    steps off the line and back (its later probes land where they land: the model follows)."""
+    xs, ys, _ = line_starts()
+    out = []
+    for i, (x, y) in enumerate(zip(xs, ys)):
+        start = (float(x), float(y), float(np.float32(0.37 * i)))
+        out.append((start, 100, np.zeros(0, dtype=np.uint8)))
+        out.append((start, 40, np.array([U, D, A | L, A | R, 0, U | S][:2 + i % 5], dtype=np.uint8)))
+    return out
+
+
+def _line_starts_shown():
+    xs, ys, n = line_starts()
+    rule, fused = wm.Bsp(hand_wad()), wm.Bsp(hand_wad(), fused=True)
+    (hit, floor), (fhit, ffloor) = rule.floor_at(xs, ys), fused.floor_at(xs, ys)
+    assert hit.all() and fhit.all()
+    other = (floor == 0.0) & (ffloor == 24.0)                 # room A's floor by the rule, room B's by a fused test
+    assert other[:n].sum() >= 4 and other[:n].all(), int(other[:n].sum())
+    assert not other[n:].any() and len(xs) - n >= 8           # an exact tie is one for a fused test too
+
+
+_line_starts_shown()

@@ -40,7 +40,8 @@ def _lumps(wad: bytes, map_name: str):
 class Bsp:
     """The map's BSP and, per subsector, the floor height get_sector_from_vertex would report (None flag: no seg with a sidedef)."""
 
-    def __init__(self, wad: bytes, map_name: str = "E1M1"):
+    def __init__(self, wad: bytes, map_name: str = "E1M1", fused: bool = False):
+        self.fused = fused                                                 # test code only: the side test as a contracting compiler would evaluate it (floor_at)
         L = _lumps(wad, map_name)
         nodes = np.frombuffer(L["NODES"], dtype="<i2").reshape(-1, 14)
         self.nx, self.ny, self.ndx, self.ndy = (nodes[:, k].astype(F) for k in range(4))
@@ -78,7 +79,10 @@ class Bsp:
                 x, y, dx, dy = self.nx[n], self.ny[n], self.ndx[n], self.ndy[n]
                 ax, ay = xs[live] - x, ys[live] - y
                 bx, by = (x + dx) - x, (y + dy) - y
-                left = (ax * by - ay * bx) <= F(0)
+                if self.fused:                                             # fma(ax, by, -(ay * bx)): the first product exact, one rounding of the sum
+                    left = (ax.astype(np.float64) * by.astype(np.float64) - (ay * bx).astype(np.float64)).astype(F) <= F(0)
+                else:
+                    left = (ax * by - ay * bx) <= F(0)
                 c = self.child[n, left.astype(np.int64)]
                 is_leaf = (c & 0x8000) != 0
                 leaf[live[is_leaf]] = c[is_leaf] & 0x7FFF
