@@ -83,6 +83,87 @@ static uint32_t classify_chunk(W0At w0_at, uint32_t c0, uint32_t c1, int32_t y0,
     return (cls << CH_CLASS_SHIFT) | (last & CH_INDEX_MASK);
 }
 
+// ---- observer (tests/test_raster_classes.py): which stage-1 path strip_body (kernels.hip) takes for every column of one 64-column strip
+// in one tile row, restated ONCE here from the span words 0 alone, like the kernel's pre-filter.  Kernel lines mirrored (kernels.hip,
+// strip_body): the staging rounds `fits` / c_lo / c_hi (the `while (c_lo < TILE_W)` loop head), the pre-filter f_n / f_hit / f_op / f_ov /
+// hit_op / big, the sole-owner ballots f_last / f_sole / ucol_wall / ucol_flat (tile_vy0 switches ucol_flat off), `under`, hit_ov, walk2,
+// nk, the packed pass `few_rows && nk == WAVES && walk2 == 0`, and stage1's choice  mu ? sole : big ? big_column_owner : owner_loop.
+//   PATH_EMPTY      no span of the column touches the tile's rows (the kernel has no branch for it: the column takes whatever path the
+//                   rest says and every row keeps the "nothing" record)
+//   PATH_SOLE_WALL  wall_offset_plain on all rows from one broadcast record (ucol_wall)
+//   PATH_SOLE_FLAT  flat_offset_plain likewise (ucol_flat; never in the tile that holds the vy == 0 row)
+//   PATH_WALK       owner_loop over at most 8 spans, then owner_texel: per-lane records, wall_offset_tile / flat_offset_tile with their votes
+//   PATH_BIG        big_column_owner (more than 8 spans in the column), then owner_texel
+//   PATH_PACKED     the 8 columns x 8 rows pass of a last tile row with at most PACK_ROWS live rows: lane-permute owner search, owner_texel
+// flags: PATH_OV_WALK  stage 2 enters its overlay branch for the column (walk2 & colmask: big_column_overlays / overlay_loop);
+//        PATH_OV_HIT   a possibly-transparent span touches the rows and is walked;  PATH_OV_UNDER  one is dropped as drawn before the sole owner.
+enum : uint8_t { PATH_EMPTY = 0, PATH_SOLE_WALL = 1, PATH_SOLE_FLAT = 2, PATH_WALK = 3, PATH_BIG = 4, PATH_PACKED = 5, PATH_MASK = 7,
+                 PATH_OV_WALK = 0x10, PATH_OV_HIT = 0x20, PATH_OV_UNDER = 0x40 };
+constexpr int OBS_TILE = 64, OBS_WAVES = 8, OBS_PACK_ROWS = 8, OBS_SPAN_CAP = 512;   // TILE_W = TILE_H, WAVES, PACK_ROWS, SPAN_CAP of kernels.hip
+
+// out[c] for the strip's columns x0 + c (c < 64; columns at or beyond W get PATH_EMPTY), tile rows y0 .. y0 + 63.
+template <typename W0At>
+static void classify_strip_paths(W0At w0_at, const uint32_t *col_off, int W, int H, float CFY, int x0, int y0, uint8_t *out) {
+    const int y_last = std::min(H, y0 + OBS_TILE) - 1;
+    const bool few_rows = H - y0 <= OBS_PACK_ROWS;
+    bool tile_vy0 = false;
+    for (int y = y0; y <= y_last; y++) tile_vy0 |= CFY - (float)y == 0.0f;
+    uint32_t lcoff[OBS_TILE + 1];
+    for (int c = 0; c <= OBS_TILE; c++) lcoff[c] = col_off[std::min(x0 + c, W)];
+    const bool fits = lcoff[OBS_TILE] - lcoff[0] <= (uint32_t)OBS_SPAN_CAP;
+    std::fill(out, out + OBS_TILE, (uint8_t)PATH_EMPTY);
+    for (int c_lo = 0, c_hi; c_lo < OBS_TILE; c_lo = c_hi) {
+        const uint32_t t0 = lcoff[c_lo];
+        c_hi = OBS_TILE;
+        if (!fits && lcoff[OBS_TILE] - t0 > (uint32_t)OBS_SPAN_CAP) {
+            c_hi = c_lo + 1;
+            while (c_hi < OBS_TILE && lcoff[c_hi + 1] - t0 <= (uint32_t)OBS_SPAN_CAP) c_hi++;
+        }
+        for (int wave = 0; wave < OBS_WAVES; wave++) {
+            const int nk = (c_hi - c_lo - wave + OBS_WAVES - 1) / OBS_WAVES;
+            struct { bool touched, big, hit_ov, has_under; int sole_kind; } col[OBS_WAVES] = {};
+            bool walk2 = false;
+            for (int k = 0; k < OBS_WAVES; k++) {
+                const int fcol = c_lo + wave + OBS_WAVES * k;
+                if (fcol >= c_hi) continue;
+                const uint32_t first = lcoff[fcol], n = lcoff[fcol + 1] - first;
+                auto touches = [&](uint32_t w0) { return w0_cbot(w0) >= y0 && w0_ctop(w0) <= y0 + (OBS_TILE - 1); };
+                for (uint32_t i = 0; i < n; i++) col[k].touched |= touches(w0_at(first + i));
+                col[k].big = n > 8u;
+                int sole = -1;                                                 // slot of the column's sole plain owner
+                if (!col[k].big) {
+                    int last_op = -1;
+                    for (uint32_t i = 0; i < n; i++) { const uint32_t w0 = w0_at(first + i); if (touches(w0) && !w0_immediate(w0)) last_op = (int)i; }
+                    if (last_op >= 0) {
+                        const uint32_t w0 = w0_at(first + (uint32_t)last_op);
+                        const bool f_sole = w0_plain(w0) && w0_ctop(w0) <= y0 && w0_cbot(w0) >= y_last;
+                        if (f_sole && w0_kind(w0) == SPAN_WALL) { sole = last_op; col[k].sole_kind = PATH_SOLE_WALL; }
+                        if (f_sole && w0_kind(w0) == SPAN_FLAT && !tile_vy0) { sole = last_op; col[k].sole_kind = PATH_SOLE_FLAT; }
+                    }
+                    for (uint32_t i = 0; i < n; i++) {
+                        const uint32_t w0 = w0_at(first + i);
+                        if (!touches(w0) || !w0_immediate(w0)) continue;
+                        if ((int)i < sole) col[k].has_under = true; else col[k].hit_ov = true;
+                    }
+                } else {
+                    for (uint32_t i = 0; i < n; i++) { const uint32_t w0 = w0_at(first + i); col[k].hit_ov |= touches(w0) && w0_immediate(w0); }
+                }
+                walk2 |= col[k].big || col[k].hit_ov;
+            }
+            const bool packed = few_rows && nk == OBS_WAVES && !walk2;
+            for (int k = 0; k < nk; k++) {
+                const int fcol = c_lo + wave + OBS_WAVES * k;
+                if (x0 + fcol >= W || !col[k].touched) continue;
+                uint8_t p = (uint8_t)(packed ? (int)PATH_PACKED : col[k].sole_kind ? col[k].sole_kind : col[k].big ? (int)PATH_BIG : (int)PATH_WALK);
+                if (!packed && (col[k].big || col[k].hit_ov)) p |= PATH_OV_WALK;
+                if (col[k].hit_ov) p |= PATH_OV_HIT;
+                if (col[k].has_under) p |= PATH_OV_UNDER;
+                out[fcol] = p;
+            }
+        }
+    }
+}
+
 // What the sole-owner fast path of dg_raster_tiles does: every (column, 64-row tile) chunk that is not CH_GENERIC is
 // rendered from its ONE owner span (or left black), and must equal the draw-order replay.  Returns false (and says why) otherwise;
 // counts[class] += chunks.
@@ -202,6 +283,90 @@ static int draw_frame_lists(const Scene &sc, int W, int H, const dg_frame_lists 
     if (!check_chunk_descriptors(ds, k, bf.hdr, pal.data(), bf.col_off.data(), rs.data(), W, H, rgb, nullptr)) return DG_ERR_INVALID;
     if (stats) { stats[0] = bf.spans.size(); stats[1] = bf.walls.size(); stats[2] = bf.planes.size(); stats[3] = bf.covered_pixels; }
     return 0;
+}
+// The observer of tests/test_raster_classes.py: takes what emul_draw_lists takes and says, without drawing, what the product's own code decided.
+//   spans[n][8]    per binned span, column-major like the kernel's list: x, ctop, cbot, kind, plain, immediate, reason, rec — kind / plain /
+//                  immediate are read from the DevRSpan word 0 that bin_frame + resolve_*_span produce; rec = the span's draw call (the n-th
+//                  wall command / the n-th non-sky visplane command of the order list); reason = why a span is not plain, recomputed here
+//                  next to resolve_wall_span / resolve_flat_span (raster_core.h) from the same records:
+//                    wall  1 height not a power of two   2 d == 0   4 first-row end out of range   8 last-row end out of range
+//                    flat  16 gwz outside the guard band   32 wz * vx outside it   64 lightf >= 7
+//                  (a plain span with a reason, or a non-plain one without, is an error of this function: DG_ERR_INVALID)
+//   chunks[ceil(H / 64)][W]   the stage-1 path and overlay flags of every (column, tile row): classify_strip_paths
+//   owner[H][W]    index (into spans) of the last opaque span that covers the pixel, -1 for none
+//   pflags[H][W]   1 a possibly-transparent span drawn after the owner shows here (opaque texel)   2 one covers the pixel but was drawn before
+//                  the owner   4 one drawn after the owner covers the pixel with a transparent texel
+// Returns the span count (< 0: an error; -1000: cap too small).
+int emul_observe_lists(void *scene, int W, int H, const dg_frame_lists *lists, uint32_t *spans, uint32_t cap, uint8_t *chunks, int32_t *owner, uint8_t *pflags) {
+    const Scene &sc = *(const Scene *)scene;
+    dg_frame_lists fl = *lists;
+    fill_view_trig(fl.view);
+    static thread_local BinnedFrame bf;
+    const FrameConsts fk = make_consts(W, H);
+    int rc = bin_frame(sc, fk, fl, bf, g_err);
+    if (rc) return rc;
+    if (bf.spans.size() > cap) { g_err = "span buffer too small"; return -1000; }
+    const size_t texels_end = (sc.texel_idx.size() + 255) & ~(size_t)255;
+    DevScene ds{};
+    ds.texel_opq = sc.texel_opq.data();
+    const BitmapInfo &sky = sc.bitmaps[(size_t)sc.sky_bitmap];
+    ds.sky_texel_off = sky.texel_off; ds.sky_w = sky.w; ds.sky_h = sky.h; ds.sky_has_holes = sky.has_holes;
+    const DevConsts k{fk.ARC, fk.GCFX, fk.CFX, fk.CFY, W, H};
+    std::vector<DevRSpan> rs(bf.spans.size());
+    for (size_t i = 0; i < bf.spans.size(); i++) {
+        const DevSpan &sp = bf.spans[i];
+        uint32_t reason = 0;
+        if (sp.kind == SPAN_WALL) {
+            const DevWallRec &r = bf.walls[sp.rec];
+            rs[i] = resolve_wall_span(sp, r);
+            const float d = (float)((int32_t)sp.bot_y - (int32_t)sp.top_y);
+            const float v_top = (float)r.h + ((float)((int32_t)sp.ctop - (int32_t)sp.top_y) / d) * r.uy1;
+            const float v_bot = (float)r.h + ((float)((int32_t)sp.cbot - (int32_t)sp.top_y) / d) * r.uy1;
+            if ((r.h & (r.h - 1)) != 0) reason |= 1u;
+            if (d == 0.0f) reason |= 2u;
+            else {
+                if (!(__builtin_fabsf(v_top) < 32000.0f)) reason |= 4u;
+                if (!(__builtin_fabsf(v_bot) < 32000.0f)) reason |= 8u;
+            }
+        } else if (sp.kind == SPAN_FLAT) {
+            const DevPlaneRec &p = bf.planes[sp.rec];
+            rs[i] = resolve_flat_span(sp, p, k, (uint32_t)texels_end);
+            if (!div_guard_ok(p.gwz)) reason |= 16u;
+            if (!div_guard_ok(p.wz * ((k.CFX - (float)sp.x) / k.ARC))) reason |= 32u;
+            if (!(p.lightf < 7.0f)) reason |= 64u;
+        } else {
+            rs[i] = resolve_sky_span(sp, ds, k, bf.hdr);
+        }
+        const uint32_t w0 = rs[i].w[0];
+        if (sp.kind != SPAN_SKY && w0_plain(w0) != (reason == 0u)) { g_err = "span " + std::to_string(i) + ": the plain bit and the recomputed reason disagree"; return DG_ERR_INVALID; }
+        uint32_t *o = spans + 8 * i;
+        o[0] = (uint32_t)sp.x; o[1] = (uint32_t)w0_ctop(w0); o[2] = (uint32_t)w0_cbot(w0); o[3] = w0_kind(w0);
+        o[4] = w0_plain(w0); o[5] = w0_immediate(w0); o[6] = reason; o[7] = sp.rec;
+    }
+    const int n_tile_rows = (H + OBS_TILE - 1) / OBS_TILE;
+    for (int ty = 0; ty < n_tile_rows; ty++)
+        for (int x0 = 0; x0 < W; x0 += OBS_TILE) {
+            uint8_t paths[OBS_TILE];
+            classify_strip_paths([&](uint32_t i) { return rs[i].w[0]; }, bf.col_off.data(), W, H, k.CFY, x0, ty * OBS_TILE, paths);
+            for (int c = 0; c < OBS_TILE && x0 + c < W; c++) chunks[(size_t)ty * W + x0 + c] = paths[c];
+        }
+    for (int x = 0; x < W; x++) {
+        for (int y = 0; y < H; y++) { owner[(size_t)y * W + x] = -1; pflags[(size_t)y * W + x] = 0; }
+        for (uint32_t i = bf.col_off[(size_t)x]; i < bf.col_off[(size_t)x + 1]; i++)
+            if (!w0_immediate(rs[i].w[0]))
+                for (int y = w0_ctop(rs[i].w[0]); y <= w0_cbot(rs[i].w[0]); y++) owner[(size_t)y * W + x] = (int32_t)i;
+        for (uint32_t i = bf.col_off[(size_t)x]; i < bf.col_off[(size_t)x + 1]; i++) {
+            const uint32_t *w = rs[i].w;
+            if (!w0_immediate(w[0])) continue;
+            for (int y = w0_ctop(w[0]); y <= w0_cbot(w[0]); y++) {
+                uint8_t &pf = pflags[(size_t)y * W + x];
+                if ((int32_t)i < owner[(size_t)y * W + x]) { pf |= 2; continue; }
+                const uint32_t o = w0_kind(w[0]) == SPAN_WALL ? wall_texel_offset(w[1], w[2], w[4], w[5], w[6], w[7], y) : sky_texel_offset(w[2], w[3], sky_row(ds, k, y));
+                pf |= (o != 0xffffffffu && ds.texel_opq[o]) ? 1 : 4;
+            }
+        }
+    }
+    return (int)bf.spans.size();
 }
 // The device column walk (fe_core.h bodies, the loops of fe_kernels.hip restated serially) on the CPU, compared span for
 // span with the host list path.  stats[0..3] = spans, parts, sprites, overflow flags; stats[4] = 1 when the column-major

@@ -29,7 +29,9 @@ def lib():
         L.emul_render_fe_slots.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_uint32, ctypes.c_void_p,
                                            ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.emul_draw_lists.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
-        L.emul_render_state.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+        L.emul_observe_lists.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]
+        L.emul_render_state.argtypes =[ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                         ctypes.c_uint32, ctypes.c_void_p]
         L.emul_fs_frame.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(ctypes.c_uint64)]
         L.emul_frame_part_records.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_void_p, ctypes.c_int]
@@ -43,6 +45,13 @@ def lib():
         L.emul_set_mobj_state.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_int]
         _lib = L
     return _lib
+
+
+# emul_observe_lists (emul.cpp): stage-1 paths of dg_raster_tiles per (column, tile row), their overlay flags, why a span is not plain, pixel flags
+PATHS = {"EMPTY": 0, "SOLE_WALL": 1, "SOLE_FLAT": 2, "WALK": 3, "BIG": 4, "PACKED": 5}
+PATH_MASK, OV_WALK, OV_HIT, OV_UNDER = 7, 0x10, 0x20, 0x40
+REASONS = {"npot": 1, "d0": 2, "first_out": 4, "last_out": 8, "gwz_out": 16, "wzvx_out": 32, "light7": 64}
+PF_SHOWS, PF_BEFORE, PF_HOLE = 1, 2, 4
 
 
 def fs_kept_counts(survivors, sky):
@@ -94,6 +103,25 @@ class EmulScene:
         if rc:
             raise RuntimeError(f"emul rc {rc}: {lib().emul_last_error().decode()}")
         return buf.tobytes(), list(st)
+
+    def observe_lists(self, W, H, frame_lists):
+        """What the product's own code decides for one dg_frame_lists, without drawing (emul.cpp emul_observe_lists) -> dict:
+        `spans` (n, 8) uint32 rows = x, ctop, cbot, kind (0 wall, 1 flat, 2 sky), plain, immediate, reason, rec — from the DevRSpan word 0 of
+        bin_frame + resolve_*_span, in the kernel's column-major order; reason (REASONS) is why a span is not plain; rec the span's draw call
+        (n-th wall command / n-th non-sky visplane command of the order list);
+        `chunks` (tile rows, W) uint8 = PATHS code | OV_* flags: the stage-1 path strip_body takes for the (column, 64-row tile);
+        `owner` (H, W) int32 = row of `spans` of the last opaque span on the pixel, -1 for none;
+        `pflags` (H, W) uint8: PF_SHOWS an overlay drawn after the owner shows, PF_BEFORE one was drawn before the owner, PF_HOLE one drawn
+        after the owner has a transparent texel here."""
+        cap = 1 << 16
+        spans = np.zeros((cap, 8), dtype=np.uint32)
+        chunks = np.zeros(((H + 63) // 64, W), dtype=np.uint8)
+        owner = np.zeros((H, W), dtype=np.int32)
+        pflags = np.zeros((H, W), dtype=np.uint8)
+        n = lib().emul_observe_lists(self._h, W, H, ctypes.byref(frame_lists), spans.ctypes.data, cap, chunks.ctypes.data, owner.ctypes.data, pflags.ctypes.data)
+        if n < 0:
+            raise RuntimeError(f"emul_observe_lists rc {n}: {lib().emul_last_error().decode()}")
+        return {"spans": spans[:n].copy(), "chunks": chunks, "owner": owner, "pflags": pflags}
 
     def sprite_frame(self, sprite, frame=0):
         sf = lib().emul_sprite_frame(self._h, sprite.encode(), frame)
