@@ -15,7 +15,8 @@
 //                                opaque spans in draw order and records per row the last one covering it (three v_readlane per
 //                                span), then every row evaluates its owner ONCE — exact last-writer-wins, no overdraw evaluation, no
 //                                divergent control flow — and issues its texel gather; stage 2 (after stage 1 of the next column)
-//                                shades and lays the possibly-transparent spans (sprites, masked walls) on top;
+//                                shades and lays the possibly-transparent spans (sprites, masked walls) on top; a wave whose eight
+//                                columns all have one plain owner of one kind takes a fixed-shape body without any per-column test;
 //                              * a wall column reads one texture column ([x][y] texel layout => consecutive bytes);
 //                              * finished pixels go to an LDS tile [col][row] and leave the CU as 12-byte-per-lane RGB24 row
 //                                segments.  Every pixel of the tile is stored (uncovered = 0,0,0) which fuses the reference's
@@ -278,32 +279,6 @@ __device__ __forceinline__ uint32_t span_texel(const FrameVgprs &T, const uint4 
     return a.z + sky_row_of(R);
 }
 
-// Stage 1 of a column that has no sole plain owner: its opaque spans that touch the tile's rows, in draw order, each evaluated with ITS
-// mapper on all 64 rows from one broadcast record and selected into the rows it covers — a later span overwrites an earlier one like
-// the reference's Pixels::set.  No owner search followed by a per-row record fetch and a vote on kinds: a chunk with a ceiling and a
-// wall costs one flat and one wall evaluation of the short kind, and both read their parameters as broadcasts.  Rows nothing covers
-// keep texel 0 with factor 0 -> 0,0,0.
-__device__ __forceinline__ uint32_t span_loop(const FrameVgprs &T, uint32_t lspans_addr, unsigned long long m, uint32_t v_lo, uint32_t v_rg, uint32_t v_off,
-                                              const RowConsts &R, bool tile_vy0, float &factor_out, uint32_t &winner_out) {
-    uint32_t o = 0, winner = 0;
-    float factor = 0.0f;
-    while (m) {
-        const int j = take_lowest(m);
-        const uint32_t off = bcast(v_off, j);
-        uint4 a, b;
-        lds_record(lspans_addr + (off & OFF_ADDR), a, b);
-        float sf;
-        const uint32_t so = span_texel<true>(T, a, b, off, R, tile_vy0, sf);
-        const bool in = ((uint32_t)R.y - bcast(v_lo, j)) <= bcast(v_rg, j);
-        o = in ? so : o;
-        factor = in ? sf : factor;
-        winner = in ? off : winner;
-    }
-    factor_out = factor;
-    winner_out = winner;
-    return o;
-}
-
 // Possibly-transparent spans in draw order (bitmap columns — masked walls, sprites — and sky-with-holes spans): where such a span
 // shows — its texel is opaque and no later opaque span owns the row — its (texel, light factor) replace the row's; the pixel is
 // shaded once, afterwards.  (Fetching two spans' texels per trip without exec masking was measured: slower at 1280x800 — most columns
@@ -375,7 +350,7 @@ __device__ __forceinline__ uint32_t big_column_owner(const uint32_t *lw0, uint32
         const bool hit = i < n && w0_cbot(w0v) >= y0 && w0_ctop(w0v) <= y0 + (TILE_H - 1) && !w0_immediate(w0v);
         uint32_t v_lo, v_rg, v_off;
         unpack_span(w0v, off0 + 32u * i, v_lo, v_rg, v_off);
-        winner = owner_loop(__ballot(hit), v_lo, v_rg, v_off, R, winner);
+        winner = owner_loop(__builtin_amdgcn_ballot_w64(hit), v_lo, v_rg, v_off, R, winner);
     }
     return winner;
 }
@@ -386,7 +361,7 @@ __device__ __forceinline__ void big_column_overlays(const RasterParams &P, const
         const uint32_t i = base + (uint32_t)lane;
         const uint32_t w0v = i < n ? lw0[i] : 0u;
         const bool hit = i < n && w0_cbot(w0v) >= y0 && w0_ctop(w0v) <= y0 + (TILE_H - 1) && w0_immediate(w0v);
-        const unsigned long long m = __ballot(hit);
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
         if (!m) continue;
         uint32_t v_lo, v_rg, v_off;
         unpack_span(w0v, off0 + 32u * i, v_lo, v_rg, v_off);
@@ -503,35 +478,37 @@ __device__ __forceinline__ void strip_body(const RasterParams &P, TileLds &L, in
         // than 8 spans take the general path).
         const int fk = lane >> 3, fslot = lane & 7;
         const int fcol = c_lo + wave + WAVES * fk;
-        uint32_t f_n0 = 0, f_n = 0, f_w0 = 0;
-        bool f_hit = false;
+        // (a lane without a span keeps a word 0 that touches no tile: first row 0x3fff, last row 0)
+        uint32_t f_n0 = 0, f_n = 0, f_w0 = 0x3fffu;
         if (fcol < c_hi) {
             f_n0 = L.lcoff[fcol] - t0;
             f_n = L.lcoff[fcol + 1] - L.lcoff[fcol];
-            if ((uint32_t)fslot < f_n && f_n <= 8u) {
-                f_w0 = L.lw0[f_n0 + (uint32_t)fslot];
-                f_hit = w0_cbot(f_w0) >= y0 && w0_ctop(f_w0) <= y0 + (TILE_H - 1);
-            }
+            if ((uint32_t)fslot < f_n && f_n <= 8u) f_w0 = L.lw0[f_n0 + (uint32_t)fslot];
         }
         uint32_t v_lo, v_rg, v_off;
         unpack_span(f_w0, 32u * (f_n0 + 1u + (uint32_t)fslot), v_lo, v_rg, v_off);
-        const bool f_op = f_hit && !w0_immediate(f_w0), f_ov = f_hit && w0_immediate(f_w0);
-        const unsigned long long hit_op = __ballot(f_op);
-        const unsigned long long big = __ballot(f_n > 8u);         // all 8 lanes of a column with more than 8 spans
+        // Every vote below is the ballot of ONE compare (the compare itself writes the lane mask) and the conjunctions are made of the
+        // masks in scalar code: the ballot of a conjunction costs a select and a second compare on top.
+        const int y_last = y0 + (TILE_H - 1) < H ? y0 + (TILE_H - 1) : H - 1;                  // the tile's last live row
+        const unsigned long long m_hit = __builtin_amdgcn_ballot_w64(w0_cbot(f_w0) >= y0) & __builtin_amdgcn_ballot_w64(w0_ctop(f_w0) <= y0 + (TILE_H - 1));
+        const unsigned long long m_imm = __builtin_amdgcn_ballot_w64(w0_immediate(f_w0));
+        const unsigned long long hit_op = m_hit & ~m_imm;
+        const unsigned long long big = __builtin_amdgcn_ballot_w64(f_n > 8u);         // all 8 lanes of a column with more than 8 spans
         // Columns with ONE opaque owner: the last OPAQUE span that touches the tile's rows is plain and covers all of the tile's live
         // rows — whatever lies under it in draw order cannot show.  Such a column (two out of three in the benchmark scene) needs no
         // range test and no select: ucol_* carry one bit per column, at the owning span's lane.
         // Possibly-transparent spans drawn after it (a sprite in front of a wall) are laid on top in stage 2 as usual; those drawn
         // before it are dropped here.
         const uint32_t my_ops = (uint32_t)(hit_op >> (lane & ~7)) & 0xffu;
-        const bool f_last = (my_ops >> (fslot + 1)) == 0u;
-        const bool f_sole = f_op && f_last && w0_plain(f_w0) && w0_ctop(f_w0) <= y0 && w0_cbot(f_w0) >= (y0 + (TILE_H - 1) < H ? y0 + (TILE_H - 1) : H - 1);
-        const unsigned long long ucol_wall = __ballot(f_sole && w0_kind(f_w0) == SPAN_WALL);   // (a bitmap height that is not a power of two, a texture row beyond i16: span_loop)
-        const unsigned long long ucol_flat = tile_vy0 ? 0ull : __ballot(f_sole && w0_kind(f_w0) == SPAN_FLAT);   // (the vy == 0 row, like numerators outside the prepared divide's domain: span_loop)
+        const unsigned long long m_cover = __builtin_amdgcn_ballot_w64(w0_ctop(f_w0) <= y0) & __builtin_amdgcn_ballot_w64(w0_cbot(f_w0) >= y_last);
+        const unsigned long long m_plain = __builtin_amdgcn_ballot_w64(w0_plain(f_w0)), m_wall = __builtin_amdgcn_ballot_w64(w0_kind(f_w0) == SPAN_WALL);
+        const unsigned long long m_sole = hit_op & __builtin_amdgcn_ballot_w64((my_ops >> (fslot + 1)) == 0u) & m_plain & m_cover;
+        const unsigned long long ucol_wall = m_sole & m_wall;   // (a bitmap height that is not a power of two, a texture row beyond i16: the owner walk)
+        const unsigned long long ucol_flat = tile_vy0 ? 0ull : m_sole & __builtin_amdgcn_ballot_w64(w0_kind(f_w0) == SPAN_FLAT);   // (the vy == 0 row, like numerators outside the prepared divide's domain: the owner walk)
         const unsigned long long ucol = ucol_wall | ucol_flat;
         const uint32_t my_ucol = (uint32_t)(ucol >> (lane & ~7)) & 0xffu;                      // the sole owner of my column, if it has one
-        const bool under = my_ucol != 0u && (1u << fslot) < my_ucol;                           // drawn before it: cannot show
-        const unsigned long long hit_ov = __ballot(f_ov && !under);
+        const unsigned long long m_under = __builtin_amdgcn_ballot_w64((1u << fslot) < my_ucol);   // drawn before it: cannot show
+        const unsigned long long hit_ov = m_hit & m_imm & ~m_under;
         const unsigned long long walk2 = big | hit_ov;                        // columns whose stage 2 has more to do than shading
         const int nk = (c_hi - c_lo - wave + WAVES - 1) / WAVES;     // columns of this chunk that are this wave's
         if (few_rows && nk == WAVES && walk2 == 0ull) {
@@ -540,7 +517,8 @@ __device__ __forceinline__ void strip_body(const RasterParams &P, TileLds &L, in
             // (first row | row count - 1 << 16; a span that does not count can never match).
             const int yp = y0 + (lane & (PACK_ROWS - 1));
             const RowConsts Rp = row_consts(yp, P.row_tab[yp < H ? yp : H - 1]);
-            const uint32_t mine_word = (f_hit && !w0_immediate(f_w0)) ? (v_lo | (v_rg << 16)) : 0x0000ffffu;
+            const bool mine_counts = w0_cbot(f_w0) >= y0 && w0_ctop(f_w0) <= y0 + (TILE_H - 1) && !w0_immediate(f_w0);
+            const uint32_t mine_word = mine_counts ? (v_lo | (v_rg << 16)) : 0x0000ffffu;
             const uint32_t off_first = (v_off & OFF_ADDR) - 32u * (uint32_t)fslot;          // staging offset of the column's first span
             uint32_t winner = 0;
 #pragma unroll
@@ -556,9 +534,73 @@ __device__ __forceinline__ void strip_body(const RasterParams &P, TileLds &L, in
             if (c_lo < TILE_W) __syncthreads();
             continue;
         }
+        uint32_t *const tcol = &L.tile[(c_lo + wave) * TILE_TS + lane];       // this lane's row in the wave's first column; column k is k * 8 columns on
+        // ---- the wave-tile whose eight columns all have a sole plain owner OF ONE KIND (two out of three in the benchmark scene: a wave's
+        // columns are eight apart, so they are eight wall columns or eight floor / ceiling columns; the two kinds mixed are under 1 %
+        // and take the general pipeline).  What that pipeline decides per column is known for all eight here, so the body has one
+        // shape: per column the owner's lane (each column group of ucol holds at most one bit: eight bits = one per group), its record
+        // as a broadcast, the plain mapper, the gather; stage 2 is palette, shade, tile write.  No owner index is carried, no row range
+        // is looked at and nothing is branched on.  Two columns in flight, A / B alternating, as below.  Two forms of each kind:
+        //   clean  nothing lies on top of any of the eight columns;
+        //   lean   every possibly-transparent span that survived the pre-filter is a plain wall covering all live rows of the tile (a masked
+        //          wall in front of a wall: they come eight columns at a time).  The sole owner wins every row and what was drawn before
+        //          it is dropped already, so such a span needs no range test, no `off > winner`, no exec masking and no kind dispatch:
+        //          its record, the plain wall mapper, both planes of the texel, two selects.
+        const unsigned long long m_lean = m_plain & m_wall & m_cover;
+        if (nk == WAVES && big == 0ull && __builtin_popcountll(ucol) == WAVES && (ucol_wall == 0ull || ucol_flat == 0ull) && (hit_ov & ~m_lean) == 0ull) {
+            const uint32_t v_rec = lspans_addr + (v_off & OFF_ADDR);     // per lane: the LDS address of its span's record
+            auto sole1 = [&](auto wall, int k, uint32_t &tex, float &factor) {
+                uint4 a, b;
+                lds_record(bcast(v_rec, __builtin_ctzll(ucol & (0xffull << (8 * k)))), a, b);
+                uint32_t o;
+                if constexpr (decltype(wall)::value) { o = wall_offset_plain(a, b, R); factor = bits_f32(a.w); }
+                else o = flat_offset_plain(T, a, b, R, factor);
+                tex = P.scene.texel_idx[o];                              // in flight until stage 2
+            };
+            auto sole2 = [&](auto lean, int k, uint32_t tex, float factor) {
+                if constexpr (decltype(lean)::value) {
+                    unsigned long long m = hit_ov & (0xffull << (8 * k));
+                    while (m) {                                          // in draw order: a later span overwrites an earlier one where it is opaque
+                        uint4 a, b;
+                        lds_record(bcast(v_rec, take_lowest(m)), a, b);
+                        uint32_t t, opq;
+                        gather_u8x2(P.scene.texel_idx, P.scene.texel_opq, wall_offset_plain(a, b, R), t, opq);
+                        tex = opq != 0u ? t : tex;
+                        factor = opq != 0u ? bits_f32(a.w) : factor;
+                    }
+                }
+                float4 c;
+                asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(c) : "v"(pal_addr + (tex << 4)));
+                tcol[k * WAVES * TILE_TS] = shade_f(c, factor);
+            };
+            auto sole_tile = [&](auto wall, auto lean) {
+                uint32_t tex_a, tex_b;
+                float fac_a, fac_b;
+                sole1(wall, 0, tex_a, fac_a);
+#pragma unroll
+                for (int k = 1; k < WAVES - 1; k += 2) {
+                    sole1(wall, k, tex_b, fac_b);
+                    sole2(lean, k - 1, tex_a, fac_a);
+                    sole1(wall, k + 1, tex_a, fac_a);
+                    sole2(lean, k, tex_b, fac_b);
+                }
+                sole1(wall, WAVES - 1, tex_b, fac_b);
+                sole2(lean, WAVES - 2, tex_a, fac_a);
+                sole2(lean, WAVES - 1, tex_b, fac_b);
+            };
+            if (ucol_flat == 0ull) {
+                if (hit_ov == 0ull) sole_tile(std::true_type{}, std::false_type{});
+                else sole_tile(std::true_type{}, std::true_type{});
+            } else {
+                if (hit_ov == 0ull) sole_tile(std::false_type{}, std::false_type{});
+                else sole_tile(std::false_type{}, std::true_type{});
+            }
+            c_lo = c_hi;
+            if (c_lo < TILE_W) __syncthreads();
+            continue;
+        }
         // Two columns in flight per wave: stage 1 of a column and its gather are issued before stage 2 of the column before it.
         struct Col { uint32_t tex, winner; float factor; };
-        uint32_t *const tcol = &L.tile[(c_lo + wave) * TILE_TS + lane];       // this lane's row in the wave's first column; column k is k * 8 columns on
         auto stage1 = [&](int k, Col &C) {
             const unsigned long long colmask = 0xffull << (8 * k);
             const unsigned long long mu = ucol & colmask;
