@@ -35,6 +35,7 @@ DG_FE_MAP_EXPLORED = 8  # dg_timing.front_end of an explored-map submission
 DG_FE_MAP_EGO = 9  # dg_timing.front_end of a player-centred map submission
 DG_FE_MAP_FLOOR = 10  # dg_timing.front_end of a floor-textured player-centred map submission
 DG_EGO_ROTATE, DG_EGO_ARROW = 1, 2   # dg_ego_map.flags
+DG_MARK_BOX, DG_MARK_HEADING = 1, 2   # dg_map_marker.flags
 DG_WALL_ANIMATE, DG_WALL_SCROLL = 1, 2   # dg_scene_set_wall_effects flags
 DG_LIGHT_THINKERS = 1                    # dg_scene_set_light_effects flag
 DG_MOBJ_THINKERS = 1                     # dg_scene_set_mobj_thinkers flag
@@ -165,6 +166,10 @@ class DgMapLine(ctypes.Structure):
 
 class DgEgoMap(ctypes.Structure):
     _fields_ = [("scale", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
+class DgMapMarker(ctypes.Structure):
+    _fields_ = [("radius", ctypes.c_int32), ("rgb", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
 class DgBitmapColumn(ctypes.Structure):
@@ -343,6 +348,21 @@ _SIGNATURES = {
                                                  ctypes.POINTER(DgViewSurfaces)]),
     "dg_render_floor_map_views": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
                                                  ctypes.POINTER(DgViewSurfaces), _P]),
+    "dg_scene_set_map_markers": (ctypes.c_int, [_P, ctypes.POINTER(DgMapMarker), ctypes.c_int]),
+    "dg_map_thing_lines": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgEgoMap), ctypes.POINTER(DgViewState),
+                                          ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgMapLine), ctypes.c_int]),
+    "dg_ego_map_things_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
+                                              ctypes.POINTER(DgViewPoses), _P]),
+    "dg_floor_map_things_host": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DgView), ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
+                                                ctypes.POINTER(DgViewSurfaces), ctypes.POINTER(DgViewPoses), _P]),
+    "dg_submit_ego_map_views_things": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
+                                                      ctypes.POINTER(DgViewPoses)]),
+    "dg_render_ego_map_views_things": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
+                                                      ctypes.POINTER(DgViewPoses), _P]),
+    "dg_submit_floor_map_views_things": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
+                                                        ctypes.POINTER(DgViewSurfaces), ctypes.POINTER(DgViewPoses)]),
+    "dg_render_floor_map_views_things": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
+                                                        ctypes.POINTER(DgViewSurfaces), ctypes.POINTER(DgViewPoses), _P]),
     "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
     "dg_walk_free": (None, [_P]),
     "dg_walk_tics": (ctypes.c_int, [_P]),
@@ -658,6 +678,47 @@ def floor_map_host(scene, width: int, height: int, view, params, mask_row=None, 
     return out
 
 
+def _one_view_inputs(state, poses, surfaces=None):
+    """(dg_view_state *, dg_view_poses *, dg_view_surfaces *, keep-alive) of ONE view's inputs, each None or as make_view_* takes an entry."""
+    vs, k1 = make_view_states([state]) if state is not None else (None, None)
+    vp, k2 = make_view_poses([poses]) if poses is not None else (None, None)
+    vf, k3 = make_view_surfaces([surfaces]) if surfaces is not None else (None, None)
+    return vs, vp, vf, (k1, k2, k3)
+
+
+def map_thing_lines(scene, width: int, height: int, view, params, state=None, poses=None) -> np.ndarray:
+    """dg_map_thing_lines: the marker lines of one map frame in draw order, (n, 5) int64 rows [x0, y0, x1, y1, rgb]; state a (lights, mobjs)
+    pair and poses a list of (mobj, x, y, angle) entries, or None."""
+    p = _ego_params(params)
+    vs, vp, _, _keep = _one_view_inputs(state, poses)
+    n = _check(lib().dg_map_thing_lines(scene._h, width, height, ctypes.byref(view), ctypes.byref(p), vs, vp, None, 0))
+    arr = (DgMapLine * max(1, n))()
+    _check(lib().dg_map_thing_lines(scene._h, width, height, ctypes.byref(view), ctypes.byref(p), vs, vp, arr, n))
+    rows = np.frombuffer(arr, dtype=np.int32, count=5 * n).reshape(n, 5).astype(np.int64)
+    rows[:, 4] &= 0xFFFFFFFF
+    return rows
+
+
+def ego_map_things_host(scene, width: int, height: int, view, params, mask_row=None, state=None, poses=None) -> np.ndarray:
+    """dg_ego_map_things_host: one player-centred map frame with the map objects' markers (H, W, 3) uint8 by the literal rule."""
+    p = _ego_params(params)
+    _keep, mp = _mask_ptr(mask_row)
+    vs, vp, _, _keep2 = _one_view_inputs(state, poses)
+    out = np.empty((height, width, 3), dtype=np.uint8)
+    _check(lib().dg_ego_map_things_host(scene._h, width, height, ctypes.byref(view), ctypes.byref(p), mp, vs, vp, out.ctypes.data_as(_P)))
+    return out
+
+
+def floor_map_things_host(scene, width: int, height: int, view, params, mask_row=None, state=None, surfaces=None, poses=None) -> np.ndarray:
+    """dg_floor_map_things_host: one floor-textured map frame with the map objects' markers (H, W, 3) uint8 by the literal rule."""
+    p = _ego_params(params)
+    _keep, mp = _mask_ptr(mask_row)
+    vs, vp, vf, _keep2 = _one_view_inputs(state, poses, surfaces)
+    out = np.empty((height, width, 3), dtype=np.uint8)
+    _check(lib().dg_floor_map_things_host(scene._h, width, height, ctypes.byref(view), ctypes.byref(p), mp, vs, vf, vp, out.ctypes.data_as(_P)))
+    return out
+
+
 def make_view_states(states):
     """states: one (lights, mobjs) pair per view; lights = [(sector, light_level), ...], mobjs = [(mobj, sprite_frame or -1, full_bright), ...].
     Returns (ctypes array of dg_view_state, keep-alive list)."""
@@ -752,6 +813,15 @@ class Scene:
 
     def set_mobj_state(self, mobj: int, sprite, frame: int = 0, full_bright: bool = False):
         _check(lib().dg_scene_set_mobj_state(self._h, mobj, sprite.encode() if sprite else None, frame, int(full_bright)))
+
+    def set_map_markers(self, markers):
+        """dg_scene_set_map_markers: one (radius, rgb, flags) per map object (rgb r | g << 8 | b << 16, flags DG_MARK_BOX | DG_MARK_HEADING or 0),
+        or None: no table.  The host functions see it at once, a Context at upload_scene."""
+        if markers is None:
+            _check(lib().dg_scene_set_map_markers(self._h, None, 0))
+            return
+        arr = (DgMapMarker * max(1, len(markers)))(*[DgMapMarker(int(r), int(c), int(f)) for r, c, f in markers])
+        _check(lib().dg_scene_set_map_markers(self._h, arr, len(markers)))
 
     def set_wall_effects(self, flags: int):
         """dg_scene_set_wall_effects: DG_WALL_ANIMATE | DG_WALL_SCROLL, or 0 (may decode bitmaps: call before Context.upload_scene,
@@ -1137,6 +1207,47 @@ class Context:
         vf, _keep3 = make_view_surfaces(surfaces) if surfaces is not None else (None, None)
         out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
         _check(lib().dg_render_floor_map_views(self._h, views, n, ctypes.byref(p), mp, vs, vf, out.ctypes.data_as(_P)))
+        return out
+
+    def submit_ego_map_things(self, slot: int, views, params, mask=None, states=None, poses=None, n=None):
+        """dg_submit_ego_map_views_things: submit_ego_map with the map objects' markers (states / poses: one entry per view as
+        make_view_states / make_view_poses take them, or None), asynchronously."""
+        p = _ego_params(params)
+        _keep, mp = _mask_ptr(mask)
+        vs, _keep2 = make_view_states(states) if states is not None else (None, None)
+        vp, _keep3 = make_view_poses(poses) if poses is not None else (None, None)
+        _check(lib().dg_submit_ego_map_views_things(self._h, slot, views, len(views) if n is None else n, ctypes.byref(p), mp, vs, vp))
+
+    def render_ego_map_things(self, views, params, mask=None, states=None, poses=None) -> np.ndarray:
+        """dg_render_ego_map_views_things: synchronous through slot 0; returns (n, H, W, 3) uint8."""
+        n = len(views)
+        p = _ego_params(params)
+        _keep, mp = _mask_ptr(mask)
+        vs, _keep2 = make_view_states(states) if states is not None else (None, None)
+        vp, _keep3 = make_view_poses(poses) if poses is not None else (None, None)
+        out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
+        _check(lib().dg_render_ego_map_views_things(self._h, views, n, ctypes.byref(p), mp, vs, vp, out.ctypes.data_as(_P)))
+        return out
+
+    def submit_floor_map_things(self, slot: int, views, params, mask=None, states=None, surfaces=None, poses=None, n=None):
+        """dg_submit_floor_map_views_things: submit_floor_map with the map objects' markers, asynchronously."""
+        p = _ego_params(params)
+        _keep, mp = _mask_ptr(mask)
+        vs, _keep2 = make_view_states(states) if states is not None else (None, None)
+        vf, _keep3 = make_view_surfaces(surfaces) if surfaces is not None else (None, None)
+        vp, _keep4 = make_view_poses(poses) if poses is not None else (None, None)
+        _check(lib().dg_submit_floor_map_views_things(self._h, slot, views, len(views) if n is None else n, ctypes.byref(p), mp, vs, vf, vp))
+
+    def render_floor_map_things(self, views, params, mask=None, states=None, surfaces=None, poses=None) -> np.ndarray:
+        """dg_render_floor_map_views_things: synchronous through slot 0; returns (n, H, W, 3) uint8."""
+        n = len(views)
+        p = _ego_params(params)
+        _keep, mp = _mask_ptr(mask)
+        vs, _keep2 = make_view_states(states) if states is not None else (None, None)
+        vf, _keep3 = make_view_surfaces(surfaces) if surfaces is not None else (None, None)
+        vp, _keep4 = make_view_poses(poses) if poses is not None else (None, None)
+        out = np.empty((n, self.height, self.width, 3), dtype=np.uint8)
+        _check(lib().dg_render_floor_map_views_things(self._h, views, n, ctypes.byref(p), mp, vs, vf, vp, out.ctypes.data_as(_P)))
         return out
 
     def seen_lines_device(self, width: int, height: int, n_frames: int, id_ptr: int, cls_ptr: int, seen_ptr: int):

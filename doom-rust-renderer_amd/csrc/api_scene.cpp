@@ -17,6 +17,7 @@
 #include "floor_map_host.hpp"
 #include "explored_cover.hpp"
 #include "frontend.hpp"
+#include "map_things_host.hpp"
 #include "observe_core.h"
 #include "plane_core.h"
 #include "plane_reduce_core.h"
@@ -680,6 +681,80 @@ int dg_floor_map_host(const dg_scene *s, int width, int height, const dg_view *v
     rc = ego_check_view(v, err);
     if (!rc) rc = floor_frame_host(*s->sc, &s->sc->fx.light, width, height, v, *params, mask_row, state, surfaces, rgb24_out, err);
     return rc ? set_err(rc, err) : DG_OK;
+}
+
+int dg_scene_set_map_markers(dg_scene *s, const dg_map_marker *markers, int n) {
+    if (!s) return set_err(DG_ERR_INVALID, "null scene");
+    std::string err;
+    const int rc = thing_check_markers(markers, n, s->sc->mobjs.size(), err);
+    if (rc) return set_err(rc, err);
+    if (markers) s->sc->markers.assign(markers, markers + n);
+    else s->sc->markers.clear();
+    return DG_OK;
+}
+
+// What the three thing functions do alike: the contract's checks (floor: the floor-textured frames' too), then the view with its trig.
+static int thing_call_checked(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, bool floor, dg_view &v) {
+    if (!s || !view || !params) return set_err(DG_ERR_INVALID, "null argument");
+    std::string err;
+    int rc = floor ? floor_check_call(*s->sc, width, height, params, err) : ego_check_call(*s->sc, width, height, params, err);
+    if (!rc) rc = thing_check_call(*s->sc, err);
+    if (rc) return set_err(rc, err);
+    v = *view;
+    fill_view_trig(v);
+    rc = ego_check_view(v, err);
+    return rc ? set_err(rc, err) : DG_OK;
+}
+
+int dg_map_thing_lines(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const dg_view_state *state,
+                       const dg_view_poses *poses, dg_map_line *out, int cap) {
+    dg_view v;
+    int rc = thing_call_checked(s, width, height, view, params, false, v);
+    if (rc) return rc;
+    const Scene &sc = *s->sc;
+    static thread_local std::vector<dg_map_line> lines;
+    lines.clear();
+    std::string err;
+    rc = thing_view_lines(sc, thing_markers(sc, sc.markers), &sc.fx.mobj, width, height, v, *params, state, poses, lines, err);
+    if (rc) return set_err(rc, err);
+    if (out && cap >= 0 && (size_t)cap >= lines.size() && !lines.empty()) std::memcpy(out, lines.data(), lines.size() * sizeof(dg_map_line));
+    return (int)lines.size();
+}
+
+// The literal rule: black, the linedefs, the markers and the arrow in draw order, every point through map_seg_point.
+int dg_ego_map_things_host(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const uint32_t *mask_row,
+                           const dg_view_state *state, const dg_view_poses *poses, uint8_t *rgb24_out) {
+    if (!rgb24_out) return set_err(DG_ERR_INVALID, "null argument");
+    dg_view v;
+    int rc = thing_call_checked(s, width, height, view, params, false, v);
+    if (rc) return rc;
+    const Scene &sc = *s->sc;
+    std::vector<dg_map_line> lines;
+    std::string err;
+    rc = thing_all_lines(sc, thing_markers(sc, sc.markers), &sc.fx.mobj, width, height, v, *params, mask_row, state, poses, lines, err);
+    if (rc) return set_err(rc, err);
+    thing_draw_lines_host(lines, width, height, rgb24_out, nullptr);
+    return DG_OK;
+}
+
+// ... and the floor under every pixel none of them wrote (a black marker's pixel is the marker's, not the floor's).
+int dg_floor_map_things_host(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const uint32_t *mask_row,
+                             const dg_view_state *state, const dg_view_surfaces *surfaces, const dg_view_poses *poses, uint8_t *rgb24_out) {
+    if (!rgb24_out) return set_err(DG_ERR_INVALID, "null argument");
+    dg_view v;
+    int rc = thing_call_checked(s, width, height, view, params, true, v);
+    if (rc) return rc;
+    const Scene &sc = *s->sc;
+    std::vector<dg_map_line> lines;
+    std::string err;
+    rc = thing_all_lines(sc, thing_markers(sc, sc.markers), &sc.fx.mobj, width, height, v, *params, mask_row, state, poses, lines, err);
+    FloorFrameHost F;
+    if (!rc) rc = floor_frame_prepare(sc, &sc.fx.light, v, mask_row, state, surfaces, F, err);
+    if (rc) return set_err(rc, err);
+    std::vector<uint8_t> covered;
+    thing_draw_lines_host(lines, width, height, rgb24_out, &covered);
+    floor_frame_fill(sc, F, width, height, v, *params, mask_row, rgb24_out, [&](size_t at) { return covered[at] != 0; });
+    return DG_OK;
 }
 
 }  // extern "C"

@@ -42,6 +42,8 @@
 #include "ego_kernels.hpp"
 #include "floor_map_host.hpp"
 #include "floor_map_kernels.hpp"
+#include "map_things_host.hpp"
+#include "map_things_kernels.hpp"
 #include "explored_cover.hpp"
 #include "explored_kernels.hpp"
 #include "map_kernels.hpp"
@@ -743,6 +745,28 @@ int upload_floor_table(dg_ctx *c, Slot &s) {
     return DG_OK;
 }
 
+// The marker and place tables of the uploaded scene (thing_tables) with the marker table the ctx took, for the map frames with markers:
+// one allocation, made by the first such submission after dg_upload_scene (untimed: 28 bytes per map object).  No marker table: an
+// empty one, and the kernels' things phase has nothing to do.
+int upload_thing_table(dg_ctx *c) {
+    const Scene &sc = *c->scene;
+    const std::vector<dg_map_marker> *markers = thing_markers(sc, c->markers);
+    std::vector<ThingMarker> tm;
+    std::vector<ThingPlace> tp;
+    if (markers) thing_tables(sc, *markers, tm, tp);
+    const size_t n = tm.size();
+    DevPtr<uint8_t> table;
+    HIP_TRY(hip_alloc(table, std::max<size_t>(n * (sizeof(ThingMarker) + sizeof(ThingPlace)), 16)));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(table.get(), tp.data(), n * sizeof(ThingPlace), hipMemcpyHostToDevice, c->kstream.get()));
+        HIP_TRY(hipMemcpyAsync(table.get() + n * sizeof(ThingPlace), tm.data(), n * sizeof(ThingMarker), hipMemcpyHostToDevice, c->kstream.get()));
+        HIP_TRY(hipStreamSynchronize(c->kstream.get()));  // (before the host copies go)
+    }
+    c->per_scene.things = (uint32_t)n;
+    c->per_scene.thing_table = std::move(table);
+    return DG_OK;
+}
+
 // The per-scene table of the slot's map kind: built by the first such submission after dg_upload_scene, which then has a timed front half.
 int ensure_map_table(dg_ctx *c, Slot &s) {
     s.map.built = false;
@@ -810,13 +834,27 @@ int enqueue_map_frames(dg_ctx *c, Slot &s) {
         E.scale = s.map.ego.scale; E.rotate = s.map.ego.flags & EGO_ROTATE;
         E.W = W; E.H = H;
         E.fb = s.d_fb.get(); E.n_frames = s.n_frames;
+        ThingParams T{};                                  // a *_things submission: the same frames through the kernels with the things phase
+        if (s.map.things) {
+            if (!t.thing_table) { if (const int rc = upload_thing_table(c)) return rc; }
+            const uint8_t *const d = s.per_scene.d_things.get();
+            T.places = reinterpret_cast<const ThingPlace *>(t.thing_table.get());
+            T.markers = reinterpret_cast<const ThingMarker *>(t.thing_table.get() + (size_t)t.things * sizeof(ThingPlace));
+            T.n_things = t.things;
+            T.shown = reinterpret_cast<const uint32_t *>(d);
+            T.shown_words = thing_shown_words(t.things);
+            T.first = reinterpret_cast<const uint32_t *>(d + s.map.things_first);
+            T.entries = reinterpret_cast<const ThingEntry *>(d + s.map.things_entries);
+        }
         if (s.front_end == DG_FE_MAP_FLOOR) {
             const Slot::PerScene &b = s.per_scene;
             const uint32_t seen_words = (uint32_t)floor_seen_words(*c->scene);
             if (E.masks) HIP_TRY(launch_floor_seen_sectors(t.floor_lines, t.ego_lines, t.floor_T.n_sectors, E.masks, E.mask_words, b.d_floor_seen.get(), seen_words, s.n_frames, ks));
             const FloorMapParams Q{E, t.floor_T, b.d_floor_cells.get(), E.masks ? b.d_floor_seen.get() : nullptr, seen_words, 1.0f / s.map.ego.scale};
-            HIP_TRY(launch_floor_map_tiles(Q, ks, s.ev_rstart.get(), s.ev_raster.get()));
-        } else HIP_TRY(launch_ego_tiles(E, ks, s.ev_rstart.get(), s.ev_raster.get()));
+            if (s.map.things) HIP_TRY(launch_floor_thing_tiles(Q, T, ks, s.ev_rstart.get(), s.ev_raster.get()));
+            else HIP_TRY(launch_floor_map_tiles(Q, ks, s.ev_rstart.get(), s.ev_raster.get()));
+        } else if (s.map.things) HIP_TRY(launch_ego_thing_tiles(E, T, ks, s.ev_rstart.get(), s.ev_raster.get()));
+        else HIP_TRY(launch_ego_tiles(E, ks, s.ev_rstart.get(), s.ev_raster.get()));
     }
     guard.armed = false;
     return queued(s);                                     // (never DG_FE_AUTO's measurement)
@@ -1199,14 +1237,71 @@ int ensure_slot_floor(dg_ctx *c, Slot &s) {
     return DG_OK;
 }
 
+// The slot's things block (staging + HBM) holds at least `bytes`: there from its first *_things submission after dg_upload_scene on, and
+// grown (never shrunk) when a submission brings more pose entries than any before it.
+int ensure_slot_things(dg_ctx *c, Slot &s, size_t bytes) {
+    Slot::PerScene &b = s.per_scene;
+    if (b.d_things && b.things_cap >= bytes) return DG_OK;
+    HIP_TRY(slot_sync(s));
+    const size_t cap = std::max<size_t>(bytes + bytes / 2, 256);
+    b.things_cap = 0;
+    HIP_TRY(hip_alloc(b.h_things, cap));
+    HIP_TRY(hip_alloc(b.d_things, cap));
+    b.things_cap = cap;
+    return DG_OK;
+}
+
+// What a *_things submission ships: n rows of shown bits, the entry index first[n + 1] and the frames' sorted pose entries, in one block.
+struct ThingBatch {
+    std::vector<uint8_t> block;
+    size_t first_at = 0, entries_at = 0;
+};
+
+// Every view's rows and entries of a *_things submission (thing_view_rows), with every check of its states and poses: the block as the
+// kernels read it.  The ctx's marker table does not fit the scene, or there is none: rows of no words and no entries.
+int build_thing_batch(dg_ctx *c, const dg_view *views, int n, const dg_view_state *states, const dg_view_poses *poses, ThingBatch &out) {
+    const Scene &sc = *c->scene;
+    std::string err;
+    int rc = thing_check_call(sc, err);
+    if (rc) return set_err(rc, err);
+    const std::vector<dg_map_marker> *markers = thing_markers(sc, c->markers);
+    const size_t words = markers ? thing_shown_words((uint32_t)sc.mobjs.size()) : 0;
+    static thread_local std::vector<uint32_t> rows, first;
+    static thread_local std::vector<ThingEntry> entries;
+    static thread_local ThingViewScratch scratch;
+    rows.assign((size_t)n * words, 0u);
+    first.assign((size_t)n + 1, 0u);
+    entries.clear();
+    for (int i = 0; i < n; i++) {
+        first[(size_t)i] = (uint32_t)entries.size();
+        const ViewInputs in{states ? states + i : nullptr, poses ? poses + i : nullptr};
+        if (!markers) rc = check_view_inputs(in, err) ? DG_OK : DG_ERR_INVALID;
+        else {
+            dg_view v = views[i];
+            fill_view_trig(v);
+            rc = thing_view_rows(sc, *markers, &c->fx.mobj, v, in.state, in.poses, scratch, rows.data() + (size_t)i * words, entries, err);
+        }
+        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
+        if (entries.size() > 0x7fffffffu) return set_err(DG_ERR_CAPACITY, "map markers: too many pose entries in one submission");
+    }
+    first[(size_t)n] = (uint32_t)entries.size();
+    out.first_at = rows.size() * sizeof(uint32_t);
+    out.entries_at = out.first_at + first.size() * sizeof(uint32_t);
+    out.block.resize(out.entries_at + std::max<size_t>(entries.size(), 1) * sizeof(ThingEntry));
+    if (!rows.empty()) std::memcpy(out.block.data(), rows.data(), out.first_at);
+    std::memcpy(out.block.data() + out.first_at, first.data(), first.size() * sizeof(uint32_t));
+    if (!entries.empty()) std::memcpy(out.block.data() + out.entries_at, entries.data(), entries.size() * sizeof(ThingEntry));
+    return DG_OK;
+}
+
 // What the map submissions do alike once each has checked its own arguments: slot `slot` for n map frames of kind fe, and their
 // kernels enqueued.  arrow_lines(v, l, err): the kind's per-view checks and the arrow's three lines of view v (trig filled; the host owns
 // the libm trig: dg_view has no field for the head angles) into l, which starts as three empty lines.  ego: a player-centred submission's
 // parameters (else null): its views follow the arrow lines.  mask: n rows of the scene's row length, or null.  cells: a floor-textured
-// submission's n rows of floor cells (else null).
+// submission's n rows of floor cells (else null).  things: a *_things submission's block (else null).
 template <class ArrowLines>
 int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int n, const dg_ego_map *ego, const uint32_t *mask, ArrowLines arrow_lines,
-                      const FloorCell *cells = nullptr) {
+                      const FloorCell *cells = nullptr, const ThingBatch *things = nullptr) {
     const int W = c->cfg.width, H = c->cfg.height;
     const size_t words = seen_words((uint32_t)c->scene->linedefs.size());
     const size_t bytes = ego_views_at(n) + (ego ? (size_t)n * sizeof(EgoView) : 0), mask_bytes = mask ? (size_t)n * words * sizeof(uint32_t) : 0;
@@ -1217,6 +1312,8 @@ int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int
     if (bytes > s.lists_cap) return set_err(DG_ERR_CAPACITY, "list slab too small");
     if (mask && (rc = ensure_slot_masks(c, s, words))) return rc;
     if (cells && (rc = ensure_slot_floor(c, s))) return rc;
+    if (things && (rc = ensure_slot_things(c, s, things->block.size()))) return rc;
+    const size_t thing_bytes = things ? things->block.size() : 0;
     const size_t cell_bytes = cells ? (size_t)n * c->scene->sectors.size() * sizeof(FloorCell) : 0;
     const auto t0 = std::chrono::steady_clock::now();
     MapSeg *h = reinterpret_cast<MapSeg *>(s.h_lists.get());
@@ -1233,13 +1330,15 @@ int submit_map_frames(dg_ctx *c, int slot, int32_t fe, const dg_view *views, int
     }
     if (mask) std::memcpy(s.per_scene.h_masks.get(), mask, mask_bytes);
     if (cells) std::memcpy(s.per_scene.h_floor_cells.get(), cells, cell_bytes);
-    s.map = Slot::MapState{ego ? *ego : dg_ego_map{}, mask != nullptr, false};
-    s.describe(fe, n, bytes + mask_bytes + cell_bytes, 0, 0);
+    if (things) std::memcpy(s.per_scene.h_things.get(), things->block.data(), thing_bytes);
+    s.map = Slot::MapState{ego ? *ego : dg_ego_map{}, mask != nullptr, false, things != nullptr, things ? things->first_at : 0, things ? things->entries_at : 0};
+    s.describe(fe, n, bytes + mask_bytes + cell_bytes + thing_bytes, 0, 0);
     built_from(s, nullptr, BatchInputs{}, n);
     s.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     HIP_TRY(hipMemcpyAsync(s.d_lists.get(), s.h_lists.get(), bytes, hipMemcpyHostToDevice, s.stream.get()));
     if (mask) HIP_TRY(hipMemcpyAsync(s.per_scene.d_masks.get(), s.per_scene.h_masks.get(), mask_bytes, hipMemcpyHostToDevice, s.stream.get()));
     if (cells) HIP_TRY(hipMemcpyAsync(s.per_scene.d_floor_cells.get(), s.per_scene.h_floor_cells.get(), cell_bytes, hipMemcpyHostToDevice, s.stream.get()));
+    if (things) HIP_TRY(hipMemcpyAsync(s.per_scene.d_things.get(), s.per_scene.h_things.get(), thing_bytes, hipMemcpyHostToDevice, s.stream.get()));
     return enqueue_kernels(c, s);
 }
 
@@ -1411,6 +1510,7 @@ int dg_upload_scene(dg_ctx *c, const dg_scene *scene) {
     HIP_TRY(hipDeviceSynchronize());
     c->scene = &sc;
     c->fx = sc.fx;                                      // the effects' setters (and dg_scene_mobj_event) take effect here
+    c->markers = sc.markers;
     c->fe_scene_ok = sky.w >= 256 && sky.h >= 128;    // a smaller sky bitmap is an index panic only when a sky visplane is drawn: host path
     c->uploaded_texels = sc.texel_idx.size();
     c->pictures = overlay_pictures(sc);
@@ -1681,9 +1781,44 @@ int dg_render_ego_map_views(dg_ctx *c, const dg_view *views, int n, const dg_ego
     return read_or_wait(c, 0, dg_submit_ego_map_views(c, 0, views, n, params, mask), n, out);
 }
 
-// Every check of the call and of every view comes before the slot is touched: the cells of all n views are built first.
-int dg_submit_floor_map_views(dg_ctx *c, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,
-                              const dg_view_surfaces *surfaces) {
+// dg_submit_ego_map_views with the things block; every check of every view, its state and its poses comes before the slot is touched.
+int dg_submit_ego_map_views_things(dg_ctx *c, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,
+                                   const dg_view_poses *poses) {
+    int rc = check_slot(c, slot);
+    if (rc) return rc;
+    if (!views || !params) return set_err(DG_ERR_INVALID, "null views or params");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    const int W = c->cfg.width, H = c->cfg.height;
+    std::string err;
+    rc = ego_check_call(*c->scene, W, H, params, err);
+    if (rc) return set_err(rc, err);
+    if (n <= 0 || n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "batch size outside [1, max_batch]");
+    const bool arrow = (params->flags & EGO_ARROW) != 0;
+    for (int i = 0; i < n; i++) {
+        dg_view v = views[i];
+        fill_view_trig(v);
+        dg_map_line l[3] = {};
+        rc = ego_check_view(v, err);
+        if (!rc && arrow) rc = ego_arrow_lines(W, H, v, *params, l, err);
+        if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
+    }
+    static thread_local ThingBatch batch;
+    rc = build_thing_batch(c, views, n, states, poses, batch);
+    if (rc) return rc;
+    return submit_map_frames(c, slot, DG_FE_MAP_EGO, views, n, params, mask, [&](const dg_view &v, dg_map_line *l, std::string &why) {
+        return arrow ? ego_arrow_lines(W, H, v, *params, l, why) : DG_OK;
+    }, nullptr, &batch);
+}
+
+int dg_render_ego_map_views_things(dg_ctx *c, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,
+                                   const dg_view_poses *poses, uint8_t *out) {
+    return read_or_wait(c, 0, dg_submit_ego_map_views_things(c, 0, views, n, params, mask, states, poses), n, out);
+}
+
+// dg_submit_floor_map_views and its *_things form.  Every check of the call and of every view comes before the slot is touched: the
+// cells of all n views (and, with things, their rows and entries) are built first.
+static int submit_floor_frames(dg_ctx *c, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,
+                               const dg_view_surfaces *surfaces, bool things, const dg_view_poses *poses) {
     int rc = check_slot(c, slot);
     if (rc) return rc;
     if (!views || !params) return set_err(DG_ERR_INVALID, "null views or params");
@@ -1699,6 +1834,7 @@ int dg_submit_floor_map_views(dg_ctx *c, int slot, const dg_view *views, int n, 
     const size_t S = sc.sectors.size();
     static thread_local std::vector<FloorCell> cells;
     static thread_local FloorRowScratch scratch;
+    static thread_local ThingBatch batch;
     cells.resize((size_t)n * S);
     for (int i = 0; i < n; i++) {
         dg_view v = views[i];
@@ -1709,9 +1845,25 @@ int dg_submit_floor_map_views(dg_ctx *c, int slot, const dg_view *views, int n, 
         if (!rc) rc = floor_view_cells(sc, &c->fx.light, v, states ? states + i : nullptr, surfaces ? surfaces + i : nullptr, scratch, cells.data() + (size_t)i * S, err);
         if (rc) return set_err(rc, "frame " + std::to_string(i) + ": " + err);
     }
+    if (things && (rc = build_thing_batch(c, views, n, states, poses, batch))) return rc;
     return submit_map_frames(c, slot, DG_FE_MAP_FLOOR, views, n, params, mask, [&](const dg_view &v, dg_map_line *l, std::string &why) {
         return arrow ? ego_arrow_lines(W, H, v, *params, l, why) : DG_OK;
-    }, cells.data());
+    }, cells.data(), things ? &batch : nullptr);
+}
+
+int dg_submit_floor_map_views(dg_ctx *c, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,
+                              const dg_view_surfaces *surfaces) {
+    return submit_floor_frames(c, slot, views, n, params, mask, states, surfaces, false, nullptr);
+}
+
+int dg_submit_floor_map_views_things(dg_ctx *c, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,
+                                     const dg_view_surfaces *surfaces, const dg_view_poses *poses) {
+    return submit_floor_frames(c, slot, views, n, params, mask, states, surfaces, true, poses);
+}
+
+int dg_render_floor_map_views_things(dg_ctx *c, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,
+                                     const dg_view_surfaces *surfaces, const dg_view_poses *poses, uint8_t *out) {
+    return read_or_wait(c, 0, dg_submit_floor_map_views_things(c, 0, views, n, params, mask, states, surfaces, poses), n, out);
 }
 
 int dg_render_floor_map_views(dg_ctx *c, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask, const dg_view_state *states,

@@ -116,6 +116,11 @@ struct Slot {
         PinnedPtr<FloorCell> h_floor_cells;
         DevPtr<FloorCell> d_floor_cells;
         DevPtr<uint32_t> d_floor_seen;
+        // map frames with markers: the last such submission's shown rows [n][ceil(map objects / 32)], entry index [n + 1]
+        // and sorted pose entries in one block (staging + HBM), there from the slot's first such submission on and grown when one needs more
+        PinnedPtr<uint8_t> h_things;
+        DevPtr<uint8_t> d_things;
+        size_t things_cap = 0;
         // per-view map-object poses, sector heights (§8n) and sector flats (§8p) through the seg walk.  Unlike the others
         // these are taken at dg_upload_scene (upload_fs_scene), so that nothing is allocated on the submit path.
         RowBuffers<PoseRows> poses;
@@ -132,6 +137,8 @@ struct Slot {
         dg_ego_map ego{};                // DG_FE_MAP_EGO, DG_FE_MAP_FLOOR: scale and flags
         bool masked = false;             // the kernel reads the slot's mask rows (a player-centred submission may come without)
         bool built = false;              // the enqueue built the kind's per-scene table: ev_start .. ev_setup time that
+        bool things = false;             // a *_things submission: the kernels with the things phase, reading the slot's things block
+        size_t things_first = 0, things_entries = 0;   // ... where its entry index and its entries start in that block (the rows: at 0)
     } map;
     // last submission
     RasterParams P{};
@@ -296,6 +303,7 @@ struct dg_ctx {
     // the scene's effects as of dg_upload_scene (every front end draws with this copy), and for the seg walk the device tables of each
     // effect that is on (only while the seg walk is uploaded)
     SceneFx fx;
+    std::vector<dg_map_marker> markers; // ... and its marker table (dg_scene_set_map_markers), or empty
     DevPtr<uint8_t> d_wall_fx;          // FsSegFx per seg | the live animation lists
     FsFx fs_fx{};
     DevPtr<uint8_t> d_light_fx;         // LfxRec per effect sector | rec_of per sector | tables
@@ -331,6 +339,8 @@ struct dg_ctx {
         DevPtr<uint8_t> floor_table;        // floor-textured map frames: segs, nodes, leaves and the linedefs' sectors (upload_floor_table)
         FloorTables floor_T{};              // ... as dg_floor_map_tiles reads them
         const FloorLine *floor_lines = nullptr;
+        DevPtr<uint8_t> thing_table;        // map frames with markers: ThingMarker per map object, then ThingPlace per map object (upload_thing_table)
+        uint32_t things = 0;                // ... their count; 0 with a table: the ctx took no marker table
         DevPtr<uint32_t> seg_line;          // dg_seen_lines_device / dg_slot_seen_lines: seg -> linedef (ensure_seen)
         DevPtr<uint32_t> seen_scratch;      // dg_slot_seen_lines: its scratch rows, sized by max_batch and the scene's row length
         DevPtr<uint8_t> walk_tables;        // dg_ctx_locate_walks: the node and leaf tables (walk_core.h)

@@ -102,6 +102,44 @@ inline void floor_seen_row(const Scene &sc, const FloorHostTables &t, const uint
     }
 }
 
+// What the floor under one view's frame is drawn with on the host: the scene's tables, the view's cells and its sector row.
+struct FloorFrameHost {
+    FloorHostTables t;
+    FloorRowScratch A;
+    std::vector<FloorCell> row;
+    std::vector<uint32_t> seen;
+    uint32_t pal[256];
+};
+// ... built, with every check of the view's state and surfaces (floor_view_cells).
+inline int floor_frame_prepare(const Scene &sc, const LightFx *lfx, const dg_view &view, const uint32_t *mask_row, const dg_view_state *state,
+                               const dg_view_surfaces *surfaces, FloorFrameHost &F, std::string &err) {
+    floor_tables(sc, F.t);
+    F.row.resize(sc.sectors.size());
+    const int rc = floor_view_cells(sc, lfx, view, state, surfaces, F.A, F.row.data(), err);
+    if (rc) return rc;
+    F.seen.clear();
+    if (mask_row) { F.seen.resize(floor_seen_words(sc)); floor_seen_row(sc, F.t, mask_row, F.seen.data()); }
+    floor_palette(sc, F.pal);
+    return DG_OK;
+}
+// Every pixel of the frame that no line covers (covered(Y * W + X) false) through floor_pixel.
+template <class Covered>
+inline void floor_frame_fill(const Scene &sc, const FloorFrameHost &F, int W, int H, const dg_view &view, const dg_ego_map &p, const uint32_t *mask_row, uint8_t *out,
+                             Covered covered) {
+    const FloorTables T = floor_tables_host(sc, F.t, F.pal);
+    const EgoView v = ego_view(view);
+    const float inv = 1.0f / p.scale;
+    const bool rotate = (p.flags & EGO_ROTATE) != 0;
+    for (int32_t Y = 0; Y < H; Y++)
+        for (int32_t X = 0; X < W; X++) {
+            const size_t at = (size_t)Y * (size_t)W + (size_t)X;
+            if (covered(at)) continue;
+            uint8_t *const px = out + 3 * at;
+            const uint32_t c = floor_value_rgb(floor_pixel(T, F.row.data(), mask_row ? F.seen.data() : nullptr, X, Y, W, H, v, inv, rotate));
+            px[0] = (uint8_t)c; px[1] = (uint8_t)(c >> 8); px[2] = (uint8_t)(c >> 16);
+        }
+}
+
 // One frame by the literal rule (call and view checked, trig filled): dg_ego_map_host's frame, and every pixel it left black through
 // floor_pixel.  (A line is never black: red or yellow.)
 inline int floor_frame_host(const Scene &sc, const LightFx *lfx, int W, int H, const dg_view &view, const dg_ego_map &p, const uint32_t *mask_row,
@@ -109,28 +147,11 @@ inline int floor_frame_host(const Scene &sc, const LightFx *lfx, int W, int H, c
     std::vector<dg_map_line> lines;
     int rc = ego_frame_lines(sc, W, H, view, p, mask_row, lines, err);
     if (rc) return rc;
-    FloorHostTables t;
-    floor_tables(sc, t);
-    FloorRowScratch A;
-    std::vector<FloorCell> row(sc.sectors.size());
-    rc = floor_view_cells(sc, lfx, view, state, surfaces, A, row.data(), err);
+    FloorFrameHost F;
+    rc = floor_frame_prepare(sc, lfx, view, mask_row, state, surfaces, F, err);
     if (rc) return rc;
-    std::vector<uint32_t> seen;
-    if (mask_row) { seen.resize(floor_seen_words(sc)); floor_seen_row(sc, t, mask_row, seen.data()); }
-    uint32_t pal[256];
-    floor_palette(sc, pal);
-    const FloorTables T = floor_tables_host(sc, t, pal);
     map_draw_lines_host(lines.data(), lines.size(), W, H, out, [](size_t) { return true; });
-    const EgoView v = ego_view(view);
-    const float inv = 1.0f / p.scale;
-    const bool rotate = (p.flags & EGO_ROTATE) != 0;
-    for (int32_t Y = 0; Y < H; Y++)
-        for (int32_t X = 0; X < W; X++) {
-            uint8_t *const px = out + 3 * ((size_t)Y * (size_t)W + (size_t)X);
-            if (px[0] | px[1] | px[2]) continue;
-            const uint32_t c = floor_value_rgb(floor_pixel(T, row.data(), mask_row ? seen.data() : nullptr, X, Y, W, H, v, inv, rotate));
-            px[0] = (uint8_t)c; px[1] = (uint8_t)(c >> 8); px[2] = (uint8_t)(c >> 16);
-        }
+    floor_frame_fill(sc, F, W, H, view, p, mask_row, out, [&](size_t at) { return (out[3 * at] | out[3 * at + 1] | out[3 * at + 2]) != 0; });
     return DG_OK;
 }
 

@@ -146,6 +146,7 @@ struct Scene {
     // as last set by set_wall_effects, set_light_effects and set_mobj_thinkers / mobj_event (dg_build_lists, dg_scene_sector_lights_at and
     // dg_scene_mobj_states_at read it)
     SceneFx fx;
+    std::vector<dg_map_marker> markers;             // the map frames' marker table (dg_scene_set_map_markers): one per map object, or empty
     // The per-seg / per-sprite inputs of fs_core.h, flattened (rebuild_fs_tables: at load and whenever bitmaps or sprite frames are added):
     // what the host walker reads per seg and what dg_upload_scene copies to the GPU for DG_FE_DEVICE_SEGS.
     std::vector<FsSeg> fs_segs;                     // one per seg

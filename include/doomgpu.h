@@ -767,7 +767,8 @@ int  dg_ctx_locate_walks(dg_ctx *ctx, dg_walk *const *walks, int n_walks);
  *     every time;
  *   dg_view_state entries, the map-object thinkers, the light effects and the wall effects compose unchanged; a dg_view_state entry and
  *     a pose entry for the same object are independent (one says what it looks like, the other where it is).
- * The 2-D map submissions draw no objects and take no poses.  Every front end gives the same pixels; with DG_FE_DEVICE_SEGS (and
+ * The 2-D map submissions take no poses and draw no objects, except the *_things map submissions (section 8u), which draw every object's
+ * marker where its pose puts it.  Every front end gives the same pixels; with DG_FE_DEVICE_SEGS (and
  * DG_FE_AUTO when it picks the seg walk) the host ships only the entries, and two kernels in front of the seg walk write the batch's
  * rows [frame][object] and find the moved objects' sectors on the GPU (device memory per slot: max_batch x map objects x 16 B of rows
  * and 20 B of entry staging, taken at dg_upload_scene; when that allocation fails, batches with poses take the host walker — same
@@ -991,12 +992,71 @@ int dg_submit_floor_map_views(dg_ctx *ctx, int slot, const dg_view *views, int n
 int dg_render_floor_map_views(dg_ctx *ctx, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask,
                               const dg_view_state *states, const dg_view_surfaces *surfaces, uint8_t *rgb24_out);
 
+/* ---- map objects on the player-centred and floor-textured map frames ------------------------------------------ */
+/* ViZDoom's OBJECTS / OBJECTS_WITH_SIZE automap modes, vanilla's am_cheat markers: every map object as its collision box and a heading
+ * line, where a dg_view_poses puts it and in the state a dg_view_state or the map-object thinkers give it.
+ *   the marker table          per scene, one entry per map object, from the caller (the library ships none, like the state tables of
+ *                             dg_scene_set_mobj_thinkers): radius in map units, colour, and which parts are drawn.  flags 0: the object
+ *                             has no marker.
+ *   which objects are shown   for a view, object i is shown when its marker has a flag set; its sprite_frame for that view is not -1
+ *                             (composed as for the colour frame: a dg_view_state entry wins, else the thinker's state at view.timestamp
+ *                             with DG_MOBJ_THINKERS, else the scene's); and its position is finite with |x|, |y| <= 32768 (the view's
+ *                             later dg_view_poses entry for i, else as loaded).  An object that fails one of these is not drawn in that
+ *                             view; that is no error.  The object's sector plays no part: an object outside every subsector is on the map.
+ *   the marker                R = (float)radius, a = the object's angle (the pose entry's, else as loaded), every operation in f32, no
+ *                             contraction.  DG_MARK_BOX: c0 = (x-R, y-R), c1 = (x+R, y-R), c2 = (x+R, y+R), c3 = (x-R, y+R) and the
+ *                             lines c0->c1, c1->c2, c2->c3, c3->c0 — Doom's own map-axis-aligned collision box, so it turns with the map
+ *                             under DG_EGO_ROTATE.  DG_MARK_HEADING: after the box, the line (x, y) -> (x + R*ca, y + R*sa) with
+ *                             ca = cosf(a), sa = sinf(a) from the host's libm (the libm caveat of the arrow applies to this line and to
+ *                             nothing else; an angle that is not finite has no heading line).  Every endpoint goes through the point rule
+ *                             of the player-centred frames unchanged, every line through the SDL line rule of the map view, points outside
+ *                             the frame dropped.
+ *   draw order and colour     the linedefs as in dg_ego_map_host (with their mask; the mask row does not touch markers), then the objects
+ *                             in index order (box lines, then heading), then the arrow; a later line goes over an earlier one.  A marker
+ *                             pixel has the marker's rgb, on a floor-textured frame too (rgb 0 is a black pixel, not a floor pixel).
+ * In contract: |x|, |y| <= 32768 and R <= 1024 put an endpoint within +-33792, so with |view.x|, |view.y| <= 65536 |r|, |f| <= 2 * 99328,
+ * times 64 plus 8192 stays below 2^24 — the line rule's precondition holds for every marker line of every in-contract view. */
+typedef struct dg_map_marker { int32_t radius; uint32_t rgb; uint32_t flags; } dg_map_marker;   /* rgb: r | g<<8 | b<<16 */
+enum { DG_MARK_BOX = 1u, DG_MARK_HEADING = 2u };   /* flags 0: the object has no marker */
+/* Sets the scene's marker table (copied); n must be dg_scene_mobj_count.  markers == NULL && n == 0 drops the table.  DG_ERR_INVALID: a
+ * NULL scene, a radius outside [0, 1024], rgb above 0xffffff, unknown flag bits, a wrong n.  The host functions below see the table at
+ * once; a ctx takes it at dg_upload_scene, like the other scene settings. */
+int dg_scene_set_map_markers(dg_scene *s, const dg_map_marker *markers, int n);
+/* The marker lines of one frame in draw order, transformed and unclipped, with the marker's colour.  Returns the count; sizing and overflow
+ * as dg_ego_map_lines.  state / poses: NULL, or the view's (entries validated as in dg_submit_views_state / dg_submit_views_poses: an
+ * index out of range or a NULL array with n > 0 is DG_ERR_INVALID).  No marker table: 0.  Errors as dg_ego_map_lines; a scene with more
+ * than 65 536 map objects: DG_ERR_CAPACITY. */
+int dg_map_thing_lines(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const dg_view_state *state,
+                       const dg_view_poses *poses, dg_map_line *out, int cap);
+/* dg_ego_map_host / dg_floor_map_host with the markers, by the literal rule, with the scene's effects as last set.  With no marker
+ * table, or one whose flags are all 0, the bytes are theirs.  Everything is checked before the first byte is written. */
+int dg_ego_map_things_host(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const uint32_t *mask_row,
+                           const dg_view_state *state, const dg_view_poses *poses, uint8_t *rgb24_out);
+int dg_floor_map_things_host(const dg_scene *s, int width, int height, const dg_view *view, const dg_ego_map *params, const uint32_t *mask_row,
+                             const dg_view_state *state, const dg_view_surfaces *surfaces, const dg_view_poses *poses, uint8_t *rgb24_out);
+/* dg_submit_ego_map_views / dg_submit_floor_map_views with the markers of the table the ctx took at dg_upload_scene; states / poses NULL or
+ * [n].  The existing calls and their kernels are untouched: these run dg_ego_thing_tiles / dg_floor_thing_tiles, the same band kernels
+ * with one more phase.  Colour frames like every map submission (readbacks, checksums, reduced readbacks, dg_observe_device,
+ * dg_slot_overlay, dg_replay_slot); dg_slot_timing gives DG_FE_MAP_EGO / DG_FE_MAP_FLOOR with the new kernel in raster_ms.  Every check
+ * comes before the slot is touched.  Per submission the host ships, per frame, a row of shown bits (one per object) and the frame's pose
+ * entries after later-wins, sorted by object (20 bytes each); the scene's marker and place tables (28 bytes per object) are uploaded by
+ * the first such submission after dg_upload_scene, and the slot keeps what a replay needs in device memory, allocated at first use.  The
+ * device never evaluates a trigonometric function.  Errors as the plain calls and as dg_map_thing_lines. */
+int dg_submit_ego_map_views_things(dg_ctx *ctx, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask,
+                                   const dg_view_state *states, const dg_view_poses *poses);
+int dg_render_ego_map_views_things(dg_ctx *ctx, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask,
+                                   const dg_view_state *states, const dg_view_poses *poses, uint8_t *rgb24_out);
+int dg_submit_floor_map_views_things(dg_ctx *ctx, int slot, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask,
+                                     const dg_view_state *states, const dg_view_surfaces *surfaces, const dg_view_poses *poses);
+int dg_render_floor_map_views_things(dg_ctx *ctx, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask,
+                                     const dg_view_state *states, const dg_view_surfaces *surfaces, const dg_view_poses *poses, uint8_t *rgb24_out);
+
 /* ---- misc ----------------------------------------------------------------------------------------------------- */
 const char *dg_last_error(void); /* thread-local message of the last failing call */
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors, the surfaces, the screen pictures, the floor-textured map frames) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors, the surfaces, the screen pictures, the floor-textured map frames, the map-object markers) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
