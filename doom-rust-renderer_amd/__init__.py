@@ -363,6 +363,13 @@ _SIGNATURES = {
                                                         ctypes.POINTER(DgViewSurfaces), ctypes.POINTER(DgViewPoses)]),
     "dg_render_floor_map_views_things": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.c_int, ctypes.POINTER(DgEgoMap), _P, ctypes.POINTER(DgViewState),
                                                         ctypes.POINTER(DgViewSurfaces), ctypes.POINTER(DgViewPoses), _P]),
+    "dg_sight_host": (ctypes.c_int, [_P, ctypes.POINTER(DgViewSectors), ctypes.c_int, _P, ctypes.c_int, _P]),
+    "dg_sight_device": (ctypes.c_int, [_P, ctypes.POINTER(DgViewSectors), ctypes.c_int, _P, ctypes.c_int, _P]),
+    "dg_sight_words": (ctypes.c_int, [_P]),
+    "dg_sight_mobjs_host": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.c_int, ctypes.c_float, _P, _P]),
+    "dg_sight_mobjs_device": (ctypes.c_int, [_P, ctypes.POINTER(DgView), ctypes.POINTER(DgViewPoses), ctypes.POINTER(DgViewSectors), ctypes.c_int, ctypes.c_float, _P, _P]),
+    "dg_ctx_sight_kernel_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "dg_scene_bsp_depth": (ctypes.c_int, [_P]),
     "dg_walk_create": (ctypes.c_int, [_P, ctypes.POINTER(DgWalkDesc), ctypes.POINTER(_P)]),
     "dg_walk_free": (None, [_P]),
     "dg_walk_tics": (ctypes.c_int, [_P]),
@@ -719,6 +726,41 @@ def floor_map_things_host(scene, width: int, height: int, view, params, mask_row
     return out
 
 
+# a dg_sight_query as numpy sees it (dg_sight_host, dg_sight_device)
+SIGHT_QUERY_DTYPE = np.dtype([("frame", "<i4"), ("x0", "<f4"), ("y0", "<f4"), ("z0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("z1_lo", "<f4"), ("z1_hi", "<f4")])
+
+
+def _sight_queries(queries) -> np.ndarray:
+    q = np.ascontiguousarray(queries, dtype=SIGHT_QUERY_DTYPE).reshape(-1)
+    return q
+
+
+def _sight_mobj_args(scene, views, mobj_height):
+    n_mobjs = lib().dg_scene_mobj_count(scene._h)
+    heights = np.ascontiguousarray(mobj_height, dtype=np.float32).reshape(-1)
+    if heights.size != n_mobjs:
+        raise ValueError("mobj_height must hold one height per map object")
+    words = _check(lib().dg_sight_words(scene._h))
+    return heights, np.empty((len(views), words), dtype=np.uint32)
+
+
+def sight_host(scene, queries, sectors=None, n_frames: int = 1) -> np.ndarray:
+    """dg_sight_host: one byte per query (SIGHT_QUERY_DTYPE array), 1 visible, 0 not; sectors: make_view_sectors' array of n_frames
+    elements, or None (every frame has the scene's heights)."""
+    q = _sight_queries(queries)
+    out = np.empty(q.size, dtype=np.uint8)
+    _check(lib().dg_sight_host(scene._h, sectors, n_frames, q.ctypes.data_as(_P), q.size, out.ctypes.data_as(_P)))
+    return out
+
+
+def sight_mobjs_host(scene, views, eye_height: float, mobj_height, poses=None, sectors=None) -> np.ndarray:
+    """dg_sight_mobjs_host: which map objects every view sees, a (len(views), dg_sight_words) uint32 array of bit rows.  mobj_height: one
+    float per map object (<= 0 leaves it out); poses / sectors: make_view_poses' / make_view_sectors' arrays, or None."""
+    heights, out = _sight_mobj_args(scene, views, mobj_height)
+    _check(lib().dg_sight_mobjs_host(scene._h, views, poses, sectors, len(views), eye_height, heights.ctypes.data_as(_P), out.ctypes.data_as(_P)))
+    return out
+
+
 def make_view_states(states):
     """states: one (lights, mobjs) pair per view; lights = [(sector, light_level), ...], mobjs = [(mobj, sprite_frame or -1, full_bright), ...].
     Returns (ctypes array of dg_view_state, keep-alive list)."""
@@ -971,6 +1013,10 @@ class Scene:
         out = np.zeros(max(n, 0), dtype=MOBJ_PLACED_DTYPE)
         _check(lib().dg_scene_mobj_poses(self._h, out.ctypes.data_as(_P), n))
         return out
+
+    def bsp_depth(self) -> int:
+        """dg_scene_bsp_depth: the nodes on the longest way from the BSP's root to a leaf."""
+        return _check(lib().dg_scene_bsp_depth(self._h))
 
     def map_lines(self, W: int, H: int, view=None) -> np.ndarray:
         """dg_map_lines: the lines of one 2-D map frame in draw order, (n, 5) int64 rows [x0, y0, x1, y1, rgb] (rgb = r | g<<8 | b<<16);
@@ -1269,6 +1315,25 @@ class Context:
         a, b = ctypes.c_float(), ctypes.c_float()
         _check(lib().dg_ctx_seen_kernel_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
         return {"lines_ms": a.value, "accumulate_ms": b.value}
+
+    def sight(self, queries, sectors=None, n_frames: int = 1) -> np.ndarray:
+        """dg_sight_device: sight_host() on the GPU, bit for bit (synchronous; touches no slot)."""
+        q = _sight_queries(queries)
+        out = np.empty(q.size, dtype=np.uint8)
+        _check(lib().dg_sight_device(self._h, sectors, n_frames, q.ctypes.data_as(_P), q.size, out.ctypes.data_as(_P)))
+        return out
+
+    def sight_mobjs(self, views, eye_height: float, mobj_height, poses=None, sectors=None) -> np.ndarray:
+        """dg_sight_mobjs_device: sight_mobjs_host() on the GPU, bit for bit (synchronous; touches no slot)."""
+        heights, out = _sight_mobj_args(self._scene, views, mobj_height)
+        _check(lib().dg_sight_mobjs_device(self._h, views, poses, sectors, len(views), eye_height, heights.ctypes.data_as(_P), out.ctypes.data_as(_P)))
+        return out
+
+    def sight_kernel_ms(self) -> dict:
+        """dg_ctx_sight_kernel_ms: GPU time (ms) of the last sight() / sight_mobjs() call's kernels (rows_ms 0: no frame had entries)."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        _check(lib().dg_ctx_sight_kernel_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return {"rows_ms": a.value, "sight_ms": b.value}
 
     def render_state(self, views, states) -> np.ndarray:
         """render() with one game-state snapshot per view (make_view_states)."""

@@ -2,8 +2,8 @@
 // runs on a stream of the ctx's own, created by its first use, and returns when its work is done.  The box downscale of frames in device
 // memory (dg_reduce_device), the reduced depth and label planes (dg_reduce_planes_device), the observation tensors
 // (dg_observe_device), the screen pictures over colour frames (dg_overlay_device, dg_slot_overlay — which draws on a slot's frames once
-// they are final), the linedefs seen in label planes (dg_seen_lines_device, dg_slot_seen_lines — the one call here that reads a slot, once its submission is final), the floor heights of
-// recorded walks (dg_ctx_locate_walks), and the getters of their kernels' times.  The readbacks of a slot's frames and planes:
+// they are final), the linedefs seen in label planes (dg_seen_lines_device, dg_slot_seen_lines — the one call here that reads a slot, once its submission is final), the
+// line-of-sight queries (dg_sight_device, dg_sight_mobjs_device), the floor heights of recorded walks (dg_ctx_locate_walks), and the getters of their kernels' times.  The readbacks of a slot's frames and planes:
 // api_readback.cpp.  Slot, dg_ctx and the slot helpers: context.hpp.
 #include <hip/hip_runtime_api.h>
 
@@ -18,6 +18,8 @@
 #include "overlay_kernels.hpp"
 #include "plane_reduce_kernels.hpp"
 #include "reduce_kernels.hpp"
+#include "sight_host.hpp"
+#include "sight_kernels.hpp"
 #include "walk.hpp"
 #include "walk_kernels.hpp"
 
@@ -260,6 +262,171 @@ int dg_ctx_seen_kernel_ms(dg_ctx *c, float *lines_ms, float *accumulate_ms) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (lines_ms) HIP_TRY(c->seen.elapsed(lines_ms));
     if (accumulate_ms) { *accumulate_ms = 0.0f; if (c->seen_acc.measured) HIP_TRY(c->seen_acc.elapsed(accumulate_ms)); }
+    return DG_OK;
+}
+
+}  // extern "C"
+
+// What dg_sight_device and dg_sight_mobjs_device need of the ctx before they queue anything: a scene the kernels' stacks hold (its BSP at
+// most SIGHT_MAX_DEPTH deep, its children in 16 bits), the no-slot stream, and the scene's sight tables on the device.  Nothing is
+// launched and no interval is touched when the scene is refused.
+static int ensure_sight(dg_ctx *c) {
+    const Scene &sc = *c->scene;
+    dg_ctx::PerScene &ps = c->per_scene;
+    if (!ps.sight_depth) ps.sight_depth = sight_scene_depth(sc);
+    if (ps.sight_depth > SIGHT_MAX_DEPTH)
+        return set_err(DG_ERR_CAPACITY, "the scene's BSP is " + std::to_string(ps.sight_depth) + " nodes deep: the device sight calls take " + std::to_string(SIGHT_MAX_DEPTH) +
+                                            " at the most (dg_sight_host has no limit)");
+    if (sc.walk_nodes.size() > 32768u || sc.subsectors.size() > 32768u) return set_err(DG_ERR_CAPACITY, "the device sight calls take 32 768 nodes and subsectors at the most");
+    if (sc.subsectors.empty() || sc.sectors.empty()) return set_err(DG_ERR_INVALID, "sight queries: the scene has no subsectors");
+    HIP_TRY(side_stream(c->xstream));
+    if (!ps.sight_table) {
+        SightHostTables H;
+        sight_tables(sc, H);
+        TablePack t;
+        const size_t nodes = t.add(sc.walk_nodes), leaves = t.add(H.leaves), seg_line = t.add(H.seg_line), lines = t.add(H.lines);
+        const size_t heights = t.add(sc.fs_heights), mobjs = t.add(sc.fs_mobjs), leaf_sector = t.add(sc.walk_leaf_sector);
+        DevPtr<uint8_t> d_table;
+        const hipError_t e = t.upload(d_table);
+        if (e != hipSuccess) return set_err(DG_ERR_HIP, std::string("sight tables: ") + hipGetErrorString(e));
+        ps.sight_T = SightTables{t.at<WalkNode>(nodes), (uint32_t)sc.walk_nodes.size(), t.at<FloorLeaf>(leaves), (uint32_t)H.leaves.size(), t.at<uint32_t>(seg_line),
+                                 (uint32_t)H.seg_line.size(), t.at<SightLine>(lines), (uint32_t)H.lines.size(), t.at<FsHeights>(heights), (uint32_t)sc.sectors.size(), 1u};
+        ps.sight_mobjs = t.at<FsMobj>(mobjs);
+        ps.sight_leaf_sector = t.at<int32_t>(leaf_sector);
+        ps.sight_table = std::move(d_table);
+    }
+    return DG_OK;
+}
+
+// A call's block in device memory: the parts a caller take()s lie on 256-byte boundaries.
+static int sight_io(dg_ctx *c, size_t bytes) {
+    dg_ctx::PerScene &ps = c->per_scene;
+    if (bytes <= ps.sight_io_cap) return DG_OK;
+    ps.sight_io_cap = 0;
+    const size_t cap = (bytes + 65535) & ~(size_t)65535;
+    HIP_TRY(hip_alloc(ps.sight_io, cap));
+    ps.sight_io_cap = cap;
+    return DG_OK;
+}
+
+// The rows of a call whose frames have entries, queued on xs after the entries' copies: the height rows into the ctx's sight_rows (T
+// then reads them), the pose rows into its sight_poses (poses / pose_frames then name them).  d_he / d_pe: the entries in device
+// memory.  The ctx's sight_rows interval spans the kernels launched here.
+static hipError_t sight_queue_rows(dg_ctx *c, hipStream_t xs, int n_frames, const SectorEntry *d_he, size_t n_he, const PoseEntry *d_pe, size_t n_pe, SightTables &T,
+                                   const FsMobj *&poses, uint32_t &pose_frames) {
+    dg_ctx::PerScene &ps = c->per_scene;
+    hipError_t e = hipSuccess;
+    if (n_he) {
+        const SectorRowParams P{T.rows, d_he, ps.sight_rows.get(), T.n_sectors, (uint32_t)n_frames, (uint32_t)n_he};
+        e = launch_view_rows<HeightRows>(P, xs, c->sight_rows.t0.get(), n_pe ? nullptr : c->sight_rows.t1.get());
+        T.rows = ps.sight_rows.get();
+        T.row_frames = (uint32_t)n_frames;
+    }
+    if (e == hipSuccess && n_pe) {
+        const PoseParams P{ps.sight_mobjs, d_pe, ps.sight_poses.get(), (uint32_t)c->scene->mobjs.size(), (uint32_t)n_frames, (uint32_t)n_pe,
+                           PoseCtx{T.nodes, ps.sight_leaf_sector, (int32_t)T.n_nodes - 1}};
+        e = launch_view_rows<PoseRows>(P, xs, n_he ? nullptr : c->sight_rows.t0.get(), c->sight_rows.t1.get());
+        poses = ps.sight_poses.get();
+        pose_frames = (uint32_t)n_frames;
+    }
+    return e;
+}
+
+extern "C" {
+
+int dg_sight_device(dg_ctx *c, const dg_view_sectors *sectors, int n_frames, const dg_sight_query *q, int n, uint8_t *visible_out) {
+    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    const Scene &sc = *c->scene;
+    std::string err;
+    int rc = sight_check_queries(&sc, n_frames, q, n, visible_out, err);
+    if (rc) return set_err(rc, err);
+    if (n_frames > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "n_frames exceeds max_batch");
+    if (n == 0) return DG_OK;
+    std::vector<SectorEntry> he;
+    if ((rc = sight_sector_entries(sc, sectors, n_frames, c->arenas[0]->heights, he, err))) return set_err(rc, err);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if ((rc = ensure_sight(c))) return rc;
+    dg_ctx::PerScene &ps = c->per_scene;
+    SlabCursor cur;
+    const size_t at_he = cur.take(he.size() * sizeof(SectorEntry)), at_q = cur.take((size_t)n * sizeof(dg_sight_query)), at_out = cur.take((size_t)n);
+    if ((rc = sight_io(c, cur.next))) return rc;
+    if (!he.empty() && !ps.sight_rows) HIP_TRY(hip_alloc(ps.sight_rows, (size_t)c->cfg.max_batch * sc.sectors.size() * sizeof(FsHeights)));
+    HIP_TRY(c->sight.begin());
+    c->sight_rows.measured = false;
+    if (!he.empty()) HIP_TRY(c->sight_rows.begin());
+    const hipStream_t xs = c->xstream.get();
+    uint8_t *const d = ps.sight_io.get();
+    SightQueryParams P{ps.sight_T, reinterpret_cast<const dg_sight_query *>(d + at_q), d + at_out, (uint32_t)n};
+    const FsMobj *no_poses = nullptr;
+    uint32_t no_pose_frames = 1;
+    hipError_t e = hipMemcpyAsync(d + at_q, q, (size_t)n * sizeof(dg_sight_query), hipMemcpyHostToDevice, xs);
+    if (e == hipSuccess && !he.empty()) e = hipMemcpyAsync(d + at_he, he.data(), he.size() * sizeof(SectorEntry), hipMemcpyHostToDevice, xs);
+    if (e == hipSuccess) e = sight_queue_rows(c, xs, n_frames, reinterpret_cast<const SectorEntry *>(d + at_he), he.size(), nullptr, 0, P.T, no_poses, no_pose_frames);
+    if (e == hipSuccess) e = launch_sight_queries(P, xs, c->sight.t0.get(), c->sight.t1.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(visible_out, d + at_out, (size_t)n, hipMemcpyDeviceToHost, xs);
+    if ((rc = finish(xs, e, "dg_sight_device"))) return rc;           // before the entries go and the caller reads, whatever was queued has run
+    c->sight.end();
+    if (!he.empty()) c->sight_rows.end();
+    return DG_OK;
+}
+
+int dg_sight_mobjs_device(dg_ctx *c, const dg_view *views, const dg_view_poses *poses, const dg_view_sectors *sectors, int n, float eye_height,
+                          const float *mobj_height, uint32_t *visible_out) {
+    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
+    if (!c->scene) return set_err(DG_ERR_INVALID, "no scene uploaded (dg_upload_scene)");
+    const Scene &sc = *c->scene;
+    std::string err;
+    int rc = sight_check_mobjs(&sc, views, n, mobj_height, visible_out, err);
+    if (rc) return set_err(rc, err);
+    if (n > c->cfg.max_batch) return set_err(DG_ERR_CAPACITY, "n exceeds max_batch");
+    if (n == 0) return DG_OK;
+    std::vector<SectorEntry> he;
+    std::vector<PoseEntry> pe;
+    if ((rc = sight_sector_entries(sc, sectors, n, c->arenas[0]->heights, he, err))) return set_err(rc, err);
+    if ((rc = sight_pose_entries(sc, poses, n, c->arenas[0]->poses, pe, err))) return set_err(rc, err);
+    const size_t M = sc.mobjs.size(), words = sight_words(sc);
+    if (M == 0) return DG_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if ((rc = ensure_sight(c))) return rc;
+    dg_ctx::PerScene &ps = c->per_scene;
+    std::vector<SightView> sv;
+    sight_views(views, n, eye_height, sv);
+    SlabCursor cur;
+    const size_t at_he = cur.take(he.size() * sizeof(SectorEntry)), at_pe = cur.take(pe.size() * sizeof(PoseEntry)), at_v = cur.take(sv.size() * sizeof(SightView));
+    const size_t at_h = cur.take(M * sizeof(float)), at_out = cur.take((size_t)n * words * sizeof(uint32_t));
+    if ((rc = sight_io(c, cur.next))) return rc;
+    if (!he.empty() && !ps.sight_rows) HIP_TRY(hip_alloc(ps.sight_rows, (size_t)c->cfg.max_batch * sc.sectors.size() * sizeof(FsHeights)));
+    if (!pe.empty() && !ps.sight_poses) HIP_TRY(hip_alloc(ps.sight_poses, (size_t)c->cfg.max_batch * M * sizeof(FsMobj)));
+    const bool rows = !he.empty() || !pe.empty();
+    HIP_TRY(c->sight.begin());
+    c->sight_rows.measured = false;
+    if (rows) HIP_TRY(c->sight_rows.begin());
+    const hipStream_t xs = c->xstream.get();
+    uint8_t *const d = ps.sight_io.get();
+    SightMobjParams P{ps.sight_T, reinterpret_cast<const SightView *>(d + at_v), ps.sight_mobjs, reinterpret_cast<const float *>(d + at_h),
+                      reinterpret_cast<uint32_t *>(d + at_out), (uint32_t)n, (uint32_t)M, (uint32_t)words, 1u};
+    hipError_t e = hipMemcpyAsync(d + at_v, sv.data(), sv.size() * sizeof(SightView), hipMemcpyHostToDevice, xs);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + at_h, mobj_height, M * sizeof(float), hipMemcpyHostToDevice, xs);
+    if (e == hipSuccess && !he.empty()) e = hipMemcpyAsync(d + at_he, he.data(), he.size() * sizeof(SectorEntry), hipMemcpyHostToDevice, xs);
+    if (e == hipSuccess && !pe.empty()) e = hipMemcpyAsync(d + at_pe, pe.data(), pe.size() * sizeof(PoseEntry), hipMemcpyHostToDevice, xs);
+    if (e == hipSuccess)
+        e = sight_queue_rows(c, xs, n, reinterpret_cast<const SectorEntry *>(d + at_he), he.size(), reinterpret_cast<const PoseEntry *>(d + at_pe), pe.size(), P.T, P.poses,
+                             P.pose_frames);
+    if (e == hipSuccess) e = launch_sight_mobjs(P, xs, c->sight.t0.get(), c->sight.t1.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(visible_out, d + at_out, (size_t)n * words * sizeof(uint32_t), hipMemcpyDeviceToHost, xs);
+    if ((rc = finish(xs, e, "dg_sight_mobjs_device"))) return rc;     // before the staged inputs go and the caller reads, whatever was queued has run
+    c->sight.end();
+    if (rows) c->sight_rows.end();
+    return DG_OK;
+}
+
+int dg_ctx_sight_kernel_ms(dg_ctx *c, float *rows_ms, float *sight_ms) {
+    if (!c) return set_err(DG_ERR_INVALID, "null ctx");
+    if (!c->sight.measured) return set_err(DG_ERR_INVALID, "no dg_sight_device or dg_sight_mobjs_device call has launched yet");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (sight_ms) HIP_TRY(c->sight.elapsed(sight_ms));
+    if (rows_ms) { *rows_ms = 0.0f; if (c->sight_rows.measured) HIP_TRY(c->sight_rows.elapsed(rows_ms)); }
     return DG_OK;
 }
 

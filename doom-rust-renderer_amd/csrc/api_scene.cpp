@@ -4,7 +4,7 @@
 // (dg_observed_size, dg_observe_host), the screen pictures (dg_scene_use_picture, dg_overlay_host), the depth planes, the label planes and boxes and a bundle's parts of caller-built lists on the host (dg_depth_lists_host, dg_label_lists_host,
 // dg_bundle_lists_host: one rule, plane_lists_host), a bundle's slab layout (dg_bundle_layout), and the explored-map frames' host rules
 // (dg_seen_words, dg_seen_lines_host, dg_seen_accumulate_host, dg_explored_map_host) and the player-centred map frames' (dg_ego_map_lines,
-// dg_ego_map_host).  Everything that takes a dg_ctx: context.cpp (a slot's submissions), api_readback.cpp (what reads a slot) and
+// dg_ego_map_host), and the line-of-sight queries' host twin (dg_sight_host, dg_sight_mobjs_host).  Everything that takes a dg_ctx: context.cpp (a slot's submissions), api_readback.cpp (what reads a slot) and
 // api_device.cpp (the calls on a stream of the ctx's own).
 #include <algorithm>
 #include <cstring>
@@ -22,6 +22,7 @@
 #include "plane_core.h"
 #include "plane_reduce_core.h"
 #include "reduce_core.h"
+#include "sight_host.hpp"
 #include "slab_layout.h"
 #include "walk.hpp"
 
@@ -754,6 +755,77 @@ int dg_floor_map_things_host(const dg_scene *s, int width, int height, const dg_
     std::vector<uint8_t> covered;
     thing_draw_lines_host(lines, width, height, rgb24_out, &covered);
     floor_frame_fill(sc, F, width, height, v, *params, mask_row, rgb24_out, [&](size_t at) { return covered[at] != 0; });
+    return DG_OK;
+}
+
+int dg_scene_bsp_depth(const dg_scene *s) {
+    if (!s) return set_err(DG_ERR_INVALID, "null scene");
+    return (int)sight_scene_depth(*s->sc);
+}
+
+int dg_sight_words(const dg_scene *s) {
+    if (!s) return set_err(DG_ERR_INVALID, "null scene");
+    return (int)sight_words(*s->sc);
+}
+
+// The host twin of dg_sight_queries: sight_core.h's traversal, one query after the other, on a stack as deep as the scene is.
+int dg_sight_host(const dg_scene *s, const dg_view_sectors *sectors, int n_frames, const dg_sight_query *q, int n, uint8_t *visible_out) {
+    std::string err;
+    int rc = sight_check_queries(s ? s->sc : nullptr, n_frames, q, n, visible_out, err);
+    if (rc) return set_err(rc, err);
+    if (n == 0) return DG_OK;
+    const Scene &sc = *s->sc;
+    LatestHeights latest;
+    std::vector<SectorEntry> entries;
+    if ((rc = sight_sector_entries(sc, sectors, n_frames, latest, entries, err))) return set_err(rc, err);
+    SightHostTables H;
+    sight_tables(sc, H);
+    std::vector<FsHeights> rows;
+    const uint32_t row_frames = sight_height_rows(sc, entries, n_frames, rows);
+    const SightTables T = sight_tables_host(sc, H, rows.data(), row_frames);
+    SightHostStack stack;
+    for (int i = 0; i < n; i++) {
+        stack.v.clear();
+        visible_out[i] = sight_query(T, q[i], stack);
+    }
+    return DG_OK;
+}
+
+// The host twin of dg_sight_mobjs: every (view, map object) pair's query through the same traversal, its bit into the view's row.
+int dg_sight_mobjs_host(const dg_scene *s, const dg_view *views, const dg_view_poses *poses, const dg_view_sectors *sectors, int n, float eye_height,
+                        const float *mobj_height, uint32_t *visible_out) {
+    std::string err;
+    int rc = sight_check_mobjs(s ? s->sc : nullptr, views, n, mobj_height, visible_out, err);
+    if (rc) return set_err(rc, err);
+    if (n == 0) return DG_OK;
+    const Scene &sc = *s->sc;
+    LatestHeights latest_h;
+    LatestPoses latest_p;
+    std::vector<SectorEntry> h_entries;
+    std::vector<PoseEntry> p_entries;
+    if ((rc = sight_sector_entries(sc, sectors, n, latest_h, h_entries, err))) return set_err(rc, err);
+    if ((rc = sight_pose_entries(sc, poses, n, latest_p, p_entries, err))) return set_err(rc, err);
+    const size_t M = sc.mobjs.size(), words = sight_words(sc);
+    if (M == 0) return DG_OK;
+    SightHostTables H;
+    sight_tables(sc, H);
+    std::vector<FsHeights> rows;
+    std::vector<FsMobj> pose_rows;
+    const uint32_t row_frames = sight_height_rows(sc, h_entries, n, rows), pose_frames = sight_pose_rows(sc, p_entries, n, pose_rows);
+    const SightTables T = sight_tables_host(sc, H, rows.data(), row_frames);
+    std::vector<SightView> sv;
+    sight_views(views, n, eye_height, sv);
+    SightHostStack stack;
+    std::fill(visible_out, visible_out + (size_t)n * words, 0u);
+    for (int f = 0; f < n; f++) {
+        const FsMobj *const pr = pose_rows.data() + (pose_frames > 1 ? (size_t)f * M : (size_t)0);
+        for (size_t m = 0; m < M; m++) {
+            dg_sight_query q;
+            if (!sight_mobj_query(T, f, sv[(size_t)f], pr[m], mobj_height[m], q)) continue;
+            stack.v.clear();
+            if (sight_query(T, q, stack)) visible_out[(size_t)f * words + (m >> 5)] |= 1u << (m & 31u);
+        }
+    }
     return DG_OK;
 }
 

@@ -26,6 +26,7 @@
 #include "pool.hpp"
 #include "reduce_core.h"
 #include "scene.hpp"
+#include "sight_core.h"
 #include "slab_layout.h"
 #include "view_rows_kernels.hpp"
 #include "walk_core.h"
@@ -346,6 +347,18 @@ struct dg_ctx {
         DevPtr<uint8_t> walk_tables;        // dg_ctx_locate_walks: the node and leaf tables (walk_core.h)
         const WalkNode *walk_nodes = nullptr;
         const WalkLeaf *walk_leaves = nullptr;
+        // dg_sight_device / dg_sight_mobjs_device: the scene's sight tables, its map objects, leaf sectors and one height
+        // row in one allocation (ensure_sight); the rows [max_batch][sectors] and [max_batch][map objects] of a call with entries; and
+        // one block for a call's entries, inputs and results, grown when a call needs more
+        DevPtr<uint8_t> sight_table;
+        SightTables sight_T{};              // ... as the kernels read them, over the scene's one row
+        const FsMobj *sight_mobjs = nullptr;
+        const int32_t *sight_leaf_sector = nullptr;
+        uint32_t sight_depth = 0;           // the BSP's depth (sight_core.h sight_depth)
+        DevPtr<FsHeights> sight_rows;
+        DevPtr<FsMobj> sight_poses;
+        DevPtr<uint8_t> sight_io;
+        size_t sight_io_cap = 0;
         void drop() { *this = PerScene{}; }
     } per_scene;
     Stream wstream;                     // dg_ctx_locate_walks: a stream of its own, created by the first call — the slots' streams and the kernel stream are not touched
@@ -355,6 +368,7 @@ struct dg_ctx {
     TimedInterval plane_reduce;         // dg_reduce_planes_device: the same stream, events of its own
     TimedInterval observe;              // dg_observe_device: likewise
     TimedInterval seen, seen_acc;       // dg_seen_lines_device / dg_slot_seen_lines: the events of the last call's kernels, on xstream
+    TimedInterval sight_rows, sight;    // dg_sight_device / dg_sight_mobjs_device: the last call's row kernels (unmeasured without entries) and its sight kernel, on xstream
     // dg_overlay_device / dg_slot_overlay: the scene's screen pictures as of dg_upload_scene (a handle beyond them was loaded since), the
     // device scratch a call stages its item and rectangle records in (grown when a call needs more), and the last call's kernel, on xstream
     std::vector<OvlPicture> pictures;

@@ -1051,12 +1051,52 @@ int dg_submit_floor_map_views_things(dg_ctx *ctx, int slot, const dg_view *views
 int dg_render_floor_map_views_things(dg_ctx *ctx, const dg_view *views, int n, const dg_ego_map *params, const uint32_t *mask,
                                      const dg_view_state *states, const dg_view_surfaces *surfaces, const dg_view_poses *poses, uint8_t *rgb24_out);
 
+/* ---- line-of-sight queries (vanilla: P_CheckSight) ---------------------------------------- */
+/* Is there a clear line from here to there?  A query is the line from (x0, y0) at height z0 to (x1, y1), whose target spans the heights
+ * [z1_lo, z1_hi]; sector heights are those of frame `frame`: the scene's, with that frame's dg_view_sectors entries on top (a door
+ * that is shut in one frame blocks there alone).  The rule, stated in full in DESIGN.md section 8v and in csrc/sight_core.h:
+ *   the line visits the BSP leaves on its way (at a node: the child on the start's side always, the other one unless the end lies
+ *   strictly on the start's side); every linedef of a visited leaf that the line crosses (the signs of the four cross products)
+ *   blocks it when it is one-sided or its opening is closed (max of the floors >= min of the ceilings), and otherwise narrows the
+ *   slope range [lo, hi], which starts as [z1_lo - z0, z1_hi - z0], by its lower and upper edge at the crossing;
+ *   visible (1) iff nothing blocked and hi > lo at the end, else 0.
+ * IEEE f32 throughout; the result does not depend on the visiting order.  A query with a float that is not finite or beyond 65536 in
+ * magnitude is out of contract: 0.  All pointers are host pointers; sectors may be NULL (every frame has the scene's heights), else it
+ * holds n_frames elements; n == 0: DG_OK, nothing done.  DG_ERR_INVALID: a NULL required argument, n or n_frames negative, a q[i].frame
+ * outside [0, n_frames), a sector entry out of range or a height outside int16 (as dg_submit_views_sectors), a NULL entry array with
+ * n > 0.  DG_ERR_CAPACITY: n above 1 << 20. */
+typedef struct dg_sight_query { int32_t frame; float x0, y0, z0, x1, y1, z1_lo, z1_hi; } dg_sight_query;
+int dg_sight_host(const dg_scene *s, const dg_view_sectors *sectors, int n_frames, const dg_sight_query *q, int n, uint8_t *visible_out);
+/* The same on the GPU (dg_sight_queries: one lane per query), bit for bit: on the ctx's stream that belongs to no slot, synchronous,
+ * touching no slot.  Needs an uploaded scene (DG_ERR_INVALID without one); its sight tables are uploaded by the first call after
+ * dg_upload_scene, the scratch buffers are the ctx's, allocated at first use.  DG_ERR_CAPACITY, before anything is launched: n_frames
+ * above max_batch, or a scene whose BSP is deeper than 64 nodes (dg_scene_bsp_depth) — the host call has no such limit. */
+int dg_sight_device(dg_ctx *ctx, const dg_view_sectors *sectors, int n_frames, const dg_sight_query *q, int n, uint8_t *visible_out);
+/* Which map objects does each of n views see?  One query per (view, map object m): from the view's (x, y) at z0 = view.floor_height +
+ * eye_height to the object's (x, y) in that view (its dg_view_poses entry, else as loaded), the target from the floor of the object's
+ * sector in that view's heights up to mobj_height[m] above it.  An object whose sector is none, or whose mobj_height is not positive
+ * (the caller's way to leave it out), is not visible.  visible_out[n][dg_sight_words]: bit m & 31 of word m >> 5 of row i; the tail
+ * bits of a row are 0.  poses and sectors may be NULL, else n elements each.  DG_ERR_INVALID: a NULL required argument, n negative, an
+ * entry out of range (as dg_submit_views_sectors), a NULL entry array with n > 0.  The device call (dg_sight_mobjs: one lane per
+ * pair, a wavefront per frame and 64 objects) as dg_sight_device, n bounded by max_batch. */
+int dg_sight_words(const dg_scene *s);                 /* ceil(map objects / 32); DG_ERR_INVALID: a NULL scene */
+int dg_sight_mobjs_host(const dg_scene *s, const dg_view *views, const dg_view_poses *poses, const dg_view_sectors *sectors, int n, float eye_height,
+                        const float *mobj_height, uint32_t *visible_out);
+int dg_sight_mobjs_device(dg_ctx *ctx, const dg_view *views, const dg_view_poses *poses, const dg_view_sectors *sectors, int n, float eye_height,
+                          const float *mobj_height, uint32_t *visible_out);
+/* GPU time of the last dg_sight_device / dg_sight_mobjs_device call's kernels in milliseconds, from events attached to the dispatches:
+ * the row kernels (dg_sector_row_* and dg_mobj_pose_*; 0 when no frame had entries) and the sight kernel.  Either output may be NULL.
+ * DG_ERR_INVALID: a NULL ctx, no such call that launched yet. */
+int dg_ctx_sight_kernel_ms(dg_ctx *ctx, float *rows_ms, float *sight_ms);
+/* The nodes on the longest way from the BSP's root to a leaf (>= 1); DG_ERR_INVALID: a NULL scene. */
+int dg_scene_bsp_depth(const dg_scene *s);
+
 /* ---- misc ----------------------------------------------------------------------------------------------------- */
 const char *dg_last_error(void); /* thread-local message of the last failing call */
 /* "doomgpu <release> (gfx950; ABI <n>)".  The ABI number changes whenever a struct in this header changes size or a function its
  * arguments: ABI 3 (round 3) dropped dg_timing.strips_ms and the third argument of dg_ctx_fallbacks; ABI 4 changes no signature
  * (it marks the library in which dg_version started to carry the number); functions added since (the map view, the effects, the walks,
- * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors, the surfaces, the screen pictures, the floor-textured map frames, the map-object markers) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
+ * the reduced readbacks, the depth frames, the label frames, the bundles, the reduced planes, the explored-map frames, the player-centred map frames, the map-object poses, the sector heights, the observation tensors, the surfaces, the screen pictures, the floor-textured map frames, the map-object markers, the sight queries) changed no struct and no signature and kept it.  A caller built against another ABI must not call on. */
 const char *dg_version(void);
 
 /* Timing of the last dg_replay_slot / submit on a slot (ms), from HIP events attached to the kernel dispatches themselves on the ctx's
